@@ -26,7 +26,8 @@ N > 1 (one process per GPU, launched by torch.distributed.run, RCCL): the 8-GPU 
 metric value = algorithmic bytes of the whole job (every stored entry once + block
 metadata + x once + y once) * K / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0 with the `roofline` and `cpu_baseline` objects.  --dump-outputs DIR also writes the y of
+the last timed step to DIR (dump_outputs): the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -46,7 +47,43 @@ MFMA_FILE = os.path.join(ROOT, "profiles", "r05_c4_mfma.json")
 C5N1_FILE = os.path.join(ROOT, "profiles", "r05_c5_n1.json")  # the N > 1 workload on ONE GPU (tools/profile_round.sh)
 ORACLE_SAMPLES = 48  # sampled block rows per rank of the full-size oracle check of the partitioned workloads
 SETUP_STEPS = 30    # N > 1 / --workload c5: untimed steps of a freshly built operator before the W warm-up steps (config.setup_steps)
-MIN_TIMED_S = 5e-3  # a timed region shorter than this is repeated (config.replays) so that host synchronisation stays below 1 %
+MIN_TIMED_S = 5e-3  # a timed region shorter than this is flagged in config.note: host synchronisation is a visible part of it
+DUMP_BYTES = 60_000_000  # --dump-outputs: data of all files of all ranks together (64 MB at most with the .npy headers)
+
+
+def dump_outputs(dirname, arrays, share=1):
+    """--dump-outputs: each named array (a numpy array of the last timed step) to DIR/<name>.npy in float32 or float64
+    (complex: real and imaginary part as the two columns of an n x 2 array).  An array larger than its part of
+    DUMP_BYTES (split over the arrays and over the `share` ranks that write) is written as a fixed sample: the rows at
+    the sorted indices of a draw with seed 0, which go to DIR/<name>_index.npy (0-based, float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // (len(arrays) * share)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        ftype = np.float32 if a.real.dtype.itemsize <= 4 else np.float64
+        a = (np.stack([a.real, a.imag], axis=-1) if a.dtype.kind == "c" else a).astype(ftype)
+        if a.nbytes > budget:
+            k = budget // (a.nbytes // len(a) + 8)
+            idx = np.sort(np.random.default_rng(0).choice(len(a), k, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def native_oracle():
+    """oracle/bsm_oracle.c built -O3 -march=native for the CPU baseline (on the machine it is timed on), by the oracle's
+    own Makefile in a temporary copy of its sources: the tree the benchmark runs from may be read-only"""
+    import ctypes as C
+    import shutil
+    import subprocess
+    import tempfile
+    from oracle.oracle import Oracle
+    with tempfile.TemporaryDirectory(prefix="bsm_oracle_native_") as d:
+        for f in ("Makefile", "bsm_oracle.c", "bsm_oracle_impl.h"):
+            shutil.copy(os.path.join(ROOT, "oracle", f), d)
+        subprocess.check_call(["make", "-s", "-C", d, "_native/libbsm_oracle_native.so"], stdout=sys.stderr)
+        return Oracle(C.CDLL(os.path.join(d, "_native", "libbsm_oracle_native.so")))  # (stays mapped once loaded)
 
 
 def read_json(path):
@@ -186,6 +223,19 @@ class StreamFloor:
                                      self.scratch.numel() * 8, hop, C.c_void_p(self.torch.cuda.current_stream().cuda_stream))
         if rc:
             raise RuntimeError("bsm_bench_stream failed")
+
+
+def time_k_steps(k_steps, barrier, torch):
+    """The timed region of the N = 1 / C2 line: ONE call of k_steps() -- the K timed steps, no more -- between two
+    barriers.  -> (wall seconds, HIP-event seconds on the stream the kernels are launched on); ms_per_step = wall / K."""
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    barrier()
+    t0 = time.perf_counter()
+    ev0.record()
+    k_steps()
+    ev1.record()
+    barrier()
+    return time.perf_counter() - t0, ev0.elapsed_time(ev1) * 1e-3
 
 
 def cold_median(fn, flush, reps, torch):
@@ -400,10 +450,15 @@ def main():
                     "interior launch (distributed.RowPartitioned(loopback=...)): the only way a one-GPU box executes RCCL")
     ap.add_argument("--no-oracle-check", action="store_true", help="--workload c5 / N > 1: skip the sampled-row oracle check of the last timed step")
     ap.add_argument("--no-anchor", action="store_true", help="N > 1: do not let rank 0 measure the same workload alone afterwards (n1_same_workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the y of the last timed step to DIR/y.npy (N > 1: every rank its own rows "
+                         "to DIR/y_rank<r>.npy); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: the parallel entry is INSIDE the call, like the reference's
@@ -710,7 +765,7 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
             osamp_max = None
         return dict(oracle_sampled=osamp_max, desc=desc, elapsed=elapsed, total_bytes=total, kdur=kmax, rank_alg=rank_bytes + 2 * n * es // world,
                     setup_s=t_setup, parity=pmax, n=n, own=own, overlap=overlap,
-                    exchange_us=(elapsed / steps - kmax) * 1e6)
+                    exchange_us=(elapsed / steps - kmax) * 1e6, y=y_step)
 
     def run_checked(share, steps, warmup, tol):
         r = run(share, steps, warmup, not args.no_overlap)
@@ -726,6 +781,8 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
     steps, warmup = args.steps, args.warmup
     tol = 1e-12
     r5 = run_checked(c5_share, steps, warmup, tol)
+    if args.dump_outputs:  # the y rows this rank holds after the last timed C5 step (loopback: all of them)
+        dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: r5["y"].cpu().numpy()}, world)
     value = r5["total_bytes"] * steps / r5["elapsed"] / 1e9
     extra = {}
     if not args.no_extra:
@@ -809,7 +866,7 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
                 try:
                     torch.cuda.empty_cache()
                     a1 = argparse.Namespace(**vars(args))
-                    a1.no_extra, a1.no_overlap, a1.note, a1.loopback, a1.no_anchor = True, False, None, False, True
+                    a1.no_extra, a1.no_overlap, a1.note, a1.loopback, a1.no_anchor, a1.dump_outputs = True, False, None, False, True, None
                     a1.steps, a1.warmup = max(args.steps, 10), max(args.warmup, 3)
 
                     def bar1():
@@ -960,41 +1017,16 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
     if graph is None:
         launch = "eager"
 
-    # ---- timed region: the K steps, R times --------------------------------------------------------------
-    # K launches of a 10 us product are 0.2 ms at the driver's K = 20: the barrier + synchronize on both sides would be
-    # 8 % of that.  When K steps take less than MIN_TIMED_S the K-step region is repeated R times back to back (the
-    # same captured graph replayed R times) and ms_per_step = total / (K R); `steps` stays K, config.replays = R.
+    # ---- timed region: exactly the K steps, once ------------------------------------------------------------
     def k_steps():
         if graph is not None:
             graph.replay()
         else:
             for _ in range(args.steps):
                 plan()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    k_steps()  # (untimed: sizes R)
-    ev1.record()
-    torch.cuda.synchronize()
-    once = max(ev0.elapsed_time(ev1) * 1e-3, 1e-6)
-    replays = 1 if once >= MIN_TIMED_S else min(1000, int(MIN_TIMED_S / once) + 1)
-    if dist is not None:  # every rank repeats the same number of times
-        rr = torch.tensor([float(replays)], dtype=torch.float64, device=reduce_scalars.comm["dev"])
-        dist.all_reduce(rr, op=dist.ReduceOp.MAX, group=reduce_scalars.comm["group"])
-        replays = int(rr.item())
-    # three such regions, the median reported (a host hiccup during the enqueue of one region -- another process of the
-    # box waking up -- cost 25 % of the wall-clock figure in one of this round's runs while the device time did not move)
-    regions = []
-    for _ in range(3):
-        barrier()
-        t0 = time.perf_counter()
-        ev0.record()  # HIP events on the stream the kernels are launched on
-        for _ in range(replays):
-            k_steps()
-        ev1.record()
-        barrier()
-        regions.append(((time.perf_counter() - t0) / replays, ev0.elapsed_time(ev1) * 1e-3 / replays))
-    regions.sort()
-    elapsed, dev_elapsed = regions[1]
+    elapsed, dev_elapsed = time_k_steps(k_steps, barrier, torch)
+    if args.dump_outputs:  # what a caller of the timed path receives: y of the last timed step (this rank's rows)
+        dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: y[own[0] - 1:own[1]].cpu().numpy()}, world)
     elapsed, total_bytes = reduce_scalars(elapsed, alg_bytes)
     value = total_bytes * args.steps / elapsed / 1e9
 
@@ -1112,7 +1144,7 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
         # (BASELINE.json's 1-GPU configuration), a different operator in a different cache state
         try:
             a5 = argparse.Namespace(**vars(args))
-            a5.steps, a5.warmup, a5.no_extra, a5.scale, a5.no_overlap, a5.note = 20, 3, True, 1.0, False, None
+            a5.steps, a5.warmup, a5.no_extra, a5.scale, a5.no_overlap, a5.note, a5.dump_outputs = 20, 3, True, 1.0, False, None, None
             o5 = run_partitioned(a5, bsm, torch, None, np, 0, 1, barrier, reduce_scalars)
             extra["c5_n1"] = {"workload": o5["config"]["workload"], "value": o5["value"], "unit": "GB/s", "ms_per_step": o5["ms_per_step"],
                               "steps": 20, "exchange_us": o5["config"]["exchange_us"], "local_kernel_us_max": o5["config"]["local_kernel_us_max"],
@@ -1165,13 +1197,16 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
         "config": {"workload": "C2: VBCRS 100000x100000 per GPU, 5000 variable 8-64 fp64 blocks per GPU "
                                "(SplitMix64 seed 0xB5A2), mul!(y, A, x), x/y/A resident in HBM",
                    "global_rows": n, "blocks_per_gpu": len(prob["blocks"]),
-                   "alg_bytes_per_gpu": int(alg_bytes), "launch": launch, "replays": replays,
-                   "timed_region": "%d x (K = %d steps) between two barriers, three times; ms_per_step = median wall time / (K x replays); "
-                                   "wall times of the three regions in ms per step: %s" % (replays, args.steps, ", ".join("%.6f" % (r[0] / args.steps * 1e3) for r in regions)),
+                   "alg_bytes_per_gpu": int(alg_bytes), "launch": launch,
+                   "timed_region": "the K = %d steps once, between two barriers: %.4f ms wall time (slowest rank); ms_per_step = "
+                                   "that / K" % (args.steps, elapsed * 1e3),
                    "partition": "block rows, no data-path collective",
                    "frac_of_hbm_peak": round(value / (HBM_PEAK_GBPS * world), 4)},
         "roofline": roofline,
     }
+    if elapsed < MIN_TIMED_S:
+        out["config"]["note"] = ("the timed region is shorter than %g ms: the host synchronisation on both of its sides is a visible "
+                                 "part of ms_per_step (a larger --steps measures the product more closely)" % (MIN_TIMED_S * 1e3))
     if extra:
         out["extra"] = extra
 
@@ -1179,8 +1214,11 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
     # LAST: every GPU figure above is complete (and kept on stderr) before these ~15 s of host work start
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         print("[bench] GPU legs complete, CPU baseline next: " + json.dumps(out), file=sys.stderr, flush=True)
-        from oracle.oracle import load_oracle_native
-        orc = load_oracle_native()  # -O3 -march=native build of oracle/bsm_oracle.c, compiled on this box
+        try:
+            orc = native_oracle()
+        except Exception as e:  # pragma: no cover  (the CPU figures must never cost the headline line)
+            out["cpu_baseline"] = {"error": repr(e)}
+            return out
         perm, rowptr, colind, rowind = orc.vbcrs_build(prob["rowstart"], prob["colstart"])
         blocks = [prob["blocks"][p - 1] for p in perm]
         xh = prob["x"]

@@ -107,3 +107,82 @@ def test_fixture_coo_of_the_bench_is_the_reference_operator():
         ref = scipy_mul({k: ([b.astype(x.dtype) for b in v] if k in ("diagonals", "offdiagonals") else v) for k, v in fx.items()},
                         N, x, np.zeros(n0, x.dtype))
         assert relerr(got, ref) < 1e-13, tname
+
+
+def test_dump_outputs_writes_float_arrays_and_a_seeded_sample_under_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): float64 / float32 as they are, complex as n x 2 (real, imaginary), and an
+    array over its share of DUMP_BYTES as the same seeded sample in every run, with its row indices beside it"""
+    import bench
+    rng = np.random.default_rng(5)
+    y = rng.standard_normal(1000)
+    z = (rng.standard_normal(300) + 1j * rng.standard_normal(300)).astype(np.complex64)
+    bench.dump_outputs(str(tmp_path / "a"), {"y": y, "z": z})
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, y)
+    gz = np.load(tmp_path / "a" / "z.npy")
+    assert gz.dtype == np.float32 and gz.shape == (300, 2)
+    assert np.array_equal(gz[:, 0], z.real) and np.array_equal(gz[:, 1], z.imag)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["y.npy", "z.npy"]
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"y": y}, share=2)  # 2000 bytes for this rank's one array
+    s, idx = np.load(tmp_path / "b" / "y.npy"), np.load(tmp_path / "b" / "y_index.npy")
+    assert s.nbytes + idx.nbytes <= 2000 and len(s) == len(idx) > 100 and idx.dtype == np.float64
+    assert np.all(np.diff(idx) > 0) and np.array_equal(s, y[idx.astype(np.int64)])
+    assert np.array_equal(s, np.load(tmp_path / "c" / "y.npy")) and np.array_equal(idx, np.load(tmp_path / "c" / "y_index.npy"))
+
+
+def test_bench_refuses_a_step_count_below_one():
+    """--steps K is the number of timed steps that ms_per_step divides by: K = 0 is refused before anything runs"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_native_oracle_of_the_cpu_baseline_is_built_outside_the_tree(oracle):
+    """bench.native_oracle (the -O3 -march=native oracle the CPU baseline times) compiles in a temporary directory -- the
+    tree the benchmark runs from may be read-only -- and computes what the test oracle computes"""
+    import bench
+    import bsm_amd as bsm
+    from _common import N, oracle_mul, relerr
+    here = os.path.join(ROOT, "oracle")
+    before = sorted(os.listdir(here))
+    fast = bench.native_oracle()
+    assert sorted(os.listdir(here)) == before
+    prob = bsm.synthetic.config2(n=3000, nblocks=150)
+    y0 = np.zeros(prob["size"][0])
+    assert relerr(oracle_mul(fast, prob, N, prob["x"], y0), oracle_mul(oracle, prob, N, prob["x"], y0)) < 1e-13
+
+
+def test_the_timed_region_is_exactly_the_k_steps(monkeypatch):
+    """--steps K: the timed region of the N = 1 line (bench.time_k_steps) holds exactly the K steps, once, and
+    ms_per_step = its time / K -- a stub plan counts its calls between the two clock reads"""
+    import types
+    import pytest
+    import bench
+    clock, calls = {"t": 0.0, "reads": []}, []
+
+    def perf_counter():
+        clock["reads"].append(len(calls))
+        return clock["t"]
+
+    def plan():  # one step: 1 ms
+        calls.append(1)
+        clock["t"] += 1e-3
+
+    class Event:
+        def __init__(self, enable_timing):
+            self.at = None
+
+        def record(self):
+            self.at = clock["t"]
+
+        def elapsed_time(self, end):
+            return (end.at - self.at) * 1e3
+
+    monkeypatch.setattr(bench, "time", types.SimpleNamespace(perf_counter=perf_counter))
+    torch = types.SimpleNamespace(cuda=types.SimpleNamespace(Event=Event))
+    K = 37
+    wall, dev = bench.time_k_steps(lambda: [plan() for _ in range(K)], lambda: None, torch)
+    assert clock["reads"] == [0, K] and len(calls) == K
+    assert wall * 1e3 / K == pytest.approx(1.0) and dev == pytest.approx(wall)
