@@ -55,7 +55,7 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_blocksparse_create",
            "bsm_symmetric_create", "bsm_mul", "bsm_mul_multi", "bsm_mul_parts", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
            "bsm_color", "bsm_destroy", "bsm_last_error", "bsm_version",
-           "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy"]
+           "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -135,6 +135,9 @@ def lib():
     if hasattr(L, "bsm_mul_parts") or "BSM_LIB" not in os.environ:
         L.bsm_mul_parts.argtypes = [C.c_void_p, C.c_int, _PP, _PP, C.c_void_p, C.c_void_p, C.c_int, _PP]
         L.bsm_mul_parts.restype = C.c_int
+    if hasattr(L, "bsm_update_blocks") or "BSM_LIB" not in os.environ:
+        L.bsm_update_blocks.argtypes = [C.c_void_p, C.c_int64, _I64P, _PP, _I64P, C.c_int, C.c_void_p]
+        L.bsm_update_blocks.restype = C.c_int
     L.bsm_get_bookkeeping.argtypes = [C.c_void_p, C.c_int, _I64P, _I64P]
     L.bsm_get_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p, _I64P]
     L.bsm_color.argtypes = [C.c_int64, _PP, _I64P, C.c_int, _I64P, _I64P]

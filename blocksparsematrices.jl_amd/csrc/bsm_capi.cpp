@@ -3,6 +3,8 @@
 // packed image and forwards bsm_mul to the HIP launchers.  Never throws across the ABI.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -314,6 +316,7 @@ struct CreateCtx {
         if (!A) return;
         free_image(A->img);  // the handle's device is still current (guard outlives this body)
         free_image(A->img_t);
+        update_free(A->upd);
         dist_destroy(A);
         delete A;
     }
@@ -360,8 +363,7 @@ int build_error(const std::string &err) {
 
 // Second ordering: the transposed operator as a forward image (rows <-> columns, blocks read
 // transposed by the packer).  Built from the same caller arrays, before they are released.
-std::string build_transpose_image(bsm_matrix_s *A, const std::vector<BlockIn> &in, const bsm_options &o,
-                                  ValueSink *sink) {
+std::vector<BlockIn> transposed_blocks(const std::vector<BlockIn> &in) {
     std::vector<BlockIn> t(in.size());
     for (size_t b = 0; b < in.size(); b++) {
         const BlockIn &B = in[b];
@@ -377,11 +379,22 @@ std::string build_transpose_image(bsm_matrix_s *A, const std::vector<BlockIn> &i
         Tb.kind = KIND_PLAIN;
         Tb.trans = !B.trans;
     }
+    return t;
+}
+
+AnalysisOptions transpose_aopt(const bsm_options &o) {
     AnalysisOptions a;
     a.scheduler = 0;
     a.accumulate = o.accumulate;
-    a.sink = sink;
     a.blocks_on_device = (o.blocks_memspace == BSM_MEM_DEVICE);
+    return a;
+}
+
+std::string build_transpose_image(bsm_matrix_s *A, const std::vector<BlockIn> &in, const bsm_options &o,
+                                  ValueSink *sink) {
+    std::vector<BlockIn> t = transposed_blocks(in);
+    AnalysisOptions a = transpose_aopt(o);
+    a.sink = sink;
     std::string err = A->an_t.build(MT_BLOCKSPARSE, A->an.dtype, A->an.ncols, A->an.nrows, t, a);
     if (err.empty()) A->has_t = true;
     return err;
@@ -418,6 +431,443 @@ hipError_t device_pack(Analysis &an, void **d_values) {
     return e;
 }
 
+// ---- bsm_update_blocks ------------------------------------------------------------------------------------------
+void update_free(UpdateState &U) {
+    if (U.pending && U.ev_done) (void)hipEventSynchronize(U.ev_done);
+    for (RefillDevice &R : U.img)
+        for (void **p : {&R.d_chunks, &R.d_colpos, &R.d_segs, &R.d_items_all, &R.d_items_id}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+    for (void *p : {(void *)U.d_src, (void *)U.d_list, (void *)U.d_cap_src, (void *)U.d_cap_list})
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)U.h_src, (void *)U.h_list, (void *)U.h_cap_src, (void *)U.h_cap_list})
+        if (p) (void)hipHostFree(p);
+    if (U.ev_done) (void)hipEventDestroy(U.ev_done);
+    U = UpdateState();
+}
+
+// The block list of a create, kept for the refill plan: index lists copied (the caller may free its own), `data` = a
+// token naming the input block id -- the analysis with blocks_on_device never reads it, it only records it as the
+// source of every chunk of its pack plan.
+std::unique_ptr<UpdateInputs> keep_inputs(int mtype, int dtype, int64_t nrows, int64_t ncols, const std::vector<BlockIn> &in,
+                                          const std::vector<int64_t> &ids, int64_t nids, const AnalysisOptions &ao,
+                                          const AnalysisOptions *ao_t) {
+    std::unique_ptr<UpdateInputs> K(new UpdateInputs());
+    K->mtype = mtype;
+    K->dtype = dtype;
+    K->nrows = nrows;
+    K->ncols = ncols;
+    K->nids = nids;
+    K->ao = ao;
+    if (ao_t) K->ao_t = *ao_t;
+    K->in = in;
+    size_t nl = 0;
+    for (const BlockIn &B : in) nl += (B.ridx ? 1 : 0) + (B.cidx && B.cidx != B.ridx ? 1 : 0);
+    K->lists.reserve(nl);  // the BlockIn point into these vectors: no reallocation below
+    for (size_t b = 0; b < in.size(); b++) {
+        BlockIn &B = K->in[b];
+        const int64_t id = ids[b];
+        B.data = reinterpret_cast<const char *>((uintptr_t)(id + 1) * 16);
+        const bool same = B.cidx == B.ridx;
+        if (B.ridx) {
+            K->lists.emplace_back(B.ridx, B.ridx + B.m);
+            B.ridx = K->lists.back().data();
+        }
+        if (same) {
+            B.cidx = B.ridx;
+        } else if (B.cidx) {
+            K->lists.emplace_back(B.cidx, B.cidx + B.n);
+            B.cidx = K->lists.back().data();
+        }
+    }
+    return K;
+}
+
+namespace {
+// the pack plan of the same analysis run on the kept block list, by input block id
+std::string make_refill_plan(const UpdateInputs &inp, bool transposed, const Analysis &real, RefillPlan &R) {
+    Analysis probe;
+    AnalysisOptions ao = transposed ? inp.ao_t : inp.ao;
+    ao.sink = nullptr;
+    ao.blocks_on_device = true;
+    ao.skip_colors = true;
+    ao.meta_only = false;
+    std::string err = transposed ? probe.build(MT_BLOCKSPARSE, inp.dtype, inp.ncols, inp.nrows, transposed_blocks(inp.in), ao)
+                                 : probe.build(inp.mtype, inp.dtype, inp.nrows, inp.ncols, inp.in, ao);
+    if (!err.empty()) return err;
+    // the placement is a function of the structure and the options only: it must reproduce the image it refills
+    if (probe.value_bytes != real.value_bytes || probe.waves.size() != real.waves.size() ||
+        std::memcmp(probe.waves.data(), real.waves.data(), real.waves.size() * sizeof(WaveWork)) != 0)
+        return "the refill plan does not reproduce the image (BSM_* tunables changed since the create?)";
+    const int E = 16 / probe.es;
+    R = RefillPlan();
+    const int64_t nids = inp.nids;
+    R.nids = nids;
+    R.cptr.assign((size_t)nids + 1, 0);
+    R.chunks.reserve(probe.pack_plan.size());
+    for (const PackChunk &pc : probe.pack_plan) {
+        RefillChunk c;
+        c.dst_unit = pc.dst_unit;
+        c.id = (int32_t)(pc.src / 16 - 1);
+        c.ra = pc.ra;
+        c.n = pc.n;
+        c.woff = pc.woff;
+        c.perm_off = pc.perm_off;
+        c.mc = (int16_t)pc.mc;
+        c.trans = (int16_t)pc.trans;
+        R.chunks.push_back(c);
+        R.cptr[(size_t)c.id + 1]++;
+    }
+    std::stable_sort(R.chunks.begin(), R.chunks.end(), [](const RefillChunk &a, const RefillChunk &b) { return a.id < b.id; });
+    for (int64_t i = 0; i < nids; i++) R.cptr[i + 1] += R.cptr[i];
+    R.colpos = std::move(probe.pack_colpos);
+    // segments: a chunk's strips (identity) or columns (scattered), cut into pieces of at most kRefillItemUnits units
+    for (size_t k = 0; k < R.chunks.size(); k++) {
+        const RefillChunk &c = R.chunks[k];
+        const int32_t lo0 = c.perm_off >= 0 ? 0 : c.woff / E;
+        const int32_t hi0 = c.perm_off >= 0 ? c.n : (c.woff + c.n - 1) / E + 1;
+        const int32_t step = std::max(1, kRefillItemUnits / (int)c.mc);
+        for (int32_t lo = lo0; lo < hi0; lo += step) {
+            const int32_t hi = std::min(hi0, lo + step);
+            R.segs.push_back(RefillSeg{(int32_t)k, lo, hi, (int32_t)c.mc * (hi - lo)});
+        }
+    }
+    // items: runs of up to 64 segments / kRefillItemUnits units; items_id never cross a block id
+    auto make_items = [&](bool by_id, std::vector<RefillItem> &out) {
+        int32_t first = 0, count = 0, units = 0;
+        for (int32_t g = 0; g < (int32_t)R.segs.size(); g++) {
+            const RefillSeg &sg = R.segs[g];
+            const bool new_id = count > 0 && R.chunks[sg.chunk].id != R.chunks[R.segs[first].chunk].id;
+            if (count > 0 && (count == 64 || units + sg.units > kRefillItemUnits || (by_id && new_id))) {
+                out.push_back(RefillItem{first, count});
+                count = units = 0;
+            }
+            if (count == 0) first = g;
+            count++;
+            units += sg.units;
+        }
+        if (count > 0) out.push_back(RefillItem{first, count});
+    };
+    make_items(false, R.items_all);
+    make_items(true, R.items_id);
+    R.iptr.assign((size_t)nids + 1, 0);
+    for (const RefillItem &it : R.items_id) R.iptr[(size_t)R.chunks[R.segs[it.seg_first].chunk].id + 1]++;
+    for (int64_t i = 0; i < nids; i++) R.iptr[i + 1] += R.iptr[i];
+    R.built = true;
+    return "";
+}
+
+struct U16 {
+    uint64_t a, b;
+};
+// one chunk into the panel at dst: element (i, w) of the chunk to merged column q (identity: woff + w), i.e. unit
+// (q / E) * mc + i, slot q % E -- what the packer of the create path writes
+template <typename U>
+void refill_chunk(const RefillChunk &c, const int32_t *colpos, const U *src, int64_t ld, int E, U *dst) {
+    for (int64_t w = 0; w < c.n; w++) {
+        const int64_t q = c.perm_off >= 0 ? colpos[c.perm_off + w] : c.woff + w;
+        U *d = dst + ((q / E) * c.mc) * E + (q % E);
+        for (int i = 0; i < c.mc; i++)
+            d[(int64_t)i * E] = c.trans ? src[w + (int64_t)(c.ra + i) * ld] : src[(c.ra + i) + w * ld];
+    }
+}
+}  // namespace
+
+int ensure_plans(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, int nimg) {
+    for (int k = 0; k < nimg; k++) {
+        if (U.plan[k].built) continue;
+        std::string err = make_refill_plan(inp, k == 1, *an[k], U.plan[k]);
+        if (!err.empty()) return fail(BSM_ERR_UNSUPPORTED, "update: " + err);
+    }
+    return BSM_OK;
+}
+
+void refill_host(const Analysis &an, const RefillPlan &P, RawBuffer &values, int64_t nupd, const int64_t *ids,
+                 const void *const *src, const int64_t *ld) {
+    const int es = an.es, E = 16 / es;
+    for (int64_t k = 0; k < nupd; k++) {
+        const int64_t id = ids[k];
+        if (id < 0 || id >= P.nids) continue;
+        for (int64_t ci = P.cptr[id]; ci < P.cptr[id + 1]; ci++) {
+            const RefillChunk &c = P.chunks[ci];
+            char *dst = values.data() + (size_t)c.dst_unit * 16;
+            if (es == 4)
+                refill_chunk<uint32_t>(c, P.colpos.data(), (const uint32_t *)src[k], ld[k], E, (uint32_t *)dst);
+            else if (es == 8)
+                refill_chunk<uint64_t>(c, P.colpos.data(), (const uint64_t *)src[k], ld[k], E, (uint64_t *)dst);
+            else
+                refill_chunk<U16>(c, P.colpos.data(), (const U16 *)src[k], ld[k], E, (U16 *)dst);
+        }
+    }
+}
+
+namespace {
+template <typename V> hipError_t upload_plan(const std::vector<V> &v, void **d) {
+    if (v.empty()) return hipSuccess;
+    hipError_t e = hipMalloc(d, v.size() * sizeof(V));
+    if (e == hipSuccess) e = hipMemcpy(*d, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice);
+    return e;
+}
+
+// first update on this device: plans, table, list, event (synchronous; later updates allocate nothing)
+hipError_t update_setup(UpdateState &U, int nimg, int64_t nids) {
+    hipError_t e = hipSuccess;
+    int64_t cap = 0;
+    for (int k = 0; k < nimg && e == hipSuccess; k++) {
+        RefillDevice &R = U.img[k];
+        const RefillPlan &P = U.plan[k];
+        cap += (int64_t)P.items_id.size();
+        if (R.ready) continue;
+        e = upload_plan(P.chunks, &R.d_chunks);
+        if (e == hipSuccess) e = upload_plan(P.colpos, &R.d_colpos);
+        if (e == hipSuccess) e = upload_plan(P.segs, &R.d_segs);
+        if (e == hipSuccess) e = upload_plan(P.items_all, &R.d_items_all);
+        if (e == hipSuccess) e = upload_plan(P.items_id, &R.d_items_id);
+        if (e == hipSuccess) R.ready = true;
+    }
+    if (e == hipSuccess && !U.d_src) {
+        U.nids = nids;
+        U.list_cap = std::max<int64_t>(cap, 1);
+        e = hipMalloc((void **)&U.d_src, (size_t)std::max<int64_t>(nids, 1) * sizeof(RefillSrc));
+        if (e == hipSuccess) e = hipMalloc((void **)&U.d_list, (size_t)U.list_cap * 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&U.h_src, (size_t)std::max<int64_t>(nids, 1) * sizeof(RefillSrc), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&U.h_list, (size_t)U.list_cap * 4, hipHostMallocDefault);
+        const size_t tb = (size_t)std::max<int64_t>(nids, 1) * sizeof(RefillSrc);
+        if (e == hipSuccess) e = hipMalloc((void **)&U.d_cap_src, tb);
+        if (e == hipSuccess) e = hipMalloc((void **)&U.d_cap_list, (size_t)U.list_cap * 4);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&U.h_cap_src, tb, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&U.h_cap_list, (size_t)U.list_cap * 4, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&U.ev_done, hipEventDisableTiming);
+        if (e == hipSuccess) {
+            std::memset(U.h_src, 0, tb);
+            std::memset(U.h_cap_src, 0, tb);
+        }
+    }
+    return e;
+}
+
+bool capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// item list of a subset update for image k at `out`: the items of every updated id; returns its length
+int64_t subset_list(const RefillPlan &P, int64_t nupd, const int64_t *ids, int32_t *out) {
+    int64_t len = 0;
+    for (int64_t q = 0; q < nupd; q++) {
+        const int64_t id = ids[q];
+        if (id < 0 || id >= (int64_t)P.iptr.size() - 1) continue;
+        for (int64_t i = P.iptr[id]; i < P.iptr[id + 1]; i++) out[len++] = (int32_t)i;
+    }
+    return len;
+}
+
+// Writes the table (entries src[q] for ids[q]) and the lists, unless the device already holds exactly these; then
+// launches the refill of every image on st.  lists[k] / nitems[k] receive what image k runs.
+int enqueue_refill(UpdateState &U, int es, DeviceImage *const *img, int nimg, int64_t nupd, const int64_t *ids, bool full,
+                   const RefillSrc *src, hipStream_t st) {
+    std::vector<int32_t> list;
+    int64_t off[2] = {0, 0}, len[2] = {0, 0};
+    if (!full) {
+        list.resize((size_t)U.list_cap);
+        int64_t at = 0;
+        for (int k = 0; k < nimg; k++) {
+            off[k] = at;
+            len[k] = subset_list(U.plan[k], nupd, ids, list.data() + at);
+            at += len[k];
+        }
+        list.resize((size_t)at);
+    }
+    const int64_t want_len = full ? -1 : (int64_t)list.size();
+    int64_t lo = INT64_MAX, hi = -1;
+    for (int64_t q = 0; q < nupd; q++) {
+        lo = std::min(lo, ids[q]);
+        hi = std::max(hi, ids[q]);
+    }
+    // does (tab, lst, lst_len) already hold this call's sources and list?
+    auto holds = [&](const RefillSrc *tab, const int32_t *lst, int64_t lst_len) {
+        if (lst_len != want_len || (!full && std::memcmp(lst, list.data(), list.size() * 4) != 0)) return false;
+        for (int64_t q = 0; q < nupd; q++)
+            if (tab[ids[q]].ptr != src[q].ptr || tab[ids[q]].ld != src[q].ld) return false;
+        return true;
+    };
+    const RefillSrc *d_tab = U.d_src;
+    const int32_t *d_lst = U.d_list;
+    hipError_t e = hipSuccess;
+    if (capturing(st)) {
+        // captured copy: the graph copies its own snapshot into the capture table, then refills from it
+        if (U.cap_valid && !holds(U.h_cap_src, U.h_cap_list, U.cap_list_len))
+            return fail(BSM_ERR_UNSUPPORTED, "a handle holds one captured source table: a later captured update must name "
+                                             "the same blocks, arrays and ids as the first one");
+        if (!U.cap_valid) {
+            for (int64_t q = 0; q < nupd; q++) U.h_cap_src[ids[q]] = src[q];
+            if (!list.empty()) std::memcpy(U.h_cap_list, list.data(), list.size() * 4);
+            U.cap_list_len = want_len;
+            U.cap_valid = true;
+        }
+        e = hipMemcpyAsync(U.d_cap_src + lo, U.h_cap_src + lo, (size_t)(hi - lo + 1) * sizeof(RefillSrc), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && !list.empty())
+            e = hipMemcpyAsync(U.d_cap_list, U.h_cap_list, list.size() * 4, hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return hip_fail(e, "update: captured source table");
+        d_tab = U.d_cap_src;
+        d_lst = U.d_cap_list;
+    } else if (U.table_valid && holds(U.h_src, U.h_list, U.list_len)) {
+        // the table of the last update serves: order this stream behind that update (its copy may be on another stream)
+        if (U.pending) e = hipStreamWaitEvent(st, U.ev_done, 0);
+        if (e != hipSuccess) return hip_fail(e, "update: wait for the source table");
+    } else {
+        if (U.pending) e = hipEventSynchronize(U.ev_done);  // the kernels of the last update have read the table
+        if (e != hipSuccess) return hip_fail(e, "update: previous refill");
+        U.pending = false;
+        U.table_valid = false;
+        for (int64_t q = 0; q < nupd; q++) U.h_src[ids[q]] = src[q];
+        e = hipMemcpyAsync(U.d_src + lo, U.h_src + lo, (size_t)(hi - lo + 1) * sizeof(RefillSrc), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && !list.empty()) {
+            std::memcpy(U.h_list, list.data(), list.size() * 4);
+            e = hipMemcpyAsync(U.d_list, U.h_list, list.size() * 4, hipMemcpyHostToDevice, st);
+        }
+        if (e != hipSuccess) return hip_fail(e, "update: source table");
+        U.list_len = want_len;
+        U.table_valid = true;
+    }
+    for (int k = 0; k < nimg; k++) {
+        const RefillDevice &R = U.img[k];
+        const RefillPlan &P = U.plan[k];
+        e = full ? launch_refill(es, R.d_chunks, R.d_colpos, R.d_segs, R.d_items_all, nullptr, (long long)P.items_all.size(),
+                                 d_tab, img[k]->d_values, st)
+                 : launch_refill(es, R.d_chunks, R.d_colpos, R.d_segs, R.d_items_id, d_lst + off[k], (long long)len[k], d_tab,
+                                 img[k]->d_values, st);
+        if (e != hipSuccess) return hip_fail(e, "refill_kernel");
+    }
+    if (d_tab == U.d_cap_src) return BSM_OK;  // a captured update leaves the eager table and its event alone
+    e = hipEventRecord(U.ev_done, st);
+    if (e != hipSuccess) return hip_fail(e, "update: event");
+    U.pending = true;
+    return BSM_OK;
+}
+}  // namespace
+
+int refill_images(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, DeviceImage *const *img, int nimg,
+                  int64_t nids, int64_t nupd, const int64_t *ids, bool full, const void *const *blocks, const int64_t *ld,
+                  const int64_t *bm, const int64_t *bn, int memspace, hipStream_t st) {
+    if (capturing(st) && (memspace != BSM_MEM_DEVICE || !U.d_src))
+        return fail(BSM_ERR_UNSUPPORTED, memspace != BSM_MEM_DEVICE
+                                             ? "an update from host blocks synchronises: it cannot be graph-captured"
+                                             : "the first update of a handle uploads its plan: run one before capturing");
+    int rc0 = ensure_plans(U, inp, an, nimg);
+    if (rc0 != BSM_OK) return rc0;
+    hipError_t e = update_setup(U, nimg, nids);
+    if (e != hipSuccess) return hip_fail(e, "update: plan upload");
+    const int es = an[0]->es;
+    if (memspace == BSM_MEM_DEVICE) {
+        std::vector<RefillSrc> src((size_t)nupd);
+        for (int64_t q = 0; q < nupd; q++) src[q] = RefillSrc{(uint64_t)(uintptr_t)blocks[q], ld[q]};
+        return enqueue_refill(U, es, img, nimg, nupd, ids, full, src.data(), st);
+    }
+    // host blocks: raw copies (ld = m) into the pinned windows of the create path, one H2D copy per window, the same
+    // kernel reads the staged blocks.  Windows alternate between two pinned and two device buffers.
+    const size_t wcap_min = (size_t)64 << 20;
+    size_t biggest = 0, total = 0;
+    for (int64_t q = 0; q < nupd; q++) {
+        const size_t b = (size_t)bm[ids[q]] * (size_t)bn[ids[q]] * (size_t)es;
+        biggest = std::max(biggest, b);
+        total += (b + 255) / 256 * 256;
+    }
+    const size_t wcap = std::max(biggest, std::min(wcap_min, total));
+    // window of every block and its offset in it
+    std::vector<int64_t> wstart(1, 0);  // first update position of every window
+    std::vector<size_t> boff((size_t)nupd);
+    {
+        size_t at = 0;
+        for (int64_t q = 0; q < nupd; q++) {
+            const size_t b = ((size_t)bm[ids[q]] * (size_t)bn[ids[q]] * (size_t)es + 255) / 256 * 256;
+            if (at + b > wcap && at > 0) {
+                wstart.push_back(q);
+                at = 0;
+            }
+            boff[q] = at;
+            at += b;
+        }
+        wstart.push_back(nupd);
+    }
+    const int nwin = (int)wstart.size() - 1;
+    std::unique_lock<std::mutex> lock(g_pool.mu);
+    void *dwin[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_pending[2] = {false, false};
+    struct Cleanup {
+        void **d;
+        hipEvent_t *ev;
+        hipStream_t st;
+        UpdateState *u;
+        ~Cleanup() {
+            (void)hipStreamSynchronize(st);
+            u->pending = false;
+            u->table_valid = false;  // the eager table named the staging windows freed here
+            for (int i = 0; i < 2; i++) {
+                if (d[i]) (void)hipFree(d[i]);
+                if (ev[i]) (void)hipEventDestroy(ev[i]);
+            }
+        }
+    } cleanup{dwin, ev, st, &U};
+    for (int i = 0; i < std::min(nwin, 2) && e == hipSuccess; i++) {
+        e = hipMalloc(&dwin[i], std::max<size_t>(wcap, 16));
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
+        if (e == hipSuccess && g_pool.cap[i] < wcap) {
+            if (g_pool.buf[i]) (void)hipHostFree(g_pool.buf[i]);
+            g_pool.buf[i] = nullptr;
+            g_pool.cap[i] = 0;
+            const size_t want = std::max<size_t>(wcap, wcap_min);
+            e = hipHostMalloc((void **)&g_pool.buf[i], want, hipHostMallocDefault);
+            if (e == hipSuccess) g_pool.cap[i] = want;
+        }
+    }
+    if (e != hipSuccess) return hip_fail(e, "update: staging windows");
+    std::vector<RefillSrc> src((size_t)nupd);
+    for (int64_t q = 0; q < nupd; q++) {
+        const int w = (int)(std::upper_bound(wstart.begin(), wstart.end(), q) - wstart.begin()) - 1;
+        src[q] = RefillSrc{(uint64_t)(uintptr_t)((char *)dwin[w & 1] + boff[q]), std::max<int64_t>(bm[ids[q]], 1)};
+    }
+    for (int w = 0; w < nwin; w++) {
+        const int i = w & 1;
+        if (ev_pending[i]) {
+            e = hipEventSynchronize(ev[i]);  // the copy out of this pinned window has run
+            if (e != hipSuccess) return hip_fail(e, "update: staging");
+            ev_pending[i] = false;
+        }
+        char *pin = g_pool.buf[i];
+        size_t bytes = 0;
+        for (int64_t q = wstart[w]; q < wstart[w + 1]; q++) {
+            const int64_t m = bm[ids[q]], n = bn[ids[q]];
+            const char *b = (const char *)blocks[q];
+            char *d = pin + boff[q];
+            if (ld[q] == m)
+                std::memcpy(d, b, (size_t)(m * n) * es);
+            else
+                for (int64_t c = 0; c < n; c++) std::memcpy(d + (size_t)(c * m) * es, b + (size_t)(c * ld[q]) * es, (size_t)m * es);
+            bytes = boff[q] + (size_t)(m * n) * es;
+        }
+        if (bytes) e = hipMemcpyAsync(dwin[i], pin, bytes, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(ev[i], st);
+        if (e != hipSuccess) return hip_fail(e, "update: staged copy");
+        ev_pending[i] = true;
+        // the whole update in one window in creation order: the items of a full refill
+        const bool wfull = full && nwin == 1;
+        int rc = enqueue_refill(U, es, img, nimg, wstart[w + 1] - wstart[w], ids + wstart[w], wfull, src.data() + wstart[w], st);
+        if (rc != BSM_OK) return rc;
+    }
+    e = hipStreamSynchronize(st);
+    U.pending = false;
+    U.table_valid = false;  // its entries named the staging windows, freed below (Cleanup)
+    if (e != hipSuccess) return hip_fail(e, "update: refill");
+    return BSM_OK;
+}
+
 AnalysisOptions to_aopt(const bsm_options &o, ValueSink *sink) {
     AnalysisOptions a;
     a.sink = sink;
@@ -435,19 +885,32 @@ AnalysisOptions to_aopt(const bsm_options &o, ValueSink *sink) {
 
 namespace {
 
+std::vector<int64_t> iota_ids(size_t n) {  // input block ids of a list kept in the caller's order
+    std::vector<int64_t> v(n);
+    for (size_t b = 0; b < n; b++) v[b] = (int64_t)b;
+    return v;
+}
+
 // Common tail of every *_create: `in` is the block list in its final order (VBCRS: sorted, with
 // A->an's perm / rowptr / ... already filled).  Single device: analysis + packing + upload; with
 // bsm_options.ctx: whole-operator bookkeeping, then one image per device of the context.
 int create_handle(int mtype, int dtype, int64_t nrows, int64_t ncols, const std::vector<BlockIn> &in,
-                  const bsm_options &o, CreateCtx &cx, bsm_matrix_t *out) {
+                  const std::vector<int64_t> &ids, const bsm_options &o, CreateCtx &cx, bsm_matrix_t *out) {
     bsm_matrix_s *A = cx.A;
+    // stored shape of every input block (bsm_update_blocks checks the new ones against it)
+    A->blk_m.assign(in.size(), 0);
+    A->blk_n.assign(in.size(), 0);
+    for (size_t b = 0; b < in.size(); b++) {
+        A->blk_m[(size_t)ids[b]] = in[b].m;
+        A->blk_n[(size_t)ids[b]] = in[b].n;
+    }
     if (o.ctx) {
         AnalysisOptions ao = to_aopt(o, nullptr);
         ao.meta_only = true;
         ao.own_lo = ao.own_hi = 0;
         std::string err = A->an.build(mtype, dtype, nrows, ncols, in, ao);
         if (!err.empty()) return build_error(err);
-        int rc = dist_create(A, (bsm_ctx_s *)o.ctx, mtype, dtype, nrows, ncols, in, o);
+        int rc = dist_create(A, (bsm_ctx_s *)o.ctx, mtype, dtype, nrows, ncols, in, ids, o);
         if (rc != BSM_OK) return rc;  // ~CreateCtx releases whatever the parts already hold
         A->on_device = true;
         *out = cx.release();
@@ -473,6 +936,11 @@ int create_handle(int mtype, int dtype, int64_t nrows, int64_t ncols, const std:
         if (plain) err = build_transpose_image(A, in, o, devblocks ? nullptr : cx.values_t());
     }
     if (!err.empty()) return build_error(err);
+    {
+        AnalysisOptions ao_t = transpose_aopt(o);
+        A->upd_in = keep_inputs(mtype, dtype, nrows, ncols, in, ids, (int64_t)in.size(), to_aopt(o, nullptr),
+                                A->has_t ? &ao_t : nullptr);
+    }
     if (devblocks) {
         hipError_t e = device_pack(A->an, &A->img.d_values);
         if (e == hipSuccess && A->has_t) e = device_pack(A->an_t, &A->img_t.d_values);
@@ -494,7 +962,7 @@ int create_vbcrs(int dtype, int64_t nrows, int64_t ncols, const std::vector<Bloc
     const std::vector<int64_t> p = cx.A->an.vbcrs_bookkeeping(nb, rs.data(), cs.data());
     std::vector<BlockIn> in(nb);
     for (int64_t k = 0; k < nb; k++) in[k] = unsorted[p[k]];
-    return create_handle(MT_VBCRS, dtype, nrows, ncols, in, o, cx, out);
+    return create_handle(MT_VBCRS, dtype, nrows, ncols, in, p, o, cx, out);  // block k of the image is input p[k]
 }
 
 }  // namespace
@@ -620,7 +1088,7 @@ extern "C" int bsm_vbcrs_create_from_symmetric(int dtype, int64_t nrows, int64_t
             B.kind = KIND_OFF;
             in.push_back(B);
         }
-        return create_handle(MT_VBCRS, dtype, nrows, ncols, in, o, cx, out);)
+        return create_handle(MT_VBCRS, dtype, nrows, ncols, in, iota_ids(in.size()), o, cx, out);)
 }
 
 extern "C" int bsm_blocksparse_create(int dtype, int64_t nrows, int64_t ncols, int64_t nblocks,
@@ -651,7 +1119,7 @@ extern "C" int bsm_blocksparse_create(int dtype, int64_t nrows, int64_t ncols, i
                 return fail(BSM_ERR_INVALID, "block " + std::to_string(b + 1) + ": null index list");
         }
         CreateCtx cx;
-        return create_handle(MT_BLOCKSPARSE, dtype, nrows, ncols, in, o, cx, out);)
+        return create_handle(MT_BLOCKSPARSE, dtype, nrows, ncols, in, iota_ids(in.size()), o, cx, out);)
 }
 
 extern "C" int bsm_symmetric_create(int dtype, int64_t nrows, int64_t ncols, int64_t ndiag,
@@ -699,7 +1167,7 @@ extern "C" int bsm_symmetric_create(int dtype, int64_t nrows, int64_t ncols, int
             in.push_back(B);
         }
         CreateCtx cx;
-        return create_handle(MT_SYMMETRIC, dtype, nrows, ncols, in, o, cx, out);)
+        return create_handle(MT_SYMMETRIC, dtype, nrows, ncols, in, iota_ids(in.size()), o, cx, out);)
 }
 
 // ---- contexts of devices (multi-GPU handles) -----------------------------------------------------
@@ -1178,6 +1646,54 @@ extern "C" int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X
     return BSM_OK;
 }
 
+extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *ids, const void *const *blocks,
+                                 const int64_t *ld, int memspace, void *stream) {
+    BSM_GUARDED(
+        if (!A) return fail(BSM_ERR_INVALID, "null handle");
+        if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
+        const int64_t nb = (int64_t)A->blk_m.size();
+        if (nupd < 0 || nupd > nb) return fail(BSM_ERR_INVALID, "nupd out of range");
+        if (!ids && nupd != nb) return fail(BSM_ERR_INVALID, "ids == NULL needs nupd == the number of blocks");
+        if (nupd > 0 && (!blocks || !ld)) return fail(BSM_ERR_INVALID, "null argument");
+        // every argument is checked before anything is written
+        std::vector<int64_t> id0((size_t)nupd);
+        std::vector<uint8_t> seen((size_t)nb, 0);
+        bool in_order = true;
+        for (int64_t k = 0; k < nupd; k++) {
+            const int64_t id = ids ? ids[k] - 1 : k;
+            if (id < 0 || id >= nb) return fail(BSM_ERR_INVALID, "update " + std::to_string(k + 1) + ": block id out of range");
+            if (seen[id]) return fail(BSM_ERR_INVALID, "update " + std::to_string(k + 1) + ": duplicate block id");
+            seen[id] = 1;
+            in_order &= (id == k);
+            id0[k] = id;
+            const int64_t m = A->blk_m[id], n = A->blk_n[id];
+            if (ld[k] < m || ld[k] < 1) return fail(BSM_ERR_INVALID, "update " + std::to_string(k + 1) + ": ld < m");
+            if (!blocks[k] && m > 0 && n > 0) return fail(BSM_ERR_INVALID, "update " + std::to_string(k + 1) + ": null block");
+        }
+        if (nupd == 0) return BSM_OK;
+        const bool full = in_order && nupd == nb;
+        hipStream_t st = (hipStream_t)stream;
+        std::lock_guard<std::mutex> lk(A->upd_mu);
+        if (A->dist) return dist_update(A, nupd, id0.data(), full, blocks, ld, memspace, st);
+        if (!A->upd_in) return fail(BSM_ERR_UNSUPPORTED, "handle keeps no block list");
+        if (!A->on_device) {
+            if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "an analysis-only handle takes host blocks only");
+            Analysis *an[2] = {&A->an, &A->an_t};
+            int rc = ensure_plans(A->upd, *A->upd_in, an, A->has_t ? 2 : 1);
+            if (rc != BSM_OK) return rc;
+            refill_host(A->an, A->upd.plan[0], A->an.values, nupd, id0.data(), blocks, ld);
+            if (A->has_t) refill_host(A->an_t, A->upd.plan[1], A->an_t.values, nupd, id0.data(), blocks, ld);
+            return BSM_OK;
+        }
+        DeviceGuard guard;
+        hipError_t e = guard.enter(A->img.device);
+        if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+        Analysis *an[2] = {&A->an, &A->an_t};
+        DeviceImage *img[2] = {&A->img, &A->img_t};
+        return refill_images(A->upd, *A->upd_in, an, img, A->has_t ? 2 : 1, nb, nupd, id0.data(), full, blocks, ld, A->blk_m.data(),
+                             A->blk_n.data(), memspace, st);)
+}
+
 static int copy_out(const std::vector<int64_t> &v, int64_t *out, int64_t *len) {
     if (!len) return fail(BSM_ERR_INVALID, "len is null");
     if (out) {
@@ -1330,6 +1846,7 @@ extern "C" int bsm_destroy(bsm_matrix_t A) {
         if (A->stage_y) (void)hipFree(A->stage_y);
         if (A->il.xr) (void)hipFree(A->il.xr);
         if (A->il.w) (void)hipFree(A->il.w);
+        update_free(A->upd);
     }
     delete A;
     return BSM_OK;

@@ -73,6 +73,8 @@ struct Part {
     // the part's own previous delivery, or everything runs on one stream), which is all the arrays need.
     ILWork il;
     bool il_failed = false;  // no memory for them: the ordinary kernels from then on
+    UpdateState upd;  // bsm_update_blocks on this part's device
+    std::unique_ptr<UpdateInputs> upd_in;
 };
 
 // the part's work arrays if its image / this product take the interleaved pass (and they can be had), else null
@@ -356,6 +358,7 @@ void dist_destroy(bsm_matrix_s *A) {
         DeviceGuard g;
         (void)g.enter(p.device);
         if (p.stream) (void)hipStreamSynchronize(p.stream);
+        update_free(p.upd);
         free_image(p.img);
         for (void *q : {p.d_x, p.d_w, p.d_recv, p.il.xr, p.il.w})
             if (q) (void)hipFree(q);
@@ -384,7 +387,7 @@ void dist_destroy(bsm_matrix_s *A) {
 }
 
 int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t nrows, int64_t ncols,
-                const std::vector<BlockIn> &in, const bsm_options &o) {
+                const std::vector<BlockIn> &in, const std::vector<int64_t> &ids, const bsm_options &o) {
     const int P = (int)ctx->devices.size();
     if (P < 1) return fail(BSM_ERR_INVALID, "context has no device");
     A->dist.reset(new DistState());
@@ -415,7 +418,11 @@ int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t n
     D.plan_n.in.resize(P);
     D.plan_t.in.resize(P);
     std::vector<std::vector<BlockIn>> subs(P);
-    for (size_t b = 0; b < in.size(); b++) subs[part_of[b]].push_back(in[b]);
+    std::vector<std::vector<int64_t>> sub_ids(P);
+    for (size_t b = 0; b < in.size(); b++) {
+        subs[part_of[b]].push_back(in[b]);
+        sub_ids[part_of[b]].push_back(ids[b]);
+    }
     for (int p = 0; p < P; p++) {
         D.parts.emplace_back(new Part());
         Part &pt = *D.parts.back();
@@ -463,6 +470,7 @@ int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t n
             ao.skip_colors = true;
             std::string err = pt.an.build(mtype, dtype, nrows, ncols, subs[p], ao);
             if (!err.empty()) return build_error("device part " + std::to_string(p) + ": " + err);
+            pt.upd_in = keep_inputs(mtype, dtype, nrows, ncols, subs[p], sub_ids[p], (int64_t)in.size(), ao, nullptr);
             if (devblocks) {  // the blocks may live on another device of the context: read over xGMI
                 e = device_pack(pt.an, &pt.img.d_values);
                 if (e != hipSuccess) return hip_fail(e, "device-side packing");
@@ -527,10 +535,9 @@ int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t n
 
 // part buffers for K columns (grow-only).  EVERY part's stream is drained before ANY buffer goes: a peer may
 // still be reading this part's work vector.
-static hipError_t grow_buffers(DistState &D, int K) {
-    if (K <= D.kcap) return hipSuccess;
+// Waits until nothing of any earlier product of the handle can still be running (or reading a part's buffers).
+static hipError_t drain_handle(DistState &D) {
     const int P = (int)D.parts.size();
-    const size_t es = (size_t)D.es;
     hipError_t e = hipSuccess;
     for (int p = 0; p < P && e == hipSuccess; p++) {
         DeviceGuard g;
@@ -550,6 +557,14 @@ static hipError_t grow_buffers(DistState &D, int K) {
             if (e == hipSuccess) e = hipDeviceSynchronize();
         }
     }
+    return e;
+}
+
+static hipError_t grow_buffers(DistState &D, int K) {
+    if (K <= D.kcap) return hipSuccess;
+    const int P = (int)D.parts.size();
+    const size_t es = (size_t)D.es;
+    hipError_t e = drain_handle(D);
     for (int p = 0; p < P && e == hipSuccess; p++) {
         Part &pt = *D.parts[p];
         DeviceGuard g;
@@ -1228,6 +1243,55 @@ int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long 
                             alpha, beta, beta_strong_zero, memspace, stream);
         if (rc != BSM_OK) return rc;
         k += kb;
+    }
+    return BSM_OK;
+}
+
+// bsm_update_blocks: every part refills its own image on its device, on its own stream, from the blocks it holds
+// (device blocks on another device are read over xGMI, as at create; host blocks are staged per part).  The fan-out
+// orders a product's work by streams, events and flags that an update is not part of, so the update stands outside
+// it: it waits for the caller's stream (where the new blocks were written) and for every earlier product of the
+// handle, refills, and returns when every part's image holds the new values.
+int dist_update(bsm_matrix_s *A, int64_t nupd, const int64_t *ids, bool full, const void *const *blocks, const int64_t *ld,
+                int memspace, hipStream_t stream) {
+    DistState &D = *A->dist;
+    std::lock_guard<std::mutex> lock(D.mu);
+    hipError_t e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = drain_handle(D);
+    if (e != hipSuccess) return hip_fail(e, "update: drain");
+    const int64_t nb = (int64_t)A->blk_m.size();
+    std::vector<int64_t> pid;
+    std::vector<const void *> pblk;
+    std::vector<int64_t> pld;
+    for (auto &pp : D.parts) {
+        Part &pt = *pp;
+        if (!pt.has_image) continue;
+        Analysis *an[1] = {&pt.an};
+        int rc0 = ensure_plans(pt.upd, *pt.upd_in, an, 1);
+        if (rc0 != BSM_OK) return rc0;
+        const RefillPlan &R = pt.upd.plan[0];
+        pid.clear();
+        pblk.clear();
+        pld.clear();
+        for (int64_t k = 0; k < nupd; k++) {
+            const int64_t id = ids[k];
+            if (id < R.nids && R.cptr[id + 1] > R.cptr[id]) {  // the part holds chunks of block id
+                pid.push_back(id);
+                pblk.push_back(blocks[k]);
+                pld.push_back(ld[k]);
+            }
+        }
+        if (pid.empty()) continue;
+        DeviceGuard g;
+        e = g.enter(pt.device);
+        if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+        DeviceImage *img[1] = {&pt.img};
+        int rc = refill_images(pt.upd, *pt.upd_in, an, img, 1, nb, (int64_t)pid.size(), pid.data(), full, pblk.data(), pld.data(),
+                               A->blk_m.data(), A->blk_n.data(), memspace, pt.stream);
+        if (rc != BSM_OK) return rc;
+        e = hipStreamSynchronize(pt.stream);
+        if (e != hipSuccess) return hip_fail(e, "update: refill");
+        pt.upd.pending = false;
     }
     return BSM_OK;
 }

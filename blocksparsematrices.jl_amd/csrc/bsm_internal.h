@@ -11,6 +11,7 @@
 #include "../../include/bsm_rocm.h"
 #include "bsm_analysis.h"
 #include "bsm_kernels.h"
+#include "bsm_refill.h"
 
 struct bsm_ctx_s {
     std::vector<int> devices;  // HIP ordinals; the same ordinal may appear several times (virtual devices)
@@ -21,6 +22,59 @@ struct bsm_ctx_s {
 
 namespace bsm {
 struct DistState;  // bsm_dist.cpp
+
+// bsm_update_blocks on one device: the device copy of the refill plans of its images (uploaded at the first update,
+// kept until the handle is destroyed) and the per-call table of source blocks (RefillSrc by input block id) with the
+// item list of a subset update.  The table is written from a pinned host mirror, and only when it differs from what
+// the last update wrote: an update that names the same arrays as the previous one enqueues nothing but the kernels.
+struct RefillDevice {
+    void *d_chunks = nullptr, *d_colpos = nullptr, *d_segs = nullptr, *d_items_all = nullptr, *d_items_id = nullptr;
+    bool ready = false;
+};
+// what *_create analysed, kept for bsm_update_blocks: the block list (index lists copied, `data` = a token naming the
+// input block id instead of an address) and the options of the image(s)
+struct UpdateInputs {
+    int mtype = 0, dtype = 0;
+    int64_t nrows = 0, ncols = 0;
+    int64_t nids = 0;          // blocks of the whole *_create call (a part of a multi-device handle holds some)
+    AnalysisOptions ao, ao_t;  // forward image, transposed image
+    std::vector<BlockIn> in;
+    std::vector<std::vector<int64_t>> lists;
+};
+// ids[b]: input block id (position in the *_create call) of in[b]
+std::unique_ptr<UpdateInputs> keep_inputs(int mtype, int dtype, int64_t nrows, int64_t ncols, const std::vector<BlockIn> &in,
+                                          const std::vector<int64_t> &ids, int64_t nids, const AnalysisOptions &ao,
+                                          const AnalysisOptions *ao_t);
+struct UpdateState {
+    RefillPlan plan[2];   // host plans (built at the first update)
+    RefillDevice img[2];  // forward image, transposed image
+    RefillSrc *d_src = nullptr, *h_src = nullptr;
+    int32_t *d_list = nullptr, *h_list = nullptr;
+    int64_t nids = 0, list_cap = 0;
+    hipEvent_t ev_done = nullptr;  // end of the last update's kernels: the table may be rewritten from then on
+    bool pending = false;
+    bool table_valid = false;  // d_src / d_list hold h_src / h_list as of the last update (false after a host update:
+                               // its entries named staging windows that are gone)
+    int64_t list_len = -1;     // length of that list (-1: full update, no list)
+    // graph-captured updates: the graph carries its own copy of the table -- a captured H2D copy from a pinned snapshot
+    // into a device table only captured updates use.  Written once, by the first captured update; eager updates never
+    // touch either, so a replay reads what its capture saw.
+    RefillSrc *d_cap_src = nullptr, *h_cap_src = nullptr;
+    int32_t *d_cap_list = nullptr, *h_cap_list = nullptr;
+    bool cap_valid = false;
+    int64_t cap_list_len = -1;
+};
+void update_free(UpdateState &U);
+// builds U.plan[0..nimg) from the kept inputs (an[k]: the image's own analysis, which the plan is checked against)
+int ensure_plans(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, int nimg);
+// host refill of an analysis-only image (Analysis::values) through plan P
+void refill_host(const Analysis &an, const RefillPlan &P, RawBuffer &values, int64_t nupd, const int64_t *ids,
+                 const void *const *src, const int64_t *ld);
+// Refills images img[0..nimg) (analyses an[]) on the CURRENT device from blocks[k] / ld[k] for the 0-based input ids
+// ids[k] (full: every id 0..nids-1 in order).  BSM_MEM_DEVICE: enqueued on `st`; BSM_MEM_HOST: staged, synchronous.
+int refill_images(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, DeviceImage *const *img, int nimg, int64_t nids, int64_t nupd,
+                  const int64_t *ids, bool full, const void *const *blocks, const int64_t *ld, const int64_t *bm,
+                  const int64_t *bn, int memspace, hipStream_t st);
 }
 
 struct bsm_matrix_s {
@@ -48,6 +102,11 @@ struct bsm_matrix_s {
     size_t stage_x_bytes = 0, stage_y_bytes = 0;
     // handle spread over the devices of a context (bsm_options.ctx)
     std::unique_ptr<bsm::DistState> dist;
+    // bsm_update_blocks: stored shape of every input block (constructor order) and the device state of the refill
+    std::vector<int64_t> blk_m, blk_n;
+    std::mutex upd_mu;
+    std::unique_ptr<bsm::UpdateInputs> upd_in;
+    bsm::UpdateState upd;
     bsm_matrix_s();
     ~bsm_matrix_s();
 };
@@ -76,8 +135,9 @@ std::unique_ptr<ValueSink> make_device_sink(void **d_values);
 // ---- bsm_dist.cpp -------------------------------------------------------------------------------
 // Row partition of `in` (already in its final order) over the context's devices; fills A->dist.
 // A->an must already hold the whole operator's bookkeeping (meta-only analysis).
+// ids[b]: input block id of in[b] (bsm_update_blocks)
 int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t nrows, int64_t ncols,
-                const std::vector<BlockIn> &in, const bsm_options &o);
+                const std::vector<BlockIn> &in, const std::vector<int64_t> &ids, const bsm_options &o);
 int dist_mul(bsm_matrix_s *A, int op, const void *x, void *y, const void *alpha, const void *beta,
              int beta_strong_zero, int memspace, hipStream_t stream);
 int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long long ldx, void *Y, long long ldy,
@@ -86,6 +146,9 @@ int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *co
                    const void *beta, int beta_strong_zero, void *const *streams);
 void dist_destroy(bsm_matrix_s *A);
 int dist_part_info(bsm_matrix_s *A, int32_t part, bsm_part_info_t *out);
+// bsm_update_blocks of a multi-device handle (arguments checked by the caller; ids 0-based)
+int dist_update(bsm_matrix_s *A, int64_t nupd, const int64_t *ids, bool full, const void *const *blocks, const int64_t *ld,
+                int memspace, hipStream_t stream);
 int64_t dist_device_bytes(const bsm_matrix_s *A);
 // (analysis, image) of every part that holds blocks
 void dist_images(bsm_matrix_s *A, std::vector<std::pair<const Analysis *, const DeviceImage *>> &out);

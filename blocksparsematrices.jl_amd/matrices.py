@@ -18,6 +18,7 @@ libbsmrocm.so (HIP, gfx950); this module only marshals arguments.  x / y may be 
 arrays (host memory: the library stages them over PCIe) or torch CUDA tensors (device
 memory, enqueued on torch's current stream).
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -37,6 +38,7 @@ __all__ = [
     "eachdiagonalindex", "eachoffdiagonalindex", "diagonalindices", "diagonalcolors",
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
+    "update_blocks", "refresh",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -453,6 +455,7 @@ class BlockSparseMatrix(AbstractBlockMatrix):
             n.ctypes.data_as(I), ld.ctypes.data_as(I), _ptrs(self.rowindices),
             _ptrs(self.colindices), C.byref(o), C.byref(h)))
         self._finish(h, dt, size, scheduler, dev, devices)
+        self._src = lambda: list(self.blocks)
         self.colors = _classes(self._bookkeeping(L.BSM_BK_COLORS))
         self.transposecolors = _classes(self._bookkeeping(L.BSM_BK_TRANSPOSECOLORS))
 
@@ -498,6 +501,7 @@ class SymmetricBlockMatrix(AbstractBlockMatrix):
             m.ctypes.data_as(I), n.ctypes.data_as(I), ld.ctypes.data_as(I),
             _ptrs(self.rowindices), _ptrs(self.colindices), C.byref(o), C.byref(h)))
         self._finish(h, dt, size, scheduler, dev, devices)
+        self._src = lambda: list(self.diagonals) + list(self.offdiagonals)  # bsm_update_blocks order: diag..., off...
         self.offdiagonalcolors = _classes(self._bookkeeping(L.BSM_BK_COLORS))
         self.transposeoffdiagonalcolors = _classes(self._bookkeeping(L.BSM_BK_TRANSPOSECOLORS))
         self.diagonalcolors = _classes(self._bookkeeping(L.BSM_BK_DIAGONALCOLORS))
@@ -538,7 +542,9 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
                 r0.ctypes.data_as(I), c0.ctypes.data_as(I), C.byref(o), C.byref(h)))
             matrixsize = s.size
             fb = mats
+            src = lambda: list(s.diagonals) + list(s.offdiagonals)  # noqa: E731  the handle's block order
         else:
+            materialized = False
             if isinstance(matrices, BlockSparseMatrix):  # src/vbcrs.jl:150-160
                 # bsm_vbcrs_create_from_blocksparse: first(rowindices(b, i)) / first(colindices(b, i))
                 # are taken inside the library (src/vbcrs.jl:201-215)
@@ -558,10 +564,12 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
                     C.byref(o), C.byref(h)))
                 matrixsize = b.size
                 mats = None
+                src = lambda: list(b.blocks)  # noqa: E731  the source's own list: edits of b.blocks[i] are seen
             elif isinstance(matrices, SymmetricBlockMatrix):  # reference behaviour: materialise
                 s = matrices
                 scheduler = s.scheduler if scheduler is None else scheduler
                 mats = list(s.diagonals) + list(s.offdiagonals) + [o.T for o in s.offdiagonals]
+                materialized = True
                 rowindices = ([int(d[0]) for d in s.diagonalindices] + [int(r[0]) for r in s.rowindices]
                               + [int(c[0]) for c in s.colindices])
                 colindices = ([int(d[0]) for d in s.diagonalindices] + [int(c[0]) for c in s.colindices]
@@ -587,12 +595,106 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
                     _DT[dt], int(matrixsize[0]), int(matrixsize[1]), len(fb), _ptrs(fb),
                     m.ctypes.data_as(I), n.ctypes.data_as(I), ld.ctypes.data_as(I), rs.ctypes.data_as(I),
                     cs.ctypes.data_as(I), C.byref(o), C.byref(h)))
+                src = (lambda fb=fb: list(fb))  # the constructor's order (self.blocks is the sorted view of it)
+                if materialized:
+                    # the handle holds every off-diagonal block twice (as given and transposed): a new value for one
+                    # must reach both, which no single entry of a block list expresses
+                    def src():
+                        raise NotImplementedError(
+                            "update_blocks / refresh of a VBCRS that materialised a SymmetricBlockMatrix: build it with "
+                            "materialize=False (the symmetric image, which refreshes from the source's lists)")
         self._finish(h, dt, matrixsize, scheduler, dev, devices)
+        self._src = src
         self.perm = self._bookkeeping(L.BSM_BK_VBCRS_PERM).copy()
         self.rowptr = self._bookkeeping(L.BSM_BK_VBCRS_ROWPTR).copy()
         self.colindices = self._bookkeeping(L.BSM_BK_VBCRS_COLINDICES).copy()
         self.rowindices = self._bookkeeping(L.BSM_BK_VBCRS_ROWINDICES).copy()
         self.blocks = [fb[p - 1] for p in self.perm]
+
+
+# ---- new values for an existing operator (bsm_update_blocks) ----------------------------------------------
+# The reference's types hold the caller's block matrices by reference (src/vbcrs.jl:98,114, src/blockmatrix.jl:26-34):
+# an in-place edit of block(A, i) is what the next mul! reads.  The handle here holds a packed copy; these two calls
+# bring it up to date without rebuilding it.  Block order = the constructor's: `blocks` of a BlockSparseMatrix or of
+# a VBCRS made from a list (NOT its sorted A.blocks), diagonals + offdiagonals of a SymmetricBlockMatrix, and the
+# source's lists for a VBCRS made from a BlockSparseMatrix / SymmetricBlockMatrix.
+def _update_ids(ids, nb):
+    if ids is None:
+        return list(range(1, nb + 1))
+    ids = [int(i) for i in ids]
+    for i in ids:
+        if not 1 <= i <= nb:
+            raise IndexError(f"block id {i} out of range 1..{nb}")
+    if len(set(ids)) != len(ids):
+        raise ValueError("duplicate block id")
+    return ids
+
+
+def _stream_ptr(stream, dev):
+    if stream is not None:
+        return stream.cuda_stream if hasattr(stream, "cuda_stream") else stream
+    return torch.cuda.current_stream(dev).cuda_stream if dev is not None else None
+
+
+def refresh(A, ids=None, stream=None):
+    """Pushes the CURRENT contents of the mirror's block fields (A.blocks / A.diagonals / A.offdiagonals, edited in
+    place by the caller) to the device image -- the reference's by-reference semantics, restored by one explicit call.
+    ids: 1-based block ids in constructor order (None = all).  Device-resident blocks (torch CUDA tensors) are read by
+    a kernel on `stream` (default: torch's current stream) without synchronising; host blocks are staged and the call
+    returns when the image holds them."""
+    A, _ = _unwrap(A)
+    src = A._src()
+    ids = _update_ids(ids, len(src))
+    blks = [src[i - 1] for i in ids]
+    devb = _is_dev(blks)
+    if devb:
+        if _dev_blocks(blks) != A.dtype:
+            raise TypeError("device blocks must have the operator's element type")
+        arrs = blks
+    else:
+        arrs = []
+        for b in blks:
+            a = _host(b)
+            if a.ndim != 2 or not a.flags.f_contiguous or a.dtype != A.dtype:
+                a = np.asfortranarray(a, dtype=A.dtype)
+            arrs.append(a)
+    ld = _lds(arrs)
+    idv = _i64(ids)
+    I = C.POINTER(C.c_int64)
+    st = _stream_ptr(stream, blks[0].device) if devb and len(blks) else None
+    L.check(L.lib().bsm_update_blocks(A._h.ptr, len(ids), idv.ctypes.data_as(I), _ptrs(arrs), ld.ctypes.data_as(I),
+                                      L.BSM_MEM_DEVICE if devb else L.BSM_MEM_HOST, st))
+
+
+def update_blocks(A, blocks, ids=None, stream=None):
+    """Replaces the values of blocks of A in place -- `copyto!(block(A, i), B)` for every new block, then one push to
+    the device (refresh).  blocks: the new values in constructor order (for a SymmetricBlockMatrix diagonals +
+    offdiagonals), numpy arrays or column-major torch CUDA tensors whatever A was built from; ids: their 1-based
+    positions (None = all).  Shapes stay as created."""
+    B, _ = _unwrap(A)
+    src = B._src()
+    ids = _update_ids(ids, len(src))
+    if len(blocks) != len(ids):
+        raise ValueError("one block per id")
+    for i, new in zip(ids, blocks):
+        if tuple(new.shape) != tuple(src[i - 1].shape):
+            raise ValueError(f"block {i}: shape {tuple(new.shape)} != {tuple(src[i - 1].shape)}")
+    dev = [i for i in ids if torch is not None and isinstance(src[i - 1], torch.Tensor)]
+    # the copies into device fields go on the stream the refill runs on (they must land before it reads them)
+    ctx = contextlib.nullcontext()
+    if dev and stream is not None:
+        st = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        st.wait_stream(torch.cuda.current_stream())  # the new values may come from the current stream's work
+        ctx = torch.cuda.stream(st)
+    with ctx:
+        for i, new in zip(ids, blocks):
+            dst = src[i - 1]
+            if torch is not None and isinstance(dst, torch.Tensor):
+                t = new if isinstance(new, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(new))
+                dst.copy_(t.to(dst.device))
+            else:
+                dst[...] = new.cpu().numpy() if (torch is not None and isinstance(new, torch.Tensor)) else new
+    refresh(B, ids, stream)
 
 
 # ---- mul! ------------------------------------------------------------------------------------------------

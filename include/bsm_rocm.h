@@ -14,8 +14,10 @@
  *     coalesced 16-byte lane loads); the caller may free its arrays afterwards;
  *   - all functions return 0 on success, a negative bsm_status otherwise, never throw;
  *     bsm_last_error() returns a thread-local message for the last failure;
- *   - a handle is immutable after creation: concurrent bsm_mul calls with distinct y
- *     (and distinct streams) are legal.
+ *   - a handle's STRUCTURE is fixed at creation (block positions, shapes, index lists, options);
+ *     its VALUES can be replaced in place with bsm_update_blocks, the counterpart of the reference
+ *     holding the caller's blocks by reference.  Concurrent bsm_mul calls with distinct y (and
+ *     distinct streams) are legal.
  */
 #ifndef BSM_ROCM_H
 #define BSM_ROCM_H
@@ -319,6 +321,47 @@ int bsm_host_unregister(void *ptr);
 int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y,
                   int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace,
                   void *stream);
+
+/* Replaces the VALUES of blocks of an existing handle -- what a Julia caller gets by editing block(A, i) in place
+ * (the reference keeps the caller's matrices by reference, src/vbcrs.jl:98,114, src/blockmatrix.jl:26-34).
+ * Structure, index lists, shapes, options and the layout of the device image stay as created: no analysis runs.
+ *   ids: nupd 1-based positions in the block order of the *_create call that made the handle -- `blocks` of
+ *     bsm_vbcrs_create / _blocksparse_create / _vbcrs_create_from_blocksparse (the caller's order, NOT the
+ *     VBCRS-sorted one), `diag` followed by `off` for bsm_symmetric_create / _vbcrs_create_from_symmetric;
+ *     NULL = all blocks in that order (nupd must then equal the count).
+ *   blocks[k] / ld[k]: block ids[k], same m x n as at creation, column-major, ld[k] >= m (ld may differ from the
+ *     one given at creation).  memspace: where the blocks live.
+ *   BSM_MEM_DEVICE: enqueued on `stream`, returns without synchronising; the blocks must stay valid until the
+ *     stream reaches the update.  The first update of a handle uploads its refill plan (allocates, synchronises);
+ *     after it an update allocates nothing.  The kernels read a table of sources (device address + ld per block):
+ *     an update that names the same blocks, arrays and ids as the previous one reuses the table and makes `stream`
+ *     wait for that update; one that names others first waits on the host for the previous update's kernels, then
+ *     copies its table on `stream`.
+ *     Graph capture (single-device handles, after one uncaptured update): a captured update carries its OWN copy of
+ *     the table -- a captured copy from a pinned snapshot taken at capture time into a device table only captured
+ *     updates use -- so a replay reads the addresses its capture saw (they must still be valid, and the data there is
+ *     what the replay refills from), whatever uncaptured updates ran in between.  A handle holds one such snapshot:
+ *     every captured update of it must name the same blocks, arrays and ids (BSM_ERR_UNSUPPORTED otherwise), and
+ *     host-block updates cannot be captured.
+ *   BSM_MEM_HOST: returns when the image holds the new values (the caller may reuse its arrays).  The blocks go
+ *     through pinned 64 MB staging windows, double-buffered, once over PCIe; the same kernel places them.
+ * Every image the handle owns is refilled: the forward one, the transposed one (bsm_options.transpose_image) and
+ * every part of a multi-device handle on its own device.  A multi-device handle's update waits for `stream` and for
+ * every earlier product of the handle, and returns when all parts hold the new values.  Analysis-only handles
+ * (BSM_DEVICE_NONE) take BSM_MEM_HOST updates (their host image, bsm_get_image, is rewritten).
+ * Products enqueued on `stream` after the call see the new values.  Products on other streams, and products
+ * running in other threads on the same handle, are the caller's to order (as for any write the caller makes to x):
+ * an update is stream-ordered like a product and takes no lock on the product path.
+ * Every argument is checked before the first byte is written: a failing call leaves the handle unchanged
+ * (BSM_ERR_INVALID: null handle or pointer, id out of range, duplicate id, nupd != count with ids == NULL, ld < m,
+ * bad memspace, BSM_MEM_DEVICE on an analysis-only handle).
+ * Memory: a handle keeps its block list from creation on (index lists copied).  The first update derives the refill
+ * plan from it -- the value-blind placement of the create, re-run and checked against the image -- and keeps it on the
+ * host and on the device until bsm_destroy: 32 B per <= 64-row chunk of every image, 16 B per segment of <= 16 KB,
+ * 8 B per wave item, 16 B per block id, 4 B per stored column of scattered index-list groups; on the device also the
+ * two 16 B per block source tables (uncaptured, captured) and their pinned host mirrors.  bsm_stats_t does not count it. */
+int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *ids, const void *const *blocks,
+                      const int64_t *ld, int memspace, void *stream);
 
 /* Bookkeeping queries (bit-exact contract; every value 1-based int64 like the reference).
  * Call with out == NULL to obtain the required length in *len. */

@@ -264,6 +264,38 @@ function part_ranges(A)
     return out
 end
 
+# ---- new values for an existing operator (bsm_update_blocks) --------------------------------------------------
+# The reference's structs hold the caller's block matrices BY REFERENCE (src/vbcrs.jl:98,114, src/blockmatrix.jl:26-34):
+# after `block(A, i) .= B` the next mul! reads the new values.  The cached handle holds a packed copy instead, so an
+# in-place edit is invisible to it until
+#     refresh!(A; ids=nothing)
+# pushes the struct's CURRENT block contents into it: the structure stays (no analysis, no new handle), only values
+# move.  ids: 1-based positions in the handle's block order -- A.blocks (VBCRS, BlockSparseMatrix), diagonals then
+# offdiagonals (SymmetricBlockMatrix) -- `nothing` = all.  Host blocks: returns when the image holds them.  ROCArray
+# blocks: enqueued on the task-local stream, like a device-vector product.
+_updblocks(A::VariableBlockCompressedRowStorage) = A.blocks
+_updblocks(A::BlockSparseMatrix) = A.blocks
+_updblocks(A::SymmetricBlockMatrix) = vcat(A.diagonals, A.offdiagonals)
+_memspace(b) = 0                    # host Matrix (device arrays: 1, below)
+_updstream(b) = C_NULL
+
+function refresh!(A::ROCmOp{<:ROCmMat}; ids=nothing)
+    B = _base(A)
+    T = eltype(B)
+    h = handle(B)
+    allb = _updblocks(B)
+    idv = ids === nothing ? collect(Int64, 1:length(allb)) : Int64.(collect(ids))
+    isempty(idv) && return A
+    sel = allb[idv]
+    ms = _memspace(first(sel))
+    bl = ms == 0 ? _cblocks(T, sel) : sel
+    st = ms == 0 ? C_NULL : _updstream(first(sel))
+    GC.@preserve B bl idv _check(ccall((:bsm_update_blocks, libbsm), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Cint, Ptr{Cvoid}),
+        h.ptr, length(idv), idv, Ptr{Cvoid}[pointer(b) for b in bl], _ld.(bl), ms, st))
+    return A
+end
+
 # ---- device-resident vectors (AMDGPU.jl) -----------------------------------------------------------------
 # Iterative solvers keep x / y in HBM: BSM_MEM_DEVICE, enqueued on the task-local HIP stream, no
 # synchronisation (the product is 10 us for a C2-sized operator against 74-118 us through host vectors).
@@ -271,6 +303,9 @@ end
 if Base.find_package("AMDGPU") !== nothing
     @eval begin
         import AMDGPU
+        # refresh! of a struct whose blocks are ROCMatrix: BSM_MEM_DEVICE, the task-local stream
+        _memspace(::AMDGPU.ROCMatrix) = 1
+        _updstream(::AMDGPU.ROCMatrix) = Base.unsafe_convert(Ptr{Cvoid}, AMDGPU.stream().stream)
         function LinearMaps._unsafe_mul!(y::AMDGPU.ROCVector{T}, A::ROCmOp{Z}, x::AMDGPU.ROCVector{T},
                 α::Number, β::Number) where {T<:ROCmEltype,Z<:ROCmMat}
             (eltype(_base(A)) === T && _fits(T, α) && _fits(T, β)) ||
