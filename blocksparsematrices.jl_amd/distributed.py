@@ -332,7 +332,6 @@ class RowPartitioned:
         # x entries this rank's blocks read (1-based inclusive) when x arrives PARTITIONED like y
         # (mul(..., x_distributed=True)); None: everything (the x slices are all-gathered first)
         self.xneed = None if xneed is None else (int(xneed[0]), int(xneed[1]))
-        self._xplan = None
         self.group = group
         self.gather = gather
         self.axis = axis
@@ -344,13 +343,14 @@ class RowPartitioned:
             if self.world != 1:
                 raise ValueError("loopback is a one-rank rehearsal")
             self._phantom = isinstance(loopback, (tuple, list))
+        # caches (None: nothing cached; a process group replaced under the object needs all three reset)
         self._ranges = None
-        self._plan = None   # halo exchange of products along the partition (buffers included)
-        self._work = None
+        self._xplan = None  # x exchange plans per _slot
+        self._plan = None   # halo exchange plans of the work matrices, receive buffers included, per _slot
+        self._work = {}     # work matrices per _slot
         self._gbuf = self._sbuf = self._pad = self._rsout = None
         self._ops = {}
         self._segadd = None
-        self._xplan_m = self._plan_m = self._work_m = None  # mul_multi: plans and the (n, K) work matrix
 
     def out_range(self, n, rank=None):
         """Output rows (1-based, inclusive) rank `rank` holds after a product ACROSS the partition."""
@@ -386,18 +386,42 @@ class RowPartitioned:
         """physical rank behind logical rank r (loopback: every logical rank is this process)"""
         return self.rank if self._phantom else r
 
+    # Vectors and (n, K) column-major matrices take the same paths below: a vector is the K = 1 view x[:, None].  Plans and
+    # buffers are kept per (n, K, dtype, device) -- `_slot` -- so vector and matrix products do not evict each other.
+    @staticmethod
+    def _slot(t):
+        return (t.shape[0], t.shape[1], t.dtype, t.device)
+
+    @staticmethod
+    def _colmajor_like(t, rows):
+        """(rows, K) matrix whose columns are contiguous, like a column-major t"""
+        return torch.empty((t.shape[1], rows), dtype=t.dtype, device=t.device).t()
+
+    def _p2p_columns(self, pairs, op):
+        """one point-to-point descriptor per COLUMN of every (peer, matrix piece): the row slice of a column-major matrix
+        is K contiguous runs, and all of them travel in the one batch of the exchange (one grouped RCCL call)"""
+        return [dist.P2POp(op, v[:, k], self._peer(r), group=self.group) for r, v in pairs for k in range(v.shape[1])]
+
     def fetch_x(self, x):
         """x arrives PARTITIONED like y (every rank holds x[own] only, the rest of the full-length
         tensor is undefined): bring in what this rank's blocks read.  With `xneed` ranges (banded /
         symmetric operators: own range + a halo) that is one batched point-to-point exchange with the
-        owners, received straight into x; without, the all-gather of the x slices."""
+        owners, received straight into x; without, the all-gather of the x slices.  x: a vector or an
+        (n, K) column-major matrix, whose K columns travel in the same one exchange."""
         ranges = self._exchange_ranges(x.device)
         if self.world == 1 and not self.loopback:
             return x
+        X = x[:, None] if x.dim() == 1 else x
         own_ranges = [(rl, rh) for rl, rh, _, _ in ranges]
         if any(xn == (0, -1) for xn in self._xneeds):  # somebody reads everything: all-gather (collective)
-            return self._allgather(x, own_ranges)
-        if self._xplan is None or self._xplan[0] is not x:
+            self._allgather(X, own_ranges)
+            return x
+        # the descriptors point at fixed views of X: built once per piece of memory they point at (not per tensor
+        # object -- a caller passing `buf.t()` hands in a new one every step; the views keep the storage alive)
+        key = (X.data_ptr(), tuple(X.shape), X.stride(), X.dtype, X.device)
+        plans = self._xplan = self._xplan or {}
+        plan = plans.get(self._slot(X))
+        if plan is None or plan[0] != key:
             olo, ohi = self.own
             nlo, nhi = self._xneeds[self.rank]
             sends, recvs, staged = [], [], []
@@ -406,63 +430,59 @@ class RowPartitioned:
                     continue
                 a, b = max(self._xneeds[r][0], olo), min(self._xneeds[r][1], ohi)  # what rank r reads of mine
                 if a <= b:
-                    sends.append((r, x[a - 1:b]))
-                a, b = max(nlo, rlo), min(nhi, min(rhi, x.shape[0]))  # what I read of rank r's
+                    sends.append((r, X[a - 1:b]))
+                a, b = max(nlo, rlo), min(nhi, min(rhi, X.shape[0]))  # what I read of rank r's
                 if a <= b:
-                    recvs.append((r, x[a - 1:b]))
+                    recvs.append((r, X[a - 1:b]))
                     if self._phantom:
                         # the phantom owner's half of the transfer: its entries leave from a buffer of their own, and
                         # the place they are received into holds NaN until they have arrived
-                        staged.append((torch.empty_like(x[a - 1:b]), x[a - 1:b]))
+                        staged.append((self._colmajor_like(X, b - a + 1), X[a - 1:b]))
                         sends.append((r, staged[-1][0]))
-            ops = [dist.P2POp(dist.isend, v, self._peer(r), group=self.group) for r, v in sends]
-            ops += [dist.P2POp(dist.irecv, v, self._peer(r), group=self.group) for r, v in recvs]
-            self._xplan = (x, ops, staged)  # the descriptors point at fixed views of x: built once
-        ops = self._xplan[1]
+            ops = self._p2p_columns(sends, dist.isend) + self._p2p_columns(recvs, dist.irecv)
+            plan = plans[self._slot(X)] = (key, ops, staged)
+        _, ops, staged = plan
         if ops:
-            for src, view in self._xplan[2]:
+            for src, view in staged:
                 src.copy_(view)
                 view.fill_(float("nan"))
-            self._host_mediated_fence(x)
+            self._host_mediated_fence(X)
             for req in dist.batch_isend_irecv(ops):
                 req.wait()
         return x
 
-    def _workvec(self, y):
-        if self._work is None or self._work.shape != y.shape or self._work.device != y.device or \
-                self._work.dtype != y.dtype:
-            self._work = torch.zeros_like(y)
-            self._plan = None
-        return self._work
+    def _work_like(self, Y):
+        """the (n, K) column-major work matrix for products into Y (zeros when first made)"""
+        key = self._slot(Y)
+        if key not in self._work:
+            self._work[key] = self._colmajor_like(Y, Y.shape[0]).zero_()
+        return self._work[key]
 
-    def _halo_plan(self, w, ranges):
-        """Send views into the work vector and preallocated receive buffers, one pair per peer whose
-        owned rows this rank touches / that touches this rank's rows."""
-        if self._plan is None:
+    def _halo_plan(self, W, ranges):
+        """Send views into the work matrix W (`_work_like`) and preallocated receive buffers with contiguous columns,
+        one pair per peer whose owned rows this rank touches / that touches this rank's rows."""
+        plans = self._plan = self._plan or {}
+        key = self._slot(W)
+        if key not in plans:
             olo, ohi = self.own
             tlo, thi = self.touched
             sends, recvs = [], []
             for r, (rlo, rhi, rtlo, rthi) in enumerate(ranges):
                 if r == self.rank:
                     continue
-                a, b = max(tlo, rlo), min(thi, rhi)  # my contributions to rank r's rows
+                a, b = max(tlo, rlo), min(thi, rhi, W.shape[0])  # my contributions to rank r's rows
                 if a <= b:
-                    sends.append((r, w[a - 1:b]))
+                    sends.append((r, a, b))
                 a, b = max(rtlo, olo), min(rthi, ohi)  # rank r's contributions to my rows
                 if a <= b:
-                    recvs.append((r, a, b, torch.empty(b - a + 1, dtype=w.dtype, device=w.device)))
+                    recvs.append((r, a, b, self._colmajor_like(W, b - a + 1)))
             if self._phantom:
-                # the phantom owners' half: they receive what this rank produced for their rows (and add it, below)
-                n = w.shape[0]
-                sends = [(r, v) for r, v in sends if v.shape[0] > 0]
-                for r, v in sends:
-                    a = int(v.storage_offset() - w.storage_offset()) + 1
-                    recvs.append((r, a, a + v.shape[0] - 1, torch.empty_like(v)))
-                assert all(b <= n for _, _, b, _ in recvs)
-            ops = [dist.P2POp(dist.isend, v, self._peer(r), group=self.group) for r, v in sends]
-            ops += [dist.P2POp(dist.irecv, buf, self._peer(r), group=self.group) for r, _, _, buf in recvs]
-            self._plan = (ops, recvs)  # the descriptors point at fixed views / buffers: built once
-        return self._plan
+                # the phantom owners' half: they receive what this rank produced for their rows (and add it)
+                recvs += [(r, a, b, self._colmajor_like(W, b - a + 1)) for r, a, b in sends]
+            ops = self._p2p_columns([(r, W[a - 1:b]) for r, a, b in sends], dist.isend)
+            ops += self._p2p_columns([(r, buf) for r, _, _, buf in recvs], dist.irecv)
+            plans[key] = (ops, recvs)  # the descriptors point at fixed views / buffers: built once
+        return plans[key]
 
     def _phantom_rows(self, y, beta):
         """loopback=(lo, hi): the phantom neighbour's own part of a product -- it has no blocks, so its rows (everything
@@ -520,113 +540,49 @@ class RowPartitioned:
         else:
             Aop = self._local_op(op)
             lm = lambda yy, xx, a, b: M.mul(yy, Aop, xx, a, b)
-        along = self.symmetric or ((op == N_) == (self.axis == 0))
-        ranges = self._exchange_ranges(y.device)
-        if not along:
+        self._exchange_ranges(y.device)  # (its all_gather at first use comes first on every path)
+        if not (self.symmetric or ((op == N_) == (self.axis == 0))):
             return self._mul_across(y, x, alpha, beta, lm)
+        # the local product gets the vectors themselves (bsm_mul), not the (n, 1) views (bsm_mul_multi)
+        lm1 = None if lm is None else (lambda YY, XX, a, b: lm(YY[:, 0], XX[:, 0], a, b))
+        self._mul_along(y[:, None], x[:, None], alpha, beta, lm1, op)
+        return y
+
+    def _mul_along(self, Y, X, alpha, beta, lm, op=M.L.BSM_OP_N):
+        """The product ALONG the partition on (n, K) column-major Y and X (mul: K = 1), x already fetched.
+        lm(W_or_Y, X, alpha, beta): the local product, None for a rank without blocks."""
+        ranges = self._exchange_ranges(Y.device)
         # collective decision: if ANY rank touches rows it does not own, every rank takes part in
         # the exchange (a rank without a halo of its own may still receive contributions)
         halo = any((rl, rh) != (tl, th) for rl, rh, tl, th in ranges)
         olo, ohi = self.own
-        if not halo and self.axis == 0 and op == N_:
+        own_slice = slice(olo - 1, ohi) if ohi >= olo else None
+        recvs = ()
+        if not halo and self.axis == 0 and op == M.L.BSM_OP_N:
             if lm is not None:
-                lm(y, x, alpha, beta)  # rows outside `own` are left untouched by the handle
-            elif ohi >= olo:
-                self._combine(y, slice(olo - 1, ohi), 0, beta)
-            if self._phantom:
-                self._phantom_rows(y, beta)
+                lm(Y, X, alpha, beta)  # rows outside `own` are left untouched by the handle
+            elif own_slice is not None:
+                self._combine(Y, own_slice, 0, beta)
         else:
-            w = self._workvec(y)
+            W = self._work_like(Y)
             if lm is not None:
-                lm(w, x, alpha, False)  # strong zero over the touched range, then accumulate
-            elif ohi >= olo:
-                w[olo - 1:ohi] = 0
-            ops, recvs = self._halo_plan(w, ranges)
+                lm(W, X, alpha, False)  # strong zero over the touched rows, then accumulate
+            elif own_slice is not None:
+                W[own_slice] = 0
+            ops, recvs = self._halo_plan(W, ranges)
             if halo and ops:
-                self._exchange(ops, recvs, w)
-            if ohi >= olo:
-                own_slice = slice(olo - 1, ohi)
-                self._combine(y, own_slice, w[own_slice], beta)
-            if self._phantom:
-                self._phantom_rows(y, beta)
-            for _, a, b, buf in recvs:
-                y[a - 1:b] += buf
+                self._exchange(ops, recvs, W)
+            if own_slice is not None:
+                self._combine(Y, own_slice, W[own_slice], beta)
+        if self._phantom:
+            self._phantom_rows(Y, beta)
+        for _, a, b, buf in recvs:
+            Y[a - 1:b] += buf
         if self.gather and (self.world > 1 or self.loopback):
-            self._allgather(y, [(rl, rh) for rl, rh, _, _ in ranges])
-        return y
+            self._allgather(Y, [(rl, rh) for rl, rh, _, _ in ranges])
+        return Y
 
     # ---- A * X: several right-hand sides -------------------------------------------------------------------------
-    @staticmethod
-    def _colmajor_like(t, rows):
-        """(rows, K) matrix whose columns are contiguous, like a column-major t"""
-        return torch.empty((t.shape[1], rows), dtype=t.dtype, device=t.device).t()
-
-    def _p2p_columns(self, pairs, op):
-        """one point-to-point descriptor per COLUMN of every (peer, matrix piece): the row slice of a column-major matrix
-        is K contiguous runs, and all of them travel in the one batch of the exchange (one grouped RCCL call)"""
-        return [dist.P2POp(op, v[:, k], self._peer(r), group=self.group) for r, v in pairs for k in range(v.shape[1])]
-
-    def _fetch_x_multi(self, X):
-        """fetch_x for an (n, K) column-major X partitioned like the rows"""
-        ranges = self._exchange_ranges(X.device)
-        if self.world == 1 and not self.loopback:
-            return X
-        own_ranges = [(rl, rh) for rl, rh, _, _ in ranges]
-        if any(xn == (0, -1) for xn in self._xneeds):  # somebody reads everything: all-gather, column by column
-            for k in range(X.shape[1]):
-                self._allgather(X[:, k], own_ranges)
-            return X
-        if self._xplan_m is None or self._xplan_m[0] is not X:
-            olo, ohi = self.own
-            nlo, nhi = self._xneeds[self.rank]
-            sends, recvs, staged = [], [], []
-            for r, (rlo, rhi) in enumerate(own_ranges):
-                if r == self.rank:
-                    continue
-                a, b = max(self._xneeds[r][0], olo), min(self._xneeds[r][1], ohi)  # what rank r reads of mine
-                if a <= b:
-                    sends.append((r, X[a - 1:b]))
-                a, b = max(nlo, rlo), min(nhi, min(rhi, X.shape[0]))  # what I read of rank r's
-                if a <= b:
-                    recvs.append((r, X[a - 1:b]))
-                    if self._phantom:  # (see fetch_x)
-                        staged.append((self._colmajor_like(X, b - a + 1), X[a - 1:b]))
-                        sends.append((r, staged[-1][0]))
-            ops = self._p2p_columns(sends, dist.isend) + self._p2p_columns(recvs, dist.irecv)
-            self._xplan_m = (X, ops, staged)
-        ops = self._xplan_m[1]
-        if ops:
-            for src, view in self._xplan_m[2]:
-                src.copy_(view)
-                view.fill_(float("nan"))
-            self._host_mediated_fence(X)
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        return X
-
-    def _halo_plan_multi(self, W, ranges):
-        """_halo_plan for the (n, K) work matrix: send views of its rows, receive buffers with contiguous columns"""
-        if self._plan_m is None or self._plan_m[0] is not W:
-            olo, ohi = self.own
-            tlo, thi = self.touched
-            sends, recvs = [], []
-            for r, (rlo, rhi, rtlo, rthi) in enumerate(ranges):
-                if r == self.rank:
-                    continue
-                a, b = max(tlo, rlo), min(thi, min(rhi, W.shape[0]))  # my contributions to rank r's rows
-                if a <= b:
-                    sends.append((r, a, b))
-                a, b = max(rtlo, olo), min(rthi, ohi)  # rank r's contributions to my rows
-                if a <= b:
-                    recvs.append((r, a, b, self._colmajor_like(W, b - a + 1)))
-            if self._phantom:  # the phantom owners receive what this rank produced for their rows
-                for r, a, b in sends:
-                    recvs.append((r, a, b, self._colmajor_like(W, b - a + 1)))
-            ops = self._p2p_columns([(r, W[a - 1:b]) for r, a, b in sends], dist.isend)
-            ops += self._p2p_columns([(r, buf) for r, _, _, buf in recvs], dist.irecv)
-            self._plan_m = (W, ops, recvs)
-        return self._plan_m[1], self._plan_m[2]
-
     def mul_multi(self, Y, X, alpha=True, beta=False, local_mul=None, x_distributed=False):
         """Y = alpha * A * X + beta * Y for (n, K) COLUMN-major matrices (torch: `.t()` of a contiguous (K, n) tensor),
         products ALONG the partition (A * X of a row-partitioned operator, any op of a symmetric one): the local product
@@ -641,48 +597,12 @@ class RowPartitioned:
         if not (self.symmetric or self.axis == 0):
             raise ValueError("mul_multi: products along the partition only (mul() column by column runs across it)")
         if x_distributed:
-            self._fetch_x_multi(X)
-        if local_mul is not None:
-            lm = local_mul
-        elif self.local is None:
-            lm = None
-        else:
+            self.fetch_x(X)
+        lm = local_mul
+        if lm is None and self.local is not None:
             A = self.local
             lm = lambda yy, xx, a, b: M.mul(yy, A, xx, a, b)
-        ranges = self._exchange_ranges(Y.device)
-        halo = any((rl, rh) != (tl, th) for rl, rh, tl, th in ranges)
-        olo, ohi = self.own
-        own_slice = slice(olo - 1, ohi) if ohi >= olo else None
-        if not halo and self.axis == 0:
-            if lm is not None:
-                lm(Y, X, alpha, beta)  # rows outside `own` are left untouched by the handle
-            elif own_slice is not None:
-                self._combine(Y, own_slice, 0, beta)
-            if self._phantom:
-                self._phantom_rows(Y, beta)
-        else:
-            if self._work_m is None or self._work_m.shape != Y.shape or self._work_m.device != Y.device or \
-                    self._work_m.dtype != Y.dtype:
-                self._work_m = torch.zeros((Y.shape[1], Y.shape[0]), dtype=Y.dtype, device=Y.device).t()
-                self._plan_m = None
-            W = self._work_m
-            if lm is not None:
-                lm(W, X, alpha, False)  # strong zero over the touched rows, then accumulate
-            elif own_slice is not None:
-                W[own_slice] = 0
-            ops, recvs = self._halo_plan_multi(W, ranges)
-            if halo and ops:
-                self._exchange(ops, recvs, W)
-            if own_slice is not None:
-                self._combine(Y, own_slice, W[own_slice], beta)
-            if self._phantom:
-                self._phantom_rows(Y, beta)
-            for _, a, b, buf in recvs:
-                Y[a - 1:b] += buf
-        if self.gather and (self.world > 1 or self.loopback):
-            for k in range(Y.shape[1]):
-                self._allgather(Y[:, k], [(rl, rh) for rl, rh, _, _ in ranges])
-        return Y
+        return self._mul_along(Y, X, alpha, beta, lm)
 
     def mul_overlapped(self, y, x, alpha=True, beta=False, local_mul=None, interior_mul=None):
         """Forward product with x and y PARTITIONED like the rows and the exchange overlapped with the
@@ -737,14 +657,15 @@ class RowPartitioned:
         elif own_slice is not None:
             self._combine(y, own_slice, 0, beta)
         with side_ctx:
-            w = self._workvec(y)
+            W = self._work_like(y[:, None])
+            w = W[:, 0]
             if local_mul is not None:
                 local_mul(w, x, alpha, False)
             elif self.local is not None:
                 M.mul(w, self.local, x, alpha, False)  # strong zero over the rows the boundary blocks touch
-            ops, recvs = self._halo_plan(w, ranges)
+            ops, recvs = self._halo_plan(W, ranges)
             if halo and ops:
-                self._exchange(ops, recvs, w)
+                self._exchange(ops, recvs, W)
         if cuda:
             main.wait_stream(side)
         if self._phantom:
@@ -759,7 +680,7 @@ class RowPartitioned:
                 src.append(w[a - 1:b])
         for _, a, b, buf in recvs:
             dst.append(y[a - 1:b])
-            src.append(buf)
+            src.append(buf[:, 0])
         if len(dst) == 1 or not cuda or any(self._overlap(p, q) for i, p in enumerate(dst) for q in dst[i + 1:]):
             for d_, s_ in zip(dst, src):  # (two segments for the same rows must not race inside one launch)
                 d_ += s_
@@ -780,7 +701,7 @@ class RowPartitioned:
         """Every rank holds a full-length partial result: reduce-scatter onto equal chunks (or one
         all-reduce when the whole y is wanted on every rank)."""
         n = y.shape[0]
-        w = self._workvec(y)
+        w = self._work_like(y[:, None])[:, 0]
         if lm is not None:
             lm(w, x, alpha, False)
         else:
@@ -807,26 +728,28 @@ class RowPartitioned:
             self._combine(y, slice(lo - 1, hi), self._rsout[:hi - lo + 1], beta)
         return y
 
-    def _allgather(self, y, own_ranges):
-        # one all-gather of the (padded) own slices instead of one broadcast per rank: a single
-        # collective whose per-peer messages (~n/N entries) use all xGMI links at once
+    def _allgather(self, Y, own_ranges):
+        """Y (n, K), partitioned like the rows: every rank's own rows of all K columns to every rank.  One all-gather of the
+        (padded) own slices instead of one broadcast per rank or column: a single collective whose per-peer messages
+        (~K n/N entries) use all xGMI links at once"""
         if self.loopback:
-            own_ranges = own_ranges[:1]  # (the phantom roles hold their rows in this very y)
+            own_ranges = own_ranges[:1]  # (the phantom roles hold their rows in this very Y)
         maxlen = max(max(rh - rl + 1, 0) for rl, rh in own_ranges)
         if maxlen == 0:
-            return y
-        if self._gbuf is None or self._gbuf.shape[0] != self.world * maxlen or self._gbuf.device != y.device or \
-                self._gbuf.dtype != y.dtype:
-            self._gbuf = torch.empty(self.world * maxlen, dtype=y.dtype, device=y.device)
-            self._sbuf = torch.zeros(maxlen, dtype=y.dtype, device=y.device)
+            return Y
+        K = Y.shape[1]
+        if self._sbuf is None or self._sbuf.shape != (K, maxlen) or self._sbuf.device != Y.device or \
+                self._sbuf.dtype != Y.dtype:
+            self._gbuf = torch.empty((self.world, K, maxlen), dtype=Y.dtype, device=Y.device)
+            self._sbuf = torch.zeros((K, maxlen), dtype=Y.dtype, device=Y.device)
         olo, ohi = self.own
         if ohi >= olo:
-            self._sbuf[:ohi - olo + 1] = y[olo - 1:ohi]
+            self._sbuf[:, :ohi - olo + 1] = Y[olo - 1:ohi].t()
             if self.loopback:
-                y[olo - 1:ohi] = float("nan")  # comes back through the collective, or shows
-        self._host_mediated_fence(y)
-        dist.all_gather_into_tensor(self._gbuf, self._sbuf, group=self.group)
+                Y[olo - 1:ohi] = float("nan")  # comes back through the collective, or shows
+        self._host_mediated_fence(Y)
+        dist.all_gather_into_tensor(self._gbuf.view(-1), self._sbuf.view(-1), group=self.group)
         for r, (rlo, rhi) in enumerate(own_ranges):
             if (r != self.rank or self.loopback) and rhi >= rlo:
-                y[rlo - 1:rhi] = self._gbuf[r * maxlen:r * maxlen + (rhi - rlo + 1)]
-        return y
+                Y[rlo - 1:rhi] = self._gbuf[r, :, :rhi - rlo + 1].t()
+        return Y

@@ -176,16 +176,20 @@ def run(backend, port, q):
                     for k in range(K):
                         one(YY[:, k], XX[:, k], a_, b_)
                     return YY
-            for alpha, beta in combos:
-                for rep in range(2):
-                    Ym = colmajor(Y0m)
-                    P.mul_multi(Ym, Xm, alpha, beta, x_distributed=True, local_mul=hook)
-                sync()
-                a_ = 1 if alpha is True else alpha
-                got = Ym.cpu().numpy()
-                err = max(relerr(got[:, k], oracle_mul(orc, prob, N, Xf[:, k].copy(), Y0m[:, k].copy(), a_, 0 if beta is False else beta,
-                                                       strong=beta is False)) for k in range(K))
-                out.append(("%s halo, %d right-hand sides (mul_multi) %s" % (kind, K, beta), err))
+            # then with xneed=None (every x entry outside own comes from the phantom) and gather=True (ONE
+            # all_gather_into_tensor of all K columns)
+            Pg = D.RowPartitioned(A, own, touched, gather=True, symmetric=issym, xneed=None, loopback=own)
+            for Pm, what in ((P, ""), (Pg, ", xneed=None, gather=True")):
+                for alpha, beta in combos:
+                    for rep in range(2):
+                        Ym = colmajor(Y0m)
+                        Pm.mul_multi(Ym, Xm, alpha, beta, x_distributed=True, local_mul=hook)
+                    sync()
+                    a_ = 1 if alpha is True else alpha
+                    got = Ym.cpu().numpy()
+                    err = max(relerr(got[:, k], oracle_mul(orc, prob, N, Xf[:, k].copy(), Y0m[:, k].copy(), a_, 0 if beta is False else beta,
+                                                           strong=beta is False)) for k in range(K))
+                    out.append(("%s halo, %d right-hand sides (mul_multi%s) %s" % (kind, K, what, beta), err))
             assert np.array_equal(Xm.cpu().numpy(), Xf), "X must be whole again after the loopback halo"
             # ---- (d) the same with the exchange OVERLAPPED with the interior rows (what bench.py --gpus N times)
             for xmode in (("halo", "allgather") if kind != "blocksparse" else ("auto",)):

@@ -159,10 +159,11 @@ def _worker(rank, world, port, kind, q):
                     dist.all_reduce(part)
                     results.append(part.numpy().copy())
                     combos = combos + (((1, 0) if beta is False else (alpha, beta)),)
-        multi = None
+        multi = []
         if kind in ("vbcrs", "symmetric", "blocksparse", "vbcrs_tiny"):
             # A * X, three right-hand sides, X and Y (column-major) PARTITIONED like the rows: mul_multi -- one local product
-            # for all columns, the columns of every halo segment in the one batch of the exchange
+            # for all columns, the columns of every halo segment in the one batch of the exchange; xneed=None: the x
+            # all-gather, gather=True: the Y all-gather, each ONE collective for all columns
             sym = kind == "symmetric"
             K = 3
             Xf = np.stack([prob["x"] * (k + 1) + 0.25 * k for k in range(K)], axis=1)
@@ -175,26 +176,36 @@ def _worker(rank, world, port, kind, q):
                 for k in range(K):
                     local_mul(YY[:, k], XX[:, k], alpha, beta)
                 return YY
-            P = D.RowPartitioned(A, own, touched, gather=False, symmetric=sym, xneed=touched if sym else None)
-            for _ in range(2):  # second pass: cached plans and buffers
-                Xd = colmajor(np.full_like(Xf, np.nan))
+            for xneed, gather in [(touched if sym else None, False), (None, True)] + ([(None, False)] if sym else []):
+                P = D.RowPartitioned(A, own, touched, gather=gather, symmetric=sym, xneed=xneed)
+                Xbuf = torch.empty((K, n), dtype=torch.float64)
+                plans = []
+                # passes 1, 2: X = Xbuf.t(), a new tensor over the same memory each time (the x plan is kept);
+                # pass 3: other memory (the x plan is rebuilt)
+                for Xb in (Xbuf, Xbuf, torch.empty((K, n), dtype=torch.float64)):
+                    Xd = Xb.t()
+                    Xd.fill_(float("nan"))
+                    if own[1] >= own[0]:
+                        Xd[own[0] - 1:own[1]] = torch.from_numpy(Xf[own[0] - 1:own[1]])
+                    Y = colmajor(Y0)
+                    P.mul_multi(Y, Xd, 0.5, -2.0, x_distributed=True, local_mul=(multi_hook if A is not None else None))
+                    plans.append(list((P._xplan or {}).values()))
+                assert all(a is b for a, b in zip(plans[0], plans[1])), "the x plan was rebuilt for the same memory"
+                if gather:  # the whole Y on every rank
+                    multi.append((Xf, Y0, Y.numpy().copy()))
+                    continue
+                part = torch.zeros((n, K), dtype=torch.float64)
                 if own[1] >= own[0]:
-                    Xd[own[0] - 1:own[1]] = torch.from_numpy(Xf[own[0] - 1:own[1]])
-                Y = colmajor(Y0)
-                P.mul_multi(Y, Xd, 0.5, -2.0, x_distributed=True, local_mul=(multi_hook if A is not None else None))
-            part = torch.zeros((n, K), dtype=torch.float64)
-            if own[1] >= own[0]:
-                part[own[0] - 1:own[1]] = Y[own[0] - 1:own[1]]
-            dist.all_reduce(part)
-            multi = (Xf, Y0, part.numpy().copy())
+                    part[own[0] - 1:own[1]] = Y[own[0] - 1:own[1]]
+                dist.all_reduce(part)
+                multi.append((Xf, Y0, part.numpy().copy()))
         if rank == 0:
             orc = load_oracle()
             errs = []
             for (alpha, beta), got in zip(combos, results):
                 ref = oracle_mul(orc, prob, op, prob["x"], y0, alpha, beta, strong=(beta == 0))
                 errs.append(relerr(got, ref))
-            if multi is not None:
-                Xf, Y0, got = multi
+            for Xf, Y0, got in multi:
                 for k in range(Xf.shape[1]):
                     errs.append(relerr(got[:, k], oracle_mul(orc, prob, N, Xf[:, k].copy(), Y0[:, k].copy(), 0.5, -2.0, strong=False)))
             q.put(("ok", errs, own, touched))
@@ -222,6 +233,22 @@ def test_row_partitioned_over_gloo(kind, world):
     assert status == "ok", errs
     assert all(e < 1e-12 for e in errs), " ".join("%.2e" % e for e in errs)
     assert all(p.exitcode == 0 for p in procs)
+
+
+@pytest.mark.parametrize("touched", [(1, 40), (1, 48)])  # no halo: straight into y; a halo: through the work matrix
+def test_local_product_gets_vectors_from_mul_and_matrices_from_mul_multi(monkeypatch, touched):
+    """mul and mul_multi share one body on (n, K) views; the local product of mul must still see vectors (bsm_mul), not
+    (n, 1) matrices (the one-column bsm_mul_multi)"""
+    sys.path.insert(0, ROOT)
+    from bsm_amd import distributed as D
+    dims = []
+    monkeypatch.setattr(D.M, "mul", lambda yy, A, xx, a, b: dims.append((yy.dim(), xx.dim())) or yy)
+    P = D.RowPartitioned(object(), (1, 40), touched)
+    y, x = torch.zeros(48, dtype=torch.float64), torch.ones(48, dtype=torch.float64)
+    P.mul(y, x)
+    P.mul(y, x, 0.5, -2.0, x_distributed=True)
+    P.mul_multi(torch.zeros((3, 48), dtype=torch.float64).t(), torch.ones((3, 48), dtype=torch.float64).t())
+    assert dims == [(1, 1), (1, 1), (2, 2)]
 
 
 def test_partition_is_a_partition():
