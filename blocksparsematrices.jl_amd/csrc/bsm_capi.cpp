@@ -602,6 +602,15 @@ void refill_host(const Analysis &an, const RefillPlan &P, RawBuffer &values, int
     }
 }
 
+bool capturing(hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return cs != hipStreamCaptureStatusNone;
+}
+
 namespace {
 template <typename V> hipError_t upload_plan(const std::vector<V> &v, void **d) {
     if (v.empty()) return hipSuccess;
@@ -645,15 +654,6 @@ hipError_t update_setup(UpdateState &U, int nimg, int64_t nids) {
         }
     }
     return e;
-}
-
-bool capturing(hipStream_t st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return cs != hipStreamCaptureStatusNone;
 }
 
 // item list of a subset update for image k at `out`: the items of every updated id; returns its length
@@ -1447,12 +1447,7 @@ struct WorkspaceClaim {
         : A(A_), st(st_), lock(A_->gather_mu, std::defer_lock) {
         held = img.d_ws != nullptr && lock.try_lock();
         if (!held) return;
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
-            (void)hipGetLastError();
-            cs = hipStreamCaptureStatusNone;
-        }
-        if (cs != hipStreamCaptureStatusNone) {
+        if (capturing(st)) {
             // a captured product would use the workspace at every replay, on whatever stream, beside eager
             // products nobody can order against: captured products take the atomic path
             held = track = false;
@@ -1478,6 +1473,23 @@ struct WorkspaceClaim {
     }
 };
 
+bool bsm::il_reserve(ILWork &il, long long need) {
+    if (il.rows >= need) return true;
+    if (il.xr) (void)hipFree(il.xr);
+    if (il.w) (void)hipFree(il.w);
+    il = ILWork{};
+    void *xr = nullptr, *w = nullptr;
+    if (hipMalloc(&xr, (size_t)need * 128) != hipSuccess || hipMalloc(&w, (size_t)need * 128) != hipSuccess) {
+        (void)hipGetLastError();
+        if (xr) (void)hipFree(xr);
+        return false;
+    }
+    il.xr = xr;
+    il.w = w;
+    il.rows = need;
+    return true;
+}
+
 // The work arrays of the interleaved multi-RHS pass (Xr, W: 128 bytes per vector entry each) belong to the handle like the
 // gather workspace, with the same rules: one product in flight -- a racing thread, a predecessor that may still run on
 // ANOTHER stream, or a stream under graph capture do not get the claim and their product takes the ordinary kernels.
@@ -1489,13 +1501,7 @@ struct ILClaim {
     bool held = false;
     ILClaim(bsm_matrix_s *A_, const DeviceImage &img, bool opT, long long nrhs, hipStream_t st_)
         : A(A_), st(st_), lock(A_->il_mu, std::defer_lock) {
-        if (!il_applies(img, opT, nrhs) || !lock.try_lock()) return;
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
-            (void)hipGetLastError();
-            cs = hipStreamCaptureStatusNone;
-        }
-        if (cs != hipStreamCaptureStatusNone) return;
+        if (!il_applies(img, opT, nrhs) || !lock.try_lock() || capturing(st)) return;
         if (A->il_pending && A->il_stream != st) {  // the stream changed: is the previous one idle?
             const hipError_t q = hipStreamQuery(A->il_stream);
             if (q != hipSuccess) {
@@ -1506,22 +1512,10 @@ struct ILClaim {
             A->il_pending = false;
         }
         const long long need = std::max(img.nrows, img.ncols);
-        if (A->il.rows < need) {
+        if (A->il.rows < need) {  // a regrow frees the arrays the previous claim's product may still read
             if (A->il_pending && hipStreamSynchronize(A->il_stream) != hipSuccess) (void)hipGetLastError();
             A->il_pending = false;
-            if (A->il.xr) (void)hipFree(A->il.xr);
-            if (A->il.w) (void)hipFree(A->il.w);
-            A->il = ILWork{};
-            void *xr = nullptr, *w = nullptr;
-            if (hipMalloc(&xr, (size_t)need * 128) != hipSuccess || hipMalloc(&w, (size_t)need * 128) != hipSuccess) {
-                (void)hipGetLastError();
-                if (xr) (void)hipFree(xr);
-                return;  // no memory for the work arrays: the ordinary kernels need none
-            }
-            A->il.xr = xr;
-            A->il.w = w;
-            A->il.rows = need;
-            A->il.w_clean = false;
+            if (!il_reserve(A->il, need)) return;  // no memory for the work arrays: the ordinary kernels need none
         }
         held = true;
     }

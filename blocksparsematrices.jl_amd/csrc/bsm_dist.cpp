@@ -80,21 +80,8 @@ struct Part {
 // the part's work arrays if its image / this product take the interleaved pass (and they can be had), else null
 static ILWork *part_il(Part &pt, bool opT, int K) {
     if (pt.il_failed || !il_applies(pt.img, opT, K)) return nullptr;
-    const long long need = std::max(pt.img.nrows, pt.img.ncols);
-    if (pt.il.rows < need) {
-        void *xr = nullptr, *w = nullptr;
-        if (hipMalloc(&xr, (size_t)need * 128) != hipSuccess || hipMalloc(&w, (size_t)need * 128) != hipSuccess) {
-            (void)hipGetLastError();
-            if (xr) (void)hipFree(xr);
-            pt.il_failed = true;
-            return nullptr;
-        }
-        pt.il.xr = xr;
-        pt.il.w = w;
-        pt.il.rows = need;
-        pt.il.w_clean = false;
-    }
-    return &pt.il;
+    pt.il_failed = !il_reserve(pt.il, std::max(pt.img.nrows, pt.img.ncols));
+    return pt.il_failed ? nullptr : &pt.il;
 }
 
 // One persistent thread per part, bound to the part's device once.  run(f) executes f(p) on every
@@ -533,8 +520,19 @@ int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t n
     return BSM_OK;
 }
 
-// part buffers for K columns (grow-only).  EVERY part's stream is drained before ANY buffer goes: a peer may
-// still be reading this part's work vector.
+// Waits for everything queued on the devices of the parts: every device is drained whatever fails, the first error is
+// returned.
+static hipError_t drain_devices(DistState &D) {
+    hipError_t first = hipSuccess;
+    for (auto &pt : D.parts) {
+        DeviceGuard g;
+        hipError_t e = g.enter(pt->device);
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (first == hipSuccess) first = e;
+    }
+    return first;
+}
+
 // Waits until nothing of any earlier product of the handle can still be running (or reading a part's buffers).
 static hipError_t drain_handle(DistState &D) {
     const int P = (int)D.parts.size();
@@ -550,16 +548,13 @@ static hipError_t drain_handle(DistState &D) {
     // buffers, so every part's ev_done has to be reached too before the first buffer is freed
     if (D.produced && D.last_mode == 0)
         for (int p = 0; p < P && e == hipSuccess; p++) e = hipEventSynchronize(D.parts[p]->ev_done);
-    if (D.produced && D.last_mode >= 1) {  // ordered by flags / by one stream: no event carries the last use -- drain the devices
-        for (int p = 0; p < P && e == hipSuccess; p++) {
-            DeviceGuard g;
-            e = g.enter(D.parts[p]->device);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
-    }
+    // ordered by flags / by one stream: no event carries the last use -- drain the devices
+    if (e == hipSuccess && D.produced && D.last_mode >= 1) e = drain_devices(D);
     return e;
 }
 
+// part buffers for K columns (grow-only).  EVERY part's stream is drained before ANY buffer goes: a peer may
+// still be reading this part's work vector.
 static hipError_t grow_buffers(DistState &D, int K) {
     if (K <= D.kcap) return hipSuccess;
     const int P = (int)D.parts.size();
@@ -582,6 +577,95 @@ static hipError_t grow_buffers(DistState &D, int K) {
     if (e == hipSuccess) D.kcap = K;
     for (auto &pt : D.parts) pt->w_clean = false;
     return e;
+}
+
+// "x and y are ready" on a caller's stream on device `sdev`: one event per device, created at its first use
+static hipError_t ready_event(DistState &D, int sdev, hipEvent_t *ev) {
+    auto it = D.ev_x.find(sdev);
+    if (it == D.ev_x.end()) {
+        DeviceGuard g;
+        hipError_t e = g.enter(sdev);
+        hipEvent_t created = nullptr;
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&created, hipEventDisableTiming);
+        if (e != hipSuccess) return e;
+        it = D.ev_x.emplace(sdev, created).first;
+    }
+    *ev = it->second;
+    return hipSuccess;
+}
+
+// (in a function that returns a bsm status and has `hipError_t e` in scope)
+#define DCHECK(call, what)                             \
+    do {                                               \
+        e = (call);                                    \
+        if (e != hipSuccess) return hip_fail(e, what); \
+    } while (0)
+
+// test hook (unexported in the header, like bsm_debug_move_image_array): the n-th fan-out from now fails between its two
+// phases, the way a launch error would (tests/test_gpu_multidevice.py: the product after it must not hang)
+static std::atomic<int> g_fail_countdown{-1};
+extern "C" void bsm_debug_dist_fail_after(int n) { g_fail_countdown.store(n); }
+static bool injected_failure() {
+    int c = g_fail_countdown.load();
+    if (c < 0) return false;
+    return g_fail_countdown.fetch_sub(1) == 0;
+}
+
+// The frame of every product of a multi-device handle.  The drivers (dist_mul_fused, dist_mul_copies) supply only what
+// differs between them: what they issue ahead of the parts (before), the work of a part in each phase (phase), and what
+// follows once every part's work has been issued (after).
+//  - The part buffers are grown to K columns.
+//  - mode: how the product is ordered -- 0 events, 1 flags, 2 nothing at all (every part AND the caller's vectors on the
+//    stream `single` of one device: stream order is the order).  The forms do not see each other: a change of form (e.g.
+//    the copy path of a host vector in between), or mode 2 on another stream, drains every device first.
+//  - The issue of every part's work is two phases with a host barrier in between (a stream can only wait for an event or
+//    a counter value that HAS been written): phase(0, p, bind) for every part, then phase(1, p, bind).  Run inline by
+//    the calling thread (bind: enter the part's device first), or from five parts on by one persistent worker thread
+//    per device, bound to it once (the host-side issue cost no longer grows with the number of GPUs).
+// What is left behind when a fan-out fails half-way: events degrade by themselves (an event that was never recorded
+// counts as complete); sequence counters do not: the failed product has consumed a number, wait packets for it may
+// already be queued, and the write packets that would release them were never issued -- the next product's previous()
+// would wait for flag >= seq forever and the drain of a mode change would block the host.  So on any error the host
+// writes the product's number into every counter (coherent pinned memory: the queued waits fall through), drains the
+// devices and leaves the handle as after create: no ordering form remembered, no delivery to wait for, work vectors
+// "unknown" (the next fused product clears them once).
+static int fan_out(DistState &D, int K, int mode, hipStream_t single, const std::function<int()> &before,
+                   const std::function<int(int, int, bool)> &phase, const std::function<int()> &after) {
+    const int P = (int)D.parts.size();
+    auto issue = [&]() -> int {
+        hipError_t e = hipSuccess;
+        DCHECK(grow_buffers(D, K), "multi-device buffers");
+        if (D.last_mode >= 0 && (D.last_mode != mode || (mode == 2 && D.last_single_stream != single)))
+            DCHECK(drain_devices(D), "hipDeviceSynchronize");
+        D.last_mode = mode;
+        D.last_single_stream = mode == 2 ? single : nullptr;
+        int rc = before();
+        for (int ph = 0; ph < 2 && rc == BSM_OK; ph++) {
+            if (ph == 1 && injected_failure()) return hip_fail(hipErrorUnknown, "injected failure between the phases of a fan-out");
+            if (D.workers)
+                rc = D.workers->run([&](int p) { return phase(ph, p, false); });
+            else
+                for (int p = 0; p < P && rc == BSM_OK; p++) rc = phase(ph, p, true);
+        }
+        if (rc != BSM_OK) return rc;
+        D.produced = true;
+        return after();
+    };
+    const int rc = issue();
+    if (rc == BSM_OK) return rc;
+    if (D.flags) {
+        volatile uint64_t *F = D.flags;
+        for (int i = 0; i < 3 * P + 1; i++)
+            if (F[i] < D.seq) F[i] = D.seq;
+        __sync_synchronize();
+    }
+    (void)drain_devices(D);
+    (void)hipGetLastError();
+    for (auto &pt : D.parts) pt->w_clean = false;
+    D.last_mode = -1;
+    D.last_single_stream = nullptr;
+    D.produced = false;
+    return rc;
 }
 
 // ---- the fused path: device-resident vectors, every device of the context peer-accessible ----------------
@@ -608,54 +692,9 @@ struct VecDest {
     int ready_flag = -1;
 };
 
-static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<VecSource> &src, long long ldx,
-                                const std::vector<VecDest> &dst, long long ldy, const void *alpha, const void *beta,
-                                int beta_strong_zero);
-
-// test hook (unexported in the header, like bsm_debug_move_image_array): the n-th fused fan-out from now fails between
-// its two phases, the way a launch error would (tests/test_gpu_multidevice.py: the product after it must not hang)
-static std::atomic<int> g_fail_countdown{-1};
-extern "C" void bsm_debug_dist_fail_after(int n) { g_fail_countdown.store(n); }
-static bool injected_failure() {
-    int c = g_fail_countdown.load();
-    if (c < 0) return false;
-    return g_fail_countdown.fetch_sub(1) == 0;
-}
-
-// The fan-out, and what is left behind when it fails half-way.  Events degrade by themselves (an event that was never
-// recorded counts as complete); sequence counters do not: the failed product has consumed a number, wait packets for it
-// may already be queued, and the write packets that would release them were never issued -- the next product's
-// previous() would wait for flag >= seq forever and the drain of a mode change would block the host.  So on any error
-// the host writes the product's number into every counter (coherent pinned memory: the queued waits fall through),
-// drains the devices and leaves the handle as after create: no ordering form remembered, no delivery to wait for, work
-// vectors "unknown" (the next fused product clears them once).
 static int dist_mul_fused(DistState &D, int op, int K, const std::vector<VecSource> &src, long long ldx,
                           const std::vector<VecDest> &dst, long long ldy, const void *alpha, const void *beta,
                           int beta_strong_zero) {
-    const int rc = dist_mul_fused_issue(D, op, K, src, ldx, dst, ldy, alpha, beta, beta_strong_zero);
-    if (rc == BSM_OK) return rc;
-    const int P = (int)D.parts.size();
-    if (D.flags) {
-        volatile uint64_t *F = D.flags;
-        for (int i = 0; i < 3 * P + 1; i++)
-            if (F[i] < D.seq) F[i] = D.seq;
-        __sync_synchronize();
-    }
-    for (int p = 0; p < P; p++) {
-        DeviceGuard g;
-        if (g.enter(D.parts[p]->device) == hipSuccess) (void)hipDeviceSynchronize();
-        (void)hipGetLastError();
-        D.parts[p]->w_clean = false;
-    }
-    D.last_mode = -1;
-    D.last_single_stream = nullptr;
-    D.produced = false;
-    return rc;
-}
-
-static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<VecSource> &src, long long ldx,
-                                const std::vector<VecDest> &dst, long long ldy, const void *alpha, const void *beta,
-                                int beta_strong_zero) {
     const int P = (int)D.parts.size();
     const bool along = (op == BSM_OP_N) || D.symmetric;
     const Plan &pl = along ? D.plan_n : D.plan_t;
@@ -663,13 +702,6 @@ static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<V
     const bool conj = (op == BSM_OP_C);
     const size_t es = (size_t)D.es;
     const size_t vlen = D.vlen;
-    hipError_t e = hipSuccess;
-#define DCHECK(call, what)                             \
-    do {                                               \
-        e = (call);                                    \
-        if (e != hipSuccess) return hip_fail(e, what); \
-    } while (0)
-    DCHECK(grow_buffers(D, K), "multi-device buffers");
     // The stream a part's work is issued on.  bsm_mul_parts: the caller's stream of that part -- local work needs
     // no cross-stream hop at all, only what depends on a PEER waits for an event.  bsm_mul: the first part that
     // lives on the caller's device works on the caller's stream for the same reason (the hops of the other
@@ -699,17 +731,6 @@ static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<V
     for (const VecDest &d : dst) single = single && d.stream == run[0] && d.sdev == D.parts[0]->device;
     const bool flags = D.use_flags && several_streams;
     const int mode = single ? 2 : (flags ? 1 : 0);
-    if (D.last_mode >= 0 && (D.last_mode != mode || (single && D.last_single_stream != run[0]))) {
-        // the previous product of the handle was ordered the other way (events / flags, e.g. the copy path of a host
-        // vector in between): the two forms do not see each other, so everything is drained once
-        for (int p = 0; p < P; p++) {
-            DeviceGuard g;
-            DCHECK(g.enter(D.parts[p]->device), "hipSetDevice");
-            DCHECK(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        }
-    }
-    D.last_mode = mode;
-    D.last_single_stream = single ? run[0] : nullptr;
     // (the counters only ever hold numbers of products ordered by flags: a product ordered by events in between must not
     // consume one, or the next one would wait for a value nobody writes)
     const uint64_t prev_seq = D.seq;
@@ -726,7 +747,8 @@ static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<V
         return flags ? hipStreamWaitValue64(st, F + flag, value, hipStreamWaitValueGte, kAll) : hipStreamWaitEvent(st, ev, 0);
     };
     // "x (and the incoming y) are ready" on every stream that produces them
-    {
+    auto before = [&]() -> int {
+        hipError_t e = hipSuccess;
         std::vector<std::pair<hipEvent_t, int>> done;
         auto record = [&](hipEvent_t ev, int flag, hipStream_t st, int dev) -> hipError_t {
             for (const auto &d : done)
@@ -738,8 +760,8 @@ static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<V
         };
         for (const VecSource &s : src) DCHECK(record(s.ready, s.ready_flag, s.stream, s.sdev), "record: inputs ready");
         for (const VecDest &d : dst) DCHECK(record(d.ready, d.ready_flag, d.stream, d.sdev), "record: inputs ready");
-    }
-    const bool was_produced = D.produced;
+        return BSM_OK;
+    };
     const bool rezero = D.rezero;  // this product leaves the work vectors it uses zero again
     static const float kOneF[2] = {1.f, 0.f};
     static const double kOneD[2] = {1.0, 0.0};
@@ -774,10 +796,10 @@ static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<V
         if (ph == 0) {
             // peers that read this part's work vector in the previous product have finished (their ev_done
             // carries that product's record until phase 1 of THIS product re-records it, after a host barrier)
-            if (was_produced && !single) {
-                // (flags: the previous product's number; a first fused product after copy-path ones was drained above.
-                // Every wait is a packet in front of the product: each delivery once, and none for a delivery that was
-                // recorded on this very stream)
+            if (D.produced && !single) {
+                // (flags: the previous product's number; a first fused product after copy-path ones was drained by
+                // fan_out.  Every wait is a packet in front of the product: each delivery once, and none for a delivery
+                // that was recorded on this very stream)
                 std::vector<int> waited;
                 auto previous = [&](int q) -> hipError_t {
                     const Part &pq = *D.parts[q];
@@ -872,35 +894,39 @@ static int dist_mul_fused_issue(DistState &D, int op, int K, const std::vector<V
         pt.done_stream = st;
         return BSM_OK;
     };
-    for (int ph = 0; ph < 2; ph++) {
-        int rc = BSM_OK;
-        if (ph == 1 && injected_failure()) return hip_fail(hipErrorUnknown, "injected failure between the phases of a fan-out");
-        if (D.workers)
-            rc = D.workers->run([&](int p) { return phase(ph, p, false); });
-        else
-            for (int p = 0; p < P && rc == BSM_OK; p++) rc = phase(ph, p, true);
-        if (rc != BSM_OK) return rc;
-    }
-    D.produced = true;
-    for (int p = 0; p < P; p++)
-        if (!direct[p]) D.parts[p]->w_clean = rezero;
-    // the consumers of y continue when the parts that deliver to them are done
-    for (int q = 0; q < P; q++) {
-        const VecDest &yd = dst[dst.size() == 1 ? 0 : (size_t)q];
-        if (yd.stream == run[(size_t)q] && yd.sdev == D.parts[q]->device) continue;  // delivered on the consumer's own stream
-        DeviceGuard g;
-        DCHECK(g.enter(yd.sdev), "hipSetDevice");
-        DCHECK(await(yd.stream, D.parts[q]->ev_done, 2 * P + q, seq), "wait: delivery");
-    }
-#undef DCHECK
-    return BSM_OK;
+    auto after = [&]() -> int {
+        hipError_t e = hipSuccess;
+        for (int p = 0; p < P; p++)
+            if (!direct[p]) D.parts[p]->w_clean = rezero;
+        // the consumers of y continue when the parts that deliver to them are done
+        for (int q = 0; q < P; q++) {
+            const VecDest &yd = dst[dst.size() == 1 ? 0 : (size_t)q];
+            if (yd.stream == run[(size_t)q] && yd.sdev == D.parts[q]->device) continue;  // delivered on the consumer's own stream
+            DeviceGuard g;
+            DCHECK(g.enter(yd.sdev), "hipSetDevice");
+            DCHECK(await(yd.stream, D.parts[q]->ev_done, 2 * P + q, seq), "wait: delivery");
+        }
+        return BSM_OK;
+    };
+    return fan_out(D, K, mode, run[0], before, phase, after);
 }
 
+// a bsm_mul / bsm_mul_multi call, resolved once for whichever driver runs it
+struct Call {
+    bool host;               // BSM_MEM_HOST (else BSM_MEM_DEVICE)
+    int xdev, ydev, sdev;    // where x, y and the caller's stream live (host vectors: -1, -1, the current device)
+    hipStream_t stream;
+    hipEvent_t ready;        // device vectors: "x and y are ready" on `stream` (ready_event), recorded by the driver
+};
+
+// ---- the copy path: host vectors, devices without peer access, BSM_DIST_COPIES=1 ----------------------------
 // K <= 16 right-hand sides in one fan-out (K = 1: bsm_mul).  X / Y: column k at x + k * ldx / y + k * ldy
-// elements.  The part buffers hold column k at k * vlen elements.
-static int dist_mul_copies(bsm_matrix_s *A, int op, int K, const void *x, long long ldx, void *y, long long ldy,
-                           const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream) {
-    DistState &D = *A->dist;
+// elements.  The part buffers hold column k at k * vlen elements.  One stream per device:
+//   phase 0 (part p): x to its device, local product, record ev_prod
+//   phase 1 (part q): the y segments other parts produced for q's rows (peer copy over xGMI + add),
+//                     then q's owned range to the caller's y, record ev_done
+static int dist_mul_copies(DistState &D, int op, int K, const void *x, long long ldx, void *y, long long ldy,
+                           const void *alpha, const void *beta, int beta_strong_zero, const Call &c) {
     const int P = (int)D.parts.size();
     const bool along = (op == BSM_OP_N) || D.symmetric;
     const Plan &pl = along ? D.plan_n : D.plan_t;
@@ -913,79 +939,37 @@ static int dist_mul_copies(bsm_matrix_s *A, int op, int K, const void *x, long l
     const size_t vlen = D.vlen;  // elements per column of the part buffers
     const char *xb = (const char *)x;
     char *yb = (char *)y;
-    const bool host = (memspace == BSM_MEM_HOST);
-    if (!host && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-    hipError_t e = hipSuccess;
-#define DCHECK(call, what)                        \
-    do {                                          \
-        e = (call);                               \
-        if (e != hipSuccess) return hip_fail(e, what); \
-    } while (0)
-
-    DCHECK(grow_buffers(D, K), "multi-device buffers");
-    if (D.last_mode >= 1) {  // the previous product was ordered by flags (or by one stream), this path orders by events: drain once
-        for (int p = 0; p < P; p++) {
-            DeviceGuard g;
-            DCHECK(g.enter(D.parts[p]->device), "hipSetDevice");
-            DCHECK(hipDeviceSynchronize(), "hipDeviceSynchronize");
-        }
-    }
-    D.last_mode = 0;
-    for (auto &pt : D.parts) pt->w_clean = false;  // (this path leaves its partial sums in the work vectors)
-    int cur = 0;
-    DCHECK(hipGetDevice(&cur), "hipGetDevice");
-    int xdev = -1, ydev = -1, sdev = cur;
-    hipEvent_t ev_ready = nullptr;
-    if (!host) {
-        xdev = pointer_device(x, cur);
-        ydev = pointer_device(y, cur);
-        if (stream) {
-            int sd = cur;
-            if (hipStreamGetDevice(stream, &sd) == hipSuccess) sdev = sd;
-            else (void)hipGetLastError();
-        }
-        auto it = D.ev_x.find(sdev);
-        if (it == D.ev_x.end()) {
-            DeviceGuard g;
-            DCHECK(g.enter(sdev), "hipSetDevice");
-            hipEvent_t ev;
-            DCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-            it = D.ev_x.emplace(sdev, ev).first;
-        }
-        ev_ready = it->second;
-        DeviceGuard g;
-        DCHECK(g.enter(sdev), "hipSetDevice");
-        DCHECK(hipEventRecord(ev_ready, stream), "hipEventRecord");  // x (and the incoming y) are ready
-    }
+    const bool host = c.host;
     const bool numeric_beta = !beta_strong_zero;
     const size_t res_need = (size_t)ylen * es * K;  // staging of numeric-beta results: column k at k * ylen
-    if (numeric_beta && host && D.h_res.size() < res_need) D.h_res.resize(res_need);
-    if (numeric_beta && !host) {
-        bool remote = false;
-        for (int q = 0; q < P; q++) remote |= (!pl.out[q].empty() && D.parts[q]->device != ydev);
-        if (remote && (D.res_dev != ydev || D.res_bytes < res_need)) {
-            if (D.d_res) {
-                DeviceGuard g;
-                (void)g.enter(D.res_dev);
-                (void)hipFree(D.d_res);
-                D.d_res = nullptr;
-            }
+    auto before = [&]() -> int {
+        hipError_t e = hipSuccess;
+        for (auto &pt : D.parts) pt->w_clean = false;  // (this path leaves its partial sums in the work vectors)
+        if (!host) {
             DeviceGuard g;
-            DCHECK(g.enter(ydev), "hipSetDevice");
-            DCHECK(hipMalloc(&D.d_res, res_need + 16), "hipMalloc(result staging)");
-            D.res_dev = ydev;
-            D.res_bytes = res_need;
+            DCHECK(g.enter(c.sdev), "hipSetDevice");
+            DCHECK(hipEventRecord(c.ready, c.stream), "hipEventRecord");  // x (and the incoming y) are ready
         }
-    }
-
-    // The issue of every part's work -- one stream per device -- is two phases with a host barrier in
-    // between (a stream can only wait for an event that HAS been recorded):
-    //   phase 0 (part p): x to its device, local product, record ev_prod
-    //   phase 1 (part q): the y segments other parts produced for q's rows (peer copy over xGMI + add),
-    //                     then q's owned range to the caller's y, record ev_done
-    // Run inline by the calling thread for up to two parts, by one persistent worker thread per device
-    // beyond that (each bound to its device once: the host-side issue cost no longer grows with the
-    // number of GPUs).
+        if (numeric_beta && host && D.h_res.size() < res_need) D.h_res.resize(res_need);
+        if (numeric_beta && !host) {
+            bool remote = false;
+            for (int q = 0; q < P; q++) remote |= (!pl.out[q].empty() && D.parts[q]->device != c.ydev);
+            if (remote && (D.res_dev != c.ydev || D.res_bytes < res_need)) {
+                if (D.d_res) {
+                    DeviceGuard g;
+                    (void)g.enter(D.res_dev);
+                    (void)hipFree(D.d_res);
+                    D.d_res = nullptr;
+                }
+                DeviceGuard g;
+                DCHECK(g.enter(c.ydev), "hipSetDevice");
+                DCHECK(hipMalloc(&D.d_res, res_need + 16), "hipMalloc(result staging)");
+                D.res_dev = c.ydev;
+                D.res_bytes = res_need;
+            }
+        }
+        return BSM_OK;
+    };
     std::vector<char> late_flag((size_t)P, 0);  // numeric beta, remote part, y on a device: combined below
     auto phase = [&](int ph, int p, bool bind) -> int {
         hipError_t e = hipSuccess;  // (per invocation: the phases of different parts run concurrently)
@@ -999,13 +983,13 @@ static int dist_mul_copies(bsm_matrix_s *A, int op, int K, const void *x, long l
                 for (int q = 0; q < P; q++) DCHECK(hipStreamWaitEvent(pt.stream, D.parts[q]->ev_done, 0), "hipStreamWaitEvent");
                 if (D.ev_tail) DCHECK(hipStreamWaitEvent(pt.stream, D.ev_tail, 0), "hipStreamWaitEvent");
             }
-            if (ev_ready) DCHECK(hipStreamWaitEvent(pt.stream, ev_ready, 0), "hipStreamWaitEvent");
+            if (c.ready) DCHECK(hipStreamWaitEvent(pt.stream, c.ready, 0), "hipStreamWaitEvent");
             const Range zr = pl.zr[p];
             if (pt.has_image) {
                 const Range xr = pl.xr[p];
                 const void *xp = pt.d_x;
                 long long xld = (long long)vlen;
-                if (!host && xdev == pt.device) {
+                if (!host && c.xdev == pt.device) {
                     xp = x;  // same device: the local product reads the caller's x directly
                     xld = ldx;
                 } else {
@@ -1015,7 +999,7 @@ static int dist_mul_copies(bsm_matrix_s *A, int op, int K, const void *x, long l
                         if (host)
                             DCHECK(hipMemcpyAsync(dst, src, (size_t)xr.len() * es, hipMemcpyHostToDevice, pt.stream), "x upload");
                         else
-                            DCHECK(copy_between(dst, pt.device, src, xdev, (size_t)xr.len() * es, pt.stream), "x peer copy");
+                            DCHECK(copy_between(dst, pt.device, src, c.xdev, (size_t)xr.len() * es, pt.stream), "x peer copy");
                     }
                 }
                 const long long z[2] = {zr.lo, zr.hi};
@@ -1059,11 +1043,11 @@ static int dist_mul_copies(bsm_matrix_s *A, int op, int K, const void *x, long l
                     char *dst = numeric_beta ? D.h_res.data() + roff : yk;
                     DCHECK(hipMemcpyAsync(dst, w, bytes, hipMemcpyDeviceToHost, pt.stream), "y download");
                 } else if (!numeric_beta) {
-                    DCHECK(copy_between(yk, ydev, w, pt.device, bytes, pt.stream), "y peer copy");
-                } else if (pt.device == ydev) {
+                    DCHECK(copy_between(yk, c.ydev, w, pt.device, bytes, pt.stream), "y peer copy");
+                } else if (pt.device == c.ydev) {
                     DCHECK(launch_vec_axpby(D.dtype, yk, w, o.len(), beta, pt.stream), "y combine");
                 } else {
-                    DCHECK(copy_between((char *)D.d_res + roff, ydev, w, pt.device, bytes, pt.stream), "y peer copy");
+                    DCHECK(copy_between((char *)D.d_res + roff, c.ydev, w, pt.device, bytes, pt.stream), "y peer copy");
                     late_flag[p] = 1;
                 }
             }
@@ -1071,123 +1055,107 @@ static int dist_mul_copies(bsm_matrix_s *A, int op, int K, const void *x, long l
         DCHECK(hipEventRecord(pt.ev_done, pt.stream), "hipEventRecord");
         return BSM_OK;
     };
-    for (int ph = 0; ph < 2; ph++) {
-        int rc = BSM_OK;
-        if (ph == 1 && injected_failure()) return hip_fail(hipErrorUnknown, "injected failure between the phases of a fan-out");
-        if (D.workers)
-            rc = D.workers->run([&](int p) { return phase(ph, p, false); });
-        else
-            for (int p = 0; p < P && rc == BSM_OK; p++) rc = phase(ph, p, true);
-        if (rc != BSM_OK) return rc;
-    }
-    D.produced = true;
-    if (host) {
-        for (int q = 0; q < P; q++) {
-            Part &pt = *D.parts[q];
-            DeviceGuard g;
-            DCHECK(g.enter(pt.device), "hipSetDevice");
-            DCHECK(hipStreamSynchronize(pt.stream), "multi-device mul");
-        }
-        if (numeric_beta) {
+    auto after = [&]() -> int {
+        hipError_t e = hipSuccess;
+        if (host) {
             for (int q = 0; q < P; q++) {
-                const Range o = pl.out[q];
-                if (o.empty()) continue;
-                for (int k = 0; k < K; k++) {
-                    char *yk = yb + ((size_t)k * ldy + o.lo) * es;
-                    const char *rk = D.h_res.data() + ((size_t)k * ylen + o.lo) * es;
-                    switch (D.dtype) {
-                        case BSM_F32: host_axpby((float *)yk, (const float *)rk, o.len(), *(const float *)beta); break;
-                        case BSM_F64: host_axpby((double *)yk, (const double *)rk, o.len(), *(const double *)beta); break;
-                        case BSM_C64: host_axpby((std::complex<float> *)yk, (const std::complex<float> *)rk, o.len(), *(const std::complex<float> *)beta); break;
-                        default: host_axpby((std::complex<double> *)yk, (const std::complex<double> *)rk, o.len(), *(const std::complex<double> *)beta); break;
+                Part &pt = *D.parts[q];
+                DeviceGuard g;
+                DCHECK(g.enter(pt.device), "hipSetDevice");
+                DCHECK(hipStreamSynchronize(pt.stream), "multi-device mul");
+            }
+            if (numeric_beta) {
+                for (int q = 0; q < P; q++) {
+                    const Range o = pl.out[q];
+                    if (o.empty()) continue;
+                    for (int k = 0; k < K; k++) {
+                        char *yk = yb + ((size_t)k * ldy + o.lo) * es;
+                        const char *rk = D.h_res.data() + ((size_t)k * ylen + o.lo) * es;
+                        switch (D.dtype) {
+                            case BSM_F32: host_axpby((float *)yk, (const float *)rk, o.len(), *(const float *)beta); break;
+                            case BSM_F64: host_axpby((double *)yk, (const double *)rk, o.len(), *(const double *)beta); break;
+                            case BSM_C64: host_axpby((std::complex<float> *)yk, (const std::complex<float> *)rk, o.len(), *(const std::complex<float> *)beta); break;
+                            default: host_axpby((std::complex<double> *)yk, (const std::complex<double> *)rk, o.len(), *(const std::complex<double> *)beta); break;
+                        }
                     }
                 }
             }
+            return BSM_OK;
         }
-        return BSM_OK;
-    }
-    // y on a device: the caller's stream continues when every part has delivered
-    {
-        DeviceGuard g;
-        DCHECK(g.enter(sdev), "hipSetDevice");
-        for (int q = 0; q < P; q++) DCHECK(hipStreamWaitEvent(stream, D.parts[q]->ev_done, 0), "hipStreamWaitEvent");
-    }
-    bool any_late = false;
-    for (int q = 0; q < P; q++) any_late |= late_flag[q] != 0;
-    if (any_late) {
-        DeviceGuard g;
-        DCHECK(g.enter(ydev), "hipSetDevice");
-        for (int q = 0; q < P; q++) {
-            if (!late_flag[q]) continue;
-            const Range o = pl.out[q];
-            for (int k = 0; k < K; k++)
-                DCHECK(launch_vec_axpby(D.dtype, yb + ((size_t)k * ldy + o.lo) * es,
-                                        (char *)D.d_res + ((size_t)k * ylen + o.lo) * es, o.len(), beta, stream), "y combine");
+        // y on a device: the caller's stream continues when every part has delivered
+        {
+            DeviceGuard g;
+            DCHECK(g.enter(c.sdev), "hipSetDevice");
+            for (int q = 0; q < P; q++) DCHECK(hipStreamWaitEvent(c.stream, D.parts[q]->ev_done, 0), "hipStreamWaitEvent");
         }
-    }
-    {  // the end of this product on the caller's stream: what the next product of the handle waits for
+        bool any_late = false;
+        for (int q = 0; q < P; q++) any_late |= late_flag[q] != 0;
+        if (any_late) {
+            DeviceGuard g;
+            DCHECK(g.enter(c.ydev), "hipSetDevice");
+            for (int q = 0; q < P; q++) {
+                if (!late_flag[q]) continue;
+                const Range o = pl.out[q];
+                for (int k = 0; k < K; k++)
+                    DCHECK(launch_vec_axpby(D.dtype, yb + ((size_t)k * ldy + o.lo) * es,
+                                            (char *)D.d_res + ((size_t)k * ylen + o.lo) * es, o.len(), beta, c.stream), "y combine");
+            }
+        }
+        // the end of this product on the caller's stream: what the next product of the handle waits for
         DeviceGuard g;
-        DCHECK(g.enter(sdev), "hipSetDevice");
-        if (D.ev_tail && D.tail_dev != sdev) {
+        DCHECK(g.enter(c.sdev), "hipSetDevice");
+        if (D.ev_tail && D.tail_dev != c.sdev) {
             (void)hipEventDestroy(D.ev_tail);
             D.ev_tail = nullptr;
         }
         if (!D.ev_tail) {
             DCHECK(hipEventCreateWithFlags(&D.ev_tail, hipEventDisableTiming), "hipEventCreate");
-            D.tail_dev = sdev;
+            D.tail_dev = c.sdev;
         }
-        DCHECK(hipEventRecord(D.ev_tail, stream), "hipEventRecord");
-    }
-#undef DCHECK
-    return BSM_OK;
+        DCHECK(hipEventRecord(D.ev_tail, c.stream), "hipEventRecord");
+        return BSM_OK;
+    };
+    return fan_out(D, K, 0, nullptr, before, phase, after);
 }
+
+// a multi-device product issues on several streams and devices and waits for events of earlier products: it cannot be
+// recorded into the caller's graph (include/bsm_rocm.h) -- refuse instead of corrupting the capture
+static const char kNoCapture[] = "a multi-device handle cannot be captured into a graph";
 
 static int dist_mul_k(bsm_matrix_s *A, int op, int K, const void *x, long long ldx, void *y, long long ldy,
                       const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream) {
     DistState &D = *A->dist;
     std::lock_guard<std::mutex> lock(D.mu);  // one product of a handle is ISSUED at a time (the work vectors are the handle's)
-    if (memspace == BSM_MEM_DEVICE && stream) {
-        // a multi-device product issues on several streams and devices and waits for events of earlier products:
-        // it cannot be recorded into the caller's graph (include/bsm_rocm.h) -- refuse instead of corrupting the capture
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &cs) != hipSuccess) (void)hipGetLastError();
-        if (cs != hipStreamCaptureStatusNone)
-            return fail(BSM_ERR_UNSUPPORTED, "a multi-device handle cannot be captured into a graph");
-    }
-    if (memspace == BSM_MEM_DEVICE && D.all_peer) {
-        int cur = 0;
-        hipError_t e = hipGetDevice(&cur);
-        if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-        const int xdev = pointer_device(x, cur), ydev = pointer_device(y, cur);
-        int sdev = cur;
-        if (stream && hipStreamGetDevice(stream, &sdev) != hipSuccess) {
+    if (memspace == BSM_MEM_DEVICE && stream && capturing(stream)) return fail(BSM_ERR_UNSUPPORTED, kNoCapture);
+    if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
+    Call c{memspace == BSM_MEM_HOST, -1, -1, 0, stream, nullptr};
+    hipError_t e = hipGetDevice(&c.sdev);
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    if (!c.host) {
+        const int cur = c.sdev;
+        c.xdev = pointer_device(x, cur);
+        c.ydev = pointer_device(y, cur);
+        if (stream && hipStreamGetDevice(stream, &c.sdev) != hipSuccess) {
             (void)hipGetLastError();
-            sdev = cur;
+            c.sdev = cur;
         }
+        e = ready_event(D, c.sdev, &c.ready);
+        if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
         bool inside = false, xin = false, yin = false;
         for (const auto &pp : D.parts) {
-            inside |= pp->device == sdev;
-            xin |= pp->device == xdev;
-            yin |= pp->device == ydev;
+            inside |= pp->device == c.sdev;
+            xin |= pp->device == c.xdev;
+            yin |= pp->device == c.ydev;
         }
-        if (inside && xin && yin) {  // x, y and the stream live on devices of the context: everybody can address them
-            auto it = D.ev_x.find(sdev);
-            if (it == D.ev_x.end()) {
-                DeviceGuard g;
-                e = g.enter(sdev);
-                hipEvent_t ev = nullptr;
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-                if (e != hipSuccess) return hip_fail(e, "hipEventCreate");
-                it = D.ev_x.emplace(sdev, ev).first;
-            }
+        if (D.all_peer && inside && xin && yin) {  // x, y and the stream live on devices of the context: everybody can address them
             const long long xlen = (op == BSM_OP_N) ? D.ncols : D.nrows;
             const int P = (int)D.parts.size();
-            std::vector<VecSource> src{VecSource{(const char *)x, Range{0, xlen}, xdev, sdev, stream, it->second, 1, 3 * P}};
-            std::vector<VecDest> dst{VecDest{(char *)y, ydev, sdev, stream, it->second, 3 * P}};
+            std::vector<VecSource> src{VecSource{(const char *)x, Range{0, xlen}, c.xdev, c.sdev, stream, c.ready, 1, 3 * P}};
+            std::vector<VecDest> dst{VecDest{(char *)y, c.ydev, c.sdev, stream, c.ready, 3 * P}};
             return dist_mul_fused(D, op, K, src, ldx, dst, ldy, alpha, beta, beta_strong_zero);
         }
     }
-    return dist_mul_copies(A, op, K, x, ldx, y, ldy, alpha, beta, beta_strong_zero, memspace, stream);
+    return dist_mul_copies(D, op, K, x, ldx, y, ldy, alpha, beta, beta_strong_zero, c);
 }
 
 // bsm_mul_parts: x and y PARTITIONED over the devices of the handle (include/bsm_rocm.h)
@@ -1209,19 +1177,13 @@ int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *co
         if ((!in.empty() && !x_parts[p]) || (!out.empty() && !y_parts[p]))
             return fail(BSM_ERR_INVALID, "part " + std::to_string(p) + ": null vector part");
         hipStream_t st = streams ? (hipStream_t)streams[p] : nullptr;
-        if (st) {
-            // like bsm_mul on a multi-device handle (include/bsm_rocm.h): the product waits for events of other streams
-            // and devices, which must not be recorded into a caller's graph
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
-            if (cs != hipStreamCaptureStatusNone)
-                return fail(BSM_ERR_UNSUPPORTED, "a multi-device handle cannot be captured into a graph");
-        }
+        if (st && capturing(st)) return fail(BSM_ERR_UNSUPPORTED, kNoCapture);  // like bsm_mul (include/bsm_rocm.h)
         src.push_back(VecSource{(const char *)x_parts[p] - (size_t)in.lo * es, in, pt.device, pt.device, st, pt.ev_in, 0, p});
         dst.push_back(VecDest{(char *)y_parts[p] - (size_t)out.lo * es, pt.device, pt.device, st, pt.ev_in, p});
     }
     return dist_mul_fused(D, op, 1, src, 0, dst, 0, alpha, beta, beta_strong_zero);
 }
+#undef DCHECK
 
 int dist_mul(bsm_matrix_s *A, int op, const void *x, void *y, const void *alpha, const void *beta,
              int beta_strong_zero, int memspace, hipStream_t stream) {

@@ -131,6 +131,11 @@ void free_image(DeviceImage &img);
 hipError_t device_pack(Analysis &an, void **d_values);  // blocks_on_device: run the pack plan on the current device
 // the value sink of a device handle (pinned staging windows + asynchronous upload); nullptr for none
 std::unique_ptr<ValueSink> make_device_sink(void **d_values);
+// whether `st` is being captured into a graph (a failed query counts as "no")
+bool capturing(hipStream_t st);
+// the work arrays of the interleaved multi-RHS pass hold `need` vector entries (Xr, W: 128 bytes per entry each); a
+// regrow frees the old arrays, so no product may still use them.  false: no memory (the arrays are left empty)
+bool il_reserve(ILWork &il, long long need);
 
 // ---- bsm_dist.cpp -------------------------------------------------------------------------------
 // Row partition of `in` (already in its final order) over the context's devices; fills A->dist.
