@@ -19,6 +19,16 @@ using namespace bsm;
 namespace {
 // RAII staging buffers: cached in the handle when uncontended, temporary otherwise
 struct Staging {
+    // the handle's buffer p (capacity `cap` bytes) holds at least `bytes`
+    static hipError_t grow(void *&p, size_t &cap, size_t bytes) {
+        if (cap >= bytes) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const hipError_t e = hipMalloc(&p, bytes + 16);
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
     bsm_matrix_s *A;
     bool locked = false;
     void *dx = nullptr, *dy = nullptr;
@@ -28,22 +38,9 @@ struct Staging {
         locked = A->host_mu.try_lock();
         hipError_t e = hipSuccess;
         if (locked) {
-            if (A->stage_x_bytes < xbytes) {
-                if (A->stage_x) (void)hipFree(A->stage_x);
-                A->stage_x = nullptr;
-                A->stage_x_bytes = 0;
-                e = hipMalloc(&A->stage_x, xbytes + 16);
-                if (e != hipSuccess) return e;
-                A->stage_x_bytes = xbytes;
-            }
-            if (A->stage_y_bytes < ybytes) {
-                if (A->stage_y) (void)hipFree(A->stage_y);
-                A->stage_y = nullptr;
-                A->stage_y_bytes = 0;
-                e = hipMalloc(&A->stage_y, ybytes + 16);
-                if (e != hipSuccess) return e;
-                A->stage_y_bytes = ybytes;
-            }
+            e = grow(A->stage_x, A->stage_x_bytes, xbytes);
+            if (e == hipSuccess) e = grow(A->stage_y, A->stage_y_bytes, ybytes);
+            if (e != hipSuccess) return e;
             dx = A->stage_x;
             dy = A->stage_y;
         } else {
@@ -1431,45 +1428,43 @@ extern "C" int bsm_part_info(bsm_matrix_t A, int32_t part, bsm_part_info_t *out)
     return dist_part_info(A, part, out);
 }
 
-// The gather workspace of an image (column sums + inverted indices) belongs to the handle and admits
-// ONE product in flight.  The enqueue is serialised; a caller that races on the same handle from
-// another thread, or whose predecessor may still be running on ANOTHER stream (same stream: stream
-// order protects it), does not get the claim and its product takes the atomic path.  Nothing is
-// enqueued for the bookkeeping (an event recorded per product costs 3 us between two 9 us launches):
-// the previous stream is queried only when the stream changes.  A product enqueued while the stream is
-// being captured into a graph never gets the claim (atomic path): a replay could meet an eager product.
-struct WorkspaceClaim {
-    bsm_matrix_s *A;
+// The gather workspace of an image (column sums + inverted indices) and the work arrays of the interleaved multi-RHS pass
+// (Xr, W: 128 bytes per vector entry each) belong to the handle and admit ONE product in flight each.  The enqueue is
+// serialised; a caller that races on the same handle from another thread, or whose predecessor may still be running on
+// ANOTHER stream (same stream: stream order protects it), does not get the claim and its product takes the kernels that
+// need neither (atomic path, ordinary multi-RHS kernels).  Nothing is enqueued for the bookkeeping (an event recorded
+// per product costs 3 us between two 9 us launches): the previous stream is queried only when the stream changes.  A
+// product enqueued while the stream is being captured into a graph never gets the claim: a replay would use the
+// resource on whatever stream, beside eager products nobody can order against.
+struct Claim {
+    ClaimState &c;
     hipStream_t st;
     std::unique_lock<std::mutex> lock;
-    bool held = false, track = false;
-    WorkspaceClaim(bsm_matrix_s *A_, const DeviceImage &img, hipStream_t st_)
-        : A(A_), st(st_), lock(A_->gather_mu, std::defer_lock) {
-        held = img.d_ws != nullptr && lock.try_lock();
-        if (!held) return;
-        if (capturing(st)) {
-            // a captured product would use the workspace at every replay, on whatever stream, beside eager
-            // products nobody can order against: captured products take the atomic path
-            held = track = false;
-            return;
-        }
-        track = true;
-        if (A->ws_pending && A->ws_stream == st) return;  // the common case: one stream, nothing to ask
-        if (A->ws_pending) {  // the stream changed: is the previous one idle?
-            const hipError_t q = hipStreamQuery(A->ws_stream);
+    bool held = false;
+    Claim(ClaimState &c_, bool wanted, hipStream_t st_) : c(c_), st(st_), lock(c_.mu, std::defer_lock) {
+        if (!wanted || !lock.try_lock() || capturing(st)) return;
+        if (c.pending && c.stream != st) {  // the stream changed: is the previous one idle?
+            const hipError_t q = hipStreamQuery(c.stream);
             if (q != hipSuccess) {
                 (void)hipGetLastError();  // hipErrorNotReady is not a failure
                 // (any other answer -- the stream may be gone -- is treated the same way once, then
                 // forgotten: work of a destroyed stream does not outlive a whole product by much)
-                if (q != hipErrorNotReady) A->ws_pending = false;
-                held = track = false;
+                if (q != hipErrorNotReady) c.pending = false;
+                return;
             }
+            c.pending = false;
         }
+        held = true;
+    }
+    // before the resource is freed (a regrow): wait for the product that may still use it
+    void drain() {
+        if (c.pending && hipStreamSynchronize(c.stream) != hipSuccess) (void)hipGetLastError();
+        c.pending = false;
     }
     void mark() {  // after the product has been enqueued
-        if (!held || !track) return;
-        A->ws_stream = st;
-        A->ws_pending = true;
+        if (!held) return;
+        c.stream = st;
+        c.pending = true;
     }
 };
 
@@ -1490,51 +1485,11 @@ bool bsm::il_reserve(ILWork &il, long long need) {
     return true;
 }
 
-// The work arrays of the interleaved multi-RHS pass (Xr, W: 128 bytes per vector entry each) belong to the handle like the
-// gather workspace, with the same rules: one product in flight -- a racing thread, a predecessor that may still run on
-// ANOTHER stream, or a stream under graph capture do not get the claim and their product takes the ordinary kernels.
-// Allocated (and grown) here, at the first product that uses them.
-struct ILClaim {
-    bsm_matrix_s *A;
-    hipStream_t st;
-    std::unique_lock<std::mutex> lock;
-    bool held = false;
-    ILClaim(bsm_matrix_s *A_, const DeviceImage &img, bool opT, long long nrhs, hipStream_t st_)
-        : A(A_), st(st_), lock(A_->il_mu, std::defer_lock) {
-        if (!il_applies(img, opT, nrhs) || !lock.try_lock() || capturing(st)) return;
-        if (A->il_pending && A->il_stream != st) {  // the stream changed: is the previous one idle?
-            const hipError_t q = hipStreamQuery(A->il_stream);
-            if (q != hipSuccess) {
-                (void)hipGetLastError();
-                if (q != hipErrorNotReady) A->il_pending = false;
-                return;
-            }
-            A->il_pending = false;
-        }
-        const long long need = std::max(img.nrows, img.ncols);
-        if (A->il.rows < need) {  // a regrow frees the arrays the previous claim's product may still read
-            if (A->il_pending && hipStreamSynchronize(A->il_stream) != hipSuccess) (void)hipGetLastError();
-            A->il_pending = false;
-            if (!il_reserve(A->il, need)) return;  // no memory for the work arrays: the ordinary kernels need none
-        }
-        held = true;
-    }
-    ILWork *work() { return held ? &A->il : nullptr; }
-    void mark() {
-        if (!held) return;
-        A->il_stream = st;
-        A->il_pending = true;
-    }
-};
-
-extern "C" int bsm_mul(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha,
-                       const void *beta, int beta_strong_zero, int memspace, void *stream) {
-    if (!A) return fail(BSM_ERR_INVALID, "null handle");
-    if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
-    if (!x || !y) return fail(BSM_ERR_INVALID, "null vector");
-    if (!A->on_device)
-        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
-    if (A->dist) return dist_mul(A, op, x, y, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
+// bsm_mul (K = 1, ld = max(length, 1)) and bsm_mul_multi after their argument checks
+static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long ldx, void *Y, long long ldy,
+                 const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t st) {
+    if (A->dist)  // multi-device handles: every device streams its part once per batch of <= 8 columns
+        return dist_mul_multi(A, op, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, st);
     // transposed products run forward on the second ordering when the handle has one
     const bool use_t = (op != BSM_OP_N) && A->has_t;
     const DeviceImage &img = use_t ? A->img_t : A->img;
@@ -1543,37 +1498,63 @@ extern "C" int bsm_mul(bsm_matrix_t A, int op, const void *x, void *y, const voi
     DeviceGuard guard;
     hipError_t e = guard.enter(img.device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    hipStream_t st = (hipStream_t)stream;
-    WorkspaceClaim claim(A, img, st);
-    const bool use_gather = claim.held;
-    auto mark_gather = [&]() { claim.mark(); };
+    // one column: the gather workspace (if the image has one); more: the interleaved pass's work arrays (if it applies)
+    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : il_applies(img, opT, K), st);
+    ILWork *il = nullptr;
+    if (claim.held && K > 1) {  // allocated (and grown) here, at the first product that uses them
+        const long long need = std::max(img.nrows, img.ncols);
+        if (A->il.rows < need) claim.drain();  // a regrow frees the arrays the previous claim's product may still read
+        if (il_reserve(A->il, need))
+            il = &A->il;
+        else
+            claim.held = false;  // no memory for the work arrays: the ordinary kernels need none
+    }
+    const bool gather = K == 1 && claim.held;
     if (memspace == BSM_MEM_DEVICE) {
-        e = launch_mul(img, opT, conj, x, y, alpha, beta, beta_strong_zero, st, use_gather);
+        e = launch_mul(img, opT, conj, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, st, gather, nullptr, il);
         if (e != hipSuccess) return hip_fail(e, "kernel launch");
-        mark_gather();
+        claim.mark();
         return BSM_OK;
     }
     if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "bad memspace");
     // host vectors: stage through device buffers (PCIe), synchronous
     const size_t es = (size_t)A->an.es;
-    const size_t xlen = (size_t)(op == 0 ? A->img.ncols : A->img.nrows);
-    const size_t ylen = (size_t)(op == 0 ? A->img.nrows : A->img.ncols);
+    const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
+    const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
     Staging sg;
-    e = sg.acquire(A, xlen * es, ylen * es);
+    e = sg.acquire(A, (size_t)xlen * K * es, (size_t)ylen * K * es);
     void *dx = sg.dx, *dy = sg.dy;
+    // K columns between host (ld) and staging (len, packed); one column: a plain copy
+    auto copy = [&](void *dst, long long ldd, const void *src, long long lds, long long len, hipMemcpyKind kind) {
+        if (K == 1) return hipMemcpyAsync(dst, src, (size_t)len * es, kind, st);
+        return hipMemcpy2DAsync(dst, (size_t)ldd * es, src, (size_t)lds * es, (size_t)len * es, (size_t)K, kind, st);
+    };
     // the incoming y travels when beta uses it -- and whenever the handle owns only a row range: rows
     // outside it that no block reaches are left untouched by the product and must come back unchanged
     const bool partial = (op == BSM_OP_N) && (img.own_lo > 0 || img.own_hi < img.nrows);
     const bool y_in = !beta_strong_zero || partial;
     // (page-locked vectors -- bsm_host_register -- make both copies true DMA; pageable ones are staged
     // by the runtime: 74 vs 118 us per C2-sized product)
-    if (e == hipSuccess) e = hipMemcpyAsync(dx, x, xlen * es, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && y_in) e = hipMemcpyAsync(dy, y, ylen * es, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_mul(img, opT, conj, dx, dy, alpha, beta, beta_strong_zero, st, use_gather);
-    if (e == hipSuccess) e = hipMemcpyAsync(y, dy, ylen * es, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = copy(dx, xlen, X, ldx, xlen, hipMemcpyHostToDevice);
+    if (e == hipSuccess && y_in) e = copy(dy, ylen, Y, ldy, ylen, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_mul(img, opT, conj, K, dx, xlen, dy, ylen, alpha, beta, beta_strong_zero, st, gather, nullptr, il);
+    claim.mark();
+    if (e == hipSuccess) e = copy(Y, ldy, dy, ylen, ylen, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "host-staged mul");
+    if (e != hipSuccess) return hip_fail(e, K == 1 ? "host-staged mul" : "host-staged multi mul");
     return BSM_OK;
+}
+
+extern "C" int bsm_mul(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha,
+                       const void *beta, int beta_strong_zero, int memspace, void *stream) {
+    if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
+    if (!x || !y) return fail(BSM_ERR_INVALID, "null vector");
+    if (!A->on_device)
+        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
+    const long long xlen = std::max<long long>(op == 0 ? A->an.ncols : A->an.nrows, 1);
+    const long long ylen = std::max<long long>(op == 0 ? A->an.nrows : A->an.ncols, 1);
+    return mul_k(A, op, 1, x, xlen, y, ylen, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
 }
 
 extern "C" int bsm_mul_parts(bsm_matrix_t A, int op, const void *const *x_parts, void *const *y_parts,
@@ -1600,44 +1581,7 @@ extern "C" int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X
     const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
     if (ldx < std::max<long long>(xlen, 1) || ldy < std::max<long long>(ylen, 1))
         return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
-    if (A->dist)  // multi-device handles: every device streams its part once per batch of <= 8 columns
-        return dist_mul_multi(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
-    const bool use_t = (op != BSM_OP_N) && A->has_t;
-    const DeviceImage &img = use_t ? A->img_t : A->img;
-    const bool opT = (op != BSM_OP_N) && !use_t;
-    const bool conj = (op == BSM_OP_C);
-    DeviceGuard guard;
-    hipError_t e = guard.enter(img.device);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    hipStream_t st = (hipStream_t)stream;
-    ILClaim il(A, img, opT, nrhs, st);
-    if (memspace == BSM_MEM_DEVICE) {
-        e = launch_mul_multi(img, opT, conj, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, st, nullptr, il.work());
-        if (e != hipSuccess) return hip_fail(e, "kernel launch");
-        il.mark();
-        return BSM_OK;
-    }
-    if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "bad memspace");
-    const size_t es = (size_t)A->an.es;
-    Staging sg;
-    e = sg.acquire(A, (size_t)xlen * nrhs * es, (size_t)ylen * nrhs * es);
-    void *dx = sg.dx, *dy = sg.dy;
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(dx, (size_t)xlen * es, X, (size_t)ldx * es, (size_t)xlen * es, (size_t)nrhs,
-                             hipMemcpyHostToDevice, st);
-    const bool partial = (op == BSM_OP_N) && (img.own_lo > 0 || img.own_hi < img.nrows);  // see bsm_mul
-    if (e == hipSuccess && (!beta_strong_zero || partial))
-        e = hipMemcpy2DAsync(dy, (size_t)ylen * es, Y, (size_t)ldy * es, (size_t)ylen * es, (size_t)nrhs,
-                             hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = launch_mul_multi(img, opT, conj, nrhs, dx, xlen, dy, ylen, alpha, beta, beta_strong_zero, st, nullptr, il.work());
-    il.mark();
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(Y, (size_t)ldy * es, dy, (size_t)ylen * es, (size_t)ylen * es, (size_t)nrhs,
-                             hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "host-staged multi mul");
-    return BSM_OK;
+    return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
 }
 
 extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *ids, const void *const *blocks,

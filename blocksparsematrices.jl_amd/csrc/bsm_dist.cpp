@@ -856,10 +856,8 @@ static int dist_mul_fused(DistState &D, int op, int K, const std::vector<VecSour
                 if (!direct[p]) pt.w_clean = false;  // (until the whole product has been issued)
                 const void *b = direct[p] ? beta : (rezero ? one : nullptr);
                 const int sz = direct[p] ? beta_strong_zero : (rezero ? 0 : 1);
-                if (K == 1)
-                    DCHECK(launch_mul(pt.img, opT, conj, xp, target, alpha, b, sz, st, false, z), "kernel launch");
-                else
-                    DCHECK(launch_mul_multi(pt.img, opT, conj, K, xp, xld, target, tld, alpha, b, sz, st, z, part_il(pt, opT, K)), "kernel launch");
+                DCHECK(launch_mul(pt.img, opT, conj, K, xp, xld, target, tld, alpha, b, sz, st, false, z, part_il(pt, opT, K)),
+                       "kernel launch");
             } else if (rezero) {
                 if (!pt.w_clean) DCHECK(hipMemsetAsync(pt.d_w, 0, (size_t)D.kcap * vlen * es, st), "memset");
                 pt.w_clean = false;
@@ -1003,12 +1001,8 @@ static int dist_mul_copies(DistState &D, int op, int K, const void *x, long long
                     }
                 }
                 const long long z[2] = {zr.lo, zr.hi};
-                if (K == 1)
-                    DCHECK(launch_mul(pt.img, opT, conj, xp, pt.d_w, alpha, nullptr, 1, pt.stream, pt.img.d_ws != nullptr, z),
-                           "kernel launch");
-                else
-                    DCHECK(launch_mul_multi(pt.img, opT, conj, K, xp, xld, pt.d_w, (long long)vlen, alpha, nullptr, 1,
-                                            pt.stream, z, part_il(pt, opT, K)), "kernel launch");
+                DCHECK(launch_mul(pt.img, opT, conj, K, xp, xld, pt.d_w, (long long)vlen, alpha, nullptr, 1, pt.stream,
+                                  pt.img.d_ws != nullptr, z, part_il(pt, opT, K)), "kernel launch");
             } else if (!zr.empty()) {
                 for (int k = 0; k < K; k++)
                     DCHECK(hipMemsetAsync((char *)pt.d_w + ((size_t)k * vlen + zr.lo) * es, 0, (size_t)zr.len() * es, pt.stream),
@@ -1184,11 +1178,6 @@ int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *co
     return dist_mul_fused(D, op, 1, src, 0, dst, 0, alpha, beta, beta_strong_zero);
 }
 #undef DCHECK
-
-int dist_mul(bsm_matrix_s *A, int op, const void *x, void *y, const void *alpha, const void *beta,
-             int beta_strong_zero, int memspace, hipStream_t stream) {
-    return dist_mul_k(A, op, 1, x, 0, y, 0, alpha, beta, beta_strong_zero, memspace, stream);
-}
 
 // Y = alpha op(A) X + beta Y: every device streams its part of A ONCE per batch of up to 8 columns
 // (bsm_mul_multi's own batching), the exchange and the delivery move the batch's columns together

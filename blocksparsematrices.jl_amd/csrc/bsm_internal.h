@@ -77,6 +77,15 @@ int refill_images(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, 
                   const int64_t *bn, int memspace, hipStream_t st);
 }
 
+namespace bsm {
+// a resource of the handle that admits one product in flight (bsm_capi.cpp: Claim)
+struct ClaimState {
+    std::mutex mu;
+    hipStream_t stream = nullptr;  // stream of the last product that held the claim
+    bool pending = false;          // ... which may still be running
+};
+}  // namespace bsm
+
 struct bsm_matrix_s {
     bsm::Analysis an;  // multi-device handles: bookkeeping / statistics of the WHOLE operator, no image
     bsm::DeviceImage img;
@@ -86,15 +95,11 @@ struct bsm_matrix_s {
     bool has_t = false;
     bsm::Analysis an_t;
     bsm::DeviceImage img_t;
-    std::mutex gather_mu;  // the gather workspace admits one product in flight per handle
-    hipStream_t ws_stream = nullptr;  // stream of the last gather-mode product
-    bool ws_pending = false;          // ... which may still be running (see WorkspaceClaim)
-    // work arrays of the interleaved multi-RHS pass (bsm_kernels.h: ILWork): allocated at the first product that takes
-    // it, one product in flight (ILClaim in bsm_capi.cpp: same rules as the gather workspace)
-    std::mutex il_mu;
+    // one product in flight per handle on the gather workspace of the images (one-column products) and on the work
+    // arrays of the interleaved multi-RHS pass (bsm_kernels.h: ILWork, allocated at the first product that takes it):
+    // bsm_capi.cpp: Claim
+    bsm::ClaimState ws_claim, il_claim;
     bsm::ILWork il;
-    hipStream_t il_stream = nullptr;
-    bool il_pending = false;
     // device staging buffers of the BSM_MEM_HOST path, kept between calls (grow-only); a second
     // concurrent host call on the same handle falls back to temporary buffers
     std::mutex host_mu;
@@ -143,8 +148,6 @@ bool il_reserve(ILWork &il, long long need);
 // ids[b]: input block id of in[b] (bsm_update_blocks)
 int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t nrows, int64_t ncols,
                 const std::vector<BlockIn> &in, const std::vector<int64_t> &ids, const bsm_options &o);
-int dist_mul(bsm_matrix_s *A, int op, const void *x, void *y, const void *alpha, const void *beta,
-             int beta_strong_zero, int memspace, hipStream_t stream);
 int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long long ldx, void *Y, long long ldy,
                    const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream);
 int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *const *y_parts, const void *alpha,

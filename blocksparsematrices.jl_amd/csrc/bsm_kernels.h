@@ -31,17 +31,6 @@ struct DeviceImage {
     long long ws_fbase = 0;
 };
 
-// Enqueues y = alpha*op(A)*x + beta*y on `stream`.  x, y device pointers.  No allocation,
-// no synchronisation (graph-capturable).
-// opT: apply the transposed operator of the image; conj: conjugate every stored entry.
-// use_gather: take the two-launch gather path (only if the image has a workspace).
-hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, const void *x, void *y,
-                      const void *alpha, const void *beta, int strong_zero, hipStream_t stream,
-                      bool use_gather = false, const long long *zrange = nullptr);
-// zrange = {lo, hi} (0-based, exclusive): the y entries the `y .*= beta` pass of the accumulate path
-// covers instead of the image's own range (multi-device fan-out; ignored by exclusive forward images,
-// whose coverage is part of the image)
-
 // dst[0..n) += src[0..n);   y[0..n) = beta * y + r   (element type `dtype`, beta: pointer to one T)
 hipError_t launch_vec_add(int dtype, void *dst, const void *src, long long n, hipStream_t stream);
 hipError_t launch_vec_axpby(int dtype, void *y, const void *r, long long n, const void *beta, hipStream_t stream);
@@ -68,21 +57,27 @@ hipError_t launch_vec_finish(int dtype, void *y, long long ldy, void *w, long lo
 hipError_t launch_vec_add_segments(int dtype, void *y, const VecPieces &pc, int npieces, hipStream_t stream);
 
 // Work arrays of the INTERLEAVED multi-RHS pass (bsm_kernels.hip: panel_kernel_il_*): X and the accumulated Y row-major,
-// one 128-byte line per vector index.  Owned by the handle (bsm_capi.cpp: ILClaim), one product in flight.
+// one 128-byte line per vector index.  Owned by the handle (bsm_capi.cpp: Claim), one product in flight.
 struct ILWork {
     void *xr = nullptr;   // rows x 128 bytes: alpha * X, K-interleaved
     void *w = nullptr;    // rows x 128 bytes: the sums; zero between products (the finish pass zeroes behind its read)
     long long rows = 0;   // capacity of both, in vector entries
     bool w_clean = false; // w is known to be zero
 };
-// whether launch_mul_multi would take the interleaved pass for this image / op / batch (so that the caller only claims
-// -- and allocates -- the work arrays when they will be used)
+// whether launch_mul would take the interleaved pass for this image / op / batch (so that the caller only claims -- and
+// allocates -- the work arrays when they will be used)
 bool il_applies(const DeviceImage &img, bool opT, long long nrhs);
 
-// nrhs right-hand sides: X (ldx) and Y (ldy) column-major; A is streamed once per batch of <= 8.
-hipError_t launch_mul_multi(const DeviceImage &img, bool opT, bool conj, long long nrhs, const void *x,
-                            long long ldx, void *y, long long ldy, const void *alpha, const void *beta,
-                            int strong_zero, hipStream_t stream, const long long *zrange = nullptr, ILWork *il = nullptr);
+// Enqueues Y = alpha*op(A)*X + beta*Y on `stream` for K right-hand sides, X (ldx) and Y (ldy) column-major device
+// pointers.  No allocation, no synchronisation (graph-capturable).
+// opT: apply the transposed operator of the image; conj: conjugate every stored entry.
+// K == 1: the one-column kernels; use_gather: take the two-launch gather path (only if the image has a workspace).
+// K > 1: A is streamed once per batch of <= 16 columns; il: the work arrays of the interleaved pass (null: not claimed).
+// zrange = {lo, hi} (0-based, exclusive): the y entries the `y .*= beta` pass of the accumulate path covers instead of
+// the image's own range (multi-device fan-out; ignored by exclusive forward images, whose coverage is part of the image)
+hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, const void *x, long long ldx, void *y,
+                      long long ldy, const void *alpha, const void *beta, int strong_zero, hipStream_t stream,
+                      bool use_gather, const long long *zrange, ILWork *il);
 
 // rowcolvals(A): COO triples (1-based int64 rows / cols, values of the image's element type) written from
 // the packed device image; d_out_off[w] = first output slot of wave descriptor w (host prefix sum of

@@ -2280,21 +2280,9 @@ static bool stream_policy(const DeviceImage &img) {
     return (mb >= 40 && mb < 100) || mb > 320;  // measured crossovers: ~105 MB and ~310-330 MB of values
 }
 
-// one launch of panel_kernel<T, L, FWD, TRN, NT> with NT taken from the run-time policy `nt`
-#define BSM_LAUNCH_PANEL(FWD_, TRN_, ...)                                                \
-    do {                                                                                  \
-        if (nt)                                                                           \
-            hipLaunchKernelGGL((panel_kernel<T, L, FWD_, TRN_, true>), __VA_ARGS__);      \
-        else                                                                              \
-            hipLaunchKernelGGL((panel_kernel<T, L, FWD_, TRN_, false>), __VA_ARGS__);     \
-    } while (0)
-
-template <typename T, int L>
-static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, const void *x, void *y,
-                               const void *alpha_p, const void *beta_p, int strong_zero,
-                               hipStream_t stream, bool use_gather = false, const long long *zrange = nullptr) {
-    const T alpha = load_scalar<T>(alpha_p, 1.0);
-    const T beta = load_scalar<T>(beta_p, 0.0);
+// ---- the frame every product launcher shares --------------------------------------------------------------------------
+// flags of every launch of a product (BSM_EXPERIMENT builds: timing-only ablations from BSM_DEBUG_FLAGS on top)
+static int base_flags(bool opT, bool conj, int strong_zero) {
     int flags = 0;
     if (strong_zero) flags |= FLAG_STRONG_ZERO;
     if (conj) flags |= FLAG_CONJ;
@@ -2302,76 +2290,117 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
 #ifdef BSM_EXPERIMENT
     if (const char *v = std::getenv("BSM_DEBUG_FLAGS")) flags |= std::atoi(v) << 16;
 #endif
-    const WaveWork *waves = (const WaveWork *)img.d_waves;
+    return flags;
+}
+
+// [lo, hi): the y entries an accumulating product scales by beta -- the rows the image owns (all of them for op T / C),
+// or zrange when the caller (multi-device fan-out) knows which y entries this image must define
+struct YRange {
+    long long lo, hi;
+};
+static YRange y_range(const DeviceImage &img, bool opT, const long long *zrange) {
+    if (zrange) return {zrange[0], zrange[1]};
+    if (opT) return {0, img.ncols};
+    return {img.own_lo, img.own_hi};
+}
+
+// Calls launch(waves, grid, wg_base) for every launch of an accumulating product: one launch over every workgroup
+// (atomics), or one launch per colour class (plain read-modify-write: the classes touch pairwise disjoint y entries, so
+// the result is bitwise reproducible).  multi: the multi-RHS kernels, which walk the coarser split of the panels
+// (bsm_analysis.h: Tunables::multi_wave_bytes) where the image has one and is not coloured.
+template <typename F> static void for_each_launch(const DeviceImage &img, bool multi, F &&launch) {
+    const bool colored = !img.color_wg_ptr.empty();
+    const bool coarse = multi && img.d_waves_multi && !colored;
+    const WaveWork *waves = (const WaveWork *)(coarse ? img.d_waves_multi : img.d_waves);
+    const long long nwg = coarse ? img.nwg_multi : img.nwg_main;
+    const size_t nlaunch = colored ? img.color_wg_ptr.size() - 1 : 1;
+    for (size_t c = 0; c < nlaunch; ++c) {
+        const long long wg0 = colored ? img.color_wg_ptr[c] : 0;
+        const long long wg1 = colored ? img.color_wg_ptr[c + 1] : nwg;
+        if (wg1 > wg0) launch(waves, dim3((unsigned)(wg1 - wg0)), (unsigned)wg0);
+    }
+}
+
+// The FWD / TRN instance of a panel kernel, passed to f as two std::bool_constants: the forward half only (op N), both
+// halves (SymmetricBlockMatrix off-diagonal pieces: every product is fused), the transposed half only (op T / C)
+template <typename F> static void with_halves(bool opT, bool has_off, F &&f) {
+    if (has_off)
+        f(std::true_type{}, std::true_type{});
+    else if (!opT)
+        f(std::true_type{}, std::false_type{});
+    else
+        f(std::false_type{}, std::true_type{});
+}
+
+// one right-hand side
+template <typename T, int L>
+static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
+                               int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
+    int flags = base_flags(opT, conj, strong_zero);
     const uint4 *values = (const uint4 *)img.d_values;
     const int *rows = (const int *)img.d_rows;
     const int *cols = (const int *)img.d_cols;
-    const T *xd = (const T *)x;
-    T *yd = (T *)y;
-    const dim3 block(64 * kWavesPerWg);
     const bool nt = stream_policy(img);
-
+    T *ws = nullptr;  // gather mode: the workspace
+    // one launch of panel_kernel<T, L, FWD, TRN, NT> with NT taken from the run-time policy `nt`
+    auto panel = [&](auto fwd, auto trn, const WaveWork *waves, dim3 grid, unsigned wg_base) {
+        constexpr bool FWD = decltype(fwd)::value, TRN = decltype(trn)::value;
+        const dim3 block(64 * kWavesPerWg);
+        if (nt)
+            hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, true>), grid, block, 0, stream, waves, values, rows, cols, xd, yd,
+                               alpha, beta, flags, wg_base, ws, img.ws_fbase);
+        else
+            hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, false>), grid, block, 0, stream, waves, values, rows, cols, xd, yd,
+                               alpha, beta, flags, wg_base, ws, img.ws_fbase);
+    };
     if (!opT && img.exclusive_fwd) {
         // one launch: every y row has exactly one producer; beta is fused into its store and
         // the rows no block covers are scaled by WORK_SCALE waves of the same grid.
         flags |= FLAG_DIRECT;
         if (img.nwg_total > 0)
-            BSM_LAUNCH_PANEL(true, false, dim3((unsigned)img.nwg_total), block, 0,
-                               stream, waves, values, rows, cols, xd, yd, alpha, beta, flags, 0u, (T *)nullptr, 0LL);
+            panel(std::true_type{}, std::false_type{}, (const WaveWork *)img.d_waves, dim3((unsigned)img.nwg_total), 0u);
         return hipGetLastError();
     }
-    // accumulate mode: y .*= beta over the owned range, then hardware atomics
-    const long long ylen = opT ? img.ncols : img.nrows;
-    long long lo = 0, hi = ylen;
-    if (!opT) {
-        lo = img.own_lo;
-        hi = img.own_hi;
-    }
-    if (zrange) {  // the caller (multi-device fan-out) knows which y entries this image must define
-        lo = zrange[0];
-        hi = zrange[1];
-    }
+    // accumulate mode: y .*= beta over the owned range, then hardware atomics (gather mode: the sums go to the
+    // workspace, and a second launch adds them up in a fixed order)
+    const YRange r = y_range(img, opT, zrange);
     const bool gather = use_gather && img.d_ws != nullptr;
-    T *ws = gather ? (T *)img.d_ws : (T *)nullptr;
-    if (gather) flags |= FLAG_GATHER;
-    if (!gather && hi > lo && (strong_zero || !is_one(beta)))
-        hipLaunchKernelGGL((scale_kernel<T>), dim3(scale_blocks<T>(hi - lo)), dim3(256), 0, stream, yd, 0LL, lo, hi, beta,
-                           strong_zero);
-    // one launch over every workgroup (atomics), or one launch per colour class (plain RMW:
-    // the classes touch pairwise disjoint y entries, so the result is bitwise reproducible)
-    const bool colored = !img.color_wg_ptr.empty();
-    if (colored) flags |= FLAG_RMW;
-    const size_t nlaunch = colored ? img.color_wg_ptr.size() - 1 : 1;
-    for (size_t c = 0; c < nlaunch; ++c) {
-        const long long wg0 = colored ? img.color_wg_ptr[c] : 0;
-        const long long wg1 = colored ? img.color_wg_ptr[c + 1] : img.nwg_main;
-        if (wg1 <= wg0) continue;
-        const dim3 grid((unsigned)(wg1 - wg0));
-        const unsigned wg_base = (unsigned)wg0;
-        if (!opT) {
-            if (img.has_off)
-                BSM_LAUNCH_PANEL(true, true, grid, block, 0, stream, waves,
-                                   values, rows, cols, xd, yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
-            else
-                BSM_LAUNCH_PANEL(true, false, grid, block, 0, stream, waves,
-                                   values, rows, cols, xd, yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
-        } else {
-            if (img.has_off)
-                BSM_LAUNCH_PANEL(true, true, grid, block, 0, stream, waves,
-                                   values, rows, cols, xd, yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
-            else
-                BSM_LAUNCH_PANEL(false, true, grid, block, 0, stream, waves,
-                                   values, rows, cols, xd, yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
-        }
+    if (gather) {
+        ws = (T *)img.d_ws;
+        flags |= FLAG_GATHER;
     }
+    if (!gather && r.hi > r.lo && (strong_zero || !is_one(beta)))
+        hipLaunchKernelGGL((scale_kernel<T>), dim3(scale_blocks<T>(r.hi - r.lo)), dim3(256), 0, stream, yd, 0LL, r.lo, r.hi,
+                           beta, strong_zero);
+    if (!img.color_wg_ptr.empty()) flags |= FLAG_RMW;
+    for_each_launch(img, false, [&](const WaveWork *waves, dim3 grid, unsigned wg_base) {
+        with_halves(opT, img.has_off, [&](auto fwd, auto trn) { panel(fwd, trn, waves, grid, wg_base); });
+    });
+    const long long ylen = opT ? img.ncols : img.nrows;
     if (gather && ylen > 0) {
         const int k = opT ? 1 : 0;
         const long long nblk = (ylen + 255) / 256;
-        hipLaunchKernelGGL((gather_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, stream, yd, ylen, lo, hi,
+        hipLaunchKernelGGL((gather_kernel<T>), dim3((unsigned)nblk), dim3(256), 0, stream, yd, ylen, r.lo, r.hi,
                            (const long long *)img.d_inv_ptr[k], (const int *)img.d_inv_idx[k], (const T *)ws,
                            alpha, beta, strong_zero);
     }
     return hipGetLastError();
+}
+
+// loads per lane in flight of the one-column kernels: L = 4 where it was measured faster, on products that are fused
+// (symmetric operators, accumulating), 8 everywhere else.  Every one-column launch takes it -- single products and the
+// single columns a multi-RHS batch ladder ends with.
+template <typename T>
+static hipError_t launch_one(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
+                             int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
+    // complex64: 61 VGPRs, 8 waves per SIMD; with 8 the fused instance needs 93-95 (5 waves): tiled BEM fixture
+    // 105.9 -> 95.1 us (profiles/r04_c64_l4.txt).  fp32, SHORT panels only: tiled BEM fixture 48.6 -> 46.5 us;
+    // 16-256-row operators lose 3-5 % with it and keep 8 (profiles/r04_fused_loads_per_lane.txt)
+    constexpr int LF = std::is_same<T, float>::value ? BSM_F32_L : std::is_same<T, double>::value ? BSM_F64_L
+                     : std::is_same<T, c64>::value ? BSM_C64_L : BSM_C128_L;
+    const bool fused = img.has_off && !img.exclusive_fwd && (!std::is_same<T, float>::value || img.mean_rows < 32.f);
+    if (LF != 8 && fused) return launch_typed<T, LF>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
+    return launch_typed<T, 8>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
 }
 
 // K right-hand sides per pass
@@ -2379,64 +2408,29 @@ template <typename T, int L, int K>
 static hipError_t launch_typed_multi(const DeviceImage &img, bool opT, bool conj, const T *xd, long long ldx,
                                      T *yd, long long ldy, T alpha, T beta, int strong_zero,
                                      hipStream_t stream, const long long *zrange, int kact = K) {
-    int flags = 0;
-    if (strong_zero) flags |= FLAG_STRONG_ZERO;
-    if (conj) flags |= FLAG_CONJ;
-    if (opT) flags |= FLAG_OPT;
+    int flags = base_flags(opT, conj, strong_zero);
     if (kact < K) flags |= kact << FLAG_KACT_SHIFT;  // a padded batch: kact of the K slots carry columns
-#ifdef BSM_EXPERIMENT
-    if (const char *v = std::getenv("BSM_DEBUG_FLAGS")) flags |= std::atoi(v) << 16;
-#endif
-    const WaveWork *waves = (const WaveWork *)img.d_waves;
     const uint4 *values = (const uint4 *)img.d_values;
     const int *rows = (const int *)img.d_rows;
     const int *cols = (const int *)img.d_cols;
-    const dim3 block(64 * kWavesPerWg);
+    auto panel = [&](auto fwd, auto trn, const WaveWork *waves, dim3 grid, unsigned wg_base) {
+        hipLaunchKernelGGL((panel_kernel_multi<T, L, decltype(fwd)::value, decltype(trn)::value, K>), grid, dim3(64 * kWavesPerWg),
+                           0, stream, waves, values, rows, cols, xd, ldx, yd, ldy, alpha, beta, flags, wg_base);
+    };
     if (!opT && img.exclusive_fwd) {
         flags |= FLAG_DIRECT;
         if (img.nwg_total > 0)
-            hipLaunchKernelGGL((panel_kernel_multi<T, L, true, false, K>), dim3((unsigned)img.nwg_total), block,
-                               0, stream, waves, values, rows, cols, xd, ldx, yd, ldy, alpha, beta, flags, 0u);
+            panel(std::true_type{}, std::false_type{}, (const WaveWork *)img.d_waves, dim3((unsigned)img.nwg_total), 0u);
         return hipGetLastError();
     }
-    const long long ylen = opT ? img.ncols : img.nrows;
-    long long lo = 0, hi = ylen;
-    if (!opT) {
-        lo = img.own_lo;
-        hi = img.own_hi;
-    }
-    if (zrange) {  // multi-device fan-out: see launch_typed
-        lo = zrange[0];
-        hi = zrange[1];
-    }
-    if (hi > lo && (strong_zero || !is_one(beta)))
-        hipLaunchKernelGGL((scale_kernel<T>), dim3(scale_blocks<T>(hi - lo), (unsigned)kact), dim3(256), 0, stream, yd, ldy, lo,
-                           hi, beta, strong_zero);
-    const bool colored = !img.color_wg_ptr.empty();
-    if (colored) flags |= FLAG_RMW;
-    // the coarser split of the panels (bsm_analysis.h: Tunables::multi_wave_bytes), where the image has one
-    long long nwg_main = img.nwg_main;
-    if (img.d_waves_multi && !colored) {
-        waves = (const WaveWork *)img.d_waves_multi;
-        nwg_main = img.nwg_multi;
-    }
-    const size_t nlaunch = colored ? img.color_wg_ptr.size() - 1 : 1;
-    for (size_t c = 0; c < nlaunch; ++c) {
-        const long long wg0 = colored ? img.color_wg_ptr[c] : 0;
-        const long long wg1 = colored ? img.color_wg_ptr[c + 1] : nwg_main;
-        if (wg1 <= wg0) continue;
-        const dim3 grid((unsigned)(wg1 - wg0));
-        const unsigned wg_base = (unsigned)wg0;
-        if (!opT && !img.has_off)
-            hipLaunchKernelGGL((panel_kernel_multi<T, L, true, false, K>), grid, block, 0, stream, waves, values,
-                               rows, cols, xd, ldx, yd, ldy, alpha, beta, flags, wg_base);
-        else if (img.has_off)
-            hipLaunchKernelGGL((panel_kernel_multi<T, L, true, true, K>), grid, block, 0, stream, waves, values,
-                               rows, cols, xd, ldx, yd, ldy, alpha, beta, flags, wg_base);
-        else
-            hipLaunchKernelGGL((panel_kernel_multi<T, L, false, true, K>), grid, block, 0, stream, waves, values,
-                               rows, cols, xd, ldx, yd, ldy, alpha, beta, flags, wg_base);
-    }
+    const YRange r = y_range(img, opT, zrange);
+    if (r.hi > r.lo && (strong_zero || !is_one(beta)))
+        hipLaunchKernelGGL((scale_kernel<T>), dim3(scale_blocks<T>(r.hi - r.lo), (unsigned)kact), dim3(256), 0, stream, yd, ldy,
+                           r.lo, r.hi, beta, strong_zero);
+    if (!img.color_wg_ptr.empty()) flags |= FLAG_RMW;
+    for_each_launch(img, true, [&](const WaveWork *waves, dim3 grid, unsigned wg_base) {
+        with_halves(opT, img.has_off, [&](auto fwd, auto trn) { panel(fwd, trn, waves, grid, wg_base); });
+    });
     return hipGetLastError();
 }
 
@@ -2469,6 +2463,7 @@ static int il_real_min_cols() {
 }
 bool il_applies(const DeviceImage &img, bool opT, long long nrhs) {
     const bool cplx = img.dtype >= 2;
+    if (nrhs < 2) return false;  // (one column: launch_mul's one-column kernels, whatever the thresholds say)
     if (il_mode() == 0 || nrhs < (cplx ? mfma_min_cols() : il_real_min_cols())) return false;
     if (!opT && img.exclusive_fwd) return false;   // plain stores with beta fused: nothing to gain
     if (!img.color_wg_ptr.empty()) return false;   // coloured launches keep their bitwise reproducible read-modify-write
@@ -2488,12 +2483,7 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     constexpr int CS = ILT<T>::CPLX ? 2 * KK : KK;  // components per vector index (8 or 16)
     const long long xlen = opT ? img.nrows : img.ncols, ylen = opT ? img.ncols : img.nrows;
     if (xlen > il.rows || ylen > il.rows) return hipErrorInvalidValue;
-    int flags = 0;
-    if (opT) flags |= FLAG_OPT;
-    if (conj) flags |= FLAG_CONJ;
-#ifdef BSM_EXPERIMENT
-    if (const char *v = std::getenv("BSM_DEBUG_FLAGS")) flags |= std::atoi(v) << 16;
-#endif
+    const int flags = base_flags(opT, conj, 0);  // (beta meets y in the finish pass)
     hipError_t e = hipSuccess;
     if (!il.w_clean) e = hipMemsetAsync(il.w, 0, (size_t)il.rows * 128, stream);
     il.w_clean = false;  // (until the finish pass has been enqueued)
@@ -2501,13 +2491,12 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     if (xlen > 0)
         hipLaunchKernelGGL((il_pack_kernel<T, KK>), dim3((unsigned)((xlen + 255) / 256)), dim3(256), 0, stream, xd, ldx, xlen, alpha,
                            kact, (T *)il.xr);
-    const WaveWork *waves = (const WaveWork *)(img.d_waves_multi ? img.d_waves_multi : img.d_waves);
-    const long long nwg = img.d_waves_multi ? img.nwg_multi : img.nwg_main;
     const uint4 *values = (const uint4 *)img.d_values;
     const int *rows = (const int *)img.d_rows, *cols = (const int *)img.d_cols;
     const R *xr = (const R *)il.xr;
     R *w = (R *)il.w;
-    if (nwg > 0) {
+    // (never coloured -- il_applies: one launch over every workgroup)
+    for_each_launch(img, true, [&](const WaveWork *waves, dim3 plain, unsigned) {
         // BSM_IL_XCD = R: XCD-aware workgroup order, runs of R consecutive workgroups per XCD (0: plain order).  Default:
         // 16 for operators with tall panels (C3 x 16 312 -> 262 us -- neighbouring 64-row panels read the same 9 x 64
         // lines of Xr, L2 hits 0.5 M -> of 9.5 M read requests with the plain order; R = 4 ... 64 alike), plain for
@@ -2518,62 +2507,41 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
         }();
         const bool small = img.max_rows <= 32;
         const int xcd = xcd_env >= 0 ? xcd_env : (small ? 0 : 16);
-        const unsigned nblk = (unsigned)nwg;
+        const unsigned nblk = plain.x;
         const unsigned xcd_run = xcd > 0 ? (unsigned)xcd : 0u, span = 8u * xcd_run;
         const dim3 grid(xcd_run ? (nblk + span - 1) / span * span : nblk), block(64 * kWavesPerWg);
-#define BSM_IL_LAUNCH(MR)                                                                                                              \
-    do {                                                                                                                           \
-        if (!opT && !img.has_off)                                                                                                  \
-            hipLaunchKernelGGL((panel_kernel_il<T, MR, true, false, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,  \
-                               flags, nblk, xcd_run);                                                                                        \
-        else if (img.has_off)                                                                                                      \
-            hipLaunchKernelGGL((panel_kernel_il<T, MR, true, true, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,   \
-                               flags, nblk, xcd_run);                                                                                        \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((panel_kernel_il<T, MR, false, true, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,  \
-                               flags, nblk, xcd_run);                                                                                        \
-    } while (0)
-        // (tall panels: all row blocks of the next 16 columns in flight -- il_panel's DEEP form, worth 1-6 % over one step
-        // ahead with the XCD-aware order, profiles/r05_il_tall_panels.txt)
-        if (small)
-            BSM_IL_LAUNCH(2);
-        else
-            BSM_IL_LAUNCH(4);
-#undef BSM_IL_LAUNCH
-    }
+        with_halves(opT, img.has_off, [&](auto fwd, auto trn) {
+            constexpr bool FWD = decltype(fwd)::value, TRN = decltype(trn)::value;
+            // (tall panels: all row blocks of the next 16 columns in flight -- il_panel's DEEP form, worth 1-6 % over one
+            // step ahead with the XCD-aware order, profiles/r05_il_tall_panels.txt)
+            if (small)
+                hipLaunchKernelGGL((panel_kernel_il<T, 2, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
+                                   flags, nblk, xcd_run);
+            else
+                hipLaunchKernelGGL((panel_kernel_il<T, 4, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
+                                   flags, nblk, xcd_run);
+        });
+    });
     // Y = beta * Y + W over the rows this handle scales (all of them for op T / C), Y += W elsewhere; W = 0 behind
-    long long lo = 0, hi = ylen;
-    if (!opT) {
-        lo = img.own_lo;
-        hi = img.own_hi;
-    }
-    if (zrange) {  // multi-device fan-out: the y entries this part's `y .*= beta` covers (see launch_typed)
-        lo = zrange[0];
-        hi = zrange[1];
-    }
+    const YRange r = y_range(img, opT, zrange);
     const T one = make_scalar<T>(1.0);
     auto finish = [&](long long a, long long b, T bt, int sz) {
         if (b > a)
             hipLaunchKernelGGL((il_finish_kernel<T, KK>), dim3((unsigned)((b - a + 255) / 256)), dim3(256), 0, stream, yd, ldy, a, b, bt,
                                sz, kact, (T *)il.w);
     };
-    finish(0, lo, one, 0);
-    finish(lo, hi, beta, strong_zero);
-    finish(hi, ylen, one, 0);
+    finish(0, r.lo, one, 0);
+    finish(r.lo, r.hi, beta, strong_zero);
+    finish(r.hi, ylen, one, 0);
     e = hipGetLastError();
     if (e == hipSuccess) il.w_clean = true;
     return e;
 }
 
 template <typename T>
-static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj, long long nrhs,
-                                     const void *x, long long ldx, void *y, long long ldy,
-                                     const void *alpha_p, const void *beta_p, int strong_zero,
-                                     hipStream_t stream, const long long *zrange, ILWork *il) {
-    const T alpha = load_scalar<T>(alpha_p, 1.0);
-    const T beta = load_scalar<T>(beta_p, 0.0);
-    const T *xd = (const T *)x;
-    T *yd = (T *)y;
+static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj, long long nrhs, const T *xd, long long ldx,
+                                     T *yd, long long ldy, T alpha, T beta, int strong_zero, hipStream_t stream,
+                                     const long long *zrange, ILWork *il) {
     long long k = 0;
     hipError_t e = hipSuccess;
     // batches of 8, then 4, then single columns: A is streamed once per batch.  The 8-column
@@ -2657,46 +2625,26 @@ static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj
         k += rem;
     }
     for (; e == hipSuccess && k < nrhs; ++k)
-        e = launch_typed<T, 8>(img, opT, conj, xd + k * ldx, yd + k * ldy, alpha_p, beta_p, strong_zero, stream, false, zrange);
+        e = launch_one<T>(img, opT, conj, xd + k * ldx, yd + k * ldy, alpha, beta, strong_zero, stream, false, zrange);
     return e;
 }
 
-hipError_t launch_mul_multi(const DeviceImage &img, bool opT, bool conj, long long nrhs, const void *x,
-                            long long ldx, void *y, long long ldy, const void *alpha, const void *beta,
-                            int strong_zero, hipStream_t stream, const long long *zrange, ILWork *il) {
+hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, const void *x, long long ldx, void *y,
+                      long long ldy, const void *alpha_p, const void *beta_p, int strong_zero, hipStream_t stream,
+                      bool use_gather, const long long *zrange, ILWork *il) {
+    auto run = [&](auto t) {
+        using T = decltype(t);
+        const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);
+        const T *xd = (const T *)x;
+        T *yd = (T *)y;
+        if (K == 1) return launch_one<T>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
+        return launch_multi_typed<T>(img, opT, conj, K, xd, ldx, yd, ldy, alpha, beta, strong_zero, stream, zrange, il);
+    };
     switch (img.dtype) {
-        case 0: return launch_multi_typed<float>(img, opT, conj, nrhs, x, ldx, y, ldy, alpha, beta, strong_zero, stream, zrange, il);
-        case 1: return launch_multi_typed<double>(img, opT, conj, nrhs, x, ldx, y, ldy, alpha, beta, strong_zero, stream, zrange, il);
-        case 2: return launch_multi_typed<c64>(img, opT, conj, nrhs, x, ldx, y, ldy, alpha, beta, strong_zero, stream, zrange, il);
-        case 3: return launch_multi_typed<c128>(img, opT, conj, nrhs, x, ldx, y, ldy, alpha, beta, strong_zero, stream, zrange, il);
-    }
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, const void *x, void *y,
-                      const void *alpha, const void *beta, int strong_zero, hipStream_t stream,
-                      bool use_gather, const long long *zrange) {
-    switch (img.dtype) {
-        case 0:
-            // fp32 fused products of SHORT panels: 4 loads per lane (tiled BEM fixture 48.6 -> 46.5 us; 16-256-row
-            // operators lose 3-5 % with it and keep 8: profiles/r04_fused_loads_per_lane.txt)
-            if (BSM_F32_L != 8 && img.has_off && !img.exclusive_fwd && img.mean_rows < 32.f)
-                return launch_typed<float, BSM_F32_L>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-            return launch_typed<float, 8>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-        case 1:
-            if (BSM_F64_L != 8 && img.has_off && !img.exclusive_fwd)
-                return launch_typed<double, BSM_F64_L>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-            return launch_typed<double, 8>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-        // complex64 fused products: 4 loads per lane in flight -- 61 VGPRs, 8 waves per SIMD; with 8 the fused instance
-        // needs 93-95 (5 waves): tiled BEM fixture 105.9 -> 95.1 us (profiles/r04_c64_l4.txt)
-        case 2:
-            if (img.has_off && !img.exclusive_fwd)
-                return launch_typed<c64, BSM_C64_L>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-            return launch_typed<c64, 8>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-        case 3:
-            if (BSM_C128_L != 8 && img.has_off && !img.exclusive_fwd)
-                return launch_typed<c128, BSM_C128_L>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
-            return launch_typed<c128, 8>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather, zrange);
+        case 0: return run(float{});
+        case 1: return run(double{});
+        case 2: return run(c64{});
+        case 3: return run(c128{});
     }
     return hipErrorInvalidValue;
 }

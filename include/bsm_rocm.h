@@ -317,7 +317,8 @@ int bsm_host_unregister(void *ptr);
  * columns = 16 real ones = N of v_mfma_{f64,f32}_16x16x4).  X is size(op(A),2) x nrhs
  * and Y is size(op(A),1) x nrhs, both column-major with leading dimensions ldx / ldy (elements).
  * Every other argument as in bsm_mul; each column gives what nrhs = 1 semantics prescribe (same
- * alpha, beta, strong zero). */
+ * alpha, beta, strong zero).  nrhs = 1 is bsm_mul: the same kernels and, on a BSM_ACC_GATHER handle, the
+ * same bitwise reproducible gather path. */
 int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y,
                   int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace,
                   void *stream);

@@ -739,6 +739,11 @@ def test_gather_mode_parity_and_determinism(torch_cuda, bsm, oracle, key):
         first = gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.5, 2.0, False)
         for _ in range(3):
             assert np.array_equal(first, gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.5, 2.0, False))
+        # one column through bsm_mul_multi (an (n, 1) Y) is bsm_mul: the same gather path, bitwise
+        Y = torch_cuda.from_numpy(y0.copy()).cuda()[:, None]
+        bsm.mul(Y, wrap(bsm, A, op), torch_cuda.from_numpy(x).cuda()[:, None], 0.5, 2.0)
+        torch_cuda.cuda.synchronize()
+        assert np.array_equal(first, Y[:, 0].cpu().numpy())
 
 
 def test_gather_mode_other_types(torch_cuda, bsm, oracle):
