@@ -10,6 +10,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BSM_LIB", os.path.join(_HERE, "libbsmrocm.so"))  # BSM_LIB: developer A/B builds
 
 BSM_F32, BSM_F64, BSM_C64, BSM_C128 = 0, 1, 2, 3
+# mixed precision: double / complex double vectors over values stored as float / complex float (include/bsm_rocm.h)
+BSM_F64_F32, BSM_C128_C64 = 4, 5
 BSM_OP_N, BSM_OP_T, BSM_OP_C = 0, 1, 2
 BSM_MEM_HOST, BSM_MEM_DEVICE = 0, 1
 BSM_SCHED_SERIAL, BSM_SCHED_DYNAMIC = 0, 1

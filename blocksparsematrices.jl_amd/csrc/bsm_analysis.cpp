@@ -261,26 +261,41 @@ struct Item {
     int32_t color;
 };
 
+// the value an entry is stored as: the caller's bits (same type), or the IEEE round-to-nearest-even cast of a double to
+// float (x86-64 SSE conversion under the default rounding mode, no flush-to-zero: subnormals are kept, overflow gives
+// +-inf) -- bit for bit what numpy's astype(float32) gives
+struct C64h {
+    float re, im;
+};
+struct C128h {
+    double re, im;
+};
+template <typename U> inline const U &stored(const U &v) { return v; }
+inline float stored(double v) { return (float)v; }
+inline C64h stored(const C128h &v) { return C64h{(float)v.re, (float)v.im}; }
+
 // scattered variant: block column w lands at merged panel column dstpos[w] (the merged column
 // list of a row group with index lists is kept SORTED by x index, see build())
-template <typename U>
-void pack_chunk_perm(const U *src, int64_t ld, int ra, int mc, int64_t n, const int32_t *dstpos, int E,
+// Entries are copied as they are, or -- mixed-precision handles (BSM_F64_F32, BSM_C128_C64) -- rounded once from the
+// caller's double-precision type V to the stored single-precision type U (stored() above)
+template <typename U, typename V = U>
+void pack_chunk_perm(const V *src, int64_t ld, int ra, int mc, int64_t n, const int32_t *dstpos, int E,
                      bool trans, U *dst) {
     for (int64_t w = 0; w < n; w++) {
         const int64_t mp = dstpos[w];
         U *d = dst + ((mp / E) * mc) * E + (mp % E);
         if (!trans) {
-            const U *col = src + ra + w * ld;
-            for (int i = 0; i < mc; i++) d[(int64_t)i * E] = col[i];
+            const V *col = src + ra + w * ld;
+            for (int i = 0; i < mc; i++) d[(int64_t)i * E] = stored(col[i]);
         } else {
-            const U *row = src + w + (int64_t)ra * ld;
-            for (int i = 0; i < mc; i++) d[(int64_t)i * E] = row[(int64_t)i * ld];
+            const V *row = src + w + (int64_t)ra * ld;
+            for (int i = 0; i < mc; i++) d[(int64_t)i * E] = stored(row[(int64_t)i * ld]);
         }
     }
 }
 
-template <typename U>
-void pack_chunk(const U *src, int64_t ld, int ra, int mc, int64_t n, int64_t woff, int E, bool trans,
+template <typename U, typename V = U>
+void pack_chunk(const V *src, int64_t ld, int ra, int mc, int64_t n, int64_t woff, int E, bool trans,
                 U *dst) {
     // dst[(s*mc + i)*E + e] = B[ra+i, w],  s*E + e = woff + w;
     // B[r, w] = src[r + w*ld] (stored as is) or src[w + r*ld] (logical block = transpose of storage)
@@ -293,13 +308,13 @@ void pack_chunk(const U *src, int64_t ld, int ra, int mc, int64_t n, int64_t wof
         U *d = dst + (s * mc) * E;
         if (!trans) {
             for (int e = e_lo; e < e_hi; e++) {
-                const U *col = src + ra + (w0 + e) * ld;
-                for (int i = 0; i < mc; i++) d[(int64_t)i * E + e] = col[i];
+                const V *col = src + ra + (w0 + e) * ld;
+                for (int i = 0; i < mc; i++) d[(int64_t)i * E + e] = stored(col[i]);
             }
         } else {
             for (int i = 0; i < mc; i++) {
-                const U *row = src + w0 + (int64_t)(ra + i) * ld;
-                for (int e = e_lo; e < e_hi; e++) d[(int64_t)i * E + e] = row[e];
+                const V *row = src + w0 + (int64_t)(ra + i) * ld;
+                for (int e = e_lo; e < e_hi; e++) d[(int64_t)i * E + e] = stored(row[e]);
             }
         }
     }
@@ -401,9 +416,13 @@ std::string Analysis::build(int mtype_, int dtype_, int64_t nrows_, int64_t ncol
 
 // ---- validation, statistics ----------------------------------------------------------------------
 std::string Analysis::stage_validate(const std::vector<BlockIn> &blocks, BuildState &st) {
-    static const int kEs[4] = {4, 8, 8, 16};
-    if (dtype < 0 || dtype > 3) return "unknown dtype";
+    // storage / vector element bytes: BSM_F32, BSM_F64, BSM_C64, BSM_C128, then the mixed BSM_F64_F32 and BSM_C128_C64
+    // (values stored in single precision, vectors in double)
+    static const int kEs[6] = {4, 8, 8, 16, 4, 8};
+    static const int kVs[6] = {4, 8, 8, 16, 8, 16};
+    if (dtype < 0 || dtype > 5) return "unknown dtype";
     es = kEs[dtype];
+    vs = kVs[dtype];
     E = 16 / es;
     if (nrows < 0 || ncols < 0) return "negative matrix size";
     if (nrows > INT32_MAX - 64 || ncols > INT32_MAX - 64) return "matrix dimension exceeds int32 range";
@@ -451,7 +470,7 @@ std::string Analysis::stage_validate(const std::vector<BlockIn> &blocks, BuildSt
             meta = 8 * ((int64_t)rowptr.size() + (int64_t)rowindices.size() + 4 * nb);
         else
             meta = 8 * idx_meta;
-        alg_bytes = stored_entries * es + meta + ncols * es + nrows * es;
+        alg_bytes = stored_entries * es + meta + ncols * vs + nrows * vs;
     }
 
     return "";
@@ -864,7 +883,11 @@ std::string Analysis::stage_pack_values(const std::vector<BlockIn> &blocks, Buil
         const BlockIn &B = blocks[c.blk];
         if (group_perm[c.group]) {
             const int32_t *dp = colpos.data() + groups[c.group].col_off + c.woff;
-            if (es == 4)
+            if (dtype == 4)
+                pack_chunk_perm<float, double>((const double *)B.data, B.ld, c.ra, c.mc, B.n, dp, E, B.trans, (float *)dst);
+            else if (dtype == 5)
+                pack_chunk_perm<C64h, C128h>((const C128h *)B.data, B.ld, c.ra, c.mc, B.n, dp, E, B.trans, (C64h *)dst);
+            else if (es == 4)
                 pack_chunk_perm<uint32_t>((const uint32_t *)B.data, B.ld, c.ra, c.mc, B.n, dp, E, B.trans, (uint32_t *)dst);
             else if (es == 8)
                 pack_chunk_perm<uint64_t>((const uint64_t *)B.data, B.ld, c.ra, c.mc, B.n, dp, E, B.trans, (uint64_t *)dst);
@@ -872,7 +895,11 @@ std::string Analysis::stage_pack_values(const std::vector<BlockIn> &blocks, Buil
                 pack_chunk_perm<U16>((const U16 *)B.data, B.ld, c.ra, c.mc, B.n, dp, E, B.trans, (U16 *)dst);
             return;
         }
-        if (es == 4)
+        if (dtype == 4)
+            pack_chunk<float, double>((const double *)B.data, B.ld, c.ra, c.mc, B.n, c.woff, E, B.trans, (float *)dst);
+        else if (dtype == 5)
+            pack_chunk<C64h, C128h>((const C128h *)B.data, B.ld, c.ra, c.mc, B.n, c.woff, E, B.trans, (C64h *)dst);
+        else if (es == 4)
             pack_chunk<uint32_t>((const uint32_t *)B.data, B.ld, c.ra, c.mc, B.n, c.woff, E, B.trans, (uint32_t *)dst);
         else if (es == 8)
             pack_chunk<uint64_t>((const uint64_t *)B.data, B.ld, c.ra, c.mc, B.n, c.woff, E, B.trans, (uint64_t *)dst);
@@ -1175,9 +1202,9 @@ void Analysis::stage_windows(BuildState &st) {
         // name every y entry twice on average), so sums that fall into one dense index range are added
         // up in LDS and leave the CU once, as contiguous atomics.  The range need not hold EVERYTHING
         // the workgroup emits -- a panel usually has a few far columns -- it is the best-filled range
-        // of at most window_entries(es) indices (sliding window over the sorted emissions); what falls
+        // of at most window_entries(vs) indices (sliding window over the sorted emissions); what falls
         // outside goes to y directly.
-        const int64_t cap = window_entries(es);
+        const int64_t cap = window_entries(vs);  // the window holds y entries: vector type
         std::vector<int64_t> em;
         win_emissions = win_inside = win_flushed = 0;
         for (size_t wg = 0; wg + kWavesPerWg <= (size_t)nwg_main * kWavesPerWg; wg += kWavesPerWg) {

@@ -146,8 +146,10 @@ static_assert(sizeof(PackChunk) == 48, "PackChunk must be 48 bytes");
 class Analysis {
   public:
     int mtype = 0, dtype = 0;
-    int es = 8;  // element size in bytes
-    int E = 2;   // columns per strip
+    int es = 8;  // element size in bytes of the STORED values (strips, placement, packing)
+    int vs = 8;  // element size in bytes of x, y, alpha, beta and of every sum (LDS windows, gather workspace); = es
+                 // except for the mixed-precision dtypes (BSM_F64_F32, BSM_C128_C64: values single, vectors double)
+    int E = 2;   // columns per strip (16 / es)
     int64_t nrows = 0, ncols = 0;
     AnalysisOptions opt;
     Tunables tun;

@@ -247,7 +247,7 @@ void fill_image(const Analysis &an, const bsm_options &o, bool use_own, DeviceIm
     img.device_bytes = (long long)((size_t)an.value_bytes + an.rows.size() * 4 + an.cols.size() * 4 +
                                    (an.waves.size() + an.waves_multi.size()) * sizeof(WaveWork));
     if (an.gather)
-        img.device_bytes += (long long)((an.ws_slots + 8) * an.es + (an.inv_ptr[0].size() + an.inv_ptr[1].size()) * 8 +
+        img.device_bytes += (long long)((an.ws_slots + 8) * an.vs + (an.inv_ptr[0].size() + an.inv_ptr[1].size()) * 8 +
                                         (an.inv_idx[0].size() + an.inv_idx[1].size()) * 4);
 }
 
@@ -270,7 +270,7 @@ hipError_t upload_image(Analysis &an, DeviceImage &img, int dev) {
             if (e == hipSuccess) e = upload(an.inv_idx[k], &img.d_inv_idx[k], total);
         }
         if (e == hipSuccess) {
-            const size_t wsb = (size_t)(an.ws_slots + 8) * (size_t)an.es;
+            const size_t wsb = (size_t)(an.ws_slots + 8) * (size_t)an.vs;  // sums: vector type
             e = hipMalloc(&img.d_ws, wsb);
             if (e == hipSuccess) e = hipMemset(img.d_ws, 0, wsb);
             total += (long long)wsb;
@@ -416,7 +416,7 @@ hipError_t device_pack(Analysis &an, void **d_values) {
             if (e == hipSuccess)
                 e = hipMemcpyAsync(d_cp, an.pack_colpos.data(), an.pack_colpos.size() * 4, hipMemcpyHostToDevice, nullptr);
         }
-        if (e == hipSuccess) e = launch_pack(an.es, d_plan, (long long)an.pack_plan.size(), d_cp, *d_values, nullptr);
+        if (e == hipSuccess) e = launch_pack(an.es, an.vs, d_plan, (long long)an.pack_plan.size(), d_cp, *d_values, nullptr);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (d_plan) (void)hipFree(d_plan);
@@ -901,6 +901,9 @@ int create_handle(int mtype, int dtype, int64_t nrows, int64_t ncols, const std:
         A->blk_m[(size_t)ids[b]] = in[b].m;
         A->blk_n[(size_t)ids[b]] = in[b].n;
     }
+    if (o.ctx && (dtype == BSM_F64_F32 || dtype == BSM_C128_C64))
+        return fail(BSM_ERR_UNSUPPORTED, "mixed-precision storage (BSM_F64_F32 / BSM_C128_C64) is single-device only: "
+                                         "create without bsm_options.ctx");
     if (o.ctx) {
         AnalysisOptions ao = to_aopt(o, nullptr);
         ao.meta_only = true;
@@ -1294,7 +1297,7 @@ extern "C" int bsm_rowcolvals(bsm_matrix_t A, int64_t *rows, int64_t *cols, void
         if (*count < A->an.nnz) return fail(BSM_ERR_INVALID, "output buffers too small");
         if (!A->on_device) return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
         if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-        const size_t es = (size_t)A->an.es;
+        const size_t es = (size_t)A->an.vs;  // the stored values leave widened to the vector type
         // one image per device part (a single one for ordinary handles); parts are written one after another
         std::vector<std::pair<const Analysis *, const DeviceImage *>> imgs;
         if (A->dist)
@@ -1395,6 +1398,8 @@ extern "C" int bsm_stream_destroy(void *stream) {
 
 extern "C" int bsm_vec_add_segments(int dtype, void *y, int32_t nseg, const int64_t *offset, const void *const *src,
                                     const int64_t *len, void *stream) {
+    if (dtype == BSM_F64_F32 || dtype == BSM_C128_C64)
+        return fail(BSM_ERR_INVALID, "bsm_vec_add_segments takes a vector type (BSM_F32 .. BSM_C128), not a mixed storage code");
     if (dtype < 0 || dtype > 3) return fail(BSM_ERR_INVALID, "bad dtype");
     if (nseg < 0 || (nseg > 0 && (!y || !offset || !src || !len))) return fail(BSM_ERR_INVALID, "null argument");
     // disjoint segments only: the launch adds without atomics
@@ -1518,7 +1523,7 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     }
     if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "bad memspace");
     // host vectors: stage through device buffers (PCIe), synchronous
-    const size_t es = (size_t)A->an.es;
+    const size_t es = (size_t)A->an.vs;
     const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
     const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
     Staging sg;
@@ -1588,6 +1593,9 @@ extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *id
                                  const int64_t *ld, int memspace, void *stream) {
     BSM_GUARDED(
         if (!A) return fail(BSM_ERR_INVALID, "null handle");
+        if (A->an.dtype == BSM_F64_F32 || A->an.dtype == BSM_C128_C64)
+            return fail(BSM_ERR_UNSUPPORTED, "bsm_update_blocks: not available on a mixed-precision handle (BSM_F64_F32 / "
+                                             "BSM_C128_C64); create a new handle from the new blocks");
         if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
         const int64_t nb = (int64_t)A->blk_m.size();
         if (nupd < 0 || nupd > nb) return fail(BSM_ERR_INVALID, "nupd out of range");

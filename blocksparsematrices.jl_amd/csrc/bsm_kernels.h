@@ -79,7 +79,7 @@ hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, 
                       long long ldy, const void *alpha, const void *beta, int strong_zero, hipStream_t stream,
                       bool use_gather, const long long *zrange, ILWork *il);
 
-// rowcolvals(A): COO triples (1-based int64 rows / cols, values of the image's element type) written from
+// rowcolvals(A): COO triples (1-based int64 rows / cols, values of the image's vector type) written from
 // the packed device image; d_out_off[w] = first output slot of wave descriptor w (host prefix sum of
 // m * ncols + m * #KIND_OFF columns)
 hipError_t launch_export_coo(int dtype, const void *d_waves, long long nwaves, const void *d_out_off,
@@ -87,8 +87,9 @@ hipError_t launch_export_coo(int dtype, const void *d_waves, long long nwaves, c
                              void *oval, hipStream_t stream);
 
 // executes Analysis::pack_plan on the device (blocks already in HBM): d_plan = PackChunk[nchunks],
-// d_colpos = int32 placements (may be null when no chunk is scattered), es = element bytes
-hipError_t launch_pack(int es, const void *d_plan, long long nchunks, const void *d_colpos, void *d_values,
+// d_colpos = int32 placements (may be null when no chunk is scattered), es = stored element bytes, src_es = the caller's
+// (= es, or 2 es for the mixed-precision dtypes: the values are rounded to the stored type as they are placed)
+hipError_t launch_pack(int es, int src_es, const void *d_plan, long long nchunks, const void *d_colpos, void *d_values,
                        hipStream_t stream);
 
 // synthetic operators generated in HBM (include/bsm_synth.h); d_desc = SynthBlock[nblocks]

@@ -48,6 +48,10 @@ template <> struct TT<c128> {
 template <typename T> struct alignas(16) Vec16 {
     T v[TT<T>::E];
 };
+// N entries of T on a 16-byte boundary (the x entries a strip of a mixed-precision image covers)
+template <typename T, int N> struct alignas(16) XVec {
+    T v[N];
+};
 
 // 16-byte matrix load with the non-temporal hint (global_load_dwordx4 ... nt): every matrix byte
 // is used exactly once per launch.  Measured on a bare streaming read of a C2-sized operator out of
@@ -101,6 +105,12 @@ __device__ __forceinline__ float cj(float a, bool) { return a; }
 __device__ __forceinline__ double cj(double a, bool) { return a; }
 __device__ __forceinline__ c64 cj(c64 a, bool c) { return c64{a.re, c ? -a.im : a.im}; }
 __device__ __forceinline__ c128 cj(c128 a, bool c) { return c128{a.re, c ? -a.im : a.im}; }
+
+// a stored value in the arithmetic type T: mixed-precision images (BSM_F64_F32, BSM_C128_C64) store S = float / c64
+// beside double / c128 vectors, and every stored value is widened in registers before it meets x (exact)
+template <typename T> __device__ __forceinline__ T widen(T, T a) { return a; }
+__device__ __forceinline__ double widen(double, float a) { return (double)a; }
+__device__ __forceinline__ c128 widen(c128, c64 a) { return c128{(double)a.re, (double)a.im}; }
 
 __device__ __forceinline__ float shx(float a, int d) { return __shfl_xor(a, d, 64); }
 __device__ __forceinline__ double shx(double a, int d) { return __shfl_xor(a, d, 64); }
@@ -340,17 +350,21 @@ template <typename T, bool TRN = false> constexpr int x_chunk_cols() {
     return TRN ? 2048 / (int)sizeof(T) : (sizeof(T) >= 16 ? 128 : (sizeof(T) == 8 ? 256 : 512));
 }
 
-template <typename T, int L, int P, bool FWD, bool TRN, bool NT>
+// S: the stored type (= T, or float / c64 under double / c128 vectors).  A strip is 16 bytes of S, i.e. E = 16 /
+// sizeof(S) columns, so a mixed image's strip covers E entries of the T-typed x slice (4 fp64 / 2 complex128).
+template <typename T, int L, int P, bool FWD, bool TRN, bool NT, typename S = T>
 __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict__ values,
                                        const int *__restrict__ rows, const int *__restrict__ cols,
                                        const T *__restrict__ x, T *__restrict__ y, T alpha,
                                        int flags, int lane, T *xs, T *vs, T *win, int win_n,
                                        T *__restrict__ ws) {
-    constexpr int E = TT<T>::E;
+    constexpr int E = TT<S>::E;
     constexpr int G = 64 / P;
     constexpr int V = L * E;
     constexpr int NC = G * L * E;                        // columns covered per iteration
     constexpr int XCH = x_chunk_cols<T, TRN>();            // columns staged per x chunk
+    // the E x entries of one strip, read from the slice as one LDS access (16 bytes; 32 for a mixed image)
+    using XV = typename std::conditional<std::is_same<S, T>::value, Vec16<T>, XVec<T, E>>::type;
     // iterations per transposed emission: the column sums of a whole staged chunk leave the wave
     // together.  Atomics (and the plain stores of the gather mode) sit in the same in-order vmcnt
     // queue as the loads and take 2-3x as long under load (MI355X_MICROARCH.md: ~3000 cycles with
@@ -392,7 +406,7 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
         const bool has_off = (kinds & kKindHasOff) != 0;
         const bool fwd_en = FWD && (!opT || has_off);
         const bool trn_en = TRN && (opT || has_off);
-        const Vec16<T> *__restrict__ vb = reinterpret_cast<const Vec16<T> *>(
+        const Vec16<S> *__restrict__ vb = reinterpret_cast<const Vec16<S> *>(
             values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
         // piece column -> x / y index: up to three inline contiguous runs, else the cols pool
         const int s1w = wd.seg1_w, s1x = wd.seg1_x - wd.seg1_w;
@@ -410,7 +424,7 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
         };
 
         // L independent 16-byte loads per lane: 8 KB of the matrix per wave in flight
-        auto load_b = [&](Vec16<T>(&b)[L], int s0) {
+        auto load_b = [&](Vec16<S>(&b)[L], int s0) {
 #pragma unroll
             for (int l = 0; l < L; ++l) {
                 const int s = s0 + l * G + g;
@@ -418,7 +432,7 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
                     b[l] = NT ? load_stream16(&vb[(uint32_t)(s * m + i)]) : vb[(uint32_t)(s * m + i)];
                 } else {
 #pragma unroll
-                    for (int e = 0; e < E; ++e) b[l].v[e] = zero_of(T{});
+                    for (int e = 0; e < E; ++e) b[l].v[e] = zero_of(S{});
                 }
             }
         };
@@ -491,14 +505,14 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
                 stage_x(c0, std::integral_constant<int, KXM>{});
         };
         // one iteration on the L loaded strips-per-group starting at strip s0 of the chunk [c0, c0 + XCH)
-        auto iteration = [&](Vec16<T>(&b)[L], int s0, int c0, int s_end) {
+        auto iteration = [&](Vec16<S>(&b)[L], int s0, int c0, int s_end) {
             if (fwd_en) {
                 const int cb = (s0 - c0 / E) * E;  // first column of this iteration inside the chunk
 #pragma unroll
                 for (int l = 0; l < L; ++l) {
-                    const Vec16<T> xv = *reinterpret_cast<const Vec16<T> *>(&xs[cb + (l * G + g) * E]);
+                    const XV xv = *reinterpret_cast<const XV *>(&xs[cb + (l * G + g) * E]);
 #pragma unroll
-                    for (int e = 0; e < E; ++e) acc[e] = madd(acc[e], cj(b[l].v[e], cjf), xv.v[e]);
+                    for (int e = 0; e < E; ++e) acc[e] = madd(acc[e], widen(T{}, cj(b[l].v[e], cjf)), xv.v[e]);
                 }
             }
 #ifdef BSM_TRACE
@@ -512,7 +526,7 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
 #pragma unroll
                 for (int l = 0; l < L; ++l)
 #pragma unroll
-                    for (int e = 0; e < E; ++e) vals[l * E + e] = mul(cj(b[l].v[e], cjf), xr);
+                    for (int e = 0; e < E; ++e) vals[l * E + e] = mul(widen(T{}, cj(b[l].v[e], cjf)), xr);
                 int pos = 0, dup = 0;
                 if (!BSM_DBG(DBG_NO_BUTTERFLY)) Butterfly<T, V, P>::run(vals, i, pos, dup);
                 constexpr int CF = (V / P) > 1 ? (V / P) : 1;
@@ -585,7 +599,7 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
                 // row clamped, so that hipcc counts the loads in flight exactly -- docs/experiments_r05.md): 108 VGPRs = 4
                 // waves instead of 6; C2 9.5 -> 12.1 us, C4 slice 301 -> 358, 1 GB VBCRS 166-175 -> 173-191: a wave of one
                 // iteration issues a second, redundant batch, and the waves lost cost more than the overlap gains.
-                Vec16<T> b[L];
+                Vec16<S> b[L];
                 // a wave about to request matrix bytes is served before its SIMD's other waves (which are in
                 // their butterfly / FMA phases): +0.3-2 % on every operator, nothing it costs
                 __builtin_amdgcn_s_setprio(3);
@@ -605,6 +619,8 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
     return a;
 }
 
+template <typename T, bool FWD, bool TRN> constexpr int kMixedWaves = (FWD && TRN && std::is_same<T, double>::value) ? 7 : 6;
+
 // Occupancy is what the small-panel (BEM-shaped) products live on: a small panel is a chain of
 // dependent memory round trips, hidden only by other resident waves.
 //   fp64 forward-only: capped at 80 VGPRs (>= 6 waves per SIMD = 1536 resident workgroups: every
@@ -614,8 +630,12 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
 //     exactly 8 workgroups fit a CU (+11-13 % on 3-28-row fp64 panels over 6 waves).
 //   complex128: capped at 80 (the fused instance compiles to 71: 7 waves).
 //   fp32 / complex64: capped at 96 = 5 waves (fp32 fused compiles to 80: 6), no scratch anywhere.
-template <typename T, int L, bool FWD, bool TRN, bool NT>
+//   mixed precision (S = float / c64 stored under double / complex128 vectors, L = 4: launch_one_mixed): capped at 80
+//     = 6 waves, the fp64 fused instance at 72 = 7 (a cap of 64 left 8 B of scratch; complex128 needs 72 + 8 B under
+//     72).  No scratch anywhere.
+template <typename T, int L, bool FWD, bool TRN, bool NT, typename S = T>
 __global__ void __launch_bounds__(64 * kWavesPerWg) __attribute__((amdgpu_waves_per_eu(
+    !std::is_same<S, T>::value ? kMixedWaves<T, FWD, TRN> :
     (FWD && TRN && (std::is_same<T, double>::value || std::is_same<T, float>::value)) ? 8 :
     (FWD && TRN && std::is_same<T, c128>::value) ? (L == 4 ? 8 : BSM_C128_FUSED_WAVES) :
     (FWD && TRN && std::is_same<T, c64>::value) ? (L == 4 ? 8 : BSM_C64_FUSED_WAVES) :
@@ -660,13 +680,13 @@ __global__ void __launch_bounds__(64 * kWavesPerWg) __attribute__((amdgpu_waves_
     T u = zero_of(T{});
     if (work == WORK_PANEL) {
         if (m <= 8)
-            u = run_panel<T, L, 8, FWD, TRN, NT>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
+            u = run_panel<T, L, 8, FWD, TRN, NT, S>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
         else if (m <= 16)
-            u = run_panel<T, L, 16, FWD, TRN, NT>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
+            u = run_panel<T, L, 16, FWD, TRN, NT, S>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
         else if (m <= 32)
-            u = run_panel<T, L, 32, FWD, TRN, NT>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
+            u = run_panel<T, L, 32, FWD, TRN, NT, S>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
         else
-            u = run_panel<T, L, 64, FWD, TRN, NT>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
+            u = run_panel<T, L, 64, FWD, TRN, NT, S>(wd, values, rows, cols, x, y, alpha, flags, lane, xs[wave], vs[wave], win, win_n, ws);
     }
     BSM_TSTAMP(4);  // the wave's piece is streamed
     const bool direct = (flags & FLAG_DIRECT) != 0;
@@ -2332,8 +2352,8 @@ template <typename F> static void with_halves(bool opT, bool has_off, F &&f) {
         f(std::false_type{}, std::true_type{});
 }
 
-// one right-hand side
-template <typename T, int L>
+// one right-hand side (S: the stored type of the image, = T unless it is a mixed-precision one)
+template <typename T, int L, typename S = T>
 static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
                                int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
     int flags = base_flags(opT, conj, strong_zero);
@@ -2342,16 +2362,22 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
     const int *cols = (const int *)img.d_cols;
     const bool nt = stream_policy(img);
     T *ws = nullptr;  // gather mode: the workspace
-    // one launch of panel_kernel<T, L, FWD, TRN, NT> with NT taken from the run-time policy `nt`
+    bool unreached = false;
+    // one launch of panel_kernel<T, L, FWD, TRN, NT, S> with NT taken from the run-time policy `nt`
     auto panel = [&](auto fwd, auto trn, const WaveWork *waves, dim3 grid, unsigned wg_base) {
         constexpr bool FWD = decltype(fwd)::value, TRN = decltype(trn)::value;
-        const dim3 block(64 * kWavesPerWg);
-        if (nt)
-            hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, true>), grid, block, 0, stream, waves, values, rows, cols, xd, yd,
-                               alpha, beta, flags, wg_base, ws, img.ws_fbase);
-        else
-            hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, false>), grid, block, 0, stream, waves, values, rows, cols, xd, yd,
-                               alpha, beta, flags, wg_base, ws, img.ws_fbase);
+        // mixed precision: only what launch_one_mixed reaches is instantiated (L = 4)
+        if constexpr (!std::is_same<S, T>::value && L != 4) {
+            unreached = true;
+        } else {
+            const dim3 block(64 * kWavesPerWg);
+            if (nt)
+                hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, true, S>), grid, block, 0, stream, waves, values, rows, cols, xd,
+                                   yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
+            else
+                hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, false, S>), grid, block, 0, stream, waves, values, rows, cols, xd,
+                                   yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
+        }
     };
     if (!opT && img.exclusive_fwd) {
         // one launch: every y row has exactly one producer; beta is fused into its store and
@@ -2359,7 +2385,7 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
         flags |= FLAG_DIRECT;
         if (img.nwg_total > 0)
             panel(std::true_type{}, std::false_type{}, (const WaveWork *)img.d_waves, dim3((unsigned)img.nwg_total), 0u);
-        return hipGetLastError();
+        return unreached ? hipErrorNotSupported : hipGetLastError();
     }
     // accumulate mode: y .*= beta over the owned range, then hardware atomics (gather mode: the sums go to the
     // workspace, and a second launch adds them up in a fixed order)
@@ -2384,6 +2410,7 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
                            (const long long *)img.d_inv_ptr[k], (const int *)img.d_inv_idx[k], (const T *)ws,
                            alpha, beta, strong_zero);
     }
+    if (unreached) return hipErrorNotSupported;
     return hipGetLastError();
 }
 
@@ -2401,6 +2428,17 @@ static hipError_t launch_one(const DeviceImage &img, bool opT, bool conj, const 
     const bool fused = img.has_off && !img.exclusive_fwd && (!std::is_same<T, float>::value || img.mean_rows < 32.f);
     if (LF != 8 && fused) return launch_typed<T, LF>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
     return launch_typed<T, 8>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
+}
+
+// Mixed-precision image (S = float / c64 stored, T = double / c128 vectors): 4 loads per lane in flight in every
+// direction.  A lane's 4 strips hold 16 fp64 / 8 complex128 values after widening -- what the fp64 / complex128 instances
+// of L = 8 hold -- and the forward instance with 8 loads needed 96 VGPRs and still spilled (the widened x reads of 8
+// strips: 64 VGPRs), i.e. 5 resident waves against 6-8 with 4.  Several right-hand sides: one of these per column (no
+// one-pass multi-RHS kernels for mixed storage).
+template <typename T, typename S>
+static hipError_t launch_one_mixed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
+                                   int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
+    return launch_typed<T, 4, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
 }
 
 // K right-hand sides per pass
@@ -2462,6 +2500,7 @@ static int il_real_min_cols() {
     return v;
 }
 bool il_applies(const DeviceImage &img, bool opT, long long nrhs) {
+    if (img.dtype > 3) return false;  // mixed-precision images: one-column products only
     const bool cplx = img.dtype >= 2;
     if (nrhs < 2) return false;  // (one column: launch_mul's one-column kernels, whatever the thresholds say)
     if (il_mode() == 0 || nrhs < (cplx ? mfma_min_cols() : il_real_min_cols())) return false;
@@ -2640,11 +2679,24 @@ hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, 
         if (K == 1) return launch_one<T>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
         return launch_multi_typed<T>(img, opT, conj, K, xd, ldx, yd, ldy, alpha, beta, strong_zero, stream, zrange, il);
     };
+    // mixed precision: K one-column products, one after another on the stream (the gather workspace only for K = 1)
+    auto run_mixed = [&](auto t, auto s) {
+        using T = decltype(t);
+        using S = decltype(s);
+        const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);
+        hipError_t e = hipSuccess;
+        for (long long k = 0; k < K && e == hipSuccess; ++k)
+            e = launch_one_mixed<T, S>(img, opT, conj, (const T *)x + k * ldx, (T *)y + k * ldy, alpha, beta, strong_zero,
+                                       stream, use_gather && K == 1, zrange);
+        return e;
+    };
     switch (img.dtype) {
         case 0: return run(float{});
         case 1: return run(double{});
         case 2: return run(c64{});
         case 3: return run(c128{});
+        case 4: return run_mixed(double{}, float{});
+        case 5: return run_mixed(c128{}, c64{});
     }
     return hipErrorInvalidValue;
 }
@@ -2822,13 +2874,14 @@ hipError_t launch_vec_axpby(int dtype, void *y, const void *r, long long n, cons
 // One wave per WaveWork descriptor; its output offset was summed up on the host (no atomics, the
 // order of the triples is fixed).  HBM-bound, one-off.
 // ========================================================================================
-template <typename T>
+// S: the stored type; a mixed-precision image's values leave widened to T
+template <typename T, typename S = T>
 __global__ void __launch_bounds__(64 * kWavesPerWg) export_coo_kernel(const WaveWork *__restrict__ waves, long long nwaves,
                                                          const long long *__restrict__ out_off,
                                                          const uint4 *__restrict__ values, const int *__restrict__ rows,
                                                          const int *__restrict__ cols, long long *__restrict__ orow,
                                                          long long *__restrict__ ocol, T *__restrict__ oval) {
-    constexpr int E = TT<T>::E;
+    constexpr int E = TT<S>::E;
     const long long wv = (long long)blockIdx.x * kWavesPerWg + (threadIdx.x >> 6);
     if (wv >= nwaves) return;
     const int lane = threadIdx.x & 63;
@@ -2836,7 +2889,7 @@ __global__ void __launch_bounds__(64 * kWavesPerWg) export_coo_kernel(const Wave
     if (wd.work != WORK_PANEL || wd.npieces == 0) return;
     const PieceD pc = wd.first;
     const int m = wd.m, ncols = pc.ncols, kinds = pc.kind;
-    const T *__restrict__ vb = reinterpret_cast<const T *>(values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
+    const S *__restrict__ vb = reinterpret_cast<const S *>(values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
     const int s1w = wd.seg1_w, s1x = wd.seg1_x - wd.seg1_w;
     const int s2w = wd.seg2_w, s2x = pc.seg2_x - wd.seg2_w;
     const long long base = out_off[wv];
@@ -2867,7 +2920,7 @@ __global__ void __launch_bounds__(64 * kWavesPerWg) export_coo_kernel(const Wave
             const int s = w / E, e = w % E;
             for (int i = 0; i < m; ++i) {
                 const int ri = (wd.rbase >= 0) ? wd.rbase + i : rows[wd.row_off + i];
-                const T v = vb[((long long)s * m + i) * E + e];
+                const T v = widen(T{}, vb[((long long)s * m + i) * E + e]);
                 const long long o = base + (long long)w * m + i;
                 orow[o] = ri + 1;
                 ocol[o] = ci + 1;
@@ -2889,15 +2942,17 @@ hipError_t launch_export_coo(int dtype, const void *d_waves, long long nwaves, c
                              void *oval, hipStream_t stream) {
     if (nwaves <= 0) return hipSuccess;
     const dim3 grid((unsigned)((nwaves + kWavesPerWg - 1) / kWavesPerWg)), block(64 * kWavesPerWg);
-#define BSM_EXPORT(T)                                                                                             \
-    hipLaunchKernelGGL((export_coo_kernel<T>), grid, block, 0, stream, (const WaveWork *)d_waves, nwaves,         \
+#define BSM_EXPORT(T, S)                                                                                          \
+    hipLaunchKernelGGL((export_coo_kernel<T, S>), grid, block, 0, stream, (const WaveWork *)d_waves, nwaves,         \
                        (const long long *)d_out_off, (const uint4 *)d_values, (const int *)d_rows,                \
                        (const int *)d_cols, (long long *)orow, (long long *)ocol, (T *)oval)
     switch (dtype) {
-        case 0: BSM_EXPORT(float); break;
-        case 1: BSM_EXPORT(double); break;
-        case 2: BSM_EXPORT(c64); break;
-        case 3: BSM_EXPORT(c128); break;
+        case 0: BSM_EXPORT(float, float); break;
+        case 1: BSM_EXPORT(double, double); break;
+        case 2: BSM_EXPORT(c64, c64); break;
+        case 3: BSM_EXPORT(c128, c128); break;
+        case 4: BSM_EXPORT(double, float); break;
+        case 5: BSM_EXPORT(c128, c64); break;
         default: return hipErrorInvalidValue;
     }
 #undef BSM_EXPORT
@@ -2932,12 +2987,44 @@ __global__ void __launch_bounds__(256) pack_kernel(const PackChunk *__restrict__
     }
 }
 
-hipError_t launch_pack(int es, const void *d_plan, long long nchunks, const void *d_colpos, void *d_values,
+// the converting variant of mixed-precision handles: the caller's double / complex double blocks are rounded to the
+// stored float / complex float as they are placed -- the round-to-nearest-even conversion (v_cvt_f32_f64 under the
+// default rounding mode, f32 denormals not flushed), bit for bit what the host packer's cast gives
+__device__ __forceinline__ float narrow(double v) { return (float)v; }
+__device__ __forceinline__ c64 narrow(c128 v) { return c64{(float)v.re, (float)v.im}; }
+template <typename S, typename T>
+__global__ void __launch_bounds__(256) pack_convert_kernel(const PackChunk *__restrict__ plan, const int *__restrict__ colpos,
+                                                           S *__restrict__ values) {
+    constexpr int E = TT<S>::E;
+    const PackChunk c = plan[blockIdx.x];
+    const T *__restrict__ src = reinterpret_cast<const T *>(c.src);
+    S *__restrict__ dst = values + c.dst_unit * (uint64_t)E;
+    const int mc = c.mc;
+    int rp = 1;
+    while (rp < mc) rp <<= 1;
+    const int i = threadIdx.x & (rp - 1);
+    const int cpw = 256 / rp;
+    if (i >= mc) return;
+    for (int w = threadIdx.x / rp; w < c.n; w += cpw) {
+        const int q = c.perm_off < 0 ? c.woff + w : colpos[c.perm_off + w];
+        const T v = c.trans ? src[(int64_t)w + (int64_t)(c.ra + i) * c.ld] : src[(int64_t)(c.ra + i) + (int64_t)w * c.ld];
+        dst[((int64_t)(q / E) * mc + i) * E + (q % E)] = narrow(v);
+    }
+}
+
+hipError_t launch_pack(int es, int src_es, const void *d_plan, long long nchunks, const void *d_colpos, void *d_values,
                        hipStream_t stream) {
     if (nchunks <= 0) return hipSuccess;
     const PackChunk *plan = (const PackChunk *)d_plan;
     const int *cp = (const int *)d_colpos;
     const dim3 grid((unsigned)nchunks), block(256);
+    if (src_es != es) {  // mixed precision: 8 -> 4 bytes (double -> float) or 16 -> 8 (complex double -> complex float)
+        if (es == 4)
+            hipLaunchKernelGGL((pack_convert_kernel<float, double>), grid, block, 0, stream, plan, cp, (float *)d_values);
+        else
+            hipLaunchKernelGGL((pack_convert_kernel<c64, c128>), grid, block, 0, stream, plan, cp, (c64 *)d_values);
+        return hipGetLastError();
+    }
     if (es == 4)
         hipLaunchKernelGGL((pack_kernel<uint32_t>), grid, block, 0, stream, plan, cp, (uint32_t *)d_values, 4);
     else if (es == 8)

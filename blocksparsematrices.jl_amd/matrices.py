@@ -43,6 +43,27 @@ __all__ = [
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
        np.dtype(np.complex64): L.BSM_C64, np.dtype(np.complex128): L.BSM_C128}
+# mixed precision (`storage=`): (vector / block type, stored type) -> dtype code
+_MIXED = {(np.dtype(np.float64), np.dtype(np.float32)): L.BSM_F64_F32,
+          (np.dtype(np.complex128), np.dtype(np.complex64)): L.BSM_C128_C64}
+
+
+def _code(dt, storage, devices=None):
+    """dtype code of a handle with blocks / vectors of type dt whose values are stored as `storage` (None: dt) ->
+    (code, stored dtype).  Mixed precision stores Float64 blocks as Float32 (ComplexF64 as ComplexF32), rounded once
+    at construction exactly like astype; products keep fp64 vectors and sums."""
+    if storage is None:
+        return _DT[dt], dt
+    try:
+        sdt = np.dtype(storage)
+    except TypeError:
+        raise TypeError(f"storage={storage!r} is not a dtype") from None
+    if (dt, sdt) not in _MIXED:
+        raise TypeError(f"storage={sdt} with {dt} blocks: mixed precision stores float64 blocks as float32 and "
+                        f"complex128 blocks as complex64, nothing else")
+    if devices is not None:
+        raise ValueError("mixed-precision storage is single-device only (devices= is not available)")
+    return _MIXED[(dt, sdt)], sdt
 
 
 # ---- schedulers (OhMyThreads names; reference src/BlockSparseMatrices.jl:12-18) --------------
@@ -300,9 +321,11 @@ class _LinearMap:
 class AbstractBlockMatrix(_LinearMap):
     """reference src/abstractblockmatrix.jl:13-62"""
 
-    def _finish(self, handle, dt, sz, sched, device=None, devices=None):
+    def _finish(self, handle, dt, sz, sched, device=None, devices=None, storage_dtype=None):
         self._h = _Handle(handle)
         self.dtype = dt
+        # the type the device image stores the values in: dtype, or float32 / complex64 for a mixed-precision handle
+        self.storage_dtype = dt if storage_dtype is None else storage_dtype
         self.size = (int(sz[0]), int(sz[1]))
         self.scheduler = sched
         self.devices = None if devices is None else tuple(int(d) for d in devices)
@@ -428,7 +451,7 @@ class BlockSparseMatrix(AbstractBlockMatrix):
 
     def __init__(self, blocks, rowindices, colindices, size, cols=None, *, scheduler=None,
                  coloringalgorithm=None, device=None, accumulate="auto", own=None,
-                 transpose_image=False, devices=None):
+                 transpose_image=False, devices=None, storage=None):
         if cols is not None:  # (blocks, rowindices, colindices, rows, cols) form, :81-89
             size = (size, cols)
         scheduler = SerialScheduler() if scheduler is None else scheduler
@@ -447,14 +470,15 @@ class BlockSparseMatrix(AbstractBlockMatrix):
         n = _i64([b.shape[1] for b in self.blocks])
         ld = _lds(self.blocks)
         dev = _default_device() if device is None else device
+        code, sdt = _code(dt, storage, devices)
         o = _options(scheduler, dev, accumulate, own, transpose_image, devices, devb, coloringalgorithm)
         h = C.c_void_p()
         I = C.POINTER(C.c_int64)
         L.check(L.lib().bsm_blocksparse_create(
-            _DT[dt], int(size[0]), int(size[1]), nb, _ptrs(self.blocks), m.ctypes.data_as(I),
+            code, int(size[0]), int(size[1]), nb, _ptrs(self.blocks), m.ctypes.data_as(I),
             n.ctypes.data_as(I), ld.ctypes.data_as(I), _ptrs(self.rowindices),
             _ptrs(self.colindices), C.byref(o), C.byref(h)))
-        self._finish(h, dt, size, scheduler, dev, devices)
+        self._finish(h, dt, size, scheduler, dev, devices, sdt)
         self._src = lambda: list(self.blocks)
         self.colors = _classes(self._bookkeeping(L.BSM_BK_COLORS))
         self.transposecolors = _classes(self._bookkeeping(L.BSM_BK_TRANSPOSECOLORS))
@@ -465,7 +489,7 @@ class SymmetricBlockMatrix(AbstractBlockMatrix):
     DynamicScheduler() (:80)."""
 
     def __init__(self, diagonals, diagonalindices, offdiagonals, rowindices, colindices, size,
-                 cols=None, *, scheduler=None, device=None, accumulate="auto", own=None, devices=None):
+                 cols=None, *, scheduler=None, device=None, accumulate="auto", own=None, devices=None, storage=None):
         if cols is not None:  # rows, cols form defaults to SerialScheduler() (:102)
             size = (size, cols)
             scheduler = SerialScheduler() if scheduler is None else scheduler
@@ -492,15 +516,16 @@ class SymmetricBlockMatrix(AbstractBlockMatrix):
         n = _i64([b.shape[1] for b in self.offdiagonals])
         ld = _lds(self.offdiagonals)
         dev = _default_device() if device is None else device
+        code, sdt = _code(dt, storage, devices)
         o = _options(scheduler, dev, accumulate, own, False, devices, devb)
         h = C.c_void_p()
         I = C.POINTER(C.c_int64)
         L.check(L.lib().bsm_symmetric_create(
-            _DT[dt], int(size[0]), int(size[1]), nd, _ptrs(self.diagonals), ds.ctypes.data_as(I),
+            code, int(size[0]), int(size[1]), nd, _ptrs(self.diagonals), ds.ctypes.data_as(I),
             dld.ctypes.data_as(I), _ptrs(self.diagonalindices), no, _ptrs(self.offdiagonals),
             m.ctypes.data_as(I), n.ctypes.data_as(I), ld.ctypes.data_as(I),
             _ptrs(self.rowindices), _ptrs(self.colindices), C.byref(o), C.byref(h)))
-        self._finish(h, dt, size, scheduler, dev, devices)
+        self._finish(h, dt, size, scheduler, dev, devices, sdt)
         self._src = lambda: list(self.diagonals) + list(self.offdiagonals)  # bsm_update_blocks order: diag..., off...
         self.offdiagonalcolors = _classes(self._bookkeeping(L.BSM_BK_COLORS))
         self.transposeoffdiagonalcolors = _classes(self._bookkeeping(L.BSM_BK_TRANSPOSECOLORS))
@@ -513,8 +538,13 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
 
     def __init__(self, matrices, rowindices=None, colindices=None, matrixsize=None, *,
                  scheduler=None, device=None, accumulate="auto", own=None, materialize=False,
-                 transpose_image=False, devices=None):
+                 transpose_image=False, devices=None, storage=None):
+        """storage: np.float32 for float64 blocks / np.complex64 for complex128 ones stores the values in single
+        precision under double-precision vectors (mixed precision).  A VBCRS made from a BlockSparseMatrix or a
+        SymmetricBlockMatrix takes the source's storage type unless told otherwise."""
         I = C.POINTER(C.c_int64)
+        if storage is None and isinstance(matrices, AbstractBlockMatrix) and matrices.storage_dtype != matrices.dtype:
+            storage = matrices.storage_dtype
         h = C.c_void_p()
         dev = _default_device() if device is None else device
         if isinstance(matrices, SymmetricBlockMatrix) and not materialize:  # src/vbcrs.jl:189-264
@@ -533,10 +563,11 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
             ld = _lds(s.offdiagonals)
             r0 = _i64([int(r[0]) for r in s.rowindices])
             c0 = _i64([int(c[0]) for c in s.colindices])
+            code, sdt = _code(dt, storage, devices)
             o = _options(scheduler, dev, accumulate, own, False, devices,
                          _is_dev(s.diagonals) or _is_dev(s.offdiagonals))
             L.check(L.lib().bsm_vbcrs_create_from_symmetric(
-                _DT[dt], int(s.size[0]), int(s.size[1]), len(s.diagonals), _ptrs(s.diagonals),
+                code, int(s.size[0]), int(s.size[1]), len(s.diagonals), _ptrs(s.diagonals),
                 ds.ctypes.data_as(I), dld.ctypes.data_as(I), d0.ctypes.data_as(I), len(s.offdiagonals),
                 _ptrs(s.offdiagonals), m.ctypes.data_as(I), n.ctypes.data_as(I), ld.ctypes.data_as(I),
                 r0.ctypes.data_as(I), c0.ctypes.data_as(I), C.byref(o), C.byref(h)))
@@ -557,9 +588,10 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
                 m = _i64([k.shape[0] for k in fb])
                 n = _i64([k.shape[1] for k in fb])
                 ld = _lds(fb)
+                code, sdt = _code(dt, storage, devices)
                 o = _options(scheduler, dev, accumulate, own, transpose_image, devices, _is_dev(fb))
                 L.check(L.lib().bsm_vbcrs_create_from_blocksparse(
-                    _DT[dt], int(b.size[0]), int(b.size[1]), len(fb), _ptrs(fb), m.ctypes.data_as(I),
+                    code, int(b.size[0]), int(b.size[1]), len(fb), _ptrs(fb), m.ctypes.data_as(I),
                     n.ctypes.data_as(I), ld.ctypes.data_as(I), _ptrs(b.rowindices), _ptrs(b.colindices),
                     C.byref(o), C.byref(h)))
                 matrixsize = b.size
@@ -590,9 +622,10 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
                 m = _i64([b.shape[0] for b in fb])
                 n = _i64([b.shape[1] for b in fb])
                 ld = _lds(fb)
+                code, sdt = _code(dt, storage, devices)
                 o = _options(scheduler, dev, accumulate, own, transpose_image, devices, devb)
                 L.check(L.lib().bsm_vbcrs_create(
-                    _DT[dt], int(matrixsize[0]), int(matrixsize[1]), len(fb), _ptrs(fb),
+                    code, int(matrixsize[0]), int(matrixsize[1]), len(fb), _ptrs(fb),
                     m.ctypes.data_as(I), n.ctypes.data_as(I), ld.ctypes.data_as(I), rs.ctypes.data_as(I),
                     cs.ctypes.data_as(I), C.byref(o), C.byref(h)))
                 src = (lambda fb=fb: list(fb))  # the constructor's order (self.blocks is the sorted view of it)
@@ -603,7 +636,7 @@ class VariableBlockCompressedRowStorage(AbstractBlockMatrix):
                         raise NotImplementedError(
                             "update_blocks / refresh of a VBCRS that materialised a SymmetricBlockMatrix: build it with "
                             "materialize=False (the symmetric image, which refreshes from the source's lists)")
-        self._finish(h, dt, matrixsize, scheduler, dev, devices)
+        self._finish(h, dt, matrixsize, scheduler, dev, devices, sdt)
         self._src = src
         self.perm = self._bookkeeping(L.BSM_BK_VBCRS_PERM).copy()
         self.rowptr = self._bookkeeping(L.BSM_BK_VBCRS_ROWPTR).copy()
@@ -636,6 +669,12 @@ def _stream_ptr(stream, dev):
     return torch.cuda.current_stream(dev).cuda_stream if dev is not None else None
 
 
+def _no_mixed_update(A):
+    if A.storage_dtype != A.dtype:
+        raise NotImplementedError("update_blocks / refresh of a mixed-precision operator (storage="
+                                  f"{A.storage_dtype} under {A.dtype}): build a new one from the new blocks")
+
+
 def refresh(A, ids=None, stream=None):
     """Pushes the CURRENT contents of the mirror's block fields (A.blocks / A.diagonals / A.offdiagonals, edited in
     place by the caller) to the device image -- the reference's by-reference semantics, restored by one explicit call.
@@ -643,6 +682,7 @@ def refresh(A, ids=None, stream=None):
     a kernel on `stream` (default: torch's current stream) without synchronising; host blocks are staged and the call
     returns when the image holds them."""
     A, _ = _unwrap(A)
+    _no_mixed_update(A)
     src = A._src()
     ids = _update_ids(ids, len(src))
     blks = [src[i - 1] for i in ids]
@@ -672,6 +712,7 @@ def update_blocks(A, blocks, ids=None, stream=None):
     offdiagonals), numpy arrays or column-major torch CUDA tensors whatever A was built from; ids: their 1-based
     positions (None = all).  Shapes stay as created."""
     B, _ = _unwrap(A)
+    _no_mixed_update(B)
     src = B._src()
     ids = _update_ids(ids, len(src))
     if len(blocks) != len(ids):

@@ -39,8 +39,23 @@ typedef enum {
     BSM_ERR_ALLOC = -4
 } bsm_status;
 
-/* element type T of blocks, x, y, alpha, beta */
-typedef enum { BSM_F32 = 0, BSM_F64 = 1, BSM_C64 = 2, BSM_C128 = 3 } bsm_dtype;
+/* element type T of blocks, x, y, alpha, beta -- and, for the two MIXED-PRECISION codes, the type S the device image
+ * stores the values in:
+ *   BSM_F64_F32  (4): blocks, x, y, alpha, beta are double, the image stores float;
+ *   BSM_C128_C64 (5): blocks, x, y, alpha, beta are complex double, the image stores complex float.
+ * Every product is bound by the bytes of the value stream; a mixed handle streams half of them and keeps the vectors
+ * and every sum in double precision.  Each entry is rounded ONCE, when the image is packed (host or device blocks
+ * alike, bit-identical): the IEEE round-to-nearest-even cast of numpy's astype(float32) / astype(complex64) --
+ * subnormals are kept, magnitudes beyond the float range become +-inf.  The image then has exactly the layout of a
+ * BSM_F32 / BSM_C64 handle of the rounded blocks.  In a product each 16-byte lane load delivers 16 / sizeof(S) stored
+ * values, which are widened in registers and combined with x by double-precision FMAs; partial sums, LDS windows,
+ * atomics and the gather workspace are double.  All five *_create functions accept the codes; bsm_mul takes every
+ * op, accumulate mode and transpose_image setting.  What a mixed handle does NOT offer:
+ *   - bsm_options.ctx (multi-device handles): BSM_ERR_UNSUPPORTED;
+ *   - bsm_update_blocks: BSM_ERR_UNSUPPORTED (create a new handle from the new blocks);
+ *   - bsm_mul_multi runs as nrhs one-column products (no one-pass multi-RHS kernels for mixed storage);
+ *   - bsm_vec_add_segments takes vector types only: the mixed codes are BSM_ERR_INVALID there. */
+typedef enum { BSM_F32 = 0, BSM_F64 = 1, BSM_C64 = 2, BSM_C128 = 3, BSM_F64_F32 = 4, BSM_C128_C64 = 5 } bsm_dtype;
 
 /* which operator of A is applied: A, transpose(A), A' -- the reference's
  * LinearMaps.TransposeMap / AdjointMap wrappers (src/blockmatrix.jl:154-160,200-206,
@@ -292,7 +307,8 @@ int bsm_stream_create_reserved(int device, int reserved_cus, void **stream);
 int bsm_stream_destroy(void *stream);
 
 /* y[offset[s] + i] += src[s][i], i < len[s], for nseg DISJOINT segments of a device vector y, in ONE launch on
- * `stream` (dtype as in the *_create calls; offsets 0-based, in elements).  The delivery step of a row-partitioned
+ * `stream` (dtype BSM_F32 .. BSM_C128 as in the *_create calls -- a mixed storage code is BSM_ERR_INVALID here;
+ * offsets 0-based, in elements).  The delivery step of a row-partitioned
  * product in a process-per-GPU layer above this ABI (blocksparsematrices.jl_amd/distributed.py: the own rows of the
  * boundary blocks' sums + every partial-y segment received from a neighbour -- the y segments other tasks of the
  * reference's fan-out would have added in shared memory, src/symmetricblockmatrix.jl:407-418): one launch behind
@@ -318,7 +334,8 @@ int bsm_host_unregister(void *ptr);
  * and Y is size(op(A),1) x nrhs, both column-major with leading dimensions ldx / ldy (elements).
  * Every other argument as in bsm_mul; each column gives what nrhs = 1 semantics prescribe (same
  * alpha, beta, strong zero).  nrhs = 1 is bsm_mul: the same kernels and, on a BSM_ACC_GATHER handle, the
- * same bitwise reproducible gather path. */
+ * same bitwise reproducible gather path.  Mixed-precision handles (BSM_F64_F32, BSM_C128_C64) run nrhs one-column
+ * products, one after another on `stream` (their multi-RHS passes stream A once per column, not once per batch). */
 int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y,
                   int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace,
                   void *stream);
@@ -355,7 +372,8 @@ int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t l
  * an update is stream-ordered like a product and takes no lock on the product path.
  * Every argument is checked before the first byte is written: a failing call leaves the handle unchanged
  * (BSM_ERR_INVALID: null handle or pointer, id out of range, duplicate id, nupd != count with ids == NULL, ld < m,
- * bad memspace, BSM_MEM_DEVICE on an analysis-only handle).
+ * bad memspace, BSM_MEM_DEVICE on an analysis-only handle).  Mixed-precision handles (BSM_F64_F32, BSM_C128_C64) are
+ * refused with BSM_ERR_UNSUPPORTED.
  * Memory: a handle keeps its block list from creation on (index lists copied).  The first update derives the refill
  * plan from it -- the value-blind placement of the create, re-run and checked against the image -- and keeps it on the
  * host and on the device until bsm_destroy: 32 B per <= 64-row chunk of every image, 16 B per segment of <= 16 KB,
@@ -382,7 +400,8 @@ int bsm_get_bookkeeping(bsm_matrix_t A, int which, int64_t *out, int64_t *len);
  * (src/sparse.jl:125-129): written by a kernel straight from the packed DEVICE image -- every stored
  * entry once, the off-diagonal blocks of a SymmetricBlockMatrix a second time transposed -- so that a
  * CSR / CSC matrix can be assembled on the GPU without the blocks ever returning to the host.
- * rows / cols: 1-based int64, vals: the handle's element type, all with room for *count entries
+ * rows / cols: 1-based int64, vals: the handle's element type T (mixed-precision handles: the stored values widened
+ * to T, i.e. exactly blocks.astype(S).astype(T)), all with room for *count entries
  * (call with NULL arrays to obtain the count = nnz(A) as the reference defines it).  The order of the
  * triples is fixed but unspecified (`sparse` sums duplicates, like mul!'s +=).  memspace: where the
  * three arrays live (BSM_MEM_DEVICE: on the handle's device).  Synchronous. */
@@ -395,8 +414,9 @@ typedef struct {
                                blocks of a SymmetricBlockMatrix count twice,
                                src/symmetricblockmatrix.jl:367-384) */
     int64_t stored_entries; /* matrix entries held on the device (each stored once) */
-    int64_t alg_bytes;      /* algorithmic bytes of one mul with beta = 0 */
-    int64_t device_bytes;   /* bytes of the packed device image (values + metadata) */
+    int64_t alg_bytes;      /* algorithmic bytes of one mul with beta = 0; mixed-precision handles count
+                               the stored type's bytes for the values, the vector type's for x and y */
+    int64_t device_bytes;   /* bytes of the packed device image (values in the stored type + metadata) */
     int64_t npanels, ntasks, nworkgroups;
     int64_t exclusive;      /* 1: forward product needs no atomics and no pre-scale pass */
     /* SymmetricBlockMatrix, op N: y contributions the fused launch produces (forward rows + transposed

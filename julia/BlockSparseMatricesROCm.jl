@@ -17,20 +17,24 @@ const libbsm = get(ENV, "BSM_ROCM_LIB", "libbsmrocm.so")
 
 # ---- the opt-in scheduler ---------------------------------------------------------------------------
 """
-    ROCmScheduler(; device=-1, devices=Int32[], accumulate=0, transpose_image=2)
+    ROCmScheduler(; device=-1, devices=Int32[], accumulate=0, transpose_image=2, storage=nothing)
 
 `BlockSparseMatrix(...; scheduler=ROCmScheduler())` etc.  `devices = [0, 1, ...]` spreads ONE matrix
 over several GPUs of the node (bsm_ctx_t: block rows partitioned by stored bytes, halo exchange over
 xGMI) -- the counterpart of the reference's `@tasks` fan-out (src/vbcrs.jl:275-276).
+`storage = Float32` stores the values of a Float64 / ComplexF64 matrix in single precision (ComplexF32 for complex
+blocks; BSM_F64_F32 / BSM_C128_C64) while x, y and every sum stay in double precision: half the bytes per product.
+Single-device only; the values are rounded once, when the handle is created.
 """
 struct ROCmScheduler
     device::Int32            # HIP ordinal, -1 = current device
     devices::Vector{Int32}   # non-empty: multi-GPU handle over these ordinals
     accumulate::Int32        # 0 auto, 1 atomics, 2 coloured launches, 3 gather, 4 direct (2-4: bitwise reproducible)
     transpose_image::Int32   # 1: keep a second, transposed ordering for A' / transpose(A); 2: when it is cheap
+    storage::Union{Nothing,DataType}  # Float32: mixed precision (values stored in single precision)
 end
-ROCmScheduler(; device=-1, devices=Int32[], accumulate=0, transpose_image=2) =
-    ROCmScheduler(Int32(device), Int32.(collect(devices)), Int32(accumulate), Int32(transpose_image))
+ROCmScheduler(; device=-1, devices=Int32[], accumulate=0, transpose_image=2, storage=nothing) =
+    ROCmScheduler(Int32(device), Int32.(collect(devices)), Int32(accumulate), Int32(transpose_image), storage)
 BlockSparseMatrices.isserial(::ROCmScheduler) = true   # no host colouring needed for the GPU path
 
 mutable struct BsmOptions           # mirrors bsm_options (72 bytes)
@@ -46,6 +50,15 @@ function _check(rc)
 end
 
 const _DTYPE = Dict(Float32 => 0, Float64 => 1, ComplexF32 => 2, ComplexF64 => 3)
+# mixed precision: (block / vector type, storage=) -> BSM_F64_F32, BSM_C128_C64
+function _dtype(::Type{T}, s::ROCmScheduler) where {T}
+    s.storage === nothing && return _DTYPE[T]
+    s.storage === Float32 || throw(ArgumentError("storage = $(s.storage): only Float32 (single-precision values)"))
+    isempty(s.devices) || throw(ArgumentError("storage = Float32 is single-device only (devices = $(s.devices))"))
+    T === Float64 && return 4
+    T === ComplexF64 && return 5
+    throw(ArgumentError("storage = Float32 needs Float64 or ComplexF64 blocks, not $T"))
+end
 const ROCmEltype = Union{Float32,Float64,ComplexF32,ComplexF64}
 
 mutable struct Handle
@@ -112,7 +125,7 @@ function _create(A::VariableBlockCompressedRowStorage{T}) where {T}
     GC.@preserve A bl _check(ccall((:bsm_vbcrs_create, libbsm), Cint,
         (Cint, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
          Ptr{Int64}, Ptr{Int64}, Ref{BsmOptions}, Ref{Ptr{Cvoid}}),
-        _DTYPE[T], size(A, 1), size(A, 2), nb, ptrs, m, n, _ld.(bl), rowstart, colstart,
+        _dtype(T, A.scheduler), size(A, 1), size(A, 2), nb, ptrs, m, n, _ld.(bl), rowstart, colstart,
         _options(A.scheduler), out))
     return Handle(out[])
 end
@@ -127,7 +140,7 @@ function _create(A::BlockSparseMatrix{T}) where {T}
     GC.@preserve A bl ri ci _check(ccall((:bsm_blocksparse_create, libbsm), Cint,
         (Cint, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
          Ptr{Ptr{Int64}}, Ptr{Ptr{Int64}}, Ref{BsmOptions}, Ref{Ptr{Cvoid}}),
-        _DTYPE[T], size(A, 1), size(A, 2), nb, Ptr{Cvoid}[pointer(b) for b in bl], m, n,
+        _dtype(T, A.scheduler), size(A, 1), size(A, 2), nb, Ptr{Cvoid}[pointer(b) for b in bl], m, n,
         _ld.(bl), pointer.(ri), pointer.(ci), _options(A.scheduler), out))
     return Handle(out[])
 end
@@ -144,7 +157,7 @@ function _create(A::SymmetricBlockMatrix{T}) where {T}
         (Cint, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Int64}},
          Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Int64}},
          Ptr{Ptr{Int64}}, Ref{BsmOptions}, Ref{Ptr{Cvoid}}),
-        _DTYPE[T], size(A, 1), size(A, 2), length(ds), Ptr{Cvoid}[pointer(b) for b in dg],
+        _dtype(T, A.scheduler), size(A, 1), size(A, 2), length(ds), Ptr{Cvoid}[pointer(b) for b in dg],
         ds, _ld.(dg), pointer.(di), length(m), Ptr{Cvoid}[pointer(b) for b in og],
         m, n, _ld.(og), pointer.(ri), pointer.(ci), _options(A.scheduler), out))
     return Handle(out[])
@@ -388,7 +401,7 @@ function ROCmVBCRS(A::SymmetricBlockMatrix{T}; scheduler::ROCmScheduler=ROCmSche
         (Cint, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
          Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
          Ref{BsmOptions}, Ref{Ptr{Cvoid}}),
-        _DTYPE[T], size(A, 1), size(A, 2), length(ds), Ptr{Cvoid}[pointer(b) for b in A.diagonals],
+        _dtype(T, scheduler), size(A, 1), size(A, 2), length(ds), Ptr{Cvoid}[pointer(b) for b in A.diagonals],
         ds, _ld.(A.diagonals), d0, length(m), Ptr{Cvoid}[pointer(b) for b in A.offdiagonals],
         m, n, _ld.(A.offdiagonals), r0, c0, _options(scheduler), out))
     h = Handle(out[])
@@ -403,7 +416,7 @@ function ROCmVBCRS(A::BlockSparseMatrix{T}; scheduler::ROCmScheduler=ROCmSchedul
     GC.@preserve A ri ci _check(ccall((:bsm_vbcrs_create_from_blocksparse, libbsm), Cint,
         (Cint, Int64, Int64, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64},
          Ptr{Ptr{Int64}}, Ptr{Ptr{Int64}}, Ref{BsmOptions}, Ref{Ptr{Cvoid}}),
-        _DTYPE[T], size(A, 1), size(A, 2), nb, Ptr{Cvoid}[pointer(b) for b in A.blocks], m, n,
+        _dtype(T, scheduler), size(A, 1), size(A, 2), nb, Ptr{Cvoid}[pointer(b) for b in A.blocks], m, n,
         _ld.(A.blocks), pointer.(ri), pointer.(ci), _options(scheduler), out))
     h = Handle(out[])
     return ROCmVBCRS{T}(h, (size(A, 1), size(A, 2)), _bookkeeping(h, 1), _bookkeeping(h, 2), _bookkeeping(h, 3), Int[])

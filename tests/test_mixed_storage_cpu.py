@@ -1,0 +1,338 @@
+"""CPU suite: mixed-precision handles (BSM_F64_F32, BSM_C128_C64) -- values stored in single precision under
+double-precision vectors.  Analysis-only handles (BSM_DEVICE_NONE): the packed image must be exactly the image of a
+pure single-precision handle of the rounded blocks, the bookkeeping that of the pure double-precision handle, the
+statistics must count stored bytes for the values and vector bytes for x / y, and the image decoded in fp64 must
+reproduce the oracle on the rounded blocks.  Plus the refusals and the mirror's `storage=` checks."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from _common import (Cc, KIND_HAS_OFF, KIND_OFF, N, T, WORK_PANEL, fixture_problem, get_image, oracle_mul, rand_vec,
+                     relerr)
+
+NODEV = -2
+OPS = [N, T, Cc]
+PAIRS = [(np.float64, np.float32), (np.complex128, np.complex64)]
+CTORS = ["blocksparse", "vbcrs", "symmetric", "vbcrs_from_blocksparse", "vbcrs_from_symmetric"]
+
+
+def _complexify(blocks, seed):
+    rng = np.random.default_rng(seed)
+    return [np.asfortranarray(b + 1j * rng.standard_normal(b.shape)) for b in blocks]
+
+
+def _problem(bsm, ctor, dt):
+    """a small problem of each constructor's kind, blocks of type dt (float64 or complex128)"""
+    S = bsm.synthetic
+    if ctor == "blocksparse":
+        p = S.config1(n=400, nblocks=40, bs=12)
+        keys = ["blocks"]
+    elif ctor == "vbcrs":
+        p = S.config2(n=3000, nblocks=160, lo=4, hi=40)
+        keys = ["blocks"]
+    elif ctor == "vbcrs_from_blocksparse":  # contiguous lists: the converter takes the first index of each
+        v = S.config2(n=2000, nblocks=120, lo=4, hi=40)
+        p = dict(kind="blocksparse", blocks=v["blocks"], size=v["size"],
+                 rowindices=[np.arange(r, r + b.shape[0], dtype=np.int64) for r, b in zip(v["rowstart"], v["blocks"])],
+                 colindices=[np.arange(c, c + b.shape[1], dtype=np.int64) for c, b in zip(v["colstart"], v["blocks"])])
+        keys = ["blocks"]
+    else:
+        p = S.config3(nseg=10, bs=20, halfband=2)
+        keys = ["diagonals", "offdiagonals"]
+    if np.dtype(dt).kind == "c":
+        for i, k in enumerate(keys):
+            p[k] = _complexify(p[k], 7 + i)
+    return p
+
+
+def _rounded(p, S):
+    q = dict(p)
+    for k in ("blocks", "diagonals", "offdiagonals"):
+        if k in p:
+            q[k] = [np.asfortranarray(b.astype(S).astype(np.result_type(S, np.float64))) for b in p[k]]
+    return q
+
+
+def _build(bsm, ctor, p, dtype_cast=None, **kw):
+    """constructor `ctor` on problem p (blocks cast to dtype_cast first if given), analysis only"""
+    M = bsm.matrices
+    if dtype_cast is not None:
+        p = dict(p)
+        for k in ("blocks", "diagonals", "offdiagonals"):
+            if k in p:
+                p[k] = [np.asfortranarray(b.astype(dtype_cast)) for b in p[k]]
+    kw.setdefault("device", NODEV)
+    storage = kw.pop("storage", None)
+    skw = {} if storage is None else {"storage": storage}
+    if ctor == "blocksparse":
+        return M.BlockSparseMatrix(p["blocks"], p["rowindices"], p["colindices"], p["size"], **kw, **skw)
+    if ctor == "vbcrs":
+        return M.VariableBlockCompressedRowStorage(p["blocks"], p["rowstart"], p["colstart"], p["size"], **kw, **skw)
+    if ctor == "symmetric":
+        kw.pop("transpose_image", None)
+        return M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"],
+                                      p["colindices"], p["size"], **kw, **skw)
+    if ctor == "vbcrs_from_blocksparse":
+        B = M.BlockSparseMatrix(p["blocks"], p["rowindices"], p["colindices"], p["size"], device=NODEV)
+        return M.VariableBlockCompressedRowStorage(B, **kw, **skw)
+    if ctor == "vbcrs_from_symmetric":
+        kw.pop("transpose_image", None)
+        Sm = M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"],
+                                    p["colindices"], p["size"], device=NODEV)
+        return M.VariableBlockCompressedRowStorage(Sm, **kw, **skw)
+    raise ValueError(ctor)
+
+
+def _oracle_problem(ctor, p):
+    """the problem as the oracle takes it: a VBCRS from a BlockSparseMatrix / SymmetricBlockMatrix is the same operator"""
+    if ctor == "vbcrs_from_blocksparse":
+        return dict(p, kind="blocksparse")
+    if ctor == "vbcrs_from_symmetric":  # [diagonals..., offdiagonals..., transposes...] at the FIRST list entries
+        d, o = p["diagonals"], p["offdiagonals"]
+        first = lambda lists: [int(v[0]) for v in lists]  # noqa: E731
+        rs = first(p["diagonalindices"]) + first(p["rowindices"]) + first(p["colindices"])
+        cs = first(p["diagonalindices"]) + first(p["colindices"]) + first(p["rowindices"])
+        return dict(kind="vbcrs", blocks=list(d) + list(o) + [np.asfortranarray(b.T) for b in o],
+                    rowstart=np.array(rs, dtype=np.int64), colstart=np.array(cs, dtype=np.int64), size=p["size"])
+    return p
+
+
+def decode_mixed(A, op, x, y0, alpha=1, beta=0, strong=True, timage=False):
+    """y = alpha op(A) x + beta y0 from the packed image of a mixed handle: every panel piece's strips are read as the
+    STORED type (E = 16 / sizeof(S) columns per strip), widened to the vector type and applied in fp64 -- the kernel's
+    arithmetic, independently of its schedule.  timage: op T / C run forward on the transposed ordering."""
+    values, rows, cols, waves = get_image(A, timage)
+    S, Tt = A.storage_dtype, A.dtype
+    E = 16 // S.itemsize
+    vals = values.view(S)
+    opT = (op != N) and not timage
+    conj = op == Cc
+    acc = np.zeros(len(y0), dtype=Tt)
+    for W in waves[(waves["work"] == WORK_PANEL) & (waves["npieces"] > 0)]:
+        m = int(W["m"])
+        ridx = np.arange(W["rbase"], W["rbase"] + m) if W["rbase"] >= 0 else rows[W["row_off"]:W["row_off"] + m]
+        P = W["first"]
+        ns, nc = int(P["nstrips"]), int(P["ncols"])
+        base = int(P["val_off"]) * 16 // S.itemsize
+        full = vals[base:base + ns * m * E].reshape(ns, m, E).transpose(1, 0, 2).reshape(m, ns * E)
+        assert not np.any(full[:, nc:]), "strip padding must be zero"
+        B = full[:, :nc].astype(Tt)
+        if conj:
+            B = B.conj()
+        kinds = int(P["kind"])
+        wv = np.arange(nc)
+        pool = cols[P["col_off"]:P["col_off"] + nc]
+        if P["xbase"] >= 0:
+            s1w, s2w = int(W["seg1_w"]), int(W["seg2_w"])
+            cidx = np.where(wv < s1w, int(P["xbase"]) + wv,
+                            np.where(wv < s2w, int(W["seg1_x"]) + wv - s1w, int(P["seg2_x"]) + wv - s2w))
+            ckind = np.where(wv < s1w, kinds & 3, np.where(wv < s2w, (kinds >> 2) & 3, (kinds >> 4) & 3))
+        else:
+            cidx = pool & 0x7fffffff
+            ckind = np.where(pool < 0, 1, kinds & 3)
+        assert bool(kinds & KIND_HAS_OFF) == bool(np.any(ckind == KIND_OFF))
+        off = ckind == KIND_OFF
+        fcols = off if opT else np.ones(nc, bool)
+        tcols = np.ones(nc, bool) if opT else off
+        if np.any(fcols):
+            np.add.at(acc, ridx, B[:, fcols] @ x[cidx[fcols]])
+        if np.any(tcols):
+            np.add.at(acc, cidx[tcols], B[:, tcols].T @ x[ridx])
+    return alpha * acc if strong else beta * y0 + alpha * acc
+
+
+def _img_bytes(A, which):
+    from bsm_amd import _lib as L
+    n = C.c_int64(0)
+    L.check(L.lib().bsm_get_image(A._h.ptr, which, None, C.byref(n)))
+    buf = np.zeros(max(n.value, 1), dtype=np.uint8)
+    L.check(L.lib().bsm_get_image(A._h.ptr, which, buf.ctypes.data, C.byref(n)))
+    return buf[:n.value]
+
+
+def _bookkeeping_equal(A, B):
+    from bsm_amd import _lib as L
+    for which in range(7):
+        try:
+            a = A._bookkeeping(which)
+        except L.BsmError:
+            with pytest.raises(L.BsmError):
+                B._bookkeeping(which)
+            continue
+        assert np.array_equal(a, B._bookkeeping(which)), f"bookkeeping {which}"
+
+
+@pytest.mark.parametrize("T_, S_", PAIRS)
+@pytest.mark.parametrize("ctor", CTORS)
+def test_mixed_image_equals_rounded_single_image(bsm, oracle, ctor, T_, S_):
+    p = _problem(bsm, ctor, T_)
+    A = _build(bsm, ctor, p, storage=S_)
+    As = _build(bsm, ctor, p, dtype_cast=S_)
+    At = _build(bsm, ctor, p)
+    assert A.dtype == np.dtype(T_) and A.storage_dtype == np.dtype(S_)
+    assert bsm.eltype(A) == np.dtype(T_)
+    assert As.storage_dtype == As.dtype == np.dtype(S_)
+    # the packed image: byte for byte the single-precision handle's (values, rows, cols)
+    for which in (0, 1, 2):
+        assert np.array_equal(_img_bytes(A, which), _img_bytes(As, which)), f"image array {which}"
+    # reference bookkeeping: that of the double-precision handle (and of the single one -- it is value-blind)
+    _bookkeeping_equal(A, At)
+    for attr in ("perm", "rowptr", "colindices", "rowindices"):
+        if hasattr(At, attr) and isinstance(getattr(At, attr), np.ndarray):
+            assert np.array_equal(getattr(A, attr), getattr(At, attr))
+    # statistics: stored bytes for the values, vector bytes for x and y
+    st, ss, stt = A.stats(), As.stats(), At.stats()
+    assert st["stored_entries"] == stt["stored_entries"] == ss["stored_entries"]
+    assert st["nnz"] == stt["nnz"]
+    ts, tt = np.dtype(S_).itemsize, np.dtype(T_).itemsize
+    nrows, ncols = A.size
+    assert st["alg_bytes"] == stt["alg_bytes"] - st["stored_entries"] * (tt - ts)
+    assert st["alg_bytes"] == ss["alg_bytes"] + (nrows + ncols) * (tt - ts)
+    assert st["device_bytes"] == ss["device_bytes"]  # (no gather workspace: values + metadata only)
+    # the image decoded in fp64 against the oracle on the ROUNDED blocks
+    orc_p = _oracle_problem(ctor, _rounded(p, S_))
+    rng = np.random.default_rng(11)
+    n = A.size[0]
+    x = rand_vec(rng, n, T_)
+    y0 = rand_vec(rng, n, T_)
+    for op in OPS:
+        for alpha, beta, strong in ((1, 0, True), (0.5, 2.0, False)):
+            ref = oracle_mul(oracle, orc_p, op, x, y0, alpha, beta, strong)
+            got = decode_mixed(A, op, x, y0, alpha, beta, strong)
+            assert relerr(got, ref) <= 1e-14, (op, alpha, beta)
+
+
+@pytest.mark.parametrize("T_, S_", PAIRS)
+@pytest.mark.parametrize("ctor", ["blocksparse", "vbcrs"])
+def test_mixed_transposed_image(bsm, oracle, ctor, T_, S_):
+    p = _problem(bsm, ctor, T_)
+    A = _build(bsm, ctor, p, storage=S_, transpose_image=1)
+    As = _build(bsm, ctor, p, dtype_cast=S_, transpose_image=1)
+    assert len(_img_bytes(A, 16)) > 16  # the handle has a transposed ordering
+    for which in (16, 17, 18):
+        assert np.array_equal(_img_bytes(A, which), _img_bytes(As, which)), f"transposed image array {which}"
+    orc_p = _oracle_problem(ctor, _rounded(p, S_))
+    rng = np.random.default_rng(5)
+    x = rand_vec(rng, A.size[0], T_)
+    y0 = rand_vec(rng, A.size[1], T_)
+    for op in (T, Cc):
+        ref = oracle_mul(oracle, orc_p, op, x, y0, 0.5, 2.0, False)
+        assert relerr(decode_mixed(A, op, x, y0, 0.5, 2.0, False, timage=True), ref) <= 1e-14
+
+
+@pytest.mark.parametrize("key", ["cuboid", "sphere"])
+@pytest.mark.parametrize("ctor", ["symmetric", "vbcrs_from_symmetric"])
+def test_mixed_golden_fixtures(bsm, oracle, key, ctor):
+    p = fixture_problem(key)  # ComplexF64 BEM near field (the reference's own fixture)
+    A = _build(bsm, ctor, p, storage=np.complex64)
+    As = _build(bsm, ctor, p, dtype_cast=np.complex64)
+    for which in (0, 1, 2):
+        assert np.array_equal(_img_bytes(A, which), _img_bytes(As, which))
+    orc_p = _oracle_problem(ctor, _rounded(p, np.complex64))
+    rng = np.random.default_rng(3)
+    x = rand_vec(rng, A.size[0], np.complex128)
+    y0 = rand_vec(rng, A.size[0], np.complex128)
+    for op in OPS:
+        ref = oracle_mul(oracle, orc_p, op, x, y0, 1j, 0.5, False)
+        assert relerr(decode_mixed(A, op, x, y0, 1j, 0.5, False), ref) <= 1e-14
+    # against the ORIGINAL blocks: within single-precision rounding, far from the fp64 result
+    ref = oracle_mul(oracle, _oracle_problem(ctor, p), N, x, y0)
+    err = relerr(decode_mixed(A, N, x, y0), ref)
+    assert 1e-10 < err < 1e-5
+
+
+def test_mixed_gather_workspace_is_double(bsm):
+    p = _problem(bsm, "symmetric", np.float64)
+    A = _build(bsm, "symmetric", p, storage=np.float32, accumulate="gather")
+    As = _build(bsm, "symmetric", p, dtype_cast=np.float32, accumulate="gather")
+    _, _, cols, waves = get_image(A)
+    lead_rows = int(np.sum(waves["m"][(waves["work"] == WORK_PANEL) & (waves["lead"] == 1)]))
+    slots = len(cols) + lead_rows + 8
+    assert A.stats()["device_bytes"] == As.stats()["device_bytes"] + slots * 4
+
+
+def test_rounding_is_numpy_astype(bsm):
+    """one rounding at pack time, IEEE round-to-nearest-even: subnormals kept, overflow to +-inf, ties to even"""
+    f32 = np.finfo(np.float32)
+    special = np.array([1e-40, -3e-42, 1e-46, 3.5e38, -1e39, f32.max, 1 + 2.0 ** -24, 1 + 3 * 2.0 ** -24,
+                        np.pi, -np.e, 0.0, -0.0, 2.0 ** -149, 1.5 * 2.0 ** -149], dtype=np.float64)
+    blk = np.asfortranarray(np.resize(special, (16, 4)))
+    for T_, S_, b in ((np.float64, np.float32, blk), (np.complex128, np.complex64, blk + 1j * blk[::-1])):
+        b = np.asfortranarray(b)
+        M = bsm.matrices
+        A = M.VariableBlockCompressedRowStorage([b], [1], [1], (16, 4), device=NODEV, storage=S_)
+        with np.errstate(over="ignore"):
+            bs = np.asfortranarray(b.astype(S_))
+        As = M.VariableBlockCompressedRowStorage([bs], [1], [1], (16, 4), device=NODEV)
+        assert np.array_equal(_img_bytes(A, 0), _img_bytes(As, 0))
+        vals = _img_bytes(A, 0).view(S_)
+        assert np.isinf(vals.real).sum() > 0 and np.any((vals.real != 0) & (np.abs(vals.real) < f32.tiny))
+
+
+def test_mixed_refusals(bsm):
+    from bsm_amd import _lib as L
+    lib = L.lib()
+    p = _problem(bsm, "blocksparse", np.float64)
+    A = _build(bsm, "blocksparse", p, storage=np.float32)
+    # bsm_update_blocks: BSM_ERR_UNSUPPORTED, through the C ABI and the mirror
+    ld = np.array([b.shape[0] for b in p["blocks"]], dtype=np.int64)
+    ptrs = (C.c_void_p * len(p["blocks"]))(*[b.ctypes.data for b in A.blocks])
+    rc = lib.bsm_update_blocks(A._h.ptr, len(p["blocks"]), None, ptrs, ld.ctypes.data_as(C.POINTER(C.c_int64)),
+                               L.BSM_MEM_HOST, None)
+    assert rc == -2 and b"mixed-precision" in lib.bsm_last_error()
+    with pytest.raises(NotImplementedError):
+        bsm.update_blocks(A, [p["blocks"][0]], ids=[1])
+    with pytest.raises(NotImplementedError):
+        bsm.refresh(A)
+    # bsm_vec_add_segments takes vector types only
+    for code in (L.BSM_F64_F32, L.BSM_C128_C64):
+        assert lib.bsm_vec_add_segments(code, None, 0, None, None, None, None) == -1
+        assert b"vector type" in lib.bsm_last_error()
+    # an unknown code is still unknown
+    with pytest.raises(L.BsmError, match="unknown dtype"):
+        from bsm_amd.matrices import _options, SerialScheduler
+        o = _options(SerialScheduler(), NODEV, "auto")
+        h = C.c_void_p()
+        blk = np.asfortranarray(np.ones((2, 2)))
+        one = np.array([1], dtype=np.int64)
+        two = np.array([2], dtype=np.int64)
+        I = C.POINTER(C.c_int64)
+        L.check(lib.bsm_vbcrs_create(6, 2, 2, 1, (C.c_void_p * 1)(blk.ctypes.data), two.ctypes.data_as(I),
+                                     two.ctypes.data_as(I), two.ctypes.data_as(I), one.ctypes.data_as(I),
+                                     one.ctypes.data_as(I), C.byref(o), C.byref(h)))
+    # multi-device handles: refused before any device is touched (the context is never dereferenced)
+    from bsm_amd.matrices import _options, SerialScheduler
+    o = _options(SerialScheduler(), NODEV, "auto")
+    o.ctx = C.c_void_p(1)
+    h = C.c_void_p()
+    blk = np.asfortranarray(np.ones((2, 2)))
+    one = np.array([1], dtype=np.int64)
+    two = np.array([2], dtype=np.int64)
+    I = C.POINTER(C.c_int64)
+    for code in (L.BSM_F64_F32, L.BSM_C128_C64):
+        rc = lib.bsm_vbcrs_create(code, 2, 2, 1, (C.c_void_p * 1)(blk.ctypes.data), two.ctypes.data_as(I),
+                                  two.ctypes.data_as(I), two.ctypes.data_as(I), one.ctypes.data_as(I),
+                                  one.ctypes.data_as(I), C.byref(o), C.byref(h))
+        assert rc == -2 and b"single-device" in lib.bsm_last_error()
+
+
+def test_mirror_storage_keyword(bsm):
+    M = bsm.matrices
+    p64 = _problem(bsm, "vbcrs_from_blocksparse", np.float64)
+    args = (p64["rowindices"], p64["colindices"], p64["size"])
+    b32 = [np.asfortranarray(b.astype(np.float32)) for b in p64["blocks"]]
+    bc = [np.asfortranarray(b.astype(np.complex128)) for b in p64["blocks"]]
+    for blocks, storage in ((p64["blocks"], np.complex64), (p64["blocks"], np.float16), (b32, np.float32),
+                            (bc, np.float32), (p64["blocks"], np.float64), (bc, np.complex128), (b32, np.float64),
+                            (p64["blocks"], "not a dtype")):
+        with pytest.raises(TypeError):
+            M.BlockSparseMatrix(blocks, *args, device=NODEV, storage=storage)
+    with pytest.raises(ValueError, match="single-device"):
+        M.BlockSparseMatrix(p64["blocks"], *args, storage=np.float32, devices=[0, 0])
+    A = M.BlockSparseMatrix(p64["blocks"], *args, device=NODEV, storage=np.float32)
+    assert A.storage_dtype == np.float32 and A.dtype == np.float64
+    V = M.VariableBlockCompressedRowStorage(A, device=NODEV)  # inherits the source's storage
+    assert V.storage_dtype == np.float32 and V.dtype == np.float64
+    P = M.BlockSparseMatrix(p64["blocks"], *args, device=NODEV)
+    assert P.storage_dtype == P.dtype == np.float64
