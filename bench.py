@@ -1,16 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the block-sparse mul! hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 A "step" is ONE mul!(y, A, x) (3-argument form, alpha = 1, beta = Bool false) through the C ABI
 (libbsmrocm.so: bsm_mul) with A, x and y resident in HBM.
 
+A plain run does only what the headline needs: set-up, the W warm-up steps, the K timed steps, --dump-outputs,
+the result line.  --full adds everything else this script measures or checks (below: `extra`, the CPU baselines,
+the live stream floor and counter passes of `roofline`, the sampled oracle check and the N = 1 anchor of the
+partitioned workloads); the headline figures are the same with and without it.
+
 N = 1 (default): BASELINE.json configs[1] = C2, VBCRS 100 000 x 100 000, 5 000 variable 8-64 sized
     fp64 blocks (SplitMix64 seed 0xB5A2); the K timed steps are one hipGraph replay of
-    K bsm_mul launches.  `roofline` describes that kernel; `extra` adds driver-timed HBM-resident
-    legs (a 1.1 GB C2-shaped VBCRS operator, the C3 fused symmetric product), a cold-cache figure and
-    the CPU baselines.
+    K bsm_mul launches.  `roofline` describes that kernel; with --full, `extra` adds driver-timed
+    HBM-resident legs (a 1.1 GB C2-shaped VBCRS operator, the C3 fused symmetric product), a cold-cache
+    figure and the CPU baselines.
 
 N > 1 (one process per GPU, launched by torch.distributed.run, RCCL): the 8-GPU configuration the
     metric is quoted on in fp64 -- C5, SymmetricBlockMatrix 5M x 5M, mixed 16-256 block sizes (28.6 GB)
@@ -20,13 +25,13 @@ N > 1 (one process per GPU, launched by torch.distributed.run, RCCL): the 8-GPU 
     holds): point-to-point exchange of the x halo, fused A + A^T local product, point-to-point
     exchange + add of the partial-y segments that belong to the neighbouring rank (ncclSend/Recv over
     xGMI).  All of it is inside the timed region.  `extra.c4` reports C4 (VBCRS 2M x 2M, 128x128 fp32
-    blocks, 16.4 GB, scattered block columns: all-gather of the x slices, then the local product).
+    blocks, 16.4 GB, scattered block columns: all-gather of the x slices, then the local product; --full).
     --workload c2 keeps the old weak-scaling C2 run.
 
 metric value = algorithmic bytes of the whole job (every stored entry once + block
 metadata + x once + y once) * K / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the `roofline` and `cpu_baseline` objects.  --dump-outputs DIR also writes the y of
+Prints ONE JSON line on rank 0 (with --full also the `cpu_baseline` object).  --dump-outputs DIR also writes the y of
 the last timed step to DIR (dump_outputs): the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
@@ -430,11 +435,16 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--workload", choices=["auto", "c2", "c5"], default="auto",
-                    help="auto: C2 at N = 1, strong-scaled C5 (+ C4 in `extra`) at N > 1")
+                    help="auto: C2 at N = 1, strong-scaled C5 (+ C4 in `extra` with --full) at N > 1")
     ap.add_argument("--launch", choices=["graph", "eager"], default="graph",
                     help="graph (N = 1): the K timed steps are one hipGraph replay of K bsm_mul launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the additional legs in `extra`")
+    ap.add_argument("--full", action="store_true", help="besides the headline, everything else this script measures or "
+                    "checks: `extra` (other operators, precisions and cache states), the CPU baselines, the live stream "
+                    "floor and rocprofv3 passes of `roofline`; N > 1 / --workload c5: C4, the sampled oracle check, the "
+                    "local-launch timing and the N = 1 anchor.  A plain run sets up, warms up, times the K steps, writes "
+                    "--dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the additional legs in `extra`")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to "
                     "rehearse the N > 1 code path on a single GPU)")
     ap.add_argument("--device", type=int, default=None, help="override LOCAL_RANK as the HIP device (rehearsal)")
@@ -442,8 +452,8 @@ def main():
     ap.add_argument("--note", default=None, help="free text carried into config.note (set by the self-launcher)")
     ap.add_argument("--no-overlap", action="store_true", help="N > 1: strictly serial exchange / product / exchange "
                     "(the round-2 step) instead of the overlapped one")
-    ap.add_argument("--no-live-pmc", action="store_true", help="take roofline.traffic from the stamped file under profiles/ "
-                    "instead of two rocprofv3 passes of this run")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: take roofline.traffic from the stamped file under "
+                    "profiles/ (what a plain run does) instead of two rocprofv3 passes of this run")
     ap.add_argument("--loopback", action="store_true", help="N = 1, --workload c5: initialise the backend (nccl = RCCL) with ONE rank and run "
                     "the N > 1 step for real -- the rank owns all but the first and last 8 diagonal segments, a phantom neighbour (this "
                     "same process) the rest, so the x halo and the partial-y halo travel through grouped self send / recv beside the "
@@ -701,22 +711,24 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
         elapsed = time.perf_counter() - t0
         chk = (1, n) if loopback else own  # loopback: the phantom's rows are this process's too -- every row is checked
         y_step = y[chk[0] - 1:chk[1]].clone()
-        # the local kernels alone (HIP events on the stream they are launched on), for the roofline object
-        yk = torch.zeros_like(y)
-        plans = [bsm.MulPlan(yk, h, x) for h in handles]
+        kmax = None
+        if args.full:
+            # the local kernels alone (HIP events on the stream they are launched on), for the roofline object
+            yk = torch.zeros_like(y)
+            plans = [bsm.MulPlan(yk, h, x) for h in handles]
 
-        def local_only():
-            for pl in plans:
-                pl()
-        for _ in range(3):
-            local_only()
-        torch.cuda.synchronize()
-        # (median of three batches: exchange_us is the difference of two millisecond figures)
-        kdur = sorted(timed(local_only, max(5, steps // 4), torch) for _ in range(3))[1]
-        del plans, yk
+            def local_only():
+                for pl in plans:
+                    pl()
+            for _ in range(3):
+                local_only()
+            torch.cuda.synchronize()
+            # (median of three batches: exchange_us is the difference of two millisecond figures)
+            kdur = sorted(timed(local_only, max(5, steps // 4), torch) for _ in range(3))[1]
+            del plans, yk
+            kmax, _ = reduce_scalars(kdur, 0)
         elapsed, total = reduce_scalars(elapsed, rank_bytes)
         total += 2 * n * es
-        kmax, _ = reduce_scalars(kdur, 0)
         # parity of the distributed result: this rank's y slice against a product that needs NO exchange --
         # every block that contributes to the rank's rows in one ordinary handle, applied to the full x
         del P, handles
@@ -737,7 +749,7 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
         # rows of this rank, runs the reference loop restatement on that sub-problem with the full x, and this rank's y of
         # the last timed step is compared on those rows (max |dy| / max |y| over them; max over ranks)
         osamp = float("nan")
-        if sampler is not None and not getattr(args, "no_oracle_check", False):
+        if sampler is not None and args.full and not getattr(args, "no_oracle_check", False):
             from oracle import load_oracle
             orc = None
             if rank == 0:  # rank 0 first: builds oracle/libbsm_oracle.so if the tree has none
@@ -765,7 +777,7 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
             osamp_max = None
         return dict(oracle_sampled=osamp_max, desc=desc, elapsed=elapsed, total_bytes=total, kdur=kmax, rank_alg=rank_bytes + 2 * n * es // world,
                     setup_s=t_setup, parity=pmax, n=n, own=own, overlap=overlap,
-                    exchange_us=(elapsed / steps - kmax) * 1e6, y=y_step)
+                    exchange_us=(elapsed / steps - kmax) * 1e6 if kmax is not None else None, y=y_step)
 
     def run_checked(share, steps, warmup, tol):
         r = run(share, steps, warmup, not args.no_overlap)
@@ -785,7 +797,7 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
         dump_outputs(args.dump_outputs, {"y" if world == 1 else "y_rank%d" % rank: r5["y"].cpu().numpy()}, world)
     value = r5["total_bytes"] * steps / r5["elapsed"] / 1e9
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
       try:  # (an additional figure must never cost the headline line)
         torch.cuda.empty_cache()
         r4 = run_checked(c4_share, steps, warmup, 1e-5)
@@ -804,12 +816,14 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
         if dist is not None:
             raise  # a rank that skipped collectives would hang the others: fail loudly instead
     kb = r5["rank_alg"]
-    roofline = {"bound": "hbm", "achieved": round(kb / r5["kdur"] / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(kb / r5["kdur"] / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
-                "kernel": "bsm::panel_kernel<double,8,true,true,true> (fused A + A^T, one rank's share: interior launch + boundary launch)",
-                "alg_bytes_per_launch": int(kb), "avg_launch_us": round(r5["kdur"] * 1e6, 2),
-                "note": "slowest rank's local launches alone (HIP events, back to back on one stream); a step adds the "
-                        "x-halo and partial-y-halo exchanges, overlapped with the interior launch (exchange_us = step - this)"}
+    roofline = None
+    if r5["kdur"] is not None:
+        roofline = {"bound": "hbm", "achieved": round(kb / r5["kdur"] / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(kb / r5["kdur"] / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
+                    "kernel": "bsm::panel_kernel<double,8,true,true,true> (fused A + A^T, one rank's share: interior launch + boundary launch)",
+                    "alg_bytes_per_launch": int(kb), "avg_launch_us": round(r5["kdur"] * 1e6, 2),
+                    "note": "slowest rank's local launches alone (HIP events, back to back on one stream); a step adds the "
+                            "x-halo and partial-y-halo exchanges, overlapped with the interior launch (exchange_us = step - this)"}
     ranks_seen = world
     backend = args.backend
     if dist is not None:
@@ -837,11 +851,12 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
                    "parity_vs_oracle_sampled_check": "every rank: its y of the last timed step vs oracle/bsm_oracle.c (orc_sym_mul, the reference's "
                                                      "three sweeps) on %d sampled diagonal segments of its rows -- the blocks reaching them regenerated "
                                                      "on the host from the same SplitMix64 streams (synthetic.config5_sample); max over ranks" % ORACLE_SAMPLES,
-                   "exchange_us": round(r5["exchange_us"], 1),
-                   "local_kernel_us_max": round(r5["kdur"] * 1e6, 1),
-                   "frac_of_hbm_peak": round(value / (HBM_PEAK_GBPS * world), 4)},
-        "roofline": roofline,
+                   "exchange_us": round(r5["exchange_us"], 1) if r5["kdur"] is not None else None,
+                   "local_kernel_us_max": round(r5["kdur"] * 1e6, 1) if r5["kdur"] is not None else None,
+                   "frac_of_hbm_peak": round(value / (HBM_PEAK_GBPS * world), 4), "full": bool(args.full)},
     }
+    if roofline is not None:
+        out["roofline"] = roofline
     notes = [t for t in (args.note, r5.get("note")) if t]
     if loopback:
         out["config"]["loopback"] = {
@@ -850,7 +865,7 @@ def run_partitioned(args, bsm, torch, dist, np, rank, world, barrier, reduce_sca
                     "the boundary blocks travel through grouped self send / recv (batch_isend_irecv on device tensors) on the side "
                     "stream beside the interior launch; every row of y is checked against an ordinary single-handle product" % (backend, r5["own"][0], r5["own"][1]),
             "librccl_loaded": bool([ln for ln in open("/proc/self/maps") if "librccl" in ln])}
-    if world > 1:
+    if world > 1 and args.full:
         # The SAME operator on ONE GPU through the same code path -- what this line's value has to be divided by for a
         # speed-up (the driver's own N = 1 run times C2: another operator, Infinity-Cache-resident).  Sources, best first:
         #   1. measured NOW: rank 0 alone, on its own GPU, after the N-rank run (same box, same build; the other ranks wait
@@ -1038,7 +1053,7 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
     kdur = dev_elapsed / args.steps
     achieved = alg_bytes / kdur / 1e9
     pmc, why, traffic_src = None, None, None
-    if rank == 0 and world == 1 and not args.no_live_pmc:
+    if rank == 0 and world == 1 and args.full and not args.no_live_pmc:
         pmc, why_live = live_traffic("panel_kernel<double, 8, true, false", int(alg_bytes))
         traffic_src = "two rocprofv3 --pmc passes of THIS run (FETCH_SIZE, WRITE_SIZE; 60 eager launches each)" if pmc else None
         if pmc is None:
@@ -1056,13 +1071,13 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
                 "kernel": KERNEL, "build": build,
                 "alg_bytes_per_launch": int(alg_bytes), "avg_launch_us": round(kdur * 1e6, 3),
                 "note": "warm: the 54 MB operator stays in the 256 MiB Infinity Cache between launches, so `frac` divides "
-                        "a cache-resident launch by the HBM peak -- stream_floor_us is what a BARE streaming read of the "
-                        "same byte count takes in the same state (same request shape, nothing else to do) and "
+                        "a cache-resident launch by the HBM peak -- stream_floor_us (--full) is what a BARE streaming read "
+                        "of the same byte count takes in the same state (same request shape, nothing else to do) and "
                         "frac_of_stream_floor the honest distance; extra.hbm_vbcrs_fp64 / extra.c3_fused / "
-                        "extra.bem_tiled are HBM-streaming legs.  traffic = rocprofv3 FETCH_SIZE x2 (gfx950 "
+                        "extra.bem_tiled (--full) are HBM-streaming legs.  traffic = rocprofv3 FETCH_SIZE x2 (gfx950 "
                         "correction) + WRITE_SIZE per launch (traffic_source)"}
     floor = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             floor = StreamFloor(torch, alg_bytes)
             for _ in range(20):
@@ -1077,12 +1092,12 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
             roofline["stream_floor_error"] = repr(e)
 
     extra = {}
-    if rank == 0 and launch == "graph":
+    if rank == 0 and launch == "graph" and args.full:
         for _ in range(20):
             plan()
         torch.cuda.synchronize()
         extra["eager_us_per_step"] = round(timed(plan, args.steps, torch) * 1e6, 3)
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")
         dirty = lambda: flush.fill_(1)
         clean = lambda: flush.sum()
@@ -1184,8 +1199,8 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
         except Exception as e:  # pragma: no cover
             extra["c5_n1_rccl_loopback"] = {"error": repr(e)}
         torch.cuda.empty_cache()
-    mf, why_mf = counter_file(MFMA_FILE, build)
-    if rank == 0:
+    if rank == 0 and args.full:
+        mf, why_mf = counter_file(MFMA_FILE, build)
         extra["c4_mfma"] = mf if mf else {"unavailable": why_mf}
 
     out = {
@@ -1200,7 +1215,7 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
                    "alg_bytes_per_gpu": int(alg_bytes), "launch": launch,
                    "timed_region": "the K = %d steps once, between two barriers: %.4f ms wall time (slowest rank); ms_per_step = "
                                    "that / K" % (args.steps, elapsed * 1e3),
-                   "partition": "block rows, no data-path collective",
+                   "partition": "block rows, no data-path collective", "full": bool(args.full),
                    "frac_of_hbm_peak": round(value / (HBM_PEAK_GBPS * world), 4)},
         "roofline": roofline,
     }
@@ -1212,7 +1227,7 @@ def run_c2(args, bsm, torch, dist, np, rank, world, barrier, reduce_scalars):
 
     # ---- CPU baseline: the oracle (reference loop structure, C port), rank 0, N = 1 only -------------
     # LAST: every GPU figure above is complete (and kept on stderr) before these ~15 s of host work start
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         print("[bench] GPU legs complete, CPU baseline next: " + json.dumps(out), file=sys.stderr, flush=True)
         try:
             orc = native_oracle()

@@ -1,10 +1,11 @@
-"""CPU suite: the pieces of bench.py and distributed.py that need no GPU -- counter files tied to a build, the
-interior / boundary split of a rank's blocks."""
+"""The pieces of bench.py and distributed.py that need no GPU -- counter files tied to a build, the
+interior / boundary split of a rank's blocks -- and one plain bench.py run on the GPU."""
 import json
 import os
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -137,6 +138,32 @@ def test_bench_refuses_a_step_count_below_one():
     import subprocess
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_bench_offers_the_full_run_as_an_option():
+    """everything beside the headline sits behind --full: the option exists and is off unless given"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
+@pytest.mark.gpu
+def test_a_plain_bench_run_prints_the_headline_and_nothing_else(tmp_path):
+    """bench.py without --full: set-up, warm-up, the K timed steps, --dump-outputs and the result line -- no `extra`
+    legs, no CPU baseline, no stream floor or counter passes"""
+    import subprocess
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "GB/s" and d["dtype"] == "f64" and d["higher_is_better"]
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["config"]["full"] is False
+    assert "extra" not in d and "cpu_baseline" not in d and "stream_floor_us" not in d["roofline"]
+    y = np.load(out / "y.npy")
+    assert y.shape == (100_000,) and np.all(np.isfinite(y))
 
 
 def test_native_oracle_of_the_cpu_baseline_is_built_outside_the_tree(oracle):

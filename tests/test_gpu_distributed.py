@@ -178,16 +178,16 @@ def test_row_partitioned_with_the_hip_local_product(kind, world):
 
 
 def test_bench_launches_its_own_ranks_and_reports_parity():
-    """`python bench.py --gpus 2` as the driver invokes it (no torch.distributed.run in front): the script starts
-    its own rank processes, runs the overlapped C5 step + C4 in `extra` (gloo rehearsal: both ranks on cuda:0,
-    operators shrunk) and prints ONE line with the parity number, the exchange time and the ranks it saw."""
+    """`python bench.py --gpus 2 --full` (no torch.distributed.run in front): the script starts its own rank
+    processes, runs the overlapped C5 step + C4 in `extra` (gloo rehearsal: both ranks on cuda:0, operators shrunk)
+    and prints ONE line with the parity number, the exchange time and the ranks it saw."""
     import json
     import subprocess
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0",
-                        "--scale", "0.02", "--steps", "4", "--warmup", "2"], env=env, stdout=subprocess.PIPE,
+                        "--scale", "0.02", "--steps", "4", "--warmup", "2", "--full"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]

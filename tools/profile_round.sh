@@ -9,9 +9,9 @@ rm -rf $O && mkdir -p $O
 BEFORE=${BSM_LIB_BEFORE:-$R/blocksparsematrices.jl_amd/libbsmrocm_head.so}
 cd /tmp
 say() { echo "[profile_round] $*"; }
-# 1. kernel trace + stats of the default bench command (the driver's command line)
-say "kernel trace of the default bench"
-rocprofv3 --output-format csv --kernel-trace --stats -d $O/kt -o kt -- python3 $R/bench.py --no-live-pmc > $O/r04_bench_c2_n1_under_rocprofv3.json 2> $O/bench_under_kt.err
+# 1. kernel trace + stats of the full bench run (--full: every leg beside the headline)
+say "kernel trace of the full bench"
+rocprofv3 --output-format csv --kernel-trace --stats -d $O/kt -o kt -- python3 $R/bench.py --full --no-live-pmc > $O/r04_bench_c2_n1_under_rocprofv3.json 2> $O/bench_under_kt.err
 # 2. HBM traffic of the C2 product: one counter per pass
 for c in FETCH_SIZE WRITE_SIZE; do
   say "C2 $c"
@@ -66,7 +66,7 @@ head -12 $O/r04_c2_bench_default_kernel_trace_by_grid.csv
 # 6. un-profiled reference runs (bench.py reads the counter files of THIS build: copy them where it looks first)
 cp $O/r04_c2_pmc.json $O/r04_c4_mfma.json $R/profiles/
 say "bench.py --gpus 1 --workload c5 (the anchor of the N > 1 lines)"
-python3 bench.py --gpus 1 --workload c5 --steps 20 --warmup 3 > $O/r04_bench_c5_full_one_gpu.json 2> /dev/null
+python3 bench.py --gpus 1 --workload c5 --steps 20 --warmup 3 --full > $O/r04_bench_c5_full_one_gpu.json 2> /dev/null
 python3 - $O/r04_bench_c5_full_one_gpu.json $O/r04_c5_n1.json <<'PY'
 import json, sys
 sys.path.insert(0, ".")
@@ -75,14 +75,14 @@ d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 out = {"value": d["value"], "unit": "GB/s", "ms_per_step": d["ms_per_step"], "steps": d["steps"], "exchange_us": d["config"]["exchange_us"],
        "local_kernel_us_max": d["config"]["local_kernel_us_max"], "parity_relerr": d["config"]["parity_relerr"],
        "workload": "C5 (SymmetricBlockMatrix 5M x 5M, 16-256 blocks, fp64, 29.0 GB algorithmic) on ONE MI355X through the N > 1 code path: "
-                   "python bench.py --gpus 1 --workload c5 --steps 20 --warmup 3",
+                   "python bench.py --gpus 1 --workload c5 --steps 20 --warmup 3 --full",
        "build": _lib.lib().bsm_version().decode().split("build ")[-1]}
 json.dump(out, open(sys.argv[2], "w"), indent=1)
 print(json.dumps(out))
 PY
 cp $O/r04_c5_n1.json $R/profiles/
-say "default bench"
-python3 bench.py > $O/r04_bench_c2_n1.json 2> /dev/null
+say "full bench"
+python3 bench.py --full > $O/r04_bench_c2_n1.json 2> /dev/null
 python3 tools/abbench.py > $O/r04_abbench.txt 2> /dev/null
 python3 tools/kbench.py c2 500 T > $O/r04_c2_transposed.txt 2>&1 || true
 KB_TIMG=1 python3 tools/kbench.py c2 500 T >> $O/r04_c2_transposed.txt 2>&1 || true
