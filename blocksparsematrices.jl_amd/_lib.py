@@ -55,7 +55,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_vbcrs_create_from_blocksparse", "bsm_ctx_create", "bsm_ctx_destroy", "bsm_ctx_devices",
            "bsm_partition_rows", "bsm_part_info", "bsm_host_register", "bsm_host_unregister", "bsm_rowcolvals",
            "bsm_blocksparse_create",
-           "bsm_symmetric_create", "bsm_mul", "bsm_mul_multi", "bsm_mul_parts", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
+           "bsm_symmetric_create", "bsm_mul", "bsm_mul_multi", "bsm_mul_parts",
+           "bsm_mul_cvec", "bsm_mul_multi_cvec", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
            "bsm_color", "bsm_destroy", "bsm_last_error", "bsm_version",
            "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks"]
 
@@ -134,6 +135,10 @@ def lib():
     L.bsm_mul_multi.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.bsm_mul_multi.restype = C.c_int
+    if hasattr(L, "bsm_mul_cvec") or "BSM_LIB" not in os.environ:  # (developer A/B builds may predate them)
+        L.bsm_mul_cvec.argtypes = L.bsm_mul.argtypes
+        L.bsm_mul_multi_cvec.argtypes = L.bsm_mul_multi.argtypes
+        L.bsm_mul_cvec.restype = L.bsm_mul_multi_cvec.restype = C.c_int
     if hasattr(L, "bsm_mul_parts") or "BSM_LIB" not in os.environ:
         L.bsm_mul_parts.argtypes = [C.c_void_p, C.c_int, _PP, _PP, C.c_void_p, C.c_void_p, C.c_int, _PP]
         L.bsm_mul_parts.restype = C.c_int

@@ -215,7 +215,7 @@ struct DeviceSink : ValueSink {
 std::unique_ptr<ValueSink> make_device_sink(void **d_values) { return std::unique_ptr<ValueSink>(new DeviceSink(d_values)); }
 
 void free_image(DeviceImage &img) {
-    for (void **p : {&img.d_values, &img.d_rows, &img.d_cols, &img.d_waves, &img.d_waves_multi, &img.d_ws, &img.d_inv_ptr[0],
+    for (void **p : {&img.d_values, &img.d_rows, &img.d_cols, &img.d_waves, &img.d_waves_multi, &img.d_ws, &img.d_wsc, &img.d_inv_ptr[0],
                      &img.d_inv_ptr[1], &img.d_inv_idx[0], &img.d_inv_idx[1]}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
@@ -1490,21 +1490,39 @@ bool bsm::il_reserve(ILWork &il, long long need) {
     return true;
 }
 
-// bsm_mul (K = 1, ld = max(length, 1)) and bsm_mul_multi after their argument checks
+// the complex gather workspace of a real image (bsm_mul_cvec), allocated at the first complex gather product -- under
+// the claim, so no product uses it yet; never regrown.  false: no memory (the product takes the atomic path)
+static bool wsc_reserve(const Analysis &an, DeviceImage &img, hipStream_t st) {
+    if (img.d_wsc) return true;
+    const size_t bytes = (size_t)(an.ws_slots + 8) * (size_t)an.vs * 2;
+    void *p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess || hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
+        (void)hipGetLastError();
+        if (p) (void)hipFree(p);
+        return false;
+    }
+    img.d_wsc = p;
+    return true;
+}
+
+// bsm_mul (K = 1, ld = max(length, 1)) and bsm_mul_multi after their argument checks; cvec: bsm_mul_cvec /
+// bsm_mul_multi_cvec (complex vectors under a real single-device handle: every size below in the complex type)
 static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long ldx, void *Y, long long ldy,
-                 const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t st) {
+                 const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t st, bool cvec = false) {
     if (A->dist)  // multi-device handles: every device streams its part once per batch of <= 8 columns
         return dist_mul_multi(A, op, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, st);
     // transposed products run forward on the second ordering when the handle has one
     const bool use_t = (op != BSM_OP_N) && A->has_t;
-    const DeviceImage &img = use_t ? A->img_t : A->img;
+    DeviceImage &img = use_t ? A->img_t : A->img;
     const bool opT = (op != BSM_OP_N) && !use_t;
     const bool conj = (op == BSM_OP_C);
     DeviceGuard guard;
     hipError_t e = guard.enter(img.device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     // one column: the gather workspace (if the image has one); more: the interleaved pass's work arrays (if it applies)
-    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : il_applies(img, opT, K), st);
+    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : il_applies(img, opT, K, cvec), st);
+    if (claim.held && K == 1 && cvec && !wsc_reserve(use_t ? A->an_t : A->an, img, st))
+        claim.held = false;  // no memory for the complex workspace: the atomic path needs none
     ILWork *il = nullptr;
     if (claim.held && K > 1) {  // allocated (and grown) here, at the first product that uses them
         const long long need = std::max(img.nrows, img.ncols);
@@ -1516,14 +1534,14 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     }
     const bool gather = K == 1 && claim.held;
     if (memspace == BSM_MEM_DEVICE) {
-        e = launch_mul(img, opT, conj, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, st, gather, nullptr, il);
+        e = launch_mul(img, opT, conj, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, st, gather, nullptr, il, cvec);
         if (e != hipSuccess) return hip_fail(e, "kernel launch");
         claim.mark();
         return BSM_OK;
     }
     if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "bad memspace");
     // host vectors: stage through device buffers (PCIe), synchronous
-    const size_t es = (size_t)A->an.vs;
+    const size_t es = (size_t)A->an.vs * (cvec ? 2 : 1);  // (complex vectors: twice the handle's vector size)
     const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
     const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
     Staging sg;
@@ -1542,7 +1560,7 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     // by the runtime: 74 vs 118 us per C2-sized product)
     if (e == hipSuccess) e = copy(dx, xlen, X, ldx, xlen, hipMemcpyHostToDevice);
     if (e == hipSuccess && y_in) e = copy(dy, ylen, Y, ldy, ylen, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_mul(img, opT, conj, K, dx, xlen, dy, ylen, alpha, beta, beta_strong_zero, st, gather, nullptr, il);
+    if (e == hipSuccess) e = launch_mul(img, opT, conj, K, dx, xlen, dy, ylen, alpha, beta, beta_strong_zero, st, gather, nullptr, il, cvec);
     claim.mark();
     if (e == hipSuccess) e = copy(Y, ldy, dy, ylen, ylen, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1587,6 +1605,47 @@ extern "C" int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X
     if (ldx < std::max<long long>(xlen, 1) || ldy < std::max<long long>(ylen, 1))
         return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
     return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
+}
+
+// bsm_mul_cvec / bsm_mul_multi_cvec: what a real handle refuses complex vectors for -- checked before anything else that
+// needs a device, so that analysis-only handles reach every answer
+static int cvec_refusal(bsm_matrix_s *A, int op, int memspace) {
+    if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    const int dt = A->an.dtype;
+    if (dt == BSM_C64 || dt == BSM_C128)
+        return fail(BSM_ERR_INVALID, "complex handle: bsm_mul / bsm_mul_multi take its complex vectors");
+    if (dt != BSM_F32 && dt != BSM_F64)
+        return fail(BSM_ERR_UNSUPPORTED, "complex vectors under a mixed-storage handle are not supported");
+    if (A->dist) return fail(BSM_ERR_UNSUPPORTED, "complex vectors under a multi-device handle are not supported");
+    if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
+    if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
+    return BSM_OK;
+}
+
+extern "C" int bsm_mul_cvec(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha, const void *beta,
+                            int beta_strong_zero, int memspace, void *stream) {
+    if (const int r = cvec_refusal(A, op, memspace)) return r;
+    if (!x || !y) return fail(BSM_ERR_INVALID, "null vector");
+    if (!A->on_device)
+        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
+    const long long xlen = std::max<long long>(op == 0 ? A->an.ncols : A->an.nrows, 1);
+    const long long ylen = std::max<long long>(op == 0 ? A->an.nrows : A->an.ncols, 1);
+    return mul_k(A, op, 1, x, xlen, y, ylen, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream, true);
+}
+
+extern "C" int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                                  const void *alpha, const void *beta, int beta_strong_zero, int memspace, void *stream) {
+    if (const int r = cvec_refusal(A, op, memspace)) return r;
+    if (nrhs < 0) return fail(BSM_ERR_INVALID, "negative nrhs");
+    if (nrhs == 0) return BSM_OK;
+    if (!X || !Y) return fail(BSM_ERR_INVALID, "null matrix");
+    if (!A->on_device)
+        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
+    const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
+    const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
+    if (ldx < std::max<long long>(xlen, 1) || ldy < std::max<long long>(ylen, 1))
+        return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
+    return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream, true);
 }
 
 extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *ids, const void *const *blocks,

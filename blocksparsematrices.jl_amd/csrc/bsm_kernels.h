@@ -27,6 +27,9 @@ struct DeviceImage {
     std::vector<long long> color_wg_ptr;  // non-empty: coloured launches, plain read-modify-write
     // gather mode (BSM_ACC_GATHER): workspace + inverted indices for op N [0] and op T / C [1]
     void *d_ws = nullptr;
+    // complex vectors under a real image (bsm_mul_cvec): the workspace in the complex type, (ws_slots + 8) * 2 * vs bytes,
+    // allocated at the first complex gather product that holds the claim (bsm_capi.cpp); null until then
+    void *d_wsc = nullptr;
     void *d_inv_ptr[2] = {nullptr, nullptr}, *d_inv_idx[2] = {nullptr, nullptr};
     long long ws_fbase = 0;
 };
@@ -66,7 +69,8 @@ struct ILWork {
 };
 // whether launch_mul would take the interleaved pass for this image / op / batch (so that the caller only claims -- and
 // allocates -- the work arrays when they will be used)
-bool il_applies(const DeviceImage &img, bool opT, long long nrhs);
+// cvec: complex vectors under a real image (bsm_mul_multi_cvec)
+bool il_applies(const DeviceImage &img, bool opT, long long nrhs, bool cvec = false);
 
 // Enqueues Y = alpha*op(A)*X + beta*Y on `stream` for K right-hand sides, X (ldx) and Y (ldy) column-major device
 // pointers.  No allocation, no synchronisation (graph-capturable).
@@ -75,9 +79,11 @@ bool il_applies(const DeviceImage &img, bool opT, long long nrhs);
 // K > 1: A is streamed once per batch of <= 16 columns; il: the work arrays of the interleaved pass (null: not claimed).
 // zrange = {lo, hi} (0-based, exclusive): the y entries the `y .*= beta` pass of the accumulate path covers instead of
 // the image's own range (multi-device fan-out; ignored by exclusive forward images, whose coverage is part of the image)
+// cvec: x, y, alpha, beta are complex of the precision of a REAL image (BSM_F32 / BSM_F64: bsm_mul_cvec); use_gather then
+// takes img.d_wsc, and il batches of 8 complex columns run the real interleaved pass over their 16 components
 hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, const void *x, long long ldx, void *y,
                       long long ldy, const void *alpha, const void *beta, int strong_zero, hipStream_t stream,
-                      bool use_gather, const long long *zrange, ILWork *il);
+                      bool use_gather, const long long *zrange, ILWork *il, bool cvec = false);
 
 // rowcolvals(A): COO triples (1-based int64 rows / cols, values of the image's vector type) written from
 // the packed device image; d_out_off[w] = first output slot of wave descriptor w (host prefix sum of

@@ -111,6 +111,9 @@ __device__ __forceinline__ c128 cj(c128 a, bool c) { return c128{a.re, c ? -a.im
 template <typename T> __device__ __forceinline__ T widen(T, T a) { return a; }
 __device__ __forceinline__ double widen(double, float a) { return (double)a; }
 __device__ __forceinline__ c128 widen(c128, c64 a) { return c128{(double)a.re, (double)a.im}; }
+// ... and a real image under complex vectors keeps its value real (madd / mul above take it as it is)
+__device__ __forceinline__ double widen(c128, double a) { return a; }
+__device__ __forceinline__ float widen(c64, float a) { return a; }
 
 __device__ __forceinline__ float shx(float a, int d) { return __shfl_xor(a, d, 64); }
 __device__ __forceinline__ double shx(double a, int d) { return __shfl_xor(a, d, 64); }
@@ -120,6 +123,25 @@ __device__ __forceinline__ c64 shx(c64 a, int d) {
 __device__ __forceinline__ c128 shx(c128 a, int d) {
     return c128{__shfl_xor(a.re, d, 64), __shfl_xor(a.im, d, 64)};
 }
+
+// a REAL stored value times a complex vector entry (complex vectors under a real image: bsm_mul_cvec): two FMAs, no
+// widening of the stored value into a complex number with a zero imaginary part (0 * x is not foldable without
+// fast-math: four FMAs per entry)
+__device__ __forceinline__ c64 mul(float a, c64 b) { return c64{a * b.re, a * b.im}; }
+__device__ __forceinline__ c128 mul(double a, c128 b) { return c128{a * b.re, a * b.im}; }
+__device__ __forceinline__ c64 madd(c64 acc, float a, c64 b) {
+    acc.re = fmaf(a, b.re, acc.re);
+    acc.im = fmaf(a, b.im, acc.im);
+    return acc;
+}
+__device__ __forceinline__ c128 madd(c128 acc, double a, c128 b) {
+    acc.re = fma(a, b.re, acc.re);
+    acc.im = fma(a, b.im, acc.im);
+    return acc;
+}
+// complex vectors under a real image: S = the real type of T (c128 / double, c64 / float)
+template <typename T, typename S> constexpr bool kCvec =
+    (std::is_same<T, c128>::value && std::is_same<S, double>::value) || (std::is_same<T, c64>::value && std::is_same<S, float>::value);
 
 // hardware floating-point atomics (global_atomic_add_f32 / _f64; built with
 // -munsafe-fp-atomics so no compare-and-swap loop is emitted)
@@ -620,6 +642,10 @@ __device__ __forceinline__ T run_panel(const WaveD &wd, const uint4 *__restrict_
 }
 
 template <typename T, bool FWD, bool TRN> constexpr int kMixedWaves = (FWD && TRN && std::is_same<T, double>::value) ? 7 : 6;
+// complex vectors under a real image (kCvec): resident waves per SIMD the instances are compiled for
+#ifndef BSM_CVEC_WAVES
+#define BSM_CVEC_WAVES 6
+#endif
 
 // Occupancy is what the small-panel (BEM-shaped) products live on: a small panel is a chain of
 // dependent memory round trips, hidden only by other resident waves.
@@ -635,6 +661,7 @@ template <typename T, bool FWD, bool TRN> constexpr int kMixedWaves = (FWD && TR
 //     72).  No scratch anywhere.
 template <typename T, int L, bool FWD, bool TRN, bool NT, typename S = T>
 __global__ void __launch_bounds__(64 * kWavesPerWg) __attribute__((amdgpu_waves_per_eu(
+    kCvec<T, S> ? BSM_CVEC_WAVES :
     !std::is_same<S, T>::value ? kMixedWaves<T, FWD, TRN> :
     (FWD && TRN && (std::is_same<T, double>::value || std::is_same<T, float>::value)) ? 8 :
     (FWD && TRN && std::is_same<T, c128>::value) ? (L == 4 ? 8 : BSM_C128_FUSED_WAVES) :
@@ -671,7 +698,11 @@ __global__ void __launch_bounds__(64 * kWavesPerWg) __attribute__((amdgpu_waves_
     }
 #endif
     // workgroup-uniform (all 4 descriptors carry the same window; coloured launches keep plain RMW)
-    const int win_n = (WIN && !(flags & FLAG_RMW)) ? wd.win_n : 0;
+    int win_n = (WIN && !(flags & FLAG_RMW)) ? wd.win_n : 0;
+    // complex vectors under a real image: the analysis cut the window at window_entries(sizeof(S)) entries, twice what
+    // the 4 KB of `win` hold in T -- the window is clamped, and the y entries beyond it take the path of every entry
+    // outside a window (global atomics)
+    if constexpr (kCvec<T, S>) win_n = min(win_n, window_entries((int)sizeof(T)));
     if (WIN && win_n > 0) {
         for (int e = threadIdx.x; e < win_n; e += 64 * kWavesPerWg) win[e] = zero_of(T{});
         __syncthreads();
@@ -2366,7 +2397,7 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
     // one launch of panel_kernel<T, L, FWD, TRN, NT, S> with NT taken from the run-time policy `nt`
     auto panel = [&](auto fwd, auto trn, const WaveWork *waves, dim3 grid, unsigned wg_base) {
         constexpr bool FWD = decltype(fwd)::value, TRN = decltype(trn)::value;
-        // mixed precision: only what launch_one_mixed reaches is instantiated (L = 4)
+        // mixed precision and complex vectors: only what launch_one_mixed / launch_one_cvec reach is instantiated (L = 4)
         if constexpr (!std::is_same<S, T>::value && L != 4) {
             unreached = true;
         } else {
@@ -2390,9 +2421,11 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
     // accumulate mode: y .*= beta over the owned range, then hardware atomics (gather mode: the sums go to the
     // workspace, and a second launch adds them up in a fixed order)
     const YRange r = y_range(img, opT, zrange);
-    const bool gather = use_gather && img.d_ws != nullptr;
+    // (complex vectors under a real image: the complex workspace, twice the bytes, allocated at the first such product)
+    void *wsp = kCvec<T, S> ? img.d_wsc : img.d_ws;
+    const bool gather = use_gather && wsp != nullptr;
     if (gather) {
-        ws = (T *)img.d_ws;
+        ws = (T *)wsp;
         flags |= FLAG_GATHER;
     }
     if (!gather && r.hi > r.lo && (strong_zero || !is_one(beta)))
@@ -2438,6 +2471,14 @@ static hipError_t launch_one(const DeviceImage &img, bool opT, bool conj, const 
 template <typename T, typename S>
 static hipError_t launch_one_mixed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
                                    int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
+    return launch_typed<T, 4, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
+}
+
+// Complex vectors under a real image (T = c128 / c64, S = double / float: bsm_mul_cvec): 4 loads per lane in flight in
+// every direction, as the mixed-precision instances -- a lane's 4 strips meet 8 complex128 / 16 complex64 x entries
+template <typename T, typename S>
+static hipError_t launch_one_cvec(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
+                                  int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
     return launch_typed<T, 4, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
 }
 
@@ -2499,8 +2540,15 @@ static int il_real_min_cols() {
     }();
     return v;
 }
-bool il_applies(const DeviceImage &img, bool opT, long long nrhs) {
+bool il_applies(const DeviceImage &img, bool opT, long long nrhs, bool cvec) {
     if (img.dtype > 3) return false;  // mixed-precision images: one-column products only
+    if (cvec) {
+        // complex vectors under a real image: the pass over 2 x nrhs real components streams the matrix once where the
+        // alternative is nrhs one-column products -- every image class takes it, exclusive forward ones included, but
+        // coloured images keep their bitwise reproducible read-modify-write (one-column products)
+        if (img.dtype > 1 || nrhs < 2 || il_mode() == 0 || !img.color_wg_ptr.empty()) return false;
+        return std::max(img.nrows, img.ncols) < (1ll << 30);
+    }
     const bool cplx = img.dtype >= 2;
     if (nrhs < 2) return false;  // (one column: launch_mul's one-column kernels, whatever the thresholds say)
     if (il_mode() == 0 || nrhs < (cplx ? mfma_min_cols() : il_real_min_cols())) return false;
@@ -2515,11 +2563,16 @@ bool il_applies(const DeviceImage &img, bool opT, long long nrhs) {
     (void)cplx;
     return il_mode() == 2 || img.mean_rows < 32.f || img.has_off;
 }
-template <typename T, int KK>
+// KT: the element type of the image the pass runs on -- T, or the real type of T for complex vectors under a real image:
+// then the KK complex columns packed into Xr are 2 KK real components of the real pass (alpha applied in the pack, beta
+// in the finish), and W comes back as KK complex sums
+template <typename T, int KK, typename KT = T>
 static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T *xd, long long ldx, T *yd, long long ldy, T alpha,
                             T beta, int strong_zero, hipStream_t stream, int kact, ILWork &il, const long long *zrange) {
     using R = typename ILT<T>::R;
+    static_assert(std::is_same<KT, T>::value || std::is_same<KT, R>::value, "the image holds T or its real type");
     constexpr int CS = ILT<T>::CPLX ? 2 * KK : KK;  // components per vector index (8 or 16)
+    if (!std::is_same<KT, T>::value) conj = false;  // (op C of a real image is op T)
     const long long xlen = opT ? img.nrows : img.ncols, ylen = opT ? img.ncols : img.nrows;
     if (xlen > il.rows || ylen > il.rows) return hipErrorInvalidValue;
     const int flags = base_flags(opT, conj, 0);  // (beta meets y in the finish pass)
@@ -2554,10 +2607,10 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
             // (tall panels: all row blocks of the next 16 columns in flight -- il_panel's DEEP form, worth 1-6 % over one
             // step ahead with the XCD-aware order, profiles/r05_il_tall_panels.txt)
             if (small)
-                hipLaunchKernelGGL((panel_kernel_il<T, 2, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
+                hipLaunchKernelGGL((panel_kernel_il<KT, 2, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
                                    flags, nblk, xcd_run);
             else
-                hipLaunchKernelGGL((panel_kernel_il<T, 4, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
+                hipLaunchKernelGGL((panel_kernel_il<KT, 4, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
                                    flags, nblk, xcd_run);
         });
     });
@@ -2598,7 +2651,7 @@ static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj
     // grow with the padded width (fp64 x 16: 615 us against 2 x 320).  BSM_MFMA_REAL_MIN_COLS overrides (17: off).
     // short scattered panels: the interleaved pass (above) -- complex types in batches of 8 columns, real types of 16,
     // then one padded remainder
-    if (il && il_applies(img, opT, nrhs)) {
+    if (il && il_applies(img, opT, nrhs, false)) {
         constexpr int KK = ILT<T>::KK;
         const int least = ILT<T>::CPLX ? mfma_min_cols() : il_real_min_cols();
         while (e == hipSuccess && nrhs - k >= least) {
@@ -2668,9 +2721,47 @@ static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj
     return e;
 }
 
+// complex vectors T under a real image of type S: one column -- or every column of a batch the interleaved pass's work
+// arrays are not claimed for -- on the one-column kernels; batches of 8 complex columns (a last one of at most 4: 8
+// components per index) through the real interleaved pass over their 16 (8) real components
+template <typename T, typename S>
+static hipError_t launch_cvec(const DeviceImage &img, bool opT, long long K, const T *xd, long long ldx, T *yd, long long ldy,
+                              T alpha, T beta, int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange,
+                              ILWork *il) {
+    hipError_t e = hipSuccess;
+    long long k = 0;
+    if (il && il_applies(img, opT, K, true)) {
+        while (e == hipSuccess && K - k >= 2) {
+            const int kact = (int)std::min<long long>(8, K - k);
+            if (kact <= 4)
+                e = launch_il<T, 4, S>(img, opT, false, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
+            else
+                e = launch_il<T, 8, S>(img, opT, false, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
+            k += kact;
+        }
+    }
+    for (; e == hipSuccess && k < K; ++k)
+        e = launch_one_cvec<T, S>(img, opT, false, xd + k * ldx, yd + k * ldy, alpha, beta, strong_zero, stream, use_gather && K == 1,
+                                  zrange);
+    return e;
+}
+
 hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, const void *x, long long ldx, void *y,
                       long long ldy, const void *alpha_p, const void *beta_p, int strong_zero, hipStream_t stream,
-                      bool use_gather, const long long *zrange, ILWork *il) {
+                      bool use_gather, const long long *zrange, ILWork *il, bool cvec) {
+    if (cvec) {  // (op C of a real image is op T: `conj` has nothing to act on)
+        auto run_cvec = [&](auto t, auto s) {
+            using T = decltype(t);
+            const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);
+            return launch_cvec<T, decltype(s)>(img, opT, K, (const T *)x, ldx, (T *)y, ldy, alpha, beta, strong_zero, stream,
+                                               use_gather, zrange, il);
+        };
+        switch (img.dtype) {
+            case 0: return run_cvec(c64{}, float{});
+            case 1: return run_cvec(c128{}, double{});
+        }
+        return hipErrorInvalidValue;
+    }
     auto run = [&](auto t) {
         using T = decltype(t);
         const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);

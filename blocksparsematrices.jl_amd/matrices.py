@@ -796,11 +796,43 @@ def _mat_info(v, dt, n, name, base=None):
     return v.ctypes.data, max(n, 1), v.shape[1], L.BSM_MEM_HOST, None, v
 
 
+# complex vectors under a real handle (bsm_mul_cvec / bsm_mul_multi_cvec): the supported (matrix, vector) pairs
+_CVEC = {np.dtype(np.float32): np.dtype(np.complex64), np.dtype(np.float64): np.dtype(np.complex128)}
+_CVEC_PAIRS = "supported pairs: (float64, complex128) and (float32, complex64)"
+
+
+def _elt(v):
+    """numpy dtype of a vector operand (None: neither a numpy array nor a torch tensor)"""
+    if torch is not None and isinstance(v, torch.Tensor):
+        return _TORCH_DT.get(v.dtype)
+    return v.dtype if isinstance(v, np.ndarray) else None
+
+
+def _vec_type(base, x, y, alpha, beta):
+    """-> (vector dtype, complex vectors under a real handle).  Raises TypeError for the pairs nobody supports."""
+    dt = base.dtype
+    xt, yt = _elt(x), _elt(y)
+    cx, cy = xt is not None and xt.kind == "c", yt is not None and yt.kind == "c"
+    if dt.kind == "c" or not (cx or cy):
+        if dt.kind != "c" and (np.iscomplexobj(alpha) or np.iscomplexobj(beta)):
+            raise TypeError("complex alpha/beta with a real matrix need complex x and y (" + _CVEC_PAIRS + ")")
+        return dt, False
+    if base.storage_dtype != dt:
+        raise TypeError(f"complex vectors under a mixed-storage matrix ({base.storage_dtype} under {dt}) are not "
+                        "supported; " + _CVEC_PAIRS)
+    if base.devices is not None:
+        raise TypeError("complex vectors under a multi-device matrix are not supported; " + _CVEC_PAIRS)
+    ct = _CVEC[dt]
+    if xt != ct or yt != ct:
+        raise TypeError(f"a {dt} matrix with x of {xt} and y of {yt}: " + _CVEC_PAIRS)
+    return ct, True
+
+
 def _mul_matrix(Y, A, X, alpha, beta):
     """mul!(Y, A, X, alpha, beta) with matrices: one bsm_mul_multi call (A streamed once per batch
     of up to 8 columns) instead of LinearMaps' column loop over _unsafe_mul!."""
     base, op = _unwrap(A)
-    dt = base.dtype
+    dt, cvec = _vec_type(base, X, Y, alpha, beta)
     nr, nc = base.size
     ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
     xp, ldx, kx, xms, _, _kx = _mat_info(X, dt, xlen, "X", base)
@@ -812,14 +844,15 @@ def _mul_matrix(Y, A, X, alpha, beta):
     strong = beta is False
     a = _scalar_buf(1 if alpha is True else alpha, dt)
     b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
-    L.check(L.lib().bsm_mul_multi(base._h.ptr, op, kx, xp, ldx, yp, ldy, a.ctypes.data, b.ctypes.data,
-                                  1 if strong else 0, xms, yst))
+    fn = L.lib().bsm_mul_multi_cvec if cvec else L.lib().bsm_mul_multi
+    L.check(fn(base._h.ptr, op, kx, xp, ldx, yp, ldy, a.ctypes.data, b.ctypes.data, 1 if strong else 0, xms, yst))
     return Y
 
 
 def mul(y, A, x, alpha=True, beta=False):
     """LinearAlgebra.mul!(y, A, x, alpha, beta): y = alpha*A*x + beta*y, returns y.
-    x / y may also be matrices (column-major): the multi right-hand-side product.
+    x / y may also be matrices (column-major): the multi right-hand-side product.  A real matrix takes complex x
+    and y of its precision (float64 / complex128, float32 / complex64), with complex alpha / beta if wanted.
 
     `beta is False` (the 3-argument form, reference src/abstractblockmatrix.jl:27-34) is Julia's
     strong zero: y is overwritten, NaN/Inf in the incoming y do not propagate.  A numeric 0.0
@@ -827,15 +860,11 @@ def mul(y, A, x, alpha=True, beta=False):
     base, op = _unwrap(A)
     if not isinstance(base, AbstractBlockMatrix):
         raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
-    dt = base.dtype
     nr, nc = base.size
     ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
     if getattr(x, "ndim", 1) == 2 or getattr(y, "ndim", 1) == 2:
-        if dt.kind != "c" and (np.iscomplexobj(alpha) or np.iscomplexobj(beta)):
-            raise TypeError("complex alpha/beta with a real matrix is not supported on the GPU path")
         return _mul_matrix(y, A, x, alpha, beta)
-    if dt.kind != "c" and (np.iscomplexobj(alpha) or np.iscomplexobj(beta)):
-        raise TypeError("complex alpha/beta with a real matrix is not supported on the GPU path")
+    dt, cvec = _vec_type(base, x, y, alpha, beta)
     xp, xms, xst, _kx = _vec_info(x, dt, xlen, "x", base)
     yp, yms, yst, _ky = _vec_info(y, dt, ylen, "y", base)
     if xms != yms:
@@ -843,8 +872,9 @@ def mul(y, A, x, alpha=True, beta=False):
     strong = beta is False
     a = _scalar_buf(1 if alpha is True else alpha, dt)
     b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
-    L.check(L.lib().bsm_mul(base._h.ptr, op, xp, yp, a.ctypes.data, b.ctypes.data,
-                            1 if strong else 0, xms, yst if yst is not None else None))
+    fn = L.lib().bsm_mul_cvec if cvec else L.lib().bsm_mul
+    L.check(fn(base._h.ptr, op, xp, yp, a.ctypes.data, b.ctypes.data, 1 if strong else 0, xms,
+               yst if yst is not None else None))
     return y
 
 
@@ -892,7 +922,7 @@ class MulPlan:
 
     def __init__(self, y, A, x, alpha=True, beta=False):
         base, op = _unwrap(A)
-        dt = base.dtype
+        dt, cvec = _vec_type(base, x, y, alpha, beta)
         nr, nc = base.size
         ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
         xp, xms, _, self._kx = _vec_info(x, dt, xlen, "x", base)
@@ -903,7 +933,7 @@ class MulPlan:
         self._a = _scalar_buf(1 if alpha is True else alpha, dt)
         self._b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
         self._base = base
-        self._fn = L.lib().bsm_mul
+        self._fn = L.lib().bsm_mul_cvec if cvec else L.lib().bsm_mul
         self._dev = y.device
         self._args = [base._h.ptr, C.c_int(op), C.c_void_p(xp), C.c_void_p(yp),
                       C.c_void_p(self._a.ctypes.data), C.c_void_p(self._b.ctypes.data),
@@ -962,7 +992,10 @@ def _apply(A, x):
         else:
             y = torch.empty(m, dtype=x.dtype, device=x.device)
     else:
-        x = np.asarray(x, dtype=eltype(A))
+        dt = eltype(A)
+        if np.iscomplexobj(x) and dt.kind != "c":  # complex vectors under a real matrix: a complex result
+            dt = np.result_type(dt, np.asarray(x).dtype)
+        x = np.asarray(x, dtype=dt)
         if x.ndim == 2:
             x = np.asfortranarray(x)
             y = np.empty((m, x.shape[1]), dtype=x.dtype, order="F")

@@ -340,6 +340,31 @@ int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t l
                   int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace,
                   void *stream);
 
+/* y = alpha * op(A) * x + beta * y for a REAL handle (BSM_F32 / BSM_F64) and COMPLEX vectors of the same precision
+ * (complex float / complex double): x, y, alpha, beta are complex; op C = op T on a real matrix.  A Float64 operator
+ * applied to ComplexF64 vectors (the Gram matrix, near fields of static kernels, real preconditioners in a BEM solve:
+ * the reference's generic loops, src/abstractblockmatrix.jl:27-34) in ONE pass over the matrix: each stored real
+ * value meets the complex x entry in two FMAs, nothing is widened to complex.  Every semantic of bsm_mul carries over
+ * (strong zero, own rows, memspaces, graph capture, accumulate modes, transpose_image, the bitwise reproducible
+ * gather path of BSM_ACC_GATHER handles).  Memory: host vectors are staged through buffers of twice the real
+ * handle's vector bytes; a BSM_ACC_GATHER image gets a second, complex workspace of (workspace slots + 8) x 2 x
+ * sizeof(real) bytes, allocated at the first complex product that takes the gather path (never under graph capture:
+ * until it exists, a captured product takes the atomic path, as a busy workspace does).
+ * Refused before anything is enqueued: a complex handle (BSM_ERR_INVALID: bsm_mul takes its vectors), a mixed-storage
+ * handle (BSM_F64_F32, BSM_C128_C64) or a multi-device handle (bsm_options.ctx): BSM_ERR_UNSUPPORTED; bad op / memspace
+ * or null pointers: BSM_ERR_INVALID; an analysis-only handle: BSM_ERR_DEVICE. */
+int bsm_mul_cvec(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha, const void *beta,
+                 int beta_strong_zero, int memspace, void *stream);
+/* bsm_mul_multi with complex vectors under a real handle (refusals and memory as bsm_mul_cvec).  Batches of 8 complex
+ * columns are ONE pass of the real multi-RHS kernels over their 16 real components (Re / Im interleaved; a last batch
+ * of at most 4 columns over 8): alpha is applied as X is interleaved, beta as Y is written back.  These passes use the
+ * handle's interleaved work arrays (128 bytes per vector entry each, allocated at the first product that takes them);
+ * when a product does not get them (another product in flight on them, graph capture) or the image is coloured
+ * (BSM_ACC_COLORED: bitwise reproducible read-modify-write), it runs as nrhs one-column products.  nrhs = 1 is
+ * bsm_mul_cvec. */
+int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                       const void *alpha, const void *beta, int beta_strong_zero, int memspace, void *stream);
+
 /* Replaces the VALUES of blocks of an existing handle -- what a Julia caller gets by editing block(A, i) in place
  * (the reference keeps the caller's matrices by reference, src/vbcrs.jl:98,114, src/blockmatrix.jl:26-34).
  * Structure, index lists, shapes, options and the layout of the device image stay as created: no analysis runs.

@@ -213,6 +213,48 @@ function LinearMaps._unsafe_mul!(y::AbstractVector, A::ROCmOp{Z}, x::AbstractVec
     return _fallback_mul!(y, A, x, α, β)
 end
 
+# Complex vectors under a real operator (bsm_mul_cvec / bsm_mul_multi_cvec): a Float64 operator times ComplexF64 vectors,
+# Float32 times ComplexF32, in ONE pass over the matrix.  Pure single-device handles only: mixed storage and multi-GPU
+# handles keep the Re / Im split of _fallback_mul!.
+_cvec_ok(A, ::Type{C}) where {C} = (R = eltype(_base(A)); R <: Union{Float32,Float64} && C === Complex{R} &&
+    _base(A).scheduler.storage === nothing && isempty(_base(A).scheduler.devices))
+
+function _mul_cvec!(y, A, x, α::C, β::C, strong::Bool, memspace::Integer, stream::Ptr{Cvoid}) where {C<:Complex}
+    h = handle(_base(A))
+    a = Ref(α); b = Ref(β)
+    GC.@preserve x y _check(ccall((:bsm_mul_cvec, libbsm), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ref{C}, Ref{C}, Cint, Cint, Ptr{Cvoid}),
+        h.ptr, _op(A), pointer(x), pointer(y), a, b, strong, memspace, stream))
+    return y
+end
+
+function _mul_multi_cvec!(Y, A, X, α::C, β::C, strong::Bool, memspace::Integer, stream::Ptr{Cvoid}) where {C<:Complex}
+    h = handle(_base(A))
+    a = Ref(α); b = Ref(β)
+    GC.@preserve X Y _check(ccall((:bsm_mul_multi_cvec, libbsm), Cint,
+        (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{C}, Ref{C}, Cint, Cint, Ptr{Cvoid}),
+        h.ptr, _op(A), size(X, 2), pointer(X), max(stride(X, 2), 1), pointer(Y), max(stride(Y, 2), 1), a, b, strong,
+        memspace, stream))
+    return Y
+end
+
+function LinearMaps._unsafe_mul!(y::Vector{C}, A::ROCmOp{Z}, x::Vector{C}, α::Number, β::Number) where
+        {R<:Union{Float32,Float64},C<:Complex{R},Z<:ROCmMat}
+    if eltype(_base(A)) === C && _fits(C, α) && _fits(C, β)  # a complex operator: bsm_mul
+        return _mul!(y, A, x, C(α), C(β === false ? 0 : β), β === false, 0, C_NULL, C)
+    end
+    _cvec_ok(A, C) || return _fallback_mul!(y, A, x, α, β)
+    return _mul_cvec!(y, A, x, C(α), C(β === false ? 0 : β), β === false, 0, C_NULL)
+end
+
+function LinearMaps._unsafe_mul!(Y::Matrix{C}, A::ROCmOp{Z}, X::Matrix{C}, α::Number, β::Number) where
+        {R<:Union{Float32,Float64},C<:Complex{R},Z<:ROCmMat}
+    if !(eltype(_base(A)) === C) && _cvec_ok(A, C)
+        return _mul_multi_cvec!(Y, A, X, C(α), C(β === false ? 0 : β), β === false, 0, C_NULL)
+    end
+    return _mul_multi!(Y, A, X, α, β)
+end
+
 function _fallback_mul!(y, A, x, α, β)
     T = eltype(_base(A))
     # (one result temporary per product; `convert` copies x only when it is not already a Vector{T})
@@ -228,8 +270,10 @@ end
 
 # `A * X` / mul!(Y, A, X, α, β) with matrices: LinearMaps would loop the columns through the vector
 # method (one sweep of A per column); bsm_mul_multi streams A once per 8 columns.
-function LinearMaps._unsafe_mul!(Y::Matrix{T}, A::ROCmOp{Z}, X::Matrix{T}, α::Number, β::Number) where
-        {T<:ROCmEltype,Z<:ROCmMat}
+LinearMaps._unsafe_mul!(Y::Matrix{T}, A::ROCmOp{Z}, X::Matrix{T}, α::Number, β::Number) where
+    {T<:Union{Float32,Float64},Z<:ROCmMat} = _mul_multi!(Y, A, X, α, β)
+
+function _mul_multi!(Y::Matrix{T}, A, X::Matrix{T}, α::Number, β::Number) where {T}
     if !(eltype(_base(A)) === T && _fits(T, α) && _fits(T, β))
         for k in axes(X, 2)
             _fallback_mul!(view(Y, :, k), A, view(X, :, k), α, β)
@@ -321,10 +365,21 @@ if Base.find_package("AMDGPU") !== nothing
         _updstream(::AMDGPU.ROCMatrix) = Base.unsafe_convert(Ptr{Cvoid}, AMDGPU.stream().stream)
         function LinearMaps._unsafe_mul!(y::AMDGPU.ROCVector{T}, A::ROCmOp{Z}, x::AMDGPU.ROCVector{T},
                 α::Number, β::Number) where {T<:ROCmEltype,Z<:ROCmMat}
-            (eltype(_base(A)) === T && _fits(T, α) && _fits(T, β)) ||
-                throw(ArgumentError("device vectors must have the matrix' element type; α, β convertible to it"))
             st = Base.unsafe_convert(Ptr{Cvoid}, AMDGPU.stream().stream)
+            if T <: Complex && eltype(_base(A)) !== T && _cvec_ok(A, T)  # complex vectors under a real operator
+                return _mul_cvec!(y, A, x, T(α), T(β === false ? 0 : β), β === false, 1, st)
+            end
+            (eltype(_base(A)) === T && _fits(T, α) && _fits(T, β)) ||
+                throw(ArgumentError("device vectors must have the matrix' element type (or, for a real matrix, its " *
+                                    "complex type); α, β convertible to it"))
             return _mul!(y, A, x, T(α), T(β === false ? 0 : β), β === false, 1, st, T)
+        end
+        function LinearMaps._unsafe_mul!(Y::AMDGPU.ROCMatrix{T}, A::ROCmOp{Z}, X::AMDGPU.ROCMatrix{T},
+                α::Number, β::Number) where {T<:Union{ComplexF32,ComplexF64},Z<:ROCmMat}
+            (eltype(_base(A)) !== T && _cvec_ok(A, T)) ||
+                throw(ArgumentError("ROCMatrix right-hand sides: complex vectors under a real operator of their precision"))
+            st = Base.unsafe_convert(Ptr{Cvoid}, AMDGPU.stream().stream)
+            return _mul_multi_cvec!(Y, A, X, T(α), T(β === false ? 0 : β), β === false, 1, st)
         end
 
         """
