@@ -1505,10 +1505,9 @@ static bool wsc_reserve(const Analysis &an, DeviceImage &img, hipStream_t st) {
     return true;
 }
 
-// bsm_mul (K = 1, ld = max(length, 1)) and bsm_mul_multi after their argument checks; cvec: bsm_mul_cvec /
-// bsm_mul_multi_cvec (complex vectors under a real single-device handle: every size below in the complex type)
+// the product after its argument checks (one column: K = 1, ld = max(length, 1)); vt: the dtype code of the vectors
 static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long ldx, void *Y, long long ldy,
-                 const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t st, bool cvec = false) {
+                 const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t st, int vt) {
     if (A->dist)  // multi-device handles: every device streams its part once per batch of <= 8 columns
         return dist_mul_multi(A, op, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, st);
     // transposed products run forward on the second ordering when the handle has one
@@ -1520,8 +1519,9 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     hipError_t e = guard.enter(img.device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     // one column: the gather workspace (if the image has one); more: the interleaved pass's work arrays (if it applies)
-    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : il_applies(img, opT, K, cvec), st);
-    if (claim.held && K == 1 && cvec && !wsc_reserve(use_t ? A->an_t : A->an, img, st))
+    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : il_applies(img, opT, K, vt), st);
+    // (complex vectors under a real image gather into the complex workspace)
+    if (claim.held && K == 1 && vt != img.dtype && img.dtype <= BSM_F64 && !wsc_reserve(use_t ? A->an_t : A->an, img, st))
         claim.held = false;  // no memory for the complex workspace: the atomic path needs none
     ILWork *il = nullptr;
     if (claim.held && K > 1) {  // allocated (and grown) here, at the first product that uses them
@@ -1534,14 +1534,14 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     }
     const bool gather = K == 1 && claim.held;
     if (memspace == BSM_MEM_DEVICE) {
-        e = launch_mul(img, opT, conj, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, st, gather, nullptr, il, cvec);
+        e = launch_mul(img, opT, conj, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, st, gather, nullptr, il, vt);
         if (e != hipSuccess) return hip_fail(e, "kernel launch");
         claim.mark();
         return BSM_OK;
     }
     if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "bad memspace");
     // host vectors: stage through device buffers (PCIe), synchronous
-    const size_t es = (size_t)A->an.vs * (cvec ? 2 : 1);  // (complex vectors: twice the handle's vector size)
+    const size_t es = vt == BSM_F32 ? 4 : vt == BSM_C128 ? 16 : 8;
     const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
     const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
     Staging sg;
@@ -1560,7 +1560,7 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     // by the runtime: 74 vs 118 us per C2-sized product)
     if (e == hipSuccess) e = copy(dx, xlen, X, ldx, xlen, hipMemcpyHostToDevice);
     if (e == hipSuccess && y_in) e = copy(dy, ylen, Y, ldy, ylen, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_mul(img, opT, conj, K, dx, xlen, dy, ylen, alpha, beta, beta_strong_zero, st, gather, nullptr, il, cvec);
+    if (e == hipSuccess) e = launch_mul(img, opT, conj, K, dx, xlen, dy, ylen, alpha, beta, beta_strong_zero, st, gather, nullptr, il, vt);
     claim.mark();
     if (e == hipSuccess) e = copy(Y, ldy, dy, ylen, ylen, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1568,16 +1568,57 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     return BSM_OK;
 }
 
-extern "C" int bsm_mul(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha,
-                       const void *beta, int beta_strong_zero, int memspace, void *stream) {
+// The four product entry points: bsm_mul / bsm_mul_multi (multi: X and Y hold nrhs columns at ldx / ldy; else one
+// packed column) and their _cvec forms (cplx: complex vectors under a real handle).  What a handle refuses complex
+// vectors for is answered before anything that needs a device, so that analysis-only handles reach every answer.
+static int mul_entry(bsm_matrix_s *A, int op, bool cplx, bool multi, int64_t nrhs, const void *X, int64_t ldx, void *Y,
+                     int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace, void *stream) {
     if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    const int dt = A->an.dtype;
+    if (cplx && (dt == BSM_C64 || dt == BSM_C128))
+        return fail(BSM_ERR_INVALID, "complex handle: bsm_mul / bsm_mul_multi take its complex vectors");
+    if (cplx && dt != BSM_F32 && dt != BSM_F64)
+        return fail(BSM_ERR_UNSUPPORTED, "complex vectors under a mixed-storage handle are not supported");
+    if (cplx && A->dist) return fail(BSM_ERR_UNSUPPORTED, "complex vectors under a multi-device handle are not supported");
     if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
-    if (!x || !y) return fail(BSM_ERR_INVALID, "null vector");
+    if (cplx && memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
+    if (nrhs < 0) return fail(BSM_ERR_INVALID, "negative nrhs");
+    if (nrhs == 0) return BSM_OK;
+    if (!X || !Y) return fail(BSM_ERR_INVALID, multi ? "null matrix" : "null vector");
     if (!A->on_device)
         return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
-    const long long xlen = std::max<long long>(op == 0 ? A->an.ncols : A->an.nrows, 1);
-    const long long ylen = std::max<long long>(op == 0 ? A->an.nrows : A->an.ncols, 1);
-    return mul_k(A, op, 1, x, xlen, y, ylen, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
+    // (the whole operator's size: a multi-device handle has no image of its own)
+    const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
+    const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
+    if (!multi) ldx = std::max<long long>(xlen, 1), ldy = std::max<long long>(ylen, 1);
+    if (ldx < std::max<long long>(xlen, 1) || ldy < std::max<long long>(ylen, 1))
+        return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
+    // the vector type: the complex one of the handle's precision, or the handle's own (double / complex double under the
+    // mixed storage codes)
+    static const int kVecType[6] = {BSM_F32, BSM_F64, BSM_C64, BSM_C128, BSM_F64, BSM_C128};
+    const int vt = cplx ? (dt == BSM_F32 ? BSM_C64 : BSM_C128) : kVecType[dt];
+    return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream, vt);
+}
+
+extern "C" int bsm_mul(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha,
+                       const void *beta, int beta_strong_zero, int memspace, void *stream) {
+    return mul_entry(A, op, false, false, 1, x, 0, y, 0, alpha, beta, beta_strong_zero, memspace, stream);
+}
+
+extern "C" int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y,
+                             int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero,
+                             int memspace, void *stream) {
+    return mul_entry(A, op, false, true, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, stream);
+}
+
+extern "C" int bsm_mul_cvec(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha, const void *beta,
+                            int beta_strong_zero, int memspace, void *stream) {
+    return mul_entry(A, op, true, false, 1, x, 0, y, 0, alpha, beta, beta_strong_zero, memspace, stream);
+}
+
+extern "C" int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y, int64_t ldy,
+                                  const void *alpha, const void *beta, int beta_strong_zero, int memspace, void *stream) {
+    return mul_entry(A, op, true, true, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, stream);
 }
 
 extern "C" int bsm_mul_parts(bsm_matrix_t A, int op, const void *const *x_parts, void *const *y_parts,
@@ -1587,65 +1628,6 @@ extern "C" int bsm_mul_parts(bsm_matrix_t A, int op, const void *const *x_parts,
     if (!x_parts || !y_parts) return fail(BSM_ERR_INVALID, "null vector parts");
     if (!A->dist) return fail(BSM_ERR_INVALID, "bsm_mul_parts needs a multi-device handle (bsm_options.ctx)");
     return dist_mul_parts(A, op, x_parts, y_parts, alpha, beta, beta_strong_zero, streams);
-}
-
-extern "C" int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y,
-                             int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero,
-                             int memspace, void *stream) {
-    if (!A) return fail(BSM_ERR_INVALID, "null handle");
-    if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
-    if (nrhs < 0) return fail(BSM_ERR_INVALID, "negative nrhs");
-    if (nrhs == 0) return BSM_OK;
-    if (!X || !Y) return fail(BSM_ERR_INVALID, "null matrix");
-    if (!A->on_device)
-        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
-    // (the whole operator's size: a multi-device handle has no image of its own)
-    const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
-    const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
-    if (ldx < std::max<long long>(xlen, 1) || ldy < std::max<long long>(ylen, 1))
-        return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
-    return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
-}
-
-// bsm_mul_cvec / bsm_mul_multi_cvec: what a real handle refuses complex vectors for -- checked before anything else that
-// needs a device, so that analysis-only handles reach every answer
-static int cvec_refusal(bsm_matrix_s *A, int op, int memspace) {
-    if (!A) return fail(BSM_ERR_INVALID, "null handle");
-    const int dt = A->an.dtype;
-    if (dt == BSM_C64 || dt == BSM_C128)
-        return fail(BSM_ERR_INVALID, "complex handle: bsm_mul / bsm_mul_multi take its complex vectors");
-    if (dt != BSM_F32 && dt != BSM_F64)
-        return fail(BSM_ERR_UNSUPPORTED, "complex vectors under a mixed-storage handle are not supported");
-    if (A->dist) return fail(BSM_ERR_UNSUPPORTED, "complex vectors under a multi-device handle are not supported");
-    if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
-    if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-    return BSM_OK;
-}
-
-extern "C" int bsm_mul_cvec(bsm_matrix_t A, int op, const void *x, void *y, const void *alpha, const void *beta,
-                            int beta_strong_zero, int memspace, void *stream) {
-    if (const int r = cvec_refusal(A, op, memspace)) return r;
-    if (!x || !y) return fail(BSM_ERR_INVALID, "null vector");
-    if (!A->on_device)
-        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
-    const long long xlen = std::max<long long>(op == 0 ? A->an.ncols : A->an.nrows, 1);
-    const long long ylen = std::max<long long>(op == 0 ? A->an.nrows : A->an.ncols, 1);
-    return mul_k(A, op, 1, x, xlen, y, ylen, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream, true);
-}
-
-extern "C" int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y, int64_t ldy,
-                                  const void *alpha, const void *beta, int beta_strong_zero, int memspace, void *stream) {
-    if (const int r = cvec_refusal(A, op, memspace)) return r;
-    if (nrhs < 0) return fail(BSM_ERR_INVALID, "negative nrhs");
-    if (nrhs == 0) return BSM_OK;
-    if (!X || !Y) return fail(BSM_ERR_INVALID, "null matrix");
-    if (!A->on_device)
-        return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
-    const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
-    const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
-    if (ldx < std::max<long long>(xlen, 1) || ldy < std::max<long long>(ylen, 1))
-        return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
-    return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream, true);
 }
 
 extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *ids, const void *const *blocks,

@@ -77,9 +77,10 @@ struct Part {
     std::unique_ptr<UpdateInputs> upd_in;
 };
 
-// the part's work arrays if its image / this product take the interleaved pass (and they can be had), else null
+// the part's work arrays if its image / this product take the interleaved pass (and they can be had), else null.
+// (A part's image is never mixed storage: its dtype is the vector type of every product.)
 static ILWork *part_il(Part &pt, bool opT, int K) {
-    if (pt.il_failed || !il_applies(pt.img, opT, K)) return nullptr;
+    if (pt.il_failed || !il_applies(pt.img, opT, K, pt.img.dtype)) return nullptr;
     pt.il_failed = !il_reserve(pt.il, std::max(pt.img.nrows, pt.img.ncols));
     return pt.il_failed ? nullptr : &pt.il;
 }
@@ -856,7 +857,8 @@ static int dist_mul_fused(DistState &D, int op, int K, const std::vector<VecSour
                 if (!direct[p]) pt.w_clean = false;  // (until the whole product has been issued)
                 const void *b = direct[p] ? beta : (rezero ? one : nullptr);
                 const int sz = direct[p] ? beta_strong_zero : (rezero ? 0 : 1);
-                DCHECK(launch_mul(pt.img, opT, conj, K, xp, xld, target, tld, alpha, b, sz, st, false, z, part_il(pt, opT, K)),
+                DCHECK(launch_mul(pt.img, opT, conj, K, xp, xld, target, tld, alpha, b, sz, st, false, z, part_il(pt, opT, K),
+                                  pt.img.dtype),
                        "kernel launch");
             } else if (rezero) {
                 if (!pt.w_clean) DCHECK(hipMemsetAsync(pt.d_w, 0, (size_t)D.kcap * vlen * es, st), "memset");
@@ -1002,7 +1004,7 @@ static int dist_mul_copies(DistState &D, int op, int K, const void *x, long long
                 }
                 const long long z[2] = {zr.lo, zr.hi};
                 DCHECK(launch_mul(pt.img, opT, conj, K, xp, xld, pt.d_w, (long long)vlen, alpha, nullptr, 1, pt.stream,
-                                  pt.img.d_ws != nullptr, z, part_il(pt, opT, K)), "kernel launch");
+                                  pt.img.d_ws != nullptr, z, part_il(pt, opT, K), pt.img.dtype), "kernel launch");
             } else if (!zr.empty()) {
                 for (int k = 0; k < K; k++)
                     DCHECK(hipMemsetAsync((char *)pt.d_w + ((size_t)k * vlen + zr.lo) * es, 0, (size_t)zr.len() * es, pt.stream),

@@ -67,10 +67,9 @@ struct ILWork {
     long long rows = 0;   // capacity of both, in vector entries
     bool w_clean = false; // w is known to be zero
 };
-// whether launch_mul would take the interleaved pass for this image / op / batch (so that the caller only claims -- and
-// allocates -- the work arrays when they will be used)
-// cvec: complex vectors under a real image (bsm_mul_multi_cvec)
-bool il_applies(const DeviceImage &img, bool opT, long long nrhs, bool cvec = false);
+// whether launch_mul would take the interleaved pass for this image / op / batch / vector dtype vt (so that the caller
+// only claims -- and allocates -- the work arrays when they will be used)
+bool il_applies(const DeviceImage &img, bool opT, long long nrhs, int vt);
 
 // Enqueues Y = alpha*op(A)*X + beta*Y on `stream` for K right-hand sides, X (ldx) and Y (ldy) column-major device
 // pointers.  No allocation, no synchronisation (graph-capturable).
@@ -79,11 +78,13 @@ bool il_applies(const DeviceImage &img, bool opT, long long nrhs, bool cvec = fa
 // K > 1: A is streamed once per batch of <= 16 columns; il: the work arrays of the interleaved pass (null: not claimed).
 // zrange = {lo, hi} (0-based, exclusive): the y entries the `y .*= beta` pass of the accumulate path covers instead of
 // the image's own range (multi-device fan-out; ignored by exclusive forward images, whose coverage is part of the image)
-// cvec: x, y, alpha, beta are complex of the precision of a REAL image (BSM_F32 / BSM_F64: bsm_mul_cvec); use_gather then
-// takes img.d_wsc, and il batches of 8 complex columns run the real interleaved pass over their 16 components
+// vt: the dtype code (BSM_F32 .. BSM_C128) of x, y, alpha, beta.  With the image's dtype it names the pair the product
+// runs on: the image's own type (BSM_F64 / BSM_C128 for the mixed storage codes), or the complex type of a REAL image's
+// precision (bsm_mul_cvec: use_gather then takes img.d_wsc, and il batches of 8 complex columns run the real interleaved
+// pass over their 16 components).  Any other pair: hipErrorInvalidValue.
 hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, const void *x, long long ldx, void *y,
                       long long ldy, const void *alpha, const void *beta, int strong_zero, hipStream_t stream,
-                      bool use_gather, const long long *zrange, ILWork *il, bool cvec = false);
+                      bool use_gather, const long long *zrange, ILWork *il, int vt);
 
 // rowcolvals(A): COO triples (1-based int64 rows / cols, values of the image's vector type) written from
 // the packed device image; d_out_off[w] = first output slot of wave descriptor w (host prefix sum of

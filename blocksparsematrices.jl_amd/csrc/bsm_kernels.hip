@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "../../include/bsm_rocm.h"
 #include "bsm_analysis.h"
 #include "bsm_kernels.h"
 #include "bsm_layout.h"
@@ -656,7 +657,7 @@ template <typename T, bool FWD, bool TRN> constexpr int kMixedWaves = (FWD && TR
 //     exactly 8 workgroups fit a CU (+11-13 % on 3-28-row fp64 panels over 6 waves).
 //   complex128: capped at 80 (the fused instance compiles to 71: 7 waves).
 //   fp32 / complex64: capped at 96 = 5 waves (fp32 fused compiles to 80: 6), no scratch anywhere.
-//   mixed precision (S = float / c64 stored under double / complex128 vectors, L = 4: launch_one_mixed): capped at 80
+//   mixed precision (S = float / c64 stored under double / complex128 vectors, L = 4: launch_one): capped at 80
 //     = 6 waves, the fp64 fused instance at 72 = 7 (a cap of 64 left 8 B of scratch; complex128 needs 72 + 8 B under
 //     72).  No scratch anywhere.
 template <typename T, int L, bool FWD, bool TRN, bool NT, typename S = T>
@@ -2383,8 +2384,8 @@ template <typename F> static void with_halves(bool opT, bool has_off, F &&f) {
         f(std::false_type{}, std::true_type{});
 }
 
-// one right-hand side (S: the stored type of the image, = T unless it is a mixed-precision one)
-template <typename T, int L, typename S = T>
+// one right-hand side (S: the stored type of the image)
+template <typename T, int L, typename S>
 static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
                                int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
     int flags = base_flags(opT, conj, strong_zero);
@@ -2393,22 +2394,16 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
     const int *cols = (const int *)img.d_cols;
     const bool nt = stream_policy(img);
     T *ws = nullptr;  // gather mode: the workspace
-    bool unreached = false;
     // one launch of panel_kernel<T, L, FWD, TRN, NT, S> with NT taken from the run-time policy `nt`
     auto panel = [&](auto fwd, auto trn, const WaveWork *waves, dim3 grid, unsigned wg_base) {
         constexpr bool FWD = decltype(fwd)::value, TRN = decltype(trn)::value;
-        // mixed precision and complex vectors: only what launch_one_mixed / launch_one_cvec reach is instantiated (L = 4)
-        if constexpr (!std::is_same<S, T>::value && L != 4) {
-            unreached = true;
-        } else {
-            const dim3 block(64 * kWavesPerWg);
-            if (nt)
-                hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, true, S>), grid, block, 0, stream, waves, values, rows, cols, xd,
-                                   yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
-            else
-                hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, false, S>), grid, block, 0, stream, waves, values, rows, cols, xd,
-                                   yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
-        }
+        const dim3 block(64 * kWavesPerWg);
+        if (nt)
+            hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, true, S>), grid, block, 0, stream, waves, values, rows, cols, xd,
+                               yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
+        else
+            hipLaunchKernelGGL((panel_kernel<T, L, FWD, TRN, false, S>), grid, block, 0, stream, waves, values, rows, cols, xd,
+                               yd, alpha, beta, flags, wg_base, ws, img.ws_fbase);
     };
     if (!opT && img.exclusive_fwd) {
         // one launch: every y row has exactly one producer; beta is fused into its store and
@@ -2416,7 +2411,7 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
         flags |= FLAG_DIRECT;
         if (img.nwg_total > 0)
             panel(std::true_type{}, std::false_type{}, (const WaveWork *)img.d_waves, dim3((unsigned)img.nwg_total), 0u);
-        return unreached ? hipErrorNotSupported : hipGetLastError();
+        return hipGetLastError();
     }
     // accumulate mode: y .*= beta over the owned range, then hardware atomics (gather mode: the sums go to the
     // workspace, and a second launch adds them up in a fixed order)
@@ -2443,43 +2438,31 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
                            (const long long *)img.d_inv_ptr[k], (const int *)img.d_inv_idx[k], (const T *)ws,
                            alpha, beta, strong_zero);
     }
-    if (unreached) return hipErrorNotSupported;
     return hipGetLastError();
 }
 
-// loads per lane in flight of the one-column kernels: L = 4 where it was measured faster, on products that are fused
-// (symmetric operators, accumulating), 8 everywhere else.  Every one-column launch takes it -- single products and the
-// single columns a multi-RHS batch ladder ends with.
-template <typename T>
+// loads per lane in flight of the one-column kernels.  Every one-column launch takes it -- single products and the
+// single columns a multi-RHS product ends with.
+//   S = T: L = 4 where it was measured faster, on products that are fused (symmetric operators, accumulating), 8
+//     everywhere else.  complex64: 61 VGPRs, 8 waves per SIMD; with 8 the fused instance needs 93-95 (5 waves): tiled
+//     BEM fixture 105.9 -> 95.1 us (profiles/r04_c64_l4.txt).  fp32, SHORT panels only: tiled BEM fixture 48.6 -> 46.5
+//     us; 16-256-row operators lose 3-5 % with it and keep 8 (profiles/r04_fused_loads_per_lane.txt)
+//   S != T: 4 in every direction.  Mixed storage (S = float / c64 stored, T = double / c128 vectors): a lane's 4 strips
+//     hold 16 fp64 / 8 complex128 values after widening -- what the fp64 / complex128 instances of L = 8 hold -- and the
+//     forward instance with 8 loads needed 96 VGPRs and still spilled (the widened x reads of 8 strips: 64 VGPRs), i.e.
+//     5 resident waves against 6-8 with 4.  Complex vectors under a real image (T = c128 / c64, S = double / float): a
+//     lane's 4 strips meet 8 complex128 / 16 complex64 x entries.
+template <typename T, typename S>
 static hipError_t launch_one(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
                              int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
-    // complex64: 61 VGPRs, 8 waves per SIMD; with 8 the fused instance needs 93-95 (5 waves): tiled BEM fixture
-    // 105.9 -> 95.1 us (profiles/r04_c64_l4.txt).  fp32, SHORT panels only: tiled BEM fixture 48.6 -> 46.5 us;
-    // 16-256-row operators lose 3-5 % with it and keep 8 (profiles/r04_fused_loads_per_lane.txt)
-    constexpr int LF = std::is_same<T, float>::value ? BSM_F32_L : std::is_same<T, double>::value ? BSM_F64_L
+    constexpr int LF = !std::is_same<S, T>::value ? 4
+                     : std::is_same<T, float>::value ? BSM_F32_L : std::is_same<T, double>::value ? BSM_F64_L
                      : std::is_same<T, c64>::value ? BSM_C64_L : BSM_C128_L;
-    const bool fused = img.has_off && !img.exclusive_fwd && (!std::is_same<T, float>::value || img.mean_rows < 32.f);
-    if (LF != 8 && fused) return launch_typed<T, LF>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
-    return launch_typed<T, 8>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
-}
-
-// Mixed-precision image (S = float / c64 stored, T = double / c128 vectors): 4 loads per lane in flight in every
-// direction.  A lane's 4 strips hold 16 fp64 / 8 complex128 values after widening -- what the fp64 / complex128 instances
-// of L = 8 hold -- and the forward instance with 8 loads needed 96 VGPRs and still spilled (the widened x reads of 8
-// strips: 64 VGPRs), i.e. 5 resident waves against 6-8 with 4.  Several right-hand sides: one of these per column (no
-// one-pass multi-RHS kernels for mixed storage).
-template <typename T, typename S>
-static hipError_t launch_one_mixed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
-                                   int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
-    return launch_typed<T, 4, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
-}
-
-// Complex vectors under a real image (T = c128 / c64, S = double / float: bsm_mul_cvec): 4 loads per lane in flight in
-// every direction, as the mixed-precision instances -- a lane's 4 strips meet 8 complex128 / 16 complex64 x entries
-template <typename T, typename S>
-static hipError_t launch_one_cvec(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
-                                  int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
-    return launch_typed<T, 4, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
+    if constexpr (std::is_same<S, T>::value && LF != 8) {
+        const bool fused = img.has_off && !img.exclusive_fwd && (!std::is_same<T, float>::value || img.mean_rows < 32.f);
+        if (!fused) return launch_typed<T, 8, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
+    }
+    return launch_typed<T, LF, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
 }
 
 // K right-hand sides per pass
@@ -2540,27 +2523,22 @@ static int il_real_min_cols() {
     }();
     return v;
 }
-bool il_applies(const DeviceImage &img, bool opT, long long nrhs, bool cvec) {
-    if (img.dtype > 3) return false;  // mixed-precision images: one-column products only
-    if (cvec) {
-        // complex vectors under a real image: the pass over 2 x nrhs real components streams the matrix once where the
-        // alternative is nrhs one-column products -- every image class takes it, exclusive forward ones included, but
-        // coloured images keep their bitwise reproducible read-modify-write (one-column products)
-        if (img.dtype > 1 || nrhs < 2 || il_mode() == 0 || !img.color_wg_ptr.empty()) return false;
-        return std::max(img.nrows, img.ncols) < (1ll << 30);
-    }
-    const bool cplx = img.dtype >= 2;
+bool il_applies(const DeviceImage &img, bool opT, long long nrhs, int vt) {
     if (nrhs < 2) return false;  // (one column: launch_mul's one-column kernels, whatever the thresholds say)
-    if (il_mode() == 0 || nrhs < (cplx ? mfma_min_cols() : il_real_min_cols())) return false;
-    if (!opT && img.exclusive_fwd) return false;   // plain stores with beta fused: nothing to gain
+    if (il_mode() == 0) return false;
     if (!img.color_wg_ptr.empty()) return false;   // coloured launches keep their bitwise reproducible read-modify-write
     if (std::max(img.nrows, img.ncols) >= (1ll << 30)) return false;  // (staged entries carry two role bits)
+    // complex vectors under a real image: the pass over 2 x nrhs real components streams the matrix once where the
+    // alternative is nrhs one-column products -- every image class takes it, exclusive forward ones included.  Mixed
+    // storage: one-column products only
+    if (vt != img.dtype) return (img.dtype == BSM_F32 && vt == BSM_C64) || (img.dtype == BSM_F64 && vt == BSM_C128);
+    if (nrhs < (vt >= BSM_C64 ? mfma_min_cols() : il_real_min_cols())) return false;
+    if (!opT && img.exclusive_fwd) return false;   // plain stores with beta fused: nothing to gain
     // automatic: short scattered panels, and tall panels where the product is FUSED (symmetric operators: both halves, the
     // transposed one all atomics -- C3 x 16 377 -> 305 us, x 8 264 -> 220, C5 slice x 16 1607 -> 1131; the C3 structure with
     // complex entries, tools/c3_complex.py: ComplexF64 x 8 175 -> 138 us, ComplexF32 76 -> 63).  Forward-only products of
     // tall panels keep their kernels: on the C4 slice (128 x 128 fp32 blocks of one GPU of eight, vectors of the full 2 M
     // entries) the pass's two vector sweeps cost more than it saves (x 8 363 -> 457 us, x 16 453 -> 562).
-    (void)cplx;
     return il_mode() == 2 || img.mean_rows < 32.f || img.has_off;
 }
 // KT: the element type of the image the pass runs on -- T, or the real type of T for complex vectors under a real image:
@@ -2572,7 +2550,6 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     using R = typename ILT<T>::R;
     static_assert(std::is_same<KT, T>::value || std::is_same<KT, R>::value, "the image holds T or its real type");
     constexpr int CS = ILT<T>::CPLX ? 2 * KK : KK;  // components per vector index (8 or 16)
-    if (!std::is_same<KT, T>::value) conj = false;  // (op C of a real image is op T)
     const long long xlen = opT ? img.nrows : img.ncols, ylen = opT ? img.ncols : img.nrows;
     if (xlen > il.rows || ylen > il.rows) return hipErrorInvalidValue;
     const int flags = base_flags(opT, conj, 0);  // (beta meets y in the finish pass)
@@ -2630,11 +2607,12 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     return e;
 }
 
+// The multi-RHS kernels of a same-type image over columns k .. nrhs - 1 (nrhs > 1), A streamed once per batch: advances
+// k past the columns they took; the rest are one-column products.
 template <typename T>
-static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj, long long nrhs, const T *xd, long long ldx,
-                                     T *yd, long long ldy, T alpha, T beta, int strong_zero, hipStream_t stream,
-                                     const long long *zrange, ILWork *il) {
-    long long k = 0;
+static hipError_t launch_ladder(const DeviceImage &img, bool opT, bool conj, long long nrhs, long long &k, const T *xd,
+                                long long ldx, T *yd, long long ldy, T alpha, T beta, int strong_zero, hipStream_t stream,
+                                const long long *zrange) {
     hipError_t e = hipSuccess;
     // batches of 8, then 4, then single columns: A is streamed once per batch.  The 8-column
     // kernels keep L = 4 loads per lane in flight instead of 8: with 8 accumulators and 8 x values
@@ -2649,27 +2627,6 @@ static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj
     // padded pass against an 8-column pass + a single product).  Short scattered panels (the BEM fixture: mean group
     // height below 32) gain nothing below 15 columns: their passes are bound by the x gather and the atomics, which
     // grow with the padded width (fp64 x 16: 615 us against 2 x 320).  BSM_MFMA_REAL_MIN_COLS overrides (17: off).
-    // short scattered panels: the interleaved pass (above) -- complex types in batches of 8 columns, real types of 16,
-    // then one padded remainder
-    if (il && il_applies(img, opT, nrhs, false)) {
-        constexpr int KK = ILT<T>::KK;
-        const int least = ILT<T>::CPLX ? mfma_min_cols() : il_real_min_cols();
-        while (e == hipSuccess && nrhs - k >= least) {
-            const int kact = (int)std::min<long long>(KK, nrhs - k);
-            if constexpr (!ILT<T>::CPLX) {
-                if (kact <= 8)  // real types, at most 8 columns left: 8 components per index (64-byte lines)
-                    e = launch_il<T, 8>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-                else
-                    e = launch_il<T, 16>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-            } else {
-                if (kact <= 4)  // complex types, at most 4 columns left: 8 components per index likewise
-                    e = launch_il<T, 4>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-                else
-                    e = launch_il<T, 8>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-            }
-            k += kact;
-        }
-    }
     if constexpr (kMfmaReal<T, 16>) {
         static const int mr_env = [] {
             const char *v = std::getenv("BSM_MFMA_REAL_MIN_COLS");
@@ -2716,78 +2673,73 @@ static hipError_t launch_multi_typed(const DeviceImage &img, bool opT, bool conj
                                             strong_zero, stream, zrange, rem);
         k += rem;
     }
-    for (; e == hipSuccess && k < nrhs; ++k)
-        e = launch_one<T>(img, opT, conj, xd + k * ldx, yd + k * ldy, alpha, beta, strong_zero, stream, false, zrange);
     return e;
 }
 
-// complex vectors T under a real image of type S: one column -- or every column of a batch the interleaved pass's work
-// arrays are not claimed for -- on the one-column kernels; batches of 8 complex columns (a last one of at most 4: 8
-// components per index) through the real interleaved pass over their 16 (8) real components
+// The products of one (T, S) pair -- T: the type of x, y, alpha, beta; S: the type the image stores -- for K right-hand
+// sides, in this order:
+//   1. the interleaved pass over the image's own type S, where il_applies says so (and its work arrays are claimed);
+//   2. same-type images only: the multi-RHS kernels (launch_ladder);
+//   3. the columns left, one at a time on the one-column kernels (the gather workspace only when K = 1).
+// vt: the dtype code of T (il_applies).
 template <typename T, typename S>
-static hipError_t launch_cvec(const DeviceImage &img, bool opT, long long K, const T *xd, long long ldx, T *yd, long long ldy,
-                              T alpha, T beta, int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange,
-                              ILWork *il) {
-    hipError_t e = hipSuccess;
+static hipError_t launch_pair(const DeviceImage &img, bool opT, bool conj, long long K, const T *xd, long long ldx, T *yd,
+                              long long ldy, T alpha, T beta, int strong_zero, hipStream_t stream, bool use_gather,
+                              const long long *zrange, ILWork *il, int vt) {
+    if constexpr (kCvec<T, S>) conj = false;  // (op C of a real image is op T: `conj` has nothing to act on)
     long long k = 0;
-    if (il && il_applies(img, opT, K, true)) {
-        while (e == hipSuccess && K - k >= 2) {
-            const int kact = (int)std::min<long long>(8, K - k);
-            if (kact <= 4)
-                e = launch_il<T, 4, S>(img, opT, false, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-            else
-                e = launch_il<T, 8, S>(img, opT, false, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-            k += kact;
+    hipError_t e = hipSuccess;
+    // The interleaved pass: complex types in batches of 8 columns, real types of 16, then one padded remainder (at most
+    // half a batch left: 8 components per index, 64-byte lines).  Complex vectors under a real image: the 2 x 8 (2 x 4)
+    // real components of 8 (4) complex columns on the real pass, from 2 columns on.  (Mixed storage: no pass.)
+    if constexpr (std::is_same<S, T>::value || kCvec<T, S>) {
+        if (il && il_applies(img, opT, K, vt)) {
+            constexpr int KK = ILT<T>::KK;
+            const int least = kCvec<T, S> ? 2 : ILT<T>::CPLX ? mfma_min_cols() : il_real_min_cols();
+            while (e == hipSuccess && K - k >= least) {
+                const int kact = (int)std::min<long long>(KK, K - k);
+                if (kact <= KK / 2)
+                    e = launch_il<T, KK / 2, S>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
+                else
+                    e = launch_il<T, KK, S>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
+                k += kact;
+            }
         }
     }
+    // (mixed storage and complex vectors under a real image: no multi-RHS kernels; one column: none, whatever the
+    // thresholds say)
+    if constexpr (std::is_same<S, T>::value) {
+        if (e == hipSuccess && K > 1)
+            e = launch_ladder<T>(img, opT, conj, K, k, xd, ldx, yd, ldy, alpha, beta, strong_zero, stream, zrange);
+    }
     for (; e == hipSuccess && k < K; ++k)
-        e = launch_one_cvec<T, S>(img, opT, false, xd + k * ldx, yd + k * ldy, alpha, beta, strong_zero, stream, use_gather && K == 1,
-                                  zrange);
+        e = launch_one<T, S>(img, opT, conj, xd + k * ldx, yd + k * ldy, alpha, beta, strong_zero, stream, use_gather && K == 1,
+                             zrange);
     return e;
 }
+
+static constexpr int pair_code(int img_dtype, int vt) { return img_dtype * 4 + vt; }
 
 hipError_t launch_mul(const DeviceImage &img, bool opT, bool conj, long long K, const void *x, long long ldx, void *y,
                       long long ldy, const void *alpha_p, const void *beta_p, int strong_zero, hipStream_t stream,
-                      bool use_gather, const long long *zrange, ILWork *il, bool cvec) {
-    if (cvec) {  // (op C of a real image is op T: `conj` has nothing to act on)
-        auto run_cvec = [&](auto t, auto s) {
-            using T = decltype(t);
-            const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);
-            return launch_cvec<T, decltype(s)>(img, opT, K, (const T *)x, ldx, (T *)y, ldy, alpha, beta, strong_zero, stream,
-                                               use_gather, zrange, il);
-        };
-        switch (img.dtype) {
-            case 0: return run_cvec(c64{}, float{});
-            case 1: return run_cvec(c128{}, double{});
-        }
-        return hipErrorInvalidValue;
-    }
-    auto run = [&](auto t) {
+                      bool use_gather, const long long *zrange, ILWork *il, int vt) {
+    auto run = [&](auto t, auto s) {
         using T = decltype(t);
         const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);
-        const T *xd = (const T *)x;
-        T *yd = (T *)y;
-        if (K == 1) return launch_one<T>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
-        return launch_multi_typed<T>(img, opT, conj, K, xd, ldx, yd, ldy, alpha, beta, strong_zero, stream, zrange, il);
+        return launch_pair<T, decltype(s)>(img, opT, conj, K, (const T *)x, ldx, (T *)y, ldy, alpha, beta, strong_zero, stream,
+                                           use_gather, zrange, il, vt);
     };
-    // mixed precision: K one-column products, one after another on the stream (the gather workspace only for K = 1)
-    auto run_mixed = [&](auto t, auto s) {
-        using T = decltype(t);
-        using S = decltype(s);
-        const T alpha = load_scalar<T>(alpha_p, 1.0), beta = load_scalar<T>(beta_p, 0.0);
-        hipError_t e = hipSuccess;
-        for (long long k = 0; k < K && e == hipSuccess; ++k)
-            e = launch_one_mixed<T, S>(img, opT, conj, (const T *)x + k * ldx, (T *)y + k * ldy, alpha, beta, strong_zero,
-                                       stream, use_gather && K == 1, zrange);
-        return e;
-    };
-    switch (img.dtype) {
-        case 0: return run(float{});
-        case 1: return run(double{});
-        case 2: return run(c64{});
-        case 3: return run(c128{});
-        case 4: return run_mixed(double{}, float{});
-        case 5: return run_mixed(c128{}, c64{});
+    // (image dtype, vector dtype) -> <T, S>: the same-type pairs, mixed storage, complex vectors under a real image
+    if (vt < BSM_F32 || vt > BSM_C128) return hipErrorInvalidValue;
+    switch (pair_code(img.dtype, vt)) {
+        case pair_code(BSM_F32, BSM_F32): return run(float{}, float{});
+        case pair_code(BSM_F64, BSM_F64): return run(double{}, double{});
+        case pair_code(BSM_C64, BSM_C64): return run(c64{}, c64{});
+        case pair_code(BSM_C128, BSM_C128): return run(c128{}, c128{});
+        case pair_code(BSM_F64_F32, BSM_F64): return run(double{}, float{});
+        case pair_code(BSM_C128_C64, BSM_C128): return run(c128{}, c64{});
+        case pair_code(BSM_F32, BSM_C64): return run(c64{}, float{});
+        case pair_code(BSM_F64, BSM_C128): return run(c128{}, double{});
     }
     return hipErrorInvalidValue;
 }

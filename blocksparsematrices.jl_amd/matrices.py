@@ -101,6 +101,7 @@ _TORCH_DT = {}
 if torch is not None:
     _TORCH_DT = {torch.float32: np.dtype(np.float32), torch.float64: np.dtype(np.float64),
                  torch.complex64: np.dtype(np.complex64), torch.complex128: np.dtype(np.complex128)}
+_TORCH_OF = {d: t for t, d in _TORCH_DT.items()}  # numpy dtype -> torch dtype
 
 
 def _is_dev(blocks):
@@ -755,8 +756,7 @@ def _vec_info(v, dt, n, name, base=None):
     if torch is not None and isinstance(v, torch.Tensor):
         if v.dim() != 1 or v.numel() != n:
             raise ValueError(f"DimensionMismatch: {name} has length {tuple(v.shape)}, expected {n}")
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-               np.dtype(np.complex64): torch.complex64, np.dtype(np.complex128): torch.complex128}[dt]
+        tdt = _TORCH_OF[dt]
         if v.dtype != tdt or not v.is_contiguous():
             raise TypeError(f"{name} must be a contiguous {tdt} tensor")
         if v.is_cuda:
@@ -777,8 +777,7 @@ def _mat_info(v, dt, n, name, base=None):
     if torch is not None and isinstance(v, torch.Tensor) and v.is_cuda and base is not None:
         _check_device(v, base, name)
     if torch is not None and isinstance(v, torch.Tensor):
-        tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
-               np.dtype(np.complex64): torch.complex64, np.dtype(np.complex128): torch.complex128}[dt]
+        tdt = _TORCH_OF[dt]
         if v.dim() != 2 or v.shape[0] != n:
             raise ValueError(f"DimensionMismatch: {name} has shape {tuple(v.shape)}, expected ({n}, k)")
         if v.dtype != tdt or v.stride(0) != 1 or (v.shape[1] > 1 and v.stride(1) < max(n, 1)):
@@ -828,25 +827,42 @@ def _vec_type(base, x, y, alpha, beta):
     return ct, True
 
 
-def _mul_matrix(Y, A, X, alpha, beta):
-    """mul!(Y, A, X, alpha, beta) with matrices: one bsm_mul_multi call (A streamed once per batch
-    of up to 8 columns) instead of LinearMaps' column loop over _unsafe_mul!."""
-    base, op = _unwrap(A)
-    dt, cvec = _vec_type(base, X, Y, alpha, beta)
-    nr, nc = base.size
-    ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
-    xp, ldx, kx, xms, _, _kx = _mat_info(X, dt, xlen, "X", base)
-    yp, ldy, ky, yms, yst, _ky = _mat_info(Y, dt, ylen, "Y", base)
-    if kx != ky:
-        raise ValueError("DimensionMismatch: X and Y have different numbers of columns")
-    if xms != yms:
-        raise ValueError("X and Y must live in the same memory space")
+def _scalars(alpha, beta, dt):
+    """-> (alpha, beta as one-element arrays of dt, strong-zero flag): `beta is False` is Julia's strong zero"""
     strong = beta is False
     a = _scalar_buf(1 if alpha is True else alpha, dt)
     b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
-    fn = L.lib().bsm_mul_multi_cvec if cvec else L.lib().bsm_mul_multi
-    L.check(fn(base._h.ptr, op, kx, xp, ldx, yp, ldy, a.ctypes.data, b.ctypes.data, 1 if strong else 0, xms, yst))
-    return Y
+    return a, b, 1 if strong else 0
+
+
+def _mul_call(y, A, x, alpha, beta, multi=False, plan=False):
+    """The one route of mul and MulPlan: resolves the vector type, checks the operands and builds the scalars ->
+    (C function, its arguments but the stream, y's stream (None: host vectors), what must stay alive while they are
+    used).  multi: x and y are column-major matrices (bsm_mul_multi, A streamed once per batch of columns instead of
+    LinearMaps' column loop over _unsafe_mul!); plan: MulPlan, device-resident vectors only."""
+    base, op = _unwrap(A)
+    dt, cvec = _vec_type(base, x, y, alpha, beta)
+    nr, nc = base.size
+    ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
+    if multi:
+        xp, ldx, kx, xms, _, xkeep = _mat_info(x, dt, xlen, "X", base)
+        yp, ldy, ky, yms, yst, ykeep = _mat_info(y, dt, ylen, "Y", base)
+        if kx != ky:
+            raise ValueError("DimensionMismatch: X and Y have different numbers of columns")
+        if xms != yms:
+            raise ValueError("X and Y must live in the same memory space")
+        vecs = (kx, xp, ldx, yp, ldy)
+    else:
+        xp, xms, _, xkeep = _vec_info(x, dt, xlen, "x", base)
+        yp, yms, yst, ykeep = _vec_info(y, dt, ylen, "y", base)
+        if plan and (xms != L.BSM_MEM_DEVICE or yms != L.BSM_MEM_DEVICE):
+            raise ValueError("MulPlan needs device-resident x and y")
+        if xms != yms:
+            raise ValueError("x and y must live in the same memory space")
+        vecs = (xp, yp)
+    a, b, strong = _scalars(alpha, beta, dt)
+    fn = getattr(L.lib(), "bsm_mul" + "_multi" * multi + "_cvec" * cvec)
+    return fn, (base._h.ptr, op, *vecs, a.ctypes.data, b.ctypes.data, strong, xms), yst, (base, a, b, xkeep, ykeep)
 
 
 def mul(y, A, x, alpha=True, beta=False):
@@ -857,24 +873,12 @@ def mul(y, A, x, alpha=True, beta=False):
     `beta is False` (the 3-argument form, reference src/abstractblockmatrix.jl:27-34) is Julia's
     strong zero: y is overwritten, NaN/Inf in the incoming y do not propagate.  A numeric 0.0
     multiplies.  Dimension checks mirror LinearMaps' check_dim_mul (DimensionMismatch)."""
-    base, op = _unwrap(A)
+    base, _ = _unwrap(A)
     if not isinstance(base, AbstractBlockMatrix):
         raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
-    nr, nc = base.size
-    ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
-    if getattr(x, "ndim", 1) == 2 or getattr(y, "ndim", 1) == 2:
-        return _mul_matrix(y, A, x, alpha, beta)
-    dt, cvec = _vec_type(base, x, y, alpha, beta)
-    xp, xms, xst, _kx = _vec_info(x, dt, xlen, "x", base)
-    yp, yms, yst, _ky = _vec_info(y, dt, ylen, "y", base)
-    if xms != yms:
-        raise ValueError("x and y must live in the same memory space")
-    strong = beta is False
-    a = _scalar_buf(1 if alpha is True else alpha, dt)
-    b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
-    fn = L.lib().bsm_mul_cvec if cvec else L.lib().bsm_mul
-    L.check(fn(base._h.ptr, op, xp, yp, a.ctypes.data, b.ctypes.data, 1 if strong else 0, xms,
-               yst if yst is not None else None))
+    multi = getattr(x, "ndim", 1) == 2 or getattr(y, "ndim", 1) == 2
+    fn, args, st, _keep = _mul_call(y, A, x, alpha, beta, multi)
+    L.check(fn(*args, st))
     return y
 
 
@@ -908,10 +912,8 @@ def mul_parts(y_parts, A, x_parts, alpha=True, beta=False):
                 raise ValueError(f"{name}_parts[{p}] lives on cuda:{v.device.index}, part {p} on cuda:{info['device']}")
             arr[p] = v.data_ptr()
         st[p] = torch.cuda.current_stream(torch.device("cuda", info["device"])).cuda_stream
-    strong = beta is False
-    a = _scalar_buf(1 if alpha is True else alpha, dt)
-    b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
-    L.check(L.lib().bsm_mul_parts(base._h.ptr, op, xp, yp, a.ctypes.data, b.ctypes.data, 1 if strong else 0, st))
+    a, b, strong = _scalars(alpha, beta, dt)
+    L.check(L.lib().bsm_mul_parts(base._h.ptr, op, xp, yp, a.ctypes.data, b.ctypes.data, strong, st))
     return y_parts
 
 
@@ -921,23 +923,10 @@ class MulPlan:
     stream -- what a Julia caller gets from `ccall` directly.  Graph-capturable."""
 
     def __init__(self, y, A, x, alpha=True, beta=False):
-        base, op = _unwrap(A)
-        dt, cvec = _vec_type(base, x, y, alpha, beta)
-        nr, nc = base.size
-        ylen, xlen = (nr, nc) if op == L.BSM_OP_N else (nc, nr)
-        xp, xms, _, self._kx = _vec_info(x, dt, xlen, "x", base)
-        yp, yms, _, self._ky = _vec_info(y, dt, ylen, "y", base)
-        if xms != L.BSM_MEM_DEVICE or yms != L.BSM_MEM_DEVICE:
-            raise ValueError("MulPlan needs device-resident x and y")
-        strong = beta is False
-        self._a = _scalar_buf(1 if alpha is True else alpha, dt)
-        self._b = _scalar_buf(0 if strong else (1 if beta is True else beta), dt)
-        self._base = base
-        self._fn = L.lib().bsm_mul_cvec if cvec else L.lib().bsm_mul
+        self._fn, args, _, self._keep = _mul_call(y, A, x, alpha, beta, plan=True)
         self._dev = y.device
-        self._args = [base._h.ptr, C.c_int(op), C.c_void_p(xp), C.c_void_p(yp),
-                      C.c_void_p(self._a.ctypes.data), C.c_void_p(self._b.ctypes.data),
-                      C.c_int(1 if strong else 0), C.c_int(L.BSM_MEM_DEVICE)]
+        # (converted once, here: the call passes ready ctypes values)
+        self._args = [args[0]] + [t(v) for t, v in zip(self._fn.argtypes[1:], args[1:])]
 
     def __call__(self):
         rc = self._fn(*self._args, C.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream))
