@@ -58,7 +58,7 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_symmetric_create", "bsm_mul", "bsm_mul_multi", "bsm_mul_parts",
            "bsm_mul_cvec", "bsm_mul_multi_cvec", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
            "bsm_color", "bsm_destroy", "bsm_last_error", "bsm_version",
-           "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks"]
+           "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks", "bsm_value_passes"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -150,6 +150,9 @@ def lib():
     L.bsm_color.argtypes = [C.c_int64, _PP, _I64P, C.c_int, _I64P, _I64P]
     L.bsm_color.restype = C.c_int
     L.bsm_stats.argtypes = [C.c_void_p, C.POINTER(BsmStats)]
+    if hasattr(L, "bsm_value_passes") or "BSM_LIB" not in os.environ:
+        L.bsm_value_passes.argtypes = [C.c_void_p, _I64P]
+        L.bsm_value_passes.restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p
     L.bsm_version.restype = C.c_char_p

@@ -1621,6 +1621,14 @@ extern "C" int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const vo
     return mul_entry(A, op, true, true, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, stream);
 }
 
+extern "C" int bsm_value_passes(bsm_matrix_t A, int64_t *count) {
+    if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    if (!count) return fail(BSM_ERR_INVALID, "null count");
+    if (A->dist) return fail(BSM_ERR_UNSUPPORTED, "bsm_value_passes: single-device handles only");
+    *count = __atomic_load_n(&A->img.value_passes, __ATOMIC_RELAXED) + __atomic_load_n(&A->img_t.value_passes, __ATOMIC_RELAXED);
+    return BSM_OK;
+}
+
 extern "C" int bsm_mul_parts(bsm_matrix_t A, int op, const void *const *x_parts, void *const *y_parts,
                              const void *alpha, const void *beta, int beta_strong_zero, void *const *streams) {
     if (!A) return fail(BSM_ERR_INVALID, "null handle");

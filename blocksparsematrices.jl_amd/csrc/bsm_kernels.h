@@ -32,6 +32,8 @@ struct DeviceImage {
     void *d_wsc = nullptr;
     void *d_inv_ptr[2] = {nullptr, nullptr}, *d_inv_idx[2] = {nullptr, nullptr};
     long long ws_fbase = 0;
+    // bsm_value_passes: streams of d_values enqueued by products of this image (launch_mul counts; relaxed atomic adds)
+    mutable long long value_passes = 0;
 };
 
 // dst[0..n) += src[0..n);   y[0..n) = beta * y + r   (element type `dtype`, beta: pointer to one T)

@@ -1806,7 +1806,13 @@ __global__ void __launch_bounds__(64 * kWavesPerWg, ((kMfmaPath32<T, K> || (kMfm
 #ifndef BSM_IL_C128_WGS
 #define BSM_IL_C128_WGS 3
 #endif
+// mixed storage (ILMixed<S>: values stored as S = float / c64, arithmetic in double): the accumulators, x operands and
+// row operands of the Float64 / ComplexF64 instances beside half their tile registers -- compiled for the same number
+// of resident workgroups as those (docs/experiments_r09.md has the register table)
+template <typename S> struct ILMixed {};
 template <typename T, int MRMAX> constexpr int il_wgs() {
+    if constexpr (std::is_same<T, ILMixed<float>>::value) return il_wgs<double, MRMAX>();
+    if constexpr (std::is_same<T, ILMixed<c64>>::value) return il_wgs<c128, MRMAX>();
     constexpr bool f64 = std::is_same<T, double>::value;
     if (MRMAX > 2) return sizeof(T) == 4 ? 4 : (sizeof(T) == 16 || f64 ? 2 : 3);
     return sizeof(T) == 16 ? BSM_IL_C128_WGS : (f64 ? 4 : 5);
@@ -1860,11 +1866,19 @@ __device__ __forceinline__ void il_atomic_add(float *p, float v, bool ok) {
 // The four element types of the interleaved pass: 16 real COMPONENTS per vector index -- 8 complex right-hand sides
 // (component 2 k + Re / Im) or 16 real ones -- of type R, one N = 16 of v_mfma_{f64,f32}_16x16x4.  A 16-byte load holds E
 // columns of one row; a step (16 rows x 16 columns) is NLD = 4 / E loads per lane (lane = row ln, strip 4 j + lk).
+// S: the type the image stores, TL: the element type of the LDS tile of the transposed half.  ILMixed<float> /
+// ILMixed<c64> (mixed storage): the loads hold S, E = 4 / 2 columns per load; a value is widened to double (exact) where
+// it enters the f64 MFMA of the forward half and where it is stored into the tile (TL = double / c128: the conversion
+// then is off the LDS read -> MFMA chain of the transposed half; against a tile kept in S, C3 x 8 192 -> 185 us, tiled
+// BEM complex x 4 279 -> 270, x 16 +-0 / +1.4 %, docs/experiments_r09.md), and everything behind that -- accumulators,
+// Xr, W, the atomics, the accumulator-row map -- is the Float64 / ComplexF64 instance's.
 template <typename T> struct ILT;
-template <> struct ILT<c128> { using R = double; using V4 = v4f64; static constexpr bool CPLX = true; static constexpr int KK = 8; };
-template <> struct ILT<double> { using R = double; using V4 = v4f64; static constexpr bool CPLX = false; static constexpr int KK = 16; };
-template <> struct ILT<c64> { using R = float; using V4 = v4f32; static constexpr bool CPLX = true; static constexpr int KK = 8; };
-template <> struct ILT<float> { using R = float; using V4 = v4f32; static constexpr bool CPLX = false; static constexpr int KK = 16; };
+template <> struct ILT<c128> { using R = double; using V4 = v4f64; using S = c128; using TL = c128; static constexpr bool CPLX = true; static constexpr int KK = 8; };
+template <> struct ILT<double> { using R = double; using V4 = v4f64; using S = double; using TL = double; static constexpr bool CPLX = false; static constexpr int KK = 16; };
+template <> struct ILT<c64> { using R = float; using V4 = v4f32; using S = c64; using TL = c64; static constexpr bool CPLX = true; static constexpr int KK = 8; };
+template <> struct ILT<float> { using R = float; using V4 = v4f32; using S = float; using TL = float; static constexpr bool CPLX = false; static constexpr int KK = 16; };
+template <> struct ILT<ILMixed<c64>> { using R = double; using V4 = v4f64; using S = c64; using TL = c128; static constexpr bool CPLX = true; static constexpr int KK = 8; };
+template <> struct ILT<ILMixed<float>> { using R = double; using V4 = v4f64; using S = float; using TL = double; static constexpr bool CPLX = false; static constexpr int KK = 16; };
 __device__ __forceinline__ double il_re(const c128 &a) { return a.re; }
 __device__ __forceinline__ double il_im(const c128 &a) { return a.im; }
 __device__ __forceinline__ float il_re(const c64 &a) { return a.re; }
@@ -1884,12 +1898,15 @@ __device__ __forceinline__ float il_im(float) { return 0.f; }
 template <typename T, int NRB, bool FWD, bool TRN, int CS, bool DEEP>
 __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restrict__ values, const int *__restrict__ rows,
                                          const int *__restrict__ cols, const typename ILT<T>::R *__restrict__ xr,
-                                         typename ILT<T>::R *__restrict__ wacc, int flags, int lane, T *tile, int *cix) {
+                                         typename ILT<T>::R *__restrict__ wacc, int flags, int lane, typename ILT<T>::TL *tile,
+                                         int *cix) {
     using R = typename ILT<T>::R;
     using V4 = typename ILT<T>::V4;
+    using S = typename ILT<T>::S;  // the stored type (= T unless mixed storage)
+    using TL = typename ILT<T>::TL;
     constexpr bool CPLX = ILT<T>::CPLX;
     constexpr bool F64MAP = sizeof(R) == 8;  // accumulator rows: lk + 4 r (f64) / 4 lk + r (f32)
-    constexpr int E = TT<T>::E;
+    constexpr int E = TT<S>::E;
     constexpr int NLD = 4 / E;
     const bool opT = (flags & FLAG_OPT) != 0;
     const bool cjf = (flags & FLAG_CONJ) != 0;
@@ -1902,7 +1919,7 @@ __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restric
     const bool has_off = (kinds & kKindHasOff) != 0;
     const bool fwd_en = FWD && (!opT || has_off);
     const bool trn_en = TRN && (opT || has_off);
-    const Vec16<T> *__restrict__ vb = reinterpret_cast<const Vec16<T> *>(values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
+    const Vec16<S> *__restrict__ vb = reinterpret_cast<const Vec16<S> *>(values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
     const int s1w = wd.seg1_w, s1x = wd.seg1_x - wd.seg1_w;
     const int s2w = wd.seg2_w, s2x = pc.seg2_x - wd.seg2_w;
     // complex: the sign of X'' = i X (conj(B): -i X) on this lane: component 2 k takes -Im, component 2 k + 1 takes +Re
@@ -1915,10 +1932,10 @@ __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restric
     auto accrow = [&](int r) { return F64MAP ? lk + 4 * r : 4 * lk + r; };  // accumulator register r of this lane -> row of D
     // matrix operand of step (t0, rb): lane = (row rb * 16 + ln, strip t0 / E + 4 j + lk), indices clamped into the panel
     // (the last strip of a panel is zero-padded to E columns)
-    auto mat = [&](int t0, int rb, int j) -> Vec16<T> {
+    auto mat = [&](int t0, int rb, int j) -> Vec16<S> {
         const int sidx = min(t0 / E + 4 * j + lk, nstrips - 1);
         const int row = min(rb * 16 + ln, m - 1);
-        if (BSM_DBG(DBG_NO_MATRIX)) return Vec16<T>{};
+        if (BSM_DBG(DBG_NO_MATRIX)) return Vec16<S>{};
         return load_stream16(&vb[(uint32_t)(sidx * m + row)]);
     };
     // ---- first batch of requests: the column list of the first block, the row list, the first tile -- all need the
@@ -1946,7 +1963,7 @@ __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restric
         }
     }
     constexpr int NBUF = DEEP ? NRB : 1;
-    Vec16<T> nb[NBUF][NLD];
+    Vec16<S> nb[NBUF][NLD];
 #pragma unroll
     for (int rb = 0; rb < NBUF; ++rb)
 #pragma unroll
@@ -2042,7 +2059,7 @@ __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restric
             V4 dt = {0, 0, 0, 0};
 #pragma unroll
             for (int rb = 0; rb < NRB; ++rb) {
-                Vec16<T> b[NLD];
+                Vec16<S> b[NLD];
 #pragma unroll
                 for (int j = 0; j < NLD; ++j) b[j] = nb[DEEP ? rb : 0][j];
                 // the next step's tile: the next row block of these columns, or the first one of the next 16 columns
@@ -2064,7 +2081,12 @@ __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restric
 #pragma unroll
                     for (int j = 0; j < NLD; ++j)
 #pragma unroll
-                        for (int e = 0; e < E; ++e) tile[(E * (4 * j + lk) + e) * 17 + ln] = b[j].v[e];
+                        for (int e = 0; e < E; ++e) {
+                            if constexpr (std::is_same<TL, S>::value)
+                                tile[(E * (4 * j + lk) + e) * 17 + ln] = b[j].v[e];
+                            else
+                                tile[(E * (4 * j + lk) + e) * 17 + ln] = widen(TL{}, b[j].v[e]);
+                        }
                 }
                 if (DEEP) {  // this row block's tile of the next 16 columns, into the registers just consumed
                     if (rb == 0) {
@@ -2079,7 +2101,7 @@ __device__ __forceinline__ void il_panel(const WaveD &wd, const uint4 *__restric
                 if (TRN && !BSM_DBG(DBG_NO_TRN_HALF)) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const T u = tile[ln * 17 + 4 * q + lk];
+                        const TL u = tile[ln * 17 + 4 * q + lk];
                         const R r1 = rr[rb * 4 + q];
                         dt = mfma(il_re(u), r1, dt);
                         if (CPLX) dt = mfma(il_im(u), second(r1), dt);
@@ -2124,7 +2146,7 @@ __global__ void __launch_bounds__(64 * kWavesPerWg, (il_wgs<T, MRMAX>()))
                     int flags, unsigned wg_base, unsigned xcd_run) {
     constexpr int WPW = kWavesPerWg;
     constexpr bool DEEP = MRMAX > 2;  // tall panels: all row blocks of the next 16 columns in flight (il_panel)
-    __shared__ T tl[WPW][TRN ? 16 * 17 : 1];
+    __shared__ typename ILT<T>::TL tl[WPW][TRN ? 16 * 17 : 1];
     __shared__ int cixs[WPW][kIlCols];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -2345,6 +2367,10 @@ static int base_flags(bool opT, bool conj, int strong_zero) {
     return flags;
 }
 
+// bsm_value_passes: one stream of the image's values is about to be enqueued -- called by the three launchers that
+// issue one (launch_typed, launch_typed_multi, launch_il), once per product or batch whatever its colour launches
+static void count_value_pass(const DeviceImage &img) { __atomic_fetch_add(&img.value_passes, 1ll, __ATOMIC_RELAXED); }
+
 // [lo, hi): the y entries an accumulating product scales by beta -- the rows the image owns (all of them for op T / C),
 // or zrange when the caller (multi-device fan-out) knows which y entries this image must define
 struct YRange {
@@ -2388,6 +2414,7 @@ template <typename F> static void with_halves(bool opT, bool has_off, F &&f) {
 template <typename T, int L, typename S>
 static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
                                int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
+    count_value_pass(img);
     int flags = base_flags(opT, conj, strong_zero);
     const uint4 *values = (const uint4 *)img.d_values;
     const int *rows = (const int *)img.d_rows;
@@ -2470,6 +2497,7 @@ template <typename T, int L, int K>
 static hipError_t launch_typed_multi(const DeviceImage &img, bool opT, bool conj, const T *xd, long long ldx,
                                      T *yd, long long ldy, T alpha, T beta, int strong_zero,
                                      hipStream_t stream, const long long *zrange, int kact = K) {
+    count_value_pass(img);
     int flags = base_flags(opT, conj, strong_zero);
     if (kact < K) flags |= kact << FLAG_KACT_SHIFT;  // a padded batch: kact of the K slots carry columns
     const uint4 *values = (const uint4 *)img.d_values;
@@ -2523,15 +2551,37 @@ static int il_real_min_cols() {
     }();
     return v;
 }
+// fewest columns of a mixed-storage product that take the pass (a batch of 8 or more always does).  What the pass
+// replaces is nrhs one-column products, i.e. nrhs streams of the matrix, against ONE stream and two vector sweeps.
+// Pass / nrhs one-column products, us (docs/experiments_r09.md):
+//                          x 2          x 3          x 4          x 5
+//   C2 (forward VBCRS)     31.0 / 20.2  30.5 / 30.2  30.6 / 40.3  31.0 / 50.1
+//   1 GB forward VBCRS     265 / 213    270 / 319    274 / 426    282 / 532
+//   ... op T               259 / 241    263 / 362    268 / 483    279 / 603
+//   C3 (fused symmetric)   184 / 194    184 / 291    184 / 388    184 / 484
+//   tiled BEM, complex     265 / 286    267 / 429    270 / 572    353 / 715
+// Symmetric operators (both halves in every product) take the pass from two columns on; on the others two columns stay
+// two one-column products and three take the pass.  BSM_IL_MIXED_MIN_COLS (2 .. 8) overrides both.
+static int il_mixed_min_cols(const DeviceImage &img) {
+    static const int env = [] {
+        const char *e = std::getenv("BSM_IL_MIXED_MIN_COLS");
+        return e ? std::min(std::max(std::atoi(e), 2), 8) : 0;
+    }();
+    return env ? env : (img.has_off ? 2 : 3);
+}
 bool il_applies(const DeviceImage &img, bool opT, long long nrhs, int vt) {
     if (nrhs < 2) return false;  // (one column: launch_mul's one-column kernels, whatever the thresholds say)
     if (il_mode() == 0) return false;
     if (!img.color_wg_ptr.empty()) return false;   // coloured launches keep their bitwise reproducible read-modify-write
     if (std::max(img.nrows, img.ncols) >= (1ll << 30)) return false;  // (staged entries carry two role bits)
     // complex vectors under a real image: the pass over 2 x nrhs real components streams the matrix once where the
-    // alternative is nrhs one-column products -- every image class takes it, exclusive forward ones included.  Mixed
-    // storage: one-column products only
-    if (vt != img.dtype) return (img.dtype == BSM_F32 && vt == BSM_C64) || (img.dtype == BSM_F64 && vt == BSM_C128);
+    // alternative is nrhs one-column products -- every image class takes it, exclusive forward ones included.
+    if (vt != img.dtype && img.dtype <= BSM_F64) return (img.dtype == BSM_F32 && vt == BSM_C64) || (img.dtype == BSM_F64 && vt == BSM_C128);
+    // Mixed storage (values in single precision under double vectors): the same alternative, the same answer -- from
+    // il_mixed_min_cols(img) columns on
+    if (vt != img.dtype)
+        return ((img.dtype == BSM_F64_F32 && vt == BSM_F64) || (img.dtype == BSM_C128_C64 && vt == BSM_C128)) &&
+               nrhs >= il_mixed_min_cols(img);
     if (nrhs < (vt >= BSM_C64 ? mfma_min_cols() : il_real_min_cols())) return false;
     if (!opT && img.exclusive_fwd) return false;   // plain stores with beta fused: nothing to gain
     // automatic: short scattered panels, and tall panels where the product is FUSED (symmetric operators: both halves, the
@@ -2543,12 +2593,18 @@ bool il_applies(const DeviceImage &img, bool opT, long long nrhs, int vt) {
 }
 // KT: the element type of the image the pass runs on -- T, or the real type of T for complex vectors under a real image:
 // then the KK complex columns packed into Xr are 2 KK real components of the real pass (alpha applied in the pack, beta
-// in the finish), and W comes back as KK complex sums
+// in the finish), and W comes back as KK complex sums; or the single-precision type a mixed-storage image stores under
+// T = double / c128 (the ILMixed instances: pack, finish and the work arrays are those of T)
 template <typename T, int KK, typename KT = T>
 static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T *xd, long long ldx, T *yd, long long ldy, T alpha,
                             T beta, int strong_zero, hipStream_t stream, int kact, ILWork &il, const long long *zrange) {
     using R = typename ILT<T>::R;
-    static_assert(std::is_same<KT, T>::value || std::is_same<KT, R>::value, "the image holds T or its real type");
+    constexpr bool MIXED = (std::is_same<T, double>::value && std::is_same<KT, float>::value) ||
+                           (std::is_same<T, c128>::value && std::is_same<KT, c64>::value);
+    static_assert(std::is_same<KT, T>::value || std::is_same<KT, R>::value || MIXED,
+                  "the image holds T, its real type or (mixed storage) its single-precision type");
+    using KI = typename std::conditional<MIXED, ILMixed<KT>, KT>::type;  // the kernel instance
+    count_value_pass(img);
     constexpr int CS = ILT<T>::CPLX ? 2 * KK : KK;  // components per vector index (8 or 16)
     const long long xlen = opT ? img.nrows : img.ncols, ylen = opT ? img.ncols : img.nrows;
     if (xlen > il.rows || ylen > il.rows) return hipErrorInvalidValue;
@@ -2584,10 +2640,10 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
             // (tall panels: all row blocks of the next 16 columns in flight -- il_panel's DEEP form, worth 1-6 % over one
             // step ahead with the XCD-aware order, profiles/r05_il_tall_panels.txt)
             if (small)
-                hipLaunchKernelGGL((panel_kernel_il<KT, 2, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
+                hipLaunchKernelGGL((panel_kernel_il<KI, 2, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
                                    flags, nblk, xcd_run);
             else
-                hipLaunchKernelGGL((panel_kernel_il<KT, 4, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
+                hipLaunchKernelGGL((panel_kernel_il<KI, 4, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
                                    flags, nblk, xcd_run);
         });
     });
@@ -2678,7 +2734,8 @@ static hipError_t launch_ladder(const DeviceImage &img, bool opT, bool conj, lon
 
 // The products of one (T, S) pair -- T: the type of x, y, alpha, beta; S: the type the image stores -- for K right-hand
 // sides, in this order:
-//   1. the interleaved pass over the image's own type S, where il_applies says so (and its work arrays are claimed);
+//   1. the interleaved pass over the image's own type S, where il_applies says so (and its work arrays are claimed) --
+//      every pair has one;
 //   2. same-type images only: the multi-RHS kernels (launch_ladder);
 //   3. the columns left, one at a time on the one-column kernels (the gather workspace only when K = 1).
 // vt: the dtype code of T (il_applies).
@@ -2691,11 +2748,13 @@ static hipError_t launch_pair(const DeviceImage &img, bool opT, bool conj, long 
     hipError_t e = hipSuccess;
     // The interleaved pass: complex types in batches of 8 columns, real types of 16, then one padded remainder (at most
     // half a batch left: 8 components per index, 64-byte lines).  Complex vectors under a real image: the 2 x 8 (2 x 4)
-    // real components of 8 (4) complex columns on the real pass, from 2 columns on.  (Mixed storage: no pass.)
-    if constexpr (std::is_same<S, T>::value || kCvec<T, S>) {
+    // real components of 8 (4) complex columns on the real pass, from 2 columns on.  Mixed storage: the batches of the
+    // vector type over the single-precision image, a remainder from il_mixed_min_cols(img) columns on.
+    {
         if (il && il_applies(img, opT, K, vt)) {
             constexpr int KK = ILT<T>::KK;
-            const int least = kCvec<T, S> ? 2 : ILT<T>::CPLX ? mfma_min_cols() : il_real_min_cols();
+            const int least = kCvec<T, S> ? 2 : !std::is_same<S, T>::value ? il_mixed_min_cols(img)
+                            : ILT<T>::CPLX ? mfma_min_cols() : il_real_min_cols();
             while (e == hipSuccess && K - k >= least) {
                 const int kact = (int)std::min<long long>(KK, K - k);
                 if (kact <= KK / 2)

@@ -349,6 +349,15 @@ class AbstractBlockMatrix(_LinearMap):
         L.check(L.lib().bsm_stats(self._h.ptr, C.byref(st)))
         return {k: getattr(st, k) for k, _ in L.BsmStats._fields_ if k != "reserved"}
 
+    def value_passes(self):
+        """How many times products of this handle have streamed a value image since it was created (bsm_value_passes):
+        a one-column product counts 1, a multi-column batch that streams the matrix once counts 1 whatever its width --
+        so `A @ X` with K columns that adds K here ran column by column.  Counted when a product is enqueued (a captured
+        one at capture).  Single-device handles."""
+        n = C.c_int64(0)
+        L.check(L.lib().bsm_value_passes(self._h.ptr, C.byref(n)))
+        return n.value
+
     def _bookkeeping(self, which):
         n = C.c_int64(0)
         L.check(L.lib().bsm_get_bookkeeping(self._h.ptr, which, None, C.byref(n)))

@@ -50,10 +50,12 @@ typedef enum {
  * BSM_F32 / BSM_C64 handle of the rounded blocks.  In a product each 16-byte lane load delivers 16 / sizeof(S) stored
  * values, which are widened in registers and combined with x by double-precision FMAs; partial sums, LDS windows,
  * atomics and the gather workspace are double.  All five *_create functions accept the codes; bsm_mul takes every
- * op, accumulate mode and transpose_image setting.  What a mixed handle does NOT offer:
+ * op, accumulate mode and transpose_image setting.
+ * bsm_mul_multi streams the single-precision image ONCE per batch of 16 double (8 complex double) columns: the
+ * interleaved pass over the stored type with double arithmetic (see bsm_mul_multi).
+ * What a mixed handle does NOT offer:
  *   - bsm_options.ctx (multi-device handles): BSM_ERR_UNSUPPORTED;
  *   - bsm_update_blocks: BSM_ERR_UNSUPPORTED (create a new handle from the new blocks);
- *   - bsm_mul_multi runs as nrhs one-column products (no one-pass multi-RHS kernels for mixed storage);
  *   - bsm_vec_add_segments takes vector types only: the mixed codes are BSM_ERR_INVALID there. */
 typedef enum { BSM_F32 = 0, BSM_F64 = 1, BSM_C64 = 2, BSM_C128 = 3, BSM_F64_F32 = 4, BSM_C128_C64 = 5 } bsm_dtype;
 
@@ -334,8 +336,17 @@ int bsm_host_unregister(void *ptr);
  * and Y is size(op(A),1) x nrhs, both column-major with leading dimensions ldx / ldy (elements).
  * Every other argument as in bsm_mul; each column gives what nrhs = 1 semantics prescribe (same
  * alpha, beta, strong zero).  nrhs = 1 is bsm_mul: the same kernels and, on a BSM_ACC_GATHER handle, the
- * same bitwise reproducible gather path.  Mixed-precision handles (BSM_F64_F32, BSM_C128_C64) run nrhs one-column
- * products, one after another on `stream` (their multi-RHS passes stream A once per column, not once per batch). */
+ * same bitwise reproducible gather path.
+ * Mixed-precision handles (BSM_F64_F32, BSM_C128_C64): from 3 columns on (2 on handles with symmetric pieces; BSM_IL_MIXED_MIN_COLS = 2 .. 8 overrides) the
+ * single-precision image is streamed ONCE per batch of 16 double / 8 complex double columns, on every image class
+ * (exclusive forward ones included): the stored values are widened in registers and meet X on the f64 matrix pipe, every
+ * sum is double.  A last batch of at most 8 / 4 columns is one pass over 8 components; columns below the threshold
+ * are one-column products.  These passes use the handle's interleaved work arrays (2 x 128 bytes per vector entry,
+ * allocated at the first multi-column product that takes them; atomics: the last bits depend on the order of the
+ * adds).  A product that does not get them -- another product in flight on them, graph capture, no memory --, a
+ * coloured image (BSM_ACC_COLORED: bitwise reproducible read-modify-write), vectors of 2^30 entries and more, or
+ * BSM_MULTI_IL=0 in the environment run nrhs one-column products, one after another on `stream`: the matrix is then
+ * streamed nrhs times (bsm_value_passes tells which happened). */
 int bsm_mul_multi(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int64_t ldx, void *Y,
                   int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace,
                   void *stream);
@@ -406,6 +417,15 @@ int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const void *X, int6
  * two 16 B per block source tables (uncaptured, captured) and their pinned host mirrors.  bsm_stats_t does not count it. */
 int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *ids, const void *const *blocks,
                       const int64_t *ld, int memspace, void *stream);
+
+/* *count = how many times products of this handle have streamed a value image since it was created.  Counted when a
+ * product is enqueued: a one-column product is 1; a multi-column batch that streams the matrix once (interleaved pass
+ * or multi-RHS kernels) is 1 whatever its width and however many colour launches it takes; columns that run one at a
+ * time are 1 each.  A product captured into a graph counts when it is captured, not when the graph is replayed.  So a
+ * bsm_mul_multi of nrhs columns that adds nrhs here ran column by column (e.g. it did not get the handle's work
+ * arrays).  Both images of a transpose_image handle count.  Single-device handles (an analysis-only one answers 0);
+ * a multi-device handle: BSM_ERR_UNSUPPORTED; null handle or pointer: BSM_ERR_INVALID. */
+int bsm_value_passes(bsm_matrix_t A, int64_t *count);
 
 /* Bookkeeping queries (bit-exact contract; every value 1-based int64 like the reference).
  * Call with out == NULL to obtain the required length in *len. */

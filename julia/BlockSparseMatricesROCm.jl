@@ -446,6 +446,14 @@ function _bookkeeping(h::Handle, which::Integer)
     return out
 end
 
+# how often products of A have streamed its value image since it was created (bsm_value_passes): a product with K
+# columns that adds K ran column by column, one that adds 1 streamed the matrix once
+function value_passes(A)
+    n = Ref{Int64}(0)
+    _check(ccall((:bsm_value_passes, libbsm), Cint, (Ptr{Cvoid}, Ref{Int64}), handle(_base(A)).ptr, n))
+    return n[]
+end
+
 function ROCmVBCRS(A::SymmetricBlockMatrix{T}; scheduler::ROCmScheduler=ROCmScheduler()) where {T<:ROCmEltype}
     ds = Int64[size(b, 1) for b in A.diagonals]
     m = Int64[size(b, 1) for b in A.offdiagonals]; n = Int64[size(b, 2) for b in A.offdiagonals]
