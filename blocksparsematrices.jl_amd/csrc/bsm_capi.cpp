@@ -1508,7 +1508,7 @@ static bool wsc_reserve(const Analysis &an, DeviceImage &img, hipStream_t st) {
 // the product after its argument checks (one column: K = 1, ld = max(length, 1)); vt: the dtype code of the vectors
 static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long ldx, void *Y, long long ldy,
                  const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t st, int vt) {
-    if (A->dist)  // multi-device handles: every device streams its part once per batch of <= 8 columns
+    if (A->dist)  // multi-device handles: every device streams its part once per batch of <= 16 columns
         return dist_mul_multi(A, op, K, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, st);
     // transposed products run forward on the second ordering when the handle has one
     const bool use_t = (op != BSM_OP_N) && A->has_t;
@@ -1519,7 +1519,7 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     hipError_t e = guard.enter(img.device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     // one column: the gather workspace (if the image has one); more: the interleaved pass's work arrays (if it applies)
-    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : il_applies(img, opT, K, vt), st);
+    Claim claim(K == 1 ? A->ws_claim : A->il_claim, K == 1 ? img.d_ws != nullptr : wants_il_arrays(plan_input(img, opT, vt, K, false)), st);
     // (complex vectors under a real image gather into the complex workspace)
     if (claim.held && K == 1 && vt != img.dtype && img.dtype <= BSM_F64 && !wsc_reserve(use_t ? A->an_t : A->an, img, st))
         claim.held = false;  // no memory for the complex workspace: the atomic path needs none

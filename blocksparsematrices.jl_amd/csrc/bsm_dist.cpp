@@ -80,7 +80,7 @@ struct Part {
 // the part's work arrays if its image / this product take the interleaved pass (and they can be had), else null.
 // (A part's image is never mixed storage: its dtype is the vector type of every product.)
 static ILWork *part_il(Part &pt, bool opT, int K) {
-    if (pt.il_failed || !il_applies(pt.img, opT, K, pt.img.dtype)) return nullptr;
+    if (pt.il_failed || !wants_il_arrays(plan_input(pt.img, opT, pt.img.dtype, K, false))) return nullptr;
     pt.il_failed = !il_reserve(pt.il, std::max(pt.img.nrows, pt.img.ncols));
     return pt.il_failed ? nullptr : &pt.il;
 }

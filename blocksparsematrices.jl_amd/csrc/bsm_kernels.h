@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "bsm_plan.h"
+
 namespace bsm {
 
 struct DeviceImage {
@@ -69,9 +71,12 @@ struct ILWork {
     long long rows = 0;   // capacity of both, in vector entries
     bool w_clean = false; // w is known to be zero
 };
-// whether launch_mul would take the interleaved pass for this image / op / batch / vector dtype vt (so that the caller
-// only claims -- and allocates -- the work arrays when they will be used)
-bool il_applies(const DeviceImage &img, bool opT, long long nrhs, int vt);
+// what the plan reads of a product of this image (bsm_plan.h).  Callers claim -- and allocate -- the work arrays only for
+// products that wants_il_arrays(plan_input(..., false)) names, and pass arrays = true where launch_mul gets them
+inline PlanInput plan_input(const DeviceImage &img, bool opT, int vt, long long K, bool arrays) {
+    return {img.dtype, vt, img.nrows, img.ncols, img.mean_rows, img.lane_fill, img.max_rows, img.exclusive_fwd, img.has_off,
+            !img.color_wg_ptr.empty(), opT, K, arrays};
+}
 
 // Enqueues Y = alpha*op(A)*X + beta*Y on `stream` for K right-hand sides, X (ldx) and Y (ldy) column-major device
 // pointers.  No allocation, no synchronisation (graph-capturable).

@@ -276,19 +276,6 @@ __shared__ unsigned long long t_trace[kWavesPerWg][16];
 #ifndef BSM_C128_FUSED_WAVES
 #define BSM_C128_FUSED_WAVES 6
 #endif
-#ifndef BSM_C64_L
-#define BSM_C64_L 4
-#endif
-// (developer builds: loads per lane of the fused kernels of the other element types)
-#ifndef BSM_F32_L
-#define BSM_F32_L 4
-#endif
-#ifndef BSM_F64_L
-#define BSM_F64_L 8
-#endif
-#ifndef BSM_C128_L
-#define BSM_C128_L 8
-#endif
 constexpr int FLAG_STRONG_ZERO = 1;
 constexpr int FLAG_DIRECT = 2;
 constexpr int FLAG_CONJ = 4;
@@ -657,7 +644,7 @@ template <typename T, bool FWD, bool TRN> constexpr int kMixedWaves = (FWD && TR
 //     exactly 8 workgroups fit a CU (+11-13 % on 3-28-row fp64 panels over 6 waves).
 //   complex128: capped at 80 (the fused instance compiles to 71: 7 waves).
 //   fp32 / complex64: capped at 96 = 5 waves (fp32 fused compiles to 80: 6), no scratch anywhere.
-//   mixed precision (S = float / c64 stored under double / complex128 vectors, L = 4: launch_one): capped at 80
+//   mixed precision (S = float / c64 stored under double / complex128 vectors, L = 4: bsm_plan.cpp): capped at 80
 //     = 6 waves, the fp64 fused instance at 72 = 7 (a cap of 64 left 8 B of scratch; complex128 needs 72 + 8 B under
 //     72).  No scratch anywhere.
 template <typename T, int L, bool FWD, bool TRN, bool NT, typename S = T>
@@ -869,9 +856,6 @@ template <typename T> __device__ __forceinline__ void settle(T &v) {
 // y entries); they are complete after the panel's row blocks and leave as scalar atomics, 4 per lane.
 // ----------------------------------------------------------------------------------------
 typedef double v4f64 __attribute__((ext_vector_type(4)));
-#ifndef BSM_MFMA_C128
-#define BSM_MFMA_C128 1
-#endif
 #ifndef BSM_MFMA_C128_WGS  // resident workgroups per CU the ComplexF64 instance is compiled for (3: 168 VGPRs)
 #define BSM_MFMA_C128_WGS 3
 #endif
@@ -882,17 +866,11 @@ template <typename T, int K> constexpr bool kMfmaPath = BSM_MFMA_C128 && std::is
 // wave-instruction = Re and Im of 16 consecutive y entries for two k) the x rows enter the A operand with their 16
 // components in transposed order: lane ln holds component 4 (ln % 4) + ln / 4, so accumulator row 4 lk + r is
 // component 4 r + lk = (k = 2 r + lk / 2, Re / Im = lk % 2).
-#ifndef BSM_MFMA_C64
-#define BSM_MFMA_C64 1
-#endif
 typedef float v4f32 __attribute__((ext_vector_type(4)));
 template <typename T, int K> constexpr bool kMfmaPath32 = BSM_MFMA_C64 && std::is_same<T, c64>::value && K == 8;
 // Real arithmetic: N = 16 is 16 right-hand sides.  The K = 16 instances (bsm_mul_multi: batches of 16, remainders of 9-15
 // padded) run the same loop with ONE MFMA per operand (no X''): Float64 = two columns per 16-byte load and the f64
 // accumulator map, Float32 = four columns per load and the f32 map with the components in transposed order.
-#ifndef BSM_MFMA_REAL
-#define BSM_MFMA_REAL 1
-#endif
 template <typename T, int K> constexpr bool kMfmaReal = BSM_MFMA_REAL && kRealType<T> && K == 16;
 template <typename T, int K> constexpr bool kMfmaAny = kMfmaPath<T, K> || kMfmaPath32<T, K> || kMfmaReal<T, K>;
 __device__ __forceinline__ v4f64 mfma16(double a, double b, v4f64 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
@@ -2367,8 +2345,8 @@ static int base_flags(bool opT, bool conj, int strong_zero) {
     return flags;
 }
 
-// bsm_value_passes: one stream of the image's values is about to be enqueued -- called by the three launchers that
-// issue one (launch_typed, launch_typed_multi, launch_il), once per product or batch whatever its colour launches
+// bsm_value_passes: one stream of the image's values is about to be enqueued -- called by launch_pair, once per batch
+// it executes (launch_typed, launch_typed_multi, launch_il: each streams them once, whatever its colour launches)
 static void count_value_pass(const DeviceImage &img) { __atomic_fetch_add(&img.value_passes, 1ll, __ATOMIC_RELAXED); }
 
 // [lo, hi): the y entries an accumulating product scales by beta -- the rows the image owns (all of them for op T / C),
@@ -2414,7 +2392,6 @@ template <typename F> static void with_halves(bool opT, bool has_off, F &&f) {
 template <typename T, int L, typename S>
 static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
                                int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
-    count_value_pass(img);
     int flags = base_flags(opT, conj, strong_zero);
     const uint4 *values = (const uint4 *)img.d_values;
     const int *rows = (const int *)img.d_rows;
@@ -2468,36 +2445,11 @@ static hipError_t launch_typed(const DeviceImage &img, bool opT, bool conj, cons
     return hipGetLastError();
 }
 
-// loads per lane in flight of the one-column kernels.  Every one-column launch takes it -- single products and the
-// single columns a multi-RHS product ends with.
-//   S = T: L = 4 where it was measured faster, on products that are fused (symmetric operators, accumulating), 8
-//     everywhere else.  complex64: 61 VGPRs, 8 waves per SIMD; with 8 the fused instance needs 93-95 (5 waves): tiled
-//     BEM fixture 105.9 -> 95.1 us (profiles/r04_c64_l4.txt).  fp32, SHORT panels only: tiled BEM fixture 48.6 -> 46.5
-//     us; 16-256-row operators lose 3-5 % with it and keep 8 (profiles/r04_fused_loads_per_lane.txt)
-//   S != T: 4 in every direction.  Mixed storage (S = float / c64 stored, T = double / c128 vectors): a lane's 4 strips
-//     hold 16 fp64 / 8 complex128 values after widening -- what the fp64 / complex128 instances of L = 8 hold -- and the
-//     forward instance with 8 loads needed 96 VGPRs and still spilled (the widened x reads of 8 strips: 64 VGPRs), i.e.
-//     5 resident waves against 6-8 with 4.  Complex vectors under a real image (T = c128 / c64, S = double / float): a
-//     lane's 4 strips meet 8 complex128 / 16 complex64 x entries.
-template <typename T, typename S>
-static hipError_t launch_one(const DeviceImage &img, bool opT, bool conj, const T *xd, T *yd, T alpha, T beta,
-                             int strong_zero, hipStream_t stream, bool use_gather, const long long *zrange) {
-    constexpr int LF = !std::is_same<S, T>::value ? 4
-                     : std::is_same<T, float>::value ? BSM_F32_L : std::is_same<T, double>::value ? BSM_F64_L
-                     : std::is_same<T, c64>::value ? BSM_C64_L : BSM_C128_L;
-    if constexpr (std::is_same<S, T>::value && LF != 8) {
-        const bool fused = img.has_off && !img.exclusive_fwd && (!std::is_same<T, float>::value || img.mean_rows < 32.f);
-        if (!fused) return launch_typed<T, 8, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
-    }
-    return launch_typed<T, LF, S>(img, opT, conj, xd, yd, alpha, beta, strong_zero, stream, use_gather, zrange);
-}
-
 // K right-hand sides per pass
 template <typename T, int L, int K>
 static hipError_t launch_typed_multi(const DeviceImage &img, bool opT, bool conj, const T *xd, long long ldx,
                                      T *yd, long long ldy, T alpha, T beta, int strong_zero,
-                                     hipStream_t stream, const long long *zrange, int kact = K) {
-    count_value_pass(img);
+                                     hipStream_t stream, const long long *zrange, int kact) {
     int flags = base_flags(opT, conj, strong_zero);
     if (kact < K) flags |= kact << FLAG_KACT_SHIFT;  // a padded batch: kact of the K slots carry columns
     const uint4 *values = (const uint4 *)img.d_values;
@@ -2524,87 +2476,20 @@ static hipError_t launch_typed_multi(const DeviceImage &img, bool opT, bool conj
     return hipGetLastError();
 }
 
-// ---- the interleaved pass (panel_kernel_il): policy and launch ---------------------------------------------
-// BSM_MULTI_IL: 0 = never, 1 = automatic (default: images that accumulate with atomics -- short scattered panels, mean
-// group height below 32, in every element type; ComplexF64 / ComplexF32 from BSM_MFMA_MIN_COLS columns on, real types
-// from BSM_IL_REAL_MIN_COLS), 2 = every image that accumulates with atomics (A / B)
-static int il_mode() {
-    static const int v = [] {
-        const char *e = std::getenv("BSM_MULTI_IL");
-        return e ? std::atoi(e) : 1;
-    }();
-    return v;
-}
-static int mfma_min_cols() {
-    static const int v = [] {
-        const char *e = std::getenv("BSM_MFMA_MIN_COLS");
-        return e ? std::atoi(e) : 3;  // (BEM fixture x 4: 362 us padded against 486 us through the 4-column kernel)
-    }();
-    return v;
-}
-static int il_real_min_cols() {
-    static const int v = [] {
-        const char *e = std::getenv("BSM_IL_REAL_MIN_COLS");
-        // (8 components per index from 5 columns on: BEM fp64 x 8 318 -> 202 us, C3 x 8 256 -> 217 us; 4 columns stay on the
-        // vector kernels: BEM 194 us, C3 195 us against ~ 200 / 217)
-        return e ? std::atoi(e) : 5;
-    }();
-    return v;
-}
-// fewest columns of a mixed-storage product that take the pass (a batch of 8 or more always does).  What the pass
-// replaces is nrhs one-column products, i.e. nrhs streams of the matrix, against ONE stream and two vector sweeps.
-// Pass / nrhs one-column products, us (docs/experiments_r09.md):
-//                          x 2          x 3          x 4          x 5
-//   C2 (forward VBCRS)     31.0 / 20.2  30.5 / 30.2  30.6 / 40.3  31.0 / 50.1
-//   1 GB forward VBCRS     265 / 213    270 / 319    274 / 426    282 / 532
-//   ... op T               259 / 241    263 / 362    268 / 483    279 / 603
-//   C3 (fused symmetric)   184 / 194    184 / 291    184 / 388    184 / 484
-//   tiled BEM, complex     265 / 286    267 / 429    270 / 572    353 / 715
-// Symmetric operators (both halves in every product) take the pass from two columns on; on the others two columns stay
-// two one-column products and three take the pass.  BSM_IL_MIXED_MIN_COLS (2 .. 8) overrides both.
-static int il_mixed_min_cols(const DeviceImage &img) {
-    static const int env = [] {
-        const char *e = std::getenv("BSM_IL_MIXED_MIN_COLS");
-        return e ? std::min(std::max(std::atoi(e), 2), 8) : 0;
-    }();
-    return env ? env : (img.has_off ? 2 : 3);
-}
-bool il_applies(const DeviceImage &img, bool opT, long long nrhs, int vt) {
-    if (nrhs < 2) return false;  // (one column: launch_mul's one-column kernels, whatever the thresholds say)
-    if (il_mode() == 0) return false;
-    if (!img.color_wg_ptr.empty()) return false;   // coloured launches keep their bitwise reproducible read-modify-write
-    if (std::max(img.nrows, img.ncols) >= (1ll << 30)) return false;  // (staged entries carry two role bits)
-    // complex vectors under a real image: the pass over 2 x nrhs real components streams the matrix once where the
-    // alternative is nrhs one-column products -- every image class takes it, exclusive forward ones included.
-    if (vt != img.dtype && img.dtype <= BSM_F64) return (img.dtype == BSM_F32 && vt == BSM_C64) || (img.dtype == BSM_F64 && vt == BSM_C128);
-    // Mixed storage (values in single precision under double vectors): the same alternative, the same answer -- from
-    // il_mixed_min_cols(img) columns on
-    if (vt != img.dtype)
-        return ((img.dtype == BSM_F64_F32 && vt == BSM_F64) || (img.dtype == BSM_C128_C64 && vt == BSM_C128)) &&
-               nrhs >= il_mixed_min_cols(img);
-    if (nrhs < (vt >= BSM_C64 ? mfma_min_cols() : il_real_min_cols())) return false;
-    if (!opT && img.exclusive_fwd) return false;   // plain stores with beta fused: nothing to gain
-    // automatic: short scattered panels, and tall panels where the product is FUSED (symmetric operators: both halves, the
-    // transposed one all atomics -- C3 x 16 377 -> 305 us, x 8 264 -> 220, C5 slice x 16 1607 -> 1131; the C3 structure with
-    // complex entries, tools/c3_complex.py: ComplexF64 x 8 175 -> 138 us, ComplexF32 76 -> 63).  Forward-only products of
-    // tall panels keep their kernels: on the C4 slice (128 x 128 fp32 blocks of one GPU of eight, vectors of the full 2 M
-    // entries) the pass's two vector sweeps cost more than it saves (x 8 363 -> 457 us, x 16 453 -> 562).
-    return il_mode() == 2 || img.mean_rows < 32.f || img.has_off;
-}
+// ---- the interleaved pass (panel_kernel_il) -- b: its batch (bsm_plan.h: columns, row-block instance, XCD run) -------
 // KT: the element type of the image the pass runs on -- T, or the real type of T for complex vectors under a real image:
 // then the KK complex columns packed into Xr are 2 KK real components of the real pass (alpha applied in the pack, beta
 // in the finish), and W comes back as KK complex sums; or the single-precision type a mixed-storage image stores under
 // T = double / c128 (the ILMixed instances: pack, finish and the work arrays are those of T)
 template <typename T, int KK, typename KT = T>
 static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T *xd, long long ldx, T *yd, long long ldy, T alpha,
-                            T beta, int strong_zero, hipStream_t stream, int kact, ILWork &il, const long long *zrange) {
+                            T beta, int strong_zero, hipStream_t stream, const Batch &b, ILWork &il, const long long *zrange) {
     using R = typename ILT<T>::R;
     constexpr bool MIXED = (std::is_same<T, double>::value && std::is_same<KT, float>::value) ||
                            (std::is_same<T, c128>::value && std::is_same<KT, c64>::value);
     static_assert(std::is_same<KT, T>::value || std::is_same<KT, R>::value || MIXED,
                   "the image holds T, its real type or (mixed storage) its single-precision type");
     using KI = typename std::conditional<MIXED, ILMixed<KT>, KT>::type;  // the kernel instance
-    count_value_pass(img);
     constexpr int CS = ILT<T>::CPLX ? 2 * KK : KK;  // components per vector index (8 or 16)
     const long long xlen = opT ? img.nrows : img.ncols, ylen = opT ? img.ncols : img.nrows;
     if (xlen > il.rows || ylen > il.rows) return hipErrorInvalidValue;
@@ -2615,31 +2500,18 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     if (e != hipSuccess) return e;
     if (xlen > 0)
         hipLaunchKernelGGL((il_pack_kernel<T, KK>), dim3((unsigned)((xlen + 255) / 256)), dim3(256), 0, stream, xd, ldx, xlen, alpha,
-                           kact, (T *)il.xr);
+                           b.kact, (T *)il.xr);
     const uint4 *values = (const uint4 *)img.d_values;
     const int *rows = (const int *)img.d_rows, *cols = (const int *)img.d_cols;
     const R *xr = (const R *)il.xr;
     R *w = (R *)il.w;
-    // (never coloured -- il_applies: one launch over every workgroup)
+    // (never coloured -- bsm_plan.cpp: one launch over every workgroup)
     for_each_launch(img, true, [&](const WaveWork *waves, dim3 plain, unsigned) {
-        // BSM_IL_XCD = R: XCD-aware workgroup order, runs of R consecutive workgroups per XCD (0: plain order).  Default:
-        // 16 for operators with tall panels (C3 x 16 312 -> 262 us -- neighbouring 64-row panels read the same 9 x 64
-        // lines of Xr, L2 hits 0.5 M -> of 9.5 M read requests with the plain order; R = 4 ... 64 alike), plain for
-        // short scattered panels (the tiled BEM fixture: +-0, 367 / 204 / 359 us against 374 / 208 / 352)
-        static const int xcd_env = [] {
-            const char *v = std::getenv("BSM_IL_XCD");
-            return v ? std::atoi(v) : -1;
-        }();
-        const bool small = img.max_rows <= 32;
-        const int xcd = xcd_env >= 0 ? xcd_env : (small ? 0 : 16);
-        const unsigned nblk = plain.x;
-        const unsigned xcd_run = xcd > 0 ? (unsigned)xcd : 0u, span = 8u * xcd_run;
+        const unsigned nblk = plain.x, xcd_run = (unsigned)b.xcd_run, span = 8u * xcd_run;
         const dim3 grid(xcd_run ? (nblk + span - 1) / span * span : nblk), block(64 * kWavesPerWg);
         with_halves(opT, img.has_off, [&](auto fwd, auto trn) {
             constexpr bool FWD = decltype(fwd)::value, TRN = decltype(trn)::value;
-            // (tall panels: all row blocks of the next 16 columns in flight -- il_panel's DEEP form, worth 1-6 % over one
-            // step ahead with the XCD-aware order, profiles/r05_il_tall_panels.txt)
-            if (small)
+            if (b.nrb == 2)
                 hipLaunchKernelGGL((panel_kernel_il<KI, 2, FWD, TRN, CS>), grid, block, 0, stream, waves, values, rows, cols, xr, w,
                                    flags, nblk, xcd_run);
             else
@@ -2650,10 +2522,10 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     // Y = beta * Y + W over the rows this handle scales (all of them for op T / C), Y += W elsewhere; W = 0 behind
     const YRange r = y_range(img, opT, zrange);
     const T one = make_scalar<T>(1.0);
-    auto finish = [&](long long a, long long b, T bt, int sz) {
-        if (b > a)
-            hipLaunchKernelGGL((il_finish_kernel<T, KK>), dim3((unsigned)((b - a + 255) / 256)), dim3(256), 0, stream, yd, ldy, a, b, bt,
-                               sz, kact, (T *)il.w);
+    auto finish = [&](long long lo, long long hi, T bt, int sz) {
+        if (hi > lo)
+            hipLaunchKernelGGL((il_finish_kernel<T, KK>), dim3((unsigned)((hi - lo + 255) / 256)), dim3(256), 0, stream, yd, ldy, lo, hi, bt,
+                               sz, b.kact, (T *)il.w);
     };
     finish(0, r.lo, one, 0);
     finish(r.lo, r.hi, beta, strong_zero);
@@ -2663,118 +2535,59 @@ static hipError_t launch_il(const DeviceImage &img, bool opT, bool conj, const T
     return e;
 }
 
-// The multi-RHS kernels of a same-type image over columns k .. nrhs - 1 (nrhs > 1), A streamed once per batch: advances
-// k past the columns they took; the rest are one-column products.
-template <typename T>
-static hipError_t launch_ladder(const DeviceImage &img, bool opT, bool conj, long long nrhs, long long &k, const T *xd,
-                                long long ldx, T *yd, long long ldy, T alpha, T beta, int strong_zero, hipStream_t stream,
-                                const long long *zrange) {
-    hipError_t e = hipSuccess;
-    // batches of 8, then 4, then single columns: A is streamed once per batch.  The 8-column
-    // kernels keep L = 4 loads per lane in flight instead of 8: with 8 accumulators and 8 x values
-    // per lane the registers, i.e. the resident waves, are worth more than the deeper load queue
-    // (fp64 fused: 143 -> 103 VGPRs; C3 3.0x -> 3.3x, 8-28-row blocks 2.0x -> 2.4x over 8 products).
-    // A remainder of 5-7 columns is one PADDED 8-column pass and 3 columns one padded 4-column pass (the idle
-    // slots repeat the last column and are never written): a pass costs 1.2-1.8 (8) / 1.1-1.4 (4) single products
-    // on the large operators, 3.9 / 3.0 on the BEM fixture -- never more than the 4 + singles it replaces; two
-    // columns stay two single products (a 4-column pass over 3-28-row panels costs three).
-    // real types, 9 columns and more: batches of 16 on the matrix pipe (N = 16 of v_mfma_*_16x16x4: kMfmaReal), a
-    // remainder of 9-15 as one padded pass (C3 x 16: 374 us against 2 x 264, C4 slice 442 against 2 x 364; x 9: one
-    // padded pass against an 8-column pass + a single product).  Short scattered panels (the BEM fixture: mean group
-    // height below 32) gain nothing below 15 columns: their passes are bound by the x gather and the atomics, which
-    // grow with the padded width (fp64 x 16: 615 us against 2 x 320).  BSM_MFMA_REAL_MIN_COLS overrides (17: off).
-    if constexpr (kMfmaReal<T, 16>) {
-        static const int mr_env = [] {
-            const char *v = std::getenv("BSM_MFMA_REAL_MIN_COLS");
-            return v ? std::atoi(v) : 0;
-        }();
-        const int mr_min = mr_env ? mr_env : (img.mean_rows < 32.f ? 15 : 9);
-        while (e == hipSuccess && nrhs - k >= 16 && mr_min <= 16) {
-            e = launch_typed_multi<T, 4, 16>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, zrange);
-            k += 16;
-        }
-        if (e == hipSuccess && nrhs - k >= mr_min && nrhs - k < 16) {
-            const int rem = (int)(nrhs - k);
-            e = launch_typed_multi<T, 4, 16>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, zrange, rem);
-            k += rem;
-        }
-    }
-    while (e == hipSuccess && nrhs - k >= 8) {
-        e = launch_typed_multi<T, 4, 8>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta,
-                                        strong_zero, stream, zrange);
-        k += 8;
-    }
-    // (ComplexF64: the 8-column pass runs on the matrix pipe -- a padded pass beats the 4-column register kernel
-    // from 3 columns on: BSM_MFMA_MIN_COLS)
-    const int mf_min = mfma_min_cols();
-    if (e == hipSuccess && nrhs - k >= (kMfmaAny<T, 8> ? mf_min : 5)) {
-        const int rem = (int)(nrhs - k);
-        e = launch_typed_multi<T, 4, 8>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta,
-                                        strong_zero, stream, zrange, rem);
-        k += rem;
-    }
-    // (two columns: a padded 4-column pass where the row groups fill their lanes -- 1.1-1.3 single products on C3 /
-    // C4 -- and two single products over short panels, where the pass would cost 2.6)
-    if (e == hipSuccess && (nrhs - k >= 3 || (nrhs - k == 2 && img.lane_fill >= 0.85f))) {
-        const int rem = (int)(nrhs - k);  // 2, 3 or 4
-        // (real arithmetic and a transposed half in the product: L = 4, i.e. the tile-pipelined kernels -- BEM fp64
-        // x 4 249 -> 211 us, C3 / C5 +-0; forward-only launches and complex: 8 loads per lane on the register path,
-        // C4 slice x 4 1.10 vs 1.16 single products with L = 4)
-        const bool fwd_only = !opT && (img.exclusive_fwd || !img.has_off);
-        if ((kRealType<T> || sizeof(T) == 16) && !fwd_only)  // (ComplexF64: L = 4 on the register path, BEM x 4 518 -> 490 us)
-            e = launch_typed_multi<T, 4, 4>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta,
-                                            strong_zero, stream, zrange, rem);
-        else
-            e = launch_typed_multi<T, 8, 4>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta,
-                                            strong_zero, stream, zrange, rem);
-        k += rem;
-    }
-    return e;
-}
-
 // The products of one (T, S) pair -- T: the type of x, y, alpha, beta; S: the type the image stores -- for K right-hand
-// sides, in this order:
-//   1. the interleaved pass over the image's own type S, where il_applies says so (and its work arrays are claimed) --
-//      every pair has one;
-//   2. same-type images only: the multi-RHS kernels (launch_ladder);
-//   3. the columns left, one at a time on the one-column kernels (the gather workspace only when K = 1).
-// vt: the dtype code of T (il_applies).
+// sides: executes the batches bsm_plan.cpp names, A streamed once per batch (the gather workspace only when K = 1).
+// vt: the dtype code of T; il: the work arrays of the interleaved pass, null when the product did not claim them.
+template <int N> using Int = std::integral_constant<int, N>;
 template <typename T, typename S>
 static hipError_t launch_pair(const DeviceImage &img, bool opT, bool conj, long long K, const T *xd, long long ldx, T *yd,
                               long long ldy, T alpha, T beta, int strong_zero, hipStream_t stream, bool use_gather,
                               const long long *zrange, ILWork *il, int vt) {
     if constexpr (kCvec<T, S>) conj = false;  // (op C of a real image is op T: `conj` has nothing to act on)
-    long long k = 0;
-    hipError_t e = hipSuccess;
-    // The interleaved pass: complex types in batches of 8 columns, real types of 16, then one padded remainder (at most
-    // half a batch left: 8 components per index, 64-byte lines).  Complex vectors under a real image: the 2 x 8 (2 x 4)
-    // real components of 8 (4) complex columns on the real pass, from 2 columns on.  Mixed storage: the batches of the
-    // vector type over the single-precision image, a remainder from il_mixed_min_cols(img) columns on.
-    {
-        if (il && il_applies(img, opT, K, vt)) {
-            constexpr int KK = ILT<T>::KK;
-            const int least = kCvec<T, S> ? 2 : !std::is_same<S, T>::value ? il_mixed_min_cols(img)
-                            : ILT<T>::CPLX ? mfma_min_cols() : il_real_min_cols();
-            while (e == hipSuccess && K - k >= least) {
-                const int kact = (int)std::min<long long>(KK, K - k);
-                if (kact <= KK / 2)
-                    e = launch_il<T, KK / 2, S>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-                else
-                    e = launch_il<T, KK, S>(img, opT, conj, xd + k * ldx, ldx, yd + k * ldy, ldy, alpha, beta, strong_zero, stream, kact, *il, zrange);
-                k += kact;
+    constexpr bool SAME = std::is_same<S, T>::value;
+    constexpr int KK = ILT<T>::KK;
+    // (the L of this pair's ONE batches where the plan does not say 8: bsm_plan.cpp, one_column)
+    constexpr int LF = !SAME ? 4 : std::is_same<T, float>::value ? BSM_F32_L : std::is_same<T, double>::value ? BSM_F64_L
+                     : std::is_same<T, c64>::value ? BSM_C64_L : BSM_C128_L;
+    const PlanInput in = plan_input(img, opT, vt, K, il != nullptr);
+    for (long long k = 0; k < K;) {
+        const Batch b = next_batch(in, k);
+        const T *x = xd + k * ldx;
+        T *y = yd + k * ldy;
+        auto il_pass = [&](auto kk) {
+            return launch_il<T, decltype(kk)::value, S>(img, opT, conj, x, ldx, y, ldy, alpha, beta, strong_zero, stream, b, *il, zrange);
+        };
+        auto multi = [&](auto l, auto width) {
+            return launch_typed_multi<T, decltype(l)::value, decltype(width)::value>(img, opT, conj, x, ldx, y, ldy, alpha, beta,
+                                                                                     strong_zero, stream, zrange, b.kact);
+        };
+        auto one = [&](auto l) {
+            return launch_typed<T, decltype(l)::value, S>(img, opT, conj, x, y, alpha, beta, strong_zero, stream, use_gather && K == 1,
+                                                          zrange);
+        };
+        count_value_pass(img);
+        const hipError_t e = [&] {
+            switch (b.kind) {
+                case Batch::IL:  // (planned only with the arrays at hand)
+                    return b.width == KK / 2 ? il_pass(Int<KK / 2>{}) : il_pass(Int<KK>{});
+                case Batch::MULTI:  // (same-type pairs only: the plan names none for the others)
+                    if constexpr (SAME) {
+                        if constexpr (kMfmaReal<T, 16>)
+                            if (b.width == 16) return multi(Int<4>{}, Int<16>{});
+                        return b.width == 8 ? multi(Int<4>{}, Int<8>{}) : b.L == 4 ? multi(Int<4>{}, Int<4>{}) : multi(Int<8>{}, Int<4>{});
+                    }
+                    break;
+                case Batch::ONE:
+                    if constexpr (SAME && LF != 8)
+                        if (b.L == 8) return one(Int<8>{});
+                    return one(Int<LF>{});
             }
-        }
+            return hipErrorInvalidValue;
+        }();
+        if (e != hipSuccess) return e;
+        k += b.kact;
     }
-    // (mixed storage and complex vectors under a real image: no multi-RHS kernels; one column: none, whatever the
-    // thresholds say)
-    if constexpr (std::is_same<S, T>::value) {
-        if (e == hipSuccess && K > 1)
-            e = launch_ladder<T>(img, opT, conj, K, k, xd, ldx, yd, ldy, alpha, beta, strong_zero, stream, zrange);
-    }
-    for (; e == hipSuccess && k < K; ++k)
-        e = launch_one<T, S>(img, opT, conj, xd + k * ldx, yd + k * ldy, alpha, beta, strong_zero, stream, use_gather && K == 1,
-                             zrange);
-    return e;
+    return hipSuccess;
 }
 
 static constexpr int pair_code(int img_dtype, int vt) { return img_dtype * 4 + vt; }

@@ -74,7 +74,7 @@ def test_random_operators_match_the_oracle(env, kind, dtype):
 @pytest.mark.parametrize("env_extra", [{"BSM_MULTI_IL": "2"}, {"BSM_MULTI_IL": "2", "BSM_IL_XCD": "5"},
                                        {"BSM_MULTI_IL": "2", "BSM_IL_XCD": "0"}, {"BSM_MULTI_IL": "0"}])
 def test_multi_rhs_fuzz_with_the_interleaved_pass_forced_and_switched_off(env_extra):
-    """The interleaved multi-RHS pass is chosen per image (csrc/bsm_kernels.hip: il_applies) from switches read once per
+    """The interleaved multi-RHS pass is chosen per image (csrc/bsm_plan.cpp: next_batch) from switches read once per
     process.  In child processes: the pass FORCED onto every image that accumulates with atomics (tall panels,
     transposed-only and forward-only products included; tall panels with all their row blocks in flight and the workgroups
     dealt to the XCDs in runs of 16), the same in runs of 5 workgroups (grids padded to multiples of 40) and in the plain
