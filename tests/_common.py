@@ -332,3 +332,47 @@ def interpret_image(A, op, x, y0, alpha=1, beta=0, strong=True, timage=False, mu
         assert not np.any(np.isnan(sums)), "a contributing workspace slot was never written"
         y = alpha * sums if strong else beta * y + alpha * sums
     return y
+
+
+def decode_mixed(A, op, x, y0, alpha=1, beta=0, strong=True, timage=False):
+    """y = alpha op(A) x + beta y0 from the packed image of a mixed handle: every panel piece's strips are read as the
+    STORED type (E = 16 / sizeof(S) columns per strip), widened to the vector type and applied in fp64 -- the kernel's
+    arithmetic, independently of its schedule.  timage: op T / C run forward on the transposed ordering."""
+    values, rows, cols, waves = get_image(A, timage)
+    S, Tt = A.storage_dtype, A.dtype
+    E = 16 // S.itemsize
+    vals = values.view(S)
+    opT = (op != N) and not timage
+    conj = op == Cc
+    acc = np.zeros(len(y0), dtype=Tt)
+    for W in waves[(waves["work"] == WORK_PANEL) & (waves["npieces"] > 0)]:
+        m = int(W["m"])
+        ridx = np.arange(W["rbase"], W["rbase"] + m) if W["rbase"] >= 0 else rows[W["row_off"]:W["row_off"] + m]
+        P = W["first"]
+        ns, nc = int(P["nstrips"]), int(P["ncols"])
+        base = int(P["val_off"]) * 16 // S.itemsize
+        full = vals[base:base + ns * m * E].reshape(ns, m, E).transpose(1, 0, 2).reshape(m, ns * E)
+        assert not np.any(full[:, nc:]), "strip padding must be zero"
+        B = full[:, :nc].astype(Tt)
+        if conj:
+            B = B.conj()
+        kinds = int(P["kind"])
+        wv = np.arange(nc)
+        pool = cols[P["col_off"]:P["col_off"] + nc]
+        if P["xbase"] >= 0:
+            s1w, s2w = int(W["seg1_w"]), int(W["seg2_w"])
+            cidx = np.where(wv < s1w, int(P["xbase"]) + wv,
+                            np.where(wv < s2w, int(W["seg1_x"]) + wv - s1w, int(P["seg2_x"]) + wv - s2w))
+            ckind = np.where(wv < s1w, kinds & 3, np.where(wv < s2w, (kinds >> 2) & 3, (kinds >> 4) & 3))
+        else:
+            cidx = pool & 0x7fffffff
+            ckind = np.where(pool < 0, 1, kinds & 3)
+        assert bool(kinds & KIND_HAS_OFF) == bool(np.any(ckind == KIND_OFF))
+        off = ckind == KIND_OFF
+        fcols = off if opT else np.ones(nc, bool)
+        tcols = np.ones(nc, bool) if opT else off
+        if np.any(fcols):
+            np.add.at(acc, ridx, B[:, fcols] @ x[cidx[fcols]])
+        if np.any(tcols):
+            np.add.at(acc, cidx[tcols], B[:, tcols].T @ x[ridx])
+    return alpha * acc if strong else beta * y0 + alpha * acc

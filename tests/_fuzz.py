@@ -32,10 +32,41 @@ def _index_list(rng, k, n):
     return np.sort(idx) if mode == 2 else idx
 
 
-def random_blocksparse(rng, dtype):
+def random_blocksparse(rng, dtype, colourable=False):
+    """colourable: the blocks of one row set take pairwise disjoint column lists (drawn among the columns the set does not
+    hold yet), so that the coloured accumulation mode -- which refuses a row set that repeats a column index -- builds.
+    The default draws exactly what it always drew: the operators of the existing seeds do not change."""
     nr, nc = int(rng.integers(150, 700)), int(rng.integers(150, 700))
     blocks, rows, cols = [], [], []
     pool = []  # row sets that get reused: several blocks on the SAME rows merge into one panel
+    # colourable: the columns held already, per run of at most 64 rows of a row list -- the unit the analysis merges (two
+    # different lists share a panel where such a run of theirs coincides, e.g. the first 64 of 100 and of 65 rows) -- and
+    # the rows held per run of columns, for the transposed ordering of a handle built with transpose_image
+    held, held_t = {}, {}
+    none = np.zeros(0, np.int64)
+
+    def runs_of(v):
+        return [tuple(int(i) for i in v[a:a + 64]) for a in range(0, len(v), 64)]
+
+    def columns(r, n):
+        if not colourable:
+            return _index_list(rng, n, nc) if n else none
+        taken = [held[k] for k in runs_of(r) if k in held]
+        free = np.setdiff1d(np.arange(1, nc + 1, dtype=np.int64), np.concatenate(taken) if taken else none)
+        n = min(n, len(free))
+        c = none
+        for _ in range(8 if n else 0):  # (a clash in the transposed ordering needs an identical run of columns: rare)
+            c = free[_index_list(rng, n, len(free)) - 1]
+            if not any(k in held_t and len(np.intersect1d(held_t[k], r)) for k in runs_of(c)):
+                break
+            c = none
+        if len(c) and len(r):
+            for k in runs_of(r):
+                held[k] = np.concatenate([held[k], c]) if k in held else c
+            for k in runs_of(c):
+                held_t[k] = np.concatenate([held_t[k], r]) if k in held_t else r
+        return c
+
     for _ in range(int(rng.integers(1, 40))):
         if pool and rng.random() < 0.4:
             r = pool[int(rng.integers(0, len(pool)))]
@@ -43,7 +74,7 @@ def random_blocksparse(rng, dtype):
             r = _index_list(rng, min(_size(rng), nr), nr)
             pool.append(r)
         n = 0 if rng.random() < 0.05 else min(_size(rng), nc)
-        c = _index_list(rng, n, nc) if n else np.zeros(0, np.int64)
+        c = columns(r, n)
         if rng.random() < 0.05:
             r = np.zeros(0, np.int64)
         blocks.append(_block(rng, len(r), len(c), dtype))
@@ -52,7 +83,7 @@ def random_blocksparse(rng, dtype):
     if rng.random() < 0.2:  # one very wide panel: many x chunks, a row group cut into several work items
         r = _index_list(rng, int(rng.choice([17, 40, 64])), nr)
         for _ in range(int(rng.integers(8, 30))):
-            c = _index_list(rng, min(int(rng.integers(60, 130)), nc), nc)
+            c = columns(r, min(int(rng.integers(60, 130)), nc))
             blocks.append(_block(rng, len(r), len(c), dtype))
             rows.append(r)
             cols.append(c)
@@ -115,6 +146,68 @@ def random_symmetric(rng, dtype):
 
 GEN = {"blocksparse": random_blocksparse, "vbcrs": random_vbcrs, "symmetric": random_symmetric}
 
+# the cross-type pairs (block type of the operator, vector type, storage= of the constructor): mixed storage (values kept
+# in single precision under double vectors) and real operators under complex vectors
+CROSS_PAIRS = [(np.float64, np.float64, np.float32), (np.complex128, np.complex128, np.complex64),
+               (np.float64, np.complex128, None), (np.float32, np.complex64, None)]
+_BLOCK_KEYS = ("blocks", "diagonals", "offdiagonals")
+
+
+def rounded(problem, S):
+    """the problem a mixed-storage handle holds: every block rounded once to the stored type S, back in double"""
+    q = dict(problem)
+    for k in _BLOCK_KEYS:
+        if k in problem:
+            q[k] = [np.asfortranarray(b.astype(S).astype(np.result_type(S, np.float64))) for b in problem[k]]
+    return q
+
+
+def cast_blocks(problem, dtype):
+    q = dict(problem)
+    for k in _BLOCK_KEYS:
+        if k in problem:
+            q[k] = [np.asfortranarray(b.astype(dtype)) for b in problem[k]]
+    return q
+
+
+def restrict_rows(problem, lo, hi):
+    """The blocks whose rows all lie in lo .. hi (1-based, inclusive): the operator a handle built with own=(lo, hi) may
+    hold if no row outside the range is to be touched.  An off-diagonal block of a symmetric operator reaches the rows of
+    its column list too (its transposed half), so both lists must lie inside."""
+    inside = lambda idx: bool(np.all((np.asarray(idx) >= lo) & (np.asarray(idx) <= hi)))  # noqa: E731
+    q = dict(problem)
+    k = problem["kind"]
+    if k == "blocksparse":
+        keep = [b for b, r in enumerate(problem["rowindices"]) if inside(r)]
+        q.update(blocks=[problem["blocks"][b] for b in keep], rowindices=[problem["rowindices"][b] for b in keep],
+                 colindices=[problem["colindices"][b] for b in keep])
+    elif k == "vbcrs":
+        keep = [b for b, (r, blk) in enumerate(zip(problem["rowstart"], problem["blocks"]))
+                if r >= lo and r + blk.shape[0] - 1 <= hi]
+        q.update(blocks=[problem["blocks"][b] for b in keep], rowstart=problem["rowstart"][keep],
+                 colstart=problem["colstart"][keep])
+    else:
+        kd = [b for b, d in enumerate(problem["diagonalindices"]) if inside(d)]
+        ko = [b for b, (r, c) in enumerate(zip(problem["rowindices"], problem["colindices"])) if inside(r) and inside(c)]
+        q.update(diagonals=[problem["diagonals"][b] for b in kd], diagonalindices=[problem["diagonalindices"][b] for b in kd],
+                 offdiagonals=[problem["offdiagonals"][b] for b in ko], rowindices=[problem["rowindices"][b] for b in ko],
+                 colindices=[problem["colindices"][b] for b in ko])
+    return q
+
+
+def build_fuzz(bsm, rng, kind, dtype, acc, redraws=5, **kw):
+    """One operator of GEN[kind] and its handle in accumulation mode acc -> (problem, handle), (problem, None) when the
+    analysis refuses the coloured mode.  The rule of the cross-pair tests for the coloured mode: block-sparse operators are
+    drawn colourable and always build; a symmetric operator whose row groups repeat a column index (one pair of row sets
+    drawn twice) is redrawn, up to `redraws` times; every other refusal is an error."""
+    colored = acc == "colored"
+    for _ in range(redraws + 1 if colored and kind == "symmetric" else 1):
+        p = random_blocksparse(rng, dtype, colourable=True) if colored and kind == "blocksparse" else GEN[kind](rng, dtype)
+        try:
+            return p, bsm.synthetic.build(p, accumulate=acc, **kw)
+        except RuntimeError as e:
+            assert colored and kind == "symmetric" and "repeat" in str(e), (kind, acc, str(e))
+    return p, None
 
 
 

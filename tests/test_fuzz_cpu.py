@@ -73,3 +73,121 @@ def test_random_operators_coarser_wave_records_match_the_oracle(env, kind, monke
             scale = max(np.max(np.abs(ref)), 1e-30)
             assert np.max(np.abs(got - ref)) / scale < 1e-12, (kind, case, op)
     assert seen >= 3
+
+
+# ---- cross-type pairs and the coloured mode on layout-edge operators ------------------------------------------------
+# Coloured cases follow _fuzz.build_fuzz: block-sparse operators are drawn colourable and always build, a symmetric
+# operator that repeats a pair of row sets is redrawn up to five times; a test asserts that at least half of its coloured
+# cases ran.  (The tests above keep their streams and their `continue`.)
+MIXED = [(np.float64, np.float32), (np.complex128, np.complex64)]
+KINDS = ["blocksparse", "vbcrs", "symmetric"]
+
+
+def _modes(kind):
+    return ["auto", "atomic", "gather"] + (["colored"] if kind != "vbcrs" else [])
+
+
+def _img_bytes(A, which):
+    import ctypes as C
+    from bsm_amd import _lib as L
+    n = C.c_int64(0)
+    L.check(L.lib().bsm_get_image(A._h.ptr, which, None, C.byref(n)))
+    buf = np.zeros(max(n.value, 1), dtype=np.uint8)
+    L.check(L.lib().bsm_get_image(A._h.ptr, which, buf.ctypes.data, C.byref(n)))
+    return buf[:n.value]
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("T_, S_", MIXED)
+def test_mixed_storage_decoded_image_matches_the_oracle_on_rounded_blocks(env, kind, T_, S_):
+    """Mixed-storage handles of random operators, every accumulation mode: the packed single-precision image decoded in
+    double (decode_mixed: the kernels' arithmetic without their schedule) against the oracle on the rounded blocks"""
+    from _common import decode_mixed
+    from _fuzz import build_fuzz, rounded
+    bsm, oracle = env
+    T_ = np.dtype(T_)
+    rng = np.random.default_rng(seed_of(kind, T_) + 11)
+    modes = _modes(kind)
+    coloured = ran = 0
+    for case in range(12):
+        acc = modes[case % len(modes)]
+        timg = kind != "symmetric" and case % 3 == 0
+        kw = {"transpose_image": True} if timg else {}
+        p, A = build_fuzz(bsm, rng, kind, T_, acc, device=NODEV, storage=S_, **kw)
+        coloured += acc == "colored"
+        if A is None:
+            continue
+        ran += acc == "colored"
+        assert A.dtype == T_ and A.storage_dtype == np.dtype(S_)
+        q = rounded(p, S_)
+        nr, nc = p["size"]
+        for op in (N, T, Cc):
+            xl, yl = (nc, nr) if op == N else (nr, nc)
+            x, y0 = rand_vec(rng, xl, T_), rand_vec(rng, yl, T_)
+            ref = oracle_mul(oracle, q, op, x, y0, -0.5, 1.25, False)
+            got = decode_mixed(A, op, x, y0, -0.5, 1.25, False, timage=(timg and op != N))
+            scale = max(np.max(np.abs(ref)), 1e-30)
+            assert np.max(np.abs(got - ref)) / scale < 1e-12, (kind, T_, case, acc, op)
+    assert 2 * ran >= coloured, (kind, T_, ran, coloured)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("T_, S_", MIXED)
+def test_mixed_values_image_is_that_of_the_blocks_cast_to_the_stored_type(env, kind, T_, S_):
+    """what test_mixed_storage_cpu.py::test_mixed_image_equals_rounded_single_image asserts on regular shapes: values,
+    rows and columns of a mixed image (and of its transposed ordering) byte for byte those of a single-precision handle"""
+    from _fuzz import build_fuzz, cast_blocks
+    bsm, _ = env
+    T_ = np.dtype(T_)
+    rng = np.random.default_rng(seed_of(kind, T_) + 12)
+    modes = _modes(kind)
+    coloured = ran = 0
+    for case in range(12):
+        acc = modes[case % len(modes)]
+        timg = kind != "symmetric" and case % 3 == 0
+        kw = {"transpose_image": True} if timg else {}
+        p, A = build_fuzz(bsm, rng, kind, T_, acc, device=NODEV, storage=S_, **kw)
+        coloured += acc == "colored"
+        if A is None:
+            continue
+        ran += acc == "colored"
+        with np.errstate(over="ignore"):
+            As = bsm.synthetic.build(cast_blocks(p, S_), device=NODEV, accumulate=acc, **kw)
+        assert As.dtype == As.storage_dtype == np.dtype(S_)
+        for which in (0, 1, 2) + ((16, 17, 18) if timg else ()):
+            a = _img_bytes(A, which)
+            assert len(a) > 0 or which != 0 or A.stats()["stored_entries"] == 0
+            assert np.array_equal(a, _img_bytes(As, which)), (kind, T_, case, acc, which)
+    assert 2 * ran >= coloured, (kind, T_, ran, coloured)
+
+
+@pytest.mark.parametrize("kind", ["blocksparse", "symmetric"])
+@pytest.mark.parametrize("dtype", [np.float64, np.complex128])
+def test_coloured_mode_builds_on_colourable_operators_and_matches_the_oracle(env, kind, dtype):
+    """Every case coloured.  Block-sparse operators drawn with colourable=True always build (no `continue`); symmetric
+    ones after at most five redraws, at least half of them"""
+    from _fuzz import build_fuzz
+    bsm, oracle = env
+    dtype = np.dtype(dtype)
+    rng = np.random.default_rng(seed_of(kind, dtype) + 13)
+    ran = 0
+    for case in range(12):
+        timg = kind != "symmetric" and case % 3 == 0
+        kw = {"transpose_image": True} if timg else {}
+        p, A = build_fuzz(bsm, rng, kind, dtype, "colored", device=NODEV, **kw)
+        if kind == "blocksparse":
+            assert A is not None
+        if A is None:
+            continue
+        ran += 1
+        nr, nc = p["size"]
+        for op in (N, T, Cc):
+            if op == Cc and dtype.kind != "c":
+                continue
+            xl, yl = (nc, nr) if op == N else (nr, nc)
+            x, y0 = rand_vec(rng, xl, dtype), rand_vec(rng, yl, dtype)
+            ref = oracle_mul(oracle, p, op, x, y0, -0.5, 1.25, False)
+            got = interpret_image(A, op, x, y0, -0.5, 1.25, False, timage=(timg and op != N))
+            scale = max(np.max(np.abs(ref)), 1e-30)
+            assert np.max(np.abs(got - ref)) / scale < 1e-12, (kind, dtype, case, op)
+    assert ran == 12 if kind == "blocksparse" else 2 * ran >= 12, (kind, dtype, ran)

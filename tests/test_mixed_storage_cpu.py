@@ -8,8 +8,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _common import (Cc, KIND_HAS_OFF, KIND_OFF, N, T, WORK_PANEL, fixture_problem, get_image, oracle_mul, rand_vec,
-                     relerr)
+from _common import Cc, N, T, WORK_PANEL, decode_mixed, fixture_problem, get_image, oracle_mul, rand_vec, relerr
+from _fuzz import rounded as _rounded
 
 NODEV = -2
 OPS = [N, T, Cc]
@@ -44,14 +44,6 @@ def _problem(bsm, ctor, dt):
         for i, k in enumerate(keys):
             p[k] = _complexify(p[k], 7 + i)
     return p
-
-
-def _rounded(p, S):
-    q = dict(p)
-    for k in ("blocks", "diagonals", "offdiagonals"):
-        if k in p:
-            q[k] = [np.asfortranarray(b.astype(S).astype(np.result_type(S, np.float64))) for b in p[k]]
-    return q
 
 
 def _build(bsm, ctor, p, dtype_cast=None, **kw):
@@ -96,50 +88,6 @@ def _oracle_problem(ctor, p):
         return dict(kind="vbcrs", blocks=list(d) + list(o) + [np.asfortranarray(b.T) for b in o],
                     rowstart=np.array(rs, dtype=np.int64), colstart=np.array(cs, dtype=np.int64), size=p["size"])
     return p
-
-
-def decode_mixed(A, op, x, y0, alpha=1, beta=0, strong=True, timage=False):
-    """y = alpha op(A) x + beta y0 from the packed image of a mixed handle: every panel piece's strips are read as the
-    STORED type (E = 16 / sizeof(S) columns per strip), widened to the vector type and applied in fp64 -- the kernel's
-    arithmetic, independently of its schedule.  timage: op T / C run forward on the transposed ordering."""
-    values, rows, cols, waves = get_image(A, timage)
-    S, Tt = A.storage_dtype, A.dtype
-    E = 16 // S.itemsize
-    vals = values.view(S)
-    opT = (op != N) and not timage
-    conj = op == Cc
-    acc = np.zeros(len(y0), dtype=Tt)
-    for W in waves[(waves["work"] == WORK_PANEL) & (waves["npieces"] > 0)]:
-        m = int(W["m"])
-        ridx = np.arange(W["rbase"], W["rbase"] + m) if W["rbase"] >= 0 else rows[W["row_off"]:W["row_off"] + m]
-        P = W["first"]
-        ns, nc = int(P["nstrips"]), int(P["ncols"])
-        base = int(P["val_off"]) * 16 // S.itemsize
-        full = vals[base:base + ns * m * E].reshape(ns, m, E).transpose(1, 0, 2).reshape(m, ns * E)
-        assert not np.any(full[:, nc:]), "strip padding must be zero"
-        B = full[:, :nc].astype(Tt)
-        if conj:
-            B = B.conj()
-        kinds = int(P["kind"])
-        wv = np.arange(nc)
-        pool = cols[P["col_off"]:P["col_off"] + nc]
-        if P["xbase"] >= 0:
-            s1w, s2w = int(W["seg1_w"]), int(W["seg2_w"])
-            cidx = np.where(wv < s1w, int(P["xbase"]) + wv,
-                            np.where(wv < s2w, int(W["seg1_x"]) + wv - s1w, int(P["seg2_x"]) + wv - s2w))
-            ckind = np.where(wv < s1w, kinds & 3, np.where(wv < s2w, (kinds >> 2) & 3, (kinds >> 4) & 3))
-        else:
-            cidx = pool & 0x7fffffff
-            ckind = np.where(pool < 0, 1, kinds & 3)
-        assert bool(kinds & KIND_HAS_OFF) == bool(np.any(ckind == KIND_OFF))
-        off = ckind == KIND_OFF
-        fcols = off if opT else np.ones(nc, bool)
-        tcols = np.ones(nc, bool) if opT else off
-        if np.any(fcols):
-            np.add.at(acc, ridx, B[:, fcols] @ x[cidx[fcols]])
-        if np.any(tcols):
-            np.add.at(acc, cidx[tcols], B[:, tcols].T @ x[ridx])
-    return alpha * acc if strong else beta * y0 + alpha * acc
 
 
 def _img_bytes(A, which):
