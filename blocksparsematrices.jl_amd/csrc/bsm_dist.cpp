@@ -1187,7 +1187,7 @@ int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long 
                    const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream) {
     const size_t es = (size_t)A->dist->es;
     // batches of 8 columns per fan-out; Float32 / Float64 operators take 9 and more columns 16 at a time (the parts'
-    // 16-column matrix-pipe passes, bsm_kernels.hip: kMfmaReal)
+    // 16-column matrix-pipe passes, bsm_multi.hip: kMfmaReal)
     const bool real = A->dist->dtype == 0 || A->dist->dtype == 1;
     for (long long k = 0; k < nrhs;) {
         const long long left = nrhs - k;

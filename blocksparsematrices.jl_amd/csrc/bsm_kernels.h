@@ -1,4 +1,4 @@
-// bsm_kernels.h -- interface between the C ABI glue and the HIP kernels.
+// bsm_kernels.h -- interface between the C ABI glue and the HIP kernels (bsm_kernels.hip: which family lives where).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -63,7 +63,7 @@ hipError_t launch_vec_finish(int dtype, void *y, long long ldy, void *w, long lo
 // y[lo_c + i] += base_c[i] for npieces <= kMaxVecPieces disjoint segments [lo_c, hi_c) of y, one launch
 hipError_t launch_vec_add_segments(int dtype, void *y, const VecPieces &pc, int npieces, hipStream_t stream);
 
-// Work arrays of the INTERLEAVED multi-RHS pass (bsm_kernels.hip: panel_kernel_il_*): X and the accumulated Y row-major,
+// Work arrays of the INTERLEAVED multi-RHS pass (bsm_il.hip: panel_kernel_il): X and the accumulated Y row-major,
 // one 128-byte line per vector index.  Owned by the handle (bsm_capi.cpp: Claim), one product in flight.
 struct ILWork {
     void *xr = nullptr;   // rows x 128 bytes: alpha * X, K-interleaved

@@ -1,10 +1,10 @@
 // bsm_plan.h -- which kernel takes the next columns of a product: the one place the multi-column policy lives.  Plain
-// C++ (no device, no handle): the launchers of bsm_kernels.hip execute what next_batch names, bsm_capi.cpp / bsm_dist.cpp
+// C++ (no device, no handle): launch_pair (bsm_kernels.hip) executes what next_batch names, bsm_capi.cpp / bsm_dist.cpp
 // ask wants_il_arrays before they claim the work arrays, tests/test_plan_cpu.py pins the table.
 #pragma once
 
 // Compile-time choices the plan reads and the kernels are built for (make variant EXTRA=-D...: both see the same value)
-#ifndef BSM_MFMA_C128  // ComplexF64, 8 columns: on the matrix pipe (bsm_kernels.hip: kMfmaPath)
+#ifndef BSM_MFMA_C128  // ComplexF64, 8 columns: on the matrix pipe (bsm_multi.hip: kMfmaPath)
 #define BSM_MFMA_C128 1
 #endif
 #ifndef BSM_MFMA_C64  // ComplexF32 likewise (kMfmaPath32)

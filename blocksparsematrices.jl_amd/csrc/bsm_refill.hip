@@ -1,5 +1,5 @@
 // bsm_refill.hip -- refill_kernel (bsm_update_blocks, include/bsm_rocm.h): new values into an existing image.
-// Kept out of bsm_kernels.hip: the build id (Makefile BUILD_ID) names the kernels and schedule of the PRODUCTS, and a
+// Kept out of the product kernel units (bsm_kernels.hip has their index): the build id (Makefile BUILD_ID) names the kernels and schedule of the PRODUCTS, and a
 // refill changes neither.
 #include <hip/hip_runtime.h>
 

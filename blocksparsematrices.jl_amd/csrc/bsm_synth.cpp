@@ -1,5 +1,5 @@
 // bsm_synth.cpp -- include/bsm_synth.h: synthetic operators of BASELINE.json generated in HBM
-// (bench / test utility; kernels in bsm_kernels.hip).
+// (bench / test utility; kernels in bsm_util.hip).
 #include <cstring>
 #include <vector>
 

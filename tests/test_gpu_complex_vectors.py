@@ -224,7 +224,7 @@ def test_cvec_golden_fixtures_real_part(torch_cuda, bsm, oracle, key, R_, C_):
 def test_cvec_lds_window_longer_than_a_complex_window(torch_cuda, bsm, oracle, R_, C_):
     """The analysis of a real image cuts its LDS y windows for the REAL element size; a complex window of the same
     4 KB holds half the entries.  The operator must have windows beyond that bound, and the complex product must
-    still be exact (bsm_kernels.hip: panel_kernel clamps the window of complex vectors under a real image)."""
+    still be exact (bsm_one.hip: panel_kernel clamps the window of complex vectors under a real image)."""
     p = fixture_problem("sphere", dtype=R_, part="real")
     twin = bsm.synthetic.build(p, device=-2)
     waves = get_image(twin)[3]

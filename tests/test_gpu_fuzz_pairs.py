@@ -345,7 +345,7 @@ def test_unaligned_vectors(env, kind, pair):
 def test_complex128_y_on_an_8_byte_boundary_through_the_c_abi(env, pair):
     """No tensor view puts a complex128 vector on an 8-byte boundary; a C caller can.  bsm_mul / bsm_mul_cvec with y at
     data_ptr() + 8, on atomic-mode handles and beta != 1 (numeric and strong zero): y .*= beta runs element by element
-    (csrc/bsm_kernels.hip: scale_kernel, the branch for a gap that is no multiple of the element size)"""
+    (csrc/bsm_one.hip: scale_kernel, the branch for a gap that is no multiple of the element size)"""
     torch, bsm, oracle = env
     from bsm_amd import _lib as L
     V = np.dtype(np.complex128)

@@ -1,5 +1,5 @@
 """GPU suite (-m gpu): several right-hand sides on mixed-precision handles (BSM_F64_F32, BSM_C128_C64) -- the
-single-precision image streamed ONCE per batch of double-precision columns (the interleaved pass, csrc/bsm_kernels.hip:
+single-precision image streamed ONCE per batch of double-precision columns (the interleaved pass, csrc/bsm_il.hip:
 panel_kernel_il<ILMixed<S>, ...>), observed through bsm_value_passes.
 
     mixed Y  vs a pure double-precision handle of the ROUNDED blocks, column by column : <= 1e-13

@@ -354,7 +354,7 @@ def test_multi_rhs_symmetric_and_blocksparse_fixture(torch_cuda, bsm, oracle, ke
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_multi_rhs_real_sixteen_column_passes_on_the_matrix_pipe(torch_cuda, bsm, oracle, dtype):
     """Real element types with 9 and more right-hand sides: batches of 16 (and padded remainders) run on
-    v_mfma_*_16x16x4 (csrc/bsm_kernels.hip: kMfmaReal) -- fused symmetric (atomic and coloured launches), exclusive
+    v_mfma_*_16x16x4 (csrc/bsm_multi.hip: kMfmaReal) -- fused symmetric (atomic and coloured launches), exclusive
     VBCRS (plain stores, beta fused, groups combined in LDS), BlockSparseMatrix, the reference's fixture (short
     scattered panels: from 15 columns on), ops N / T, numeric and strong-zero beta, every column against the oracle."""
     r = bsm.synthetic.config3(nseg=40, dtype=dtype)
@@ -387,7 +387,7 @@ def test_multi_rhs_real_fused_and_transposed_tile_pipeline(torch_cuda, bsm, orac
 
 
 def test_multi_rhs_interleaved_pass_state_and_ownership(torch_cuda, bsm, oracle):
-    """The interleaved multi-RHS pass (csrc/bsm_kernels.hip: panel_kernel_il -- X and the accumulated Y row-major in work
+    """The interleaved multi-RHS pass (csrc/bsm_il.hip: panel_kernel_il -- X and the accumulated Y row-major in work
     arrays of the handle, csrc/bsm_capi.cpp: ILClaim): what the oracle comparisons of the other multi-RHS tests do not
     reach --
       * the work arrays are kept and re-used: alternating ops, batch widths and component counts (8 / 16 per index) on ONE

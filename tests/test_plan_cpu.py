@@ -3,7 +3,8 @@ columns of a product, for every (image dtype, vector dtype) pair, image class, o
 
 What is expected is written down here from the launchers the plan replaced -- `launch_pair` (the interleaved pass while
 enough columns are left), `launch_ladder` (16 / 8 / padded 8 / 4, one stage after the other, each advancing k),
-`launch_one` (L of the single columns) and `il_applies` -- as they stood in csrc/bsm_kernels.hip, stage by stage with a
+`launch_one` (L of the single columns) and `il_applies` -- as they stood in csrc/bsm_kernels.hip
+(today: launch_pair there, the instances in bsm_one.hip / bsm_multi.hip / bsm_il.hip), stage by stage with a
 running k (`_model`), and as literal sequences at the documented crossovers.  The library answers through the unexported
 hook bsm_debug_plan (plain numbers in, batches out)."""
 import ctypes as C

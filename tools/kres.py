@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Developer probe: one line per kernel of csrc/bsm_kernels.hip with its registers, scratch, occupancy and LDS
-(hipcc -Rpass-analysis=kernel-resource-usage).  usage: kres.py [substring ...] [-D...]"""
+"""Developer probe: one line per kernel of ONE kernel translation unit (csrc/bsm_kernels.hip has the index) with its
+registers, scratch, occupancy and LDS (hipcc -Rpass-analysis=kernel-resource-usage); only that unit is compiled.
+usage: kres.py one|multi|il|util|refill|FILE.hip [substring ...] [-D...]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(ROOT, "blocksparsematrices.jl_amd", "csrc")
 defs = [a for a in sys.argv[1:] if a.startswith("-D")]
-pats = [a for a in sys.argv[1:] if not a.startswith("-D")]
+unit, *pats = [a for a in sys.argv[1:] if not a.startswith("-D")] or sys.exit(__doc__)
+unit = unit if unit.endswith(".hip") else f"bsm_{unit}.hip"
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-munsafe-fp-atomics",
-       "-Rpass-analysis=kernel-resource-usage", "-c", "bsm_kernels.hip", "-o", "/dev/null"] + defs
+       "-Rpass-analysis=kernel-resource-usage", "-c", unit, "-o", "/dev/null"] + defs
 out = subprocess.run(cmd, cwd=src, capture_output=True, text=True).stderr
 cur = None
 rows = []
