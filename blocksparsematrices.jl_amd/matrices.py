@@ -119,7 +119,8 @@ def _dev_blocks(*blocklists):
                 raise TypeError("device-resident blocks must all be 2-D torch CUDA tensors")
             if b.dtype not in _TORCH_DT or (dt is not None and _TORCH_DT[b.dtype] != dt):
                 raise TypeError("device-resident blocks must share one supported element type")
-            if b.shape[0] > 1 and b.stride(0) != 1 or (b.shape[1] > 1 and b.stride(1) < max(b.shape[0], 1)):
+            # (an empty block has no layout: torch gives a 0 x n tensor whatever strides its maker had)
+            if b.numel() > 0 and (b.shape[0] > 1 and b.stride(0) != 1 or (b.shape[1] > 1 and b.stride(1) < b.shape[0])):
                 raise TypeError("device-resident blocks must be column-major (e.g. torch.empty(n, m).t())")
             if dev is not None and b.device != dev:
                 raise ValueError("device-resident blocks must live on one device")

@@ -210,6 +210,83 @@ def build_fuzz(bsm, rng, kind, dtype, acc, redraws=5, **kw):
     return p, None
 
 
+# ---- the entries of an operator, straight from its numpy blocks (no library code) --------------------------------------
+def coo_triples(problem):
+    """(rows, cols, vals), 1-based: every entry of every block, the off-diagonal blocks of a symmetric operator a second
+    time transposed (not conjugated); overlapping blocks give one triple each, empty blocks none"""
+    rows, cols, vals = [], [], []
+
+    def push(b, ri, ci):
+        b = np.asarray(b)
+        if b.size == 0:
+            return
+        ri, ci = np.asarray(ri, dtype=np.int64), np.asarray(ci, dtype=np.int64)
+        rows.append(np.repeat(ri, len(ci)))  # row-major enumeration of the block
+        cols.append(np.tile(ci, len(ri)))
+        vals.append(np.ascontiguousarray(b).ravel())
+
+    k = problem["kind"]
+    if k == "vbcrs":
+        for b, r0, c0 in zip(problem["blocks"], problem["rowstart"], problem["colstart"]):
+            push(b, int(r0) + np.arange(b.shape[0]), int(c0) + np.arange(b.shape[1]))
+    elif k == "blocksparse":
+        for b, r, c in zip(problem["blocks"], problem["rowindices"], problem["colindices"]):
+            push(b, r, c)
+    else:
+        for b, d in zip(problem["diagonals"], problem["diagonalindices"]):
+            push(b, d, d)
+        for b, r, c in zip(problem["offdiagonals"], problem["rowindices"], problem["colindices"]):
+            push(b, r, c)
+            push(np.asarray(b).T, c, r)
+    if not rows:
+        first = [b for key in _BLOCK_KEYS for b in problem.get(key, [])]
+        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, first[0].dtype if first else np.float64)
+    return np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+
+
+def canonical(rows, cols, vals):
+    """The triples sorted by (row, col, bit pattern of the value) as one uint64 array with a row per triple: row << 32 | col,
+    then the value's bytes as unsigned integers (real part, imaginary part).  Duplicate positions of overlapping blocks,
+    NaNs and signed zeros compare exactly: two sets of triples are equal when their canonical forms are array_equal."""
+    rows, cols = np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64)
+    vals = np.ascontiguousarray(vals)
+    assert rows.shape == cols.shape == vals.shape and rows.ndim == 1
+    assert len(rows) == 0 or (rows.min() >= 0 and cols.min() >= 0 and rows.max() < 2 ** 31 and cols.max() < 2 ** 32), \
+        ("an index outside 0 .. 2^31", int(rows.min()), int(rows.max()), int(cols.min()), int(cols.max()))
+    word = {4: np.uint32, 8: np.uint64}[vals.dtype.itemsize // (2 if vals.dtype.kind == "c" else 1)]
+    bits = vals.view(word).reshape(len(vals), 2 if vals.dtype.kind == "c" else 1).astype(np.uint64)
+    out = np.empty((len(vals), 1 + bits.shape[1]), dtype=np.uint64)
+    out[:, 0] = (rows.astype(np.uint64) << np.uint64(32)) | cols.astype(np.uint64)
+    out[:, 1:] = bits
+    order = np.lexsort(tuple(out[:, k] for k in range(out.shape[1] - 1, -1, -1)))
+    return out[order]
+
+
+def edge_features(problem):
+    """which of the layout edges the operator reaches: "empty" (a block of size 0), "tall" (a block of more than 64 rows:
+    several chunks), "thin" (a non-empty block of one row or one column), "shared" (a row list / row start that two or more
+    blocks use: a merged panel), "scattered" (an index list that is not contiguous)"""
+    k = problem["kind"]
+    blocks = [b for key in _BLOCK_KEYS for b in problem.get(key, [])]
+    out = set()
+    if any(b.size == 0 for b in blocks):
+        out.add("empty")
+    if any(b.shape[0] > 64 for b in blocks):
+        out.add("tall")
+    if any(b.size > 0 and 1 in b.shape for b in blocks):
+        out.add("thin")
+    if k == "vbcrs":
+        rowkeys, lists = [int(r) for r in problem["rowstart"]], []
+    else:
+        rlists = list(problem.get("diagonalindices", [])) + list(problem["rowindices"])
+        rowkeys = [tuple(int(i) for i in r) for r in rlists if len(r)]
+        lists = rlists + list(problem["colindices"])
+    if len(set(rowkeys)) < len(rowkeys):
+        out.add("shared")
+    if any(len(v) > 1 and np.any(np.diff(np.asarray(v)) != 1) for v in lists):
+        out.add("scattered")
+    return out
+
 
 def seed_of(kind, dtype):
     """deterministic per (type, element type); BSM_FUZZ_OFFSET=k explores other streams"""

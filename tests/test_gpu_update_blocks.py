@@ -5,10 +5,10 @@ import numpy as np
 import pytest
 
 from _common import N, T, fixture_problem, oracle_mul, rand_vec, relerr
+from _values import dev_copy, new_values, on_device, padded, raw_update, src_list, with_values
 
 pytestmark = pytest.mark.gpu
 C_OP = 2
-KEYS = ("blocks", "diagonals", "offdiagonals")
 
 
 @pytest.fixture(scope="module")
@@ -17,41 +17,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     return torch
-
-
-def dev_copy(torch, b):
-    return torch.from_numpy(np.ascontiguousarray(b.T)).cuda().t()
-
-
-def src_list(p):
-    return [b for k in KEYS if k in p and not (k == "blocks" and p["kind"] == "symmetric") for b in p[k]]
-
-
-def with_values(p, vals):
-    """problem p with its blocks (constructor order: blocks, or diagonals + offdiagonals) replaced by vals"""
-    q = dict(p)
-    if p["kind"] == "symmetric":
-        nd = len(p["diagonals"])
-        q["diagonals"], q["offdiagonals"] = list(vals[:nd]), list(vals[nd:])
-    else:
-        q["blocks"] = list(vals)
-    return q
-
-
-def on_device(torch, p):
-    """the same problem with its blocks in HBM (column-major CUDA tensors): a handle built from it refills from
-    device memory"""
-    return with_values(p, [dev_copy(torch, b) for b in src_list(p)])
-
-
-def new_values(p, rng):
-    out = []
-    for b in src_list(p):
-        r = rng.standard_normal(b.shape)
-        if np.iscomplexobj(b):
-            r = r + 1j * rng.standard_normal(b.shape)
-        out.append(np.asfortranarray(r.astype(b.dtype)))
-    return out
 
 
 def products(bsm, torch, A, x, ops=(N, T, C_OP)):
@@ -211,29 +176,6 @@ def test_update_and_product_in_one_graph(torch_cuda, bsm, oracle):
     g.replay()
     torch.cuda.synchronize()
     assert relerr(y.cpu().numpy(), oracle_mul(oracle, with_values(p, vb), N, p["x"], np.zeros(n))) < 1e-12
-
-
-def raw_update(A, ids, blocks, lds, memspace, stream=None):
-    """bsm_update_blocks straight through the C ABI (1-based ids; numpy or CUDA-tensor blocks)"""
-    import ctypes as C
-    from bsm_amd import _lib as L
-    ids = np.ascontiguousarray(list(ids), dtype=np.int64)
-    ptrs = (C.c_void_p * max(len(blocks), 1))(*[(b.data_ptr() if hasattr(b, "data_ptr") else b.ctypes.data) for b in blocks])
-    ldv = np.ascontiguousarray(lds, dtype=np.int64)
-    I = C.POINTER(C.c_int64)
-    L.check(L.lib().bsm_update_blocks(A._h.ptr, len(blocks), ids.ctypes.data_as(I), ptrs, ldv.ctypes.data_as(I), memspace,
-                                      stream))
-
-
-def padded(torch, b, pad, device):
-    """b inside a column-major array with ld = m + pad (host array or CUDA tensor); returns (array, ld)"""
-    m, n = b.shape
-    a = np.zeros((m + pad, n), dtype=b.dtype, order="F")
-    a[:m] = b
-    a[m:] = np.nan  # rows outside the block must never be read
-    if device:
-        return torch.from_numpy(np.ascontiguousarray(a.T)).cuda().t(), m + pad
-    return a, m + pad
 
 
 def subset_round(torch, rng, p, A, cur, where, stream):
