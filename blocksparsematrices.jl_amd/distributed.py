@@ -9,6 +9,9 @@ in-library multi-device handles (bsm_ctx_t, csrc/bsm_dist.cpp) are the two MI355
   * VBCRS forward: block rows own disjoint y ranges (reference src/vbcrs.jl:275-283), so every
     rank multiplies its own rows and NO collective is needed; `gather=True` adds one all-gather of
     the y slices for callers that need the whole y on every GPU (a Krylov iteration: y is the next x).
+    Block rows that OVERLAP (a block that starts in one rank's rows and ends in the next rank's) are the
+    exception: such a rank touches rows it does not own, `touched_range` says which, and they travel
+    like the halo of the next two cases.
   * SymmetricBlockMatrix: the off-diagonal block (I, J) lives with the owner of row set I but also
     contributes B^T x_I to y_J, which may belong to another rank (for banded operators: the
     previous rank only).  Each rank accumulates into a work vector over the rows it TOUCHES and the
@@ -100,8 +103,12 @@ def _minrow(lst):
 
 def split_vbcrs(problem, rank, nparts, axis=0):
     """Partition a VBCRS problem dict into contiguous ranges of block rows (axis=0) or block columns
-    (axis=1: for transposed products) balanced by stored entries (bsm_partition_rows).
-    Returns (local problem, own=(lo, hi) 1-based inclusive along `axis`; hi = lo - 1: nothing)."""
+    (axis=1: for transposed products) balanced by stored entries (bsm_partition_rows): a block goes with
+    the part that owns its FIRST row (column).
+    Returns (local problem, own=(lo, hi) 1-based inclusive along `axis`; hi = lo - 1: nothing).
+    Block rows that start at arbitrary rows may overlap, and a block that starts in this part's range can then
+    reach into the next part's: what goes into `build_local` / `RowPartitioned(touched=...)` is
+    `touched_range(local, own, axis)`, which is `own` itself when no block crosses a cut."""
     keys = np.asarray(problem["rowstart" if axis == 0 else "colstart"], dtype=np.int64)
     weights = [b.size for b in problem["blocks"]]
     part, own = M.partition_rows(problem["size"][axis], keys, weights, nparts)
@@ -118,6 +125,25 @@ def _touched(own, lists):
         if len(lst):
             lo, hi = min(lo, int(np.min(lst))), max(hi, int(np.max(lst)))
     return (lo, hi) if hi >= lo else (own[0], own[0] - 1)
+
+
+def touched_range(local, own, axis=0):
+    """The range a rank's handle and its `RowPartitioned` must be given as `touched`: the hull of `own` and of every
+    row (axis=0; axis=1: every column, for a column partition and its transposed products) in the index lists of the
+    blocks of `local` -- for all three kinds; a symmetric off-diagonal block writes its row AND its column list.  This is
+    what `split_blocksparse` / `split_symmetric` return as their third value and what a `split_vbcrs` caller computes
+    itself.  (own_lo, own_lo - 1) when the rank owns nothing and has no block."""
+    kind = local["kind"]
+    if kind == "vbcrs":
+        start = local["rowstart" if axis == 0 else "colstart"]
+        lists = [_range_list(s, b.shape[axis]) for s, b in zip(start, local["blocks"]) if b.shape[axis]]
+    elif kind == "blocksparse":
+        lists = list(local["rowindices" if axis == 0 else "colindices"])
+    elif kind == "symmetric":
+        lists = list(local["diagonalindices"]) + list(local["rowindices"]) + list(local["colindices"])
+    else:
+        raise ValueError(kind)
+    return _touched((int(own[0]), int(own[1])), lists)
 
 
 def split_blocksparse(problem, rank, nparts):
@@ -159,8 +185,9 @@ def is_empty(local):
 
 
 def build_local(local, touched=None, **kw):
-    """The rank's handle: built with own = the rows it TOUCHES, so that its `y .*= beta` pass covers
-    exactly the rows it writes.  None for a rank without blocks."""
+    """The rank's handle: built with own = the rows it TOUCHES (`touched_range(local, own)`; the third value of
+    `split_blocksparse` / `split_symmetric`), so that its `y .*= beta` pass covers exactly the rows it writes.
+    None for a rank without blocks."""
     if is_empty(local):
         return None
     from . import synthetic
@@ -297,7 +324,9 @@ class RowPartitioned:
     x must hold the FULL vector on every rank.  After mul() the rank's output range is final in y
     (the whole y when gather=True): `own` for products along the partition, `out_range(n)` (equal
     chunks) for products across it.  `local` is this rank's matrix (built with own=touched range so
-    its beta pass covers exactly the rows it touches), or None for a rank without blocks."""
+    its beta pass covers exactly the rows it touches), or None for a rank without blocks.
+    `touched` = `touched_range(local blocks, own, axis)`: a `touched` that leaves out rows (axis=1: columns) a
+    local block writes drops those contributions silently -- `own` is enough only when no block crosses a cut."""
 
     def __init__(self, local, own, touched=None, group=None, gather=False, axis=0, symmetric=None, xneed=None,
                  interior=None, loopback=None, solo=False):

@@ -2,7 +2,9 @@
 GPU: HIP path vs oracle).  The generator aims at the corners of the packed layout rather than at
 realism: row counts around the 8/16/32/64 lane-group boundaries and the 64-row chunk limit, single
 rows and columns, empty blocks, repeated row sets (merged panels), overlapping row ranges, unsorted
-and strided index lists, rectangular operators, more than three column runs per panel."""
+and strided index lists, rectangular operators, more than three column runs per panel.
+For the multi-GPU layers: `squared`, the documented row partition in numpy (`partition_rule`) and the partition edges a
+(problem, number of parts) pair reaches (`partition_features`)."""
 import numpy as np
 
 EDGE = [1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 100, 129]
@@ -285,6 +287,101 @@ def edge_features(problem):
         out.add("shared")
     if any(len(v) > 1 and np.any(np.diff(np.asarray(v)) != 1) for v in lists):
         out.add("scattered")
+    return out
+
+
+def squared(problem):
+    """the same blocks with size = (n, n), n = max(size): rows and columns can then be partitioned alike (the
+    partitioned-vector legs of the multi-GPU layers on block-sparse and VBCRS operators); symmetric operators come back
+    as they are"""
+    q = dict(problem)
+    n = int(max(problem["size"]))
+    q["size"] = (n, n)
+    return q
+
+
+def block_lists(problem):
+    """per block, in the order the multi-GPU layers number them (symmetric: diagonals first) -> (row hulls, column hulls,
+    row keys, weights); a hull is (lo, hi) 1-based inclusive or None for an empty list, the key of a block is its smallest
+    row index (1 for an empty list), its weight the stored entries"""
+    k = problem["kind"]
+    if k == "vbcrs":
+        rl = [np.arange(int(r), int(r) + b.shape[0]) for r, b in zip(problem["rowstart"], problem["blocks"])]
+        cl = [np.arange(int(c), int(c) + b.shape[1]) for c, b in zip(problem["colstart"], problem["blocks"])]
+        blocks = problem["blocks"]
+    elif k == "blocksparse":
+        rl, cl, blocks = list(problem["rowindices"]), list(problem["colindices"]), problem["blocks"]
+    else:
+        rl = list(problem["diagonalindices"]) + list(problem["rowindices"])
+        cl = list(problem["diagonalindices"]) + list(problem["colindices"])
+        blocks = list(problem["diagonals"]) + list(problem["offdiagonals"])
+    hull = lambda v: (int(np.min(v)), int(np.max(v))) if len(v) else None  # noqa: E731
+    return [hull(v) for v in rl], [hull(v) for v in cl], [int(np.min(v)) if len(v) else 1 for v in rl], \
+        [int(b.size) for b in blocks]
+
+
+def partition_rule(nrows, keys, weights, nparts):
+    """The row partition of both multi-GPU layers as include/bsm_rocm.h documents it (bsm_partition_rows), in numpy: the
+    distinct keys, ascending, are cut into nparts contiguous ranges of about equal weight -- part p starts at the first
+    key whose running weight in front of it reaches p / nparts of the total --; part p owns the rows from its first key
+    to the next part's first key - 1 (the first part that has a key from row 1, the last one to nrows; a part without
+    a key: an empty range just below the next part's first row; no block at all: part 0 owns everything).
+    -> (part of every block, [(own_lo, own_hi)] 1-based inclusive)"""
+    keys, weights = np.asarray(keys, dtype=np.int64), np.asarray(weights, dtype=np.int64)
+    uk, kidx = np.unique(keys, return_inverse=True)
+    nk = len(uk)
+    w = np.zeros(nk, dtype=np.float64)
+    np.add.at(w, kidx.reshape(-1), np.maximum(weights, 0).astype(np.float64))
+    csum = np.concatenate([[0.0], np.cumsum(w)])
+    cut = [0]
+    for p in range(1, nparts):
+        k = int(np.searchsorted(csum, csum[-1] * p / nparts, side="left"))
+        cut.append(min(max(k, cut[-1]), nk))
+    cut.append(nk)
+    part_of_key = np.zeros(nk, dtype=np.int32)
+    own = []
+    for p in range(nparts):
+        part_of_key[cut[p]:cut[p + 1]] = p
+        if cut[p] == cut[p + 1]:
+            lo = int(uk[cut[p]]) if cut[p] < nk else nrows + 1
+            own.append([lo, lo - 1])
+        else:
+            own.append([int(uk[cut[p]]), int(uk[cut[p + 1]]) - 1 if cut[p + 1] < nk else nrows])
+    have = [p for p in range(nparts) if cut[p] < cut[p + 1]]
+    if have:
+        own[have[0]][0], own[have[-1]][1] = 1, nrows
+    else:
+        own[0] = [1, nrows]
+    return part_of_key[kidx.reshape(-1)] if nk else np.zeros(0, np.int32), [tuple(o) for o in own]
+
+
+def partition_features(problem, parts):
+    """which edges of the row partition into `parts` parts the operator reaches: "empty_part" (a part without a block),
+    "halo_below" / "halo_above" (a part whose blocks write rows below / above the rows it owns -- through a row list, or
+    through the column list of a symmetric off-diagonal block), "crossing_block" (VBCRS: a block that starts in a part's
+    rows and ends behind them), "tall" / "wide" (more rows than columns / more columns than rows)"""
+    rh, ch, keys, weights = block_lists(problem)
+    part, own = partition_rule(problem["size"][0], keys, weights, parts)
+    sym = problem["kind"] == "symmetric"
+    out = set()
+    for p in range(parts):
+        mine = [b for b in range(len(keys)) if part[b] == p]
+        if not mine:
+            out.add("empty_part")
+        lo, hi = own[p]
+        for b in mine:
+            for h in [rh[b]] + ([ch[b]] if sym else []):
+                if h is None:
+                    continue
+                if h[0] < lo:
+                    out.add("halo_below")
+                if h[1] > hi:
+                    out.add("halo_above")
+                    if problem["kind"] == "vbcrs":
+                        out.add("crossing_block")
+    nr, nc = problem["size"]
+    if nr != nc:
+        out.add("tall" if nr > nc else "wide")
     return out
 
 

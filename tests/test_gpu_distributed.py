@@ -47,7 +47,7 @@ def _worker(rank, world, port, kind, q):
                             rowstart=np.array([4, 30]), colstart=np.array([2, 20]), size=(40, 40),
                             x=rng.standard_normal(40))
             local, own = D.split_vbcrs(prob, rank, world)
-            touched = own
+            touched = D.touched_range(local, own)
             if kind == "vbcrs_T":  # transposed product of a ROW-partitioned operator: reduce-scatter
                 op = T
         elif kind == "blocksparse":
@@ -175,6 +175,26 @@ def test_row_partitioned_with_the_hip_local_product(kind, world):
     assert status == "ok", errs
     assert all(e < 1e-12 for e in errs), errs
     assert all(p.exitcode == 0 for p in procs)
+
+
+@pytest.mark.parametrize("world", [2, 3])
+@pytest.mark.parametrize("kind,dtype,mode", [("vbcrs", "float64", "square"), ("blocksparse", "float64", "square"),
+                                             ("symmetric", "float64", "square"), ("vbcrs", "float64", "rect"),
+                                             ("symmetric", "complex128", "square")])
+def test_layout_edge_operators_with_the_hip_local_product(kind, dtype, mode, world):
+    """Six operators of tests/_fuzz.py per spawn -- block rows that overlap the next rank's rows, scattered index lists,
+    ranks without blocks -- through the rank process of the CPU tests (tests/_distworker.py) with real device handles:
+    "square": both gather modes, partitioned x, build_overlapped with xmode "halo" / "allgather" / "auto", mul_multi
+    (complex symmetric: op T and C as well); "rect": op N, op T across the row partition and on the column partition of
+    operators as drawn.  A rank that crashes or does not finish in time fails the test and nothing else is started."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _distworker import spawn
+    status, errs, own, touched, codes = spawn(("fuzz", kind, dtype, 6, mode), world, device="cuda", timeout=240)
+    assert status == "ok", errs
+    print("DISTHIP {} {} {} world {} products {} worst {:.3e}".format(kind, dtype, mode, world, len(errs), max(errs)))
+    assert len(errs) >= 6 * 8
+    assert all(e < 1e-12 for e in errs), " ".join("%.2e" % e for e in errs)
+    assert all(c == 0 for c in codes)
 
 
 def test_bench_launches_its_own_ranks_and_reports_parity():
