@@ -1,5 +1,8 @@
-"""Shared test helpers: fixture reader, oracle drivers, and a numpy interpreter of the packed
-device image (so the host analysis is checked on CPU, without a GPU).  Test code only."""
+"""Shared test helpers that need no device: the op codes and the small conventions every suite uses (`wrap`, `lens`,
+`acc_modes`, `NODEV`, `BLOCK_KEYS`, `nblocks`), the fixture reader, the oracle drivers and error norms, and a numpy
+interpreter of the packed device image (`get_image`, `img_bytes`, `interpret_image`, `decode_mixed`), so the host
+analysis is checked on CPU.  Device helpers live in _gpu.py, the five constructor routes in _ctors.py, the random
+operators in _fuzz.py, block-value helpers in _values.py.  Test code only."""
 import ctypes as C
 import os
 import struct
@@ -8,6 +11,28 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 N, T, Cc = 0, 1, 2  # ops
+NODEV = -2  # BSM_DEVICE_NONE: an analysis-only handle
+BLOCK_KEYS = ("blocks", "diagonals", "offdiagonals")  # the block lists of a problem dict, in constructor order
+
+
+def wrap(bsm, A, op):
+    """A, transpose(A) or adjoint(A) by op"""
+    return A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
+
+
+def lens(problem, op):
+    """(length of x, length of y) of op(A)"""
+    nr, nc = problem["size"]
+    return (nc, nr) if op == N else (nr, nc)
+
+
+def acc_modes(kind):
+    """the accumulation modes the fuzz tests cycle through (VBCRS has no coloured mode)"""
+    return ["auto", "atomic", "gather"] + (["colored"] if kind != "vbcrs" else [])
+
+
+def nblocks(problem):
+    return sum(len(problem.get(k, ())) for k in BLOCK_KEYS)
 
 
 def read_fixture(key):
@@ -191,6 +216,16 @@ def get_image(A, timage=False, multi=False):
         L.check(L.lib().bsm_get_image(A._h.ptr, which, buf.ctypes.data, C.byref(n)))
         out.append(buf[:n.value].view(dt))
     return out
+
+
+def img_bytes(A, which):
+    """array `which` of bsm_get_image as raw bytes"""
+    from bsm_amd import _lib as L
+    n = C.c_int64(0)
+    L.check(L.lib().bsm_get_image(A._h.ptr, which, None, C.byref(n)))
+    buf = np.zeros(max(n.value, 1), dtype=np.uint8)
+    L.check(L.lib().bsm_get_image(A._h.ptr, which, buf.ctypes.data, C.byref(n)))
+    return buf[:n.value]
 
 
 def get_inverted_index(A, timage=False):

@@ -20,7 +20,6 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODEV = -2
 
 
 def free_port():
@@ -111,7 +110,7 @@ def _one_operator(prob, legs, rank, world, device, fuzz):
     import torch.distributed as dist
     import bsm_amd as bsm
     from bsm_amd import distributed as D
-    from _common import Cc, N, T, interpret_image
+    from _common import NODEV, Cc, N, T, interpret_image, nblocks
 
     cpu = device == "cpu"
     kind = prob["kind"]
@@ -223,8 +222,7 @@ def _one_operator(prob, legs, rank, world, device, fuzz):
         # the same partitioned-vector product with the exchange OVERLAPPED with the interior rows: two images per rank
         # (interior / boundary blocks, distributed.split_interior), the boundary one on the side of the exchange
         interior, boundary, bt, bx = D.split_interior(local, own)
-        cnt = lambda p_: sum(len(p_.get(k, ())) for k in ("blocks", "diagonals", "offdiagonals"))  # noqa: E731
-        assert cnt(interior) + cnt(boundary) == cnt(local)
+        assert nblocks(interior) + nblocks(boundary) == nblocks(local)
         if cpu:
             Ai = None if D.is_empty(interior) else bsm.synthetic.build(interior, device=NODEV, own=own)
             Ab = None if D.is_empty(boundary) else bsm.synthetic.build(boundary, device=NODEV, own=bt)

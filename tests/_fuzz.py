@@ -4,8 +4,12 @@ realism: row counts around the 8/16/32/64 lane-group boundaries and the 64-row c
 rows and columns, empty blocks, repeated row sets (merged panels), overlapping row ranges, unsorted
 and strided index lists, rectangular operators, more than three column runs per panel.
 For the multi-GPU layers: `squared`, the documented row partition in numpy (`partition_rule`) and the partition edges a
-(problem, number of parts) pair reaches (`partition_features`)."""
+(problem, number of parts) pair reaches (`partition_features`).  Also what the fuzz suites share: the cross-type
+pairs, `rounded` / `cast_blocks`, `build_fuzz` (the coloured-mode rule), the strict error norm `fuzz_err` and the `Stat`
+counter behind the PAIRSTAT / DISTDEV lines."""
 import numpy as np
+
+from _common import BLOCK_KEYS
 
 EDGE = [1, 2, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 100, 129]
 
@@ -152,13 +156,12 @@ GEN = {"blocksparse": random_blocksparse, "vbcrs": random_vbcrs, "symmetric": ra
 # in single precision under double vectors) and real operators under complex vectors
 CROSS_PAIRS = [(np.float64, np.float64, np.float32), (np.complex128, np.complex128, np.complex64),
                (np.float64, np.complex128, None), (np.float32, np.complex64, None)]
-_BLOCK_KEYS = ("blocks", "diagonals", "offdiagonals")
 
 
 def rounded(problem, S):
     """the problem a mixed-storage handle holds: every block rounded once to the stored type S, back in double"""
     q = dict(problem)
-    for k in _BLOCK_KEYS:
+    for k in BLOCK_KEYS:
         if k in problem:
             q[k] = [np.asfortranarray(b.astype(S).astype(np.result_type(S, np.float64))) for b in problem[k]]
     return q
@@ -166,7 +169,7 @@ def rounded(problem, S):
 
 def cast_blocks(problem, dtype):
     q = dict(problem)
-    for k in _BLOCK_KEYS:
+    for k in BLOCK_KEYS:
         if k in problem:
             q[k] = [np.asfortranarray(b.astype(dtype)) for b in problem[k]]
     return q
@@ -212,6 +215,38 @@ def build_fuzz(bsm, rng, kind, dtype, acc, redraws=5, **kw):
     return p, None
 
 
+def fuzz_err(got, ref):
+    """max|got - ref| / max|ref|, the norm of the fuzz suites.  Unlike _common.relerr an all-zero reference does not
+    divide by 1 but by 1e-30: any non-zero entry of `got` then fails"""
+    return float(np.max(np.abs(got - ref)) / max(np.max(np.abs(ref)), 1e-30)) if len(ref) else 0.0
+
+
+def scalar_sets(dt):
+    """(alpha, beta, strong zero) of the one-column legs of the GPU fuzz suites; complex vectors add a complex pair"""
+    s = [(1, 0, True), (-0.5, 1.25, False)]
+    return s + [(0.5 - 0.25j, 1.5 + 0.5j, False)] if np.dtype(dt).kind == "c" else s
+
+
+class Stat:
+    """The counters of one GPU fuzz test: every check prints its error and feeds `worst`; `done` prints the summary line
+    docs/ quote and asserts that at least half of the coloured cases ran."""
+
+    def __init__(self, *tag):
+        self.tag, self.worst = tag, 0.0
+        self.products = self.columns = self.cases = self.empty_parts = self.coloured = self.ran = 0
+
+    def check(self, got, ref, tol, what):
+        e = fuzz_err(got, ref)
+        print(f"  {self.tag} {what}: {e:.3e}")
+        self.worst = max(self.worst, e) if e == e else float("nan")
+        self.columns += 1
+        assert e < tol, (self.tag, what, e)
+
+    def done(self, head, counts):
+        print("{} {} {} {} worst {:.3e} {} coloured {} of {}".format(head, *self.tag, self.worst, counts, self.ran, self.coloured))
+        assert 2 * self.ran >= self.coloured, (self.tag, self.ran, self.coloured)
+
+
 # ---- the entries of an operator, straight from its numpy blocks (no library code) --------------------------------------
 def coo_triples(problem):
     """(rows, cols, vals), 1-based: every entry of every block, the off-diagonal blocks of a symmetric operator a second
@@ -241,7 +276,7 @@ def coo_triples(problem):
             push(b, r, c)
             push(np.asarray(b).T, c, r)
     if not rows:
-        first = [b for key in _BLOCK_KEYS for b in problem.get(key, [])]
+        first = [b for key in BLOCK_KEYS for b in problem.get(key, [])]
         return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, first[0].dtype if first else np.float64)
     return np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
 
@@ -269,7 +304,7 @@ def edge_features(problem):
     several chunks), "thin" (a non-empty block of one row or one column), "shared" (a row list / row start that two or more
     blocks use: a merged panel), "scattered" (an index list that is not contiguous)"""
     k = problem["kind"]
-    blocks = [b for key in _BLOCK_KEYS for b in problem.get(key, [])]
+    blocks = [b for key in BLOCK_KEYS for b in problem.get(key, [])]
     out = set()
     if any(b.size == 0 for b in blocks):
         out.add("empty")

@@ -21,7 +21,6 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODEV = -2
 
 
 def loaded_libraries(sub):
@@ -59,7 +58,7 @@ def run(backend, port, q):
             dist.batch_isend_irecv = in_process
         import bsm_amd as bsm
         from bsm_amd import distributed as D
-        from _common import N, T, interpret_image, oracle_mul, relerr
+        from _common import NODEV, N, T, interpret_image, oracle_mul, relerr
         from oracle import load_oracle
         orc = load_oracle()
         dev = "cuda" if gpu else "cpu"

@@ -5,13 +5,10 @@ import ctypes as C
 
 import numpy as np
 
-KEYS = ("blocks", "diagonals", "offdiagonals")
-NODEV = -2  # BSM_DEVICE_NONE
+from _common import BLOCK_KEYS as KEYS
+from _gpu import dev_copy
+
 MEM_HOST, MEM_DEVICE = 0, 1  # BSM_MEM_HOST / BSM_MEM_DEVICE
-
-
-def dev_copy(torch, b):
-    return torch.from_numpy(np.ascontiguousarray(b.T)).cuda().t()
 
 
 def src_list(p):
@@ -45,15 +42,22 @@ def new_values(p, rng):
     return out
 
 
-def raw_update(A, ids, blocks, lds, memspace, stream=None):
-    """bsm_update_blocks straight through the C ABI (1-based ids; numpy or CUDA-tensor blocks)"""
+def update_rc(A, ids, blocks, lds, memspace=MEM_HOST, stream=None, nupd=None):
+    """bsm_update_blocks straight through the C ABI (1-based ids or None; numpy or CUDA-tensor blocks; nupd: the count
+    passed in place of len(blocks)) -> its return code"""
     from bsm_amd import _lib as L
-    ids = np.ascontiguousarray(list(ids), dtype=np.int64)
+    I = C.POINTER(C.c_int64)
+    idv = None if ids is None else np.ascontiguousarray(list(ids), dtype=np.int64)
     ptrs = (C.c_void_p * max(len(blocks), 1))(*[(b.data_ptr() if hasattr(b, "data_ptr") else b.ctypes.data) for b in blocks])
     ldv = np.ascontiguousarray(lds, dtype=np.int64)
-    I = C.POINTER(C.c_int64)
-    L.check(L.lib().bsm_update_blocks(A._h.ptr, len(blocks), ids.ctypes.data_as(I), ptrs, ldv.ctypes.data_as(I), memspace,
-                                      stream))
+    return L.lib().bsm_update_blocks(A._h.ptr, len(blocks) if nupd is None else nupd,
+                                     None if idv is None else idv.ctypes.data_as(I), ptrs, ldv.ctypes.data_as(I), memspace, stream)
+
+
+def raw_update(A, ids, blocks, lds, memspace, stream=None):
+    """update_rc that raises on an error code"""
+    from bsm_amd import _lib as L
+    L.check(update_rc(A, ids, blocks, lds, memspace, stream))
 
 
 def padded(torch, b, pad, device):
@@ -63,7 +67,7 @@ def padded(torch, b, pad, device):
     a[:m] = b
     a[m:] = np.nan  # rows outside the block must never be read
     if device:
-        return torch.from_numpy(np.ascontiguousarray(a.T)).cuda().t(), m + pad
+        return dev_copy(torch, a), m + pad
     return a, m + pad
 
 

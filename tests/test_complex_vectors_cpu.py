@@ -6,9 +6,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _common import Cc, N, T
+from _common import NODEV, Cc, N, T
 
-NODEV = -2
 OK, INVALID, UNSUPPORTED, DEVICE = 0, -1, -2, -3
 
 

@@ -17,6 +17,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+from _common import BLOCK_KEYS, nblocks  # noqa: E402
 from _distworker import fuzz_problems, spawn  # noqa: E402
 from _fuzz import block_lists, partition_features, partition_rule, squared  # noqa: E402
 
@@ -28,13 +29,6 @@ COUNT = 8  # operators per spawn
 APPLICABLE = {"vbcrs": {"empty_part", "halo_above", "crossing_block", "tall", "wide"},
               "blocksparse": {"empty_part", "halo_above", "tall", "wide"},
               "symmetric": {"empty_part", "halo_below", "halo_above"}}
-_KEYS = ("blocks", "diagonals", "offdiagonals")
-
-
-def _nblocks(p):
-    return sum(len(p.get(k, ())) for k in _KEYS)
-
-
 def _rows_written(p):
     """the hulls (lo, hi) of the rows every block of p writes under op N (symmetric: of the column lists too)"""
     rh, ch, _, _ = block_lists(p)
@@ -70,8 +64,8 @@ def test_partition_and_splits_on_layout_edge_operators(kind):
                     local, o, touched = (D.split_blocksparse if kind == "blocksparse" else D.split_symmetric)(prob, r, parts)
                     assert touched == D.touched_range(local, o)
                 assert o == own[r]
-                seen += _nblocks(local)  # (every block in exactly one part: the parts' counts are those of `part`)
-                assert _nblocks(local) == int(np.sum(part == r))
+                seen += nblocks(local)  # (every block in exactly one part: the parts' counts are those of `part`)
+                assert nblocks(local) == int(np.sum(part == r))
                 lrh, lch, lkeys, _ = block_lists(local)
                 assert all(o[0] <= k <= o[1] for k, h in zip(lkeys, lrh) if h is not None), (kind, parts, r)
                 assert touched[0] <= o[0] and touched[1] >= o[1] or o[1] < o[0]
@@ -79,8 +73,8 @@ def test_partition_and_splits_on_layout_edge_operators(kind):
                     assert touched[0] <= lo and hi <= touched[1], (kind, parts, r, touched, (lo, hi))
                 # ---- split_interior -----------------------------------------------------------------------------
                 interior, boundary, bt, bx = D.split_interior(local, o)
-                assert _nblocks(interior) + _nblocks(boundary) == _nblocks(local)
-                for k in _KEYS:  # interior + boundary = local, block by block
+                assert nblocks(interior) + nblocks(boundary) == nblocks(local)
+                for k in BLOCK_KEYS:  # interior + boundary = local, block by block
                     ids = sorted(id(b) for b in local.get(k, ()))
                     assert sorted([id(b) for b in interior.get(k, ())] + [id(b) for b in boundary.get(k, ())]) == ids
                 irh, ich, _, _ = block_lists(interior)
@@ -96,7 +90,7 @@ def test_partition_and_splits_on_layout_edge_operators(kind):
                 assert bt == ((min(h[0] for h in wr), max(h[1] for h in wr)) if wr else empty)
                 assert bx == ((min(h[0] for h in rd), max(h[1] for h in rd)) if rd else empty)
                 checked += 1
-            assert seen == _nblocks(prob)
+            assert seen == nblocks(prob)
     assert checked == 12 * (2 + 3 + 5 + 8)
 
 

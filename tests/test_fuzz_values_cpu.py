@@ -6,8 +6,9 @@ export to; and the twelve operators of every (type, element type) reach every la
 import numpy as np
 import pytest
 
+from _common import NODEV
 from _fuzz import canonical, coo_triples, edge_features
-from _values import (NODEV, NOPS, SPECIAL, assert_coverage, copied, explain, image_parts, new_values, options, raw_update, seeded,
+from _values import (NOPS, SPECIAL, assert_coverage, copied, explain, image_parts, new_values, options, raw_update, seeded,
                      src_list, subset_of, value_operators, value_seed, with_values)
 
 KINDS = ["blocksparse", "vbcrs", "symmetric"]

@@ -9,7 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _common import Cc, N, T, fixture_as_blocksparse, fixture_problem, get_image, oracle_mul, rand_vec, relerr
+from _common import Cc, N, NODEV, T, fixture_as_blocksparse, fixture_problem, get_image, lens, oracle_mul, rand_vec, relerr, wrap
+from _ctors import ctor_build, ctor_oracle_problem, ctor_problem
+from _fuzz import cast_blocks
+from _gpu import dev_mat, gpu_mul, outside_bytes, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 OPS = [N, T, Cc]
@@ -17,85 +20,20 @@ PAIRS = [(np.float64, np.complex128), (np.float32, np.complex64)]
 ACCS = ["auto", "colored", "atomic", "gather"]
 CTORS = ["vbcrs", "vbcrs_from_symmetric", "blocksparse", "symmetric"]
 TOL = {np.dtype(np.complex128): 1e-13, np.dtype(np.complex64): 1e-5}
+# the generators' keywords per constructor route; FULL: C2 and C3 at full size
+SIZES = {"blocksparse": dict(n=600, nblocks=60, bs=16), "vbcrs": dict(n=4000, nblocks=200, lo=4, hi=48),
+         "symmetric": dict(nseg=16, bs=24, halfband=2), "vbcrs_from_symmetric": dict(nseg=16, bs=24, halfband=2)}
+FULL = {"vbcrs": {}, "symmetric": {}}
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    from bsm_amd import _lib as L
-    L.lib()
-    return torch
-
-
-def _cast(p, dt):
-    q = dict(p)
-    for k in ("blocks", "diagonals", "offdiagonals"):
-        if k in p:
-            q[k] = [np.asfortranarray(b.astype(dt)) for b in p[k]]
-    return q
-
-
-def _problem(bsm, ctor, dt, big=False):
-    S = bsm.synthetic
-    if ctor == "blocksparse":
-        p = S.config1(n=600, nblocks=60, bs=16)
-    elif ctor == "vbcrs":
-        p = S.config2() if big else S.config2(n=4000, nblocks=200, lo=4, hi=48)
-    else:
-        p = S.config3() if big else S.config3(nseg=16, bs=24, halfband=2)
-    return _cast(p, dt)
-
-
-def _build(bsm, ctor, p, **kw):
-    M = bsm.matrices
-    tim = kw.pop("transpose_image", False)
-    if ctor == "blocksparse":
-        return M.BlockSparseMatrix(p["blocks"], p["rowindices"], p["colindices"], p["size"], transpose_image=tim, **kw)
-    if ctor == "vbcrs":
-        return M.VariableBlockCompressedRowStorage(p["blocks"], p["rowstart"], p["colstart"], p["size"],
-                                                   transpose_image=tim, **kw)
-    if ctor == "symmetric":
-        return M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"],
-                                      p["colindices"], p["size"], **kw)
-    # a VBCRS from a SymmetricBlockMatrix (not materialised as a dense operator)
-    Sm = M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"],
-                                p["colindices"], p["size"], device=-2)
-    return M.VariableBlockCompressedRowStorage(Sm, **kw)
-
-
-def _oracle_problem(ctor, p):
+def _complex_problem(ctor, p):
     """the problem as the oracle takes it, blocks promoted to complex128"""
-    if ctor == "vbcrs_from_symmetric":  # [diagonals..., offdiagonals..., transposes...] at the FIRST list entries
-        d, o = p["diagonals"], p["offdiagonals"]
-        first = lambda lists: [int(v[0]) for v in lists]  # noqa: E731
-        rs = first(p["diagonalindices"]) + first(p["rowindices"]) + first(p["colindices"])
-        cs = first(p["diagonalindices"]) + first(p["colindices"]) + first(p["rowindices"])
-        p = dict(kind="vbcrs", blocks=list(d) + list(o) + [np.asfortranarray(b.T) for b in o],
-                 rowstart=np.array(rs, dtype=np.int64), colstart=np.array(cs, dtype=np.int64), size=p["size"])
-    return _cast(p, np.complex128)
+    return cast_blocks(ctor_oracle_problem(ctor, p), np.complex128)
 
 
 def _orc(oracle, q, op, x, y0, alpha=1, beta=0, strong=True):
     c = np.complex128
     return oracle_mul(oracle, q, op, np.asarray(x, c), np.asarray(y0, c), alpha, beta, strong)
-
-
-def _wrap(bsm, A, op):
-    return A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
-
-
-def _gpu(torch, bsm, A, op, x, y0, alpha=1, beta=0, strong=True):
-    xd = torch.from_numpy(np.array(x, copy=True)).cuda()
-    yd = torch.from_numpy(np.array(y0, copy=True)).cuda()
-    bsm.mul(yd, _wrap(bsm, A, op), xd, alpha, False if strong else beta)
-    torch.cuda.synchronize()
-    return yd.cpu().numpy()
-
-
-def _lens(p, op):
-    nr, nc = p["size"]
-    return (nc, nr) if op == N else (nr, nc)
 
 
 # (transpose_image applies to VBCRS / BlockSparseMatrix operators without symmetric pieces)
@@ -106,30 +44,30 @@ CTOR_TIMAGE = [(c, t) for c in CTORS for t in (0, 1) if t == 0 or c in ("vbcrs",
 @pytest.mark.parametrize("R_, C_", PAIRS)
 @pytest.mark.parametrize("ctor, timage", CTOR_TIMAGE)
 def test_cvec_product_matrix(torch_cuda, bsm, oracle, ctor, timage, R_, C_, acc):
-    p = _problem(bsm, ctor, R_)
-    A = _build(bsm, ctor, p, accumulate=acc, transpose_image=timage)
-    q = _oracle_problem(ctor, p)
+    p = ctor_problem(bsm, ctor, R_, SIZES)
+    A = ctor_build(bsm, ctor, p, accumulate=acc, transpose_image=timage)
+    q = _complex_problem(ctor, p)
     rng = np.random.default_rng(1)
     tol = TOL[np.dtype(C_)]
     for op in OPS:
-        xl, yl = _lens(p, op)
+        xl, yl = lens(p, op)
         x, y0 = rand_vec(rng, xl, C_), rand_vec(rng, yl, C_)
-        got = _gpu(torch_cuda, bsm, A, op, x, y0)
+        got = gpu_mul(torch_cuda, bsm, A, op, x, y0)
         assert got.dtype == np.dtype(C_)
         assert relerr(got, _orc(oracle, q, op, x, y0)) <= tol, op
-        got = _gpu(torch_cuda, bsm, A, op, x, y0, 0.5, 2.0, False)
+        got = gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.5, 2.0, False)
         assert relerr(got, _orc(oracle, q, op, x, y0, 0.5, 2.0, False)) <= tol, op
         if acc in ("colored", "gather"):  # bitwise reproducible run to run
-            a = _gpu(torch_cuda, bsm, A, op, x, y0, 0.5, 2.0, False)
+            a = gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.5, 2.0, False)
             assert a.tobytes() == got.tobytes(), op
 
 
 @pytest.mark.parametrize("R_, C_", PAIRS)
 @pytest.mark.parametrize("ctor", ["vbcrs", "symmetric"])
 def test_cvec_complex_scalars_strong_and_numeric_zero(torch_cuda, bsm, oracle, ctor, R_, C_):
-    p = _problem(bsm, ctor, R_)
-    A = _build(bsm, ctor, p)
-    q = _oracle_problem(ctor, p)
+    p = ctor_problem(bsm, ctor, R_, SIZES)
+    A = ctor_build(bsm, ctor, p)
+    q = _complex_problem(ctor, p)
     rng = np.random.default_rng(2)
     n = p["size"][0]
     tol = TOL[np.dtype(C_)]
@@ -137,18 +75,18 @@ def test_cvec_complex_scalars_strong_and_numeric_zero(torch_cuda, bsm, oracle, c
     ynan = np.full(n, np.nan, dtype=C_)
     alpha, beta = 0.5 - 0.25j, 1.5 + 0.5j
     for op in OPS:
-        got = _gpu(torch_cuda, bsm, A, op, x, ynan, alpha, 0, True)  # strong zero: the NaN must vanish
+        got = gpu_mul(torch_cuda, bsm, A, op, x, ynan, alpha, 0, True)  # strong zero: the NaN must vanish
         assert np.all(np.isfinite(got))
         assert relerr(got, _orc(oracle, q, op, x, ynan, alpha, 0, True)) <= tol
-        got = _gpu(torch_cuda, bsm, A, op, x, ynan, alpha, 0.0, False)  # numeric zero multiplies: NaN stays
+        got = gpu_mul(torch_cuda, bsm, A, op, x, ynan, alpha, 0.0, False)  # numeric zero multiplies: NaN stays
         assert np.all(np.isnan(got))
         y0 = rand_vec(rng, n, C_)
-        got = _gpu(torch_cuda, bsm, A, op, x, y0, alpha, beta, False)
+        got = gpu_mul(torch_cuda, bsm, A, op, x, y0, alpha, beta, False)
         assert relerr(got, _orc(oracle, q, op, x, y0, alpha, beta, False)) <= tol
         # MulPlan, A @ x
         xd = torch_cuda.from_numpy(x).cuda()
         yd = torch_cuda.from_numpy(y0.copy()).cuda()
-        bsm.MulPlan(yd, _wrap(bsm, A, op), xd, alpha, beta)()
+        bsm.MulPlan(yd, wrap(bsm, A, op), xd, alpha, beta)()
         torch_cuda.cuda.synchronize()
         assert relerr(yd.cpu().numpy(), got) <= tol  # (atomic paths: not bitwise run to run)
         if op == N:
@@ -161,15 +99,15 @@ def test_cvec_complex_scalars_strong_and_numeric_zero(torch_cuda, bsm, oracle, c
 def test_cvec_host_and_device_vectors_and_owned_rows(torch_cuda, bsm, oracle, R_, C_):
     torch = torch_cuda
     tol = TOL[np.dtype(C_)]
-    prob = _cast(bsm.synthetic.config2(n=4000, nblocks=150), R_)
+    prob = cast_blocks(bsm.synthetic.config2(n=4000, nblocks=150), R_)
     A = bsm.synthetic.build(prob)
-    q = _cast(prob, np.complex128)
+    q = cast_blocks(prob, np.complex128)
     rng = np.random.default_rng(3)
     for op in OPS:
         x, y0 = rand_vec(rng, 4000, C_), rand_vec(rng, 4000, C_)
         h = y0.copy()
-        bsm.mul(h, _wrap(bsm, A, op), x.copy(), 0.25 + 1j, -1.0 + 0.5j)  # host (numpy) vectors
-        d = _gpu(torch, bsm, A, op, x, y0, 0.25 + 1j, -1.0 + 0.5j, False)
+        bsm.mul(h, wrap(bsm, A, op), x.copy(), 0.25 + 1j, -1.0 + 0.5j)  # host (numpy) vectors
+        d = gpu_mul(torch, bsm, A, op, x, y0, 0.25 + 1j, -1.0 + 0.5j, False)
         assert relerr(h, _orc(oracle, q, op, x, y0, 0.25 + 1j, -1.0 + 0.5j, False)) <= tol
         assert relerr(h, d) <= tol
     # a handle that owns a row range: rows outside it come back bit-unchanged, host path and device path
@@ -180,7 +118,7 @@ def test_cvec_host_and_device_vectors_and_owned_rows(torch_cuda, bsm, oracle, R_
     hi = int(max(r + b.shape[0] - 1 for r, b in zip(sub["rowstart"], sub["blocks"])))
     Ao = bsm.synthetic.build(sub, own=(lo, hi))
     x = rand_vec(rng, 4000, C_)
-    ref = _orc(oracle, _cast(sub, np.complex128), N, x, np.zeros(4000))
+    ref = _orc(oracle, cast_blocks(sub, np.complex128), N, x, np.zeros(4000))
     for first in (3.5 - 1.25j, -7.25 + 2j):
         y = np.full(4000, first, dtype=C_)
         bsm.mul(y, Ao, x.copy())
@@ -199,7 +137,7 @@ def test_cvec_host_and_device_vectors_and_owned_rows(torch_cuda, bsm, oracle, R_
         assert Y[:lo - 1].tobytes() == np.full((lo - 1, k), first, C_).tobytes()
         assert Y[hi:].tobytes() == np.full((4000 - hi, k), first, C_).tobytes()
         for j in range(k):
-            r = _orc(oracle, _cast(sub, np.complex128), N, X[:, j], np.zeros(4000))
+            r = _orc(oracle, cast_blocks(sub, np.complex128), N, X[:, j], np.zeros(4000))
             assert relerr(Y[lo - 1:hi, j], r[lo - 1:hi]) <= tol, j
 
 
@@ -212,11 +150,11 @@ def test_cvec_golden_fixtures_real_part(torch_cuda, bsm, oracle, key, R_, C_):
     rng = np.random.default_rng(4)
     for p in (fixture_problem(key, dtype=R_, part="real"), fixture_as_blocksparse(key, dtype=R_, part="real")):
         A = bsm.synthetic.build(p)
-        q = _cast(p, np.complex128)
+        q = cast_blocks(p, np.complex128)
         for op in OPS:
-            xl, yl = _lens(p, op)
+            xl, yl = lens(p, op)
             x, y0 = rand_vec(rng, xl, C_), rand_vec(rng, yl, C_)
-            got = _gpu(torch_cuda, bsm, A, op, x, y0, 1 - 0.5j, 0.5j, False)
+            got = gpu_mul(torch_cuda, bsm, A, op, x, y0, 1 - 0.5j, 0.5j, False)
             assert relerr(got, _orc(oracle, q, op, x, y0, 1 - 0.5j, 0.5j, False)) <= tol, (p["kind"], op)
 
 
@@ -226,69 +164,57 @@ def test_cvec_lds_window_longer_than_a_complex_window(torch_cuda, bsm, oracle, R
     4 KB holds half the entries.  The operator must have windows beyond that bound, and the complex product must
     still be exact (bsm_one.hip: panel_kernel clamps the window of complex vectors under a real image)."""
     p = fixture_problem("sphere", dtype=R_, part="real")
-    twin = bsm.synthetic.build(p, device=-2)
+    twin = bsm.synthetic.build(p, device=NODEV)
     waves = get_image(twin)[3]
     bound = 4096 // np.dtype(C_).itemsize  # entries of a complex window of 4 KB: 256 complex128, 512 complex64
     assert np.any(waves["win_span8"].astype(np.int64) * 8 > bound)
     A = bsm.synthetic.build(p)
-    q = _cast(p, np.complex128)
+    q = cast_blocks(p, np.complex128)
     rng = np.random.default_rng(5)
     n = p["size"][0]
     for op in OPS:
         x, y0 = rand_vec(rng, n, C_), rand_vec(rng, n, C_)
-        got = _gpu(torch_cuda, bsm, A, op, x, y0, 0.75, -1.5j, False)
+        got = gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.75, -1.5j, False)
         assert relerr(got, _orc(oracle, q, op, x, y0, 0.75, -1.5j, False)) <= TOL[np.dtype(C_)], op
 
 
 @pytest.mark.parametrize("R_, C_", PAIRS)
 @pytest.mark.parametrize("ctor", ["vbcrs", "symmetric"])
 def test_cvec_gather_handle_is_bitwise_reproducible(torch_cuda, bsm, ctor, R_, C_):
-    p = _problem(bsm, ctor, R_)
-    A = _build(bsm, ctor, p, accumulate="gather")
+    p = ctor_problem(bsm, ctor, R_, SIZES)
+    A = ctor_build(bsm, ctor, p, accumulate="gather")
     rng = np.random.default_rng(6)
     for op in OPS:
-        xl, yl = _lens(p, op)
+        xl, yl = lens(p, op)
         x, y0 = rand_vec(rng, xl, C_), rand_vec(rng, yl, C_)
-        a = _gpu(torch_cuda, bsm, A, op, x, y0, 0.5 + 0.5j, 2.0, False)
-        b = _gpu(torch_cuda, bsm, A, op, x, y0, 0.5 + 0.5j, 2.0, False)
+        a = gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.5 + 0.5j, 2.0, False)
+        b = gpu_mul(torch_cuda, bsm, A, op, x, y0, 0.5 + 0.5j, 2.0, False)
         assert a.tobytes() == b.tobytes(), op
-
-
-def _padded(torch, rng, n, ld, k, dt, fill=None):
-    """column-major (n x k) view of a (k x ld) CUDA tensor: rows n..ld-1 of every column are NaN sentinels"""
-    base = np.full((k, ld), np.nan, dtype=dt)
-    if fill is None:
-        base[:, :n] = np.stack([rand_vec(rng, n, dt) for _ in range(k)])
-    else:
-        base[:, :n] = fill
-    t = torch.from_numpy(base).cuda()
-    return t, t[:, :n].t()
 
 
 @pytest.mark.parametrize("R_, C_", PAIRS)
 @pytest.mark.parametrize("ctor", ["vbcrs", "symmetric", "blocksparse"])
 def test_cvec_multi_rhs(torch_cuda, bsm, oracle, ctor, R_, C_):
     torch = torch_cuda
-    p = _problem(bsm, ctor, R_)
-    A = _build(bsm, ctor, p)
-    q = _oracle_problem(ctor, p)
+    p = ctor_problem(bsm, ctor, R_, SIZES)
+    A = ctor_build(bsm, ctor, p)
+    q = _complex_problem(ctor, p)
     tol = TOL[np.dtype(C_)]
     rng = np.random.default_rng(7)
     alpha, beta = 0.5 - 1j, 0.25 + 0.5j
     for op in (N, Cc):
-        xl, yl = _lens(p, op)
+        xl, yl = lens(p, op)
         for k in (1, 2, 4, 5, 8, 9, 17):
-            xb, X = _padded(torch, rng, xl, xl + 13, k, C_)
-            yb, Y = _padded(torch, rng, yl, yl + 7, k, C_)
+            xb, X = dev_mat(torch, np.stack([rand_vec(rng, xl, C_) for _ in range(k)], axis=1), 13)
+            yb, Y = dev_mat(torch, np.stack([rand_vec(rng, yl, C_) for _ in range(k)], axis=1), 7)
             X0, Y0 = X.cpu().numpy(), Y.cpu().numpy()
-            bsm.mul(Y, _wrap(bsm, A, op), X, alpha, beta)
+            bsm.mul(Y, wrap(bsm, A, op), X, alpha, beta)
             torch.cuda.synchronize()
-            full = yb.cpu().numpy()
-            assert np.all(np.isnan(full[:, yl:])), (op, k)  # the padding rows are untouched
-            assert np.all(np.isnan(xb.cpu().numpy()[:, xl:]))
+            assert np.all(np.isnan(np.frombuffer(outside_bytes(yb, yl, yl + 7, k), dtype=C_))), (op, k)  # the padding rows are untouched
+            assert np.all(np.isnan(np.frombuffer(outside_bytes(xb, xl, xl + 13, k), dtype=C_)))
             got = Y.cpu().numpy()
             for j in range(k):
-                one = _gpu(torch, bsm, A, op, X0[:, j], Y0[:, j], alpha, beta, False)
+                one = gpu_mul(torch, bsm, A, op, X0[:, j], Y0[:, j], alpha, beta, False)
                 assert relerr(got[:, j], one) <= tol, (op, k, j)
                 assert relerr(got[:, j], _orc(oracle, q, op, X0[:, j], Y0[:, j], alpha, beta, False)) <= tol, (op, k, j)
     # A @ X: a complex column-major result
@@ -300,8 +226,8 @@ def test_cvec_multi_rhs(torch_cuda, bsm, oracle, ctor, R_, C_):
 @pytest.mark.parametrize("R_, C_", PAIRS)
 def test_cvec_graph_capture(torch_cuda, bsm, R_, C_):
     torch = torch_cuda
-    p = _problem(bsm, "symmetric", R_)
-    A = _build(bsm, "symmetric", p, accumulate="colored")
+    p = ctor_problem(bsm, "symmetric", R_, SIZES)
+    A = ctor_build(bsm, "symmetric", p, accumulate="colored")
     n = p["size"][0]
     rng = np.random.default_rng(8)
     tol = TOL[np.dtype(C_)]
@@ -341,13 +267,13 @@ def test_cvec_graph_capture(torch_cuda, bsm, R_, C_):
 @pytest.mark.parametrize("ctor", ["vbcrs", "symmetric"])
 def test_cvec_full_size_c2_c3(torch_cuda, bsm, oracle, ctor):
     """C2 (VBCRS, 100 k rows) and C3 (symmetric, 200 k rows) at full size, float64 with complex128 vectors"""
-    p = _problem(bsm, ctor, np.float64, big=True)
-    A = _build(bsm, ctor, p)
-    q = _cast(p, np.complex128)
+    p = ctor_problem(bsm, ctor, np.float64, FULL)
+    A = ctor_build(bsm, ctor, p)
+    q = cast_blocks(p, np.complex128)
     rng = np.random.default_rng(9)
     x = rand_vec(rng, p["size"][1], np.complex128)
     y0 = np.full(p["size"][0], np.nan, dtype=np.complex128)
-    got = _gpu(torch_cuda, bsm, A, N, x, y0)
+    got = gpu_mul(torch_cuda, bsm, A, N, x, y0)
     assert relerr(got, _orc(oracle, q, N, x, y0)) <= 1e-13
 
 
@@ -355,12 +281,12 @@ def test_cvec_refused_on_mixed_and_multi_device_handles(torch_cuda, bsm):
     """a mixed-storage handle and a multi-device handle (a real context of two virtual devices):
     BSM_ERR_UNSUPPORTED from the C ABI, TypeError from the mirror"""
     from bsm_amd import _lib as L
-    p = _problem(bsm, "vbcrs", np.float64)
+    p = ctor_problem(bsm, "vbcrs", np.float64, SIZES)
     n = p["size"][0]
     x = torch_cuda.from_numpy(rand_vec(np.random.default_rng(10), n, np.complex128)).cuda()
     y = torch_cuda.zeros_like(x)
     one = C.c_int64(n)
-    for A in (_build(bsm, "vbcrs", p, storage=np.float32), _build(bsm, "vbcrs", p, devices=[0, 0])):
+    for A in (ctor_build(bsm, "vbcrs", p, storage=np.float32), ctor_build(bsm, "vbcrs", p, devices=[0, 0])):
         assert L.lib().bsm_mul_cvec(A._h.ptr, N, x.data_ptr(), y.data_ptr(), None, None, 1, 1, None) == -2
         assert L.lib().bsm_mul_multi_cvec(A._h.ptr, N, 1, x.data_ptr(), one, y.data_ptr(), one, None, None, 1, 1,
                                           None) == -2

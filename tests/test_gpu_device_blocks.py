@@ -5,34 +5,20 @@ synthetic configs (include/bsm_synth.h), which must reproduce the numpy streams 
 import numpy as np
 import pytest
 
-from _common import N, T, oracle_mul, rand_vec, relerr, sampled_relerr
+from _common import BLOCK_KEYS, N, T, oracle_mul, relerr, sampled_relerr
+from _gpu import dev_copy, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    from bsm_amd import _lib as L
-    L.lib()
-    return torch
 
 
 def to_host(prob):
     """host copy (numpy, column-major) of a problem generated in HBM"""
     out = dict(prob)
-    for key in ("blocks", "diagonals", "offdiagonals"):
+    for key in BLOCK_KEYS:
         if key in prob:
             out[key] = [np.asfortranarray(b.cpu().numpy()) for b in prob[key]]
     out["x"] = prob["x"].cpu().numpy()
     return out
-
-
-def dev_copy(torch, b):
-    """column-major CUDA copy of a numpy block"""
-    t = torch.from_numpy(np.ascontiguousarray(b.T)).cuda()  # (n, m) row-major == (m, n) column-major
-    return t.t()
 
 
 def test_generator_in_hbm_is_bit_identical_to_the_numpy_streams(torch_cuda, bsm):
@@ -54,7 +40,7 @@ def test_generator_in_hbm_is_bit_identical_to_the_numpy_streams(torch_cuda, bsm)
                       (S.config3(nseg=12, bs=16, halfband=3), S.config3(nseg=12, bs=16, halfband=3, on_device=True)),
                       (S.config4(ngrid=12, bs=16, per_row=4), S.config4(ngrid=12, bs=16, per_row=4, on_device=True))):
         h = to_host(dev)
-        for key in ("blocks", "diagonals", "offdiagonals"):
+        for key in BLOCK_KEYS:
             if key in host:
                 assert len(host[key]) == len(h[key])
                 assert all(np.array_equal(a, b) for a, b in zip(host[key], h[key])), key

@@ -5,22 +5,17 @@ creates its own single-device handle through the C ABI (own = the rows it touche
 bsm_partition_rows), multiplies on the GPU, exchanges the halo / reduce-scatters / all-gathers, and
 rank 0 compares the assembled result with the CPU oracle on the WHOLE operator."""
 import os
-import socket
 import sys
 
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+from _distworker import free_port  # noqa: E402
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+pytestmark = pytest.mark.gpu
 
 
 def _worker(rank, world, port, kind, q):
@@ -165,7 +160,7 @@ def test_row_partitioned_with_the_hip_local_product(kind, world):
     import torch.multiprocessing as mp
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, kind, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -241,7 +236,7 @@ def test_rccl_executes_every_collective_branch_on_one_rank():
     import _loopback
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=_loopback.run, args=("nccl", _free_port(), q))
+    p = ctx.Process(target=_loopback.run, args=("nccl", free_port(), q))
     p.start()
     status, res, extra = q.get(timeout=500)
     p.join(timeout=120)

@@ -3,23 +3,11 @@ mode, HIP path through the C ABI against the CPU oracle."""
 import numpy as np
 import pytest
 
-from _common import Cc, N, T, oracle_mul, rand_vec
-from _fuzz import GEN, seed_of
+from _common import Cc, N, T, acc_modes, lens, oracle_mul, rand_vec, wrap
+from _fuzz import GEN, fuzz_err, seed_of
+from _gpu import TOL, env, gpu_mul  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12,
-       np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-5}
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    assert torch.cuda.is_available()
-    import bsm_amd as bsm
-    from bsm_amd import _lib as L
-    from oracle import load_oracle
-    L.lib()
-    return torch, bsm, load_oracle()
 
 
 @pytest.mark.parametrize("kind", ["blocksparse", "vbcrs", "symmetric"])
@@ -30,9 +18,7 @@ def test_random_operators_match_the_oracle(env, kind, dtype):
     rng = np.random.default_rng(seed_of(kind, dtype))
     for case in range(30):
         p = GEN[kind](rng, dtype)
-        modes = ["auto", "atomic", "gather"]
-        if kind != "vbcrs":
-            modes.append("colored")
+        modes = acc_modes(kind)
         acc = modes[case % len(modes)]
         kw = {"accumulate": acc}
         if kind != "symmetric" and case % 3 == 0:
@@ -42,20 +28,15 @@ def test_random_operators_match_the_oracle(env, kind, dtype):
         except RuntimeError as e:  # coloured mode refuses repeated indices inside a row set: documented
             assert acc == "colored" and "repeat" in str(e), (kind, dtype, case, str(e))
             continue
-        nr, nc = p["size"]
         for op in (N, T, Cc):
             if op == Cc and dtype.kind != "c":
                 continue
-            xl, yl = (nc, nr) if op == N else (nr, nc)
+            xl, yl = lens(p, op)
             x, y0 = rand_vec(rng, xl, dtype), rand_vec(rng, yl, dtype)
             for alpha, beta, strong in ((1, 0, True), (-0.5, 1.25, False)):
                 ref = oracle_mul(oracle, p, op, x, y0, alpha, beta, strong)
-                Aop = A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
-                yd = torch.from_numpy(y0.copy()).cuda()
-                bsm.mul(yd, Aop, torch.from_numpy(x).cuda(), alpha, False if strong else beta)
-                got = yd.cpu().numpy()
-                scale = max(np.max(np.abs(ref)), 1e-30)
-                assert np.max(np.abs(got - ref)) / scale < TOL[dtype], (kind, dtype, case, acc, op, alpha, beta)
+                got = gpu_mul(torch, bsm, A, op, x, y0, alpha, beta, strong)
+                assert fuzz_err(got, ref) < TOL[dtype], (kind, dtype, case, acc, op, alpha, beta)
             if case % 2 == 1:  # A*X with a column-major matrix (bsm_mul_multi): passes of 8, padded remainders
                 k = int(rng.integers(2, 18))
                 X = np.asfortranarray(np.stack([rand_vec(rng, xl, dtype) for _ in range(k)], axis=1))
@@ -63,12 +44,11 @@ def test_random_operators_match_the_oracle(env, kind, dtype):
                 Yd = torch.from_numpy(Y0.T.copy()).cuda().T  # column-major device matrix
                 # (complex scalars for the complex types: the ComplexF64 8-column pass folds alpha into its x rows)
                 am, bm = (-0.5 + 0.75j, 1.25 - 0.5j) if dtype.kind == "c" else (-0.5, 1.25)
-                bsm.mul(Yd, Aop, torch.from_numpy(X.T.copy()).cuda().T, am, bm)
+                bsm.mul(Yd, wrap(bsm, A, op), torch.from_numpy(X.T.copy()).cuda().T, am, bm)
                 got = Yd.cpu().numpy()
                 for j in range(k):
                     ref = oracle_mul(oracle, p, op, X[:, j].copy(), Y0[:, j].copy(), am, bm, False)
-                    scale = max(np.max(np.abs(ref)), 1e-30)
-                    assert np.max(np.abs(got[:, j] - ref)) / scale < TOL[dtype], (kind, dtype, case, acc, op, "multi", j)
+                    assert fuzz_err(got[:, j], ref) < TOL[dtype], (kind, dtype, case, acc, op, "multi", j)
 
 
 @pytest.mark.parametrize("env_extra", [{"BSM_MULTI_IL": "2"}, {"BSM_MULTI_IL": "2", "BSM_IL_XCD": "5"},

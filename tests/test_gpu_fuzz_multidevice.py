@@ -17,13 +17,13 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
 
-from _common import Cc, N, T, oracle_mul, rand_vec  # noqa: E402
-from _fuzz import build_fuzz, seed_of, squared  # noqa: E402
+from _common import Cc, N, T, acc_modes, lens, nblocks, oracle_mul, rand_vec, wrap  # noqa: E402
+from _fuzz import Stat, build_fuzz, scalar_sets, seed_of, squared  # noqa: E402
+from _gpu import TOL, dev_mat, env, gpu_mul, outside_bytes, scatter  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 KINDS = ["blocksparse", "vbcrs", "symmetric"]
 DTYPES = [np.float64, np.complex128, np.float32, np.complex64]
-TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12, np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-5}
 PS = (2, 3, 5)
 KS = (3, 8, 11, 17, 20)  # the 8-column batches, a remainder, more than the copy path's 16
 OPS = (N, T, Cc)
@@ -33,62 +33,16 @@ def _did(dt):
     return np.dtype(dt).name
 
 
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    import bsm_amd as bsm
-    from bsm_amd import _lib as L
-    from oracle import load_oracle
-    L.lib()
-    return torch, bsm, load_oracle()
+def _distdev(st, need_empty=False):
+    st.done("DISTDEV", f"products {st.products} operators {st.cases} parts_without_blocks {st.empty_parts}")
+    if need_empty:
+        assert st.empty_parts > 0, (st.tag, "no part without blocks in the whole run")
 
 
-def _err(got, ref):
-    return float(np.max(np.abs(got - ref)) / max(np.max(np.abs(ref)), 1e-30)) if len(ref) else 0.0
-
-
-def _wrap(bsm, A, op):
-    return A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
-
-
-def _modes(kind):
-    return ["auto", "atomic", "gather"] + (["colored"] if kind != "vbcrs" else [])
-
-
-def _scalar_sets(dt):
-    s = [(1, 0, True), (-0.5, 1.25, False)]
-    return s + [(0.5 - 0.25j, 1.5 + 0.5j, False)] if np.dtype(dt).kind == "c" else s
-
-
-def _lens(p, op):
-    nr, nc = p["size"]
-    return (nc, nr) if op == N else (nr, nc)
-
-
-class Stat:
-    def __init__(self, name, kind, dt):
-        self.tag = (name, kind, _did(dt))
-        self.worst, self.products, self.empty_parts, self.coloured, self.ran, self.cases = 0.0, 0, 0, 0, 0, 0
-
-    def check(self, got, ref, tol, what):
-        e = _err(got, ref)
-        print(f"  {self.tag} {what}: {e:.3e}")
-        self.worst = max(self.worst, e) if e == e else float("nan")
-        assert e < tol, (self.tag, what, e)
-
-    def done(self, need_empty=False):
-        print("DISTDEV {} {} {} worst {:.3e} products {} operators {} parts_without_blocks {} coloured {} of {}".format(
-            *self.tag, self.worst, self.products, self.cases, self.empty_parts, self.ran, self.coloured))
-        assert 2 * self.ran >= self.coloured, (self.tag, self.ran, self.coloured)
-        if need_empty:
-            assert self.empty_parts > 0, (self.tag, "no part without blocks in the whole run")
-
-
-def _cases(bsm, st, kind, dt, count, offset, modes=None, square_every=0):
+def _device_cases(bsm, st, kind, dt, count, offset, modes=None, square_every=0):
     """`count` operators of GEN[kind] over P = 2, 3, 5 virtual devices, modes cycled -> (case, acc, P, problem, handle);
     square_every = k: every k-th operator widened to square (_fuzz.squared) before the handle is built"""
-    modes = modes or _modes(kind)
+    modes = modes or acc_modes(kind)
     rng = np.random.default_rng(seed_of(kind, dt) + offset)
     for case in range(count):
         acc, P = modes[case % len(modes)], PS[case % len(PS)]
@@ -103,10 +57,6 @@ def _cases(bsm, st, kind, dt, count, offset, modes=None, square_every=0):
         st.cases += 1
         st.empty_parts += sum(q["nblocks"] == 0 for q in A.parts())
         yield case, acc, P, p, A, rng
-
-
-def _nblocks(p):
-    return sum(len(p.get(k, ())) for k in ("blocks", "diagonals", "offdiagonals"))
 
 
 def _check_parts(p, A, P):
@@ -129,20 +79,8 @@ def _check_parts(p, A, P):
     for q in parts:
         if q["own"][1] >= q["own"][0] and q["touched"][1] >= q["touched"][0]:
             assert q["touched"][0] <= q["own"][0] and q["touched"][1] >= q["own"][1], q
-    assert sum(q["nblocks"] for q in parts) == _nblocks(p)
+    assert sum(q["nblocks"] for q in parts) == nblocks(p)
     return parts
-
-
-def _tdt(torch, dt):
-    return torch.from_numpy(np.zeros(1, dtype=dt)).dtype
-
-
-def _mat(torch, M, pad):
-    """M as a column-major device view with leading dimension rows + pad, NaN in the pad rows -> (buffer, view)"""
-    n, k = M.shape
-    buf = torch.full((k, n + pad), float("nan"), dtype=_tdt(torch, M.dtype), device="cuda")
-    buf[:, :n] = torch.from_numpy(np.ascontiguousarray(M.T)).cuda()
-    return buf, buf[:, :n].t()
 
 
 def _one(torch, bsm, oracle, st, p, A, op, x, yin, y0, alpha, beta, strong, where, tol, what):
@@ -150,11 +88,9 @@ def _one(torch, bsm, oracle, st, p, A, op, x, yin, y0, alpha, beta, strong, wher
     ref = oracle_mul(oracle, p, op, x, y0, alpha, beta, strong)
     if where == "host":
         got = np.array(yin, copy=True)
-        bsm.mul(got, _wrap(bsm, A, op), x, alpha, False if strong else beta)
+        bsm.mul(got, wrap(bsm, A, op), x, alpha, False if strong else beta)
     else:
-        yd = torch.from_numpy(np.array(yin, copy=True)).cuda()
-        bsm.mul(yd, _wrap(bsm, A, op), torch.from_numpy(x).cuda(), alpha, False if strong else beta)
-        got = yd.cpu().numpy()
+        got = gpu_mul(torch, bsm, A, op, x, yin, alpha, beta, strong)
     st.products += 1
     if strong:
         assert np.all(np.isfinite(got)), (st.tag, what, where, "the strong zero left a NaN")
@@ -167,28 +103,28 @@ def _one(torch, bsm, oracle, st, p, A, op, x, yin, y0, alpha, beta, strong, wher
 def test_parts_and_products(env, kind, dt):
     torch, bsm, oracle = env
     dt = np.dtype(dt)
-    st = Stat("mul", kind, dt)
-    for case, acc, P, p, A, rng in _cases(bsm, st, kind, dt, 10, 1000):
+    st = Stat("mul", kind, _did(dt))
+    for case, acc, P, p, A, rng in _device_cases(bsm, st, kind, dt, 10, 1000):
         _check_parts(p, A, P)
         for op in OPS:
-            xl, yl = _lens(p, op)
+            xl, yl = lens(p, op)
             x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
             ynan = y0.copy()
             ynan[::7] = np.nan
-            for alpha, beta, strong in _scalar_sets(dt):
+            for alpha, beta, strong in scalar_sets(dt):
                 for where in ("host", "device"):
                     _one(torch, bsm, oracle, st, p, A, op, x, ynan if strong else y0, y0, alpha, beta, strong, where, TOL[dt],
                          (case, acc, P, op, alpha, beta))
-    st.done(need_empty=True)
+    _distdev(st, need_empty=True)
 
 
 # ---- 2. several right-hand sides ----------------------------------------------------------------------------------------
-def _multi(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=OPS):
+def _several(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=OPS):
     from bsm_amd import _lib as L
     tol = TOL[dt]
     am, bm = (-0.5 + 0.75j, 1.25 - 0.5j) if dt.kind == "c" else (-0.5, 1.25)
     for op in ops:
-        xl, yl = _lens(p, op)
+        xl, yl = lens(p, op)
         k = int(rng.choice(KS))
         strong = bool(rng.integers(0, 2))
         padx, pady = 2 * int(rng.integers(0, 5)) + 1, 2 * int(rng.integers(0, 5)) + 1
@@ -198,13 +134,13 @@ def _multi(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=OPS):
                 for j in range(k)]
         what = (case, acc, P, op, k, "strong" if strong else "beta")
         # device memory, padded leading dimensions through bsm.mul
-        xb, Xd = _mat(torch, X, padx)
-        yb, Yd = _mat(torch, Y0, pady)
-        pads = yb[:, yl:].cpu().numpy().tobytes()
-        bsm.mul(Yd, _wrap(bsm, A, op), Xd, am, False if strong else bm)
+        xb, Xd = dev_mat(torch, X, padx)
+        yb, Yd = dev_mat(torch, Y0, pady)
+        pads = outside_bytes(yb, yl, yl + pady, k)
+        bsm.mul(Yd, wrap(bsm, A, op), Xd, am, False if strong else bm)
         torch.cuda.synchronize()
         st.products += 1
-        assert yb[:, yl:].cpu().numpy().tobytes() == pads and np.all(np.isnan(np.frombuffer(pads, dtype=dt))), \
+        assert outside_bytes(yb, yl, yl + pady, k) == pads and np.all(np.isnan(np.frombuffer(pads, dtype=dt))), \
             (st.tag, what, "pad rows of Y written")
         assert bool(torch.equal(Xd.cpu(), torch.from_numpy(X))), (st.tag, what, "X written")
         got = Yd.cpu().numpy()
@@ -229,17 +165,13 @@ def _multi(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=OPS):
 def test_several_columns(env, kind, dt):
     torch, bsm, oracle = env
     dt = np.dtype(dt)
-    st = Stat("multi", kind, dt)
-    for case, acc, P, p, A, rng in _cases(bsm, st, kind, dt, 10, 2000):
-        _multi(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt)
-    st.done()
+    st = Stat("multi", kind, _did(dt))
+    for case, acc, P, p, A, rng in _device_cases(bsm, st, kind, dt, 10, 2000):
+        _several(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt)
+    _distdev(st)
 
 
 # ---- 3. partitioned vectors: bsm.mul_parts ------------------------------------------------------------------------------
-def _scatter(torch, v, ranges):
-    return [torch.from_numpy(np.ascontiguousarray(v[lo - 1:hi])).cuda() if hi >= lo else None for lo, hi in ranges]
-
-
 def _gathered(parts_t, ranges, n, dt):
     got = np.full(n, np.nan, dtype=dt)
     for (lo, hi), t in zip(ranges, parts_t):
@@ -253,8 +185,8 @@ def _parts_product(torch, bsm, oracle, st, p, A, op, x, yin, y0, alpha, beta, st
     rows, cols = [q["own"] for q in parts], [q["cols"] for q in parts]
     xr, yr = (cols, rows) if op == N else (rows, cols)
     ref = oracle_mul(oracle, p, op, x, y0, alpha, beta, strong)
-    xp, yp = _scatter(torch, x, xr), _scatter(torch, yin, yr)
-    bsm.mul_parts(yp, _wrap(bsm, A, op), xp, alpha, False if strong else beta)
+    xp, yp = scatter(torch, x, xr), scatter(torch, yin, yr)
+    bsm.mul_parts(yp, wrap(bsm, A, op), xp, alpha, False if strong else beta)
     torch.cuda.synchronize()
     st.products += 1
     st.check(_gathered(yp, yr, len(y0), y0.dtype), ref, tol, what + ("parts",))
@@ -268,24 +200,24 @@ def test_partitioned_vectors(env, kind, dt):
     real operators the y parts of one product are the x parts of the next"""
     torch, bsm, oracle = env
     dt = np.dtype(dt)
-    st = Stat("parts", kind, dt)
+    st = Stat("parts", kind, _did(dt))
     rect = chained = 0
-    for case, acc, P, p, A, rng in _cases(bsm, st, kind, dt, 10, 3000, square_every=3):
+    for case, acc, P, p, A, rng in _device_cases(bsm, st, kind, dt, 10, 3000, square_every=3):
         parts = _check_parts(p, A, P)
         nr, nc = p["size"]
         rect += nr != nc
         for op in OPS:
-            xl, yl = _lens(p, op)
+            xl, yl = lens(p, op)
             x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
             ynan = y0.copy()
             ynan[::7] = np.nan
-            for alpha, beta, strong in _scalar_sets(dt):
+            for alpha, beta, strong in scalar_sets(dt):
                 for rep in range(2):
                     _parts_product(torch, bsm, oracle, st, p, A, op, x, ynan if strong else y0, y0, alpha, beta, strong,
                                    TOL[dt], (case, acc, P, op, alpha, beta, rep))
         if nr == nc and dt.kind != "c":
             x = rand_vec(rng, nc, dt)
-            xp = _scatter(torch, x, [q["cols"] for q in parts])
+            xp = scatter(torch, x, [q["cols"] for q in parts])
             y1 = [torch.full_like(t, float("nan")) if t is not None else None for t in xp]
             y2 = [torch.full_like(t, float("nan")) if t is not None else None for t in xp]
             bsm.mul_parts(y1, A, xp)
@@ -298,7 +230,7 @@ def test_partitioned_vectors(env, kind, dt):
             st.check(_gathered(y2, [q["own"] for q in parts], nr, dt), oracle_mul(oracle, p, N, mid, np.zeros(nr, dtype=dt)),
                      TOL[dt], (case, acc, P, "chain 2"))
             chained += 1
-    st.done()
+    _distdev(st)
     assert chained > 0 or dt.kind == "c"
     assert rect > 0 or kind == "symmetric"
 
@@ -312,25 +244,25 @@ def test_copy_path(env, kind, dt, monkeypatch):
     torch, bsm, oracle = env
     monkeypatch.setenv("BSM_DIST_COPIES", "1")
     dt = np.dtype(dt)
-    st = Stat("copies", kind, dt)
-    for case, acc, P, p, A, rng in _cases(bsm, st, kind, dt, 5, 4000):
+    st = Stat("copies", kind, _did(dt))
+    for case, acc, P, p, A, rng in _device_cases(bsm, st, kind, dt, 5, 4000):
         for op in OPS:
-            xl, yl = _lens(p, op)
+            xl, yl = lens(p, op)
             x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
             ynan = y0.copy()
             ynan[::7] = np.nan
-            for alpha, beta, strong in _scalar_sets(dt)[-2:]:
+            for alpha, beta, strong in scalar_sets(dt)[-2:]:
                 for where in ("host", "device"):
                     _one(torch, bsm, oracle, st, p, A, op, x, ynan if strong else y0, y0, alpha, beta, strong, where, TOL[dt],
                          (case, acc, P, op, alpha, beta))
-        _multi(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=(OPS[case % 3], OPS[(case + 1) % 3]))
+        _several(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=(OPS[case % 3], OPS[(case + 1) % 3]))
         if case == 0:
             parts = A.parts()
-            xp = _scatter(torch, rand_vec(rng, p["size"][1], dt), [q["cols"] for q in parts])
-            yp = _scatter(torch, rand_vec(rng, p["size"][0], dt), [q["own"] for q in parts])
+            xp = scatter(torch, rand_vec(rng, p["size"][1], dt), [q["cols"] for q in parts])
+            yp = scatter(torch, rand_vec(rng, p["size"][0], dt), [q["own"] for q in parts])
             with pytest.raises(RuntimeError, match="peer access"):
                 bsm.mul_parts(yp, A, xp)
-    st.done()
+    _distdev(st)
 
 
 # ---- 5. the switches of the fused path ---------------------------------------------------------------------------------
@@ -345,27 +277,27 @@ def test_fused_path_switches(env, kind, switch, monkeypatch):
     monkeypatch.setenv("BSM_DIST_ONE_STREAM", "1" if switch == "one_stream" else "0")
     monkeypatch.setenv("BSM_DIST_REZERO", "0" if switch == "rezero_off" else "1")
     for dt in (np.dtype(np.float64),):
-        st = Stat(switch, kind, dt)
-        for case, acc, P, p, A, rng in _cases(bsm, st, kind, dt, 3, 5000, modes=["auto", "atomic", "gather"]):
+        st = Stat(switch, kind, _did(dt))
+        for case, acc, P, p, A, rng in _device_cases(bsm, st, kind, dt, 3, 5000, modes=["auto", "atomic", "gather"]):
             pending = []
             for op in (N, T, N, T):
-                xl, yl = _lens(p, op)
+                xl, yl = lens(p, op)
                 x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
                 y0[::5] = np.nan
                 yd = torch.from_numpy(y0.copy()).cuda()
-                bsm.mul(yd, _wrap(bsm, A, op), torch.from_numpy(x).cuda())  # no synchronisation in between
+                bsm.mul(yd, wrap(bsm, A, op), torch.from_numpy(x).cuda())  # no synchronisation in between
                 pending.append((op, x, y0, yd))
             x = rand_vec(rng, p["size"][1], dt)
             y0 = rand_vec(rng, p["size"][0], dt)
             _parts_product(torch, bsm, oracle, st, p, A, N, x, y0, y0, 0.75, -1.5, False, TOL[dt], (case, acc, P, switch))
             _one(torch, bsm, oracle, st, p, A, T, pending[1][1], pending[1][2], np.nan_to_num(pending[1][2]), 1, 0, True,
                  "host", TOL[dt], (case, acc, P, switch))
-            _multi(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=(N,))
+            _several(torch, bsm, oracle, st, case, acc, P, p, A, rng, dt, ops=(N,))
             torch.cuda.synchronize()
             for i, (op, x, y0, yd) in enumerate(pending):
                 st.products += 1
                 st.check(yd.cpu().numpy(), oracle_mul(oracle, p, op, x, y0, 1, 0, True), TOL[dt], (case, acc, P, switch, i))
-        st.done()
+        _distdev(st)
 
 
 # ---- 6. stale state on one handle ------------------------------------------------------------------------------------
@@ -378,15 +310,15 @@ def test_products_in_random_order_on_one_handle(env, kind, dt):
     torch, bsm, oracle = env
     dt = np.dtype(dt)
     tol = TOL[dt]
-    st = Stat("order", kind, dt)
+    st = Stat("order", kind, _did(dt))
     am, bm = (-0.5 + 0.75j, 1.25 - 0.5j) if dt.kind == "c" else (-0.5, 1.25)
-    for case, acc, P, p, A, rng in _cases(bsm, st, kind, dt, 6, 6000):
+    for case, acc, P, p, A, rng in _device_cases(bsm, st, kind, dt, 6, 6000):
         for step in range(12):
             op = OPS[int(rng.integers(0, 3))]
             k = int(rng.choice((1, 5, 11)))
             where = ("host", "device", "parts")[int(rng.integers(0, 3))]
             strong = bool(rng.integers(0, 2))
-            xl, yl = _lens(p, op)
+            xl, yl = lens(p, op)
             what = (case, acc, P, step, op, k, where, "strong" if strong else "beta")
             if where == "parts" or k == 1:
                 x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
@@ -402,13 +334,13 @@ def test_products_in_random_order_on_one_handle(env, kind, dt):
             Y0 = np.asfortranarray(np.stack([rand_vec(rng, yl, dt) for _ in range(k)], axis=1))
             if where == "host":
                 got = Y0.copy(order="F")
-                bsm.mul(got, _wrap(bsm, A, op), X, am, False if strong else bm)
+                bsm.mul(got, wrap(bsm, A, op), X, am, False if strong else bm)
             else:
-                yb, Yd = _mat(torch, Y0, 3)
-                bsm.mul(Yd, _wrap(bsm, A, op), _mat(torch, X, 1)[1], am, False if strong else bm)
+                yb, Yd = dev_mat(torch, Y0, 3)
+                bsm.mul(Yd, wrap(bsm, A, op), dev_mat(torch, X, 1)[1], am, False if strong else bm)
                 got = Yd.cpu().numpy()
             st.products += 1
             for j in range(k):
                 ref = oracle_mul(oracle, p, op, np.ascontiguousarray(X[:, j]), np.ascontiguousarray(Y0[:, j]), am, bm, strong)
                 st.check(got[:, j], ref, tol, what + (j,))
-    st.done()
+    _distdev(st)

@@ -22,14 +22,14 @@ ROOT = os.path.dirname(HERE)
 if __name__ == "__main__":  # the child process of test_several_columns_under_the_plan_switches
     sys.path[:0] = [ROOT, HERE]
 
-from _common import Cc, N, T, oracle_mul, rand_vec  # noqa: E402
-from _fuzz import CROSS_PAIRS, GEN, build_fuzz, cast_blocks, restrict_rows, rounded, seed_of  # noqa: E402
+from _common import BLOCK_KEYS, Cc, N, T, acc_modes, lens, oracle_mul, rand_vec, wrap  # noqa: E402
+from _fuzz import CROSS_PAIRS, GEN, Stat, build_fuzz, cast_blocks, restrict_rows, rounded, scalar_sets, seed_of  # noqa: E402
+from _gpu import TOL, dev_mat, dev_vec, env, gpu_mul, outside_bytes  # noqa: E402, F401
 
 pytestmark = pytest.mark.gpu
 KINDS = ["blocksparse", "vbcrs", "symmetric"]
 SAME_PAIRS = [(t, t, None) for t in (np.float32, np.float64, np.complex64, np.complex128)]
 KS = (2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 24, 35)
-TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12, np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-5}
 
 
 def _pid(pair):
@@ -39,21 +39,6 @@ def _pid(pair):
 def _seed(kind, pair, offset):
     """seed_of plus a fixed offset per test and pair (two cross pairs share a block type)"""
     return seed_of(kind, pair[0]) + offset + 100 * (CROSS_PAIRS + SAME_PAIRS).index(pair)
-
-
-@pytest.fixture(scope="module")
-def env():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    import bsm_amd as bsm
-    from bsm_amd import _lib as L
-    from oracle import load_oracle
-    L.lib()
-    return torch, bsm, load_oracle()
-
-
-def _modes(kind):
-    return ["auto", "atomic", "gather"] + (["colored"] if kind != "vbcrs" else [])
 
 
 def _storage_kw(pair):
@@ -73,44 +58,6 @@ def _ref(oracle, q, pair, op, x, y0, alpha, beta, strong):
         x, y0 = np.asarray(x, np.complex128), np.asarray(y0, np.complex128)
         op = T if op == Cc else op
     return oracle_mul(oracle, q, op, np.ascontiguousarray(x), np.ascontiguousarray(y0), alpha, beta, strong)
-
-
-def _err(got, ref):
-    return float(np.max(np.abs(got - ref)) / max(np.max(np.abs(ref)), 1e-30)) if len(ref) else 0.0
-
-
-def _wrap(bsm, A, op):
-    return A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
-
-
-def _tdt(torch, dt):
-    return torch.from_numpy(np.zeros(1, dtype=dt)).dtype
-
-
-def _vec(torch, v, off=0, guard=0):
-    """v as a contiguous view `off` elements into a NaN-filled device buffer with `guard` elements behind -> (buffer, view)"""
-    buf = torch.full((off + len(v) + guard,), float("nan"), dtype=_tdt(torch, v.dtype), device="cuda")
-    buf[off:off + len(v)] = torch.from_numpy(np.ascontiguousarray(v)).cuda()
-    return buf, buf[off:off + len(v)]
-
-
-def _mat(torch, M, pad, off=0, guard=0):
-    """M as a column-major view with leading dimension rows + pad, `off` elements into a NaN-filled buffer"""
-    n, k = M.shape
-    ld = n + pad
-    buf = torch.full((off + k * ld + guard,), float("nan"), dtype=_tdt(torch, M.dtype), device="cuda")
-    body = buf[off:off + k * ld].view(k, ld)
-    body[:, :n] = torch.from_numpy(np.ascontiguousarray(M.T)).cuda()
-    return buf, body[:, :n].t()
-
-
-def _outside(buf, off, n, ld, k):
-    """the bytes of a buffer outside the n x k matrix (leading dimension ld) that starts `off` elements into it"""
-    a = buf.cpu().numpy()
-    keep = np.ones(len(a), dtype=bool)
-    for j in range(k):
-        keep[off + j * ld:off + j * ld + n] = False
-    return a[keep].tobytes()
 
 
 def _has_off(p):
@@ -140,26 +87,13 @@ def _passes(K, pair, has_off, colored):
     return n + left
 
 
-class Stat:
-    def __init__(self, name, kind, pair):
-        self.tag, self.worst, self.products, self.columns, self.coloured, self.ran = (name, kind, _pid(pair)), 0.0, 0, 0, 0, 0
-
-    def check(self, got, ref, tol, what, columns=1):
-        e = _err(got, ref)
-        print(f"  {self.tag} {what}: {e:.3e}")
-        self.worst = max(self.worst, e) if e == e else float("nan")
-        self.columns += columns
-        assert e < tol, (self.tag, what, e)
-
-    def done(self):
-        print("PAIRSTAT {} {} {} worst {:.3e} products {} columns {} coloured {} of {}".format(
-            *self.tag, self.worst, self.products, self.columns, self.ran, self.coloured))
-        assert 2 * self.ran >= self.coloured, (self.tag, self.ran, self.coloured)
+def _pairstat(st):
+    st.done("PAIRSTAT", f"products {st.products} columns {st.columns}")
 
 
 def _cases(bsm, st, rng, kind, pair, count, modes=None):
     """`count` operators of GEN[kind], modes cycled, transpose_image every third case -> (case, acc, problem, handle)"""
-    modes = modes or _modes(kind)
+    modes = modes or acc_modes(kind)
     for case in range(count):
         acc = modes[case % len(modes)]
         kw = _storage_kw(pair)
@@ -173,11 +107,6 @@ def _cases(bsm, st, rng, kind, pair, count, modes=None):
         yield case, acc, p, A
 
 
-def _scalar_sets(V):
-    s = [(1, 0, True), (-0.5, 1.25, False)]
-    return s + [(0.5 - 0.25j, 1.5 + 0.5j, False)] if np.dtype(V).kind == "c" else s
-
-
 # ---- 1. one column ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("pair", CROSS_PAIRS, ids=_pid)
@@ -185,38 +114,32 @@ def test_one_column(env, kind, pair):
     torch, bsm, oracle = env
     V = np.dtype(pair[1])
     tol = TOL[V]
-    st = Stat("one", kind, pair)
+    st = Stat("one", kind, _pid(pair))
     rng = np.random.default_rng(_seed(kind, pair, 1000))
     for case, acc, p, A in _cases(bsm, st, rng, kind, pair, 24):
         q = _oracle_problem(p, pair)
-        nr, nc = p["size"]
         for op in (N, T, Cc):
-            xl, yl = (nc, nr) if op == N else (nr, nc)
+            xl, yl = lens(p, op)
             x, y0 = rand_vec(rng, xl, V), rand_vec(rng, yl, V)
             ynan = y0.copy()
             ynan[::7] = np.nan
-            xd = torch.from_numpy(x).cuda()
-            for alpha, beta, strong in _scalar_sets(V):
+            for alpha, beta, strong in scalar_sets(V):
                 # strong zero: the NaN of the incoming y must vanish
-                yd = torch.from_numpy(ynan if strong else y0.copy()).cuda()
-                bsm.mul(yd, _wrap(bsm, A, op), xd, alpha, False if strong else beta)
-                got = yd.cpu().numpy()
+                got = gpu_mul(torch, bsm, A, op, x, ynan if strong else y0, alpha, beta, strong)
                 st.products += 1
                 if strong:
                     assert np.all(np.isfinite(got)), (st.tag, case, acc, op, "strong zero left a NaN")
                 ref = _ref(oracle, q, pair, op, x, y0, alpha, beta, strong)
                 st.check(got, ref, tol, (case, acc, op, alpha, beta))
             # a numeric zero multiplies: the NaN stays, every other entry is alpha * op(A) * x
-            yd = torch.from_numpy(ynan).cuda()
-            bsm.mul(yd, _wrap(bsm, A, op), xd, -0.5, 0.0)
-            got = yd.cpu().numpy()
+            got = gpu_mul(torch, bsm, A, op, x, ynan, -0.5, 0.0, False)
             st.products += 1
             assert np.all(np.isnan(got[::7])), (st.tag, case, acc, op, "numeric beta = 0 dropped a NaN")
             ref = _ref(oracle, q, pair, op, x, y0, -0.5, 0, True)
             keep = np.ones(yl, dtype=bool)
             keep[::7] = False
             st.check(np.where(keep, got, 0), np.where(keep, ref, 0), tol, (case, acc, op, "beta = 0.0"))
-    st.done()
+    _pairstat(st)
 
 
 # ---- 2. several columns ------------------------------------------------------------------------------------------------
@@ -230,24 +153,23 @@ def _several_columns(torch, bsm, oracle, st, kind, pair, count, offset):
     for case, acc, p, A in _cases(bsm, st, rng, kind, pair, count):
         q = _oracle_problem(p, pair)
         has_off = _has_off(p)
-        nr, nc = p["size"]
         for op in (N, T, Cc):
-            xl, yl = (nc, nr) if op == N else (nr, nc)
+            xl, yl = lens(p, op)
             k = int(rng.choice(KS))
             strong = bool(rng.integers(0, 2))
             padx, pady = 2 * int(rng.integers(0, 5)) + 1, 2 * int(rng.integers(0, 5)) + 1
             X = np.asfortranarray(np.stack([rand_vec(rng, xl, V) for _ in range(k)], axis=1))
             Y0 = np.asfortranarray(np.stack([rand_vec(rng, yl, V) for _ in range(k)], axis=1))
-            xb, Xd = _mat(torch, X, padx)
-            yb, Yd = _mat(torch, Y0, pady)
-            before = (_outside(xb, 0, xl, xl + padx, k), _outside(yb, 0, yl, yl + pady, k), xb.cpu().numpy().tobytes())
+            xb, Xd = dev_mat(torch, X, padx)
+            yb, Yd = dev_mat(torch, Y0, pady)
+            before = (outside_bytes(xb, xl, xl + padx, k), outside_bytes(yb, yl, yl + pady, k), xb.cpu().numpy().tobytes())
             passes = A.value_passes()
-            bsm.mul(Yd, _wrap(bsm, A, op), Xd, am, False if strong else bm)
+            bsm.mul(Yd, wrap(bsm, A, op), Xd, am, False if strong else bm)
             torch.cuda.synchronize()
             st.products += 1
             what = (case, acc, op, k, "strong" if strong else "beta")
             assert A.value_passes() - passes == _passes(k, pair, has_off, acc == "colored"), (st.tag, what, "value streams")
-            pads = _outside(yb, 0, yl, yl + pady, k)
+            pads = outside_bytes(yb, yl, yl + pady, k)
             assert pads == before[1] and np.all(np.isnan(np.frombuffer(pads, dtype=V))), (st.tag, what, "pad rows of Y written")
             assert xb.cpu().numpy().tobytes() == before[2], (st.tag, what, "X written")
             assert np.all(np.isnan(np.frombuffer(before[0], dtype=V)))
@@ -261,9 +183,9 @@ def _several_columns(torch, bsm, oracle, st, kind, pair, count, offset):
 @pytest.mark.parametrize("pair", CROSS_PAIRS, ids=_pid)
 def test_several_columns(env, kind, pair):
     torch, bsm, oracle = env
-    st = Stat("multi", kind, pair)
+    st = Stat("multi", kind, _pid(pair))
     _several_columns(torch, bsm, oracle, st, kind, pair, 24, 2000)
-    st.done()
+    _pairstat(st)
 
 
 # ---- 3. the plan's switches, read once per process --------------------------------------------------------------------
@@ -281,7 +203,7 @@ def test_several_columns_under_the_plan_switches(env_extra):
     assert last.startswith("CHILD OK") and int(last.split()[2]) > 1000, last
 
 
-def _child(count):
+def _child_switches(count):
     import torch
     import bsm_amd as bsm
     from oracle import load_oracle
@@ -289,9 +211,9 @@ def _child(count):
     columns = 0
     for kind in KINDS:
         for pair in CROSS_PAIRS:
-            st = Stat("child", kind, pair)
+            st = Stat("child", kind, _pid(pair))
             _several_columns(torch, bsm, oracle, st, kind, pair, count, 3000)
-            st.done()
+            _pairstat(st)
             columns += st.columns
     print(f"CHILD OK {columns} columns checked")
 
@@ -305,40 +227,39 @@ def test_unaligned_vectors(env, kind, pair):
     torch, bsm, oracle = env
     V = np.dtype(pair[1])
     tol = TOL[V]
-    st = Stat("unaligned", kind, pair)
+    st = Stat("unaligned", kind, _pid(pair))
     rng = np.random.default_rng(_seed(kind, pair, 4000))
     am, bm = (-0.5 + 0.75j, 1.25 - 0.5j) if V.kind == "c" else (-0.5, 1.25)
     for case, acc, p, A in _cases(bsm, st, rng, kind, pair, 6, modes=["atomic", "gather"]):
         q = _oracle_problem(p, pair)
-        nr, nc = p["size"]
         offx, offy = case % 3 + 1, (case + 1) % 3 + 1
         for op in (N, T, Cc):
-            xl, yl = (nc, nr) if op == N else (nr, nc)
+            xl, yl = lens(p, op)
             for k in (1, 5):
                 X = np.asfortranarray(np.stack([rand_vec(rng, xl, V) for _ in range(k)], axis=1))
                 Y0 = np.asfortranarray(np.stack([rand_vec(rng, yl, V) for _ in range(k)], axis=1))
                 for strong in (True, False):
                     if k == 1:
-                        xb, xv = _vec(torch, X[:, 0], offx, 5)
-                        yb, yv = _vec(torch, Y0[:, 0], offy, 5)
+                        xb, xv = dev_vec(torch, X[:, 0], offx, 5)
+                        yb, yv = dev_vec(torch, Y0[:, 0], offy, 5)
                         padx = pady = 0
                     else:
                         padx, pady = 3, 1
-                        xb, xv = _mat(torch, X, padx, offx, 5)
-                        yb, yv = _mat(torch, Y0, pady, offy, 5)
+                        xb, xv = dev_mat(torch, X, padx, offx, 5)
+                        yb, yv = dev_mat(torch, Y0, pady, offy, 5)
                     assert xv.data_ptr() % 16 == (offx * V.itemsize) % 16 and yv.data_ptr() % 16 == (offy * V.itemsize) % 16
-                    before = (xb.cpu().numpy().tobytes(), _outside(yb, offy, yl, yl + pady, k))
-                    bsm.mul(yv, _wrap(bsm, A, op), xv, am, False if strong else bm)
+                    before = (xb.cpu().numpy().tobytes(), outside_bytes(yb, yl, yl + pady, k, offy))
+                    bsm.mul(yv, wrap(bsm, A, op), xv, am, False if strong else bm)
                     torch.cuda.synchronize()
                     st.products += 1
                     what = (case, acc, op, k, "strong" if strong else "beta", offx, offy)
                     assert xb.cpu().numpy().tobytes() == before[0], (st.tag, what, "x written")
-                    assert _outside(yb, offy, yl, yl + pady, k) == before[1], (st.tag, what, "a guard element of y changed")
+                    assert outside_bytes(yb, yl, yl + pady, k, offy) == before[1], (st.tag, what, "a guard element of y changed")
                     got = yv.cpu().numpy().reshape(yl, k)
                     for j in range(k):
                         ref = _ref(oracle, q, pair, op, X[:, j], Y0[:, j], am, bm, strong)
                         st.check(got[:, j], ref, tol, what + (j,))
-    st.done()
+    _pairstat(st)
 
 
 @pytest.mark.parametrize("pair", [SAME_PAIRS[3], CROSS_PAIRS[1], CROSS_PAIRS[2]], ids=_pid)
@@ -349,16 +270,15 @@ def test_complex128_y_on_an_8_byte_boundary_through_the_c_abi(env, pair):
     torch, bsm, oracle = env
     from bsm_amd import _lib as L
     V = np.dtype(np.complex128)
-    st = Stat("abi8", "all", pair)
+    st = Stat("abi8", "all", _pid(pair))
     fn = L.lib().bsm_mul_cvec if np.dtype(pair[0]).kind != "c" else L.lib().bsm_mul
     alpha, beta = np.array([-0.5 + 0.75j]), np.array([1.25 - 0.5j])
     for kind in KINDS:
         rng = np.random.default_rng(_seed(kind, pair, 5000))
         for case, acc, p, A in _cases(bsm, st, rng, kind, pair, 4, modes=["atomic"]):
             q = _oracle_problem(p, pair)
-            nr, nc = p["size"]
             for op in (N, T, Cc):
-                xl, yl = (nc, nr) if op == N else (nr, nc)
+                xl, yl = lens(p, op)
                 x, y0 = rand_vec(rng, xl, V), rand_vec(rng, yl, V)
                 xd = torch.from_numpy(x).cuda()
                 for strong in (1, 0):
@@ -375,11 +295,11 @@ def test_complex128_y_on_an_8_byte_boundary_through_the_c_abi(env, pair):
                     assert out[:1].tobytes() + out[1 + 2 * yl:].tobytes() == flat[:1].tobytes() + flat[1 + 2 * yl:].tobytes(), what
                     ref = _ref(oracle, q, pair, op, x, y0, alpha[0], beta[0], bool(strong))
                     st.check(out[1:1 + 2 * yl].copy().view(np.complex128), ref, TOL[V], what)
-    st.done()
+    _pairstat(st)
 
 
 def _entries(p):
-    return sum(b.size for k in ("blocks", "diagonals", "offdiagonals") for b in p.get(k, []))
+    return sum(b.size for k in BLOCK_KEYS for b in p.get(k, []))
 
 
 def _first_hull(p):
@@ -406,7 +326,7 @@ def test_owned_rows(env, kind, pair):
     torch, bsm, oracle = env
     B, V = np.dtype(pair[0]), np.dtype(pair[1])
     tol = TOL[V]
-    st = Stat("own", kind, pair)
+    st = Stat("own", kind, _pid(pair))
     rng = np.random.default_rng(_seed(kind, pair, 6000))
     am, bm = (-0.5 + 0.75j, 1.25 - 0.5j) if V.kind == "c" else (-0.5, 1.25)
     modes = ["auto", "atomic", "gather"]
@@ -436,8 +356,8 @@ def test_owned_rows(env, kind, pair):
                         bsm.mul(yh, A, xh, am, False if strong else bm)
                         got = yh.reshape(nr, k)
                     else:
-                        xb, xv = _vec(torch, X[:, 0]) if k == 1 else _mat(torch, X, 1)
-                        yb, yv = _vec(torch, Yin[:, 0]) if k == 1 else _mat(torch, Yin, 3)
+                        xb, xv = dev_vec(torch, X[:, 0]) if k == 1 else dev_mat(torch, X, 1)
+                        yb, yv = dev_vec(torch, Yin[:, 0]) if k == 1 else dev_mat(torch, Yin, 3)
                         bsm.mul(yv, A, xv, am, False if strong else bm)
                         torch.cuda.synchronize()
                         got = yv.cpu().numpy().reshape(nr, k)
@@ -448,8 +368,8 @@ def test_owned_rows(env, kind, pair):
                     for j in range(k):
                         ref = _ref(oracle, q, pair, N, X[:, j], Y0[:, j], am, bm, strong)
                         st.check(got[inside, j], ref[inside], tol, what + (j,))
-    st.done()
+    _pairstat(st)
 
 
 if __name__ == "__main__":
-    _child(int(sys.argv[1]))
+    _child_switches(int(sys.argv[1]))

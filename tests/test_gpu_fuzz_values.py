@@ -14,26 +14,17 @@ import functools
 import numpy as np
 import pytest
 
-from _common import WORK_SCALE, Cc, N, T, _image_exclusive, get_image, rand_vec, relerr
+from _common import NODEV, WORK_SCALE, Cc, N, T, _image_exclusive, get_image, rand_vec, relerr, wrap
 from _fuzz import canonical, coo_triples, edge_features, rounded
-from _values import (MEM_DEVICE, MEM_HOST, NODEV, NOPS, assert_coverage, dev_copy, explain, nan_blocks, new_values, on_device,
-                     options, padded, raw_update, seeded, src_list, subset_of, value_operators, value_seed, with_values)
+from _gpu import TOL, dev_copy, torch_cuda  # noqa: F401
+from _values import (MEM_DEVICE, MEM_HOST, NOPS, assert_coverage, explain, nan_blocks, new_values, on_device, options, padded,
+                     raw_update, seeded, src_list, subset_of, value_operators, value_seed, with_values)
 
 pytestmark = pytest.mark.gpu
 KINDS = ["blocksparse", "vbcrs", "symmetric"]
 DTYPES = [np.float32, np.float64, np.complex64, np.complex128]
 DOUBLES = [(np.float64, np.float32), (np.complex128, np.complex64)]
-TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12, np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-5}
 name_of = lambda d: np.dtype(d).name  # noqa: E731
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    from bsm_amd import _lib as L
-    L.lib()
-    return torch
 
 
 @functools.lru_cache(maxsize=None)
@@ -255,7 +246,7 @@ def test_captured_refill(torch_cuda, bsm, kind, dtype):
 def one_column_products(bsm, torch, A, xs):
     out = []
     for op, x in zip((N, T, Cc), xs):
-        M = A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
+        M = wrap(bsm, A, op)
         y = torch.zeros(A.size[0] if op == N else A.size[1], dtype=x.dtype, device="cuda")
         bsm.mul(y, M, x)
         out.append(y.cpu().numpy())

@@ -19,58 +19,25 @@ ROOT = os.path.dirname(HERE)
 if __name__ == "__main__":  # the child process of test_one_pass_observed
     sys.path[:0] = [ROOT, HERE]
 
-from _common import Cc, N, T, fixture_problem, oracle_mul, rand_vec, relerr  # noqa: E402
-from test_gpu_mixed_storage import (PAIRS, _build, _complexify, _device_blocks, _oracle_problem, _problem,  # noqa: E402
-                                    _rounded, _wrap)
+from _common import Cc, N, T, fixture_problem, lens, oracle_mul, rand_vec, relerr, wrap  # noqa: E402
+from _ctors import complexify, ctor_build, ctor_oracle_problem, ctor_problem  # noqa: E402
+from _fuzz import rounded  # noqa: E402
+from _gpu import dev_mat, gpu_mul, gpu_mul_multi, torch_cuda  # noqa: E402, F401
+from _values import on_device  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 OPS = [N, T, Cc]
+PAIRS = [(np.float64, np.float32), (np.complex128, np.complex64)]
 KS = (2, 3, 4, 5, 8, 9, 16, 17)
 TOL_ROUNDED, TOL_ORACLE = 1e-13, 1e-5
+# the generators' keywords per constructor route (those of tests/test_gpu_mixed_storage.py); FULL: C2 and C3 at full size
+SIZES = {"blocksparse": dict(n=600, nblocks=60, bs=16), "vbcrs": dict(n=4000, nblocks=200, lo=4, hi=48),
+         "symmetric": dict(nseg=16, bs=24, halfband=2), "vbcrs_from_symmetric": dict(nseg=16, bs=24, halfband=2)}
+FULL = {"vbcrs": {}, "symmetric": {}}
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    from bsm_amd import _lib as L
-    L.lib()
-    return torch
-
-
-def _mat(rng, n, k, dt):
+def _cols(rng, n, k, dt):
     return np.asfortranarray(np.stack([rand_vec(rng, n, dt) for _ in range(k)], axis=1))
-
-
-def _dev(torch, M, pad=0):
-    """column-major device copy of M with leading dimension n + pad, the padding full of NaN -> (storage, view)"""
-    n, k = M.shape
-    buf = torch.full((k, n + pad), float("nan"), dtype=torch.from_numpy(M[:1, :1].copy()).dtype, device="cuda")
-    buf[:, :n] = torch.from_numpy(np.ascontiguousarray(M.T)).cuda()
-    return buf, buf[:, :n].t()
-
-
-def _pad_bytes(buf, n):
-    return buf[:, n:].contiguous().cpu().numpy().tobytes()
-
-
-def _multi(torch, bsm, A, op, X, Y0, alpha=1, beta=0, strong=True, pad=0):
-    """Y = alpha op(A) X + beta Y0 through ONE bsm_mul_multi; with pad: the padding of X and Y must come back bit-identical"""
-    xb, xv = _dev(torch, X, pad)
-    yb, yv = _dev(torch, Y0, pad)
-    before = (_pad_bytes(xb, X.shape[0]), _pad_bytes(yb, Y0.shape[0]))
-    bsm.mul(yv, _wrap(bsm, A, op), xv, alpha, False if strong else beta)
-    torch.cuda.synchronize()
-    assert (_pad_bytes(xb, X.shape[0]), _pad_bytes(yb, Y0.shape[0])) == before, "padding of X / Y was written"
-    return yv.cpu().numpy()
-
-
-def _single(torch, bsm, A, op, x, y0, alpha=1, beta=0, strong=True):
-    xd = torch.from_numpy(np.ascontiguousarray(x)).cuda()
-    yd = torch.from_numpy(np.array(y0, copy=True, order="C")).cuda()
-    bsm.mul(yd, _wrap(bsm, A, op), xd, alpha, False if strong else beta)
-    torch.cuda.synchronize()
-    return yd.cpu().numpy()
 
 
 def _scalars(T_):
@@ -88,25 +55,24 @@ CTOR_TIMAGE = [(c, t) for c in CTORS for t in (0, 1) if t == 0 or c in ("blocksp
 @pytest.mark.parametrize("ctor, timage", CTOR_TIMAGE)
 def test_mixed_multi_product_matrix(torch_cuda, bsm, oracle, ctor, timage, T_, S_, acc):
     torch = torch_cuda
-    p = _problem(bsm, ctor, T_)
-    A = _build(bsm, ctor, p, storage=S_, accumulate=acc, transpose_image=timage)
-    R = _build(bsm, ctor, _rounded(p, S_), accumulate=acc, transpose_image=timage)  # pure T, rounded blocks
+    p = ctor_problem(bsm, ctor, T_, SIZES)
+    A = ctor_build(bsm, ctor, p, storage=S_, accumulate=acc, transpose_image=timage)
+    R = ctor_build(bsm, ctor, rounded(p, S_), accumulate=acc, transpose_image=timage)  # pure T, rounded blocks
     rng = np.random.default_rng(11)
-    nr, nc = p["size"]
     kmax = max(KS)
     worst = 0.0
     for op in OPS:
-        xl, yl = (nc, nr) if op == N else (nr, nc)
-        X, Y0 = _mat(rng, xl, kmax, T_), _mat(rng, yl, kmax, T_)
+        xl, yl = lens(p, op)
+        X, Y0 = _cols(rng, xl, kmax, T_), _cols(rng, yl, kmax, T_)
         cases = _scalars(T_)
         # every column through the rounded pure handle's ONE-column product, and (beta = 0) the oracle on the original blocks
-        refs = [np.stack([_single(torch, bsm, R, op, X[:, j], Y0[:, j], a, b, s) for j in range(kmax)], axis=1)
+        refs = [np.stack([gpu_mul(torch, bsm, R, op, X[:, j], Y0[:, j], a, b, s) for j in range(kmax)], axis=1)
                 for a, b, s in cases]
-        orc = np.stack([oracle_mul(oracle, _oracle_problem(ctor, p), op, X[:, j].copy(), Y0[:, j].copy())
+        orc = np.stack([oracle_mul(oracle, ctor_oracle_problem(ctor, p), op, X[:, j].copy(), Y0[:, j].copy())
                         for j in range(kmax)], axis=1)
         for k in KS:
             for (a, b, s), ref in zip(cases, refs):
-                got = _multi(torch, bsm, A, op, X[:, :k], Y0[:, :k], a, b, s, pad=7)
+                got = gpu_mul_multi(torch, bsm, A, op, X[:, :k], Y0[:, :k], a, b, s, pad=7)
                 for j in range(k):
                     e = relerr(got[:, j], ref[:, j])
                     worst = max(worst, e)
@@ -121,17 +87,17 @@ def test_mixed_multi_product_matrix(torch_cuda, bsm, oracle, ctor, timage, T_, S
 @pytest.mark.parametrize("ctor", ["vbcrs", "symmetric"])
 def test_mixed_multi_strong_zero_and_nan(torch_cuda, bsm, ctor, T_, S_):
     torch = torch_cuda
-    p = _problem(bsm, ctor, T_)
-    A = _build(bsm, ctor, p, storage=S_)
+    p = ctor_problem(bsm, ctor, T_, SIZES)
+    A = ctor_build(bsm, ctor, p, storage=S_)
     n = p["size"][0]
-    X = _mat(np.random.default_rng(12), n, 8, T_)
+    X = _cols(np.random.default_rng(12), n, 8, T_)
     Ynan = np.full((n, 8), np.nan, dtype=T_, order="F")
     for op in OPS:
         before = A.value_passes()
-        got = _multi(torch, bsm, A, op, X, Ynan, 0.5, 0, True, pad=3)   # strong zero: the NaN must not propagate
+        got = gpu_mul_multi(torch, bsm, A, op, X, Ynan, 0.5, 0, True, pad=3)   # strong zero: the NaN must not propagate
         assert A.value_passes() - before == 1, "K = 8 did not take the pass"
         assert np.all(np.isfinite(got)), op
-        got = _multi(torch, bsm, A, op, X, Ynan, 0.5, 0.0, False, pad=3)  # a numeric zero multiplies: NaN stays
+        got = gpu_mul_multi(torch, bsm, A, op, X, Ynan, 0.5, 0.0, False, pad=3)  # a numeric zero multiplies: NaN stays
         assert np.all(np.isnan(got)), op
 
 
@@ -155,13 +121,13 @@ def test_mixed_multi_state_claim_and_ownership(torch_cuda, bsm, oracle, T_, S_):
         ri.append(np.sort(rng.choice(nr, m_, replace=False)) + 1)
         ci.append(rng.choice(nc, n_, replace=False) + 1)
     p = dict(kind="blocksparse", blocks=blocks, rowindices=ri, colindices=ci, size=(nr, nc))
-    pr = _rounded(p, S_)
+    pr = rounded(p, S_)
     A = bsm.synthetic.build(p, storage=S_)
     al, be = ((0.5 - 1j), 2j) if cplx else (0.75, -1.5)
     for op, k in ((N, 8), (T, 3), (Cc, 8), (N, 2), (T, 13), (N, 4), (Cc, 5), (N, 8)):
-        xl, yl = (nc, nr) if op == N else (nr, nc)
-        X, Y0 = _mat(rng, xl, k, T_), _mat(rng, yl, k, T_)
-        got = _multi(torch, bsm, A, op, X, Y0, al, be, False, pad=1)
+        xl, yl = lens(p, op)
+        X, Y0 = _cols(rng, xl, k, T_), _cols(rng, yl, k, T_)
+        got = gpu_mul_multi(torch, bsm, A, op, X, Y0, al, be, False, pad=1)
         ref = np.stack([oracle_mul(oracle, pr, op, X[:, j].copy(), Y0[:, j].copy(), al, be, False) for j in range(k)], axis=1)
         for j in range(k):
             assert relerr(got[:, j], ref[:, j]) <= TOL_ROUNDED, (op, k, j)
@@ -174,12 +140,12 @@ def test_mixed_multi_state_claim_and_ownership(torch_cuda, bsm, oracle, T_, S_):
             assert relerr(yd.cpu().numpy(), ref[:, 0]) <= TOL_ROUNDED
     # two streams, one handle, no synchronisation in between
     f = fixture_problem("cuboid") if cplx else fixture_problem("cuboid", np.float64, "real")
-    fr = _rounded(f, S_)
+    fr = rounded(f, S_)
     F = bsm.synthetic.build(f, storage=S_)
     n = f["size"][0]
-    Xs = [_mat(rng, n, 8, T_) for _ in range(2)]
-    Xd = [_dev(torch, x)[1] for x in Xs]
-    Yd = [_dev(torch, np.full((n, 8), np.nan, dtype=T_, order="F"))[1] for _ in range(2)]
+    Xs = [_cols(rng, n, 8, T_) for _ in range(2)]
+    Xd = [dev_mat(torch, x)[1] for x in Xs]
+    Yd = [dev_mat(torch, np.full((n, 8), np.nan, dtype=T_, order="F"))[1] for _ in range(2)]
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     torch.cuda.synchronize()
     before = F.value_passes()
@@ -200,16 +166,16 @@ def test_mixed_multi_state_claim_and_ownership(torch_cuda, bsm, oracle, T_, S_):
     s_ = bsm.synthetic.config5(n=9000, lo=8, hi=40, halfband=3)
     if cplx:
         for i, key in enumerate(("diagonals", "offdiagonals")):
-            s_[key] = _complexify(s_[key], 40 + i)
-    sr = _rounded(s_, S_)
+            s_[key] = complexify(s_[key], 40 + i)
+    sr = rounded(s_, S_)
     n = s_["size"][0]
     own = (3001, 6000)
     Sm = bsm.synthetic.build(s_, own=own, storage=S_)
     for k in (8, 16, 5):
-        X, Y0 = _mat(rng, n, k, T_), _mat(rng, n, k, T_)
-        got = _multi(torch, bsm, Sm, N, X, Y0, al, be, False)
+        X, Y0 = _cols(rng, n, k, T_), _cols(rng, n, k, T_)
+        got = gpu_mul_multi(torch, bsm, Sm, N, X, Y0, al, be, False)
         for j in range(k):  # the single product through the same handle defines the semantics outside the owned range
-            assert relerr(got[:, j], _single(torch, bsm, Sm, N, X[:, j], Y0[:, j], al, be, False)) <= TOL_ROUNDED, (k, j)
+            assert relerr(got[:, j], gpu_mul(torch, bsm, Sm, N, X[:, j], Y0[:, j], al, be, False)) <= TOL_ROUNDED, (k, j)
         ref = oracle_mul(oracle, sr, N, X[:, 0].copy(), Y0[:, 0].copy(), al, be, False)
         assert relerr(got[own[0] - 1:own[1], 0], ref[own[0] - 1:own[1]]) <= TOL_ROUNDED
 
@@ -219,12 +185,12 @@ def test_mixed_multi_state_claim_and_ownership(torch_cuda, bsm, oracle, T_, S_):
 def test_mixed_multi_graph_capture(torch_cuda, bsm, T_, S_):
     """a captured K = 8 product never gets the work arrays: it is eight one-column products, counted at capture"""
     torch = torch_cuda
-    p = _problem(bsm, "symmetric", T_)
-    A = _build(bsm, "symmetric", p, storage=S_)
+    p = ctor_problem(bsm, "symmetric", T_, SIZES)
+    A = ctor_build(bsm, "symmetric", p, storage=S_)
     n = p["size"][0]
-    X = _dev(torch, _mat(np.random.default_rng(14), n, 8, T_))[1]
-    Y = _dev(torch, np.zeros((n, 8), dtype=T_, order="F"))[1]
-    eager = _dev(torch, np.zeros((n, 8), dtype=T_, order="F"))[1]
+    X = dev_mat(torch, _cols(np.random.default_rng(14), n, 8, T_))[1]
+    Y = dev_mat(torch, np.zeros((n, 8), dtype=T_, order="F"))[1]
+    eager = dev_mat(torch, np.zeros((n, 8), dtype=T_, order="F"))[1]
     before = A.value_passes()
     bsm.mul(eager, A, X)
     torch.cuda.synchronize()
@@ -255,23 +221,23 @@ def test_mixed_multi_graph_capture(torch_cuda, bsm, T_, S_):
 @pytest.mark.parametrize("T_, S_", PAIRS)
 @pytest.mark.parametrize("ctor", ["vbcrs", "symmetric"])
 def test_mixed_multi_host_vectors(torch_cuda, bsm, oracle, ctor, T_, S_):
-    p = _problem(bsm, ctor, T_)
-    A = _build(bsm, ctor, p, storage=S_)
+    p = ctor_problem(bsm, ctor, T_, SIZES)
+    A = ctor_build(bsm, ctor, p, storage=S_)
     n = p["size"][0]
     rng = np.random.default_rng(15)
     al, be = _scalars(T_)[1][:2]
     for op in (N, T):
-        X, Y0 = _mat(rng, n, 8, T_), _mat(rng, n, 8, T_)
+        X, Y0 = _cols(rng, n, 8, T_), _cols(rng, n, 8, T_)
         Y = Y0.copy(order="F")
         before = A.value_passes()
-        bsm.mul(Y, _wrap(bsm, A, op), X, al, be)
+        bsm.mul(Y, wrap(bsm, A, op), X, al, be)
         assert A.value_passes() - before == 1
         Z = np.full((n, 8), np.nan, dtype=T_, order="F")
-        bsm.mul(Z, _wrap(bsm, A, op), X)
+        bsm.mul(Z, wrap(bsm, A, op), X)
         for j in range(8):
-            ref = oracle_mul(oracle, _oracle_problem(ctor, _rounded(p, S_)), op, X[:, j].copy(), Y0[:, j].copy(), al, be, False)
+            ref = oracle_mul(oracle, ctor_oracle_problem(ctor, rounded(p, S_)), op, X[:, j].copy(), Y0[:, j].copy(), al, be, False)
             assert relerr(Y[:, j], ref) <= TOL_ROUNDED, (op, j)
-            assert relerr(Z[:, j], oracle_mul(oracle, _oracle_problem(ctor, p), op, X[:, j].copy(), Y0[:, j].copy())) <= TOL_ORACLE
+            assert relerr(Z[:, j], oracle_mul(oracle, ctor_oracle_problem(ctor, p), op, X[:, j].copy(), Y0[:, j].copy())) <= TOL_ORACLE
 
 
 # ---- 6. one pass, observed ---------------------------------------------------------------------------------------------
@@ -279,27 +245,26 @@ def _observed_handles(bsm, T_, S_):
     """name -> (handle, problem): an atomic, an exclusive-forward and a fused symmetric mixed handle, a coloured one, and
     a gather one whose column products are deterministic in every op (one producer per y entry: VBCRS with its second,
     transposed ordering -- bsm_mul_multi never takes the gather workspace, its columns accumulate with atomics)"""
-    pb, pv, ps = (_problem(bsm, c, T_) for c in ("blocksparse", "vbcrs", "symmetric"))
-    out = dict(atomic=(_build(bsm, "blocksparse", pb, storage=S_, accumulate="atomic"), pb),
-               exclusive=(_build(bsm, "vbcrs", pv, storage=S_), pv),
-               fused=(_build(bsm, "symmetric", ps, storage=S_), ps),
-               colored=(_build(bsm, "symmetric", ps, storage=S_, accumulate="colored"), ps),
-               gather=(_build(bsm, "vbcrs", pv, storage=S_, accumulate="gather", transpose_image=1), pv))
+    pb, pv, ps = (ctor_problem(bsm, c, T_, SIZES) for c in ("blocksparse", "vbcrs", "symmetric"))
+    out = dict(atomic=(ctor_build(bsm, "blocksparse", pb, storage=S_, accumulate="atomic"), pb),
+               exclusive=(ctor_build(bsm, "vbcrs", pv, storage=S_), pv),
+               fused=(ctor_build(bsm, "symmetric", ps, storage=S_), ps),
+               colored=(ctor_build(bsm, "symmetric", ps, storage=S_, accumulate="colored"), ps),
+               gather=(ctor_build(bsm, "vbcrs", pv, storage=S_, accumulate="gather", transpose_image=1), pv))
     assert out["exclusive"][0].stats()["exclusive"] == 1
     return out
 
 
 def _delta(torch, bsm, A, p, k, op=N):
     T_ = A.dtype
-    nr, nc = p["size"]
-    xl, yl = (nc, nr) if op == N else (nr, nc)
+    xl, yl = lens(p, op)
     rng = np.random.default_rng(100 + k)
-    X = _mat(rng, xl, k, T_)
+    X = _cols(rng, xl, k, T_)
     before = A.value_passes()
     if k == 1:
-        Y = _single(torch, bsm, A, op, X[:, 0], np.zeros(yl, T_))[:, None]
+        Y = gpu_mul(torch, bsm, A, op, X[:, 0], np.zeros(yl, T_))[:, None]
     else:
-        Y = _multi(torch, bsm, A, op, X, np.zeros((yl, k), dtype=T_, order="F"))
+        Y = gpu_mul_multi(torch, bsm, A, op, X, np.zeros((yl, k), dtype=T_, order="F"))
     return A.value_passes() - before, X, Y
 
 
@@ -314,8 +279,8 @@ def test_one_pass_observed(torch_cuda, bsm, T_, S_):
         for k, passes in want.items():
             assert _delta(torch, bsm, A, p, k)[0] == passes, (name, k)
     assert _delta(torch, bsm, *H["colored"], 8)[0] == 8   # coloured images keep their bitwise reproducible columns
-    ps = _problem(bsm, "symmetric", T_)
-    assert _delta(torch, bsm, _build(bsm, "symmetric", ps), ps, 8)[0] == 1  # the counter on the existing paths
+    ps = ctor_problem(bsm, "symmetric", T_, SIZES)
+    assert _delta(torch, bsm, ctor_build(bsm, "symmetric", ps), ps, 8)[0] == 1  # the counter on the existing paths
     # BSM_MULTI_IL=0: today's contract, still reachable (the library reads the switch once per process)
     r = subprocess.run([sys.executable, os.path.abspath(__file__), np.dtype(T_).name, np.dtype(S_).name],
                        env=dict(os.environ, BSM_MULTI_IL="0"), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -323,7 +288,7 @@ def test_one_pass_observed(torch_cuda, bsm, T_, S_):
     assert r.returncode == 0 and out.strip().endswith("CHILD OK"), out[-3000:] + r.stderr.decode()[-3000:]
 
 
-def _child(T_, S_):
+def _child_no_il(T_, S_):
     """BSM_MULTI_IL=0: K = 8 is eight one-column products on every mixed handle, bitwise equal to eight bsm_mul calls
     where those are deterministic (op N of the exclusive-forward handle, every op of the gather one)"""
     import torch
@@ -336,10 +301,10 @@ def _child(T_, S_):
             assert d == 8, (name, op, d)
             if (name == "exclusive" and op == N) or name == "gather":
                 for j in range(8):
-                    col = _single(torch, bsm, A, op, X[:, j], np.zeros(Y.shape[0], A.dtype))
+                    col = gpu_mul(torch, bsm, A, op, X[:, j], np.zeros(Y.shape[0], A.dtype))
                     assert Y[:, j].tobytes() == col.tobytes(), (name, op, j)
-    ps = _problem(bsm, "symmetric", T_)
-    assert _delta(torch, bsm, _build(bsm, "symmetric", ps), ps, 8)[0] == 1  # pure handle: the multi-RHS kernels
+    ps = ctor_problem(bsm, "symmetric", T_, SIZES)
+    assert _delta(torch, bsm, ctor_build(bsm, "symmetric", ps), ps, 8)[0] == 1  # pure handle: the multi-RHS kernels
     print("CHILD OK")
 
 
@@ -347,26 +312,25 @@ def _child(T_, S_):
 @pytest.fixture(scope="module")
 def c3_pair(torch_cuda, bsm):
     """full-size C3: (problem, mixed handle, pure double handle of the rounded blocks), built once for tests 7 and 8"""
-    p = _problem(bsm, "symmetric", np.float64, big=True)
-    A = _build(bsm, "symmetric", _device_blocks(torch_cuda, p), storage=np.float32)
-    pr = _rounded(p, np.float32)
-    R = _build(bsm, "symmetric", _device_blocks(torch_cuda, pr))
+    p = ctor_problem(bsm, "symmetric", np.float64, FULL)
+    A = ctor_build(bsm, "symmetric", on_device(torch_cuda, p), storage=np.float32)
+    pr = rounded(p, np.float32)
+    R = ctor_build(bsm, "symmetric", on_device(torch_cuda, pr))
     return p, pr, A, R
 
 
 def _full_size(torch, bsm, oracle, p, pr, A, R):
-    nr, nc = p["size"]
     rng = np.random.default_rng(16)
     for op in (N, T):
-        xl, yl = (nc, nr) if op == N else (nr, nc)
-        X, Y0 = _mat(rng, xl, 8, np.float64), _mat(rng, yl, 8, np.float64)
+        xl, yl = lens(p, op)
+        X, Y0 = _cols(rng, xl, 8, np.float64), _cols(rng, yl, 8, np.float64)
         before = A.value_passes()
-        got = _multi(torch, bsm, A, op, X, Y0, 0.5, 2.0, False, pad=64)
+        got = gpu_mul_multi(torch, bsm, A, op, X, Y0, 0.5, 2.0, False, pad=64)
         assert A.value_passes() - before == 1
         for j in range(8):
-            ref = _single(torch, bsm, R, op, X[:, j], Y0[:, j], 0.5, 2.0, False)
+            ref = gpu_mul(torch, bsm, R, op, X[:, j], Y0[:, j], 0.5, 2.0, False)
             assert relerr(got[:, j], ref) <= TOL_ROUNDED, (op, j)
-        got = _multi(torch, bsm, A, op, X, np.full_like(Y0, np.nan))
+        got = gpu_mul_multi(torch, bsm, A, op, X, np.full_like(Y0, np.nan))
         for j in (0, 7):
             assert relerr(got[:, j], oracle_mul(oracle, pr, op, X[:, j].copy(), Y0[:, j].copy())) <= TOL_ROUNDED, (op, j)
             assert relerr(got[:, j], oracle_mul(oracle, p, op, X[:, j].copy(), Y0[:, j].copy())) <= TOL_ORACLE, (op, j)
@@ -377,10 +341,10 @@ def test_mixed_multi_full_size_c3(torch_cuda, bsm, oracle, c3_pair):
 
 
 def test_mixed_multi_full_size_c2(torch_cuda, bsm, oracle):
-    p = _problem(bsm, "vbcrs", np.float64, big=True)
-    pr = _rounded(p, np.float32)
-    A = _build(bsm, "vbcrs", _device_blocks(torch_cuda, p), storage=np.float32)
-    R = _build(bsm, "vbcrs", _device_blocks(torch_cuda, pr))
+    p = ctor_problem(bsm, "vbcrs", np.float64, FULL)
+    pr = rounded(p, np.float32)
+    A = ctor_build(bsm, "vbcrs", on_device(torch_cuda, p), storage=np.float32)
+    R = ctor_build(bsm, "vbcrs", on_device(torch_cuda, pr))
     _full_size(torch_cuda, bsm, oracle, p, pr, A, R)
 
 
@@ -394,8 +358,8 @@ def test_mixed_multi_pays_on_c3(torch_cuda, bsm, c3_pair):
     p, _, A, _ = c3_pair
     n = p["size"][0]
     rng = np.random.default_rng(17)
-    X = _dev(torch, _mat(rng, n, 8, np.float64))[1]
-    Y = _dev(torch, np.zeros((n, 8), order="F"))[1]
+    X = dev_mat(torch, _cols(rng, n, 8, np.float64))[1]
+    Y = dev_mat(torch, np.zeros((n, 8), order="F"))[1]
     xs = [X[:, j].contiguous() for j in range(8)]
     ys = [torch.zeros(n, dtype=torch.float64, device="cuda") for _ in range(8)]
 
@@ -430,4 +394,4 @@ def test_mixed_multi_pays_on_c3(torch_cuda, bsm, c3_pair):
 
 
 if __name__ == "__main__":
-    _child(np.dtype(sys.argv[1]).type, np.dtype(sys.argv[2]).type)
+    _child_no_il(np.dtype(sys.argv[1]).type, np.dtype(sys.argv[2]).type)

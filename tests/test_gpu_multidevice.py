@@ -10,34 +10,19 @@ device-to-device copy).  Every product is compared with the CPU oracle on the WH
 import numpy as np
 import pytest
 
-from _common import Cc, N, T, fixture_as_blocksparse, fixture_problem, oracle_mul, rand_vec, relerr
+from _common import Cc, N, T, fixture_as_blocksparse, fixture_problem, lens, oracle_mul, rand_vec, relerr, wrap
+from _gpu import TOL, gpu_mul, scatter, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12,
-       np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-5}
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    from bsm_amd import _lib as L
-    L.lib()
-    return torch
-
-
-def wrap(bsm, A, op):
-    return A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
-
-
-def check(torch, bsm, oracle, problem, A, ops=(N, T, Cc)):
+def check_products(torch, bsm, oracle, problem, A, ops=(N, T, Cc)):
     dt = np.dtype(A.dtype)
-    nr, nc = problem["size"]
     rng = np.random.default_rng(5)
     for op in ops:
         if op == Cc and dt.kind != "c":
             continue
-        xl, yl = (nc, nr) if op == N else (nr, nc)
+        xl, yl = lens(problem, op)
         x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
         y0[::7] = np.nan  # the strong zero must not let them through
         combos = [(1, 0, True), (0.75, -1.5, False)]
@@ -51,10 +36,8 @@ def check(torch, bsm, oracle, problem, A, ops=(N, T, Cc)):
             bsm.mul(yh, wrap(bsm, A, op), x, alpha, False if strong else beta)
             assert relerr(yh, ref) < TOL[dt], ("host", op, alpha, beta)
             # device vectors on cuda:0
-            xd, yd = torch.from_numpy(x).cuda(), torch.from_numpy(np.array(yin, copy=True)).cuda()
-            bsm.mul(yd, wrap(bsm, A, op), xd, alpha, False if strong else beta)
-            torch.cuda.synchronize()
-            assert relerr(yd.cpu().numpy(), ref) < TOL[dt], ("device", op, alpha, beta)
+            got = gpu_mul(torch, bsm, A, op, x, yin, alpha, beta, strong)
+            assert relerr(got, ref) < TOL[dt], ("device", op, alpha, beta)
 
 
 def check_parts(A, nparts):
@@ -80,7 +63,7 @@ def test_vbcrs_over_virtual_devices(torch_cuda, bsm, oracle, ndev):
     perm, rowptr, colind, rowind = oracle.vbcrs_build(prob["rowstart"], prob["colstart"])
     assert np.array_equal(A.perm, perm) and np.array_equal(A.rowptr, rowptr)
     assert np.array_equal(A.colindices, colind) and np.array_equal(A.rowindices, rowind)
-    check(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
+    check_products(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
 
 
 @pytest.mark.parametrize("ndev", [2, 4])
@@ -91,7 +74,7 @@ def test_symmetric_halo_over_virtual_devices(torch_cuda, bsm, oracle, ndev):
     # banded structure: a part touches rows of the part below it (the halo) and nothing else
     parts = A.parts()
     assert any(p["touched"][0] < p["own"][0] for p in parts[1:])
-    check(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
+    check_products(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
 
 
 @pytest.mark.parametrize("key", ["cuboid", "sphere"])
@@ -101,23 +84,23 @@ def test_reference_fixture_over_virtual_devices(torch_cuda, bsm, oracle, key):
     prob = fixture_problem(key)
     A = bsm.synthetic.build(prob, devices=[0, 0, 0])
     check_parts(A, 3)
-    check(torch_cuda, bsm, oracle, prob, A)
+    check_products(torch_cuda, bsm, oracle, prob, A)
     pb = fixture_as_blocksparse(key)
     B = bsm.synthetic.build(pb, devices=[0, 0])
-    check(torch_cuda, bsm, oracle, pb, B)
+    check_products(torch_cuda, bsm, oracle, pb, B)
 
 
 def test_blocksparse_config1_and_more_devices_than_block_rows(torch_cuda, bsm, oracle):
     prob = bsm.synthetic.config1()
     A = bsm.synthetic.build(prob, devices=[0, 0, 0])
-    check(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
+    check_products(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
     # 2 block rows on 4 devices: two parts stay empty (no image) and the product is still complete
     rng = np.random.default_rng(2)
     blocks = [np.asfortranarray(rng.standard_normal((5, 7))), np.asfortranarray(rng.standard_normal((6, 4)))]
     small = dict(kind="vbcrs", blocks=blocks, rowstart=np.array([3, 20]), colstart=np.array([1, 9]), size=(30, 16))
     V = bsm.synthetic.build(small, devices=[0, 0, 0, 0])
     assert sorted(p["nblocks"] for p in V.parts()) == [0, 0, 1, 1]
-    check(torch_cuda, bsm, oracle, small, V, ops=(N, T))
+    check_products(torch_cuda, bsm, oracle, small, V, ops=(N, T))
 
 
 def test_vbcrs_view_of_symmetric_and_multi_rhs(torch_cuda, bsm, oracle):
@@ -125,7 +108,7 @@ def test_vbcrs_view_of_symmetric_and_multi_rhs(torch_cuda, bsm, oracle):
     prob = bsm.synthetic.config3(nseg=40, bs=24, halfband=3)
     S = bsm.synthetic.build(prob)
     V = bsm.VariableBlockCompressedRowStorage(S, devices=[0, 0])
-    check(torch, bsm, oracle, prob, V, ops=(N, T))
+    check_products(torch, bsm, oracle, prob, V, ops=(N, T))
     # A * X through the multi-device handle (one fan-out per column)
     n = prob["size"][0]
     rng = np.random.default_rng(3)
@@ -427,11 +410,6 @@ def test_work_vectors_stay_zero_across_directions_batches_and_paths(torch_cuda, 
 
 
 # ---- partitioned vectors behind the C ABI: bsm_mul_parts ------------------------------------------------------------
-def _scatter(torch, v, ranges):
-    """the parts of a full host vector (1-based inclusive ranges) as CUDA tensors"""
-    return [torch.from_numpy(np.ascontiguousarray(v[lo - 1:hi])).cuda() if hi >= lo else None for lo, hi in ranges]
-
-
 @pytest.mark.parametrize("kind,ndev", [("vbcrs", 3), ("vbcrs_rect", 2), ("symmetric", 2), ("symmetric", 4), ("fixture", 3),
                                        ("blocksparse", 3)])
 def test_partitioned_vectors_through_the_multi_device_handle(torch_cuda, bsm, oracle, kind, ndev):
@@ -472,7 +450,7 @@ def test_partitioned_vectors_through_the_multi_device_handle(torch_cuda, bsm, or
     rng = np.random.default_rng(5)
     ops = (N, T, Cc) if dt.kind == "c" else (N, T)
     for op in ops:
-        xl, yl = (nc, nr) if op == N else (nr, nc)
+        xl, yl = lens(prob, op)
         xr, yr = (cols, rows) if op == N else (rows, cols)
         x, y0 = rand_vec(rng, xl, dt), rand_vec(rng, yl, dt)
         y0[::7] = np.nan
@@ -481,7 +459,7 @@ def test_partitioned_vectors_through_the_multi_device_handle(torch_cuda, bsm, or
             yin = y0 if strong else np.nan_to_num(y0, nan=0.25)
             ref = oracle_mul(oracle, prob, op, x, yin, alpha, beta, strong)
             for _ in range(2):
-                xp, yp = _scatter(torch, x, xr), _scatter(torch, yin, yr)
+                xp, yp = scatter(torch, x, xr), scatter(torch, yin, yr)
                 bsm.mul_parts(yp, wrap(bsm, A, op), xp, alpha, False if strong else beta)
                 torch.cuda.synchronize()
                 got = np.full(yl, np.nan, dtype=dt)
@@ -492,7 +470,7 @@ def test_partitioned_vectors_through_the_multi_device_handle(torch_cuda, bsm, or
     # chained: y parts of one product are the x parts of the next (square operators), no host round trip
     if nr == nc and dt.kind != "c":
         x = rand_vec(rng, nc, dt)
-        xp = _scatter(torch, x, cols)
+        xp = scatter(torch, x, cols)
         y1 = [torch.empty_like(t) if t is not None else None for t in xp]
         y2 = [torch.empty_like(t) if t is not None else None for t in xp]
         bsm.mul_parts(y1, A, xp)
@@ -509,8 +487,8 @@ def test_copy_path_of_the_multi_device_handle_still_works(torch_cuda, bsm, oracl
     monkeypatch.setenv("BSM_DIST_COPIES", "1")
     prob = bsm.synthetic.config5(n=30_000, lo=16, hi=96, halfband=3)
     A = bsm.synthetic.build(prob, devices=[0, 0, 0])
-    check(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
-    xp = _scatter(torch_cuda, prob["x"], [p["cols"] for p in A.parts()])
+    check_products(torch_cuda, bsm, oracle, prob, A, ops=(N, T))
+    xp = scatter(torch_cuda, prob["x"], [p["cols"] for p in A.parts()])
     with pytest.raises(RuntimeError, match="peer access"):  # the partitioned-vector entry has no copy path
         bsm.mul_parts([torch_cuda.empty_like(t) for t in xp], A, xp)
 
@@ -631,7 +609,7 @@ def test_partitioned_vectors_fp32_and_device_resident_blocks(torch_cuda, bsm, or
         rows, cols = [q["own"] for q in parts], [q["cols"] for q in parts]
         for op in (N, T):
             ref = oracle_mul(oracle, prob, op, x, np.zeros(n, dtype=np.float32))
-            xp, yp = _scatter(torch, x, cols if op == N else rows), [torch.full((hi - lo + 1,), float("nan"), dtype=torch.float32, device="cuda")
+            xp, yp = scatter(torch, x, cols if op == N else rows), [torch.full((hi - lo + 1,), float("nan"), dtype=torch.float32, device="cuda")
                                                                       for lo, hi in (rows if op == N else cols)]
             bsm.mul_parts(yp, wrap(bsm, A, op), xp)
             torch.cuda.synchronize()

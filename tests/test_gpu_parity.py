@@ -11,54 +11,22 @@ covered in the CPU suite (tests/test_host_logic.py), which needs no GPU.
 import numpy as np
 import pytest
 
-from _common import (Cc, N, T, fixture_as_blocksparse, fixture_problem, oracle_mul, rand_vec, relerr,
-                     scipy_mul)
+from _common import (Cc, N, T, fixture_as_blocksparse, fixture_problem, lens, oracle_mul, rand_vec, relerr,
+                     scipy_mul, wrap)
+from _gpu import TOL, gpu_mul, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-TOL = {np.dtype(np.float64): 1e-12, np.dtype(np.complex128): 1e-12,
-       np.dtype(np.float32): 1e-5, np.dtype(np.complex64): 1e-5}
 OPS = [N, T, Cc]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    from bsm_amd import _lib as L
-    L.lib()  # fails loudly if the HIP extension is missing
-    return torch
-
-
-def wrap(bsm, A, op):
-    return A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
-
-
-def gpu_mul(torch, bsm, A, op, x, y0, alpha, beta, strong, host=False):
-    Aop = wrap(bsm, A, op)
-    if host:  # BSM_MEM_HOST: the library stages x/y itself
-        y = np.array(y0, copy=True)
-        if strong:
-            return bsm.mul(y, Aop, x) if alpha == 1 else bsm.mul(y, Aop, x, alpha, False)
-        return bsm.mul(y, Aop, x, alpha, beta)
-    xd = torch.from_numpy(x).cuda()
-    yd = torch.from_numpy(np.array(y0, copy=True)).cuda()
-    if strong:
-        bsm.mul(yd, Aop, xd, alpha, False)
-    else:
-        bsm.mul(yd, Aop, xd, alpha, beta)
-    torch.cuda.synchronize()
-    return yd.cpu().numpy()
 
 
 def check_all(torch, bsm, oracle, problem, A, dtype, ops=OPS, seeds=(0,), host_too=True):
     dtype = np.dtype(dtype)
-    nr, nc = problem["size"]
     for seed in seeds:
         rng = np.random.default_rng(seed)
         for op in ops:
             if op == Cc and dtype.kind != "c":
                 continue
-            xl, yl = (nc, nr) if op == N else (nr, nc)
+            xl, yl = lens(problem, op)
             x, y0 = rand_vec(rng, xl, dtype), rand_vec(rng, yl, dtype)
             ab = [(1, 0, True), (0.75, -1.5, False)]
             if dtype.kind == "c":
@@ -80,8 +48,7 @@ def check_all(torch, bsm, oracle, problem, A, dtype, ops=OPS, seeds=(0,), host_t
 def test_symmetric_fixture(torch_cuda, bsm, oracle, key, dtype, part):
     p = fixture_problem(key, dtype, part)
     for sched in (bsm.SerialScheduler(), bsm.DynamicScheduler()):
-        A = bsm.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"],
-                                     p["rowindices"], p["colindices"], p["size"], scheduler=sched)
+        A = bsm.synthetic.build(p, scheduler=sched)
         check_all(torch_cuda, bsm, oracle, p, A, dtype, seeds=(0, 1))
     # the reference's own check: A*x ~ sparse(A)*x  (test_symmetricblockmatrix.jl:67-71)
     rng = np.random.default_rng(5)
@@ -94,7 +61,7 @@ def test_symmetric_fixture(torch_cuda, bsm, oracle, key, dtype, part):
 @pytest.mark.parametrize("acc", ["auto", "atomic"])
 def test_blocksparse_fixture(torch_cuda, bsm, oracle, key, acc):
     p = fixture_as_blocksparse(key)
-    A = bsm.BlockSparseMatrix(p["blocks"], p["rowindices"], p["colindices"], p["size"], accumulate=acc)
+    A = bsm.synthetic.build(p, accumulate=acc)
     assert A.stats()["exclusive"] == (1 if acc == "auto" else 0)
     check_all(torch_cuda, bsm, oracle, p, A, np.complex128)
 
@@ -306,12 +273,11 @@ def test_transpose_image_parity_and_determinism(torch_cuda, bsm, oracle):
 # ---- multi right-hand-side product: A * X, mul!(Y, A, X, a, b) with matrices ---------------------------
 def _check_multi(torch, bsm, oracle, problem, A, dtype, nrhs_list=(1, 3, 4, 8, 13), ops=OPS):
     dtype = np.dtype(dtype)
-    nr, nc = problem["size"]
     rng = np.random.default_rng(21)
     for op in ops:
         if op == Cc and dtype.kind != "c":
             continue
-        xl, yl = (nc, nr) if op == N else (nr, nc)
+        xl, yl = lens(problem, op)
         Aop = wrap(bsm, A, op)
         for k in nrhs_list:
             X = np.asfortranarray(np.stack([rand_vec(rng, xl, dtype) for _ in range(k)], axis=1))
@@ -409,7 +375,7 @@ def test_multi_rhs_interleaved_pass_state_and_ownership(torch_cuda, bsm, oracle)
     p = dict(kind="blocksparse", blocks=blocks, rowindices=ri, colindices=ci, size=(nr, nc))
     A = bsm.synthetic.build(p)
     for op, k in ((N, 8), (T, 3), (Cc, 8), (N, 2), (T, 13), (N, 4), (Cc, 5), (N, 8)):
-        xl, yl = (nc, nr) if op == N else (nr, nc)
+        xl, yl = lens(p, op)
         X = np.asfortranarray(rng.standard_normal((xl, k)) + 1j * rng.standard_normal((xl, k)))
         Y0 = np.asfortranarray(rng.standard_normal((yl, k)) + 1j * rng.standard_normal((yl, k)))
         Xd, Yd = torch.from_numpy(X.T.copy()).cuda().t(), torch.from_numpy(Y0.T.copy()).cuda().t()

@@ -4,25 +4,18 @@ right-hand sides, multi-device handles; stream order and graph capture as includ
 import numpy as np
 import pytest
 
-from _common import N, T, fixture_problem, oracle_mul, rand_vec, relerr
-from _values import dev_copy, new_values, on_device, padded, raw_update, src_list, with_values
+from _common import N, T, fixture_problem, oracle_mul, rand_vec, relerr, wrap
+from _gpu import dev_copy, torch_cuda  # noqa: F401
+from _values import new_values, on_device, padded, raw_update, src_list, with_values
 
 pytestmark = pytest.mark.gpu
 C_OP = 2
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    torch = pytest.importorskip("torch")
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
 def products(bsm, torch, A, x, ops=(N, T, C_OP)):
     out = []
     for op in ops:
-        M = A if op == N else (bsm.transpose(A) if op == T else bsm.adjoint(A))
+        M = wrap(bsm, A, op)
         n = A.size[0] if op == N else A.size[1]
         y = torch.zeros(n, dtype=x.dtype, device="cuda")
         bsm.mul(y, M, x)

@@ -9,11 +9,10 @@ import re
 import numpy as np
 import pytest
 
-from _common import (Cc, N, T, fixture_as_blocksparse, fixture_problem, interpret_image, oracle_mul,
+from _common import (NODEV, Cc, N, T, fixture_as_blocksparse, fixture_problem, interpret_image, oracle_mul,
                      rand_vec, relerr)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NODEV = -2
 OPS = [N, T, Cc]
 
 

@@ -7,6 +7,9 @@ import re
 import numpy as np
 import pytest
 
+from _common import NODEV
+from _fuzz import cast_blocks
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "bsm_rocm.h")
 
@@ -29,12 +32,8 @@ def test_value_passes_refusals_and_a_fresh_analysis_only_handle(bsm, dt, storage
     fn = L.lib().bsm_value_passes
     n = C.c_int64(-7)
     assert fn(None, C.byref(n)) == -1 and n.value == -7            # BSM_ERR_INVALID: null handle, *count untouched
-    p = bsm.synthetic.config3(nseg=6, bs=8, halfband=1)
-    for k in ("diagonals", "offdiagonals"):
-        p[k] = [np.asfortranarray(b.astype(dt)) for b in p[k]]
-    M = bsm.matrices
-    A = M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"], p["colindices"],
-                               p["size"], device=L.BSM_DEVICE_NONE, storage=storage)
+    p = cast_blocks(bsm.synthetic.config3(nseg=6, bs=8, halfband=1), dt)
+    A = bsm.synthetic.build(p, device=NODEV, storage=storage)
     assert fn(A._h.ptr, None) == -1                                 # BSM_ERR_INVALID: null pointer
     assert fn(A._h.ptr, C.byref(n)) == 0 and n.value == 0           # nothing has streamed the image
     assert A.value_passes() == 0

@@ -8,95 +8,16 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _common import Cc, N, T, WORK_PANEL, decode_mixed, fixture_problem, get_image, oracle_mul, rand_vec, relerr
-from _fuzz import rounded as _rounded
+from _common import (Cc, N, NODEV, T, WORK_PANEL, decode_mixed, fixture_problem, get_image, img_bytes, oracle_mul, rand_vec,
+                     relerr)
+from _ctors import CTORS, ctor_build, ctor_oracle_problem, ctor_problem
+from _fuzz import cast_blocks, rounded
 
-NODEV = -2
 OPS = [N, T, Cc]
 PAIRS = [(np.float64, np.float32), (np.complex128, np.complex64)]
-CTORS = ["blocksparse", "vbcrs", "symmetric", "vbcrs_from_blocksparse", "vbcrs_from_symmetric"]
-
-
-def _complexify(blocks, seed):
-    rng = np.random.default_rng(seed)
-    return [np.asfortranarray(b + 1j * rng.standard_normal(b.shape)) for b in blocks]
-
-
-def _problem(bsm, ctor, dt):
-    """a small problem of each constructor's kind, blocks of type dt (float64 or complex128)"""
-    S = bsm.synthetic
-    if ctor == "blocksparse":
-        p = S.config1(n=400, nblocks=40, bs=12)
-        keys = ["blocks"]
-    elif ctor == "vbcrs":
-        p = S.config2(n=3000, nblocks=160, lo=4, hi=40)
-        keys = ["blocks"]
-    elif ctor == "vbcrs_from_blocksparse":  # contiguous lists: the converter takes the first index of each
-        v = S.config2(n=2000, nblocks=120, lo=4, hi=40)
-        p = dict(kind="blocksparse", blocks=v["blocks"], size=v["size"],
-                 rowindices=[np.arange(r, r + b.shape[0], dtype=np.int64) for r, b in zip(v["rowstart"], v["blocks"])],
-                 colindices=[np.arange(c, c + b.shape[1], dtype=np.int64) for c, b in zip(v["colstart"], v["blocks"])])
-        keys = ["blocks"]
-    else:
-        p = S.config3(nseg=10, bs=20, halfband=2)
-        keys = ["diagonals", "offdiagonals"]
-    if np.dtype(dt).kind == "c":
-        for i, k in enumerate(keys):
-            p[k] = _complexify(p[k], 7 + i)
-    return p
-
-
-def _build(bsm, ctor, p, dtype_cast=None, **kw):
-    """constructor `ctor` on problem p (blocks cast to dtype_cast first if given), analysis only"""
-    M = bsm.matrices
-    if dtype_cast is not None:
-        p = dict(p)
-        for k in ("blocks", "diagonals", "offdiagonals"):
-            if k in p:
-                p[k] = [np.asfortranarray(b.astype(dtype_cast)) for b in p[k]]
-    kw.setdefault("device", NODEV)
-    storage = kw.pop("storage", None)
-    skw = {} if storage is None else {"storage": storage}
-    if ctor == "blocksparse":
-        return M.BlockSparseMatrix(p["blocks"], p["rowindices"], p["colindices"], p["size"], **kw, **skw)
-    if ctor == "vbcrs":
-        return M.VariableBlockCompressedRowStorage(p["blocks"], p["rowstart"], p["colstart"], p["size"], **kw, **skw)
-    if ctor == "symmetric":
-        kw.pop("transpose_image", None)
-        return M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"],
-                                      p["colindices"], p["size"], **kw, **skw)
-    if ctor == "vbcrs_from_blocksparse":
-        B = M.BlockSparseMatrix(p["blocks"], p["rowindices"], p["colindices"], p["size"], device=NODEV)
-        return M.VariableBlockCompressedRowStorage(B, **kw, **skw)
-    if ctor == "vbcrs_from_symmetric":
-        kw.pop("transpose_image", None)
-        Sm = M.SymmetricBlockMatrix(p["diagonals"], p["diagonalindices"], p["offdiagonals"], p["rowindices"],
-                                    p["colindices"], p["size"], device=NODEV)
-        return M.VariableBlockCompressedRowStorage(Sm, **kw, **skw)
-    raise ValueError(ctor)
-
-
-def _oracle_problem(ctor, p):
-    """the problem as the oracle takes it: a VBCRS from a BlockSparseMatrix / SymmetricBlockMatrix is the same operator"""
-    if ctor == "vbcrs_from_blocksparse":
-        return dict(p, kind="blocksparse")
-    if ctor == "vbcrs_from_symmetric":  # [diagonals..., offdiagonals..., transposes...] at the FIRST list entries
-        d, o = p["diagonals"], p["offdiagonals"]
-        first = lambda lists: [int(v[0]) for v in lists]  # noqa: E731
-        rs = first(p["diagonalindices"]) + first(p["rowindices"]) + first(p["colindices"])
-        cs = first(p["diagonalindices"]) + first(p["colindices"]) + first(p["rowindices"])
-        return dict(kind="vbcrs", blocks=list(d) + list(o) + [np.asfortranarray(b.T) for b in o],
-                    rowstart=np.array(rs, dtype=np.int64), colstart=np.array(cs, dtype=np.int64), size=p["size"])
-    return p
-
-
-def _img_bytes(A, which):
-    from bsm_amd import _lib as L
-    n = C.c_int64(0)
-    L.check(L.lib().bsm_get_image(A._h.ptr, which, None, C.byref(n)))
-    buf = np.zeros(max(n.value, 1), dtype=np.uint8)
-    L.check(L.lib().bsm_get_image(A._h.ptr, which, buf.ctypes.data, C.byref(n)))
-    return buf[:n.value]
+SIZES = {"blocksparse": dict(n=400, nblocks=40, bs=12), "vbcrs": dict(n=3000, nblocks=160, lo=4, hi=40),
+         "vbcrs_from_blocksparse": dict(n=2000, nblocks=120, lo=4, hi=40), "symmetric": dict(nseg=10, bs=20, halfband=2),
+         "vbcrs_from_symmetric": dict(nseg=10, bs=20, halfband=2)}
 
 
 def _bookkeeping_equal(A, B):
@@ -114,16 +35,16 @@ def _bookkeeping_equal(A, B):
 @pytest.mark.parametrize("T_, S_", PAIRS)
 @pytest.mark.parametrize("ctor", CTORS)
 def test_mixed_image_equals_rounded_single_image(bsm, oracle, ctor, T_, S_):
-    p = _problem(bsm, ctor, T_)
-    A = _build(bsm, ctor, p, storage=S_)
-    As = _build(bsm, ctor, p, dtype_cast=S_)
-    At = _build(bsm, ctor, p)
+    p = ctor_problem(bsm, ctor, T_, SIZES)
+    A = ctor_build(bsm, ctor, p, device=NODEV, storage=S_)
+    As = ctor_build(bsm, ctor, cast_blocks(p, S_), device=NODEV)
+    At = ctor_build(bsm, ctor, p, device=NODEV)
     assert A.dtype == np.dtype(T_) and A.storage_dtype == np.dtype(S_)
     assert bsm.eltype(A) == np.dtype(T_)
     assert As.storage_dtype == As.dtype == np.dtype(S_)
     # the packed image: byte for byte the single-precision handle's (values, rows, cols)
     for which in (0, 1, 2):
-        assert np.array_equal(_img_bytes(A, which), _img_bytes(As, which)), f"image array {which}"
+        assert np.array_equal(img_bytes(A, which), img_bytes(As, which)), f"image array {which}"
     # reference bookkeeping: that of the double-precision handle (and of the single one -- it is value-blind)
     _bookkeeping_equal(A, At)
     for attr in ("perm", "rowptr", "colindices", "rowindices"):
@@ -139,7 +60,7 @@ def test_mixed_image_equals_rounded_single_image(bsm, oracle, ctor, T_, S_):
     assert st["alg_bytes"] == ss["alg_bytes"] + (nrows + ncols) * (tt - ts)
     assert st["device_bytes"] == ss["device_bytes"]  # (no gather workspace: values + metadata only)
     # the image decoded in fp64 against the oracle on the ROUNDED blocks
-    orc_p = _oracle_problem(ctor, _rounded(p, S_))
+    orc_p = ctor_oracle_problem(ctor, rounded(p, S_))
     rng = np.random.default_rng(11)
     n = A.size[0]
     x = rand_vec(rng, n, T_)
@@ -154,13 +75,13 @@ def test_mixed_image_equals_rounded_single_image(bsm, oracle, ctor, T_, S_):
 @pytest.mark.parametrize("T_, S_", PAIRS)
 @pytest.mark.parametrize("ctor", ["blocksparse", "vbcrs"])
 def test_mixed_transposed_image(bsm, oracle, ctor, T_, S_):
-    p = _problem(bsm, ctor, T_)
-    A = _build(bsm, ctor, p, storage=S_, transpose_image=1)
-    As = _build(bsm, ctor, p, dtype_cast=S_, transpose_image=1)
-    assert len(_img_bytes(A, 16)) > 16  # the handle has a transposed ordering
+    p = ctor_problem(bsm, ctor, T_, SIZES)
+    A = ctor_build(bsm, ctor, p, device=NODEV, storage=S_, transpose_image=1)
+    As = ctor_build(bsm, ctor, cast_blocks(p, S_), device=NODEV, transpose_image=1)
+    assert len(img_bytes(A, 16)) > 16  # the handle has a transposed ordering
     for which in (16, 17, 18):
-        assert np.array_equal(_img_bytes(A, which), _img_bytes(As, which)), f"transposed image array {which}"
-    orc_p = _oracle_problem(ctor, _rounded(p, S_))
+        assert np.array_equal(img_bytes(A, which), img_bytes(As, which)), f"transposed image array {which}"
+    orc_p = ctor_oracle_problem(ctor, rounded(p, S_))
     rng = np.random.default_rng(5)
     x = rand_vec(rng, A.size[0], T_)
     y0 = rand_vec(rng, A.size[1], T_)
@@ -173,11 +94,11 @@ def test_mixed_transposed_image(bsm, oracle, ctor, T_, S_):
 @pytest.mark.parametrize("ctor", ["symmetric", "vbcrs_from_symmetric"])
 def test_mixed_golden_fixtures(bsm, oracle, key, ctor):
     p = fixture_problem(key)  # ComplexF64 BEM near field (the reference's own fixture)
-    A = _build(bsm, ctor, p, storage=np.complex64)
-    As = _build(bsm, ctor, p, dtype_cast=np.complex64)
+    A = ctor_build(bsm, ctor, p, device=NODEV, storage=np.complex64)
+    As = ctor_build(bsm, ctor, cast_blocks(p, np.complex64), device=NODEV)
     for which in (0, 1, 2):
-        assert np.array_equal(_img_bytes(A, which), _img_bytes(As, which))
-    orc_p = _oracle_problem(ctor, _rounded(p, np.complex64))
+        assert np.array_equal(img_bytes(A, which), img_bytes(As, which))
+    orc_p = ctor_oracle_problem(ctor, rounded(p, np.complex64))
     rng = np.random.default_rng(3)
     x = rand_vec(rng, A.size[0], np.complex128)
     y0 = rand_vec(rng, A.size[0], np.complex128)
@@ -185,15 +106,15 @@ def test_mixed_golden_fixtures(bsm, oracle, key, ctor):
         ref = oracle_mul(oracle, orc_p, op, x, y0, 1j, 0.5, False)
         assert relerr(decode_mixed(A, op, x, y0, 1j, 0.5, False), ref) <= 1e-14
     # against the ORIGINAL blocks: within single-precision rounding, far from the fp64 result
-    ref = oracle_mul(oracle, _oracle_problem(ctor, p), N, x, y0)
+    ref = oracle_mul(oracle, ctor_oracle_problem(ctor, p), N, x, y0)
     err = relerr(decode_mixed(A, N, x, y0), ref)
     assert 1e-10 < err < 1e-5
 
 
 def test_mixed_gather_workspace_is_double(bsm):
-    p = _problem(bsm, "symmetric", np.float64)
-    A = _build(bsm, "symmetric", p, storage=np.float32, accumulate="gather")
-    As = _build(bsm, "symmetric", p, dtype_cast=np.float32, accumulate="gather")
+    p = ctor_problem(bsm, "symmetric", np.float64, SIZES)
+    A = ctor_build(bsm, "symmetric", p, device=NODEV, storage=np.float32, accumulate="gather")
+    As = ctor_build(bsm, "symmetric", cast_blocks(p, np.float32), device=NODEV, accumulate="gather")
     _, _, cols, waves = get_image(A)
     lead_rows = int(np.sum(waves["m"][(waves["work"] == WORK_PANEL) & (waves["lead"] == 1)]))
     slots = len(cols) + lead_rows + 8
@@ -213,16 +134,16 @@ def test_rounding_is_numpy_astype(bsm):
         with np.errstate(over="ignore"):
             bs = np.asfortranarray(b.astype(S_))
         As = M.VariableBlockCompressedRowStorage([bs], [1], [1], (16, 4), device=NODEV)
-        assert np.array_equal(_img_bytes(A, 0), _img_bytes(As, 0))
-        vals = _img_bytes(A, 0).view(S_)
+        assert np.array_equal(img_bytes(A, 0), img_bytes(As, 0))
+        vals = img_bytes(A, 0).view(S_)
         assert np.isinf(vals.real).sum() > 0 and np.any((vals.real != 0) & (np.abs(vals.real) < f32.tiny))
 
 
 def test_mixed_refusals(bsm):
     from bsm_amd import _lib as L
     lib = L.lib()
-    p = _problem(bsm, "blocksparse", np.float64)
-    A = _build(bsm, "blocksparse", p, storage=np.float32)
+    p = ctor_problem(bsm, "blocksparse", np.float64, SIZES)
+    A = ctor_build(bsm, "blocksparse", p, device=NODEV, storage=np.float32)
     # bsm_update_blocks: BSM_ERR_UNSUPPORTED, through the C ABI and the mirror
     ld = np.array([b.shape[0] for b in p["blocks"]], dtype=np.int64)
     ptrs = (C.c_void_p * len(p["blocks"]))(*[b.ctypes.data for b in A.blocks])
@@ -267,7 +188,7 @@ def test_mixed_refusals(bsm):
 
 def test_mirror_storage_keyword(bsm):
     M = bsm.matrices
-    p64 = _problem(bsm, "vbcrs_from_blocksparse", np.float64)
+    p64 = ctor_problem(bsm, "vbcrs_from_blocksparse", np.float64, SIZES)
     args = (p64["rowindices"], p64["colindices"], p64["size"])
     b32 = [np.asfortranarray(b.astype(np.float32)) for b in p64["blocks"]]
     bc = [np.asfortranarray(b.astype(np.complex128)) for b in p64["blocks"]]

@@ -7,10 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _common import get_image
+from _common import NODEV, get_image
+from _values import update_rc
 
 DTYPES = (np.float32, np.float64, np.complex64, np.complex128)
-NONE = -2  # BSM_DEVICE_NONE
 
 
 def rand_block(rng, m, n, dt):
@@ -26,7 +26,7 @@ def cuts(sizes):
 
 
 # every constructor as (name, shapes of the blocks in constructor order, make(values) -> mirror object)
-def problems(bsm, rng, dt, tim):
+def constructors(bsm, rng, dt, tim):
     S = bsm
     out = []
     # a grid of contiguous blocks: tall (> 64 rows: several chunks), odd widths (16-byte units shared by two blocks)
@@ -40,11 +40,11 @@ def problems(bsm, rng, dt, tim):
     rs = [rp[i][0] for i, _ in cells]
     cs = [cp[j][0] for _, j in cells]
     out.append(("vbcrs", shapes, lambda v: S.VariableBlockCompressedRowStorage(
-        v, rs, cs, (n, n), device=NONE, transpose_image=tim)))
+        v, rs, cs, (n, n), device=NODEV, transpose_image=tim)))
     rl = [np.arange(rp[i][0], rp[i][0] + rp[i][1]) for i, _ in cells]
     cl = [np.arange(cp[j][0], cp[j][0] + cp[j][1]) for _, j in cells]
     out.append(("vbcrs_from_blocksparse", shapes, lambda v: S.VariableBlockCompressedRowStorage(
-        S.BlockSparseMatrix(v, rl, cl, (n, n), device=NONE), device=NONE, transpose_image=tim)))
+        S.BlockSparseMatrix(v, rl, cl, (n, n), device=NODEV), device=NODEV, transpose_image=tim)))
     # symmetric on the row partition: diagonals, then the upper off-diagonal blocks
     offc = [(i, j) for i in range(len(rp)) for j in range(i + 1, len(rp)) if rng.random() < 0.6]
     dshapes = [(k, k) for _, k in rp]
@@ -56,17 +56,17 @@ def problems(bsm, rng, dt, tim):
         return dl, [dl[i] for i, _ in offc], [dl[j] for _, j in offc]
     dl, orl, ocl = sym_lists(np.arange(1, n + 1))
     out.append(("vbcrs_from_symmetric", dshapes + oshapes, lambda v: S.VariableBlockCompressedRowStorage(
-        S.SymmetricBlockMatrix(v[:nd], dl, v[nd:], orl, ocl, (n, n), device=NONE), device=NONE)))
+        S.SymmetricBlockMatrix(v[:nd], dl, v[nd:], orl, ocl, (n, n), device=NODEV), device=NODEV)))
     # scattered, unsorted index lists with blocks taller than 64 rows (permuted placement, multi-chunk blocks)
     ns = 900
     sh = [(70, 33), (5, 130), (64, 64), (130, 7), (3, 3), (66, 1)]
     srows = [rng.permutation(ns)[:m] + 1 for m, _ in sh]
     scols = [rng.permutation(ns)[:k] + 1 for _, k in sh]
     out.append(("blocksparse", sh, lambda v: S.BlockSparseMatrix(
-        v, srows, scols, (ns, ns), device=NONE, transpose_image=tim)))
+        v, srows, scols, (ns, ns), device=NODEV, transpose_image=tim)))
     sdl, sorl, socl = sym_lists(rng.permutation(n) + 1)
     out.append(("symmetric", dshapes + oshapes, lambda v: S.SymmetricBlockMatrix(
-        v[:nd], sdl, v[nd:], sorl, socl, (n, n), device=NONE)))
+        v[:nd], sdl, v[nd:], sorl, socl, (n, n), device=NODEV)))
     return out
 
 
@@ -87,22 +87,11 @@ def has_t(A):
     return L.lib().bsm_get_image(A._h.ptr, 16, None, C.byref(n)) == 0
 
 
-def raw_update(A, ids, blocks, lds, memspace=0, nupd=None):
-    from bsm_amd import _lib as L
-    I = C.POINTER(C.c_int64)
-    idv = None if ids is None else np.ascontiguousarray(ids, dtype=np.int64)
-    ptrs = (C.c_void_p * max(len(blocks), 1))(*[b.ctypes.data for b in blocks])
-    ldv = np.ascontiguousarray(lds, dtype=np.int64)
-    return L.lib().bsm_update_blocks(A._h.ptr, len(blocks) if nupd is None else nupd,
-                                     None if idv is None else idv.ctypes.data_as(I), ptrs, ldv.ctypes.data_as(I),
-                                     memspace, None)
-
-
 @pytest.mark.parametrize("dt", DTYPES, ids=lambda d: np.dtype(d).name)
 def test_full_and_subset_update_equal_a_fresh_handle(bsm, dt):
     rng = np.random.default_rng(20 + DTYPES.index(dt))
     for tim in (False, True):
-        for name, shapes, make in problems(bsm, rng, dt, tim):
+        for name, shapes, make in constructors(bsm, rng, dt, tim):
             va = [rand_block(rng, m, k, dt) for m, k in shapes]
             vb = [rand_block(rng, m, k, dt) for m, k in shapes]
             A = make([a.copy(order="F") for a in va])
@@ -128,7 +117,7 @@ def test_full_and_subset_update_equal_a_fresh_handle(bsm, dt):
                 newv.append(big)
                 lds.append(m + 3)
                 mixed[i - 1] = np.asfortranarray(big[:m, :])
-            assert raw_update(A, ids, newv, lds) == 0
+            assert update_rc(A, ids, newv, lds) == 0
             got = images(A, has_t(A))
             want = images(make(mixed), has_t(A))
             for k in ("values", "t_values"):
@@ -140,7 +129,7 @@ def test_errors_leave_the_handle_unchanged(bsm):
     from bsm_amd import _lib as L
     rng = np.random.default_rng(5)
     dt = np.float64
-    name, shapes, make = problems(bsm, rng, dt, True)[0]
+    name, shapes, make = constructors(bsm, rng, dt, True)[0]
     A = make([rand_block(rng, m, k, dt) for m, k in shapes])
     before = images(A, True)
     nb = len(shapes)
@@ -149,27 +138,27 @@ def test_errors_leave_the_handle_unchanged(bsm):
     I = C.POINTER(C.c_int64)
     cases = [
         lambda: L.lib().bsm_update_blocks(None, 1, None, None, None, 0, None),   # null handle
-        lambda: raw_update(A, [1, nb + 1], good[:2], lds[:2]),                   # id out of range
-        lambda: raw_update(A, [0], good[:1], lds[:1]),                           # ids are 1-based
-        lambda: raw_update(A, [2, 1, 2], good[:3], lds[:3]),                     # duplicate id
-        lambda: raw_update(A, None, good[:-1], lds[:-1]),                        # ids == NULL needs every block
-        lambda: raw_update(A, [1, 2], good[:2], [lds[0], shapes[1][0] - 1]),    # ld < m
-        lambda: raw_update(A, None, good, lds, memspace=7),                      # bad memspace
-        lambda: raw_update(A, None, good, lds, memspace=1),                      # device blocks, no device
+        lambda: update_rc(A, [1, nb + 1], good[:2], lds[:2]),                   # id out of range
+        lambda: update_rc(A, [0], good[:1], lds[:1]),                           # ids are 1-based
+        lambda: update_rc(A, [2, 1, 2], good[:3], lds[:3]),                     # duplicate id
+        lambda: update_rc(A, None, good[:-1], lds[:-1]),                        # ids == NULL needs every block
+        lambda: update_rc(A, [1, 2], good[:2], [lds[0], shapes[1][0] - 1]),    # ld < m
+        lambda: update_rc(A, None, good, lds, memspace=7),                      # bad memspace
+        lambda: update_rc(A, None, good, lds, memspace=1),                      # device blocks, no device
         lambda: L.lib().bsm_update_blocks(A._h.ptr, nb, None, None, np.ascontiguousarray(lds, dtype=np.int64).ctypes.data_as(I), 0, None),
-        lambda: raw_update(A, [1], good[:1], lds[:1], nupd=-1),                  # negative count
+        lambda: update_rc(A, [1], good[:1], lds[:1], nupd=-1),                  # negative count
     ]
     for k, call in enumerate(cases):
         assert call() == -1, k  # BSM_ERR_INVALID
         assert images(A, True) == before, k
-    assert raw_update(A, [], [], []) == 0  # nothing to do is not an error
+    assert update_rc(A, [], [], []) == 0  # nothing to do is not an error
     assert images(A, True) == before
 
 
 @pytest.mark.parametrize("dt", (np.float64, np.complex64), ids=lambda d: np.dtype(d).name)
 def test_refresh_after_in_place_edit_equals_update_blocks(bsm, dt):
     rng = np.random.default_rng(9)
-    for name, shapes, make in problems(bsm, rng, dt, True):
+    for name, shapes, make in constructors(bsm, rng, dt, True):
         va = [rand_block(rng, m, k, dt) for m, k in shapes]
         A = make([a.copy(order="F") for a in va])
         Bm = make([a.copy(order="F") for a in va])
@@ -194,7 +183,7 @@ def test_vbcrs_mirror_edit_of_sorted_blocks(bsm):
     """A.blocks of a VBCRS is the SORTED view of the constructor's list: an in-place edit of A.blocks[k] is an edit of
     constructor block perm[k], and refresh pushes it there."""
     rng = np.random.default_rng(3)
-    name, shapes, make = problems(bsm, rng, np.float64, False)[0]
+    name, shapes, make = constructors(bsm, rng, np.float64, False)[0]
     va = [rand_block(rng, m, k, np.float64) for m, k in shapes]
     A = make([a.copy(order="F") for a in va])
     k = len(shapes) // 2
@@ -213,8 +202,8 @@ def test_materialized_symmetric_vbcrs_refuses_updates(bsm):
     d = [rand_block(rng, 3, 3, np.float64), rand_block(rng, 2, 2, np.float64)]
     o = [rand_block(rng, 3, 2, np.float64)]
     S = bsm.SymmetricBlockMatrix(d, [np.arange(1, 4), np.arange(4, 6)], o, [np.arange(1, 4)], [np.arange(4, 6)], (5, 5),
-                                 device=NONE)
-    V = bsm.VariableBlockCompressedRowStorage(S, device=NONE, materialize=True)
+                                 device=NODEV)
+    V = bsm.VariableBlockCompressedRowStorage(S, device=NODEV, materialize=True)
     with pytest.raises(NotImplementedError):
         bsm.refresh(V)
     with pytest.raises(NotImplementedError):
