@@ -54,10 +54,9 @@ struct Plan {
 
 }  // namespace
 
-struct Part {
-    int device = 0;
-    Analysis an;
-    DeviceImage img;
+// the part's operator on its device (`device` is set for every part; one that holds no block is never built), and what
+// the fan-out adds to it
+struct Part : LocalOperator {
     bool has_image = false;
     int64_t nblocks = 0;
     Range own;         // rows it owns
@@ -68,13 +67,10 @@ struct Part {
     bool w_clean = false;               // d_w is zero everywhere (DistState::rezero)
     void *d_x = nullptr, *d_w = nullptr, *d_recv = nullptr;
     Range colpart;  // the part's share of the COLUMN partition (vectors of length ncols held in parts)
-    // work arrays of the interleaved multi-RHS pass (bsm_kernels.h: ILWork) of this part's image, allocated at the first
-    // multi-RHS product that takes it.  A part's successive products are ordered by the fan-out itself (a product waits for
-    // the part's own previous delivery, or everything runs on one stream), which is all the arrays need.
-    ILWork il;
+    // The work arrays of the interleaved multi-RHS pass (LocalOperator::il) need no claim here: a part's successive
+    // products are ordered by the fan-out itself (a product waits for the part's own previous delivery, or everything
+    // runs on one stream).
     bool il_failed = false;  // no memory for them: the ordinary kernels from then on
-    UpdateState upd;  // bsm_update_blocks on this part's device
-    std::unique_ptr<UpdateInputs> upd_in;
 };
 
 // the part's work arrays if its image / this product take the interleaved pass (and they can be had), else null.
@@ -346,9 +342,8 @@ void dist_destroy(bsm_matrix_s *A) {
         DeviceGuard g;
         (void)g.enter(p.device);
         if (p.stream) (void)hipStreamSynchronize(p.stream);
-        update_free(p.upd);
-        free_image(p.img);
-        for (void *q : {p.d_x, p.d_w, p.d_recv, p.il.xr, p.il.w})
+        p.release();
+        for (void *q : {p.d_x, p.d_w, p.d_recv})
             if (q) (void)hipFree(q);
         if (p.ev_prod) (void)hipEventDestroy(p.ev_prod);
         if (p.ev_done) (void)hipEventDestroy(p.ev_done);
@@ -451,21 +446,9 @@ int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t n
             // the image defines (scales / overwrites) every row it touches plus the rows it owns
             po.own_lo = D.plan_n.zr[p].lo + 1;
             po.own_hi = D.plan_n.zr[p].hi;
-            const bool devblocks = (o.blocks_memspace == BSM_MEM_DEVICE);
-            std::unique_ptr<ValueSink> sink;
-            if (!devblocks) sink = make_device_sink(&pt.img.d_values);
-            AnalysisOptions ao = to_aopt(po, sink.get());
-            ao.skip_colors = true;
-            std::string err = pt.an.build(mtype, dtype, nrows, ncols, subs[p], ao);
-            if (!err.empty()) return build_error("device part " + std::to_string(p) + ": " + err);
-            pt.upd_in = keep_inputs(mtype, dtype, nrows, ncols, subs[p], sub_ids[p], (int64_t)in.size(), ao, nullptr);
-            if (devblocks) {  // the blocks may live on another device of the context: read over xGMI
-                e = device_pack(pt.an, &pt.img.d_values);
-                if (e != hipSuccess) return hip_fail(e, "device-side packing");
-            }
-            fill_image(pt.an, po, true, pt.img);
-            e = upload_image(pt.an, pt.img, pt.device);
-            if (e != hipSuccess) return hip_fail(e, "device upload");
+            int rc = pt.build(mtype, dtype, nrows, ncols, subs[p], sub_ids[p], (int64_t)in.size(), po, false,
+                              "device part " + std::to_string(p) + ": ");
+            if (rc != BSM_OK) return rc;
         }
         e = hipStreamCreateWithFlags(&pt.stream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&pt.ev_prod, hipEventDisableTiming);
@@ -1212,15 +1195,13 @@ int dist_update(bsm_matrix_s *A, int64_t nupd, const int64_t *ids, bool full, co
     hipError_t e = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = drain_handle(D);
     if (e != hipSuccess) return hip_fail(e, "update: drain");
-    const int64_t nb = (int64_t)A->blk_m.size();
     std::vector<int64_t> pid;
     std::vector<const void *> pblk;
     std::vector<int64_t> pld;
     for (auto &pp : D.parts) {
         Part &pt = *pp;
         if (!pt.has_image) continue;
-        Analysis *an[1] = {&pt.an};
-        int rc0 = ensure_plans(pt.upd, *pt.upd_in, an, 1);
+        int rc0 = pt.ensure_plans();
         if (rc0 != BSM_OK) return rc0;
         const RefillPlan &R = pt.upd.plan[0];
         pid.clear();
@@ -1238,9 +1219,7 @@ int dist_update(bsm_matrix_s *A, int64_t nupd, const int64_t *ids, bool full, co
         DeviceGuard g;
         e = g.enter(pt.device);
         if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        DeviceImage *img[1] = {&pt.img};
-        int rc = refill_images(pt.upd, *pt.upd_in, an, img, 1, nb, (int64_t)pid.size(), pid.data(), full, pblk.data(), pld.data(),
-                               A->blk_m.data(), A->blk_n.data(), memspace, pt.stream);
+        int rc = pt.refill((int64_t)pid.size(), pid.data(), full, pblk.data(), pld.data(), memspace, pt.stream, A->blk_m, A->blk_n);
         if (rc != BSM_OK) return rc;
         e = hipStreamSynchronize(pt.stream);
         if (e != hipSuccess) return hip_fail(e, "update: refill");

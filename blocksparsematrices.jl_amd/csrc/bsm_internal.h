@@ -1,5 +1,6 @@
-// bsm_internal.h -- what bsm_capi.cpp (single-device handles) and bsm_dist.cpp (handles spread
-// over the devices of a bsm_ctx_t) share.  Not part of the C ABI.
+// bsm_internal.h -- what bsm_capi.cpp (the C ABI; single-device handles), bsm_dist.cpp (handles spread over the
+// devices of a bsm_ctx_t) and bsm_operator.cpp (the packed operator on one device that both are made of) share.
+// Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -41,10 +42,6 @@ struct UpdateInputs {
     std::vector<BlockIn> in;
     std::vector<std::vector<int64_t>> lists;
 };
-// ids[b]: input block id (position in the *_create call) of in[b]
-std::unique_ptr<UpdateInputs> keep_inputs(int mtype, int dtype, int64_t nrows, int64_t ncols, const std::vector<BlockIn> &in,
-                                          const std::vector<int64_t> &ids, int64_t nids, const AnalysisOptions &ao,
-                                          const AnalysisOptions *ao_t);
 struct UpdateState {
     RefillPlan plan[2];   // host plans (built at the first update)
     RefillDevice img[2];  // forward image, transposed image
@@ -64,17 +61,43 @@ struct UpdateState {
     bool cap_valid = false;
     int64_t cap_list_len = -1;
 };
-void update_free(UpdateState &U);
-// builds U.plan[0..nimg) from the kept inputs (an[k]: the image's own analysis, which the plan is checked against)
-int ensure_plans(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, int nimg);
-// host refill of an analysis-only image (Analysis::values) through plan P
-void refill_host(const Analysis &an, const RefillPlan &P, RawBuffer &values, int64_t nupd, const int64_t *ids,
-                 const void *const *src, const int64_t *ld);
-// Refills images img[0..nimg) (analyses an[]) on the CURRENT device from blocks[k] / ld[k] for the 0-based input ids
-// ids[k] (full: every id 0..nids-1 in order).  BSM_MEM_DEVICE: enqueued on `st`; BSM_MEM_HOST: staged, synchronous.
-int refill_images(UpdateState &U, const UpdateInputs &inp, Analysis *const *an, DeviceImage *const *img, int nimg, int64_t nids, int64_t nupd,
-                  const int64_t *ids, bool full, const void *const *blocks, const int64_t *ld, const int64_t *bm,
-                  const int64_t *bn, int memspace, hipStream_t st);
+
+// A packed operator on one device: what a single-device handle is, and what every part of a multi-device handle is
+// (bsm_operator.cpp).  Built once, refilled by bsm_update_blocks, released with its device current.
+struct LocalOperator {
+    // HIP ordinal of the images, set before build(); BSM_DEVICE_NONE: analysis only (the packed values stay in
+    // Analysis::values).  A part that holds no block keeps its ordinal and is never built.
+    int device = BSM_DEVICE_NONE;
+    Analysis an;
+    DeviceImage img;
+    // optional second ordering (bsm_options.transpose_image): the transposed operator as its own forward image
+    bool has_t = false;
+    Analysis an_t;
+    DeviceImage img_t;
+    // bsm_update_blocks: the kept block list and the refill state on `device`
+    std::unique_ptr<UpdateInputs> upd_in;
+    UpdateState upd;
+    // work arrays of the interleaved multi-RHS pass (bsm_kernels.h: ILWork), allocated at the first product that takes it
+    ILWork il;
+
+    // Analysis, packing and upload of `in` (the block list in its final order; ids[b]: input block id of in[b], of nids
+    // in the whole *_create call) on `device`, which must be current.  Host blocks are streamed to the device while they
+    // are packed, device blocks (o.blocks_memspace) are packed there by a kernel.  colors: compute the reference
+    // colourings; prefix: put in front of an analysis error ("device part 3: ").  BSM_OK, or the code of the error set;
+    // whatever a failed build leaves behind goes with release().
+    int build(int mtype, int dtype, int64_t nrows, int64_t ncols, const std::vector<BlockIn> &in, const std::vector<int64_t> &ids,
+              int64_t nids, const bsm_options &o, bool colors, const std::string &prefix);
+    // Frees both images, the refill state and the work arrays; `device` must be current.
+    void release();
+    // Replaces the values of the blocks with the 0-based input ids ids[k] by blocks[k] / ld[k] (full: every id 0..nids-1
+    // in order).  bm / bn: stored shape of every input block.
+    // BSM_MEM_DEVICE: enqueued on `st`; BSM_MEM_HOST: staged, synchronous; analysis-only operators: host blocks only,
+    // Analysis::values is rewritten.
+    int refill(int64_t nupd, const int64_t *ids, bool full, const void *const *blocks, const int64_t *ld, int memspace, hipStream_t st,
+               const std::vector<int64_t> &bm, const std::vector<int64_t> &bn);
+    // builds upd.plan[] from the kept inputs at the first update (refill() calls it; dist_update reads plan[0] first)
+    int ensure_plans();
+};
 }
 
 namespace bsm {
@@ -86,20 +109,15 @@ struct ClaimState {
 };
 }  // namespace bsm
 
-struct bsm_matrix_s {
-    bsm::Analysis an;  // multi-device handles: bookkeeping / statistics of the WHOLE operator, no image
-    bsm::DeviceImage img;
+// The operator of a single-device handle is the handle's base.  Multi-device handles: `an` holds the bookkeeping /
+// statistics of the WHOLE operator, there is no image (device == BSM_DEVICE_NONE) and every part is an operator of
+// its own (bsm_dist.cpp: Part).
+struct bsm_matrix_s : bsm::LocalOperator {
     bool on_device = false;
-    // optional second ordering (bsm_options.transpose_image): the transposed operator as its own
-    // forward image
-    bool has_t = false;
-    bsm::Analysis an_t;
-    bsm::DeviceImage img_t;
     // one product in flight per handle on the gather workspace of the images (one-column products) and on the work
     // arrays of the interleaved multi-RHS pass (bsm_kernels.h: ILWork, allocated at the first product that takes it):
     // bsm_capi.cpp: Claim
     bsm::ClaimState ws_claim, il_claim;
-    bsm::ILWork il;
     // device staging buffers of the BSM_MEM_HOST path, kept between calls (grow-only); a second
     // concurrent host call on the same handle falls back to temporary buffers
     std::mutex host_mu;
@@ -107,11 +125,9 @@ struct bsm_matrix_s {
     size_t stage_x_bytes = 0, stage_y_bytes = 0;
     // handle spread over the devices of a context (bsm_options.ctx)
     std::unique_ptr<bsm::DistState> dist;
-    // bsm_update_blocks: stored shape of every input block (constructor order) and the device state of the refill
+    // bsm_update_blocks: stored shape of every input block (constructor order); one update at a time
     std::vector<int64_t> blk_m, blk_n;
     std::mutex upd_mu;
-    std::unique_ptr<bsm::UpdateInputs> upd_in;
-    bsm::UpdateState upd;
     bsm_matrix_s();
     ~bsm_matrix_s();
 };
@@ -130,12 +146,6 @@ struct DeviceGuard {
 };
 
 AnalysisOptions to_aopt(const bsm_options &o, ValueSink *sink);
-void fill_image(const Analysis &an, const bsm_options &o, bool use_own, DeviceImage &img);
-hipError_t upload_image(Analysis &an, DeviceImage &img, int dev);
-void free_image(DeviceImage &img);
-hipError_t device_pack(Analysis &an, void **d_values);  // blocks_on_device: run the pack plan on the current device
-// the value sink of a device handle (pinned staging windows + asynchronous upload); nullptr for none
-std::unique_ptr<ValueSink> make_device_sink(void **d_values);
 // whether `st` is being captured into a graph (a failed query counts as "no")
 bool capturing(hipStream_t st);
 // the work arrays of the interleaved multi-RHS pass hold `need` vector entries (Xr, W: 128 bytes per entry each); a

@@ -3,7 +3,7 @@
 // The placement is what the pack plan of a device-block create (Analysis::pack_plan) records, with the source named by
 // input block id (position in the *_create call) instead of an address, so that the same plan refills the image from
 // whatever arrays hold the new values.  It is derived at the first update of a handle by re-running the value-blind
-// analysis on the block list kept from creation (bsm_capi.cpp: make_refill_plan) and checked against the image.
+// analysis on the block list kept from creation (bsm_operator.cpp: make_refill_plan) and checked against the image.
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -354,8 +354,8 @@ def test_multi_rhs_real_fused_and_transposed_tile_pipeline(torch_cuda, bsm, orac
 
 def test_multi_rhs_interleaved_pass_state_and_ownership(torch_cuda, bsm, oracle):
     """The interleaved multi-RHS pass (csrc/bsm_il.hip: panel_kernel_il -- X and the accumulated Y row-major in work
-    arrays of the handle, csrc/bsm_capi.cpp: ILClaim): what the oracle comparisons of the other multi-RHS tests do not
-    reach --
+    arrays of the handle, csrc/bsm_internal.h: LocalOperator::il, claimed by csrc/bsm_capi.cpp: Claim): what the oracle
+    comparisons of the other multi-RHS tests do not reach --
       * the work arrays are kept and re-used: alternating ops, batch widths and component counts (8 / 16 per index) on ONE
         handle, rectangular operator (x and y of different lengths), the accumulator must be zero again after every pass;
       * one product in flight per handle: two streams issuing on the same handle without synchronisation -- the one that
@@ -751,7 +751,7 @@ def test_gather_mode_two_streams_share_one_workspace(torch_cuda, bsm, oracle):
 
 def test_streamed_upload_matches_one_shot_upload(torch_cuda, bsm, oracle, monkeypatch):
     # large operators are packed window by window into pinned staging and copied while the next
-    # window is packed (bsm_capi.cpp DeviceSink); forced here on small operators with tiny windows
+    # window is packed (bsm_operator.cpp DeviceSink); forced here on small operators with tiny windows
     monkeypatch.setenv("BSM_STREAM_MIN_BYTES", "1")
     monkeypatch.setenv("BSM_UPLOAD_WINDOW_BYTES", "20000")
     for p, dt, kw in ((bsm.synthetic.config2(n=20000, nblocks=900), np.float64, {"transpose_image": True}),
