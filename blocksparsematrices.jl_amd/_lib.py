@@ -58,7 +58,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_symmetric_create", "bsm_mul", "bsm_mul_multi", "bsm_mul_parts",
            "bsm_mul_cvec", "bsm_mul_multi_cvec", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
            "bsm_color", "bsm_destroy", "bsm_last_error", "bsm_version",
-           "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks", "bsm_value_passes"]
+           "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks", "bsm_value_passes",
+           "bsm_submatrices", "bsm_diag"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -153,6 +154,10 @@ def lib():
     if hasattr(L, "bsm_value_passes") or "BSM_LIB" not in os.environ:
         L.bsm_value_passes.argtypes = [C.c_void_p, _I64P]
         L.bsm_value_passes.restype = C.c_int
+    if hasattr(L, "bsm_submatrices") or "BSM_LIB" not in os.environ:
+        L.bsm_submatrices.argtypes = [C.c_void_p, C.c_int, C.c_int64, _PP, _I64P, _PP, _I64P, _PP, _I64P, C.c_int, C.c_void_p]
+        L.bsm_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.bsm_submatrices.restype = L.bsm_diag.restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p
     L.bsm_version.restype = C.c_char_p

@@ -100,6 +100,26 @@ hipError_t launch_export_coo(int dtype, const void *d_waves, long long nwaves, c
                              const void *d_values, const void *d_rows, const void *d_cols, void *orow, void *ocol,
                              void *oval, hipStream_t stream);
 
+// bsm_submatrices / bsm_diag (bsm_extract.hip): entries of the operator added into caller windows, from the packed
+// device image.  maps: the set (-1: not requested) and the position inside it of every row / column of the STORED
+// operator (device arrays, nrows / ncols int32 each); d_table: one ExtractOut per set.  Entry (r, c) with rset[r] ==
+// cset[c] = s goes to table[s].ptr[rpos[r] + ld * cpos[c]] (opT: [cpos[c] + ld * rpos[r]]; conj: conjugated).
+// maps == nullptr: diag(A) -- every entry with r == c is added to d_diag[r].  The windows must be zero beforehand.
+struct ExtractMaps {
+    const int *rset, *rpos, *cset, *cpos;
+};
+struct ExtractOut {
+    uint64_t ptr;  // device address of the window's first element (vector type of the image)
+    long long ld;
+};
+static_assert(sizeof(ExtractOut) == 16, "ExtractOut must be 16 bytes");
+hipError_t launch_extract(int dtype, const void *d_waves, long long nwaves, const void *d_values, const void *d_rows,
+                          const void *d_cols, const ExtractMaps *maps, const void *d_table, void *d_diag, long long nrows,
+                          long long ncols, bool opT, bool conj, hipStream_t stream);
+// the ni x nj window of every set = 0: d_shape = {ni, nj} int64 pairs, vt the vector type, largest = max ni * nj
+hipError_t launch_zero_windows(int vt, const void *d_table, const void *d_shape, long long nsets, long long largest,
+                               hipStream_t stream);
+
 // executes Analysis::pack_plan on the device (blocks already in HBM): d_plan = PackChunk[nchunks],
 // d_colpos = int32 placements (may be null when no chunk is scattered), es = stored element bytes, src_es = the caller's
 // (= es, or 2 es for the mixed-precision dtypes: the values are rounded to the stored type as they are placed)

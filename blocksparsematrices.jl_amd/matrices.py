@@ -38,7 +38,7 @@ __all__ = [
     "eachdiagonalindex", "eachoffdiagonalindex", "diagonalindices", "diagonalcolors",
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
-    "update_blocks", "refresh",
+    "update_blocks", "refresh", "submatrices", "submatrix", "diag",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -305,9 +305,15 @@ class _LinearMap:
         return adjoint(self)
 
     def __getitem__(self, key):
-        """A[:, :] -- LinearMaps materialises through products with unit vectors."""
-        if key != (slice(None), slice(None)):
-            raise IndexError("only A[:, :] is supported")
+        """A[:, :] -- LinearMaps materialises through products with unit vectors.
+        Every other key reads the entries out of the packed image in one pass (submatrices): Python indexing, 0-BASED,
+        each axis key taken as numpy takes it on that axis -- ints (negative ones too; an int drops its axis), slices
+        with steps, integer arrays, boolean masks; a key numpy refuses raises what numpy raises.  Two index arrays
+        select the sub-matrix A[np.ix_(I, J)] like the reference's A[I, J], not numpy's pointwise pairing."""
+        if not (isinstance(key, tuple) and len(key) == 2):
+            raise IndexError("a block matrix takes two indices: A[i, j]")
+        if not all(isinstance(k, slice) and k == slice(None) for k in key):
+            return _getitem(self, key)
         m, n = size(self)
         dt = eltype(self)
         out = np.zeros((m, n), dtype=dt, order="F")
@@ -1096,6 +1102,90 @@ def nnz(A):
     """SparseArrays.nnz -- src/blockmatrix.jl:208-223, src/symmetricblockmatrix.jl:367-384
     (off-diagonal blocks count twice), src/vbcrs.jl:290-296."""
     return int(_unwrap(A)[0].stats()["nnz"])
+
+
+# ---- entries of the operator, read out of the packed image (bsm_submatrices / bsm_diag) ------------------------------
+def _out_device(base):
+    return torch.device("cuda", base.device if base.devices is None else base.devices[0])
+
+
+def submatrices(A, rowsets, colsets=None, device=False):
+    """[A[I_s, J_s] for s] in ONE pass over the packed image (bsm_submatrices).  rowsets / colsets: lists of 1-BASED
+    index lists, like rowindices(A, i); colsets=None means the row sets again, so
+    `submatrices(S, [diagonalindices(S, d) for d in eachdiagonalindex(S)])` gives the block-Jacobi blocks.  The row sets
+    must be pairwise disjoint and free of repeats, and so must the column sets.  Overlapping blocks add, like sparse(A).
+    Returns column-major numpy arrays; device=True: torch tensors on the handle's device, written there by the kernel
+    on torch's current stream.  Synchronous.  transpose(A) / adjoint(A) are taken as such."""
+    base, op = _unwrap(A)
+    if not isinstance(base, AbstractBlockMatrix):
+        raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
+    rs = [_i64(np.asarray(r).reshape(-1)) for r in rowsets]
+    cs = rs if colsets is None else [_i64(np.asarray(c).reshape(-1)) for c in colsets]
+    if len(rs) != len(cs):
+        raise ValueError("one column set per row set")
+    n, dt = len(rs), base.dtype
+    ni, nj = _i64([len(r) for r in rs]), _i64([len(c) for c in cs])
+    ld = np.maximum(ni, 1)
+    outp = (C.c_void_p * max(n, 1))()
+    st = None
+    if device:
+        if torch is None or base.device is None and base.devices is None:
+            raise ValueError("device=True needs a handle with a device image")
+        dev = _out_device(base)
+        outs = [torch.empty((int(b), int(a)), dtype=_TORCH_OF[dt], device=dev).t() for a, b in zip(ni, nj)]
+        for s, o in enumerate(outs):
+            outp[s] = o.data_ptr() if o.numel() else None
+        st = torch.cuda.current_stream(dev).cuda_stream
+    else:
+        outs = [np.empty((int(a), int(b)), dtype=dt, order="F") for a, b in zip(ni, nj)]
+        for s, o in enumerate(outs):
+            outp[s] = o.ctypes.data if o.size else None
+    I = C.POINTER(C.c_int64)
+    L.check(L.lib().bsm_submatrices(base._h.ptr, op, n, _ptrs(rs), ni.ctypes.data_as(I), _ptrs(cs), nj.ctypes.data_as(I),
+                                    outp, ld.ctypes.data_as(I), L.BSM_MEM_DEVICE if device else L.BSM_MEM_HOST, st))
+    return outs
+
+
+def submatrix(A, I, J, device=False):
+    """A[I, J] for 1-BASED index lists without repeats (one set of submatrices)."""
+    return submatrices(A, [I], [J], device)[0]
+
+
+def diag(A, device=False):
+    """LinearAlgebra.diag(A): the min(size) diagonal entries, read out of the packed image (bsm_diag); only the strips
+    that cross the diagonal are loaded.  device=True: a torch tensor on the handle's device."""
+    base, op = _unwrap(A)
+    if not isinstance(base, AbstractBlockMatrix):
+        raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
+    n, dt = min(base.size), base.dtype
+    if device:
+        if torch is None or base.device is None and base.devices is None:
+            raise ValueError("device=True needs a handle with a device image")
+        dev = _out_device(base)
+        d = torch.empty(n, dtype=_TORCH_OF[dt], device=dev)
+        L.check(L.lib().bsm_diag(base._h.ptr, d.data_ptr() if n else None, L.BSM_MEM_DEVICE,
+                                 torch.cuda.current_stream(dev).cuda_stream))
+    else:
+        d = np.empty(n, dtype=dt)
+        L.check(L.lib().bsm_diag(base._h.ptr, d.ctypes.data if n else None, L.BSM_MEM_HOST, None))
+    return d.conj() if op == L.BSM_OP_C and dt.kind == "c" else d
+
+
+def _getitem(A, key):
+    """A[key] for every key but (:, :) -- see _LinearMap.__getitem__"""
+    m, n = size(A)
+    ri, ci = np.arange(m)[key[0]], np.arange(n)[key[1]]
+    if np.ndim(ri) > 1 or np.ndim(ci) > 1:
+        raise IndexError("an axis key must select a scalar or a 1-D set of indices")
+    # repeated indices are extracted once and expanded here
+    ru, rinv = np.unique(np.atleast_1d(ri), return_inverse=True)
+    cu, cinv = np.unique(np.atleast_1d(ci), return_inverse=True)
+    out = submatrix(A, ru + 1, cu + 1)[np.ix_(rinv.reshape(-1), cinv.reshape(-1))]
+    if np.ndim(ci) == 0:
+        out = out[:, 0]
+    if np.ndim(ri) == 0:
+        out = out[0]
+    return out
 
 
 # ---- conversion used by the reference's tests as their oracle (host utility, not the hot path) ----

@@ -453,6 +453,45 @@ int bsm_get_bookkeeping(bsm_matrix_t A, int which, int64_t *out, int64_t *len);
 int bsm_rowcolvals(bsm_matrix_t A, int64_t *rows, int64_t *cols, void *vals, int64_t *count, int memspace,
                    void *stream);
 
+/* A[I, J]: entries of the operator read out of its packed image --
+ *   out[s][a + b * ldo[s]] = op(A)[I[s][a], J[s][b]]   for a < ni[s], b < nj[s], s < nsets
+ * in ONE pass over the image, whatever nsets is: what `A[i, j]`, `A[:, j]`, `A[I, J]` of the reference's LinearMap
+ * surface and the self-interaction blocks A[I_k, I_k] of a block-Jacobi / near-field preconditioner ask for (by unit
+ * vectors: one pass per 8 or 16 requested columns).  The pass reads only the strips that hold a requested column of a
+ * requested row's set.
+ *   Index lists: I, J, ni, nj, ldo and the `out` pointer array are host memory.  Indices are 1-based int64, in any
+ *     order; I[s] indexes rows of op(A), J[s] its columns.  The row sets must be pairwise disjoint and free of repeats,
+ *     and so must the column sets (a row then belongs to at most one set: that is what lets one pass serve every set; a
+ *     binding expands repeated indices itself).  ni[s] == 0 or nj[s] == 0 is legal and out[s] may then be NULL;
+ *     ldo[s] >= max(ni[s], 1).
+ *   Values: the sum of every stored entry at that position -- overlapping blocks of a BlockSparseMatrix add, as in
+ *     sparse(A) (reference src/sparse.jl:127-129) and in mul!'s +=; an off-diagonal block of a symmetric operator counts
+ *     at (r, c) and, transposed and not conjugated, at (c, r): the enumeration of bsm_rowcolvals.  op T swaps the roles
+ *     of the index lists, op C also conjugates.  The element type is the handle's vector type T; mixed-precision handles
+ *     deliver the stored value widened (exactly blocks.astype(S).astype(T)).  Where several stored entries meet, the
+ *     last bits depend on the order of the adds.
+ *   Output: the ni x nj window of every out[s] is OVERWRITTEN (zeroed, then summed: NaN in the incoming buffer does not
+ *     survive); no byte outside the windows is written, the ldo padding included.
+ *   memspace: where the out[s] arrays live.  BSM_MEM_DEVICE: on the handle's device, the work goes on `stream`.  The
+ *     call is SYNCHRONOUS either way, like bsm_rowcolvals: it uploads its maps (4 bytes per row and per column, twice)
+ *     and is a setup-time call, not to be graph-captured.
+ *   Analysis-only handles (BSM_DEVICE_NONE) answer BSM_MEM_HOST calls from their host image.
+ *   Multi-device handles (bsm_options.ctx): every stored entry lives in exactly one part, so the parts run one after
+ *     another, each into a zeroed staging buffer on its own device; the buffers return to the host, are added there and
+ *     delivered (to host or device windows).  Cost linear in the OUTPUT size per part, on top of the pass.
+ *   What is read: the forward image only.  A transpose_image handle, any accumulate mode and an own_lo / own_hi slice
+ *     give the entries of the blocks the handle holds.
+ * Every argument is checked before the first byte is written.  BSM_ERR_INVALID: null handle or pointer, bad op or
+ * memspace, an index outside 1..size(op(A), dim), an index in two sets or twice in one, ldo too small, nsets < 0,
+ * BSM_MEM_DEVICE on an analysis-only handle. */
+int bsm_submatrices(bsm_matrix_t A, int op, int64_t nsets, const int64_t *const *I, const int64_t *ni,
+                    const int64_t *const *J, const int64_t *nj, void *const *out, const int64_t *ldo, int memspace,
+                    void *stream);
+/* diag(A): d[k] = A[k + 1, k + 1], k < min(nrows, ncols) -- the same pass without index lists (values, memspace,
+ * synchronisation, handle kinds and refusals as bsm_submatrices; d is overwritten).  Only the strips that cross the
+ * diagonal are read. */
+int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

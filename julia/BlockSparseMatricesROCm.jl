@@ -496,4 +496,58 @@ end
 LinearMaps._unsafe_mul!(y::AbstractVector, A::ROCmViewOp, x::AbstractVector) =
     LinearMaps._unsafe_mul!(y, A, x, true, false)
 
+# ---- A[I, J] and diag(A): entries read out of the packed image ---------------------------------------------------
+# LinearMaps answers getindex with one product per requested column (unit vectors); bsm_submatrices reads the
+# entries in ONE pass over the image, and only the strips that hold a requested column.  Host results, synchronous.
+const ROCmAnyOp = Union{ROCmOp{<:ROCmMat},ROCmViewOp}
+
+"""
+    submatrices(A, rowsets, colsets=rowsets)
+
+`[A[I, J] for (I, J) in zip(rowsets, colsets)]` in one pass over the image.  The row sets must be pairwise disjoint
+and free of repeats, and so must the column sets: `submatrices(S, S.diagonalindices)` gives the block-Jacobi blocks
+of a SymmetricBlockMatrix.  Overlapping blocks add, like `sparse(A)`.
+"""
+function submatrices(A::ROCmAnyOp, rowsets, colsets=rowsets)
+    T = eltype(_base(A))
+    length(rowsets) == length(colsets) || throw(DimensionMismatch("one column set per row set"))
+    I = [collect(Int64, r) for r in rowsets]; J = [collect(Int64, c) for c in colsets]
+    outs = [Matrix{T}(undef, length(i), length(j)) for (i, j) in zip(I, J)]
+    ni = Int64[length(i) for i in I]; nj = Int64[length(j) for j in J]
+    GC.@preserve I J outs _check(ccall((:bsm_submatrices, libbsm), Cint,
+        (Ptr{Cvoid}, Cint, Int64, Ptr{Ptr{Int64}}, Ptr{Int64}, Ptr{Ptr{Int64}}, Ptr{Int64}, Ptr{Ptr{Cvoid}}, Ptr{Int64},
+         Cint, Ptr{Cvoid}),
+        handle(_base(A)).ptr, _op(A), length(I), pointer.(I), ni, pointer.(J), nj,
+        Ptr{Cvoid}[pointer(o) for o in outs], max.(ni, 1), 0, C_NULL))
+    return outs
+end
+
+# repeated indices are extracted once and expanded here (the C entry takes sets)
+function _getindex(A::ROCmAnyOp, I::AbstractVector{<:Integer}, J::AbstractVector{<:Integer})
+    checkbounds(Bool, 1:size(A, 1), I) && checkbounds(Bool, 1:size(A, 2), J) || throw(BoundsError(A, (I, J)))
+    ui = unique(I); uj = unique(J)
+    S = submatrices(A, [ui], [uj])[1]
+    return S[indexin(I, ui), indexin(J, uj)]
+end
+const _Idx = Union{Integer,AbstractVector{<:Integer},Colon}
+_idx(::Colon, n) = 1:n
+_idx(i::Integer, n) = [i]
+_idx(v::AbstractVector{Bool}, n) = (length(v) == n || throw(BoundsError(1:n, v)); findall(v))
+_idx(v::AbstractVector{<:Integer}, n) = v
+function Base.getindex(A::ROCmAnyOp, i::_Idx, j::_Idx)
+    S = _getindex(A, _idx(i, size(A, 1)), _idx(j, size(A, 2)))
+    i isa Integer && j isa Integer && return S[1, 1]
+    i isa Integer && return S[1, :]
+    j isa Integer && return S[:, 1]
+    return S
+end
+
+function LinearAlgebra.diag(A::ROCmAnyOp)
+    T = eltype(_base(A))
+    d = Vector{T}(undef, min(size(A)...))
+    GC.@preserve d _check(ccall((:bsm_diag, libbsm), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+        handle(_base(A)).ptr, pointer(d), 0, C_NULL))
+    return _op(A) == 2 ? conj!(d) : d
+end
+
 end # module
