@@ -18,6 +18,8 @@ BSM_SCHED_SERIAL, BSM_SCHED_DYNAMIC = 0, 1
 BSM_ACC_AUTO, BSM_ACC_ATOMIC, BSM_ACC_COLORED, BSM_ACC_GATHER, BSM_ACC_DIRECT = 0, 1, 2, 3, 4
 BSM_DEVICE_CURRENT, BSM_DEVICE_NONE = -1, -2
 BSM_COLOR_WORKSTREAM_DSATUR, BSM_COLOR_DSATUR = 0, 1
+# bsm_invert_blocks: largest n * n * sizeof(T) eliminated in LDS, largest order it takes (include/bsm_rocm.h)
+BSM_INVERT_LDS_BYTES, BSM_INVERT_MAX_N = 131072, 1024
 (BSM_BK_VBCRS_PERM, BSM_BK_VBCRS_ROWPTR, BSM_BK_VBCRS_COLINDICES, BSM_BK_VBCRS_ROWINDICES,
  BSM_BK_COLORS, BSM_BK_TRANSPOSECOLORS, BSM_BK_DIAGONALCOLORS) = range(7)
 
@@ -59,7 +61,7 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_mul_cvec", "bsm_mul_multi_cvec", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
            "bsm_color", "bsm_destroy", "bsm_last_error", "bsm_version",
            "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks", "bsm_value_passes",
-           "bsm_submatrices", "bsm_diag"]
+           "bsm_submatrices", "bsm_diag", "bsm_invert_blocks"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -158,6 +160,9 @@ def lib():
         L.bsm_submatrices.argtypes = [C.c_void_p, C.c_int, C.c_int64, _PP, _I64P, _PP, _I64P, _PP, _I64P, C.c_int, C.c_void_p]
         L.bsm_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.bsm_submatrices.restype = L.bsm_diag.restype = C.c_int
+    if hasattr(L, "bsm_invert_blocks") or "BSM_LIB" not in os.environ:
+        L.bsm_invert_blocks.argtypes = [C.c_int, C.c_int64, _PP, _I64P, _I64P, _I64P, C.c_int, C.c_void_p]
+        L.bsm_invert_blocks.restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p
     L.bsm_version.restype = C.c_char_p

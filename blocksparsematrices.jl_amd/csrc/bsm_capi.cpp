@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "bsm_internal.h"
+#include "bsm_invert.h"
 
 using namespace bsm;
 
@@ -824,6 +825,90 @@ extern "C" int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream) {
         if (n == 0) return BSM_OK;
         const std::vector<Window> win{Window{n, 1, n, d}};
         return extract_run(A, BSM_OP_N, nullptr, win, memspace, (hipStream_t)stream);)
+}
+
+// ---- bsm_invert_blocks: batched in-place inverse of dense blocks ---------------------------------------------------------
+namespace {
+// the device leg: the non-empty blocks sorted by descending order (the large ones start first), cut into launches of
+// one regime whose blocks need more than half the LDS of the launch's first -- a 16 x 16 block does not reserve the
+// LDS of the 128 x 128 one that came in the same call
+int invert_device(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld, int64_t *info,
+                  hipStream_t stream) {
+    const int es = dtype == BSM_F32 ? 4 : dtype == BSM_C128 ? 16 : 8;
+    std::vector<InvertBlock> table;
+    for (int64_t b = 0; b < nblocks; b++)
+        if (n[b] > 0) table.push_back(InvertBlock{(uint64_t)(uintptr_t)blocks[b], (long long)ld[b], (int)n[b], (int)table.size()});
+    if (table.empty()) return BSM_OK;
+    std::stable_sort(table.begin(), table.end(), [](const InvertBlock &a, const InvertBlock &b) { return a.n > b.n; });
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && stream && hipStreamGetDevice(stream, &dev) != hipSuccess) {
+        (void)hipGetLastError();
+        e = hipGetDevice(&dev);
+    }
+    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
+    DeviceGuard g;
+    e = g.enter(dev);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    DevBuf db;  // the table, behind it one int32 of info per table entry
+    const size_t tb = (table.size() * sizeof(InvertBlock) + 15) / 16 * 16;
+    e = db.alloc(tb + table.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(db.p, table.data(), table.size() * sizeof(InvertBlock), hipMemcpyHostToDevice, stream);
+    int *d_info = (int *)((char *)db.p + tb);
+    auto resident = [&](const InvertBlock &t) { return (long long)t.n * t.n * es <= (long long)BSM_INVERT_LDS_BYTES; };
+    for (size_t i = 0; i < table.size() && e == hipSuccess;) {
+        const bool res = resident(table[i]);
+        const int head = invert_lds(table[i].n, es, res).total;
+        size_t j = i + 1;
+        while (j < table.size() && resident(table[j]) == res && 2 * invert_lds(table[j].n, es, res).total > head) j++;
+        e = launch_invert(dtype, (const InvertBlock *)db.p + i, (long long)(j - i), table[i].n, res, d_info, stream);
+        i = j;
+    }
+    std::vector<int> hinfo(table.size(), 0);
+    if (e == hipSuccess) e = hipMemcpyAsync(hinfo.data(), d_info, table.size() * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hip_fail(e, "invert");
+    if (info) {
+        int64_t k = 0;  // table ids count the non-empty blocks in the caller's order
+        for (int64_t b = 0; b < nblocks; b++)
+            if (n[b] > 0) info[b] = hinfo[(size_t)k++];
+    }
+    return BSM_OK;
+}
+}  // namespace
+
+extern "C" int bsm_invert_blocks(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld,
+                                 int64_t *info, int memspace, void *stream) {
+    BSM_GUARDED(
+        if (dtype == BSM_F64_F32 || dtype == BSM_C128_C64)
+            return fail(BSM_ERR_INVALID, "bsm_invert_blocks takes a vector type (BSM_F32 .. BSM_C128), not a mixed storage code");
+        if (dtype < 0 || dtype > 3) return fail(BSM_ERR_INVALID, "bad dtype");
+        if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
+        if (nblocks < 0 || nblocks > INT32_MAX) return fail(BSM_ERR_INVALID, "bad number of blocks");
+        if (nblocks > 0 && (!blocks || !n || !ld)) return fail(BSM_ERR_INVALID, "null argument");
+        for (int64_t b = 0; b < nblocks; b++) {
+            const std::string blk = "block " + std::to_string(b + 1) + ": ";
+            if (n[b] < 0) return fail(BSM_ERR_INVALID, blk + "negative size");
+            if (ld[b] < std::max<int64_t>(n[b], 1)) return fail(BSM_ERR_INVALID, blk + "ld < max(n, 1)");
+            if (n[b] > 0 && !blocks[b]) return fail(BSM_ERR_INVALID, blk + "null block");
+        }
+        for (int64_t b = 0; b < nblocks; b++)
+            if (n[b] > BSM_INVERT_MAX_N)
+                return fail(BSM_ERR_UNSUPPORTED, "block " + std::to_string(b + 1) + ": n = " + std::to_string(n[b]) +
+                                                     " > 1024 (one workgroup eliminates one block)");
+        if (info) std::fill(info, info + nblocks, (int64_t)0);
+        if (memspace == BSM_MEM_DEVICE) return invert_device(dtype, nblocks, blocks, n, ld, info, (hipStream_t)stream);
+        for (int64_t b = 0; b < nblocks; b++) {
+            int rc = 0;
+            switch (dtype) {
+                case BSM_F32: rc = invert_block_host<float, 1>((float *)blocks[b], n[b], ld[b]); break;
+                case BSM_F64: rc = invert_block_host<double, 1>((double *)blocks[b], n[b], ld[b]); break;
+                case BSM_C64: rc = invert_block_host<float, 2>((float *)blocks[b], n[b], ld[b]); break;
+                default: rc = invert_block_host<double, 2>((double *)blocks[b], n[b], ld[b]); break;
+            }
+            if (info) info[b] = rc;
+        }
+        return BSM_OK;)
 }
 
 extern "C" int bsm_host_register(void *ptr, int64_t bytes) {

@@ -761,6 +761,13 @@ static int dist_mul_fused(DistState &D, int op, int K, const std::vector<VecSour
         bool alone = D.parts[p]->has_image && yd.device == D.parts[p]->device && pl.zr[p].lo == pl.out[p].lo &&
                      pl.zr[p].hi == pl.out[p].hi;
         for (const Transfer &t : pl.transfers) alone = alone && t.from != p && t.to != p;
+        // (the interleaved multi-RHS pass ends in Y = beta * Y + W over the part's rows and Y += W -- a plain read-modify-
+        // write of zeros -- over every OTHER row of y: into the caller's y that would race with the part that owns those
+        // rows whenever the two work on different streams.  Such a part goes through its work vector, whose delivery
+        // touches its own rows only)
+        if (several_streams && !D.parts[p]->il_failed &&
+            wants_il_arrays(plan_input(D.parts[p]->img, opT, D.parts[p]->img.dtype, K, false)))
+            alone = false;
         direct[p] = alone;
     }
     // (a NULL stream is a different stream on every device: "same stream" needs the same device too)

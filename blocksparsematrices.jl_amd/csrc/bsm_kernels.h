@@ -120,6 +120,36 @@ hipError_t launch_extract(int dtype, const void *d_waves, long long nwaves, cons
 hipError_t launch_zero_windows(int vt, const void *d_table, const void *d_shape, long long nsets, long long largest,
                                hipStream_t stream);
 
+// bsm_invert_blocks (bsm_invert.hip): d_table[0 .. count) = the blocks of ONE launch, one 256-thread workgroup each, all
+// of one regime -- resident: n * n * sizeof(T) <= BSM_INVERT_LDS_BYTES, eliminated in LDS; else in place, n <= 1024 --
+// and none larger than nmax, which sizes the launch's dynamic LDS (invert_lds).  d_info[id] = 0, or the 1-based step whose
+// pivot was zero or not finite.  dtype: BSM_F32 .. BSM_C128.
+struct InvertBlock {
+    uint64_t ptr;  // device address of the block's first element
+    long long ld;  // leading dimension, elements
+    int n, id;     // order; position in the caller's arrays (info)
+};
+static_assert(sizeof(InvertBlock) == 24, "InvertBlock must be 24 bytes");
+// byte offsets into the dynamic LDS of a launch whose largest block has order nmax (es: element bytes): the staged pivot
+// row and column, the row swaps, the column order of the write-back and -- resident launches -- the block itself; the
+// first 128 bytes hold the four records of the pivot search
+struct InvertLds {
+    int prow, pcol, piv, perm, mat, total;
+};
+__host__ __device__ inline InvertLds invert_lds(int nmax, int es, bool resident) {
+    const int v = (nmax * es + 15) & ~15, w = (nmax * 4 + 15) & ~15;
+    InvertLds l;
+    l.prow = 128;
+    l.pcol = l.prow + v;
+    l.piv = l.pcol + v;
+    l.perm = l.piv + w;
+    l.mat = l.perm + w;
+    l.total = l.mat + (resident ? nmax * nmax * es : 0);
+    return l;
+}
+hipError_t launch_invert(int dtype, const void *d_table, long long count, int nmax, bool resident, void *d_info,
+                         hipStream_t stream);
+
 // executes Analysis::pack_plan on the device (blocks already in HBM): d_plan = PackChunk[nchunks],
 // d_colpos = int32 placements (may be null when no chunk is scattered), es = stored element bytes, src_es = the caller's
 // (= es, or 2 es for the mixed-precision dtypes: the values are rounded to the stored type as they are placed)

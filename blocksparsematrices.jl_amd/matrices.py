@@ -38,7 +38,7 @@ __all__ = [
     "eachdiagonalindex", "eachoffdiagonalindex", "diagonalindices", "diagonalcolors",
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
-    "update_blocks", "refresh", "submatrices", "submatrix", "diag",
+    "update_blocks", "refresh", "submatrices", "submatrix", "diag", "invert_blocks", "BlockJacobi", "block_jacobi",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -1186,6 +1186,110 @@ def _getitem(A, key):
     if np.ndim(ri) == 0:
         out = out[0]
     return out
+
+
+# ---- block-Jacobi: the self-interaction blocks inverted where they are (bsm_invert_blocks) -----------------------------
+def invert_blocks(blocks):
+    """Inverts square column-major blocks IN PLACE (bsm_invert_blocks: Gauss-Jordan with partial row pivoting, one
+    workgroup per block on the device, the same elimination serially for host blocks) -> info, one int64 per block:
+    0, or the 1-based step whose pivot was zero or not finite (that block is then unspecified).  blocks: numpy arrays
+    (Fortran order) or torch CUDA tensors (column-major, e.g. what submatrices(..., device=True) returns) of ONE
+    element type and device, orders 0 .. 1024.  Device blocks go on torch's current stream; the call is synchronous."""
+    blocks = list(blocks)
+    nb = len(blocks)
+    devb = _is_dev(blocks)
+    if devb:
+        dt = _dev_blocks(blocks)
+    else:
+        dt = None
+        for b in blocks:
+            if not (isinstance(b, np.ndarray) and b.ndim == 2 and b.dtype in _DT and b.flags.f_contiguous and b.flags.writeable):
+                raise TypeError("host blocks must be writeable 2-D Fortran-order numpy arrays of a supported element type")
+            if dt is not None and b.dtype != dt:
+                raise TypeError("the blocks must share one element type")
+            dt = b.dtype
+    for b in blocks:
+        if b.shape[0] != b.shape[1]:
+            raise ValueError(f"a block of shape {tuple(b.shape)} is not square")
+    info = np.zeros(max(nb, 1), dtype=np.int64)
+    if nb == 0:
+        return info[:0]
+    n, ld = _i64([b.shape[0] for b in blocks]), _lds(blocks)
+    ptrs = (C.c_void_p * nb)()
+    for k, b in enumerate(blocks):
+        if b.shape[0]:
+            ptrs[k] = b.data_ptr() if devb else b.ctypes.data
+    I = C.POINTER(C.c_int64)
+    st = _stream_ptr(None, blocks[0].device) if devb else None
+    L.check(L.lib().bsm_invert_blocks(_DT[dt], nb, ptrs, n.ctypes.data_as(I), ld.ctypes.data_as(I), info.ctypes.data_as(I),
+                                      L.BSM_MEM_DEVICE if devb else L.BSM_MEM_HOST, st))
+    return info
+
+
+def _inverted_blocks(A, sets, stream=None):
+    """[inv(A[I_s, I_s]) for s]: extracted where the image lives and inverted there (device tensors on the handle's first
+    device, numpy arrays for an analysis-only handle)"""
+    base, _ = _unwrap(A)
+    on_dev = base.device is not None or base.devices is not None
+    ctx = contextlib.nullcontext()
+    if on_dev and stream is not None:
+        st = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        ctx = torch.cuda.stream(st)  # submatrices and invert_blocks both take torch's current stream
+    with ctx:
+        blocks = submatrices(A, sets, device=on_dev)
+        info = invert_blocks(blocks)
+    bad = np.nonzero(info)[0]
+    if len(bad):
+        raise np.linalg.LinAlgError(f"block_jacobi: A[I, I] of set {int(bad[0]) + 1} is singular to working precision (the pivot of "
+                                    f"elimination step {int(info[bad[0]])} is zero or not finite)")
+    return blocks
+
+
+class BlockJacobi(BlockSparseMatrix):
+    """M = sum_s E_s inv(A[I_s, I_s]) E_s^T -- the block-Jacobi (near-field) preconditioner of A as an ordinary
+    BlockSparseMatrix handle: mul, M @ X, MulPlan, the wrappers, complex vectors under a real M and M[I, J] work as on
+    any other.  Built by block_jacobi(A, sets).  Fields beside BlockSparseMatrix's: `sets` (1-based index arrays) and
+    `source` (the A it was built from)."""
+
+    def __init__(self, A, sets=None, *, storage=None, accumulate="auto", transpose_image=False):
+        base, _ = _unwrap(A)
+        if not isinstance(base, AbstractBlockMatrix):
+            raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
+        if sets is None:
+            if not isinstance(base, SymmetricBlockMatrix):
+                raise ValueError("sets=None means the diagonalindices of a SymmetricBlockMatrix; pass index sets for other types")
+            sets = base.diagonalindices
+        m, n = size(A)
+        if m != n:
+            raise ValueError(f"block_jacobi needs a square operator, size(A) = {(m, n)}")
+        self.sets = [_i64(np.asarray(s).reshape(-1)) for s in sets]
+        self.source = A
+        blocks = _inverted_blocks(A, self.sets)
+        dev = L.BSM_DEVICE_NONE if base.device is None and base.devices is None else _out_device(base).index
+        super().__init__(blocks, self.sets, self.sets, (m, n), device=dev, storage=storage, accumulate=accumulate,
+                         transpose_image=transpose_image)
+
+    def refresh(self, A=None, stream=None):
+        """Re-extracts the blocks of A (default: `source`, e.g. after update_blocks(A, ...)), inverts them and pushes them
+        into this handle with update_blocks: no analysis, no reallocation of the image, the tensors of `blocks` stay.  A
+        singular block raises LinAlgError and leaves M as it was; a `storage=` M raises what update_blocks raises."""
+        _no_mixed_update(self)
+        A = self.source if A is None else A
+        if size(A) != self.size:
+            raise ValueError(f"size(A) = {size(A)} but the preconditioner is {self.size}")
+        update_blocks(self, _inverted_blocks(A, self.sets, stream), stream=stream)
+        self.source = A
+
+
+def block_jacobi(A, sets=None, *, storage=None, accumulate="auto", transpose_image=False):
+    """The block-Jacobi preconditioner of A over `sets` (1-based index lists, pairwise disjoint and free of repeats;
+    None: the diagonalindices of a SymmetricBlockMatrix) -> BlockJacobi.  submatrices(A, sets, device=True), invert_blocks
+    and the BlockSparseMatrix constructor from device tensors: no matrix byte crosses PCIe.  An analysis-only A takes
+    the same route on the host and gives an analysis-only M; a multi-device A gives a single-device M on its first
+    device; transpose(A) / adjoint(A) are taken as such; a mixed-storage A gives its stored values widened, inverted in
+    the vector type (storage= here is that of M).  Rows in no set are zero rows of M -- pass singleton sets for
+    point-Jacobi rows.  A singular block raises numpy.linalg.LinAlgError naming the set and the elimination step."""
+    return BlockJacobi(A, sets, storage=storage, accumulate=accumulate, transpose_image=transpose_image)
 
 
 # ---- conversion used by the reference's tests as their oracle (host utility, not the hot path) ----

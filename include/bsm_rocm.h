@@ -492,6 +492,44 @@ int bsm_submatrices(bsm_matrix_t A, int op, int64_t nsets, const int64_t *const 
  * diagonal are read. */
 int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream);
 
+/* Batched inverse of dense blocks of different sizes, in place:
+ *   blocks[b][i + j * ld[b]], i, j < n[b]   becomes   inv(block b)      for b < nblocks
+ * -- the step between bsm_submatrices (the self-interaction blocks A[I_s, I_s] of an operator) and the block-Jacobi /
+ * near-field preconditioner M = sum_s E_s inv(A[I_s, I_s]) E_s^T, which is then an ordinary BlockSparseMatrix handle
+ * built from the inverted blocks (blocks_memspace = BSM_MEM_DEVICE) and applied by bsm_mul.  (No counterpart in the
+ * reference: its LinearMap surface offers A[I, J] and leaves factorisations to the caller.)
+ *   Arguments: dtype BSM_F32 .. BSM_C128 (the mixed storage codes are BSM_ERR_INVALID, as in bsm_vec_add_segments).
+ *     blocks, n, ld and info are HOST arrays; block b is column-major with leading dimension ld[b] >= max(n[b], 1).
+ *     n[b] == 0 is legal and blocks[b] may then be NULL; n[b] > 1024 is BSM_ERR_UNSUPPORTED (one workgroup eliminates
+ *     one block: this is a setup-time call for preconditioner blocks).  The blocks must not overlap in memory (the
+ *     caller's contract, not checked).
+ *   Algorithm (fixed, so that host and device choose the same pivots): in-place Gauss-Jordan elimination with partial
+ *     row pivoting.  At step k the pivot is the entry of column k in rows k .. n-1 with the largest magnitude -- |v| for
+ *     real, |re| + |im| for complex types (LAPACK's cabs1), a NaN counted as +inf --, ties to the smallest row; the rows
+ *     are swapped, the pivot row is scaled by the reciprocal of the pivot, every other row is reduced by a rank-1
+ *     update with its multiplier A[i, k] / pivot (a true division: a row that duplicates the pivot row cancels exactly
+ *     and the block is reported singular); after the last step the column swaps are undone in reverse order.  As for
+ *     any explicit inverse the forward error grows with the condition number of the block: ill-conditioned blocks want
+ *     a factorisation.
+ *   info (may be NULL): info[b] = 0 -- block b holds its inverse; info[b] = k (1-based) -- the pivot of step k was
+ *     exactly zero or not finite, the contents of that block are then unspecified, the other blocks are unaffected.  The
+ *     call still returns BSM_OK (LAPACK style).
+ *   memspace: where the blocks live.
+ *     BSM_MEM_DEVICE: pointers valid on the current device, or on the device of `stream` when one is given; the work
+ *       is enqueued on `stream`.  One 256-thread workgroup per block, the largest blocks first.  A block with
+ *       n * n * sizeof(T) <= BSM_INVERT_LDS_BYTES is eliminated in LDS, a larger one in place in device memory.  The
+ *       call is SYNCHRONOUS like bsm_submatrices -- it uploads a table of (address, n, ld) per block and reads info
+ *       back -- and is not to be graph-captured.  Results are bit-identical from run to run.
+ *     BSM_MEM_HOST: the same elimination, serially on the host in plain C++; needs no device (works wherever
+ *       analysis-only handles do); `stream` is ignored.
+ *   Nothing outside the n x n windows is written, the ld padding included.  Every argument is checked before the first
+ *   byte is written.  BSM_ERR_INVALID: null blocks / n / ld with nblocks > 0, nblocks < 0, a negative n, ld too small,
+ *   bad dtype or memspace, a NULL block with n > 0. */
+#define BSM_INVERT_LDS_BYTES 131072 /* of the 160 KiB of LDS per CU; staging arrays take less than 8 KiB more */
+#define BSM_INVERT_MAX_N 1024
+int bsm_invert_blocks(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld,
+                      int64_t *info, int memspace, void *stream);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal
