@@ -1,0 +1,485 @@
+// bsm_krylov.hip -- the kernels of bsm_krylov_orth and bsm_gmres_solve (include/bsm_rocm.h): the orthogonalisation of
+// restarted GMRES and the small dense steps around it.  Kept out of the product kernel units like bsm_extract.hip and
+// bsm_invert.hip: the build id (Makefile BUILD_ID) names the kernels and schedule of the PRODUCTS.
+// (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+//
+// One classical Gram-Schmidt pass  h = V^H w,  w -= V h,  ||w||  is two launches with a kernel boundary between them --
+// no workgroup ever waits for another inside a launch, and there is no floating-point atomic anywhere:
+//   dot_kernel    workgroup g owns a contiguous range of the rows (the same split in both kernels, krylov_grid of them).
+//                 It walks the range in tiles of 256 threads x U 16-byte groups; a tile of w is loaded ONCE and stays in
+//                 registers while the k columns of V stream past it, CB columns -- CB * U loads per thread -- in flight.
+//                 Per column: the lane's products, 6 xor-shuffles for the wave, lane 0 adds the wave's sum to its LDS slot
+//                 (acc[c][wave]); behind the last tile thread c folds the four slots and writes ONE partial per
+//                 workgroup and column, part[c * G + g].
+//   sweep_kernel  every workgroup first sums the G partials of every column in the same fixed order (S threads per
+//                 column, strided, then xor-shuffles: all workgroups get the same h, bit for bit), keeps h in LDS, and
+//                 walks its rows again: a tile of w in registers, the columns streamed past it, w -= V h, stored once,
+//                 |w|^2 summed on the way -> nrmpart[g].  Workgroup 0 also adds h to hsum.
+//                 The same kernel with combine = true is  u = V y  (coefficients read from y, accumulator starting at
+//                 0, no norm), and with k = 0 and a device scalar it is  V[:, j + 1] = w * inv_norm  (scale_store).
+// Loads and stores are 16 bytes per lane where the pointers allow it -- w, out and every column of V congruent modulo
+// 16, i.e. (ldv * sizeof(T)) % 16 == 0 --: the vector groups start at the first 16-byte boundary of w, the elements in
+// front of it and behind the last whole group go element by element through the same code (a group that is not wholly
+// inside [0, n) is read and written under a per-element guard).  Otherwise every group is one element (VE = 1).
+// Every sum has a fixed order: the results are bit-identical from run to run.
+// The consumers of the per-workgroup norm shares -- norm_kernel (bsm_krylov_orth), start_kernel, hess_kernel (one wave
+// each) -- add them in a fixed order too.  hess_kernel and trsolve_kernel run the arithmetic of bsm_krylov.h.
+#include "bsm_krylov.h"
+
+#include "../../include/bsm_rocm.h"
+
+namespace bsm {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kU = 2;   // 16-byte groups per thread and tile
+constexpr int kCB = 4;  // columns in flight
+
+template <typename R> struct alignas(16) Vec16 {
+    R r[16 / sizeof(R)];
+};
+
+// one group of VE elements (GC = VE * NC components) starting at element e0 of p; A16: groups are 16-byte aligned
+template <typename R, int NC, int VE, bool A16>
+__device__ __forceinline__ void load_group(const R *__restrict__ p, long long e0, long long n, bool valid, R (&v)[VE * NC]) {
+    constexpr int GC = VE * NC;
+    if (A16) {
+        if (valid && e0 >= 0 && e0 + VE <= n) {
+            const Vec16<R> t = *reinterpret_cast<const Vec16<R> *>(p + e0 * NC);
+#pragma unroll
+            for (int q = 0; q < GC; ++q) v[q] = t.r[q];
+            return;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < VE; ++e) {
+        const bool in = valid && e0 + e >= 0 && e0 + e < n;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) v[e * NC + c] = in ? p[(e0 + e) * NC + c] : R(0);
+    }
+}
+template <typename R, int NC, int VE, bool A16>
+__device__ __forceinline__ void store_group(R *__restrict__ p, long long e0, long long n, bool valid, const R (&v)[VE * NC]) {
+    constexpr int GC = VE * NC;
+    if (A16) {
+        if (valid && e0 >= 0 && e0 + VE <= n) {
+            Vec16<R> t;
+#pragma unroll
+            for (int q = 0; q < GC; ++q) t.r[q] = v[q];
+            *reinterpret_cast<Vec16<R> *>(p + e0 * NC) = t;
+            return;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < VE; ++e) {
+        if (valid && e0 + e >= 0 && e0 + e < n) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) p[(e0 + e) * NC + c] = v[e * NC + c];
+        }
+    }
+}
+
+template <typename R> __device__ __forceinline__ R wave_sum(R v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// the rows of workgroup wg: groups [g0, g1) of the ng groups that cover elements lo .. n - 1 (lo <= 0: the first group
+// may start in front of the vector)
+__device__ __forceinline__ void wg_range(long long ng, int G, int wg, long long &g0, long long &g1) {
+    const long long per = (ng + G - 1) / G;
+    g0 = per * wg;
+    g1 = g0 + per < ng ? g0 + per : ng;
+}
+
+template <typename R, int NC, int VE, bool A16>
+__global__ void __launch_bounds__(kThreads) dot_kernel(long long n, int k, const R *__restrict__ V, long long ldv,
+                                                       const R *__restrict__ w, R *__restrict__ part, long long lo, long long ng) {
+    constexpr int GC = VE * NC;
+    __shared__ R acc[BSM_GMRES_MAX_RESTART * 4 * NC];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, G = gridDim.x, wg = blockIdx.x;
+    for (int i = t; i < k * 4 * NC; i += kThreads) acc[i] = R(0);
+    __syncthreads();
+    long long g0, g1;
+    wg_range(ng, G, wg, g0, g1);
+    for (long long tile = g0; tile < g1; tile += (long long)kThreads * kU) {
+        R wv[kU][GC];
+        long long e0[kU];
+        bool ok[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const long long g = tile + (long long)u * kThreads + t;
+            ok[u] = g < g1;
+            e0[u] = lo + g * VE;
+            load_group<R, NC, VE, A16>(w, e0[u], n, ok[u], wv[u]);
+        }
+        for (int c0 = 0; c0 < k; c0 += kCB) {
+            R vv[kCB][kU][GC];
+#pragma unroll
+            for (int cc = 0; cc < kCB; ++cc)
+#pragma unroll
+                for (int u = 0; u < kU; ++u)
+                    load_group<R, NC, VE, A16>(V + (long long)(c0 + cc) * ldv * NC, e0[u], n, ok[u] && c0 + cc < k, vv[cc][u]);
+            R s[kCB][NC];
+#pragma unroll
+            for (int cc = 0; cc < kCB; ++cc) {
+#pragma unroll
+                for (int c = 0; c < NC; ++c) s[cc][c] = R(0);
+#pragma unroll
+                for (int u = 0; u < kU; ++u)
+#pragma unroll
+                    for (int e = 0; e < VE; ++e) {
+                        if (NC == 1) {
+                            s[cc][0] = fma(vv[cc][u][e], wv[u][e], s[cc][0]);
+                        } else {  // conj(v) * w
+                            const R vr = vv[cc][u][e * NC], vi = vv[cc][u][e * NC + NC - 1];
+                            const R wr = wv[u][e * NC], wi = wv[u][e * NC + NC - 1];
+                            s[cc][0] = fma(vr, wr, s[cc][0]);
+                            s[cc][0] = fma(vi, wi, s[cc][0]);
+                            s[cc][NC - 1] = fma(vr, wi, s[cc][NC - 1]);
+                            s[cc][NC - 1] = fma(-vi, wr, s[cc][NC - 1]);
+                        }
+                    }
+            }
+#pragma unroll
+            for (int cc = 0; cc < kCB; ++cc)
+#pragma unroll
+                for (int c = 0; c < NC; ++c) s[cc][c] = wave_sum(s[cc][c]);
+            if (lane == 0) {
+#pragma unroll
+                for (int cc = 0; cc < kCB; ++cc)
+                    if (c0 + cc < k) {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) acc[((c0 + cc) * 4 + wave) * NC + c] += s[cc][c];
+                    }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < k * NC; i += kThreads) {
+        const int c = i / NC, q = i % NC;
+        const R a = (acc[(c * 4 + 0) * NC + q] + acc[(c * 4 + 1) * NC + q]) + (acc[(c * 4 + 2) * NC + q] + acc[(c * 4 + 3) * NC + q]);
+        part[((long long)c * G + wg) * NC + q] = a;
+    }
+}
+
+template <typename R, int NC, int VE, bool A16, bool COMBINE>
+__global__ void __launch_bounds__(kThreads)
+    sweep_kernel(long long n, int k, const R *__restrict__ V, long long ldv, const R *in, R *out, const R *__restrict__ part,
+                 const R *__restrict__ coef, R *__restrict__ hsum, const R *__restrict__ scale, R *__restrict__ nrmpart,
+                 long long lo, long long ng) {
+    constexpr int GC = VE * NC;
+    __shared__ R hs[BSM_GMRES_MAX_RESTART * NC];
+    __shared__ R red[4];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, G = gridDim.x, wg = blockIdx.x;
+    if (COMBINE) {
+        for (int i = t; i < k * NC; i += kThreads) hs[i] = coef[i];
+    } else if (k > 0) {
+        // S threads per column (a power of two, at most a wave), column c = t / S: its lanes are neighbours in one wave
+        int kp = 1;
+        while (kp < k) kp <<= 1;
+        int S = kThreads / kp;
+        if (S > 64) S = 64;
+        const int c = t / S, sl = t % S;
+        R a[NC];
+#pragma unroll
+        for (int q = 0; q < NC; ++q) a[q] = R(0);
+        if (c < k)
+            for (int g = sl; g < G; g += S) {
+#pragma unroll
+                for (int q = 0; q < NC; ++q) a[q] += part[((long long)c * G + g) * NC + q];
+            }
+        for (int d = S >> 1; d >= 1; d >>= 1) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q) a[q] += __shfl_xor(a[q], d, 64);
+        }
+        if (c < k && sl == 0) {
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+                hs[c * NC + q] = -a[q];
+                if (wg == 0 && hsum) hsum[c * NC + q] += a[q];
+            }
+        }
+    }
+    __syncthreads();
+    const R sc = scale ? scale[0] : R(1);
+    R nn = R(0);
+    long long g0, g1;
+    wg_range(ng, G, wg, g0, g1);
+    for (long long tile = g0; tile < g1; tile += (long long)kThreads * kU) {
+        R wv[kU][GC];
+        long long e0[kU];
+        bool ok[kU];
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            const long long g = tile + (long long)u * kThreads + t;
+            ok[u] = g < g1;
+            e0[u] = lo + g * VE;
+            if (COMBINE) {
+#pragma unroll
+                for (int q = 0; q < GC; ++q) wv[u][q] = R(0);
+            } else {
+                load_group<R, NC, VE, A16>(in, e0[u], n, ok[u], wv[u]);
+            }
+        }
+        for (int c0 = 0; c0 < k; c0 += kCB) {
+            R vv[kCB][kU][GC];
+#pragma unroll
+            for (int cc = 0; cc < kCB; ++cc)
+#pragma unroll
+                for (int u = 0; u < kU; ++u)
+                    load_group<R, NC, VE, A16>(V + (long long)(c0 + cc) * ldv * NC, e0[u], n, ok[u] && c0 + cc < k, vv[cc][u]);
+#pragma unroll
+            for (int cc = 0; cc < kCB; ++cc) {
+                if (c0 + cc < k) {
+                    const R hr = hs[(c0 + cc) * NC], hi = hs[(c0 + cc) * NC + NC - 1];
+#pragma unroll
+                    for (int u = 0; u < kU; ++u)
+#pragma unroll
+                        for (int e = 0; e < VE; ++e) {
+                            if (NC == 1) {
+                                wv[u][e] = fma(vv[cc][u][e], hr, wv[u][e]);
+                            } else {
+                                const R vr = vv[cc][u][e * NC], vi = vv[cc][u][e * NC + NC - 1];
+                                wv[u][e * NC] = fma(vr, hr, wv[u][e * NC]);
+                                wv[u][e * NC] = fma(-vi, hi, wv[u][e * NC]);
+                                wv[u][e * NC + NC - 1] = fma(vr, hi, wv[u][e * NC + NC - 1]);
+                                wv[u][e * NC + NC - 1] = fma(vi, hr, wv[u][e * NC + NC - 1]);
+                            }
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kU; ++u) {
+            if (scale) {
+#pragma unroll
+                for (int q = 0; q < GC; ++q) wv[u][q] *= sc;
+            }
+            if (!COMBINE) {
+                // (a group in front of the vector or behind it holds zeros where it is outside: they add nothing)
+#pragma unroll
+                for (int q = 0; q < GC; ++q) nn = fma(wv[u][q], wv[u][q], nn);
+            }
+            store_group<R, NC, VE, A16>(out, e0[u], n, ok[u], wv[u]);
+        }
+    }
+    if (!COMBINE && nrmpart) {
+        nn = wave_sum(nn);
+        if (lane == 0) red[wave] = nn;
+        __syncthreads();
+        if (t == 0) nrmpart[wg] = (red[0] + red[1]) + (red[2] + red[3]);
+    }
+}
+
+// sum of p[0 .. G) by one wave in a fixed order
+template <typename R> __device__ __forceinline__ R wave_total(const R *__restrict__ p, int G, int lane) {
+    R a = R(0);
+    for (int g = lane; g < G; g += 64) a += p[g];
+    return wave_sum(a);
+}
+
+template <typename R> __global__ void __launch_bounds__(64) norm_kernel(int G, const R *__restrict__ nrmpart, R *__restrict__ nrm) {
+    const R a = wave_total(nrmpart, G, (int)threadIdx.x);
+    if (threadIdx.x == 0) nrm[0] = sqrt(a);
+}
+
+template <typename R, int NC>
+__global__ void __launch_bounds__(64) start_kernel(int G, int m, const R *__restrict__ nrmpart, R *__restrict__ g, R *__restrict__ hsum,
+                                                   R *__restrict__ inv, double *__restrict__ res) {
+    const int lane = threadIdx.x;
+    const R beta = sqrt(wave_total(nrmpart, G, lane));
+    for (int i = lane; i < (m + 1) * NC; i += 64) g[i] = i == 0 ? beta : R(0);
+    for (int i = lane; i < m * NC; i += 64) hsum[i] = R(0);
+    if (lane == 0) {
+        inv[0] = beta == R(0) ? R(0) : R(1) / beta;
+        res[m] = (double)beta;
+    }
+}
+
+template <typename R, int NC>
+__global__ void __launch_bounds__(64) hess_kernel(int G, int m, int j, const R *__restrict__ nrmpart, R *__restrict__ hsum,
+                                                  R *__restrict__ Hm, R *__restrict__ cs, R *__restrict__ sn, R *__restrict__ g,
+                                                  R *__restrict__ inv, double *__restrict__ res) {
+    __shared__ R col[(BSM_GMRES_MAX_RESTART + 1) * NC];
+    __shared__ R rot[BSM_GMRES_MAX_RESTART * 3];  // cs, sn of the stored rotations
+    __shared__ R gg[2 * NC];
+    const int lane = threadIdx.x;
+    const R hn = sqrt(wave_total(nrmpart, G, lane));
+    for (int i = lane; i < (j + 1) * NC; i += 64) {
+        col[i] = hsum[i];
+        hsum[i] = R(0);
+    }
+    for (int i = lane; i < j; i += 64) rot[i] = cs[i];
+    for (int i = lane; i < j * NC; i += 64) rot[BSM_GMRES_MAX_RESTART + i] = sn[i];
+    if (lane < NC) gg[lane] = g[j * NC + lane];
+    __syncthreads();
+    if (lane == 0) {
+        const R est = krylov_hess_column<R, NC>(j, col, hn, rot, rot + BSM_GMRES_MAX_RESTART, gg - (long long)j * NC);
+        cs[j] = rot[j];
+        for (int q = 0; q < NC; ++q) {
+            sn[j * NC + q] = rot[BSM_GMRES_MAX_RESTART + j * NC + q];
+            g[j * NC + q] = gg[q];
+            g[(j + 1) * NC + q] = gg[NC + q];
+        }
+        res[j] = (double)est;
+        inv[0] = hn == R(0) ? R(0) : R(1) / hn;
+    }
+    __syncthreads();
+    R *const dst = Hm + (long long)j * (m + 1) * NC;
+    for (int i = lane; i < (j + 1) * NC; i += 64) dst[i] = col[i];
+}
+
+template <typename R, int NC>
+__global__ void __launch_bounds__(64) trsolve_kernel(int m, int k, const R *__restrict__ Hm, const R *__restrict__ g, R *__restrict__ y) {
+    __shared__ R ys[BSM_GMRES_MAX_RESTART * NC];
+    __shared__ R q[2];
+    const int lane = threadIdx.x;
+    const long long ldh = m + 1;
+    for (int i = lane; i < k * NC; i += 64) ys[i] = g[i];
+    __syncthreads();
+    for (int i = k - 1; i >= 0; --i) {
+        if (lane == 0) {
+            R d[2] = {R(0), R(0)};
+            k_div<R, NC>(ys + i * NC, Hm + ((long long)i + i * ldh) * NC, d);
+            for (int c = 0; c < NC; ++c) q[c] = ys[i * NC + c] = d[c];
+        }
+        __syncthreads();
+        const R qr = q[0], qi = q[NC - 1];
+        for (int r = lane; r < i; r += 64) {
+            const R *a = Hm + ((long long)r + i * ldh) * NC;
+            if (NC == 1) {
+                ys[r] -= a[0] * qr;
+            } else {
+                ys[r * NC] -= a[0] * qr - a[NC - 1] * qi;
+                ys[r * NC + NC - 1] -= a[0] * qi + a[NC - 1] * qr;
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = lane; i < k * NC; i += 64) y[i] = ys[i];
+}
+
+// whether 16-byte groups serve all of the pointers (null ones do not count), and where the first one starts
+struct Split {
+    bool a16;
+    long long lo, ng;
+};
+Split split_of(long long n, int es, long long ldv, int k, const void *V, const void *a, const void *b) {
+    const int ve = 16 / es;
+    const void *first = a ? a : b;
+    const uintptr_t f = (uintptr_t)first;
+    bool ok = f % (uintptr_t)es == 0;
+    if (a && b) ok = ok && ((uintptr_t)a - (uintptr_t)b) % 16 == 0;
+    if (k > 0) ok = ok && ((uintptr_t)V - f) % 16 == 0 && (k == 1 || (ldv * es) % 16 == 0);
+    Split s;
+    s.a16 = ok;
+    if (!ok) {
+        s.lo = 0;
+        s.ng = n;
+        return s;
+    }
+    const long long head = (long long)(((16 - f % 16) % 16) / (uintptr_t)es);  // elements in front of the first boundary
+    s.lo = head > 0 ? head - ve : 0;
+    s.ng = (n - s.lo + ve - 1) / ve;
+    return s;
+}
+
+}  // namespace
+
+#define BSM_KRYLOV_TYPES(CALL)                  \
+    switch (dtype) {                            \
+        case BSM_F32: CALL(float, 1); break;    \
+        case BSM_F64: CALL(double, 1); break;   \
+        case BSM_C64: CALL(float, 2); break;    \
+        case BSM_C128: CALL(double, 2); break;  \
+        default: return hipErrorInvalidValue;   \
+    }
+
+static int es_of(int dtype) { return dtype == BSM_F32 ? 4 : dtype == BSM_C128 ? 16 : 8; }
+
+hipError_t launch_krylov_dot(int dtype, long long n, int k, const void *V, long long ldv, const void *w, void *part,
+                             hipStream_t stream) {
+    if (dtype < 0 || dtype > 3 || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
+    if (k == 0) return hipSuccess;
+    const int es = es_of(dtype);
+    const Split s = split_of(n, es, ldv, k, V, w, nullptr);
+    const dim3 grid((unsigned)krylov_grid(n, es)), block(kThreads);
+#define BSM_DOT(R, NC)                                                                                                        \
+    do {                                                                                                                      \
+        constexpr int VE = 16 / (int)(sizeof(R) * NC);                                                                        \
+        if (s.a16)                                                                                                            \
+            hipLaunchKernelGGL((dot_kernel<R, NC, VE, true>), grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w,  \
+                               (R *)part, s.lo, s.ng);                                                                        \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((dot_kernel<R, NC, 1, false>), grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w,  \
+                               (R *)part, s.lo, s.ng);                                                                        \
+    } while (0)
+    BSM_KRYLOV_TYPES(BSM_DOT)
+#undef BSM_DOT
+    return hipGetLastError();
+}
+
+hipError_t launch_krylov_sweep(int dtype, bool combine, long long n, int k, const void *V, long long ldv, const void *in, void *out,
+                               const void *part, const void *coef, void *hsum, const void *scale, void *nrmpart, hipStream_t stream) {
+    if (dtype < 0 || dtype > 3 || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
+    const int es = es_of(dtype);
+    const Split s = split_of(n, es, ldv, k, V, combine ? nullptr : in, out);
+    const dim3 grid((unsigned)krylov_grid(n, es)), block(kThreads);
+#define BSM_SWEEP_ARGS(R) n, k, (const R *)V, ldv, (const R *)in, (R *)out, (const R *)part, (const R *)coef, (R *)hsum, (const R *)scale, (R *)nrmpart, s.lo, s.ng
+#define BSM_SWEEP(R, NC)                                                                                                      \
+    do {                                                                                                                      \
+        constexpr int VE = 16 / (int)(sizeof(R) * NC);                                                                        \
+        if (s.a16 && combine)                                                                                                 \
+            hipLaunchKernelGGL((sweep_kernel<R, NC, VE, true, true>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));             \
+        else if (s.a16)                                                                                                       \
+            hipLaunchKernelGGL((sweep_kernel<R, NC, VE, true, false>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));            \
+        else if (combine)                                                                                                     \
+            hipLaunchKernelGGL((sweep_kernel<R, NC, 1, false, true>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));             \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((sweep_kernel<R, NC, 1, false, false>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));            \
+    } while (0)
+    BSM_KRYLOV_TYPES(BSM_SWEEP)
+#undef BSM_SWEEP
+#undef BSM_SWEEP_ARGS
+    return hipGetLastError();
+}
+
+hipError_t launch_krylov_norm(int dtype, int G, const void *nrmpart, void *nrm, hipStream_t stream) {
+    if (dtype == BSM_F32 || dtype == BSM_C64)
+        hipLaunchKernelGGL(norm_kernel<float>, dim3(1), dim3(64), 0, stream, G, (const float *)nrmpart, (float *)nrm);
+    else
+        hipLaunchKernelGGL(norm_kernel<double>, dim3(1), dim3(64), 0, stream, G, (const double *)nrmpart, (double *)nrm);
+    return hipGetLastError();
+}
+
+hipError_t launch_krylov_start(int dtype, int G, int m, const KrylovSmall &s, hipStream_t stream) {
+#define BSM_START(R, NC) \
+    hipLaunchKernelGGL((start_kernel<R, NC>), dim3(1), dim3(64), 0, stream, G, m, (const R *)s.nrmpart, (R *)s.g, (R *)s.hsum, (R *)s.inv, s.res)
+    BSM_KRYLOV_TYPES(BSM_START)
+#undef BSM_START
+    return hipGetLastError();
+}
+
+hipError_t launch_krylov_hess(int dtype, int G, int m, int j, const KrylovSmall &s, hipStream_t stream) {
+    if (j < 0 || j >= m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
+#define BSM_HESS(R, NC)                                                                                                            \
+    hipLaunchKernelGGL((hess_kernel<R, NC>), dim3(1), dim3(64), 0, stream, G, m, j, (const R *)s.nrmpart, (R *)s.hsum, (R *)s.Hm, \
+                       (R *)s.cs, (R *)s.sn, (R *)s.g, (R *)s.inv, s.res)
+    BSM_KRYLOV_TYPES(BSM_HESS)
+#undef BSM_HESS
+    return hipGetLastError();
+}
+
+hipError_t launch_krylov_trsolve(int dtype, int m, int k, const KrylovSmall &s, hipStream_t stream) {
+    if (k < 0 || k > m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
+    if (k == 0) return hipSuccess;
+#define BSM_TRS(R, NC) \
+    hipLaunchKernelGGL((trsolve_kernel<R, NC>), dim3(1), dim3(64), 0, stream, m, k, (const R *)s.Hm, (const R *)s.g, (R *)s.y)
+    BSM_KRYLOV_TYPES(BSM_TRS)
+#undef BSM_TRS
+    return hipGetLastError();
+}
+
+}  // namespace bsm

@@ -39,6 +39,7 @@ __all__ = [
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
     "update_blocks", "refresh", "submatrices", "submatrix", "diag", "invert_blocks", "BlockJacobi", "block_jacobi",
+    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -1290,6 +1291,133 @@ def block_jacobi(A, sets=None, *, storage=None, accumulate="auto", transpose_ima
     the vector type (storage= here is that of M).  Rows in no set are zero rows of M -- pass singleton sets for
     point-Jacobi rows.  A singular block raises numpy.linalg.LinAlgError naming the set and the elimination step."""
     return BlockJacobi(A, sets, storage=storage, accumulate=accumulate, transpose_image=transpose_image)
+
+
+# ---- restarted GMRES on the device (bsm_gmres_*) and its building block (bsm_krylov_orth) ------------------------------
+def krylov_orth_work(dtype, n, k):
+    """Bytes of the `work` array one krylov_orth pass over n entries and k columns of `dtype` needs."""
+    return int(L.lib().bsm_krylov_orth_work(_DT[np.dtype(dtype)], int(n), int(k)))
+
+
+def krylov_orth(V, w, k, hsum, nrm, work=None, stream=None):
+    """One classical Gram-Schmidt pass on the device (bsm_krylov_orth): h = V[:, :k]^H w, w -= V[:, :k] h, hsum[:k] += h,
+    nrm[0] = ||w||.  V: column-major torch CUDA tensor (n x >= k, e.g. torch.empty(cols, ld).t()[:n]), w: n entries of the
+    same type, hsum: >= k entries of it, nrm: one real of its precision, work: a uint8 tensor of krylov_orth_work bytes
+    (None: allocated here).  Enqueued on `stream` (default: torch's current stream); nothing is synchronised."""
+    if torch is None or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (V, w, hsum, nrm)):
+        raise TypeError("krylov_orth takes torch CUDA tensors")
+    dt = _TORCH_DT.get(w.dtype)
+    if dt is None or V.dtype != w.dtype or hsum.dtype != w.dtype:
+        raise TypeError("V, w and hsum must share one supported element type")
+    if _TORCH_DT.get(nrm.dtype) != np.dtype(np.zeros(1, dt).real.dtype):
+        raise TypeError(f"nrm must be one real of the precision of {dt}")
+    if any(t.device != w.device for t in (V, hsum, nrm)):
+        raise ValueError("V, w, hsum and nrm must live on one device")
+    n, k = w.numel(), int(k)
+    if w.dim() != 1 or not w.is_contiguous() or V.dim() != 2 or V.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: w must be a contiguous vector and V have its {n} rows")
+    if not 0 <= k <= min(V.shape[1], L.BSM_GMRES_MAX_RESTART) or hsum.numel() < k or nrm.numel() < 1:
+        raise ValueError(f"k = {k} outside 0 .. min(columns of V, {L.BSM_GMRES_MAX_RESTART}), or hsum shorter than k")
+    if n > 1 and V.stride(0) != 1:
+        raise TypeError("V must be column-major (e.g. torch.empty(cols, ld).t()[:n])")
+    ldv = V.stride(1) if V.shape[1] > 1 else max(n, 1)
+    need = krylov_orth_work(dt, n, k)
+    if work is None:
+        work = torch.empty(need + 16, dtype=torch.uint8, device=w.device)
+    if work.device != w.device or work.numel() * work.element_size() < need:
+        raise ValueError(f"work must hold {need} bytes on the device of w")
+    L.check(L.lib().bsm_krylov_orth(_DT[dt], n, k, V.data_ptr(), ldv, w.data_ptr(), hsum.data_ptr(), nrm.data_ptr(),
+                                    work.data_ptr(), _stream_ptr(stream, w.device)))
+    return w
+
+
+class GmresInfo:
+    """What a solve reports (bsm_gmres_info): status (0 converged, 1 maxiter reached, 2 a non-finite residual),
+    iterations, cycles, residual (absolute estimate), bnorm, a_products, m_products, workspace_bytes, workspace (device
+    address) and history: the absolute estimate after every iteration, a numpy array."""
+
+    def __init__(self, info, history):
+        for name, _ in L.BsmGmresInfo._fields_:
+            setattr(self, name, getattr(info, name))
+        self.history = history
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"GmresInfo(status={self.status}, iterations={self.iterations}, cycles={self.cycles}, "
+                f"residual={self.residual:.3e}, bnorm={self.bnorm:.3e})")
+
+
+class Gmres:
+    """Right-preconditioned restarted GMRES(restart) for A x = b, every step of it on the device (bsm_gmres_*).
+    A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g. block_jacobi(A,
+    sets)), or None.  dtype: the type of b and x -- default A's vector type; a real A (and M) of the same precision
+    takes complex vectors.  The workspace (restart + 4 vectors) is allocated here, once; A and M are kept alive."""
+
+    def __init__(self, A, M=None, restart=30, dtype=None):
+        base, op = _unwrap(A)
+        if not isinstance(base, AbstractBlockMatrix):
+            raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
+        mbase, mop = (None, L.BSM_OP_N) if M is None else _unwrap(M)
+        if M is not None and not isinstance(mbase, AbstractBlockMatrix):
+            raise TypeError("M must be a block matrix or its transpose/adjoint wrapper")
+        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
+        if self.dtype not in _DT:
+            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        self.A, self.M, self.restart = A, M, int(restart)
+        self.n = size(A)[0]
+        self._base, self._mbase = base, mbase
+        ptr = C.c_void_p()
+        L.check(L.lib().bsm_gmres_create(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype],
+                                         self.restart, C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                L.lib().bsm_gmres_destroy(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def solve(self, b, x=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None, stream=None):
+        """-> (x, GmresInfo).  b: torch CUDA tensor (enqueued on `stream`, default torch's current stream) or numpy
+        array (staged); x: where the solution goes (default: a new vector like b); x0: the initial guess (copied into x;
+        None: zero).  Converged when the estimate is <= max(rtol * ||b||, atol); maxiter (default: the order of A)
+        bounds the iterations.  Synchronous."""
+        dev = torch is not None and isinstance(b, torch.Tensor) and b.is_cuda
+        if x is None:
+            x = torch.empty_like(b) if torch is not None and isinstance(b, torch.Tensor) else np.empty_like(b)
+        bp, bms, _, bkeep = _vec_info(b, self.dtype, self.n, "b", self._base)
+        xp, xms, _, xkeep = _vec_info(x, self.dtype, self.n, "x", self._base)
+        if bms != xms:
+            raise ValueError("b and x must live in the same memory space")
+        if x0 is not None:
+            if _elt(x0) != self.dtype or tuple(x0.shape) != (self.n,):
+                raise TypeError(f"x0 must be a vector of {self.n} entries of {self.dtype}")
+            if x0 is not x:
+                if torch is not None and isinstance(x, torch.Tensor):
+                    x.copy_(x0 if isinstance(x0, torch.Tensor) else torch.from_numpy(x0))
+                else:
+                    x[...] = x0.cpu().numpy() if torch is not None and isinstance(x0, torch.Tensor) else x0
+        maxiter = max(self.n, 1) if maxiter is None else int(maxiter)
+        hist = np.zeros(max(maxiter, 1), dtype=np.float64)
+        p = L.BsmGmresParams(C.sizeof(L.BsmGmresParams), 0 if x0 is None else 1, float(rtol), float(atol), maxiter, maxiter)
+        info = L.BsmGmresInfo()
+        st = _stream_ptr(stream, b.device) if dev else None
+        if dev and stream is not None and x0 is not None and x0 is not x:
+            torch.cuda.current_stream(b.device).synchronize()  # the copy of x0 went on torch's current stream
+        L.check(L.lib().bsm_gmres_solve(self._ptr, bp, xp, C.byref(p), C.byref(info), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                        bms, st))
+        del bkeep, xkeep
+        return x, GmresInfo(info, hist[:min(info.iterations, maxiter)].copy())
+
+
+def gmres(A, b, M=None, restart=30, **kw):
+    """One-shot form: Gmres(A, M, restart, dtype of b).solve(b, **kw) -> (x, info)."""
+    return Gmres(A, M, restart=restart, dtype=_elt(b)).solve(b, **kw)
 
 
 # ---- conversion used by the reference's tests as their oracle (host utility, not the hot path) ----

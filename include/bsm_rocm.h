@@ -530,6 +530,100 @@ int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream);
 int bsm_invert_blocks(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld,
                       int64_t *info, int memspace, void *stream);
 
+/* ---- Krylov building block and solver: restarted GMRES wholly on the device ----------------------------------------
+ * What consumes a preconditioner handle M (block_jacobi: bsm_submatrices + bsm_invert_blocks + a BlockSparseMatrix
+ * handle): A x = b for the non-symmetric and complex operators the reference exists for, without a Krylov loop in the
+ * host language that issues a dozen tiny kernels and several synchronisations per iteration.  (No counterpart in the
+ * reference: its operators are LinearMaps, handed to a Julia solver package.)
+ *
+ * bsm_krylov_orth -- ONE classical Gram-Schmidt pass of w against the first k columns of a basis V (n x k, column-major,
+ * leading dimension ldv >= max(n, 1), element type T = dtype):
+ *     h = V[:, 0:k]^H w;   w -= V[:, 0:k] h;   hsum[0:k] += h;   nrm[0] = || w ||_2 of the result (one REAL of T's precision).
+ * A solver runs it twice per iteration (CGS2) on the same hsum.  All pointers are DEVICE pointers (valid on the current
+ * device, or on the device of `stream` when one is given: the launches are issued with that device current); the call enqueues three launches on `stream` and returns: no
+ * allocation, no synchronisation, no scalar crosses to the host, so it can be graph-captured.  The dot phase reads V
+ * and w once for all k columns; every sum -- per wave, per workgroup, the per-workgroup partials in `work` -- has a
+ * fixed order and there are no floating-point atomics: results are bit-identical from run to run.  16-byte loads are
+ * used when V, w and ldv * sizeof(T) are congruent modulo 16; any other alignment of whole elements works element by
+ * element.  `work`: bsm_krylov_orth_work(dtype, n, k) bytes, 16-byte aligned, contents unspecified before and after.
+ * k = 0 gives only the norm; n = 0 is legal (nrm = 0, hsum unchanged).  Nothing of V, and nothing outside the n entries
+ * of w, hsum[0:k] and nrm[0], is written.
+ * BSM_ERR_INVALID: a mixed storage code or a bad dtype (as in bsm_vec_add_segments), n < 0, k < 0 or k >
+ * BSM_GMRES_MAX_RESTART, ldv < max(n, 1) with k > 0, a null pointer that is needed (hsum with k > 0; V with k > 0 and n > 0;
+ * w with n > 0; nrm; work), a work array that is not 16-byte aligned, a negative result of the size query for bad arguments. */
+#define BSM_GMRES_MAX_RESTART 128
+int64_t bsm_krylov_orth_work(int dtype, int64_t n, int64_t k);
+int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, int64_t ldv, void *w, void *hsum, void *nrm,
+                    void *work, void *stream);
+
+/* bsm_gmres_*: right-preconditioned restarted GMRES(restart) for op(A) x = b with M ~ inv(op(A)) applied as opM(M).
+ *   r = b - op(A) x,  beta = ||r||,  v_0 = r / beta;  iteration j: z = M v_j (skipped without M), w = op(A) z, two
+ *   bsm_krylov_orth passes against v_0 .. v_j, one one-wave kernel that applies the j stored Givens rotations to the new
+ *   Hessenberg column, forms rotation j and the residual estimate |g[j + 1]|, then v_{j+1} = w / ||w||.  At the end of a
+ *   cycle, or at convergence after k iterations: back substitution R y = g[0:k] (one wave), u = V[:, 0:k] y, x += M u,
+ *   and the next cycle starts from the TRUE residual b - op(A) x.  Right preconditioning: the estimate is the residual
+ *   norm of the unpreconditioned system.
+ * create: allocates everything a solve needs, once, on A's device: V as n x (restart + 2) (the basis, the residual in
+ *   the spare column), two work vectors, the small arrays (Hessenberg factor, rotations, g, y, partial sums), a pinned
+ *   host slot and an event per iteration of a cycle.  vdtype (BSM_F32 .. BSM_C128) is the type of b and x.  Each of A, M
+ *   must have that vector type -- a mixed-storage handle counts with its double vectors -- or be a real, unmixed handle
+ *   of the same precision under a complex vdtype, which is then driven through bsm_mul_cvec.  The handles must outlive
+ *   the solver.  Refusals: null A or out, bad op / vdtype, a type pair not named above, op(A) not square, M of another
+ *   order or on another device, restart < 1 or > BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID; a multi-device handle:
+ *   BSM_ERR_UNSUPPORTED; an analysis-only handle: BSM_ERR_DEVICE.
+ * solve: b, x of n elements.  Converged when the estimate is <= max(rtol * ||b||_2, atol).  maxiter bounds the
+ *   iterations (products with A inside cycles).  use_x0 == 0: x is overwritten (NaN in the incoming x does not
+ *   survive); else x is the initial guess.  b = 0 gives x = 0, 0 iterations, status 0.
+ *   Look-ahead: after each iteration its estimate is copied to its pinned slot and an event is recorded; the host
+ *   enqueues iteration j + 1 before it waits for the event of iteration j, so the device never idles on the check.  The
+ *   answer uses exactly the k iterations up to the first one whose estimate met the tolerance; what was enqueued beyond
+ *   it lands in workspace only: iterations, history and x do not depend on timing.
+ *   history (may be NULL): history[i] = the absolute estimate after iteration i + 1, at most history_capacity entries.
+ *   Two exits report status 0: an iteration whose ESTIMATE met the tolerance (the last history entry is then <= the
+ *   tolerance and info.residual equals it), and the start of a cycle whose TRUE residual b - op(A) x already met it (the
+ *   last cycle ended with an estimate just above the tolerance, or x0 solves the system: info.residual is that true
+ *   residual norm, no history entry is written for it, and the last history entry, if any, still lies above the tolerance).
+ *   memspace: BSM_MEM_DEVICE -- b, x on A's device; BSM_MEM_HOST -- staged through device buffers the solver allocates
+ *   at its first host solve.  The call is SYNCHRONOUS: it returns when x is complete.  It runs wholly on `stream` and
+ *   must not be graph-captured.  One solve at a time per solver object.
+ *   BSM_ERR_INVALID: null S / b / x / p / info with n > 0, x overlapping b, negative rtol / atol / maxiter /
+ *   history_capacity, NaN tolerances, bad memspace, struct_size mismatch.
+ * info.status: 0 converged; 1 maxiter reached; 2 a residual norm or estimate was not finite (NaN / Inf in b, x0 or the
+ *   operator): x holds the last finished cycle.  The call returns BSM_OK for all three.
+ *   a_products = iterations + one per cycle for the true residual (none for the first cycle with use_x0 == 0, where
+ *   r = b); m_products (0 without M) = iterations + one per cycle that ran an iteration (x += M u).
+ *   workspace / workspace_bytes: the device address and size of the allocation made by create (fixed for its life). */
+typedef struct bsm_gmres_s *bsm_gmres_t;
+typedef struct {
+    int32_t struct_size; /* = sizeof(bsm_gmres_params) */
+    int32_t use_x0;
+    double rtol, atol;
+    int64_t maxiter;
+    int64_t history_capacity;
+} bsm_gmres_params;
+typedef struct {
+    int32_t status, cycles;
+    int64_t iterations;
+    double residual; /* absolute: the last estimate (or true residual norm at a restart) */
+    double bnorm;
+    int64_t a_products, m_products;
+    int64_t workspace_bytes;
+    uint64_t workspace;
+} bsm_gmres_info;
+BSM_LAYOUT_ASSERT(sizeof(bsm_gmres_params) == 40 && offsetof(bsm_gmres_params, rtol) == 8 &&
+                      offsetof(bsm_gmres_params, maxiter) == 24,
+                  "bsm_gmres_params layout");
+BSM_LAYOUT_ASSERT(sizeof(bsm_gmres_info) == 64 && offsetof(bsm_gmres_info, iterations) == 8 &&
+                      offsetof(bsm_gmres_info, a_products) == 32 && offsetof(bsm_gmres_info, workspace) == 56,
+                  "bsm_gmres_info layout");
+int bsm_gmres_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t restart, bsm_gmres_t *out);
+/* (S is a bsm_gmres_t: `struct bsm_gmres_s *` is the same type spelled out.  The spelling is an artefact -- the static
+ * checker of the bindings, tests/test_julia_ccall_signatures.py, classifies a parameter as a pointer by its `*` or by the
+ * two handle typedefs it knows --, not a second type: pass the bsm_gmres_t that bsm_gmres_create returned.) */
+int bsm_gmres_solve(struct bsm_gmres_s *S, const void *b, void *x, const bsm_gmres_params *p, bsm_gmres_info *info,
+                    double *history, int memspace, void *stream);
+int bsm_gmres_destroy(struct bsm_gmres_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

@@ -586,4 +586,44 @@ function block_jacobi(A::ROCmAnyOp, sets=_base(A).diagonalindices; scheduler::RO
     return BlockSparseMatrix(blocks, I, I, size(A); scheduler=scheduler)
 end
 
+# ---- restarted GMRES on the device (bsm_gmres_*) ----------------------------------------------------------------------
+mutable struct BsmGmresParams       # mirrors bsm_gmres_params (40 bytes)
+    struct_size::Int32; use_x0::Int32; rtol::Float64; atol::Float64; maxiter::Int64; history_capacity::Int64
+end
+mutable struct BsmGmresInfo         # mirrors bsm_gmres_info (64 bytes)
+    status::Int32; cycles::Int32; iterations::Int64; residual::Float64; bnorm::Float64
+    a_products::Int64; m_products::Int64; workspace_bytes::Int64; workspace::UInt64
+end
+
+"""
+    gmres!(x, A, b; M=nothing, restart=30, rtol=1e-8, atol=0.0, maxiter=size(A, 1), x0=false) -> (x, info, history)
+
+Right-preconditioned restarted GMRES for `A x = b`, every step of it on the device (bsm_gmres_create / _solve /
+_destroy): `A` (and the preconditioner `M`, e.g. `block_jacobi(A)`) are matrices on the MI355X path or their
+`transpose` / `adjoint` wrappers; `b` and `x` are host vectors of `A`'s element type, or complex ones of its precision
+under real `A` and `M`.  Converged when the residual estimate is `<= max(rtol * norm(b), atol)`.  `x0 = true` takes
+the incoming `x` as the initial guess.  `info.status`: 0 converged, 1 `maxiter` reached, 2 a non-finite residual;
+`history[i]` is the absolute estimate after iteration `i`.  (The reference offers nothing here: a `LinearMap` is
+handed to a Julia solver package, whose Krylov loop runs on the host.)
+"""
+function gmres!(x::Vector{T}, A::ROCmAnyOp, b::Vector{T}; M=nothing, restart::Integer=30, rtol::Real=1e-8, atol::Real=0.0,
+                maxiter::Integer=size(A, 1), x0::Bool=false) where {T<:ROCmEltype}
+    size(A, 1) == size(A, 2) == length(b) == length(x) || throw(DimensionMismatch("gmres! needs a square operator and vectors of its order"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = M === nothing ? C_NULL : handle(_base(M)).ptr
+    _check(ccall((:bsm_gmres_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), mptr, M === nothing ? 0 : _op(M), _DTYPE[T], restart, out))
+    p = BsmGmresParams(sizeof(BsmGmresParams), x0, rtol, atol, maxiter, maxiter)
+    info = BsmGmresInfo(0, 0, 0, 0.0, 0.0, 0, 0, 0, 0)
+    history = zeros(Float64, max(maxiter, 1))
+    try
+        GC.@preserve A M x b history _check(ccall((:bsm_gmres_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ref{BsmGmresParams}, Ref{BsmGmresInfo}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+            out[], pointer(b), pointer(x), p, info, history, 0, C_NULL))
+    finally
+        ccall((:bsm_gmres_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return x, info, history[1:min(info.iterations, maxiter)]
+end
+
 end # module
