@@ -2,7 +2,9 @@
 #include "bsm_analysis.h"
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,6 +32,8 @@ Tunables Tunables::from_env() {
     if (const char *f = std::getenv("BSM_FAT_FILL_BELOW")) t.fat_fill_below = std::atof(f);
     t.pack_threads = (int)geti("BSM_PACK_THREADS", t.pack_threads);
     t.wg_order = (int)geti("BSM_ORDER", t.wg_order);
+    t.wg_cap_pct = (int)geti("BSM_WG_CAP", t.wg_cap_pct);
+    t.resident_wgs = geti("BSM_RESIDENT_WGS", t.resident_wgs);
     t.deep_group_bytes = geti("BSM_DEEP_GROUP_BYTES", t.deep_group_bytes);
     t.deep_total_bytes = geti("BSM_DEEP_TOTAL_BYTES", t.deep_total_bytes);
     t.window_bytes = (size_t)geti("BSM_UPLOAD_WINDOW_BYTES", (int64_t)t.window_bytes);
@@ -336,6 +340,10 @@ uint64_t hash_list(const int64_t *p, int64_t n) {
 
 }  // namespace
 
+namespace {
+int64_t count_scale_waves(const std::vector<uint8_t> &cover, int64_t own_lo, int64_t own_hi);  // below, beside plan_cuts
+}
+
 // Working state shared by the stages of Analysis::build (each stage below is one step of the host
 // analysis; the CPU image-interpreter tests of tests/test_host_logic.py check their combined result).
 struct Analysis::BuildState {
@@ -356,6 +364,15 @@ struct Analysis::BuildState {
     int32_t ncolors_fused = 1;
     std::vector<Item> items;
     bool use_window = false;
+    // contiguous row ranges cut lower than chunk_rows: (first row << 8 | rows of the uncut chunk) -> chunk height
+    std::unordered_map<uint64_t, int32_t> cuts;
+    // the workgroup (numbered in item order) stage_waves packs every item into: a multi-wave item starts on a multiple
+    // of its wave count inside the workgroup.  THE packing rule: plan_cuts, stage_dispatch_order and stage_place_values
+    // read it, stage_waves asserts that it packs the same way.  Empty for coloured launches (classes start on
+    // workgroup boundaries).
+    std::vector<int64_t> item_wg;
+    int64_t nwg_items = 0;
+    std::vector<int64_t> wg_perm;  // balanced dispatch order: workgroup (in item order) at every dispatch slot; empty: none
 };
 
 std::string Analysis::build(int mtype_, int dtype_, int64_t nrows_, int64_t ncols_,
@@ -400,6 +417,15 @@ std::string Analysis::build(int mtype_, int dtype_, int64_t nrows_, int64_t ncol
         }
     } colour_join{colour_thread};  // also on the error returns below
     stage_work_items(st);
+    if (plan_cuts(st)) {  // some row groups are cut by rows: group again (the reference colourings only read the blocks)
+        if (!(err = stage_row_groups(blocks, st)).empty()) return err;
+        if (!(err = stage_merge_columns(blocks, st)).empty()) return err;
+        if (!(err = stage_accumulation(blocks, st)).empty()) return err;
+        stage_work_items(st);
+        assert(st.nwg_items + (count_scale_waves(st.cover, st.own_lo, st.own_hi) + kWavesPerWg - 1) / kWavesPerWg <= resident_capacity());
+        lap("row cuts: groups again");
+    }
+    stage_dispatch_order(st);
     stage_place_values(st);
     lap("work items + value placement");
     if (!(err = stage_pack_values(blocks, st)).empty()) return err;
@@ -543,73 +569,92 @@ std::string Analysis::stage_row_groups(const std::vector<BlockIn> &blocks, Build
     const int chunk_rows = tun.chunk_rows;
     std::unordered_map<uint64_t, std::vector<int64_t>> gmap;  // hash -> candidate groups
 
+    chunks.clear();
+    groups.clear();
+    glist.clear();
     rows.clear();
     cols.clear();
     for (int64_t b = 0; b < nb; b++) {
         const BlockIn &B = blocks[b];
         if (B.m == 0 || B.n == 0) continue;
-        for (int64_t ra = 0; ra < B.m; ra += chunk_rows) {
-            const int mc = (int)std::min<int64_t>(chunk_rows, B.m - ra);
-            bool rcontig = true;
-            if (B.ridx)
-                for (int i = 1; i < mc; i++)
-                    if (B.ridx[ra + i] != B.ridx[ra] + i) {
-                        rcontig = false;
-                        break;
+        for (int64_t ra0 = 0; ra0 < B.m; ra0 += chunk_rows) {
+            const int mc0 = (int)std::min<int64_t>(chunk_rows, B.m - ra0);
+            // a row range whose group was found too expensive for one workgroup (plan_cuts) is cut into lower chunks:
+            // every block of the range alike, so they meet again in one group per chunk
+            int cut_h = mc0;
+            if (!st.cuts.empty() && B.kind == KIND_PLAIN) {
+                bool contig = true;
+                if (B.ridx)
+                    for (int i = 1; i < mc0 && contig; i++) contig = B.ridx[ra0 + i] == B.ridx[ra0] + i;
+                if (contig) {
+                    const int64_t rb = (B.ridx ? B.ridx[ra0] : B.r0 + ra0) - 1;
+                    auto it = st.cuts.find(((uint64_t)rb << 8) | (uint64_t)mc0);
+                    if (it != st.cuts.end()) cut_h = it->second;
+                }
+            }
+            for (int64_t ra = ra0; ra < ra0 + mc0; ra += cut_h) {
+                const int mc = (int)std::min<int64_t>(cut_h, ra0 + mc0 - ra);
+                bool rcontig = true;
+                if (B.ridx)
+                    for (int i = 1; i < mc; i++)
+                        if (B.ridx[ra + i] != B.ridx[ra] + i) {
+                            rcontig = false;
+                            break;
+                        }
+                const int64_t rbase = rcontig ? (B.ridx ? B.ridx[ra] : B.r0 + ra) - 1 : -1;
+                uint64_t h;
+                if (rcontig)
+                    h = ((uint64_t)rbase * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)mc << 56) ^ 0x51ull;
+                else
+                    h = hash_list(B.ridx + ra, mc);
+                // plain blocks never share a group with symmetric ones; DIAG and OFF chunks of the same
+                // rows do (per-column kinds)
+                const int gkind = (B.kind == KIND_PLAIN) ? KIND_PLAIN : KIND_OFF;
+                h ^= (uint64_t)gkind * 0xD6E8FEB86659FD93ull;
+                int64_t gid = -1;
+                auto &cand = gmap[h];
+                for (int64_t g : cand) {
+                    const Group &G = groups[g];
+                    if (G.mc != mc || ((G.kind == KIND_PLAIN) != (B.kind == KIND_PLAIN))) continue;
+                    if (rcontig) {
+                        if (G.rbase == rbase) gid = g;
+                    } else if (G.rbase < 0 &&
+                               std::memcmp(glist[g], B.ridx + ra, sizeof(int64_t) * mc) == 0) {
+                        gid = g;
                     }
-            const int64_t rbase = rcontig ? (B.ridx ? B.ridx[ra] : B.r0 + ra) - 1 : -1;
-            uint64_t h;
-            if (rcontig)
-                h = ((uint64_t)rbase * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)mc << 56) ^ 0x51ull;
-            else
-                h = hash_list(B.ridx + ra, mc);
-            // plain blocks never share a group with symmetric ones; DIAG and OFF chunks of the same
-            // rows do (per-column kinds)
-            const int gkind = (B.kind == KIND_PLAIN) ? KIND_PLAIN : KIND_OFF;
-            h ^= (uint64_t)gkind * 0xD6E8FEB86659FD93ull;
-            int64_t gid = -1;
-            auto &cand = gmap[h];
-            for (int64_t g : cand) {
-                const Group &G = groups[g];
-                if (G.mc != mc || ((G.kind == KIND_PLAIN) != (B.kind == KIND_PLAIN))) continue;
-                if (rcontig) {
-                    if (G.rbase == rbase) gid = g;
-                } else if (G.rbase < 0 &&
-                           std::memcmp(glist[g], B.ridx + ra, sizeof(int64_t) * mc) == 0) {
-                    gid = g;
+                    if (gid >= 0) break;
                 }
-                if (gid >= 0) break;
-            }
-            if (gid < 0) {
-                gid = (int64_t)groups.size();
-                Group G;
-                G.mc = mc;
-                G.kind = B.kind;
-                G.rbase = (int32_t)rbase;
-                if (!rcontig) {
-                    if ((int64_t)rows.size() + mc + 8 > INT32_MAX) return "row index pool exceeds int32";
-                    G.row_off = (int32_t)rows.size();
-                    for (int i = 0; i < mc; i++) rows.push_back((int32_t)(B.ridx[ra + i] - 1));
+                if (gid < 0) {
+                    gid = (int64_t)groups.size();
+                    Group G;
+                    G.mc = mc;
+                    G.kind = B.kind;
+                    G.rbase = (int32_t)rbase;
+                    if (!rcontig) {
+                        if ((int64_t)rows.size() + mc + 8 > INT32_MAX) return "row index pool exceeds int32";
+                        G.row_off = (int32_t)rows.size();
+                        for (int i = 0; i < mc; i++) rows.push_back((int32_t)(B.ridx[ra + i] - 1));
+                    }
+                    groups.push_back(G);
+                    glist.push_back(rcontig ? nullptr : B.ridx + ra);
+                    cand.push_back(gid);
                 }
-                groups.push_back(G);
-                glist.push_back(rcontig ? nullptr : B.ridx + ra);
-                cand.push_back(gid);
+                Chunk c;
+                c.blk = (int32_t)b;
+                c.ra = (int32_t)ra;
+                c.mc = mc;
+                c.group = gid;
+                c.woff = groups[gid].width;
+                groups[gid].width += B.n;
+                if (B.kind == KIND_OFF) {
+                    groups[gid].has_off = true;
+                    groups[gid].kind = KIND_OFF;
+                } else if (B.kind == KIND_DIAG) {
+                    groups[gid].has_diag = true;
+                }
+                groups[gid].chunks.push_back((int32_t)chunks.size());
+                chunks.push_back(c);
             }
-            Chunk c;
-            c.blk = (int32_t)b;
-            c.ra = (int32_t)ra;
-            c.mc = mc;
-            c.group = gid;
-            c.woff = groups[gid].width;
-            groups[gid].width += B.n;
-            if (B.kind == KIND_OFF) {
-                groups[gid].has_off = true;
-                groups[gid].kind = KIND_OFF;
-            } else if (B.kind == KIND_DIAG) {
-                groups[gid].has_diag = true;
-            }
-            groups[gid].chunks.push_back((int32_t)chunks.size());
-            chunks.push_back(c);
         }
     }
     ngroups = (int64_t)groups.size();
@@ -636,6 +681,8 @@ std::string Analysis::stage_merge_columns(const std::vector<BlockIn> &blocks, Bu
     // index: neighbouring lanes then gather neighbouring x entries and emit neighbouring y
     // entries, and scattered index lists (BEM near-field panels) collapse into contiguous runs.
     group_perm.assign(groups.size(), 0);
+    colpos.clear();
+    ckind.clear();
     colpos.reserve(cols.capacity());
     ckind.reserve(cols.capacity());
     {
@@ -846,6 +893,157 @@ void Analysis::stage_work_items(BuildState &st) {
         if (use_window && a.nw < 4) return locality(a) < locality(b);
         return a.bytes > b.bytes;
     });
+    st.item_wg.clear();
+    st.nwg_items = 0;
+    if (!colored) {
+        int64_t pos = 0;
+        for (const Item &it : items) {
+            while ((pos % kWavesPerWg) % it.nw != 0) pos++;
+            st.item_wg.push_back(pos / kWavesPerWg);
+            pos += it.nw;
+        }
+        st.nwg_items = (pos + kWavesPerWg - 1) / kWavesPerWg;
+    }
+}
+
+// ---- one resident round: every workgroup of the launch is on the chip at once --------------------------------
+// Workgroups a device holds at once: CUs x the waves per SIMD the forward kernel of the element type is compiled for
+// (bsm_one.hip: 6 for 8- and 16-byte vectors, 5 for float / complex64; 4 SIMDs per CU, kWavesPerWg waves per workgroup).
+int64_t Analysis::resident_capacity() const {
+    if (tun.resident_wgs > 0) return tun.resident_wgs;
+    const int64_t cus = opt.num_cus > 0 ? opt.num_cus : 256;
+    const int64_t waves_per_simd = (dtype == 0 || dtype == 2) ? 5 : 6;
+    return cus * 4 * waves_per_simd / kWavesPerWg;
+}
+
+namespace {
+// waves of scale work an exclusive forward launch gets for the rows no group covers (stage_waves)
+int64_t count_scale_waves(const std::vector<uint8_t> &cover, int64_t own_lo, int64_t own_hi) {
+    int64_t n = 0, r = own_lo;
+    while (r < own_hi) {
+        if (cover[r]) {
+            r++;
+            continue;
+        }
+        int64_t e = r;
+        while (e < own_hi && !cover[e] && e - r < kScaleRowsPerWave) e++;
+        n++;
+        r = e;
+    }
+    return n;
+}
+}  // namespace
+
+// ---- cap the cost of a workgroup: outlier row groups are cut by rows ---------------------------------------------
+// A one-round launch is as long as its most loaded CU, and nothing rebalances a CU's share after dispatch: a row group
+// of 128 KB is one workgroup (its rows stay exclusive) and 60 % of a CU's mean share of a C2-sized operator.  Row groups
+// that fill a workgroup of their own and cost more than wg_cap_pct % of the mean workgroup (bytes) are cut into k = ceil(cost / cap) chunks of
+// ceil(rows / k) rows rounded up to a multiple of 8 (64 -> 32 + 32 keeps the lanes full), each a row group of its own:
+// rows stay exclusive, nothing is combined.  Only contiguous row ranges of plain blocks are cut.  The launch must stay one
+// round: while the cuts would add more workgroups than the device holds, the cap is raised.  Fills st.cuts; true when
+// stage_row_groups has to run again.
+bool Analysis::plan_cuts(BuildState &st) {
+    st.cuts.clear();
+    if (tun.wg_cap_pct <= 0 || !exclusive_fwd || st.colored || gather || st.sym) return false;
+    int64_t nwaves = 0, bytes = 0;
+    for (const Item &it : st.items) {
+        nwaves += it.nw;
+        bytes += it.bytes;
+    }
+    const int64_t scale_wgs = (count_scale_waves(st.cover, st.own_lo, st.own_hi) + kWavesPerWg - 1) / kWavesPerWg;
+    const int64_t nwg = st.nwg_items, capacity = resident_capacity();
+    if (nwg < 2 || nwg + scale_wgs > capacity) return false;  // several rounds: the split stays as it is
+    auto waves_of = [&](int64_t b) { return b >= tun.split4_bytes ? 4 : (b >= tun.split2_bytes ? 2 : 1); };
+    double cap = (double)bytes / (double)nwg * tun.wg_cap_pct / 100.0;
+    for (int attempt = 0; attempt < 64; attempt++, cap *= 1.1) {
+        st.cuts.clear();
+        int64_t extra = 0;
+        for (const Item &it : st.items) {
+            const Group &G = st.groups[it.group];
+            if (it.nw < kWavesPerWg || (double)it.bytes <= cap || G.rbase < 0 || G.kind != KIND_PLAIN || G.mc < 16) continue;
+            const int64_t k = (int64_t)std::ceil((double)it.bytes / cap);
+            const int h = (int)std::max<int64_t>(8, ((G.mc + k - 1) / k + 7) / 8 * 8);
+            if (h >= G.mc) continue;
+            for (int r = 0; r < G.mc; r += h) extra += waves_of((int64_t)std::min(h, G.mc - r) * G.strips * 16);
+            extra -= it.nw;
+            st.cuts[((uint64_t)G.rbase << 8) | (uint64_t)G.mc] = h;
+        }
+        if (st.cuts.empty()) return false;
+        // the items are sorted by waves descending (4, 2, 1): no slot is lost to alignment and the cut launch has
+        // ceil(waves / 4) workgroups; build() checks the count again on the items of the cut launch
+        if ((nwaves + extra + kWavesPerWg - 1) / kWavesPerWg + scale_wgs <= capacity) return true;
+    }
+    st.cuts.clear();
+    return false;
+}
+
+// ---- balanced dispatch order of a one-round exclusive forward launch (BSM_ORDER=2) ------------------------------
+// Every workgroup of such a launch is resident at once, so the launch ends when the most loaded CU does.  The dispatcher
+// deals the workgroups out in index order: slot k goes to XCD k % 8 and there round the XCD's 32 CUs, so the slots k,
+// k + 256, k + 512, .. share one CU.  WHICH CU that is rotates from launch to launch, the grouping does not (single
+// launches, back-to-back launches and graph replays of C2: tools/placement_census.py, docs/experiments_r20.md), and a
+// CU's last store follows the bytes of its workgroups (R^2 0.72-0.83; lane-padded bytes 0.68, iterations 0.60).
+// Largest first, every workgroup goes to the CU with the smallest sum of bytes that still has a free slot: the
+// longest-processing-time rule.  Fills st.wg_perm (the workgroups of stage_waves, numbered in item order).
+static int64_t dispatch_cu(int64_t slot, int64_t ncus) { return slot % ncus; }
+
+void Analysis::stage_dispatch_order(BuildState &st) {
+    st.wg_perm.clear();
+    const int order = tun.wg_order < 0 ? 2 : tun.wg_order;
+    if (order != 2 || !exclusive_fwd || st.colored) return;
+    const int64_t nwg = st.nwg_items;
+    std::vector<int64_t> cost((size_t)nwg, 0);  // bytes of every workgroup (BuildState::item_wg)
+    for (size_t i = 0; i < st.items.size(); i++) cost[(size_t)st.item_wg[i]] += st.items[i].bytes;
+    const int64_t scale_wgs = (count_scale_waves(st.cover, st.own_lo, st.own_hi) + kWavesPerWg - 1) / kWavesPerWg;
+    if (nwg < 3 || nwg + scale_wgs > resident_capacity()) return;  // several rounds: a CU's share is not fixed at dispatch
+    const int64_t ncus = std::min<int64_t>(nwg, opt.num_cus > 0 ? opt.num_cus : 256);
+    std::vector<std::vector<int64_t>> slots((size_t)ncus);  // dispatch slots of every CU, ascending
+    for (int64_t k = 0; k < nwg; k++) slots[(size_t)dispatch_cu(k, ncus)].push_back(k);
+    std::vector<int64_t> by_cost((size_t)nwg);
+    std::iota(by_cost.begin(), by_cost.end(), 0);
+    std::stable_sort(by_cost.begin(), by_cost.end(), [&](int64_t a, int64_t b) { return cost[a] > cost[b]; });
+    using Load = std::pair<int64_t, int64_t>;  // (bytes so far, CU)
+    std::set<Load> open;
+    for (int64_t c = 0; c < ncus; c++)
+        if (!slots[(size_t)c].empty()) open.insert(Load(0, c));
+    std::vector<std::vector<int64_t>> mine((size_t)ncus);  // workgroups of every CU, largest first
+    std::vector<int64_t> load((size_t)ncus, 0);
+    for (int64_t w : by_cost) {
+        const Load l = *open.begin();
+        open.erase(open.begin());
+        const size_t c = (size_t)l.second;
+        mine[c].push_back(w);
+        load[c] += cost[w];
+        if (mine[c].size() < slots[c].size()) open.insert(Load(load[c], l.second));
+    }
+    // the slot counts bind (a full chip gives every CU the same number of workgroups), so the rule alone leaves a few
+    // per cent: the most loaded CU then trades one workgroup for a smaller one of another CU while that lowers the larger
+    // of the two sums
+    for (int64_t round = 0; round < 8 * ncus; round++) {
+        const size_t a = (size_t)(std::max_element(load.begin(), load.end()) - load.begin());
+        int64_t best = load[a];
+        size_t bc = 0, bi = 0, bj = 0;
+        for (size_t c = 0; c < (size_t)ncus; c++) {
+            if (c == a) continue;
+            for (size_t i = 0; i < mine[a].size(); i++)
+                for (size_t j = 0; j < mine[c].size(); j++) {
+                    const int64_t d = cost[mine[a][i]] - cost[mine[c][j]];
+                    if (d <= 0) continue;
+                    const int64_t worst = std::max(load[a] - d, load[c] + d);
+                    if (worst < best) best = worst, bc = c, bi = i, bj = j;
+                }
+        }
+        if (best == load[a]) break;
+        const int64_t d = cost[mine[a][bi]] - cost[mine[bc][bj]];
+        std::swap(mine[a][bi], mine[bc][bj]);
+        load[a] -= d;
+        load[bc] += d;
+    }
+    st.wg_perm.assign((size_t)nwg, -1);
+    for (size_t c = 0; c < (size_t)ncus; c++) {
+        std::stable_sort(mine[c].begin(), mine[c].end(), [&](int64_t a, int64_t b) { return cost[a] > cost[b]; });
+        for (size_t i = 0; i < mine[c].size(); i++) st.wg_perm[(size_t)slots[c][i]] = mine[c][i];
+    }
 }
 
 // ---- value stream layout: the panels lie in the order in which the launch reaches them --------------------
@@ -857,10 +1055,19 @@ void Analysis::stage_place_values(BuildState &st) {
     std::vector<uint8_t> placed(groups.size(), 0);
     st.layout.clear();
     st.layout.reserve(groups.size());
-    for (const Item &it : st.items)
-        if (!placed[it.group]) {
-            placed[it.group] = 1;
-            st.layout.push_back(it.group);
+    std::vector<const Item *> order;  // the items in the order their workgroups are dispatched
+    order.reserve(st.items.size());
+    if (st.wg_perm.empty()) {
+        for (const Item &it : st.items) order.push_back(&it);
+    } else {
+        std::vector<std::vector<const Item *>> of_wg(st.wg_perm.size());
+        for (size_t i = 0; i < st.items.size(); i++) of_wg[(size_t)st.item_wg[i]].push_back(&st.items[i]);
+        for (int64_t w : st.wg_perm) order.insert(order.end(), of_wg[(size_t)w].begin(), of_wg[(size_t)w].end());
+    }
+    for (const Item *it : order)
+        if (!placed[it->group]) {
+            placed[it->group] = 1;
+            st.layout.push_back(it->group);
         }
     for (size_t g = 0; g < groups.size(); g++)
         if (!placed[g]) st.layout.push_back((int64_t)g);
@@ -1084,15 +1291,25 @@ void Analysis::stage_waves(BuildState &st) {
             cur_color = it.color;
         }
         item_waves(it);
+        // one packing rule: the item sits in the workgroup BuildState::item_wg names
+        assert(colored || (int64_t)(waves.size() - (size_t)it.nw) / kWavesPerWg == st.item_wg[(size_t)(&it - items.data())]);
     }
     while (waves.size() % kWavesPerWg) emit_nop();
     nwg_main = (int64_t)waves.size() / kWavesPerWg;
+    assert(colored || nwg_main == st.nwg_items);
     // dispatch order: largest first; for exclusive forward images every other block of 256 workgroups
     // (one per CU) is reversed, so that the same CUs do not receive the larger workgroup of every
     // layer (C2-sized operators: +2.5 %; neutral on long launches).  BSM_ORDER=0 keeps plain
-    // largest-first.
+    // largest-first, BSM_ORDER=2 (the default) balances one-round launches and leaves the snake to the others.
     const bool snake = tun.wg_order != 0 && exclusive_fwd;
-    if (!colored && snake && nwg_main > 2) {
+    if (!st.wg_perm.empty()) {
+        assert((int64_t)st.wg_perm.size() == nwg_main);
+        // balanced (stage_dispatch_order): dispatch slot k runs workgroup wg_perm[k]
+        std::vector<WaveWork> re(waves.size());
+        for (int64_t k = 0; k < nwg_main; k++)
+            for (int w = 0; w < kWavesPerWg; w++) re[k * kWavesPerWg + w] = waves[st.wg_perm[k] * kWavesPerWg + w];
+        waves.swap(re);
+    } else if (!colored && snake && nwg_main > 2) {
         std::vector<WaveWork> re(waves.size());
         const int64_t blk = 256;
         int64_t k = 0;

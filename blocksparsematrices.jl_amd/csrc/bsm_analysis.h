@@ -87,7 +87,14 @@ struct Tunables {
     int pack_threads = 8;
     size_t window_bytes = 64u << 20;  // staging window of a streamed upload (BSM_UPLOAD_WINDOW_BYTES)
     int lds_window = 1;  // LDS y window for locality-packed small symmetric row groups
-    int wg_order = -1;  // workgroup dispatch order (BSM_ORDER): -1 auto (snake for exclusive images), 0 plain largest first
+    // Workgroup dispatch order (BSM_ORDER) of exclusive forward images: 0 plain largest first, 1 snake (every other
+    // block of 256 workgroups reversed), 2 balanced (one-round launches: largest first into the least loaded CU of the
+    // measured placement, stage_waves; launches of several rounds fall back to the snake); -1 auto = 2
+    int wg_order = -1;
+    // One-round exclusive forward launches: a row group that costs more than wg_cap_pct % of the launch's mean
+    // workgroup is cut by rows into chunks of its own (plan_cuts).  BSM_WG_CAP, 0 = never cut.
+    int wg_cap_pct = 150;
+    int64_t resident_wgs = 0;  // workgroups of one resident round (BSM_RESIDENT_WGS); 0: CUs x waves per SIMD of the kernel
     static Tunables from_env();
 };
 
@@ -116,6 +123,7 @@ struct AnalysisOptions {
     int coloring = 0;  // reference colourings: 0 WorkstreamDSATUR (the reference's default), 1 plain DSATUR
     bool meta_only = false;    // validation, statistics and the reference colourings only (no image)
     bool skip_colors = false;  // leave `colors` empty (the parts of a multi-device handle)
+    int num_cus = 0;           // compute units of the device the image is built for (0: unknown, an MI355X's 256)
 };
 
 // Deterministic DSATUR colouring of blocks by index-list conflicts (two blocks conflict
@@ -206,6 +214,9 @@ class Analysis {
     std::string stage_merge_columns(const std::vector<BlockIn> &blocks, BuildState &st);
     std::string stage_accumulation(const std::vector<BlockIn> &blocks, BuildState &st);
     void stage_work_items(BuildState &st);
+    int64_t resident_capacity() const;
+    bool plan_cuts(BuildState &st);
+    void stage_dispatch_order(BuildState &st);
     void stage_place_values(BuildState &st);
     std::string stage_pack_values(const std::vector<BlockIn> &blocks, BuildState &st);
     void stage_waves(BuildState &st);

@@ -251,7 +251,10 @@ template <typename T, int CUR, int D> struct ReduceAbove {
 static __device__ unsigned long long *g_trace = nullptr;
 static hipError_t set_trace_here(void *buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_trace), &buf, sizeof(buf)); }
 __shared__ unsigned long long t_trace[kWavesPerWg][16];
-#define BSM_TSTAMP(slot)                                                   \
+// s_getreg operands (id | offset << 6 | (size - 1) << 11), all 32 bits: HW_REG_HW_ID = 4, HW_REG_XCC_ID = 20
+#define BSM_GETREG_HW_ID (4 | (31 << 11))
+#define BSM_GETREG_XCC_ID (20 | (31 << 11))
+#define BSM_TSTAMP(slot)                                                  \
     do {                                                                   \
         if (lane == 0) t_trace[threadIdx.x >> 6][(slot)] = clock64();      \
     } while (0)

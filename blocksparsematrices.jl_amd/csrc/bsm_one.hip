@@ -348,6 +348,10 @@ __global__ void __launch_bounds__(64 * kWavesPerWg) __attribute__((amdgpu_waves_
         t_trace[threadIdx.x >> 6][6] =
             (unsigned long long)(wd.work == WORK_PANEL && wd.npieces ? (long long)wd.first.nstrips * wd.m * 16 : 0);
         t_trace[threadIdx.x >> 6][7] = wall_clock64();
+        // where the wave runs (tools/placement_census.py): slot 9 = HW_ID (wave 3:0, SIMD 5:4, CU 11:8, SH 12, SE 15:13),
+        // slot 10 = XCC_ID (XCD 3:0); plain register reads
+        t_trace[threadIdx.x >> 6][9] = (unsigned long long)__builtin_amdgcn_s_getreg(BSM_GETREG_HW_ID);
+        t_trace[threadIdx.x >> 6][10] = (unsigned long long)__builtin_amdgcn_s_getreg(BSM_GETREG_XCC_ID);
     }
 #endif
     // workgroup-uniform (all 4 descriptors carry the same window; coloured launches keep plain RMW)

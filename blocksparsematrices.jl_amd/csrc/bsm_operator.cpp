@@ -728,6 +728,14 @@ int LocalOperator::build(int mtype, int dtype, int64_t nrows, int64_t ncols, con
     DeviceSink sink(&img.d_values), sink_t(&img_t.d_values);
     AnalysisOptions ao = to_aopt(o, streamed ? &sink : nullptr);
     ao.skip_colors = !colors;
+    // what one resident round of the device holds decides how far outlier row groups may be cut (Analysis::plan_cuts)
+    if (device != BSM_DEVICE_NONE) {
+        int ncu = 0;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess)
+            ao.num_cus = ncu;
+        else
+            (void)hipGetLastError();
+    }
     std::string err = an.build(mtype, dtype, nrows, ncols, in, ao);
     ao.sink = nullptr;
     bool want_t = o.transpose_image == 1;
@@ -741,6 +749,7 @@ int LocalOperator::build(int mtype, int dtype, int64_t nrows, int64_t ncols, con
     // second ordering: the transposed operator as a forward image (rows <-> columns, blocks read transposed by the
     // packer), built from the same caller arrays
     AnalysisOptions ao_t = transpose_aopt(o);
+    ao_t.num_cus = ao.num_cus;
     if (err.empty() && want_t && mtype != MT_SYMMETRIC) {
         bool plain = true;
         for (const BlockIn &B : in) plain &= (B.kind == KIND_PLAIN);
