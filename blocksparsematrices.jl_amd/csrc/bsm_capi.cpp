@@ -1,4 +1,5 @@
-// bsm_capi.cpp -- the extern "C" surface of libbsmrocm.so (include/bsm_rocm.h).
+// bsm_capi.cpp -- the extern "C" surface of libbsmrocm.so (include/bsm_rocm.h), but for the features whose unit holds
+// its own entry points: reading entries (bsm_entries.cpp), the block inverse (bsm_invert.cpp), GMRES (bsm_krylov.cpp).
 // Plain pointers and sizes only; checks and converts arguments, has the operator built, refilled and
 // released (bsm_operator.cpp: LocalOperator; bsm_dist.cpp for handles over several devices) and
 // forwards bsm_mul to the HIP launchers.  Never throws across the ABI.
@@ -14,7 +15,6 @@
 #include <vector>
 
 #include "bsm_internal.h"
-#include "bsm_invert.h"
 
 using namespace bsm;
 
@@ -194,7 +194,7 @@ int create_handle(int mtype, int dtype, int64_t nrows, int64_t ncols, const std:
         A->blk_m[(size_t)ids[b]] = in[b].m;
         A->blk_n[(size_t)ids[b]] = in[b].n;
     }
-    if (o.ctx && (dtype == BSM_F64_F32 || dtype == BSM_C128_C64))
+    if (o.ctx && is_mixed(dtype))
         return fail(BSM_ERR_UNSUPPORTED, "mixed-precision storage (BSM_F64_F32 / BSM_C128_C64) is single-device only: "
                                          "create without bsm_options.ctx");
     if (o.ctx) {
@@ -235,15 +235,6 @@ int create_vbcrs(int dtype, int64_t nrows, int64_t ncols, const std::vector<Bloc
 }
 
 }  // namespace
-
-#define BSM_GUARDED(...)                                         \
-    try {                                                        \
-        __VA_ARGS__                                              \
-    } catch (const std::bad_alloc &) {                           \
-        return fail(BSM_ERR_ALLOC, "out of host memory");        \
-    } catch (const std::exception &e) {                          \
-        return fail(BSM_ERR_INVALID, e.what());                  \
-    }
 
 extern "C" int bsm_vbcrs_create(int dtype, int64_t nrows, int64_t ncols, int64_t nblocks,
                                 const void *const *blocks, const int64_t *m, const int64_t *n,
@@ -457,460 +448,6 @@ extern "C" int bsm_partition_rows(int64_t nrows, int64_t nblocks, const int64_t 
         return BSM_OK;)
 }
 
-namespace {
-// triples of one packed image -> device buffers of its device (orow / ocol int64, oval element type)
-int export_image(const Analysis &an, const DeviceImage &img, void *orow, void *ocol, void *oval, hipStream_t st) {
-    const long long nw = (long long)an.waves.size();
-    std::vector<long long> off((size_t)nw + 1, 0);
-    for (long long w = 0; w < nw; w++) {
-        const WaveWork &W = an.waves[w];
-        long long cnt = 0;
-        if (W.work == WORK_PANEL && W.npieces > 0) {
-            const Piece &P = W.first;
-            long long noff = 0;
-            if (P.xbase < 0) {
-                if ((P.kind & 3) == KIND_OFF)
-                    for (int32_t k = 0; k < P.ncols; k++) noff += an.cols[(size_t)P.col_off + k] >= 0;
-            } else {
-                const long long w1 = std::min<long long>(W.seg1_w, P.ncols), w2 = std::min<long long>(W.seg2_w, P.ncols);
-                if ((P.kind & 3) == KIND_OFF) noff += w1;
-                if (((P.kind >> 2) & 3) == KIND_OFF) noff += std::max<long long>(0, w2 - w1);
-                if (((P.kind >> 4) & 3) == KIND_OFF) noff += std::max<long long>(0, P.ncols - w2);
-            }
-            cnt = (long long)W.m * (P.ncols + noff);
-        }
-        off[w + 1] = off[w] + cnt;
-    }
-    if (off[nw] != an.nnz) return fail(BSM_ERR_DEVICE, "rowcolvals: image / nnz mismatch");
-    if (nw == 0 || an.nnz == 0) return BSM_OK;
-    void *d_off = nullptr;
-    hipError_t e = hipMalloc(&d_off, off.size() * sizeof(long long));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-        e = launch_export_coo(an.dtype, img.d_waves, nw, d_off, img.d_values, img.d_rows, img.d_cols, orow, ocol, oval, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_off) (void)hipFree(d_off);
-    if (e != hipSuccess) return hip_fail(e, "rowcolvals");
-    return BSM_OK;
-}
-}  // namespace
-
-extern "C" int bsm_rowcolvals(bsm_matrix_t A, int64_t *rows, int64_t *cols, void *vals, int64_t *count,
-                              int memspace, void *stream) {
-    BSM_GUARDED(
-        if (!A || !count) return fail(BSM_ERR_INVALID, "null argument");
-        if (!rows || !cols || !vals) {
-            *count = A->an.nnz;
-            return BSM_OK;
-        }
-        if (*count < A->an.nnz) return fail(BSM_ERR_INVALID, "output buffers too small");
-        if (!A->on_device) return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
-        if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-        const size_t es = (size_t)A->an.vs;  // the stored values leave widened to the vector type
-        // one image per device part (a single one for ordinary handles); parts are written one after another
-        std::vector<std::pair<const Analysis *, const DeviceImage *>> imgs;
-        if (A->dist)
-            dist_images(A, imgs);
-        else
-            imgs.emplace_back(&A->an, &A->img);
-        int64_t done = 0;
-        for (auto &pi : imgs) {
-            const Analysis &an = *pi.first;
-            const DeviceImage &img = *pi.second;
-            const int64_t n = an.nnz;
-            if (n == 0) continue;
-            DeviceGuard g;
-            hipError_t e = g.enter(img.device);
-            if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-            // staged through buffers on the image's device unless the caller's arrays already live there
-            bool direct = false;
-            if (memspace == BSM_MEM_DEVICE && !A->dist) direct = true;
-            void *r = nullptr; void *c = nullptr; void *v = nullptr;
-            if (direct) {
-                r = rows + done;
-                c = cols + done;
-                v = (char *)vals + (size_t)done * es;
-            } else {
-                e = hipMalloc(&r, (size_t)n * 8);
-                if (e == hipSuccess) e = hipMalloc(&c, (size_t)n * 8);
-                if (e == hipSuccess) e = hipMalloc(&v, (size_t)n * es);
-                if (e != hipSuccess) {
-                    for (void *q : {r, c, v}) if (q) (void)hipFree(q);
-                    return hip_fail(e, "rowcolvals staging");
-                }
-            }
-            int rc = export_image(an, img, r, c, v, direct ? (hipStream_t)stream : nullptr);
-            if (rc == BSM_OK && !direct) {
-                e = hipMemcpy(rows + done, r, (size_t)n * 8, hipMemcpyDefault);
-                if (e == hipSuccess) e = hipMemcpy(cols + done, c, (size_t)n * 8, hipMemcpyDefault);
-                if (e == hipSuccess) e = hipMemcpy((char *)vals + (size_t)done * es, v, (size_t)n * es, hipMemcpyDefault);
-                if (e != hipSuccess) rc = hip_fail(e, "rowcolvals copy");
-            }
-            if (!direct) for (void *q : {r, c, v}) (void)hipFree(q);
-            if (rc != BSM_OK) return rc;
-            done += n;
-        }
-        *count = done;
-        return BSM_OK;)
-}
-
-// ---- bsm_submatrices / bsm_diag: entries of the operator read out of its image -------------------------------------------
-namespace {
-// one output window: ni x nj entries of the vector type at `out`, leading dimension ld (elements).  diag(A) is one
-// window of min(nrows, ncols) x 1
-struct Window {
-    int64_t ni, nj, ld;
-    void *out;
-};
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-int vector_code(int dtype) { return dtype == BSM_F64_F32 ? BSM_F64 : dtype == BSM_C128_C64 ? BSM_C128 : dtype; }
-
-// The host image of an analysis-only handle, by a plain loop over the wave records the kernel walks (bsm_extract.hip:
-// same decode, same conditions, same addresses).  R / RS: real type of the vector / stored type, NC: 2 for complex.
-// maps: rset, rpos (nrows each), cset, cpos (ncols each); null: diag(A) into win[0].  The windows are zero beforehand.
-template <typename R, typename RS, int NC>
-void extract_host(const Analysis &an, const int32_t *maps, const std::vector<Window> &win, bool opT, bool conj) {
-    const int32_t *rset = maps, *rpos = maps ? maps + an.nrows : nullptr;
-    const int32_t *cset = maps ? maps + 2 * an.nrows : nullptr, *cpos = maps ? maps + 2 * an.nrows + an.ncols : nullptr;
-    auto add = [&](void *base, int64_t idx, const RS *v) {
-        R *p = (R *)base + idx * NC;
-        p[0] += (R)v[0];
-        if (NC == 2) p[NC - 1] += conj ? -(R)v[NC - 1] : (R)v[NC - 1];
-    };
-    const int E = an.E;
-    for (const WaveWork &W : an.waves) {
-        if (W.work != WORK_PANEL || W.npieces == 0) continue;
-        const Piece &P = W.first;
-        const int64_t m = W.m;
-        const RS *vb = (const RS *)(an.values.data() + P.val_off * 16);
-        for (int32_t w = 0; w < P.ncols; w++) {
-            bool off;
-            int64_t ci;
-            if (P.xbase < 0) {
-                const int32_t raw = an.cols[(size_t)P.col_off + w];
-                off = raw >= 0 && (P.kind & 3) == KIND_OFF;
-                ci = raw & 0x7fffffff;
-            } else {
-                const int sh = w < W.seg1_w ? 0 : (w < W.seg2_w ? 2 : 4);
-                off = ((P.kind >> sh) & 3) == KIND_OFF;
-                ci = w < W.seg1_w ? P.xbase + w : (w < W.seg2_w ? W.seg1_x + (w - W.seg1_w) : P.seg2_x + (w - W.seg2_w));
-            }
-            const int64_t s = w / E, e = w % E;
-            for (int64_t i = 0; i < m; i++) {
-                const int64_t ri = (W.rbase >= 0) ? (int64_t)W.rbase + i : an.rows[(size_t)W.row_off + i];
-                const RS *v = vb + ((s * m + i) * E + e) * NC;
-                if (!maps) {
-                    if (ri == ci) {
-                        add(win[0].out, ri, v);
-                        if (off) add(win[0].out, ri, v);
-                    }
-                    continue;
-                }
-                const int32_t fs = rset[ri];
-                if (fs >= 0 && cset[ci] == fs) {
-                    const Window &o = win[(size_t)fs];
-                    add(o.out, opT ? cpos[ci] + o.ld * rpos[ri] : rpos[ri] + o.ld * cpos[ci], v);
-                }
-                if (off && ci < an.nrows && ri < an.ncols) {  // the transposed copy sits at (ci, ri)
-                    const int32_t us = rset[ci];
-                    if (us >= 0 && cset[ri] == us) {
-                        const Window &o = win[(size_t)us];
-                        add(o.out, opT ? cpos[ri] + o.ld * rpos[ci] : rpos[ci] + o.ld * cpos[ri], v);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// one packed image -> windows in the memory of its device (current): uploads the maps and the table of windows, zeroes
-// the windows when `shape` says which they are, runs the kernel on `st` and waits for it
-int extract_image(const Analysis &an, const DeviceImage &img, const std::vector<int32_t> *maps, const std::vector<ExtractOut> &table,
-                  const std::vector<long long> *shape, void *d_diag, bool opT, bool conj, hipStream_t st) {
-    // one allocation: the maps, behind them the table of windows and their shapes (16-byte aligned)
-    DevBuf db;
-    ExtractMaps mp{nullptr, nullptr, nullptr, nullptr};
-    void *d_table = nullptr;
-    hipError_t e = hipSuccess;
-    if (maps) {
-        const size_t mb = (maps->size() * 4 + 15) / 16 * 16, tb = table.size() * sizeof(ExtractOut);
-        e = db.alloc(mb + tb + (shape ? shape->size() * 8 : 0));
-        if (e == hipSuccess) e = hipMemcpyAsync(db.p, maps->data(), maps->size() * 4, hipMemcpyHostToDevice, st);
-        d_table = (char *)db.p + mb;
-        if (e == hipSuccess && !table.empty()) e = hipMemcpyAsync(d_table, table.data(), tb, hipMemcpyHostToDevice, st);
-        const int *b = (const int *)db.p;
-        mp = ExtractMaps{b, b + an.nrows, b + 2 * an.nrows, b + 2 * an.nrows + an.ncols};
-        if (e == hipSuccess && shape) {
-            long long largest = 0;
-            for (size_t s = 0; s < table.size(); s++) largest = std::max(largest, (*shape)[2 * s] * (*shape)[2 * s + 1]);
-            void *d_shape = (char *)d_table + tb;
-            if (!shape->empty()) e = hipMemcpyAsync(d_shape, shape->data(), shape->size() * 8, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess)
-                e = launch_zero_windows(vector_code(an.dtype), d_table, d_shape, (long long)table.size(), largest, st);
-        }
-    }
-    if (e == hipSuccess)
-        e = launch_extract(an.dtype, img.d_waves, (long long)an.waves.size(), img.d_values, img.d_rows, img.d_cols,
-                           maps ? &mp : nullptr, d_table, d_diag, an.nrows, an.ncols, opT, conj, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(e, "extract");
-    return BSM_OK;
-}
-
-// the checked request (maps == nullptr: diag(A), win[0] = d) on whatever the handle is made of
-int extract_run(bsm_matrix_s *A, int op, const std::vector<int32_t> *maps, const std::vector<Window> &win, int memspace,
-                hipStream_t stream) {
-    const Analysis &an0 = A->an;
-    const size_t vs = (size_t)an0.vs;
-    const int vt = vector_code(an0.dtype);
-    const bool opT = op != BSM_OP_N, conj = op == BSM_OP_C;
-    if (!A->on_device) {  // analysis-only handle, host windows: zeroed, then summed
-        for (const Window &w : win)
-            for (int64_t b = 0; b < w.nj; b++) std::memset((char *)w.out + (size_t)(b * w.ld) * vs, 0, (size_t)w.ni * vs);
-        const int32_t *mp = maps ? maps->data() : nullptr;
-        switch (an0.dtype) {
-            case BSM_F32: extract_host<float, float, 1>(an0, mp, win, opT, conj); break;
-            case BSM_F64: extract_host<double, double, 1>(an0, mp, win, opT, conj); break;
-            case BSM_C64: extract_host<float, float, 2>(an0, mp, win, opT, conj); break;
-            case BSM_C128: extract_host<double, double, 2>(an0, mp, win, opT, conj); break;
-            case BSM_F64_F32: extract_host<double, float, 1>(an0, mp, win, opT, conj); break;
-            case BSM_C128_C64: extract_host<double, float, 2>(an0, mp, win, opT, conj); break;
-            default: return fail(BSM_ERR_INVALID, "bad dtype");
-        }
-        return BSM_OK;
-    }
-    if (memspace == BSM_MEM_DEVICE && !A->dist) {  // straight into the caller's windows
-        DeviceGuard g;
-        hipError_t e = g.enter(A->img.device);
-        if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        if (!maps) {
-            if (win[0].ni == 0) return BSM_OK;
-            e = hipMemsetAsync(win[0].out, 0, (size_t)win[0].ni * vs, stream);
-            if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync");
-            return extract_image(A->an, A->img, nullptr, {}, nullptr, win[0].out, opT, conj, stream);
-        }
-        std::vector<ExtractOut> table(win.size());
-        std::vector<long long> shape(2 * win.size());
-        for (size_t s = 0; s < win.size(); s++) {
-            table[s] = ExtractOut{(uint64_t)(uintptr_t)win[s].out, (long long)win[s].ld};
-            shape[2 * s] = win[s].ni;
-            shape[2 * s + 1] = win[s].nj;
-        }
-        return extract_image(A->an, A->img, maps, table, &shape, nullptr, opT, conj, stream);
-    }
-    // host windows, or a multi-device handle: every image adds into a zeroed, compact staging buffer on its own device;
-    // the buffers come back to the host, are summed there (an entry lives in exactly one part) and delivered
-    std::vector<size_t> off(win.size() + 1, 0);
-    for (size_t s = 0; s < win.size(); s++) off[s + 1] = off[s] + (size_t)win[s].ni * (size_t)win[s].nj;
-    const size_t total = off[win.size()];
-    if (total == 0) return BSM_OK;
-    std::vector<std::pair<const Analysis *, const DeviceImage *>> imgs;
-    if (A->dist)
-        dist_images(A, imgs);
-    else
-        imgs.emplace_back(&A->an, &A->img);
-    std::vector<char> sum(total * vs, 0), part;
-    bool first = true;
-    for (auto &pi : imgs) {
-        DeviceGuard g;
-        hipError_t e = g.enter(pi.second->device);
-        if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        DevBuf stg;
-        e = stg.alloc(total * vs);
-        if (e == hipSuccess) e = hipMemsetAsync(stg.p, 0, total * vs, nullptr);
-        if (e != hipSuccess) return hip_fail(e, "extract staging");
-        std::vector<ExtractOut> table(maps ? win.size() : 0);
-        for (size_t s = 0; s < table.size(); s++)
-            table[s] = ExtractOut{(uint64_t)(uintptr_t)((char *)stg.p + off[s] * vs), (long long)std::max<int64_t>(win[s].ni, 1)};
-        const int rc = extract_image(*pi.first, *pi.second, maps, table, nullptr, stg.p, opT, conj, nullptr);
-        if (rc != BSM_OK) return rc;
-        std::vector<char> &dst = first ? sum : part;
-        dst.resize(total * vs);
-        e = hipMemcpy(dst.data(), stg.p, total * vs, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "extract copy");
-        if (!first) {
-            if (vt == BSM_F32 || vt == BSM_C64) {
-                float *a = (float *)sum.data();
-                const float *b = (const float *)part.data();
-                for (size_t k = 0; k < total * vs / 4; k++) a[k] += b[k];
-            } else {
-                double *a = (double *)sum.data();
-                const double *b = (const double *)part.data();
-                for (size_t k = 0; k < total * vs / 8; k++) a[k] += b[k];
-            }
-        }
-        first = false;
-    }
-    for (size_t s = 0; s < win.size(); s++) {
-        const Window &w = win[s];
-        if (w.ni == 0 || w.nj == 0) continue;
-        const char *src = sum.data() + off[s] * vs;
-        if (memspace == BSM_MEM_HOST) {
-            for (int64_t b = 0; b < w.nj; b++)
-                std::memcpy((char *)w.out + (size_t)(b * w.ld) * vs, src + (size_t)(b * w.ni) * vs, (size_t)w.ni * vs);
-        } else {
-            const hipError_t e = hipMemcpy2D(w.out, (size_t)w.ld * vs, src, (size_t)w.ni * vs, (size_t)w.ni * vs, (size_t)w.nj,
-                                             hipMemcpyHostToDevice);
-            if (e != hipSuccess) return hip_fail(e, "extract delivery");
-        }
-    }
-    return BSM_OK;
-}
-}  // namespace
-
-extern "C" int bsm_submatrices(bsm_matrix_t A, int op, int64_t nsets, const int64_t *const *I, const int64_t *ni,
-                               const int64_t *const *J, const int64_t *nj, void *const *out, const int64_t *ldo, int memspace,
-                               void *stream) {
-    BSM_GUARDED(
-        if (!A) return fail(BSM_ERR_INVALID, "null handle");
-        if (op != BSM_OP_N && op != BSM_OP_T && op != BSM_OP_C) return fail(BSM_ERR_INVALID, "bad op");
-        if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-        if (memspace == BSM_MEM_DEVICE && !A->on_device)
-            return fail(BSM_ERR_INVALID, "BSM_MEM_DEVICE windows need a device image (handle created with BSM_DEVICE_NONE)");
-        if (nsets < 0 || nsets > INT32_MAX) return fail(BSM_ERR_INVALID, "bad number of sets");
-        if (nsets > 0 && (!I || !ni || !J || !nj || !out || !ldo)) return fail(BSM_ERR_INVALID, "null argument");
-        const Analysis &an = A->an;
-        if (an.nrows > INT32_MAX || an.ncols > INT32_MAX) return fail(BSM_ERR_UNSUPPORTED, "operator too large for int32 maps");
-        // the four maps over the rows and columns of the STORED operator: I indexes the rows of op(A), i.e. the columns
-        // of A for op T / C.  Filling them is the duplicate check: an index is written once.
-        std::vector<int32_t> maps((size_t)(2 * an.nrows + 2 * an.ncols), 0);
-        int32_t *rset = maps.data(), *rpos = rset + an.nrows, *cset = rpos + an.nrows, *cpos = cset + an.ncols;
-        std::fill(rset, rset + an.nrows, -1);
-        std::fill(cset, cset + an.ncols, -1);
-        const bool opT = op != BSM_OP_N;
-        std::vector<Window> win((size_t)nsets);
-        for (int64_t s = 0; s < nsets; s++) {
-            const std::string set = "set " + std::to_string(s + 1) + ": ";
-            if (ni[s] < 0 || nj[s] < 0 || ni[s] > INT32_MAX || nj[s] > INT32_MAX) return fail(BSM_ERR_INVALID, set + "bad size");
-            if ((ni[s] > 0 && !I[s]) || (nj[s] > 0 && !J[s])) return fail(BSM_ERR_INVALID, set + "null index list");
-            if (ldo[s] < std::max<int64_t>(ni[s], 1)) return fail(BSM_ERR_INVALID, set + "ldo < max(ni, 1)");
-            if (ni[s] > 0 && nj[s] > 0 && !out[s]) return fail(BSM_ERR_INVALID, set + "null output window");
-            for (int side = 0; side < 2; side++) {
-                const int64_t *idx = side ? J[s] : I[s];
-                const int64_t cnt = side ? nj[s] : ni[s];
-                const bool stored_rows = (side == 0) != opT;  // this list names rows of the stored operator
-                const int64_t dim = stored_rows ? an.nrows : an.ncols;
-                int32_t *sm = stored_rows ? rset : cset, *pm = stored_rows ? rpos : cpos;
-                for (int64_t k = 0; k < cnt; k++) {
-                    const int64_t v = idx[k];
-                    if (v < 1 || v > dim)
-                        return fail(BSM_ERR_INVALID, set + (side ? "column" : "row") + " index " + std::to_string(v) + " outside 1.." + std::to_string(dim));
-                    if (sm[v - 1] >= 0)
-                        return fail(BSM_ERR_INVALID, set + (side ? "column" : "row") + " index " + std::to_string(v) +
-                                                         " is listed twice (the sets must be disjoint and free of repeats)");
-                    sm[v - 1] = (int32_t)s;
-                    pm[v - 1] = (int32_t)k;
-                }
-            }
-            win[(size_t)s] = Window{ni[s], nj[s], ldo[s], out[s]};
-        }
-        if (nsets == 0) return BSM_OK;
-        return extract_run(A, op, &maps, win, memspace, (hipStream_t)stream);)
-}
-
-extern "C" int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream) {
-    BSM_GUARDED(
-        if (!A) return fail(BSM_ERR_INVALID, "null handle");
-        if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-        if (memspace == BSM_MEM_DEVICE && !A->on_device)
-            return fail(BSM_ERR_INVALID, "a BSM_MEM_DEVICE result needs a device image (handle created with BSM_DEVICE_NONE)");
-        const int64_t n = std::min(A->an.nrows, A->an.ncols);
-        if (n > 0 && !d) return fail(BSM_ERR_INVALID, "d is null");
-        if (n == 0) return BSM_OK;
-        const std::vector<Window> win{Window{n, 1, n, d}};
-        return extract_run(A, BSM_OP_N, nullptr, win, memspace, (hipStream_t)stream);)
-}
-
-// ---- bsm_invert_blocks: batched in-place inverse of dense blocks ---------------------------------------------------------
-namespace {
-// the device leg: the non-empty blocks sorted by descending order (the large ones start first), cut into launches of
-// one regime whose blocks need more than half the LDS of the launch's first -- a 16 x 16 block does not reserve the
-// LDS of the 128 x 128 one that came in the same call
-int invert_device(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld, int64_t *info,
-                  hipStream_t stream) {
-    const int es = dtype == BSM_F32 ? 4 : dtype == BSM_C128 ? 16 : 8;
-    std::vector<InvertBlock> table;
-    for (int64_t b = 0; b < nblocks; b++)
-        if (n[b] > 0) table.push_back(InvertBlock{(uint64_t)(uintptr_t)blocks[b], (long long)ld[b], (int)n[b], (int)table.size()});
-    if (table.empty()) return BSM_OK;
-    std::stable_sort(table.begin(), table.end(), [](const InvertBlock &a, const InvertBlock &b) { return a.n > b.n; });
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && stream && hipStreamGetDevice(stream, &dev) != hipSuccess) {
-        (void)hipGetLastError();
-        e = hipGetDevice(&dev);
-    }
-    if (e != hipSuccess) return hip_fail(e, "hipGetDevice");
-    DeviceGuard g;
-    e = g.enter(dev);
-    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
-    DevBuf db;  // the table, behind it one int32 of info per table entry
-    const size_t tb = (table.size() * sizeof(InvertBlock) + 15) / 16 * 16;
-    e = db.alloc(tb + table.size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(db.p, table.data(), table.size() * sizeof(InvertBlock), hipMemcpyHostToDevice, stream);
-    int *d_info = (int *)((char *)db.p + tb);
-    auto resident = [&](const InvertBlock &t) { return (long long)t.n * t.n * es <= (long long)BSM_INVERT_LDS_BYTES; };
-    for (size_t i = 0; i < table.size() && e == hipSuccess;) {
-        const bool res = resident(table[i]);
-        const int head = invert_lds(table[i].n, es, res).total;
-        size_t j = i + 1;
-        while (j < table.size() && resident(table[j]) == res && 2 * invert_lds(table[j].n, es, res).total > head) j++;
-        e = launch_invert(dtype, (const InvertBlock *)db.p + i, (long long)(j - i), table[i].n, res, d_info, stream);
-        i = j;
-    }
-    std::vector<int> hinfo(table.size(), 0);
-    if (e == hipSuccess) e = hipMemcpyAsync(hinfo.data(), d_info, table.size() * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hip_fail(e, "invert");
-    if (info) {
-        int64_t k = 0;  // table ids count the non-empty blocks in the caller's order
-        for (int64_t b = 0; b < nblocks; b++)
-            if (n[b] > 0) info[b] = hinfo[(size_t)k++];
-    }
-    return BSM_OK;
-}
-}  // namespace
-
-extern "C" int bsm_invert_blocks(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld,
-                                 int64_t *info, int memspace, void *stream) {
-    BSM_GUARDED(
-        if (dtype == BSM_F64_F32 || dtype == BSM_C128_C64)
-            return fail(BSM_ERR_INVALID, "bsm_invert_blocks takes a vector type (BSM_F32 .. BSM_C128), not a mixed storage code");
-        if (dtype < 0 || dtype > 3) return fail(BSM_ERR_INVALID, "bad dtype");
-        if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
-        if (nblocks < 0 || nblocks > INT32_MAX) return fail(BSM_ERR_INVALID, "bad number of blocks");
-        if (nblocks > 0 && (!blocks || !n || !ld)) return fail(BSM_ERR_INVALID, "null argument");
-        for (int64_t b = 0; b < nblocks; b++) {
-            const std::string blk = "block " + std::to_string(b + 1) + ": ";
-            if (n[b] < 0) return fail(BSM_ERR_INVALID, blk + "negative size");
-            if (ld[b] < std::max<int64_t>(n[b], 1)) return fail(BSM_ERR_INVALID, blk + "ld < max(n, 1)");
-            if (n[b] > 0 && !blocks[b]) return fail(BSM_ERR_INVALID, blk + "null block");
-        }
-        for (int64_t b = 0; b < nblocks; b++)
-            if (n[b] > BSM_INVERT_MAX_N)
-                return fail(BSM_ERR_UNSUPPORTED, "block " + std::to_string(b + 1) + ": n = " + std::to_string(n[b]) +
-                                                     " > 1024 (one workgroup eliminates one block)");
-        if (info) std::fill(info, info + nblocks, (int64_t)0);
-        if (memspace == BSM_MEM_DEVICE) return invert_device(dtype, nblocks, blocks, n, ld, info, (hipStream_t)stream);
-        for (int64_t b = 0; b < nblocks; b++) {
-            int rc = 0;
-            switch (dtype) {
-                case BSM_F32: rc = invert_block_host<float, 1>((float *)blocks[b], n[b], ld[b]); break;
-                case BSM_F64: rc = invert_block_host<double, 1>((double *)blocks[b], n[b], ld[b]); break;
-                case BSM_C64: rc = invert_block_host<float, 2>((float *)blocks[b], n[b], ld[b]); break;
-                default: rc = invert_block_host<double, 2>((double *)blocks[b], n[b], ld[b]); break;
-            }
-            if (info) info[b] = rc;
-        }
-        return BSM_OK;)
-}
-
 extern "C" int bsm_host_register(void *ptr, int64_t bytes) {
     if (!ptr || bytes <= 0) return fail(BSM_ERR_INVALID, "bad argument");
     hipError_t e = hipHostRegister(ptr, (size_t)bytes, hipHostRegisterDefault);
@@ -964,9 +501,8 @@ extern "C" int bsm_stream_destroy(void *stream) {
 
 extern "C" int bsm_vec_add_segments(int dtype, void *y, int32_t nseg, const int64_t *offset, const void *const *src,
                                     const int64_t *len, void *stream) {
-    if (dtype == BSM_F64_F32 || dtype == BSM_C128_C64)
-        return fail(BSM_ERR_INVALID, "bsm_vec_add_segments takes a vector type (BSM_F32 .. BSM_C128), not a mixed storage code");
-    if (dtype < 0 || dtype > 3) return fail(BSM_ERR_INVALID, "bad dtype");
+    const std::string why = vec_type_refusal("bsm_vec_add_segments", dtype);
+    if (!why.empty()) return fail(BSM_ERR_INVALID, why);
     if (nseg < 0 || (nseg > 0 && (!y || !offset || !src || !len))) return fail(BSM_ERR_INVALID, "null argument");
     // disjoint segments only: the launch adds without atomics
     for (int32_t a = 0; a < nseg; a++) {
@@ -1090,7 +626,7 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
     }
     if (memspace != BSM_MEM_HOST) return fail(BSM_ERR_INVALID, "bad memspace");
     // host vectors: stage through device buffers (PCIe), synchronous
-    const size_t es = vt == BSM_F32 ? 4 : vt == BSM_C128 ? 16 : 8;
+    const size_t es = (size_t)elem_bytes(vt);
     const long long xlen = (op == 0 ? A->an.ncols : A->an.nrows);
     const long long ylen = (op == 0 ? A->an.nrows : A->an.ncols);
     Staging sg;
@@ -1144,8 +680,7 @@ static int mul_entry(bsm_matrix_s *A, int op, bool cplx, bool multi, int64_t nrh
         return fail(BSM_ERR_INVALID, "leading dimension smaller than the vector length");
     // the vector type: the complex one of the handle's precision, or the handle's own (double / complex double under the
     // mixed storage codes)
-    static const int kVecType[6] = {BSM_F32, BSM_F64, BSM_C64, BSM_C128, BSM_F64, BSM_C128};
-    const int vt = cplx ? (dt == BSM_F32 ? BSM_C64 : BSM_C128) : kVecType[dt];
+    const int vt = cplx ? (dt == BSM_F32 ? BSM_C64 : BSM_C128) : vec_type(dt);
     return mul_k(A, op, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream, vt);
 }
 
@@ -1191,7 +726,7 @@ extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *id
                                  const int64_t *ld, int memspace, void *stream) {
     BSM_GUARDED(
         if (!A) return fail(BSM_ERR_INVALID, "null handle");
-        if (A->an.dtype == BSM_F64_F32 || A->an.dtype == BSM_C128_C64)
+        if (is_mixed(A->an.dtype))
             return fail(BSM_ERR_UNSUPPORTED, "bsm_update_blocks: not available on a mixed-precision handle (BSM_F64_F32 / "
                                              "BSM_C128_C64); create a new handle from the new blocks");
         if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");

@@ -1057,12 +1057,11 @@ static int dist_mul_copies(DistState &D, int op, int K, const void *x, long long
                     for (int k = 0; k < K; k++) {
                         char *yk = yb + ((size_t)k * ldy + o.lo) * es;
                         const char *rk = D.h_res.data() + ((size_t)k * ylen + o.lo) * es;
-                        switch (D.dtype) {
-                            case BSM_F32: host_axpby((float *)yk, (const float *)rk, o.len(), *(const float *)beta); break;
-                            case BSM_F64: host_axpby((double *)yk, (const double *)rk, o.len(), *(const double *)beta); break;
-                            case BSM_C64: host_axpby((std::complex<float> *)yk, (const std::complex<float> *)rk, o.len(), *(const std::complex<float> *)beta); break;
-                            default: host_axpby((std::complex<double> *)yk, (const std::complex<double> *)rk, o.len(), *(const std::complex<double> *)beta); break;
-                        }
+                        with_types(D.dtype, [&](auto r, auto, auto nc) {
+                            using R = decltype(r);
+                            using T = std::conditional_t<decltype(nc)::value == 1, R, std::complex<R>>;
+                            host_axpby((T *)yk, (const T *)rk, o.len(), *(const T *)beta);
+                        });
                     }
                 }
             }
@@ -1253,9 +1252,11 @@ int dist_part_info(bsm_matrix_s *A, int32_t part, bsm_part_info_t *out) {
     return BSM_OK;
 }
 
-void dist_images(bsm_matrix_s *A, std::vector<std::pair<const Analysis *, const DeviceImage *>> &out) {
+std::vector<ImageRef> dist_images(bsm_matrix_s *A) {
+    std::vector<ImageRef> out;
     for (const auto &p : A->dist->parts)
         if (p->has_image) out.emplace_back(&p->an, &p->img);
+    return out;
 }
 
 int64_t dist_device_bytes(const bsm_matrix_s *A) {

@@ -2,6 +2,7 @@
 // of its packed image.  Kept out of the product kernel units (bsm_kernels.hip has their index): the build id (Makefile
 // BUILD_ID) names the kernels and schedule of the PRODUCTS, and reading entries changes neither.
 #include "bsm_device.h"
+#include "bsm_types.h"
 
 namespace bsm {
 
@@ -158,17 +159,11 @@ hipError_t launch_zero_windows(int vt, const void *d_table, const void *d_shape,
     if (nsets <= 0 || largest <= 0) return hipSuccess;
     const long long gy = (largest + 4095) / 4096;  // 16 entries per thread where a window is large
     const dim3 grid((unsigned)(nsets < 65535 ? nsets : 65535), (unsigned)(gy < 1024 ? gy : 1024)), block(256);
-#define BSM_ZERO(T) \
-    hipLaunchKernelGGL((zero_windows_kernel<T>), grid, block, 0, stream, (const ExtractOut *)d_table, (const long long *)d_shape, nsets)
-    switch (vt) {
-        case BSM_F32: BSM_ZERO(float); break;
-        case BSM_F64: BSM_ZERO(double); break;
-        case BSM_C64: BSM_ZERO(c64); break;
-        case BSM_C128: BSM_ZERO(c128); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef BSM_ZERO
-    return hipGetLastError();
+    return with_pair(vt, vt, [&](auto t, auto) {  // (the same-type pair of vt: its T)
+        using T = decltype(t);
+        hipLaunchKernelGGL((zero_windows_kernel<T>), grid, block, 0, stream, (const ExtractOut *)d_table, (const long long *)d_shape, nsets);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_extract(int dtype, const void *d_waves, long long nwaves, const void *d_values, const void *d_rows,
@@ -177,28 +172,21 @@ hipError_t launch_extract(int dtype, const void *d_waves, long long nwaves, cons
     if (nwaves <= 0) return hipSuccess;
     const dim3 grid((unsigned)((nwaves + kWavesPerWg - 1) / kWavesPerWg)), block(64 * kWavesPerWg);
     const ExtractMaps mp = maps ? *maps : ExtractMaps{nullptr, nullptr, nullptr, nullptr};
-#define BSM_EXTRACT(T, S)                                                                                                       \
-    do {                                                                                                                        \
-        if (maps)                                                                                                               \
-            hipLaunchKernelGGL((extract_kernel<T, S, false>), grid, block, 0, stream, (const WaveWork *)d_waves, nwaves,          \
-                               (const uint4 *)d_values, (const int *)d_rows, (const int *)d_cols, mp, (const ExtractOut *)d_table, \
-                               (T *)nullptr, (int)nrows, (int)ncols, (int)opT, (int)conj);                                        \
-        else                                                                                                                    \
-            hipLaunchKernelGGL((extract_kernel<T, S, true>), grid, block, 0, stream, (const WaveWork *)d_waves, nwaves,           \
-                               (const uint4 *)d_values, (const int *)d_rows, (const int *)d_cols, mp, (const ExtractOut *)nullptr, \
-                               (T *)d_diag, (int)nrows, (int)ncols, (int)opT, (int)conj);                                         \
-    } while (0)
-    switch (dtype) {
-        case BSM_F32: BSM_EXTRACT(float, float); break;
-        case BSM_F64: BSM_EXTRACT(double, double); break;
-        case BSM_C64: BSM_EXTRACT(c64, c64); break;
-        case BSM_C128: BSM_EXTRACT(c128, c128); break;
-        case BSM_F64_F32: BSM_EXTRACT(double, float); break;
-        case BSM_C128_C64: BSM_EXTRACT(c128, c64); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef BSM_EXTRACT
-    return hipGetLastError();
+    return with_pair(dtype, vec_type(dtype), [&](auto t, auto st) {
+        using T = decltype(t);
+        using S = decltype(st);
+        // (complex vectors under a real image are no pair of vec_type: no kernel is made for them)
+        if constexpr (std::is_arithmetic<T>::value != std::is_arithmetic<S>::value) return hipErrorInvalidValue;
+        else if (maps)
+            hipLaunchKernelGGL((extract_kernel<T, S, false>), grid, block, 0, stream, (const WaveWork *)d_waves, nwaves,
+                               (const uint4 *)d_values, (const int *)d_rows, (const int *)d_cols, mp, (const ExtractOut *)d_table,
+                               (T *)nullptr, (int)nrows, (int)ncols, (int)opT, (int)conj);
+        else
+            hipLaunchKernelGGL((extract_kernel<T, S, true>), grid, block, 0, stream, (const WaveWork *)d_waves, nwaves,
+                               (const uint4 *)d_values, (const int *)d_rows, (const int *)d_cols, mp, (const ExtractOut *)nullptr,
+                               (T *)d_diag, (int)nrows, (int)ncols, (int)opT, (int)conj);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace bsm

@@ -1,11 +1,12 @@
 // bsm_internal.h -- what bsm_capi.cpp (the C ABI; single-device handles), bsm_dist.cpp (handles spread over the
-// devices of a bsm_ctx_t) and bsm_operator.cpp (the packed operator on one device that both are made of) share.
-// Not part of the C ABI.
+// devices of a bsm_ctx_t), bsm_operator.cpp (the packed operator on one device that both are made of) and the units that
+// hold a feature's own entry points (bsm_entries.cpp, bsm_invert.cpp, bsm_krylov.cpp) share.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -13,6 +14,7 @@
 #include "bsm_analysis.h"
 #include "bsm_kernels.h"
 #include "bsm_refill.h"
+#include "bsm_types.h"
 
 struct bsm_ctx_s {
     std::vector<int> devices;  // HIP ordinals; the same ordinal may appear several times (virtual devices)
@@ -144,6 +146,24 @@ struct DeviceGuard {
     hipError_t enter(int dev);
     ~DeviceGuard();
 };
+// a scratch allocation on the current device, freed with its scope
+struct DevBuf {
+    void *p = nullptr;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+};
+
+// the body of an extern "C" entry point that allocates on the host: nothing is thrown across the ABI
+#define BSM_GUARDED(...)                                         \
+    try {                                                        \
+        __VA_ARGS__                                              \
+    } catch (const std::bad_alloc &) {                           \
+        return fail(BSM_ERR_ALLOC, "out of host memory");        \
+    } catch (const std::exception &e) {                          \
+        return fail(BSM_ERR_INVALID, e.what());                  \
+    }
 
 AnalysisOptions to_aopt(const bsm_options &o, ValueSink *sink);
 // whether `st` is being captured into a graph (a failed query counts as "no")
@@ -169,7 +189,8 @@ int dist_update(bsm_matrix_s *A, int64_t nupd, const int64_t *ids, bool full, co
                 int memspace, hipStream_t stream);
 int64_t dist_device_bytes(const bsm_matrix_s *A);
 // (analysis, image) of every part that holds blocks
-void dist_images(bsm_matrix_s *A, std::vector<std::pair<const Analysis *, const DeviceImage *>> &out);
+using ImageRef = std::pair<const Analysis *, const DeviceImage *>;
+std::vector<ImageRef> dist_images(bsm_matrix_s *A);
 
 // smallest row index of every block (its partition key) and its weight (stored entries)
 void block_row_keys(const std::vector<BlockIn> &in, std::vector<int64_t> &key, std::vector<int64_t> &weight);

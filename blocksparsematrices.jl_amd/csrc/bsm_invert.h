@@ -1,7 +1,7 @@
 // bsm_invert.h -- the host side of bsm_invert_blocks (include/bsm_rocm.h): in-place inverse of one dense column-major
 // block by Gauss-Jordan elimination with partial row pivoting, the elimination invert_kernel (bsm_invert.hip) runs on
 // the device, written down once more in plain C++ so that both choose the same pivots.  Depends on the standard
-// library only: bsm_capi.cpp calls it for BSM_MEM_HOST, and a stand-alone program can include it.
+// library only: bsm_invert.cpp calls it for BSM_MEM_HOST, and a stand-alone program can include it.
 //
 // The elimination, step k = 0 .. n-1:
 //   1. pivot = the entry of column k in rows k .. n-1 with the largest magnitude (|v| for real, |re| + |im| for complex:

@@ -235,31 +235,21 @@ hipError_t launch_invert(int dtype, const void *d_table, long long count, int nm
                          hipStream_t stream) {
     if (count <= 0) return hipSuccess;
     const dim3 grid((unsigned)count), block(256);
-#define BSM_INVERT(T)                                                                                                          \
-    do {                                                                                                                       \
-        const size_t lds = (size_t)invert_lds(nmax, (int)sizeof(T), resident).total;                                           \
-        if (resident) {                                                                                                        \
-            if (lds > 65536) {                                                                                                 \
-                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&invert_kernel<T, true>),              \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                \
-                if (e != hipSuccess) return e;                                                                                 \
-            }                                                                                                                  \
-            hipLaunchKernelGGL((invert_kernel<T, true>), grid, block, lds, stream, (const InvertBlock *)d_table, (int *)d_info, \
-                               nmax);                                                                                          \
-        } else {                                                                                                               \
-            hipLaunchKernelGGL((invert_kernel<T, false>), grid, block, lds, stream, (const InvertBlock *)d_table,               \
-                               (int *)d_info, nmax);                                                                           \
-        }                                                                                                                      \
-    } while (0)
-    switch (dtype) {
-        case BSM_F32: BSM_INVERT(float); break;
-        case BSM_F64: BSM_INVERT(double); break;
-        case BSM_C64: BSM_INVERT(c64); break;
-        case BSM_C128: BSM_INVERT(c128); break;
-        default: return hipErrorInvalidValue;
-    }
-#undef BSM_INVERT
-    return hipGetLastError();
+    return with_pair(dtype, dtype, [&](auto t, auto) {  // (the same-type pair of dtype: its T)
+        using T = decltype(t);
+        const size_t lds = (size_t)invert_lds(nmax, (int)sizeof(T), resident).total;
+        if (resident) {
+            if (lds > 65536) {
+                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&invert_kernel<T, true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) return e;
+            }
+            hipLaunchKernelGGL((invert_kernel<T, true>), grid, block, lds, stream, (const InvertBlock *)d_table, (int *)d_info, nmax);
+        } else {
+            hipLaunchKernelGGL((invert_kernel<T, false>), grid, block, lds, stream, (const InvertBlock *)d_table, (int *)d_info, nmax);
+        }
+        return hipGetLastError();
+    });
 }
 
 }  // namespace bsm

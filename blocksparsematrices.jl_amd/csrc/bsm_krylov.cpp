@@ -19,14 +19,10 @@ using namespace bsm;
 
 namespace {
 
-int es_of(int dtype) { return dtype == BSM_F32 ? 4 : dtype == BSM_C128 ? 16 : 8; }
-int rs_of(int dtype) { return (dtype == BSM_F32 || dtype == BSM_C64) ? 4 : 8; }
-bool vector_code(int dtype) { return dtype >= BSM_F32 && dtype <= BSM_C128; }
-
 // bytes of the partials of one pass: k columns of G elements, then G reals (the norm shares), each part 16-byte aligned
 int64_t orth_work_bytes(int dtype, int64_t n, int64_t k) {
-    const int64_t G = krylov_grid(n, es_of(dtype));
-    return (k * G * es_of(dtype) + 15) / 16 * 16 + (G * rs_of(dtype) + 15) / 16 * 16;
+    const int64_t G = krylov_grid(n, elem_bytes(dtype));
+    return (k * G * elem_bytes(dtype) + 15) / 16 * 16 + (G * real_bytes(dtype) + 15) / 16 * 16;
 }
 
 // one element holding the real value v
@@ -38,21 +34,20 @@ struct Scalar {
         d[0] = v;
         f[0] = (float)v;
     }
-    const void *ptr() const { return rs_of(dtype) == 4 ? (const void *)f : (const void *)d; }
+    const void *ptr() const { return real_bytes(dtype) == 4 ? (const void *)f : (const void *)d; }
 };
 
 }  // namespace
 
 extern "C" int64_t bsm_krylov_orth_work(int dtype, int64_t n, int64_t k) {
-    if (!vector_code(dtype) || n < 0 || k < 0 || k > BSM_GMRES_MAX_RESTART) return (int64_t)fail(BSM_ERR_INVALID, "bad argument");
+    if (!is_vec_type(dtype) || n < 0 || k < 0 || k > BSM_GMRES_MAX_RESTART) return (int64_t)fail(BSM_ERR_INVALID, "bad argument");
     return orth_work_bytes(dtype, n, k);
 }
 
 extern "C" int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, int64_t ldv, void *w, void *hsum, void *nrm,
                                void *work, void *stream) {
-    if (dtype == BSM_F64_F32 || dtype == BSM_C128_C64)
-        return fail(BSM_ERR_INVALID, "bsm_krylov_orth takes a vector type (BSM_F32 .. BSM_C128), not a mixed storage code");
-    if (!vector_code(dtype)) return fail(BSM_ERR_INVALID, "bad dtype");
+    const std::string why = vec_type_refusal("bsm_krylov_orth", dtype);
+    if (!why.empty()) return fail(BSM_ERR_INVALID, why);
     if (n < 0 || k < 0 || k > BSM_GMRES_MAX_RESTART) return fail(BSM_ERR_INVALID, "n < 0, or k outside 0 .. BSM_GMRES_MAX_RESTART");
     if (k > 0 && ldv < std::max<int64_t>(n, 1)) return fail(BSM_ERR_INVALID, "ldv < max(n, 1)");
     if (!nrm || !work || (n > 0 && !w) || (k > 0 && !hsum) || (k > 0 && n > 0 && !V)) return fail(BSM_ERR_INVALID, "null argument");
@@ -67,7 +62,7 @@ extern "C" int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, i
     } else {
         (void)hipGetLastError();
     }
-    const int es = es_of(dtype), G = krylov_grid(n, es);
+    const int es = elem_bytes(dtype), G = krylov_grid(n, es);
     void *nrmpart = (char *)work + (k * G * es + 15) / 16 * 16;
     hipError_t e = launch_krylov_dot(dtype, n, (int)k, V, ldv, w, work, st);
     if (e == hipSuccess) e = krylov_orth_update(dtype, n, (int)k, V, ldv, w, work, hsum, nrmpart, st);
@@ -81,17 +76,15 @@ extern "C" int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, i
 // the rotations and the back substitution the one-wave kernels run.  H is overwritten by the triangular factor; y: k
 // elements; res (may be NULL): k doubles, the residual norm after every column.  Needs no device.
 extern "C" int bsm_debug_krylov_lsq_host(int dtype, int32_t k, void *H, int64_t ldh, double beta, void *y, double *res) {
-    if (!vector_code(dtype)) return fail(BSM_ERR_INVALID, "bad dtype");
+    if (!is_vec_type(dtype)) return fail(BSM_ERR_INVALID, "bad dtype");
     if (k < 1 || k > BSM_GMRES_MAX_RESTART || ldh < (int64_t)k + 1 || !H || !y) return fail(BSM_ERR_INVALID, "bad argument");
     try {
         std::vector<double> r((size_t)k);
         std::vector<double> work((size_t)(3 * k + 1) * 2);
-        switch (dtype) {
-            case BSM_F32: krylov_lsq_host<float, 1>(k, (float *)H, ldh, (float)beta, (float *)y, r.data(), (float *)work.data()); break;
-            case BSM_F64: krylov_lsq_host<double, 1>(k, (double *)H, ldh, beta, (double *)y, r.data(), work.data()); break;
-            case BSM_C64: krylov_lsq_host<float, 2>(k, (float *)H, ldh, (float)beta, (float *)y, r.data(), (float *)work.data()); break;
-            default: krylov_lsq_host<double, 2>(k, (double *)H, ldh, beta, (double *)y, r.data(), work.data()); break;
-        }
+        with_types(dtype, [&](auto t, auto, auto nc) {
+            using R = decltype(t);
+            krylov_lsq_host<R, decltype(nc)::value>(k, (R *)H, ldh, (R)beta, (R *)y, r.data(), (R *)work.data());
+        });
         if (res) std::copy(r.begin(), r.end(), res);
     } catch (const std::bad_alloc &) {
         return fail(BSM_ERR_ALLOC, "out of host memory");
@@ -116,7 +109,7 @@ struct bsm_gmres_s {
     // BSM_MEM_HOST solves: device copies of b and x, allocated at the first one
     void *hb = nullptr, *hx = nullptr;
 
-    char *col(int64_t j) const { return V + j * ldv * es_of(vt); }
+    char *col(int64_t j) const { return V + j * ldv * elem_bytes(vt); }
     void release() {
         if (ws) (void)hipFree(ws);
         if (hb) (void)hipFree(hb);
@@ -134,10 +127,9 @@ namespace {
 
 // how `H` is applied to vectors of type vt: 0 bsm_mul, 1 bsm_mul_cvec, -1 not at all
 int pairing(const bsm_matrix_s *H, int vt) {
-    static const int kVecType[6] = {BSM_F32, BSM_F64, BSM_C64, BSM_C128, BSM_F64, BSM_C128};
     const int dt = H->an.dtype;
     if (dt < 0 || dt > 5) return -1;
-    if (kVecType[dt] == vt) return 0;
+    if (vec_type(dt) == vt) return 0;
     if ((dt == BSM_F32 && vt == BSM_C64) || (dt == BSM_F64 && vt == BSM_C128)) return 1;
     return -1;
 }
@@ -160,7 +152,7 @@ extern "C" int bsm_gmres_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM
     *out = nullptr;
     if (!A) return fail(BSM_ERR_INVALID, "null handle");
     if (opA < 0 || opA > 2 || (M && (opM < 0 || opM > 2))) return fail(BSM_ERR_INVALID, "bad op");
-    if (!vector_code(vdtype)) return fail(BSM_ERR_INVALID, "vdtype must be a vector type (BSM_F32 .. BSM_C128)");
+    if (!is_vec_type(vdtype)) return fail(BSM_ERR_INVALID, "vdtype must be a vector type (BSM_F32 .. BSM_C128)");
     if (restart < 1 || restart > BSM_GMRES_MAX_RESTART) return fail(BSM_ERR_INVALID, "restart outside 1 .. BSM_GMRES_MAX_RESTART");
     if (A->an.nrows != A->an.ncols) return fail(BSM_ERR_INVALID, "op(A) is not square");
     if (M && (M->an.nrows != A->an.nrows || M->an.ncols != A->an.ncols)) return fail(BSM_ERR_INVALID, "M has another order than A");
@@ -175,7 +167,7 @@ extern "C" int bsm_gmres_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM
     S->A = A, S->M = M, S->opA = opA, S->opM = opM, S->vt = vdtype, S->m = restart, S->device = A->img.device;
     S->a_cvec = pa == 1, S->m_cvec = pm == 1;
     S->n = A->an.nrows;
-    const int64_t es = es_of(vdtype), rs = rs_of(vdtype), m = restart, n = S->n;
+    const int64_t es = elem_bytes(vdtype), rs = real_bytes(vdtype), m = restart, n = S->n;
     S->ldv = (std::max<int64_t>(n, 1) * es + 15) / 16 * 16 / es;
     auto pad = [](int64_t b) { return (b + 63) / 64 * 64; };
     const int64_t vec = pad(S->ldv * es);
@@ -224,7 +216,7 @@ namespace {
 // the solve on device vectors b, x (arguments checked)
 int solve_device(bsm_gmres_s *S, const void *b, void *x, const bsm_gmres_params &p, bsm_gmres_info &info, double *history,
                  hipStream_t st) {
-    const int vt = S->vt, m = S->m, es = es_of(vt);
+    const int vt = S->vt, m = S->m, es = elem_bytes(vt);
     const int64_t n = S->n;
     const int G = krylov_grid(n, es);
     const KrylovSmall &sm = S->sm;
@@ -376,7 +368,7 @@ extern "C" int bsm_gmres_solve(bsm_gmres_t S, const void *b, void *x, const bsm_
     if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
     if (!(p->rtol >= 0) || !(p->atol >= 0) || p->maxiter < 0 || p->history_capacity < 0)
         return fail(BSM_ERR_INVALID, "rtol, atol, maxiter and history_capacity must be >= 0");
-    const size_t bytes = (size_t)S->n * es_of(S->vt);
+    const size_t bytes = (size_t)S->n * elem_bytes(S->vt);
     if (S->n > 0 && (!b || !x)) return fail(BSM_ERR_INVALID, "null vector");
     if (S->n > 0 && overlap(b, x, bytes)) return fail(BSM_ERR_INVALID, "x must not alias b");
     const hipStream_t st = (hipStream_t)stream;

@@ -18,6 +18,8 @@
 #include <cmath>
 #include <cstdint>
 
+#include "bsm_types.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define BSM_HD __host__ __device__ inline

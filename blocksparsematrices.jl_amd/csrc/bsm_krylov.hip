@@ -388,66 +388,54 @@ Split split_of(long long n, int es, long long ldv, int k, const void *V, const v
 
 }  // namespace
 
-#define BSM_KRYLOV_TYPES(CALL)                  \
-    switch (dtype) {                            \
-        case BSM_F32: CALL(float, 1); break;    \
-        case BSM_F64: CALL(double, 1); break;   \
-        case BSM_C64: CALL(float, 2); break;    \
-        case BSM_C128: CALL(double, 2); break;  \
-        default: return hipErrorInvalidValue;   \
-    }
-
-static int es_of(int dtype) { return dtype == BSM_F32 ? 4 : dtype == BSM_C128 ? 16 : 8; }
-
 hipError_t launch_krylov_dot(int dtype, long long n, int k, const void *V, long long ldv, const void *w, void *part,
                              hipStream_t stream) {
-    if (dtype < 0 || dtype > 3 || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
+    if (!is_vec_type(dtype) || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
     if (k == 0) return hipSuccess;
-    const int es = es_of(dtype);
+    const int es = elem_bytes(dtype);
     const Split s = split_of(n, es, ldv, k, V, w, nullptr);
     const dim3 grid((unsigned)krylov_grid(n, es)), block(kThreads);
-#define BSM_DOT(R, NC)                                                                                                        \
-    do {                                                                                                                      \
-        constexpr int VE = 16 / (int)(sizeof(R) * NC);                                                                        \
-        if (s.a16)                                                                                                            \
-            hipLaunchKernelGGL((dot_kernel<R, NC, VE, true>), grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w,  \
-                               (R *)part, s.lo, s.ng);                                                                        \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((dot_kernel<R, NC, 1, false>), grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w,  \
-                               (R *)part, s.lo, s.ng);                                                                        \
-    } while (0)
-    BSM_KRYLOV_TYPES(BSM_DOT)
-#undef BSM_DOT
+    with_types(dtype, [&](auto r, auto, auto nc) {
+        using R = decltype(r);
+        constexpr int NC = decltype(nc)::value, VE = 16 / (int)(sizeof(R) * NC);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w, (R *)part, s.lo, s.ng);
+        };
+        if (s.a16)
+            launch(dot_kernel<R, NC, VE, true>);
+        else
+            launch(dot_kernel<R, NC, 1, false>);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_krylov_sweep(int dtype, bool combine, long long n, int k, const void *V, long long ldv, const void *in, void *out,
                                const void *part, const void *coef, void *hsum, const void *scale, void *nrmpart, hipStream_t stream) {
-    if (dtype < 0 || dtype > 3 || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
-    const int es = es_of(dtype);
+    if (!is_vec_type(dtype) || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
+    const int es = elem_bytes(dtype);
     const Split s = split_of(n, es, ldv, k, V, combine ? nullptr : in, out);
     const dim3 grid((unsigned)krylov_grid(n, es)), block(kThreads);
-#define BSM_SWEEP_ARGS(R) n, k, (const R *)V, ldv, (const R *)in, (R *)out, (const R *)part, (const R *)coef, (R *)hsum, (const R *)scale, (R *)nrmpart, s.lo, s.ng
-#define BSM_SWEEP(R, NC)                                                                                                      \
-    do {                                                                                                                      \
-        constexpr int VE = 16 / (int)(sizeof(R) * NC);                                                                        \
-        if (s.a16 && combine)                                                                                                 \
-            hipLaunchKernelGGL((sweep_kernel<R, NC, VE, true, true>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));             \
-        else if (s.a16)                                                                                                       \
-            hipLaunchKernelGGL((sweep_kernel<R, NC, VE, true, false>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));            \
-        else if (combine)                                                                                                     \
-            hipLaunchKernelGGL((sweep_kernel<R, NC, 1, false, true>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));             \
-        else                                                                                                                  \
-            hipLaunchKernelGGL((sweep_kernel<R, NC, 1, false, false>), grid, block, 0, stream, BSM_SWEEP_ARGS(R));            \
-    } while (0)
-    BSM_KRYLOV_TYPES(BSM_SWEEP)
-#undef BSM_SWEEP
-#undef BSM_SWEEP_ARGS
+    with_types(dtype, [&](auto r, auto, auto nc) {
+        using R = decltype(r);
+        constexpr int NC = decltype(nc)::value, VE = 16 / (int)(sizeof(R) * NC);
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)in, (R *)out, (const R *)part,
+                               (const R *)coef, (R *)hsum, (const R *)scale, (R *)nrmpart, s.lo, s.ng);
+        };
+        if (s.a16 && combine)
+            launch(sweep_kernel<R, NC, VE, true, true>);
+        else if (s.a16)
+            launch(sweep_kernel<R, NC, VE, true, false>);
+        else if (combine)
+            launch(sweep_kernel<R, NC, 1, false, true>);
+        else
+            launch(sweep_kernel<R, NC, 1, false, false>);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_krylov_norm(int dtype, int G, const void *nrmpart, void *nrm, hipStream_t stream) {
-    if (dtype == BSM_F32 || dtype == BSM_C64)
+    if (real_bytes(dtype) == 4)
         hipLaunchKernelGGL(norm_kernel<float>, dim3(1), dim3(64), 0, stream, G, (const float *)nrmpart, (float *)nrm);
     else
         hipLaunchKernelGGL(norm_kernel<double>, dim3(1), dim3(64), 0, stream, G, (const double *)nrmpart, (double *)nrm);
@@ -455,30 +443,33 @@ hipError_t launch_krylov_norm(int dtype, int G, const void *nrmpart, void *nrm, 
 }
 
 hipError_t launch_krylov_start(int dtype, int G, int m, const KrylovSmall &s, hipStream_t stream) {
-#define BSM_START(R, NC) \
-    hipLaunchKernelGGL((start_kernel<R, NC>), dim3(1), dim3(64), 0, stream, G, m, (const R *)s.nrmpart, (R *)s.g, (R *)s.hsum, (R *)s.inv, s.res)
-    BSM_KRYLOV_TYPES(BSM_START)
-#undef BSM_START
+    if (!is_vec_type(dtype)) return hipErrorInvalidValue;
+    with_types(dtype, [&](auto r, auto, auto nc) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((start_kernel<R, decltype(nc)::value>), dim3(1), dim3(64), 0, stream, G, m, (const R *)s.nrmpart, (R *)s.g,
+                           (R *)s.hsum, (R *)s.inv, s.res);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_krylov_hess(int dtype, int G, int m, int j, const KrylovSmall &s, hipStream_t stream) {
-    if (j < 0 || j >= m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
-#define BSM_HESS(R, NC)                                                                                                            \
-    hipLaunchKernelGGL((hess_kernel<R, NC>), dim3(1), dim3(64), 0, stream, G, m, j, (const R *)s.nrmpart, (R *)s.hsum, (R *)s.Hm, \
-                       (R *)s.cs, (R *)s.sn, (R *)s.g, (R *)s.inv, s.res)
-    BSM_KRYLOV_TYPES(BSM_HESS)
-#undef BSM_HESS
+    if (!is_vec_type(dtype) || j < 0 || j >= m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
+    with_types(dtype, [&](auto r, auto, auto nc) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((hess_kernel<R, decltype(nc)::value>), dim3(1), dim3(64), 0, stream, G, m, j, (const R *)s.nrmpart,
+                           (R *)s.hsum, (R *)s.Hm, (R *)s.cs, (R *)s.sn, (R *)s.g, (R *)s.inv, s.res);
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_krylov_trsolve(int dtype, int m, int k, const KrylovSmall &s, hipStream_t stream) {
-    if (k < 0 || k > m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
+    if (!is_vec_type(dtype) || k < 0 || k > m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
     if (k == 0) return hipSuccess;
-#define BSM_TRS(R, NC) \
-    hipLaunchKernelGGL((trsolve_kernel<R, NC>), dim3(1), dim3(64), 0, stream, m, k, (const R *)s.Hm, (const R *)s.g, (R *)s.y)
-    BSM_KRYLOV_TYPES(BSM_TRS)
-#undef BSM_TRS
+    with_types(dtype, [&](auto r, auto, auto nc) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((trsolve_kernel<R, decltype(nc)::value>), dim3(1), dim3(64), 0, stream, m, k, (const R *)s.Hm, (const R *)s.g,
+                           (R *)s.y);
+    });
     return hipGetLastError();
 }
 

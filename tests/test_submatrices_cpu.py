@@ -2,7 +2,8 @@
 answer from their host image by a plain loop over the wave records the kernel walks, so the decode -- rows from rbase or
 the rows pool, columns from the inline segments or the cols pool, the transposed role of symmetric off-diagonal columns
 -- is checked here without a GPU, on the layout-edge operators of tests/_fuzz.py, against dense arrays built from
-_fuzz.coo_triples.  The acceptance rule is derived in tests/_submat.py."""
+_fuzz.coo_triples (the whole operator and diag(A) also from _common.coo_of).  The acceptance rule is derived in
+tests/_submat.py."""
 import ctypes as C
 import os
 import re
@@ -10,8 +11,8 @@ import re
 import numpy as np
 import pytest
 
-from _common import NODEV, Cc, N, T, wrap
-from _fuzz import GEN, seed_of
+from _common import NODEV, WORK_PANEL, Cc, N, T, coo_of, get_image, wrap
+from _fuzz import GEN, rounded, seed_of
 from _submat import Truth, accept, check_sets, disjoint_rounds, partition_sets, raw_submatrices
 from _values import NOPS, assert_coverage, value_operators
 
@@ -60,6 +61,50 @@ def test_full_shuffled_and_partitioned_selections(bsm, kind, dtype, storage):
             nsets += len(I) + 2
             entries += sum(o.size for o in outs)
     print(f"SUBSTAT selections {kind} {TYPE_IDS[TYPES.index((dtype, storage))]} operators {NOPER} sets {nsets} entries {entries}")
+
+
+def column_forms(A):
+    """how the wave records of an analysis-only handle name their columns: "pool" (the cols pool; "pool_flag": with a
+    column whose sign bit takes it out of the piece's kind) and "inline1" .. "inline3" (that many inline segments;
+    "inline_mixed": of different kinds)"""
+    _, _, cols, waves = get_image(A)
+    out = set()
+    for W in waves:
+        if W["work"] != WORK_PANEL or W["npieces"] == 0:
+            continue
+        P, n = W["first"], W["first"]["ncols"]
+        if P["xbase"] < 0:
+            out.add("pool")
+            if np.any(cols[P["col_off"]:P["col_off"] + n] < 0):
+                out.add("pool_flag")
+        else:
+            nseg = 1 + int(W["seg1_w"] < n) + int(W["seg2_w"] < n)
+            out.add(f"inline{nseg}")
+            if len({(P["kind"] >> (2 * s)) & 3 for s in range(nseg)}) > 1:
+                out.add("inline_mixed")
+    return out
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("dtype,storage", TYPES, ids=TYPE_IDS)
+def test_whole_operator_and_diag_against_the_dense_sum_of_coo_of(bsm, kind, dtype, storage):
+    """A[all rows, all columns] and diag(A) of every layout-edge operator against the dense sum of _common.coo_of, the
+    reference's own oracle path: the host walker over the columns of a wave record on every branch it has"""
+    forms = set()
+    for case, p in enumerate(value_operators(kind, dtype)):
+        A = build(bsm, p, storage)
+        forms |= column_forms(A)
+        r, c, v = coo_of(rounded(p, storage) if storage is not None else p)
+        D, Ab, Cn = np.zeros(p["size"], dtype=dtype), np.zeros(p["size"]), np.zeros(p["size"], dtype=np.int64)
+        np.add.at(D, (r - 1, c - 1), v)
+        np.add.at(Ab, (r - 1, c - 1), np.abs(v))
+        np.add.at(Cn, (r - 1, c - 1), 1)
+        m, n = p["size"]
+        accept(bsm.submatrix(A, one_based(m), one_based(n)), D, Ab, Cn, (kind, case, "whole operator"))
+        k = np.arange(min(m, n))
+        accept(bsm.diag(A), D[k, k], Ab[k, k], Cn[k, k], (kind, case, "diag"))
+    want = {"pool", "inline1", "inline2", "inline3"} | ({"pool_flag", "inline_mixed"} if kind == "symmetric" else set())
+    assert forms == want, (kind, sorted(forms))
 
 
 @pytest.mark.parametrize("dtype,storage", TYPES, ids=TYPE_IDS)
