@@ -21,6 +21,8 @@ BSM_COLOR_WORKSTREAM_DSATUR, BSM_COLOR_DSATUR = 0, 1
 # bsm_invert_blocks: largest n * n * sizeof(T) eliminated in LDS, largest order it takes (include/bsm_rocm.h)
 BSM_INVERT_LDS_BYTES, BSM_INVERT_MAX_N = 131072, 1024
 BSM_GMRES_MAX_RESTART = 128  # bsm_gmres_create's restart, bsm_krylov_orth's k (include/bsm_rocm.h)
+BSM_CG_MAX_RHS = 16  # bsm_cg_create's nrhs_max (include/bsm_rocm.h)
+BSM_CG_METHOD_CG, BSM_CG_METHOD_COCG = 0, 1
 (BSM_BK_VBCRS_PERM, BSM_BK_VBCRS_ROWPTR, BSM_BK_VBCRS_COLINDICES, BSM_BK_VBCRS_ROWINDICES,
  BSM_BK_COLORS, BSM_BK_TRANSPOSECOLORS, BSM_BK_DIAGONALCOLORS) = range(7)
 
@@ -56,6 +58,22 @@ class BsmGmresInfo(C.Structure):
                 ("workspace_bytes", C.c_int64), ("workspace", C.c_uint64)]
 
 
+class BsmCgParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("use_x0", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("maxiter", C.c_int64), ("history_capacity", C.c_int64)]
+
+
+class BsmCgInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("columns_converged", C.c_int32), ("iterations", C.c_int64),
+                ("a_products", C.c_int64), ("m_products", C.c_int64), ("workspace_bytes", C.c_int64),
+                ("workspace", C.c_uint64)]
+
+
+class BsmCgColumn(C.Structure):
+    _fields_ = [("status", C.c_int32), ("reserved", C.c_int32), ("iterations", C.c_int64), ("residual", C.c_double),
+                ("bnorm", C.c_double)]
+
+
 class BsmError(RuntimeError):
     pass
 
@@ -75,7 +93,7 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks", "bsm_value_passes",
            "bsm_submatrices", "bsm_diag", "bsm_invert_blocks",
            "bsm_krylov_orth_work", "bsm_krylov_orth", "bsm_gmres_create", "bsm_gmres_solve",
-           "bsm_gmres_destroy"]
+           "bsm_gmres_destroy", "bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -187,6 +205,13 @@ def lib():
                                       C.POINTER(BsmGmresInfo), C.POINTER(C.c_double), C.c_int, C.c_void_p]
         L.bsm_gmres_destroy.argtypes = [C.c_void_p]
         for name in ("bsm_krylov_orth", "bsm_gmres_create", "bsm_gmres_solve", "bsm_gmres_destroy"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "bsm_cg_create") or "BSM_LIB" not in os.environ:
+        L.bsm_cg_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bsm_cg_solve.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(BsmCgParams),
+                                   C.POINTER(BsmCgInfo), C.POINTER(BsmCgColumn), C.POINTER(C.c_double), C.c_int, C.c_void_p]
+        L.bsm_cg_destroy.argtypes = [C.c_void_p]
+        for name in ("bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy"):
             getattr(L, name).restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p

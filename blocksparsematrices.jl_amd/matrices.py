@@ -39,7 +39,7 @@ __all__ = [
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
     "update_blocks", "refresh", "submatrices", "submatrix", "diag", "invert_blocks", "BlockJacobi", "block_jacobi",
-    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work",
+    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg", "CgInfo", "cg", "cocg",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -1418,6 +1418,145 @@ class Gmres:
 def gmres(A, b, M=None, restart=30, **kw):
     """One-shot form: Gmres(A, M, restart, dtype of b).solve(b, **kw) -> (x, info)."""
     return Gmres(A, M, restart=restart, dtype=_elt(b)).solve(b, **kw)
+
+
+# ---- CG / COCG on several right-hand sides in lockstep, on the device (bsm_cg_*) -------------------------------------------
+_CG_METHODS = {"cg": L.BSM_CG_METHOD_CG, "cocg": L.BSM_CG_METHOD_COCG}
+
+
+class CgInfo:
+    """What a solve reports (bsm_cg_info and the bsm_cg_column entries): status (the largest column status), iterations
+    (the largest column count), columns_converged, a_products, m_products, workspace_bytes, workspace (device address);
+    per column, as numpy arrays of k entries: column_status (0 converged, 1 maxiter reached, 2 a non-finite residual,
+    3 breakdown), column_iterations, residual (absolute, by the recurrence), bnorm; history: (iterations, k), the
+    residual norm of every column after every lockstep iteration (a finished column repeats its last value)."""
+
+    def __init__(self, info, cols, history):
+        for name, _ in L.BsmCgInfo._fields_:
+            setattr(self, name, getattr(info, name))
+        self.column_status = np.array([c.status for c in cols], dtype=np.int64)
+        self.column_iterations = np.array([c.iterations for c in cols], dtype=np.int64)
+        self.residual = np.array([c.residual for c in cols], dtype=np.float64)
+        self.bnorm = np.array([c.bnorm for c in cols], dtype=np.float64)
+        self.history = history
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"CgInfo(status={self.status}, iterations={self.iterations}, columns_converged={self.columns_converged} of "
+                f"{len(self.column_status)}, column_iterations={self.column_iterations.tolist()})")
+
+
+class Cg:
+    """Preconditioned conjugate gradients for A X = B with up to `nrhs` right-hand sides advancing in lockstep on ONE
+    multi-column product per iteration, every step on the device (bsm_cg_*).  method="cg": real symmetric / Hermitian
+    positive definite A (and M); method="cocg": complex symmetric ones (the unconjugated form).  The CALLER asserts the
+    symmetry.  A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g.
+    block_jacobi(A, sets)), or None.  dtype: the type of B and X -- default A's vector type; a real A (and M) of the same
+    precision takes complex vectors.  The workspace (4 n x nrhs matrices, 5 with M) is allocated here, once; A and M are
+    kept alive."""
+
+    def __init__(self, A, M=None, nrhs=1, dtype=None, method="cg"):
+        base, op = _unwrap(A)
+        if not isinstance(base, AbstractBlockMatrix):
+            raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
+        mbase, mop = (None, L.BSM_OP_N) if M is None else _unwrap(M)
+        if M is not None and not isinstance(mbase, AbstractBlockMatrix):
+            raise TypeError("M must be a block matrix or its transpose/adjoint wrapper")
+        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
+        if self.dtype not in _DT:
+            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        if method not in _CG_METHODS:
+            raise ValueError(f"method={method!r}: 'cg' or 'cocg'")
+        self.A, self.M, self.nrhs, self.method = A, M, int(nrhs), method
+        self.n = size(A)[0]
+        self._base, self._mbase = base, mbase
+        ptr = C.c_void_p()
+        L.check(L.lib().bsm_cg_create(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype],
+                                      self.nrhs, _CG_METHODS[method], C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                L.lib().bsm_cg_destroy(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def _operand(self, v, name, vector):
+        """-> (pointer, ld, columns, memspace, keepalive)"""
+        if vector:
+            ptr, ms, _, keep = _vec_info(v, self.dtype, self.n, name, self._base)
+            return ptr, max(self.n, 1), 1, ms, keep
+        ptr, ld, k, ms, _, keep = _mat_info(v, self.dtype, self.n, name, self._base)
+        return ptr, ld, k, ms, keep
+
+    history_capacity = 4096  # rows of CgInfo.history a solve keeps at the most (an attribute: set it on the solver to change it)
+
+    def solve(self, B, X=None, X0=None, rtol=1e-8, atol=0.0, maxiter=None, stream=None, history=True):
+        """-> (X, CgInfo).  B: a vector (n,) or a column-major matrix (n, k), k <= nrhs -- torch CUDA tensor (enqueued on
+        `stream`, default torch's current stream) or numpy array (staged), taken as mul takes them; X: where the solution
+        goes (default: new, like B); X0: the initial guess (copied into X; None: zero).  Column c is converged when its
+        residual norm is <= max(rtol * ||b_c||, atol); maxiter (default: the order of A) bounds the lockstep iterations.
+        A vector in gives a vector out.  info.history holds the first min(iterations, history_capacity = 4096) rows;
+        history=False keeps none.  Synchronous."""
+        is_t = torch is not None and isinstance(B, torch.Tensor)
+        dev = is_t and B.is_cuda
+        vector = getattr(B, "ndim", 1) == 1
+        if X is None:
+            if vector:
+                X = torch.empty_like(B) if is_t else np.empty_like(B)
+            elif is_t:
+                X = torch.empty((B.shape[1], B.shape[0]), dtype=B.dtype, device=B.device).t()
+            else:
+                X = np.empty(B.shape, dtype=B.dtype, order="F")
+        bp, ldb, k, bms, bkeep = self._operand(B, "B", vector)
+        xp, ldx, kx, xms, xkeep = self._operand(X, "X", vector)
+        if kx != k:
+            raise ValueError("DimensionMismatch: B and X have different numbers of columns")
+        if bms != xms:
+            raise ValueError("B and X must live in the same memory space")
+        if not 1 <= k <= self.nrhs:
+            raise ValueError(f"B has {k} columns; this solver takes 1 .. {self.nrhs}")
+        if X0 is not None:
+            if _elt(X0) != self.dtype or tuple(X0.shape) != tuple(X.shape):
+                raise TypeError(f"X0 must have the shape {tuple(X.shape)} and the type {self.dtype}")
+            if X0 is not X:
+                if torch is not None and isinstance(X, torch.Tensor):
+                    X.copy_(X0 if isinstance(X0, torch.Tensor) else torch.from_numpy(X0))
+                else:
+                    X[...] = X0.cpu().numpy() if torch is not None and isinstance(X0, torch.Tensor) else X0
+        maxiter = max(self.n, 1) if maxiter is None else int(maxiter)
+        cap = min(maxiter, self.history_capacity) if history else 0
+        hist = np.empty((max(cap, 1), k), dtype=np.float64)
+        p = L.BsmCgParams(C.sizeof(L.BsmCgParams), 0 if X0 is None else 1, float(rtol), float(atol), maxiter, cap)
+        info = L.BsmCgInfo()
+        cols = (L.BsmCgColumn * k)()
+        st = _stream_ptr(stream, B.device) if dev else None
+        if dev and stream is not None and X0 is not None and X0 is not X:
+            torch.cuda.current_stream(B.device).synchronize()  # the copy of X0 went on torch's current stream
+        L.check(L.lib().bsm_cg_solve(self._ptr, k, bp, ldb, xp, ldx, C.byref(p), C.byref(info), cols,
+                                     hist.ctypes.data_as(C.POINTER(C.c_double)), bms, st))
+        del bkeep, xkeep
+        return X, CgInfo(info, cols, hist[:min(info.iterations, cap)].copy())
+
+
+def _cg_oneshot(A, B, M, method, kw):
+    k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
+    return Cg(A, M, nrhs=k, dtype=_elt(B), method=method).solve(B, **kw)
+
+
+def cg(A, B, M=None, **kw):
+    """One-shot form: Cg(A, M, columns of B, dtype of B, "cg").solve(B, **kw) -> (X, info)."""
+    return _cg_oneshot(A, B, M, "cg", kw)
+
+
+def cocg(A, B, M=None, **kw):
+    """One-shot form of the unconjugated method for complex symmetric A: Cg(..., method="cocg").solve(B, **kw)."""
+    return _cg_oneshot(A, B, M, "cocg", kw)
 
 
 # ---- conversion used by the reference's tests as their oracle (host utility, not the hot path) ----

@@ -624,6 +624,101 @@ int bsm_gmres_solve(struct bsm_gmres_s *S, const void *b, void *x, const bsm_gmr
                     double *history, int memspace, void *stream);
 int bsm_gmres_destroy(struct bsm_gmres_s *S);
 
+/* bsm_cg_*: preconditioned conjugate gradients for SYMMETRIC operators, nrhs = 1 .. BSM_CG_MAX_RHS right-hand sides in
+ * lockstep, wholly on the device.  The short recurrence GMRES cannot use: 4 work vectors per right-hand side (5 with M)
+ * instead of restart + 4, and 3 vector launches per iteration (4 with M) beside the products; the K systems advance on
+ * ONE multi-column product op(A) P per iteration (bsm_mul_multi: the matrix is streamed once per batch of columns).
+ * (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+ *   Method, per column c:
+ *     r = b - op(A) x0 (or b);  z = opM(M) r (or r);  p = z;  rz = <r, z>
+ *     repeat:  q = op(A) p;  pq = <p, q>;  alpha = rz / pq;  x += alpha p;  r -= alpha q;  rn = ||r||_2
+ *              z = opM(M) r (or r);  rz' = <r, z>;  beta = rz' / rz;  p = z + beta p;  rz = rz'
+ *   method = BSM_CG_METHOD_CG:   <u, v> = sum conj(u_i) v_i -- real symmetric / Hermitian positive definite op(A), opM(M);
+ *   method = BSM_CG_METHOD_COCG: <u, v> = sum u_i v_i       -- complex symmetric ones (S' = conj(S): the operators of a
+ *     SymmetricBlockMatrix with complex blocks).  The two coincide for real types.  ||r|| is always the 2-norm.
+ *   THE CALLER asserts that op(A) and opM(M) are symmetric / Hermitian: nothing checks it, and the solver takes any kind
+ *   of handle and any op.  Column c is converged when rn_c <= tol_c = max(rtol * ||b_c||_2, atol).
+ * create: one device allocation on A's device, reported in info: X, R, P, Q (and Z with M) as n x nrhs_max column-major
+ *   with the leading dimension rounded up to whole 16-byte groups, the per-workgroup partial sums, the column states; a
+ *   ring of pinned record slots and events.  vdtype (BSM_F32 .. BSM_C128) is the type of B and X; the (handle, vector)
+ *   pairings are those of bsm_gmres_create: a handle of that vector type (a mixed-storage handle counts with its double
+ *   vectors) goes through bsm_mul_multi, a real unmixed handle of the same precision under a complex vdtype through
+ *   bsm_mul_multi_cvec (one column is bsm_mul / bsm_mul_cvec: the same entry).  The handles must outlive the solver.
+ *   Refusals: null A or out, bad op / vdtype / method, another pairing, op(A) not square, M of another order or on another
+ *   device, nrhs_max outside 1 .. BSM_CG_MAX_RHS: BSM_ERR_INVALID; a multi-device handle: BSM_ERR_UNSUPPORTED; an
+ *   analysis-only handle: BSM_ERR_DEVICE.
+ * solve: B (n x nrhs, leading dimension ldb) and X (ldx), column-major, ldb / ldx >= max(n, 1), any element alignment.
+ *   They are touched only by the start (B is read, X too with use_x0 != 0) and by the final copy-out, which writes the n
+ *   rows of the nrhs columns of X and nothing else.  use_x0 == 0: the solve starts from zero (NaN in the incoming X does
+ *   not survive).
+ *   Kernels (csrc/bsm_cg.hip), launched as (row ranges, columns): cg_start (r, the shares of ||b||^2 and ||r||^2),
+ *   cg_dot (<p, q>, <r, z>: one partial per workgroup and column), cg_update (x, r, the shares of ||r||^2 and, without M,
+ *   of <r, r>), cg_dir (p; its workgroup 0 writes the column's state and record).  Per iteration: product, cg_dot,
+ *   cg_update, cg_dir without M; product A, cg_dot, cg_update, product M, cg_dot, cg_dir with M.  Every workgroup of a
+ *   column adds that column's partials itself in one fixed order: no scalar kernel, no floating-point atomic, nobody
+ *   waits; a launch never reads a scalar that the same launch replaces (two slots alternating by iteration parity).
+ *   The decisions are taken ON THE DEVICE: a column whose rn met its tolerance (status 0), whose rn is not finite
+ *   (status 2: NaN / Inf in B, X0 or the operator) or that broke down -- pq == 0 or rz == 0 while rn > tol, status 3; no
+ *   division by zero is executed -- is FROZEN from the next launch on: its workgroups return at once, x and r do not
+ *   change again whatever the host enqueues.  The host enqueues iteration j + 1 before it waits for the record of
+ *   iteration j (per column rn, ||b||, status and iteration count, in a pinned slot behind an event) and stops when no
+ *   column is running or maxiter is reached: X, every column's iterations and history do not depend on how late it
+ *   notices.  Columns still running after maxiter lockstep iterations report status 1.
+ *   What lockstep costs: the multi-column products run on all nrhs columns until the LAST column stops -- the vector
+ *   kernels skip a frozen column, the products do not --, so an iteration does not get cheaper as columns finish; and a
+ *   solve that ends before maxiter has paid one product of A (and of M) more than it reports, for the iteration that was
+ *   enqueued ahead of the last record.
+ *   history (may be NULL): history[it * nrhs + c] = rn_c after iteration it + 1, it < history_capacity; a frozen column
+ *   repeats its last value.  cols (may be NULL): nrhs entries.
+ *   info: status = the largest column status; iterations = the largest column count; a_products = iterations (+ 1 with
+ *   use_x0) and m_products = iterations + 1 with M, 0 without: the multi-column products the answer uses (the iteration
+ *   enqueued ahead of the last record costs one more product on frozen columns, which is not counted).
+ *   memspace: BSM_MEM_DEVICE -- B, X on A's device; BSM_MEM_HOST -- staged through device buffers the solver keeps from
+ *   its first host solve on.  SYNCHRONOUS; runs wholly on `stream`; must not be graph-captured; one solve at a time per
+ *   solver.  n == 0: status 0, nothing touched.
+ *   BSM_ERR_INVALID: null S / p / info, null B / X with n > 0, nrhs outside 1 .. nrhs_max, ldb or ldx < max(n, 1), X
+ *   overlapping B, negative or NaN rtol / atol, negative maxiter / history_capacity, bad memspace, graph capture, a
+ *   struct_size mismatch.  The call returns BSM_OK for every column status. */
+#define BSM_CG_MAX_RHS 16
+enum { BSM_CG_METHOD_CG = 0, BSM_CG_METHOD_COCG = 1 };
+struct bsm_cg_s;
+typedef struct {
+    int32_t struct_size; /* = sizeof(bsm_cg_params) */
+    int32_t use_x0;
+    double rtol, atol;
+    int64_t maxiter;
+    int64_t history_capacity; /* rows of `history` */
+} bsm_cg_params;
+typedef struct {
+    int32_t status;            /* the largest column status */
+    int32_t columns_converged; /* columns with status 0 */
+    int64_t iterations;        /* lockstep iterations the answer uses: the largest column count */
+    int64_t a_products, m_products;
+    int64_t workspace_bytes;
+    uint64_t workspace;
+} bsm_cg_info;
+typedef struct {
+    int32_t status; /* 0 converged, 1 maxiter reached, 2 non-finite residual, 3 breakdown */
+    int32_t reserved;
+    int64_t iterations;
+    double residual; /* absolute: ||r||_2 by the recurrence when the column stopped */
+    double bnorm;
+} bsm_cg_column;
+BSM_LAYOUT_ASSERT(sizeof(bsm_cg_params) == 40 && offsetof(bsm_cg_params, rtol) == 8 && offsetof(bsm_cg_params, maxiter) == 24,
+                  "bsm_cg_params layout");
+BSM_LAYOUT_ASSERT(sizeof(bsm_cg_info) == 48 && offsetof(bsm_cg_info, iterations) == 8 && offsetof(bsm_cg_info, a_products) == 16 &&
+                      offsetof(bsm_cg_info, workspace) == 40,
+                  "bsm_cg_info layout");
+BSM_LAYOUT_ASSERT(sizeof(bsm_cg_column) == 32 && offsetof(bsm_cg_column, iterations) == 8 && offsetof(bsm_cg_column, residual) == 16,
+                  "bsm_cg_column layout");
+/* (the handle is spelled `struct bsm_cg_s *` for the static checker of the bindings, as in bsm_gmres_solve) */
+int bsm_cg_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, int32_t method,
+                  struct bsm_cg_s **out);
+int bsm_cg_solve(struct bsm_cg_s *S, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_cg_params *p,
+                 bsm_cg_info *info, bsm_cg_column *cols /* nrhs, may be NULL */,
+                 double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
+int bsm_cg_destroy(struct bsm_cg_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

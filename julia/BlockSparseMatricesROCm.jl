@@ -626,4 +626,53 @@ function gmres!(x::Vector{T}, A::ROCmAnyOp, b::Vector{T}; M=nothing, restart::In
     return x, info, history[1:min(info.iterations, maxiter)]
 end
 
+# ---- CG / COCG on several right-hand sides in lockstep, on the device (bsm_cg_*) -----------------------------------------
+mutable struct BsmCgParams          # mirrors bsm_cg_params (40 bytes)
+    struct_size::Int32; use_x0::Int32; rtol::Float64; atol::Float64; maxiter::Int64; history_capacity::Int64
+end
+mutable struct BsmCgInfo            # mirrors bsm_cg_info (48 bytes)
+    status::Int32; columns_converged::Int32; iterations::Int64
+    a_products::Int64; m_products::Int64; workspace_bytes::Int64; workspace::UInt64
+end
+struct BsmCgColumn                  # mirrors bsm_cg_column (32 bytes)
+    status::Int32; reserved::Int32; iterations::Int64; residual::Float64; bnorm::Float64
+end
+
+"""
+    cg!(X, A, B; M=nothing, method=:cg, rtol=1e-8, atol=0.0, maxiter=size(A, 1), x0=false) -> (X, info, columns, history)
+
+Preconditioned conjugate gradients for `A X = B` with 1 to 16 right-hand sides advancing in lockstep on one multi-column
+product per iteration, every step of it on the device (bsm_cg_create / _solve / _destroy).  `method = :cg` is for real
+symmetric / Hermitian positive definite `A` (and `M`), `method = :cocg` (the unconjugated form) for complex symmetric
+ones, e.g. a `SymmetricBlockMatrix` with complex blocks; the caller asserts the symmetry.  `B` and `X` are host vectors
+or matrices of `A`'s element type, or complex ones of its precision under real `A` and `M`.  Column `c` is converged when
+its residual norm is `<= max(rtol * norm(B[:, c]), atol)`.  `columns[c].status`: 0 converged, 1 `maxiter` reached, 2 a
+non-finite residual, 3 breakdown; `history[c, i]` is the residual norm of column `c` after iteration `i`.  (The reference
+offers nothing here: a `LinearMap` is handed to a Julia solver package, whose Krylov loop runs on the host.)
+"""
+function cg!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; M=nothing, method::Symbol=:cg, rtol::Real=1e-8, atol::Real=0.0,
+             maxiter::Integer=size(A, 1), x0::Bool=false) where {T<:ROCmEltype}
+    n, k = size(B, 1), size(B, 2)
+    size(A, 1) == size(A, 2) == n && size(X) == size(B) || throw(DimensionMismatch("cg! needs a square operator and B, X of its order"))
+    1 <= k <= 16 || throw(ArgumentError("cg! takes 1 to 16 right-hand sides"))
+    method in (:cg, :cocg) || throw(ArgumentError("method must be :cg or :cocg"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = M === nothing ? C_NULL : handle(_base(M)).ptr
+    _check(ccall((:bsm_cg_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), mptr, M === nothing ? 0 : _op(M), _DTYPE[T], k, method === :cg ? 0 : 1, out))
+    p = BsmCgParams(sizeof(BsmCgParams), x0, rtol, atol, maxiter, maxiter)
+    info = BsmCgInfo(0, 0, 0, 0, 0, 0, 0)
+    columns = Vector{BsmCgColumn}(undef, k)
+    history = zeros(Float64, k, max(maxiter, 1))
+    ld = max(n, 1)
+    try
+        GC.@preserve A M X B columns history _check(ccall((:bsm_cg_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{BsmCgParams}, Ref{BsmCgInfo}, Ptr{BsmCgColumn}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+            out[], k, pointer(B), ld, pointer(X), ld, p, info, columns, history, 0, C_NULL))
+    finally
+        ccall((:bsm_cg_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return X, info, columns, history[:, 1:min(info.iterations, maxiter)]
+end
+
 end # module
