@@ -5,7 +5,7 @@
 //
 // Every kernel is a pure stream over n x K elements with a reduction, in the conventions of bsm_krylov.hip: 256-thread
 // workgroups, the krylov_grid(n, es) row ranges walked in tiles of 256 threads x kU 16-byte groups, xor-shuffles for the
-// wave sum, one LDS slot per wave, one partial per workgroup.  The launch is (krylov_grid, K): a workgroup owns one row
+// wave sum, one LDS slot per wave, one partial per workgroup (the helpers: bsm_cg_device.h, shared with bsm_bicgstab.hip).  The launch is (krylov_grid, K): a workgroup owns one row
 // range of ONE column, so K columns fill the compute units where one column of n = 100 000 gives 98 workgroups.
 //   start_kernel   r = B - q (B element by element under a guard: any ldb, any alignment; q = A x0 or none), the shares of
 //                  ||b||^2, ||r||^2 and, without M, of <r, r> in the method's form.
@@ -23,51 +23,10 @@
 #include "bsm_cg.h"
 
 #include "../../include/bsm_rocm.h"
+#include "bsm_cg_device.h"
 
 namespace bsm {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kU = 2;  // 16-byte groups per thread, array and tile
-
-template <typename R> struct alignas(16) Vec16 {
-    R r[16 / sizeof(R)];
-};
-template <typename R> __device__ __forceinline__ Vec16<R> load16(const R *p) { return *reinterpret_cast<const Vec16<R> *>(p); }
-template <typename R> __device__ __forceinline__ void store16(R *p, const Vec16<R> &v) { *reinterpret_cast<Vec16<R> *>(p) = v; }
-
-template <typename R> __device__ __forceinline__ R wave_sum(R v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-// sum of p[0], p[stride], .. (G terms) by one wave in a fixed order: every wave of every workgroup gets the same bits
-template <typename R> __device__ __forceinline__ R wave_total(const R *__restrict__ p, int G, int stride, int lane) {
-    R a = R(0);
-    for (int g = lane; g < G; g += 64) a += p[(long long)g * stride];
-    return wave_sum(a);
-}
-// v[q] = the workgroup's sum of v[q], in every thread
-template <typename R, int NV> __device__ __forceinline__ void block_sum(R (&v)[NV], R (*red)[NV]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = wave_sum(v[q]);
-    if (lane == 0) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) red[wave][q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NV; ++q) v[q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
-}
-__device__ __forceinline__ void wg_range(long long ng, int G, int wg, long long &g0, long long &g1) {
-    const long long per = (ng + G - 1) / G;
-    g0 = per * wg;
-    g0 = g0 < ng ? g0 : ng;
-    g1 = g0 + per < ng ? g0 + per : ng;
-}
-// whether an element (NC reals) is zero
-template <typename R, int NC> __device__ __forceinline__ bool is_zero(const R *a) { return a[0] == R(0) && a[NC - 1] == R(0); }
 
 template <typename R, int NC, bool RR>
 __global__ void __launch_bounds__(kThreads)
@@ -380,23 +339,11 @@ __global__ void __launch_bounds__(kThreads)
     }
 }
 
-template <typename F> hipError_t dispatch(const CgDims &d, F &&f) {
-    if (!is_vec_type(d.dtype) || d.n < 0 || d.nrhs < 1 || d.nrhs > kCgMaxRhs || d.G < 1 || d.G > kKrylovMaxGrid)
-        return hipErrorInvalidValue;
-    with_types(d.dtype, [&](auto r, auto, auto nc) {
-        using R = decltype(r);
-        constexpr int NC = decltype(nc)::value;
-        const long long ng = d.ld / (16 / (long long)(sizeof(R) * NC));
-        f(r, nc, ng, dim3((unsigned)d.G, (unsigned)d.nrhs), (R)(d.conj ? 1 : -1));
-    });
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_cg_start(const CgDims &d, const void *B, long long ldb, const void *q, void *r, void *pbb, void *pnn, void *prz,
                            CgState *st, hipStream_t stream) {
-    return dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto sgn) {
+    return cg_dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto sgn) {
         using R = decltype(rt);
         constexpr int NC = decltype(nc)::value;
         auto launch = [&](auto kernel) {
@@ -411,7 +358,7 @@ hipError_t launch_cg_start(const CgDims &d, const void *B, long long ldb, const 
 }
 
 hipError_t launch_cg_copy(const CgDims &d, bool to_ws, void *X, long long ldx, void *ws, hipStream_t stream) {
-    return dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto) {
+    return cg_dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto) {
         using R = decltype(rt);
         constexpr int NC = decltype(nc)::value;
         if (to_ws)
@@ -422,7 +369,7 @@ hipError_t launch_cg_copy(const CgDims &d, bool to_ws, void *X, long long ldx, v
 }
 
 hipError_t launch_cg_dot(const CgDims &d, int par, const void *u, const void *v, void *part, const CgState *st, hipStream_t stream) {
-    return dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto sgn) {
+    return cg_dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto sgn) {
         using R = decltype(rt);
         constexpr int NC = decltype(nc)::value;
         hipLaunchKernelGGL((dot_kernel<R, NC>), grid, dim3(kThreads), 0, stream, d.ld, ng, sgn, par, (const R *)u, (const R *)v, (R *)part, st);
@@ -431,7 +378,7 @@ hipError_t launch_cg_dot(const CgDims &d, int par, const void *u, const void *v,
 
 hipError_t launch_cg_update(const CgDims &d, int par, const void *ppq, const void *p, const void *q, void *x, void *r, void *pnn,
                             void *prz, CgState *st, hipStream_t stream) {
-    return dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto sgn) {
+    return cg_dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto sgn) {
         using R = decltype(rt);
         constexpr int NC = decltype(nc)::value;
         auto launch = [&](auto kernel) {
@@ -447,7 +394,7 @@ hipError_t launch_cg_update(const CgDims &d, int par, const void *ppq, const voi
 
 hipError_t launch_cg_dir(const CgDims &d, bool first, int par, long long it, double rtol, double atol, const void *pbb, const void *pnn,
                          const void *prz, const void *z, void *p, CgState *st, hipStream_t stream) {
-    return dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto) {
+    return cg_dispatch(d, [&](auto rt, auto nc, long long ng, dim3 grid, auto) {
         using R = decltype(rt);
         constexpr int NC = decltype(nc)::value;
         hipLaunchKernelGGL((dir_kernel<R, NC>), grid, dim3(kThreads), 0, stream, d.ld, ng, first ? 1 : 0, par, it, rtol, atol,

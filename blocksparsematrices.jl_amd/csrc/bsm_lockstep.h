@@ -1,0 +1,252 @@
+// bsm_lockstep.h -- the host side that the lockstep solver objects (bsm_cg.cpp: bsm_cg_*, bsm_bicgstab.cpp: bsm_bicgstab_*;
+// include/bsm_rocm.h) share: what a solver object holds whatever its method, the (handle, vector) pairings and the
+// multi-column product on the workspace, the refusals of create and solve, the one device allocation with its ring of
+// pinned record slots, the staging of host matrices, and the look-ahead loop that reads one record per iteration.  A
+// method adds its vectors and partial sums to the allocation (Carve) and supplies its start and its iteration.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "bsm_cg.h"
+#include "bsm_internal.h"
+
+namespace bsm {
+
+constexpr int kLockstepRing = 4;  // pinned record slots and events: at most two records are in flight
+
+struct LockstepSolver {
+    bsm_matrix_s *A = nullptr, *M = nullptr;
+    int opA = 0, opM = 0, vt = 0, kmax = 0, device = 0;
+    bool a_cvec = false, m_cvec = false;
+    int64_t n = 0, ld = 0;
+    int G = 1;
+    // ONE device allocation (info.workspace): the method's vectors as ld x kmax, its partials, the state
+    void *ws = nullptr;
+    int64_t ws_bytes = 0;
+    CgState *state = nullptr;
+    CgRecord *slots = nullptr;  // pinned, kLockstepRing of them
+    hipEvent_t ev[kLockstepRing] = {};
+    // BSM_MEM_HOST solves: device copies of B and X (n x kmax), allocated at the first one
+    void *hb = nullptr, *hx = nullptr;
+
+    void release() {
+        if (ws) (void)hipFree(ws);
+        if (hb) (void)hipFree(hb);
+        if (hx) (void)hipFree(hx);
+        if (slots) (void)hipHostFree(slots);
+        for (hipEvent_t &e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        ws = hb = hx = nullptr;
+        slots = nullptr;
+    }
+};
+
+// how `H` is applied to vectors of type vt: 0 bsm_mul_multi, 1 bsm_mul_multi_cvec, -1 not at all (as bsm_gmres_create)
+inline int pairing(const bsm_matrix_s *H, int vt) {
+    const int dt = H->an.dtype;
+    if (dt < 0 || dt > 5) return -1;
+    if (vec_type(dt) == vt) return 0;
+    if ((dt == BSM_F32 && vt == BSM_C64) || (dt == BSM_F64 && vt == BSM_C128)) return 1;
+    return -1;
+}
+
+// Y = op(H) X on nrhs columns of the workspace (leading dimension ld), Y overwritten
+inline int apply(bsm_matrix_s *H, int op, bool cvec, int nrhs, int64_t ld, int vt, const void *X, void *Y, hipStream_t st) {
+    const double one_d[2] = {1, 0}, zero_d[2] = {0, 0};
+    const float one_f[2] = {1, 0}, zero_f[2] = {0, 0};
+    const bool f = real_bytes(vt) == 4;
+    auto fn = cvec ? bsm_mul_multi_cvec : bsm_mul_multi;
+    return fn(H, op, nrhs, X, ld, Y, ld, f ? (const void *)one_f : (const void *)one_d, f ? (const void *)zero_f : (const void *)zero_d, 1,
+              BSM_MEM_DEVICE, (void *)st);
+}
+
+inline bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) {
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return p < q + bbytes && q < p + abytes;
+}
+
+// offsets into the one allocation, 64-byte aligned
+struct Carve {
+    int64_t off = 0;
+    int64_t take(int64_t bytes) {
+        const int64_t o = off;
+        off += (bytes + 63) / 64 * 64;
+        return o;
+    }
+};
+
+// The argument checks every create begins with.  method_error: null, or what is wrong with the method's own argument
+// (reported in its place in the order of the checks, behind vdtype).
+inline int lockstep_check_create(const void *A, int opA, const void *M, int opM, int vdtype, int32_t nrhs_max,
+                                 const char *method_error = nullptr) {
+    if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    if (opA < 0 || opA > 2 || (M && (opM < 0 || opM > 2))) return fail(BSM_ERR_INVALID, "bad op");
+    if (!is_vec_type(vdtype)) return fail(BSM_ERR_INVALID, "vdtype must be a vector type (BSM_F32 .. BSM_C128)");
+    if (method_error) return fail(BSM_ERR_INVALID, method_error);
+    if (nrhs_max < 1 || nrhs_max > BSM_CG_MAX_RHS) return fail(BSM_ERR_INVALID, "nrhs_max outside 1 .. BSM_CG_MAX_RHS");
+    return BSM_OK;
+}
+// The other refusals of create that do not depend on the method (`what`: "bsm_cg", "bsm_bicgstab"), and on success the fields
+// of S that follow from the arguments.  out has been checked and cleared by the caller.
+inline int lockstep_init(LockstepSolver *S, const char *what, bsm_matrix_s *A, int opA, bsm_matrix_s *M, int opM, int vdtype,
+                         int32_t nrhs_max) {
+    if (A->an.nrows != A->an.ncols) return fail(BSM_ERR_INVALID, "op(A) is not square");
+    if (M && (M->an.nrows != A->an.nrows || M->an.ncols != A->an.ncols)) return fail(BSM_ERR_INVALID, "M has another order than A");
+    const int pa = pairing(A, vdtype), pm = M ? pairing(M, vdtype) : 0;
+    if (pa < 0 || pm < 0)
+        return fail(BSM_ERR_INVALID, "a handle's vector type must be vdtype, or real and unmixed of the same precision under a complex vdtype");
+    if (A->dist || (M && M->dist)) return fail(BSM_ERR_UNSUPPORTED, std::string("multi-device handles are not supported by ") + what);
+    if (!A->on_device || (M && !M->on_device)) return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
+    if (M && M->img.device != A->img.device) return fail(BSM_ERR_INVALID, "A and M live on different devices");
+    S->A = A, S->M = M, S->opA = opA, S->opM = opM, S->vt = vdtype, S->kmax = nrhs_max, S->device = A->img.device;
+    S->a_cvec = pa == 1, S->m_cvec = pm == 1;
+    S->n = A->an.nrows;
+    const int64_t es = elem_bytes(vdtype);
+    S->ld = (std::max<int64_t>(S->n, 1) * es + 15) / 16 * 16 / es;
+    S->G = krylov_grid(S->n, (int)es);
+    return BSM_OK;
+}
+
+// The allocation of `bytes` (zeroed: the padding of the vectors is zero from here on, bsm_cg.h), the pinned slots and the
+// events.  On failure everything is released; the caller deletes S.
+inline int lockstep_alloc(LockstepSolver *S, int64_t bytes, const char *what) {
+    S->ws_bytes = bytes;
+    DeviceGuard guard;
+    hipError_t e = guard.enter(S->device);
+    if (e == hipSuccess) e = hipMalloc(&S->ws, (size_t)bytes);
+    if (e == hipSuccess) e = hipMemset(S->ws, 0, (size_t)bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&S->slots, sizeof(CgRecord) * kLockstepRing, hipHostMallocDefault);
+    for (int i = 0; i < kLockstepRing && e == hipSuccess; i++) e = hipEventCreateWithFlags(&S->ev[i], hipEventDisableTiming);
+    if (e == hipSuccess) return BSM_OK;
+    S->release();
+    return e == hipErrorOutOfMemory ? fail(BSM_ERR_ALLOC, std::string("out of device memory for the ") + what + " workspace")
+                                    : hip_fail(e, (std::string(what) + " workspace").c_str());
+}
+
+inline int lockstep_destroy(LockstepSolver *S) {
+    DeviceGuard guard;
+    (void)guard.enter(S->device);
+    S->release();
+    return BSM_OK;
+}
+
+// record k (0: the start, j + 1: iteration j) -> its pinned slot, behind its event
+inline hipError_t lockstep_post(LockstepSolver *S, int64_t k, hipStream_t st) {
+    hipError_t q = hipMemcpyAsync(S->slots + k % kLockstepRing, &S->state->rec, sizeof(CgRecord), hipMemcpyDeviceToHost, st);
+    if (q == hipSuccess) q = hipEventRecord(S->ev[k % kLockstepRing], st);
+    return q;
+}
+// The loop of a device solve after its start has been enqueued and record 0 posted: iterate(j) enqueues iteration j (it
+// leaves its record in state->rec), the host reads record j one iteration behind the enqueue, fills history and stops
+// when no column runs or maxiter is reached; then the copy-out of X (launch_cg_copy: n rows of nrhs columns and nothing
+// else), and info / cols from the last record.  info.a_products / m_products are the caller's.
+template <typename Iterate>
+int lockstep_run(LockstepSolver *S, const CgDims &d, void *X, int64_t ldx, void *wsX, const bsm_cg_params &p, bsm_cg_info &info,
+                 bsm_cg_column *cols, double *history, hipStream_t st, Iterate &&iterate) {
+    const int nrhs = d.nrhs;
+    const int64_t maxiter = std::min<int64_t>(p.maxiter, INT32_MAX);
+    hipError_t e = hipSuccess;
+    int64_t enq = 0, rd = 0;
+    const CgRecord *last = nullptr;
+    for (;;) {
+        if (enq < maxiter) {
+            const int rc = iterate(enq);
+            if (rc != BSM_OK) return rc;
+            enq++;
+            if ((e = lockstep_post(S, enq, st)) != hipSuccess) return hip_fail(e, "record of an iteration");
+        }
+        if ((e = hipEventSynchronize(S->ev[rd % kLockstepRing])) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
+        last = S->slots + rd % kLockstepRing;
+        int running = 0;
+        for (int c = 0; c < nrhs; c++) {
+            running += last->status[c] == kCgRun;
+            if (history && rd >= 1 && rd - 1 < p.history_capacity) history[(rd - 1) * nrhs + c] = last->rn[c];
+        }
+        if (running == 0 || rd == maxiter) break;
+        rd++;
+    }
+    // (an iteration enqueued beyond record rd found every column frozen: it wrote nothing)
+    CgRecord fin = *last;
+    if ((e = launch_cg_copy(d, false, X, ldx, wsX, st)) != hipSuccess) return hip_fail(e, "launch_cg_copy");
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    for (int c = 0; c < nrhs; c++) {
+        const int status = fin.status[c] == kCgRun ? 1 : fin.status[c];
+        const int64_t its = fin.done[c];
+        info.status = std::max(info.status, status);
+        info.iterations = std::max(info.iterations, its);
+        info.columns_converged += status == 0;
+        if (cols) {
+            cols[c].status = status;
+            cols[c].reserved = 0;
+            cols[c].iterations = its;
+            cols[c].residual = fin.rn[c];
+            cols[c].bnorm = fin.bnorm[c];
+        }
+    }
+    return BSM_OK;
+}
+
+// The whole of a solve entry point but the method: the refusals, info cleared and its workspace fields set, n == 0, the
+// device guard, and for BSM_MEM_HOST the staging through the dense buffers the solver keeps.  solve_device(B, ldb, X, ldx)
+// is the solve on device matrices.  `what`: the entry's name for the capture refusal.
+template <typename SolveDevice>
+int lockstep_solve(LockstepSolver *S, const char *what, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_cg_params *p,
+                   bsm_cg_info *info, bsm_cg_column *cols, int memspace, hipStream_t st, SolveDevice &&solve_device) {
+    if (!S || !p || !info) return fail(BSM_ERR_INVALID, "null argument");
+    if (p->struct_size != (int32_t)sizeof(bsm_cg_params)) return fail(BSM_ERR_INVALID, "bsm_cg_params.struct_size mismatch");
+    if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
+    if (!(p->rtol >= 0) || !(p->atol >= 0) || p->maxiter < 0 || p->history_capacity < 0)
+        return fail(BSM_ERR_INVALID, "rtol, atol, maxiter and history_capacity must be >= 0");
+    if (nrhs < 1 || nrhs > S->kmax) return fail(BSM_ERR_INVALID, "nrhs outside 1 .. nrhs_max");
+    const int64_t n = S->n, lmin = std::max<int64_t>(n, 1);
+    if (ldb < lmin || ldx < lmin) return fail(BSM_ERR_INVALID, "ldb / ldx < max(n, 1)");
+    const size_t es = (size_t)elem_bytes(S->vt);
+    const size_t bbytes = ((size_t)(nrhs - 1) * (size_t)ldb + (size_t)n) * es, xbytes = ((size_t)(nrhs - 1) * (size_t)ldx + (size_t)n) * es;
+    if (n > 0 && (!B || !X)) return fail(BSM_ERR_INVALID, "null matrix");
+    if (n > 0 && overlap(B, bbytes, X, xbytes)) return fail(BSM_ERR_INVALID, "X must not overlap B");
+    if (capturing(st)) return fail(BSM_ERR_INVALID, std::string(what) + " must not be graph-captured");
+    std::memset(info, 0, sizeof(*info));
+    info->workspace_bytes = S->ws_bytes;
+    info->workspace = (uint64_t)(uintptr_t)S->ws;
+    if (n == 0) {  // nothing to solve: status 0, no iteration, B and X (which may be null) untouched
+        info->columns_converged = nrhs;
+        if (cols) std::memset(cols, 0, sizeof(*cols) * (size_t)nrhs);
+        return BSM_OK;
+    }
+    DeviceGuard guard;
+    hipError_t e = guard.enter(S->device);
+    if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (memspace == BSM_MEM_DEVICE) return solve_device(B, ldb, X, ldx);
+    // host matrices: staged column by column through dense buffers the solver keeps
+    const size_t col = (size_t)n * es;
+    if (!S->hb || !S->hx) {
+        if (!S->hb) e = hipMalloc(&S->hb, col * (size_t)S->kmax + 16);
+        if (e == hipSuccess && !S->hx) e = hipMalloc(&S->hx, col * (size_t)S->kmax + 16);
+        if (e != hipSuccess) {  // (a buffer that was obtained is kept; the next host solve asks for the other again)
+            if (e != hipErrorOutOfMemory) return hip_fail(e, "staging buffers");
+            (void)hipGetLastError();
+            return fail(BSM_ERR_ALLOC, "out of device memory for the staging buffers");
+        }
+    }
+    for (int c = 0; c < nrhs && e == hipSuccess; c++) {
+        e = hipMemcpyAsync((char *)S->hb + c * col, (const char *)B + (size_t)c * (size_t)ldb * es, col, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess && p->use_x0)
+            e = hipMemcpyAsync((char *)S->hx + c * col, (const char *)X + (size_t)c * (size_t)ldx * es, col, hipMemcpyHostToDevice, st);
+    }
+    if (e != hipSuccess) return hip_fail(e, "host-staged solve");
+    const int rc = solve_device(S->hb, n, S->hx, n);
+    if (rc != BSM_OK) return rc;
+    for (int c = 0; c < nrhs && e == hipSuccess; c++)
+        e = hipMemcpyAsync((char *)X + (size_t)c * (size_t)ldx * es, (char *)S->hx + c * col, col, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(e, "host-staged solve");
+    return BSM_OK;
+}
+
+}  // namespace bsm

@@ -39,7 +39,7 @@ __all__ = [
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
     "update_blocks", "refresh", "submatrices", "submatrix", "diag", "invert_blocks", "BlockJacobi", "block_jacobi",
-    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg", "CgInfo", "cg", "cocg",
+    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg", "CgInfo", "cg", "cocg", "BiCgStab", "bicgstab",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -1449,16 +1449,15 @@ class CgInfo:
                 f"{len(self.column_status)}, column_iterations={self.column_iterations.tolist()})")
 
 
-class Cg:
-    """Preconditioned conjugate gradients for A X = B with up to `nrhs` right-hand sides advancing in lockstep on ONE
-    multi-column product per iteration, every step on the device (bsm_cg_*).  method="cg": real symmetric / Hermitian
-    positive definite A (and M); method="cocg": complex symmetric ones (the unconjugated form).  The CALLER asserts the
-    symmetry.  A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g.
-    block_jacobi(A, sets)), or None.  dtype: the type of B and X -- default A's vector type; a real A (and M) of the same
-    precision takes complex vectors.  The workspace (4 n x nrhs matrices, 5 with M) is allocated here, once; A and M are
-    kept alive."""
+class _LockstepSolver:
+    """What the lockstep solver objects (Cg, BiCgStab) share: the checks and the create call, the destroy call, and solve().
+    A subclass names its entry points in _abi (_abi + "_create" / "_solve" / "_destroy") and calls _setup()."""
 
-    def __init__(self, A, M=None, nrhs=1, dtype=None, method="cg"):
+    _abi = None
+
+    def _setup(self, A, M, nrhs, dtype, extra=None):
+        """the checks and the create call; extra(): called once A, M and dtype have passed, gives the arguments of create
+        between nrhs_max and out"""
         base, op = _unwrap(A)
         if not isinstance(base, AbstractBlockMatrix):
             raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
@@ -1468,20 +1467,19 @@ class Cg:
         self.dtype = np.dtype(base.dtype if dtype is None else dtype)
         if self.dtype not in _DT:
             raise TypeError(f"dtype={self.dtype} is not a supported vector type")
-        if method not in _CG_METHODS:
-            raise ValueError(f"method={method!r}: 'cg' or 'cocg'")
-        self.A, self.M, self.nrhs, self.method = A, M, int(nrhs), method
+        extra = () if extra is None else extra()
+        self.A, self.M, self.nrhs = A, M, int(nrhs)
         self.n = size(A)[0]
         self._base, self._mbase = base, mbase
         ptr = C.c_void_p()
-        L.check(L.lib().bsm_cg_create(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype],
-                                      self.nrhs, _CG_METHODS[method], C.byref(ptr)))
+        L.check(getattr(L.lib(), self._abi + "_create")(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype],
+                                                        self.nrhs, *extra, C.byref(ptr)))
         self._ptr = ptr
 
     def __del__(self):
         try:
             if self._ptr:
-                L.lib().bsm_cg_destroy(self._ptr)
+                getattr(L.lib(), self._abi + "_destroy")(self._ptr)
                 self._ptr = None
         except Exception:
             pass
@@ -1538,10 +1536,30 @@ class Cg:
         st = _stream_ptr(stream, B.device) if dev else None
         if dev and stream is not None and X0 is not None and X0 is not X:
             torch.cuda.current_stream(B.device).synchronize()  # the copy of X0 went on torch's current stream
-        L.check(L.lib().bsm_cg_solve(self._ptr, k, bp, ldb, xp, ldx, C.byref(p), C.byref(info), cols,
-                                     hist.ctypes.data_as(C.POINTER(C.c_double)), bms, st))
+        L.check(getattr(L.lib(), self._abi + "_solve")(self._ptr, k, bp, ldb, xp, ldx, C.byref(p), C.byref(info), cols,
+                                                       hist.ctypes.data_as(C.POINTER(C.c_double)), bms, st))
         del bkeep, xkeep
         return X, CgInfo(info, cols, hist[:min(info.iterations, cap)].copy())
+
+
+class Cg(_LockstepSolver):
+    """Preconditioned conjugate gradients for A X = B with up to `nrhs` right-hand sides advancing in lockstep on ONE
+    multi-column product per iteration, every step on the device (bsm_cg_*).  method="cg": real symmetric / Hermitian
+    positive definite A (and M); method="cocg": complex symmetric ones (the unconjugated form).  The CALLER asserts the
+    symmetry.  A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g.
+    block_jacobi(A, sets)), or None.  dtype: the type of B and X -- default A's vector type; a real A (and M) of the same
+    precision takes complex vectors.  The workspace (4 n x nrhs matrices, 5 with M) is allocated here, once; A and M are
+    kept alive."""
+
+    _abi = "bsm_cg"
+
+    def __init__(self, A, M=None, nrhs=1, dtype=None, method="cg"):
+        def code():
+            if method not in _CG_METHODS:
+                raise ValueError(f"method={method!r}: 'cg' or 'cocg'")
+            return (_CG_METHODS[method],)
+        self._setup(A, M, nrhs, dtype, code)
+        self.method = method
 
 
 def _cg_oneshot(A, B, M, method, kw):
@@ -1557,6 +1575,28 @@ def cg(A, B, M=None, **kw):
 def cocg(A, B, M=None, **kw):
     """One-shot form of the unconjugated method for complex symmetric A: Cg(..., method="cocg").solve(B, **kw)."""
     return _cg_oneshot(A, B, M, "cocg", kw)
+
+
+# ---- BiCGSTAB on several right-hand sides in lockstep, on the device (bsm_bicgstab_*) ---------------------------------------
+class BiCgStab(_LockstepSolver):
+    """Right-preconditioned BiCGSTAB for A X = B with A NOT necessarily symmetric and up to `nrhs` right-hand sides
+    advancing in lockstep on TWO multi-column products per iteration, every step on the device (bsm_bicgstab_*).  A: a
+    block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g. block_jacobi(A, sets)),
+    or None.  dtype: the type of B and X -- default A's vector type; a real A (and M) of the same precision takes complex
+    vectors.  The workspace (6 n x nrhs matrices, 7 with M) is allocated here, once; A and M are kept alive.  solve() is
+    the one Cg has: the same arguments, (X, CgInfo) back; a column that converges after the first half of an iteration reports
+    that half step's residual norm.  info.a_products = 2 * iterations (+ 1 with X0), m_products = 2 * iterations with M."""
+
+    _abi = "bsm_bicgstab"
+
+    def __init__(self, A, M=None, nrhs=1, dtype=None):
+        self._setup(A, M, nrhs, dtype)
+
+
+def bicgstab(A, B, M=None, **kw):
+    """One-shot form: BiCgStab(A, M, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
+    k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
+    return BiCgStab(A, M, nrhs=k, dtype=_elt(B)).solve(B, **kw)
 
 
 # ---- conversion used by the reference's tests as their oracle (host utility, not the hot path) ----

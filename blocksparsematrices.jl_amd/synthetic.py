@@ -136,6 +136,12 @@ def config1(n=1000, nblocks=50, bs=32, dtype=np.float64, seed=0xB5A1):
                 x=vector(seed, n, dtype))
 
 
+def config2_row_segments(n=100_000, lo=8, hi=64, seed=0xB5A2):
+    """(start, size) of C2's row segments (0-based starts), of the GLOBAL operator of n rows: every block of config2 spans
+    one of them (not every one of them holds a block)."""
+    return _segments(seed, 0, n, lo, hi)
+
+
 def config2(n=100_000, nblocks=5000, lo=8, hi=64, dtype=np.float64, seed=0xB5A2, part=None, on_device=False):
     """C2: VBCRS n x n; rows and cols each cut into consecutive segments of size U{lo..hi};
     nblocks distinct (row-seg, col-seg) pairs drawn uniformly; block = seg-height x seg-width.
@@ -148,7 +154,7 @@ def config2(n=100_000, nblocks=5000, lo=8, hi=64, dtype=np.float64, seed=0xB5A2,
     rank, nparts = part if part is not None else (0, 1)
     n_per, n = n, n * nparts
     nblocks = nblocks * nparts
-    rstart, rsz = _segments(seed, 0, n, lo, hi)
+    rstart, rsz = config2_row_segments(n, lo, hi, seed)
     cstart, csz = _segments(seed, 1 << 20, n, lo, hi)
     nr, nc = len(rsz), len(csz)
     nblocks = min(nblocks, nr * nc)

@@ -719,6 +719,79 @@ int bsm_cg_solve(struct bsm_cg_s *S, int32_t nrhs, const void *B, int64_t ldb, v
                  double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
 int bsm_cg_destroy(struct bsm_cg_s *S);
 
+/* bsm_bicgstab_*: right-preconditioned BiCGSTAB for operators that need NOT be symmetric, nrhs = 1 .. BSM_CG_MAX_RHS
+ * right-hand sides in lockstep, wholly on the device.  The short recurrence for what bsm_cg cannot take and bsm_gmres takes
+ * one column at a time: 6 work vectors per right-hand side (7 with M) whatever the iteration count, instead of restart + 4,
+ * two products per iteration, both of them ONE multi-column product on all K systems (bsm_mul_multi: the matrix is
+ * streamed once per batch of columns), and no transposed product.  Parameters, info and columns are those of bsm_cg_*.
+ * (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+ *   Method, per column c, with <u, v> = sum conj(u_i) v_i always:
+ *     r = b - op(A) x0 (or b);  rhat = r;  rho = <rhat, r>;  p = r
+ *     repeat:  phat = opM(M) p (or p);  v = op(A) phat;  sigma = <rhat, v>;  alpha = rho / sigma
+ *              x += alpha phat;  r -= alpha v  (r now holds s);  sn = ||r||_2
+ *              shat = opM(M) r (or r);  t = op(A) shat;  ts = <t, r>;  tt = <t, t>
+ *              sn <= tol_c:  the column converges HERE (x already holds the half step)
+ *              omega = ts / tt;  x += omega shat;  r -= omega t;  rn = ||r||_2;  rho' = <rhat, r>
+ *              beta = (rho' / rho) (alpha / omega);  p = r + beta (p - omega v);  rho = rho'
+ *   Column c is converged when sn_c or rn_c <= tol_c = max(rtol * ||b_c||_2, atol); the starting residual is checked too
+ *   (0 iterations).  The residual is that of the unpreconditioned system (right preconditioning).
+ * create: one device allocation on A's device, reported in info: X, R, Rhat, P, V, T (and Z with M: it serves as phat and,
+ *   after the half step has been accumulated into x, as shat) as n x nrhs_max column-major with the leading dimension
+ *   rounded up to whole 16-byte groups, the per-workgroup partial sums, the column states; a ring of pinned record slots
+ *   and events.  vdtype (BSM_F32 .. BSM_C128) is the type of B and X; the (handle, vector) pairings are those of
+ *   bsm_cg_create: a handle of that vector type (a mixed-storage handle counts with its double vectors) goes through
+ *   bsm_mul_multi, a real unmixed handle of the same precision under a complex vdtype through bsm_mul_multi_cvec.  The
+ *   handles must outlive the solver.  Refusals: null A or out, bad op / vdtype, another pairing, op(A) not square, M of
+ *   another order or on another device, nrhs_max outside 1 .. BSM_CG_MAX_RHS: BSM_ERR_INVALID; a multi-device handle:
+ *   BSM_ERR_UNSUPPORTED; an analysis-only handle: BSM_ERR_DEVICE.
+ * solve: B (n x nrhs, leading dimension ldb) and X (ldx), column-major, ldb / ldx >= max(n, 1), any element alignment.
+ *   They are touched only by the start (B is read, X too with use_x0 != 0) and by the final copy-out, which writes the n
+ *   rows of the nrhs columns of X and nothing else.  use_x0 == 0: the solve starts from zero (NaN in the incoming X does
+ *   not survive).
+ *   Kernels (csrc/bsm_bicgstab.hip), launched as (row ranges, columns): bicg_start (r = rhat, the shares of ||b||^2 and
+ *   ||r||^2), bicg_dot (<rhat, v>; <t, s> and ||t||^2 in one pass: one partial per workgroup and column), bicg_half (x, r,
+ *   the shares of ||s||^2), bicg_update (x, r, the shares of ||r||^2 and <rhat, r>), bicg_dir (p; its workgroup 0 writes
+ *   the column's state and record).  Per iteration: [product M,] product A, bicg_dot, bicg_half, [product M,] product A,
+ *   bicg_dot, bicg_update, bicg_dir.  Every workgroup of a column adds that column's partials itself in one fixed order:
+ *   no scalar kernel, no floating-point atomic, nobody waits; alpha, omega and every decision are re-derived by each
+ *   launch that needs them from the same partials, and a launch never reads a scalar that the same launch replaces (two
+ *   slots alternating by iteration parity).
+ *   The decisions are taken ON THE DEVICE, per iteration in this order:
+ *     rho == 0 or sigma == 0 at the top: breakdown, status 3; nothing is written and the column's count does not advance;
+ *     sn not finite: status 2;  sn <= tol_c: status 0;  else tt == 0, ts == 0 or a quotient ts / tt that underflows to 0:
+ *       breakdown, status 3 -- all three with
+ *       the half step in x, s in r, the iteration counted and sn as the residual (at n = 1 the method ends through
+ *       sn <= tol_c with tt possibly zero: the order matters);
+ *     rn not finite: status 2;  rn <= tol_c: status 0.
+ *   No division by zero is executed.  A column that has a status is FROZEN from the next launch on: its workgroups return
+ *   at once, x and r do not change again whatever the host enqueues (the products write V, T and Z only).  The host
+ *   enqueues iteration j + 1 before it waits for the record of iteration j (per column the residual, ||b||, status and
+ *   iteration count, in a pinned slot behind an event) and stops when no column is running or maxiter is reached: X,
+ *   every column's iterations and history do not depend on how late it notices.  Columns still running after maxiter
+ *   lockstep iterations report status 1.
+ *   What lockstep costs: the multi-column products run on all nrhs columns until the LAST column stops -- the vector
+ *   kernels skip a frozen column, the products do not --, and a solve that ends before maxiter has paid up to two
+ *   products of A (and of M) more than it reports, for the iteration that was enqueued ahead of the last record.
+ *   history (may be NULL): history[it * nrhs + c] = the residual norm of column c after iteration it + 1 (rn, or sn where
+ *   the column ended at the half step), it < history_capacity; a frozen column repeats its last value.  cols (may be
+ *   NULL): nrhs entries.
+ *   info: status = the largest column status; iterations = the largest column count; a_products = 2 * iterations (+ 1
+ *   with use_x0) and m_products = 2 * iterations with M, 0 without: the multi-column products the answer uses (the
+ *   iteration enqueued ahead of the last record costs up to two more of each on frozen columns, which are not counted).
+ *   memspace: BSM_MEM_DEVICE -- B, X on A's device; BSM_MEM_HOST -- staged through device buffers the solver keeps from
+ *   its first host solve on.  SYNCHRONOUS; runs wholly on `stream`; must not be graph-captured; one solve at a time per
+ *   solver.  n == 0: status 0, nothing touched.
+ *   BSM_ERR_INVALID: null S / p / info, null B / X with n > 0, nrhs outside 1 .. nrhs_max, ldb or ldx < max(n, 1), X
+ *   overlapping B, negative or NaN rtol / atol, negative maxiter / history_capacity, bad memspace, graph capture, a
+ *   struct_size mismatch.  The call returns BSM_OK for every column status. */
+struct bsm_bicgstab_s;
+int bsm_bicgstab_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max,
+                        struct bsm_bicgstab_s **out);
+int bsm_bicgstab_solve(struct bsm_bicgstab_s *S, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx,
+                       const bsm_cg_params *p, bsm_cg_info *info, bsm_cg_column *cols /* nrhs, may be NULL */,
+                       double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
+int bsm_bicgstab_destroy(struct bsm_bicgstab_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal
