@@ -113,10 +113,12 @@ class BicgTwin:
         self.residual = history[-1] if history else rn0
 
 
-def bicgstab_twin(D, b, Minv, rtol, atol, maxiter, dtype, x0=None, order=None):
+def bicgstab_twin(D, b, Minv, rtol, atol, maxiter, dtype, x0=None, order=None, keep=None):
     """numpy twin of one column of bsm_bicgstab_solve (module docstring) -> BicgTwin.  D: dense array or BlockDiagonal;
-    Minv: dense preconditioner or None; order: a permutation the sums of the forms and of the products with dense
-    operators run in (None: as stored)"""
+    Minv: dense preconditioner or None; order: a permutation the sums of the forms, of the norms and of the products run
+    in (None: as stored; a BlockDiagonal permutes inside its blocks); keep: a MUTATION for the tests of the tests -- every
+    form sums its first `keep` terms only, as a kernel that loses the last workgroup's share would (None: all; not
+    together with order)"""
     dtype = np.dtype(dtype)
     real = real_of(dtype)
     D = D.astype(dtype)
@@ -125,14 +127,19 @@ def bicgstab_twin(D, b, Minv, rtol, atol, maxiter, dtype, x0=None, order=None):
     n = len(b)
     perm = np.arange(n) if order is None else order
 
+    assert order is None or keep is None
+
     def form(u, v):
-        return np.sum((np.conj(u) * v).astype(dtype)[perm], dtype=dtype)
+        terms = (np.conj(u) * v).astype(dtype)
+        return np.sum(terms[perm] if keep is None else terms[:keep], dtype=dtype)
 
     def norm(v):
-        return float(np.linalg.norm(v).astype(real))
+        return float(np.linalg.norm(v if order is None else v[perm]).astype(real))
 
     def times(H, v):
-        if order is None or not isinstance(H, np.ndarray):
+        if isinstance(H, BlockDiagonal):
+            return H.times(v, order).astype(dtype)
+        if order is None:
             return (H @ v).astype(dtype)
         return (np.ascontiguousarray(H[:, perm]) @ v[perm]).astype(dtype)
 

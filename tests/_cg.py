@@ -84,10 +84,22 @@ class BlockDiagonal:
         return BlockDiagonal(self.main.astype(dtype), self.tail.astype(dtype))
 
     def __matmul__(self, v):
+        return self.times(v)
+
+    def times(self, v, order=None):
+        """diag(blocks) v.  order: a permutation of the rows; the ranks of its first bs (tail: t) entries are the order the
+        columns of every block are summed in (None: as stored)"""
         nb, bs, _ = self.main.shape
+        t = self.tail.shape[0]
         out = np.empty_like(v)
-        out[:nb * bs] = np.einsum("bij,bj->bi", self.main, v[:nb * bs].reshape(nb, bs)).ravel()
-        out[nb * bs:] = self.tail @ v[nb * bs:]
+        if order is None:
+            out[:nb * bs] = np.einsum("bij,bj->bi", self.main, v[:nb * bs].reshape(nb, bs)).ravel()
+            out[nb * bs:] = self.tail @ v[nb * bs:]
+            return out
+        q, qt = np.argsort(order[:bs]), np.argsort(order[:t])
+        out[:nb * bs] = np.einsum("bij,bj->bi", np.ascontiguousarray(self.main[:, :, q]),
+                                  np.ascontiguousarray(v[:nb * bs].reshape(nb, bs)[:, q])).ravel()
+        out[nb * bs:] = np.ascontiguousarray(self.tail[:, qt]) @ v[nb * bs:][qt]
         return out
 
     def dense(self):
@@ -123,10 +135,12 @@ class CgTwin:
         self.residual = history[-1] if history else None
 
 
-def cg_twin(D, b, Minv, conj, rtol, atol, maxiter, dtype, x0=None, order=None):
+def cg_twin(D, b, Minv, conj, rtol, atol, maxiter, dtype, x0=None, order=None, keep=None):
     """numpy twin of one column of bsm_cg_solve (module docstring) -> CgTwin.  D: dense array or BlockDiagonal; Minv:
-    dense preconditioner or None; order: a permutation the sums of the forms and of the products with a dense D run in
-    (None: as stored)"""
+    dense preconditioner or None; order: a permutation the sums of the forms, of the norms and of the products with D run
+    in (None: as stored; a BlockDiagonal permutes inside its blocks); keep: a MUTATION for the tests of the tests -- the
+    forms <p, q> and <r, z> sum their first `keep` terms only, as a kernel that loses the last workgroup's share would
+    (None: all; not together with order)"""
     dtype = np.dtype(dtype)
     real = real_of(dtype)
     D = D.astype(dtype)
@@ -135,14 +149,19 @@ def cg_twin(D, b, Minv, conj, rtol, atol, maxiter, dtype, x0=None, order=None):
     n = len(b)
     perm = np.arange(n) if order is None else order
 
+    assert order is None or keep is None
+
     def form(u, v):
-        return np.sum(((np.conj(u) if conj else u) * v).astype(dtype)[perm], dtype=dtype)
+        terms = ((np.conj(u) if conj else u) * v).astype(dtype)
+        return np.sum(terms[perm] if keep is None else terms[:keep], dtype=dtype)
 
     def norm(v):
-        return float(np.linalg.norm(v).astype(real))
+        return float(np.linalg.norm(v if order is None else v[perm]).astype(real))
 
     def times(v):
-        if order is None or not isinstance(D, np.ndarray):
+        if isinstance(D, BlockDiagonal):
+            return D.times(v, order).astype(dtype)
+        if order is None:
             return (D @ v).astype(dtype)
         return (np.ascontiguousarray(D[:, perm]) @ v[perm]).astype(dtype)
 

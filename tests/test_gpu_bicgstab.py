@@ -11,6 +11,7 @@ from _bicgstab import (BI_KINDS, EDGE, EDGE_IDS, ERR_INVALID, ERR_UNSUPPORTED, M
 from _ctors import ctor_build
 from _gpu import dev_copy, dev_mat, outside_bytes, torch_cuda, torch_dtype  # noqa: F401
 from _jacobi import CODE, DTYPES, uniform
+from _lockstep import solve_in_guarded_buffers
 
 pytestmark = pytest.mark.gpu
 
@@ -259,22 +260,6 @@ def test_host_matrices_and_a_side_stream(torch_cuda, bsm, twins):
 
 
 # ---- 8. layout edges of the kernels ----------------------------------------------------------------------------------------
-def solve_in_guarded_buffers(torch, bsm, S, B, kmax):
-    """the solve with B at ldb = n + 3 and X one element past a 16-byte boundary (ldx = n + 1, kmax columns of room),
-    both inside NaN-filled buffers: padding, guard elements and the columns beyond nrhs must keep their bytes"""
-    n, k = B.shape
-    bbuf, bview = dev_mat(torch, B, pad=3, guard=5)
-    xbuf, xall = dev_mat(torch, np.full((n, kmax), np.nan, dtype=B.dtype), pad=1, off=1, guard=5)
-    xview = xall[:, :k]
-    before = (outside_bytes(bbuf, n, n + 3, k), outside_bytes(xbuf, n, n + 1, k, off=1), bbuf.cpu().numpy().tobytes())
-    X, info = S.solve(bview, X=xview, rtol=rtol_of(B.dtype), maxiter=200)
-    torch.cuda.synchronize()
-    assert outside_bytes(bbuf, n, n + 3, k) == before[0], "the padding of B was written"
-    assert outside_bytes(xbuf, n, n + 1, k, off=1) == before[1], "X was written outside its n x nrhs window"
-    assert bbuf.cpu().numpy().tobytes() == before[2], "B was written"
-    return X.cpu().numpy(), info
-
-
 @pytest.mark.parametrize("dtype, n, k", EDGE, ids=EDGE_IDS)
 def test_layout_edges(torch_cuda, bsm, dtype, n, k):
     """small nonsymmetric block-diagonal operators (blocks T + 8 I of order <= 8), no preconditioner, every column against

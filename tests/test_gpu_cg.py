@@ -10,6 +10,7 @@ from _cg import (CG, COCG, ERR_INVALID, ERR_UNSUPPORTED, MAX_RHS, NB, NCG, cg_pr
 from _ctors import ctor_build
 from _gpu import dev_copy, dev_mat, outside_bytes, torch_cuda, torch_dtype  # noqa: F401
 from _jacobi import CODE, DTYPES, KINDS, uniform
+from _lockstep import solve_in_guarded_buffers
 
 pytestmark = pytest.mark.gpu
 
@@ -262,22 +263,6 @@ for _dt in (np.float32, np.complex64, np.complex128):  # both diagonals of the n
     for _i, _n in enumerate(EDGE_N):
         _j = _i * len(EDGE_K) // len(EDGE_N)
         EDGE += sorted({(_dt, _n, EDGE_K[_j]), (_dt, _n, EDGE_K[len(EDGE_K) - 1 - _j])}, key=lambda t: t[2])
-
-
-def solve_in_guarded_buffers(torch, bsm, S, B, kmax):
-    """the solve with B at ldb = n + 3 and X one element past a 16-byte boundary (ldx = n + 1, kmax columns of room),
-    both inside NaN-filled buffers: padding, guard elements and the columns beyond nrhs must keep their bytes"""
-    n, k = B.shape
-    bbuf, bview = dev_mat(torch, B, pad=3, guard=5)
-    xbuf, xall = dev_mat(torch, np.full((n, kmax), np.nan, dtype=B.dtype), pad=1, off=1, guard=5)
-    xview = xall[:, :k]
-    before = (outside_bytes(bbuf, n, n + 3, k), outside_bytes(xbuf, n, n + 1, k, off=1), bbuf.cpu().numpy().tobytes())
-    X, info = S.solve(bview, X=xview, rtol=rtol_of(B.dtype), maxiter=200)
-    torch.cuda.synchronize()
-    assert outside_bytes(bbuf, n, n + 3, k) == before[0], "the padding of B was written"
-    assert outside_bytes(xbuf, n, n + 1, k, off=1) == before[1], "X was written outside its n x nrhs window"
-    assert bbuf.cpu().numpy().tobytes() == before[2], "B was written"
-    return X.cpu().numpy(), info
 
 
 @pytest.mark.parametrize("dtype, n, k", EDGE, ids=[f"{np.dtype(d).name}-n{n}-k{k}" for d, n, k in EDGE])
