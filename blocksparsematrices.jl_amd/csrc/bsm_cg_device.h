@@ -1,4 +1,4 @@
-// bsm_cg_device.h -- the device-side pieces the lockstep solver units (bsm_cg.hip, bsm_bicgstab.hip) share: the 16-byte
+// bsm_cg_device.h -- the device-side pieces the lockstep solver units (bsm_cg.hip, bsm_bicgstab.hip, bsm_gmres_multi.hip) share: the 16-byte
 // access, the wave / workgroup sums, the fixed-order sum of a column's partials, a workgroup's row range and the dispatch
 // of a launch on the vector type.  For the kernel units only; the layout these walk is described in bsm_cg.h.
 #pragma once

@@ -27,6 +27,7 @@
 #include "bsm_krylov.h"
 
 #include "../../include/bsm_rocm.h"
+#include "bsm_krylov_device.h"
 
 namespace bsm {
 namespace {
@@ -128,19 +129,7 @@ __global__ void __launch_bounds__(kThreads) dot_kernel(long long n, int k, const
                 for (int c = 0; c < NC; ++c) s[cc][c] = R(0);
 #pragma unroll
                 for (int u = 0; u < kU; ++u)
-#pragma unroll
-                    for (int e = 0; e < VE; ++e) {
-                        if (NC == 1) {
-                            s[cc][0] = fma(vv[cc][u][e], wv[u][e], s[cc][0]);
-                        } else {  // conj(v) * w
-                            const R vr = vv[cc][u][e * NC], vi = vv[cc][u][e * NC + NC - 1];
-                            const R wr = wv[u][e * NC], wi = wv[u][e * NC + NC - 1];
-                            s[cc][0] = fma(vr, wr, s[cc][0]);
-                            s[cc][0] = fma(vi, wi, s[cc][0]);
-                            s[cc][NC - 1] = fma(vr, wi, s[cc][NC - 1]);
-                            s[cc][NC - 1] = fma(-vi, wr, s[cc][NC - 1]);
-                        }
-                    }
+                    BSM_GS_DOT(R, NC, VE, vv[cc][u], wv[u], s[cc])
             }
 #pragma unroll
             for (int cc = 0; cc < kCB; ++cc)
@@ -176,25 +165,9 @@ __global__ void __launch_bounds__(kThreads)
     if (COMBINE) {
         for (int i = t; i < k * NC; i += kThreads) hs[i] = coef[i];
     } else if (k > 0) {
-        // S threads per column (a power of two, at most a wave), column c = t / S: its lanes are neighbours in one wave
-        int kp = 1;
-        while (kp < k) kp <<= 1;
-        int S = kThreads / kp;
-        if (S > 64) S = 64;
-        const int c = t / S, sl = t % S;
+        int c;
         R a[NC];
-#pragma unroll
-        for (int q = 0; q < NC; ++q) a[q] = R(0);
-        if (c < k)
-            for (int g = sl; g < G; g += S) {
-#pragma unroll
-                for (int q = 0; q < NC; ++q) a[q] += part[((long long)c * G + g) * NC + q];
-            }
-        for (int d = S >> 1; d >= 1; d >>= 1) {
-#pragma unroll
-            for (int q = 0; q < NC; ++q) a[q] += __shfl_xor(a[q], d, 64);
-        }
-        if (c < k && sl == 0) {
+        if (gs_sum_partials<R, NC>(part, k, G, t, kThreads, c, a)) {
 #pragma unroll
             for (int q = 0; q < NC; ++q) {
                 hs[c * NC + q] = -a[q];
@@ -235,19 +208,7 @@ __global__ void __launch_bounds__(kThreads)
                 if (c0 + cc < k) {
                     const R hr = hs[(c0 + cc) * NC], hi = hs[(c0 + cc) * NC + NC - 1];
 #pragma unroll
-                    for (int u = 0; u < kU; ++u)
-#pragma unroll
-                        for (int e = 0; e < VE; ++e) {
-                            if (NC == 1) {
-                                wv[u][e] = fma(vv[cc][u][e], hr, wv[u][e]);
-                            } else {
-                                const R vr = vv[cc][u][e * NC], vi = vv[cc][u][e * NC + NC - 1];
-                                wv[u][e * NC] = fma(vr, hr, wv[u][e * NC]);
-                                wv[u][e * NC] = fma(-vi, hi, wv[u][e * NC]);
-                                wv[u][e * NC + NC - 1] = fma(vr, hi, wv[u][e * NC + NC - 1]);
-                                wv[u][e * NC + NC - 1] = fma(vi, hr, wv[u][e * NC + NC - 1]);
-                            }
-                        }
+                    for (int u = 0; u < kU; ++u) gs_axpy<R, NC, VE>(vv[cc][u], hr, hi, wv[u]);
                 }
             }
         }
@@ -307,58 +268,20 @@ __global__ void __launch_bounds__(64) hess_kernel(int G, int m, int j, const R *
     __shared__ R gg[2 * NC];
     const int lane = threadIdx.x;
     const R hn = sqrt(wave_total(nrmpart, G, lane));
-    for (int i = lane; i < (j + 1) * NC; i += 64) {
-        col[i] = hsum[i];
-        hsum[i] = R(0);
-    }
-    for (int i = lane; i < j; i += 64) rot[i] = cs[i];
-    for (int i = lane; i < j * NC; i += 64) rot[BSM_GMRES_MAX_RESTART + i] = sn[i];
-    if (lane < NC) gg[lane] = g[j * NC + lane];
-    __syncthreads();
+    BSM_HESS_GATHER(R, NC, j, lane, hsum, cs, sn, g, col, rot, gg)
     if (lane == 0) {
-        const R est = krylov_hess_column<R, NC>(j, col, hn, rot, rot + BSM_GMRES_MAX_RESTART, gg - (long long)j * NC);
-        cs[j] = rot[j];
-        for (int q = 0; q < NC; ++q) {
-            sn[j * NC + q] = rot[BSM_GMRES_MAX_RESTART + j * NC + q];
-            g[j * NC + q] = gg[q];
-            g[(j + 1) * NC + q] = gg[NC + q];
-        }
+        BSM_HESS_ROTATE(R, NC, j, hn, cs, sn, g, col, rot, gg, est)
         res[j] = (double)est;
         inv[0] = hn == R(0) ? R(0) : R(1) / hn;
     }
-    __syncthreads();
-    R *const dst = Hm + (long long)j * (m + 1) * NC;
-    for (int i = lane; i < (j + 1) * NC; i += 64) dst[i] = col[i];
+    BSM_HESS_SCATTER(R, NC, m, j, lane, Hm, col)
 }
 
 template <typename R, int NC>
 __global__ void __launch_bounds__(64) trsolve_kernel(int m, int k, const R *__restrict__ Hm, const R *__restrict__ g, R *__restrict__ y) {
     __shared__ R ys[BSM_GMRES_MAX_RESTART * NC];
     __shared__ R q[2];
-    const int lane = threadIdx.x;
-    const long long ldh = m + 1;
-    for (int i = lane; i < k * NC; i += 64) ys[i] = g[i];
-    __syncthreads();
-    for (int i = k - 1; i >= 0; --i) {
-        if (lane == 0) {
-            R d[2] = {R(0), R(0)};
-            k_div<R, NC>(ys + i * NC, Hm + ((long long)i + i * ldh) * NC, d);
-            for (int c = 0; c < NC; ++c) q[c] = ys[i * NC + c] = d[c];
-        }
-        __syncthreads();
-        const R qr = q[0], qi = q[NC - 1];
-        for (int r = lane; r < i; r += 64) {
-            const R *a = Hm + ((long long)r + i * ldh) * NC;
-            if (NC == 1) {
-                ys[r] -= a[0] * qr;
-            } else {
-                ys[r * NC] -= a[0] * qr - a[NC - 1] * qi;
-                ys[r * NC + NC - 1] -= a[0] * qi + a[NC - 1] * qr;
-            }
-        }
-        __syncthreads();
-    }
-    for (int i = lane; i < k * NC; i += 64) y[i] = ys[i];
+    trsolve_wave<R, NC>(m, k, Hm, g, y, ys, q, (int)threadIdx.x);
 }
 
 // whether 16-byte groups serve all of the pointers (null ones do not count), and where the first one starts

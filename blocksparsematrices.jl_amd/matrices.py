@@ -39,7 +39,7 @@ __all__ = [
     "offdiagonalcolors", "transposeoffdiagonalcolors", "rowcolvals", "sparse", "ColorInfo", "conflicts",
     "color", "coloringalgorithm", "Context", "partition_rows", "host_register", "host_unregister", "rowcolvals_device", "sparse_device",
     "update_blocks", "refresh", "submatrices", "submatrix", "diag", "invert_blocks", "BlockJacobi", "block_jacobi",
-    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg", "CgInfo", "cg", "cocg", "BiCgStab", "bicgstab",
+    "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg", "CgInfo", "cg", "cocg", "BiCgStab", "bicgstab", "GmresMulti",
 ]
 
 _DT = {np.dtype(np.float32): L.BSM_F32, np.dtype(np.float64): L.BSM_F64,
@@ -1416,7 +1416,10 @@ class Gmres:
 
 
 def gmres(A, b, M=None, restart=30, **kw):
-    """One-shot form: Gmres(A, M, restart, dtype of b).solve(b, **kw) -> (x, info)."""
+    """One-shot form: Gmres(A, M, restart, dtype of b).solve(b, **kw) -> (x, GmresInfo); a matrix B of k columns goes to
+    GmresMulti(A, M, k, restart, dtype of B).solve(B, **kw) -> (X, CgInfo), its columns advancing in lockstep."""
+    if getattr(b, "ndim", 1) == 2:
+        return GmresMulti(A, M, nrhs=b.shape[1], restart=restart, dtype=_elt(b)).solve(b, **kw)
     return Gmres(A, M, restart=restart, dtype=_elt(b)).solve(b, **kw)
 
 
@@ -1450,7 +1453,7 @@ class CgInfo:
 
 
 class _LockstepSolver:
-    """What the lockstep solver objects (Cg, BiCgStab) share: the checks and the create call, the destroy call, and solve().
+    """What the lockstep solver objects (Cg, BiCgStab, GmresMulti) share: the checks and the create call, the destroy call, and solve().
     A subclass names its entry points in _abi (_abi + "_create" / "_solve" / "_destroy") and calls _setup()."""
 
     _abi = None
@@ -1597,6 +1600,28 @@ def bicgstab(A, B, M=None, **kw):
     """One-shot form: BiCgStab(A, M, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
     k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
     return BiCgStab(A, M, nrhs=k, dtype=_elt(B)).solve(B, **kw)
+
+
+# ---- restarted GMRES on several right-hand sides in lockstep, on the device (bsm_gmres_multi_*) ----------------------------
+class GmresMulti(_LockstepSolver):
+    """Right-preconditioned restarted GMRES(restart) for A X = B with up to `nrhs` right-hand sides advancing in lockstep on
+    ONE multi-column product per iteration, every step on the device (bsm_gmres_multi_*): per column the method of Gmres,
+    all columns restarting together.  A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind
+    and order (e.g. block_jacobi(A, sets)), or None.  dtype: the type of B and X -- default A's vector type; a real A (and
+    M) of the same precision takes complex vectors.  The workspace (restart + 3 n x nrhs matrices, restart + 4 with M) is
+    allocated here, once; A and M are kept alive.  solve() is the one Cg has: the same arguments, (X, CgInfo) back;
+    info.history holds the residual ESTIMATES, info.cycles = ceil(iterations / restart); statuses 0, 1, 2 (never 3)."""
+
+    _abi = "bsm_gmres_multi"
+
+    def __init__(self, A, M=None, nrhs=1, restart=30, dtype=None):
+        self.restart = int(restart)
+        self._setup(A, M, nrhs, dtype, lambda: (self.restart,))
+
+    def solve(self, B, **kw):
+        X, info = super().solve(B, **kw)
+        info.cycles = -(-int(info.iterations) // self.restart)
+        return X, info
 
 
 # ---- conversion used by the reference's tests as their oracle (host utility, not the hot path) ----

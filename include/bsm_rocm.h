@@ -792,6 +792,58 @@ int bsm_bicgstab_solve(struct bsm_bicgstab_s *S, int32_t nrhs, const void *B, in
                        double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
 int bsm_bicgstab_destroy(struct bsm_bicgstab_s *S);
 
+/* bsm_gmres_multi_*: right-preconditioned restarted GMRES(restart) for op(A) X = B on nrhs = 1 .. BSM_CG_MAX_RHS right-hand
+ * sides in lockstep, wholly on the device: the method for operators that need not be symmetric when the residual has to go
+ * down monotonically and no breakdown is acceptable, on ONE multi-column product per iteration (bsm_mul_multi: the matrix
+ * is streamed once per batch of columns).  Parameters, info and columns are those of bsm_cg_*.  Per column it is the method
+ * bsm_gmres_solve documents -- two classical Gram-Schmidt passes, Givens rotations, the estimate |g[j + 1]|, x += opM(M) V y
+ * at the end of a cycle, the next cycle from the TRUE residual --, so column c of a lockstep solve is, as a method, the
+ * stand-alone solve of b_c.  All columns start together and restart together, every `restart` iterations: a column's cycle
+ * boundaries are the ones it would have alone.  Inside a cycle each column has its own basis, Hessenberg factor, rotations
+ * and g.  (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+ * create: one device allocation on A's device, reported in info: the basis V_0 .. V_restart, W, X (and Z with M) -- restart + 3
+ *   matrices, restart + 4 with M -- as n x nrhs_max column-major with the leading dimension rounded up to whole 16-byte
+ *   groups (basis vector i of ALL columns is one such matrix, so op(A) V_j is a plain multi-column product), per column the
+ *   small arrays of a cycle and the per-workgroup partial sums of a pass, the column states; a ring of pinned record slots
+ *   and events.  vdtype and the (handle, vector) pairings are those of bsm_cg_create.  The handles must outlive the solver.
+ *   Refusals: those of bsm_cg_create, and restart outside 1 .. BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID.
+ * solve: B, X, ldb, ldx, use_x0, memspace, stream, history layout, cols and the refusals as in bsm_cg_solve.
+ *   Kernels (csrc/bsm_gmres_multi.hip), vector launches as (row ranges, columns): gm_start (r = B - op(A) X -> V_0, the shares
+ *   of ||r||^2 and ||b||^2), gm_begin (V_0 /= beta; g = beta e_1; the decision of a start), per iteration [product M,] product
+ *   A, twice gm_dot / gm_update (one partial per workgroup, basis vector and column; every workgroup adds them itself in one
+ *   fixed order), gm_hess (one wave per column: the new Hessenberg column, rotation, estimate, the decision), gm_scale; at
+ *   the end of a cycle gm_trsolve (one wave per column), gm_combine (U = V y), [product M,] gm_axpy.  No floating-point
+ *   atomic, nobody waits, and a launch never reads a scalar that the same launch replaces (gm_begin and gm_hess read one
+ *   slot of the state and write the other).
+ *   The decisions are taken ON THE DEVICE.  Column c converges when its estimate is <= tol_c = max(rtol * ||b_c||_2, atol)
+ *   (status 0: its answer uses exactly the iterations of the open cycle up to that one, added to x at the end of that
+ *   cycle), or when the TRUE residual at a start or restart already meets it (status 0, no history row for it, `residual`
+ *   is that true norm).  A non-finite norm or estimate gives status 2, and x_c holds its last finished cycle.  Status 3 is
+ *   never reported: a lucky breakdown ||w|| = 0 is convergence (1 / ||w|| is replaced by 0, no NaN).  A column that has a
+ *   status is FROZEN: the workgroups of every vector launch return before their first vector load, and the products write
+ *   W and Z only, so nothing the host enqueues late reaches its x, count or history.
+ *   The host only enqueues; it reads one record per gm_begin / gm_hess from the pinned ring, one step behind its enqueues.
+ *   It ends a cycle early when no column runs, always enqueues the cycle's end (harmless on columns that owe nothing), and
+ *   enqueues the restart without waiting.  maxiter bounds the lockstep iterations; columns still running after it report
+ *   status 1; a cycle that maxiter cuts short has min(restart, maxiter - done) iterations.
+ *   history[it * nrhs + c] = the residual ESTIMATE of column c after lockstep iteration it + 1, it < history_capacity; a
+ *   frozen column repeats its last value (its `residual`).  Only gm_hess records fill rows.
+ *   info: status = the largest column status; iterations = the largest column count, which also gives the cycles:
+ *   ceil(iterations / restart).  a_products = iterations + one true-residual product per restart that found a column running
+ *   (+ 1 with use_x0); m_products = iterations + one per cycle that ran an iteration, 0 without M.  These count multi-column
+ *   products the answer uses.
+ *   What lockstep costs: the products run on all nrhs columns until the last column stops, and every column keeps its own
+ *   basis: the orthogonalisation does not share across columns.  The look-ahead: a solve that ends before maxiter has paid
+ *   at most ONE product of A and one of M beyond these counts -- the iteration, or the restart's op(A) X, that was enqueued
+ *   ahead of the record that showed no column running. */
+struct bsm_gmres_multi_s;
+int bsm_gmres_multi_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, int32_t restart,
+                           struct bsm_gmres_multi_s **out);
+int bsm_gmres_multi_solve(struct bsm_gmres_multi_s *S, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx,
+                          const bsm_cg_params *p, bsm_cg_info *info, bsm_cg_column *cols /* nrhs, may be NULL */,
+                          double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
+int bsm_gmres_multi_destroy(struct bsm_gmres_multi_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

@@ -676,6 +676,39 @@ function cg!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; M=nothing, method::Sy
 end
 
 """
+    gmres!(X, A, B; M=nothing, restart=30, rtol=1e-8, atol=0.0, maxiter=size(A, 1), x0=false) -> (X, info, columns, history)
+
+Right-preconditioned restarted GMRES for `A X = B` with 1 to 16 right-hand sides advancing in lockstep on one multi-column
+product per iteration, every step of it on the device (bsm_gmres_multi_create / _solve / _destroy).  Per column it is the
+method of the vector form of `gmres!`; all columns restart together.  `info`, `columns` and `history` are those of
+[`cg!`](@ref), `history` holding the residual estimates: `columns[c].status` 0 converged, 1 `maxiter` reached, 2 a
+non-finite residual; the cycles are `cld(info.iterations, restart)`.
+"""
+function gmres!(X::Matrix{T}, A::ROCmAnyOp, B::Matrix{T}; M=nothing, restart::Integer=30, rtol::Real=1e-8, atol::Real=0.0,
+                maxiter::Integer=size(A, 1), x0::Bool=false) where {T<:ROCmEltype}
+    n, k = size(B, 1), size(B, 2)
+    size(A, 1) == size(A, 2) == n && size(X) == size(B) || throw(DimensionMismatch("gmres! needs a square operator and B, X of its order"))
+    1 <= k <= 16 || throw(ArgumentError("gmres! takes 1 to 16 right-hand sides"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = M === nothing ? C_NULL : handle(_base(M)).ptr
+    _check(ccall((:bsm_gmres_multi_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), mptr, M === nothing ? 0 : _op(M), _DTYPE[T], k, restart, out))
+    p = BsmCgParams(sizeof(BsmCgParams), x0, rtol, atol, maxiter, maxiter)
+    info = BsmCgInfo(0, 0, 0, 0, 0, 0, 0)
+    columns = Vector{BsmCgColumn}(undef, k)
+    history = zeros(Float64, k, max(maxiter, 1))
+    ld = max(n, 1)
+    try
+        GC.@preserve A M X B columns history _check(ccall((:bsm_gmres_multi_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{BsmCgParams}, Ref{BsmCgInfo}, Ptr{BsmCgColumn}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+            out[], k, pointer(B), ld, pointer(X), ld, p, info, columns, history, 0, C_NULL))
+    finally
+        ccall((:bsm_gmres_multi_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return X, info, columns, history[:, 1:min(info.iterations, maxiter)]
+end
+
+"""
     bicgstab!(X, A, B; M=nothing, rtol=1e-8, atol=0.0, maxiter=size(A, 1), x0=false) -> (X, info, columns, history)
 
 Right-preconditioned BiCGSTAB for `A X = B` with `A` not necessarily symmetric and 1 to 16 right-hand sides advancing in
