@@ -1,5 +1,6 @@
 // bsm_capi.cpp -- the extern "C" surface of libbsmrocm.so (include/bsm_rocm.h), but for the features whose unit holds
-// its own entry points: reading entries (bsm_entries.cpp), the block inverse (bsm_invert.cpp), GMRES (bsm_krylov.cpp).
+// its own entry points: reading entries (bsm_entries.cpp), the block inverse (bsm_invert.cpp), the Gram-Schmidt pass
+// (bsm_krylov.cpp), GMRES (bsm_gmres_multi.cpp).
 // Plain pointers and sizes only; checks and converts arguments, has the operator built, refilled and
 // released (bsm_operator.cpp: LocalOperator; bsm_dist.cpp for handles over several devices) and
 // forwards bsm_mul to the HIP launchers.  Never throws across the ABI.

@@ -1,9 +1,10 @@
-// bsm_gmres_multi.cpp -- the bsm_gmres_multi_* solver object (include/bsm_rocm.h): the host side of right-preconditioned
-// restarted GMRES on up to BSM_CG_MAX_RHS right-hand sides in lockstep.  The products go through the public bsm_mul_multi /
-// bsm_mul_multi_cvec, the vector work through the kernels of bsm_gmres_multi.hip.  Every decision of the method is taken on
-// the device; the host only enqueues, and reads one record per gm_begin / gm_hess one step late.  Refusals, allocation
-// and the staging of host matrices are bsm_lockstep.h, shared with bsm_cg.cpp and bsm_bicgstab.cpp; the loop over cycles is
-// this unit's (lockstep_run is one flat sequence of iterations).
+// bsm_gmres_multi.cpp -- the bsm_gmres_multi_* and bsm_gmres_* solver objects (include/bsm_rocm.h): the host side of
+// right-preconditioned restarted GMRES on up to BSM_CG_MAX_RHS right-hand sides in lockstep, and its one-column front.  The
+// products go through the public bsm_mul_multi / bsm_mul_multi_cvec, the vector work through the kernels of
+// bsm_gmres_multi.hip.  Every decision of the method is taken on the device; the host only enqueues, and reads one record
+// per gm_begin / gm_hess one step late.  Refusals, allocation and the staging of host matrices are bsm_lockstep.h, shared
+// with bsm_cg.cpp and bsm_bicgstab.cpp; the loop over cycles is this unit's (lockstep_run is one flat sequence of
+// iterations).  bsm_gmres_* is the same solver created with nrhs_max = 1 behind its own parameter and info structs.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -26,16 +27,22 @@ struct bsm_gmres_multi_s : LockstepSolver {
     char *basis(int64_t i) const { return V + i * ld * kmax * elem_bytes(vt); }
 };
 
-extern "C" int bsm_gmres_multi_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, int32_t restart,
-                                      struct bsm_gmres_multi_s **out) {
+// the solver of bsm_gmres_*: the lockstep solver with one column
+struct bsm_gmres_s : bsm_gmres_multi_s {};
+
+namespace {
+
+// create of both solver objects (`what`: "bsm_gmres_multi", "bsm_gmres")
+template <typename Solver>
+int gm_create(const char *what, bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, int32_t restart, Solver **out) {
     if (!out) return fail(BSM_ERR_INVALID, "out is null");
     *out = nullptr;
     int rc = lockstep_check_create(A, opA, M, opM, vdtype, nrhs_max,
                                    restart < 1 || restart > BSM_GMRES_MAX_RESTART ? "restart outside 1 .. BSM_GMRES_MAX_RESTART" : nullptr);
     if (rc != BSM_OK) return rc;
-    bsm_gmres_multi_s *S = new (std::nothrow) bsm_gmres_multi_s;
+    Solver *S = new (std::nothrow) Solver;
     if (!S) return fail(BSM_ERR_ALLOC, "out of host memory");
-    if ((rc = lockstep_init(S, "bsm_gmres_multi", A, opA, M, opM, vdtype, nrhs_max)) != BSM_OK) {
+    if ((rc = lockstep_init(S, what, A, opA, M, opM, vdtype, nrhs_max)) != BSM_OK) {
         delete S;
         return rc;
     }
@@ -59,14 +66,12 @@ extern "C" int bsm_gmres_multi_create(bsm_matrix_t A, int opA, bsm_matrix_t M, i
     return BSM_OK;
 }
 
-extern "C" int bsm_gmres_multi_destroy(struct bsm_gmres_multi_s *S) {
+template <typename Solver> int gm_destroy(Solver *S) {
     if (!S) return BSM_OK;
     lockstep_destroy(S);
     delete S;
     return BSM_OK;
 }
-
-namespace {
 
 // the solve on device matrices B, X (arguments checked)
 int solve_device(bsm_gmres_multi_s *S, int nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_cg_params &p, bsm_cg_info &info,
@@ -208,14 +213,51 @@ int solve_device(bsm_gmres_multi_s *S, int nrhs, const void *B, int64_t ldb, voi
     return BSM_OK;
 }
 
+// solve of both solver objects (`what`: the entry's name)
+int gm_solve(bsm_gmres_multi_s *S, const char *what, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_cg_params *p,
+             bsm_cg_info *info, bsm_cg_column *cols, double *history, int memspace, hipStream_t st) {
+    return lockstep_solve(S, what, nrhs, B, ldb, X, ldx, p, info, cols, memspace, st, [&](const void *Bd, int64_t ldbd, void *Xd, int64_t ldxd) {
+        return solve_device(S, nrhs, Bd, ldbd, Xd, ldxd, *p, *info, cols, history, st);
+    });
+}
+
 }  // namespace
+
+extern "C" int bsm_gmres_multi_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, int32_t restart,
+                                      struct bsm_gmres_multi_s **out) {
+    return gm_create("bsm_gmres_multi", A, opA, M, opM, vdtype, nrhs_max, restart, out);
+}
 
 extern "C" int bsm_gmres_multi_solve(struct bsm_gmres_multi_s *S, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx,
                                      const bsm_cg_params *p, bsm_cg_info *info, bsm_cg_column *cols, double *history, int memspace,
                                      void *stream) {
-    const hipStream_t st = (hipStream_t)stream;
-    return lockstep_solve(S, "bsm_gmres_multi_solve", nrhs, B, ldb, X, ldx, p, info, cols, memspace, st,
-                          [&](const void *Bd, int64_t ldbd, void *Xd, int64_t ldxd) {
-                              return solve_device(S, nrhs, Bd, ldbd, Xd, ldxd, *p, *info, cols, history, st);
-                          });
+    return gm_solve(S, "bsm_gmres_multi_solve", nrhs, B, ldb, X, ldx, p, info, cols, history, memspace, (hipStream_t)stream);
 }
+
+extern "C" int bsm_gmres_multi_destroy(struct bsm_gmres_multi_s *S) { return gm_destroy(S); }
+
+// ---- bsm_gmres_*: one column.  Its own structs in, bsm_cg_params / bsm_cg_info / one bsm_cg_column through gm_solve, its
+// own info out; history row i of one column is history[i].
+extern "C" int bsm_gmres_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t restart, bsm_gmres_t *out) {
+    return gm_create("bsm_gmres", A, opA, M, opM, vdtype, 1, restart, out);
+}
+
+extern "C" int bsm_gmres_solve(bsm_gmres_t S, const void *b, void *x, const bsm_gmres_params *p, bsm_gmres_info *info,
+                               double *history, int memspace, void *stream) {
+    if (!S || !p || !info) return fail(BSM_ERR_INVALID, "null argument");
+    if (p->struct_size != (int32_t)sizeof(bsm_gmres_params)) return fail(BSM_ERR_INVALID, "bsm_gmres_params.struct_size mismatch");
+    const size_t bytes = (size_t)S->n * elem_bytes(S->vt);
+    if (S->n > 0 && (!b || !x)) return fail(BSM_ERR_INVALID, "null vector");
+    if (S->n > 0 && overlap(b, bytes, x, bytes)) return fail(BSM_ERR_INVALID, "x must not alias b");
+    const bsm_cg_params q{(int32_t)sizeof(bsm_cg_params), p->use_x0, p->rtol, p->atol, p->maxiter, p->history_capacity};
+    const int64_t ld = std::max<int64_t>(S->n, 1);
+    bsm_cg_info ci;
+    bsm_cg_column col;
+    const int rc = gm_solve(S, "bsm_gmres_solve", 1, b, ld, x, ld, &q, &ci, &col, history, memspace, (hipStream_t)stream);
+    if (rc != BSM_OK) return rc;
+    *info = bsm_gmres_info{ci.status,     (int32_t)((ci.iterations + S->m - 1) / S->m), ci.iterations,      col.residual, col.bnorm,
+                           ci.a_products, ci.m_products,                                ci.workspace_bytes, ci.workspace};
+    return BSM_OK;
+}
+
+extern "C" int bsm_gmres_destroy(bsm_gmres_t S) { return gm_destroy(S); }

@@ -1,12 +1,11 @@
-// bsm_gmres_multi.h -- what bsm_gmres_multi.hip (the kernels) and bsm_gmres_multi.cpp (bsm_gmres_multi_*; include/bsm_rocm.h)
-// share: the device-side state of a multi-column restarted GMRES solve and the launch interface.
+// bsm_gmres_multi.h -- what bsm_gmres_multi.hip (the kernels) and bsm_gmres_multi.cpp (bsm_gmres_multi_*, bsm_gmres_*;
+// include/bsm_rocm.h) share: the device-side state of a multi-column restarted GMRES solve and the launch interface.
 // (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
 //
 // The vectors are those of bsm_cg.h: ld x K column-major in the solver's workspace, ld rounded up to whole 16-byte groups,
 // the padding zero and staying zero, every launch (krylov_grid(n, es), columns).  Basis vector i of ALL columns is one
 // ld x kmax matrix V_i, so op(A) V_j is a plain multi-column product; the basis of column c is V_0[:, c], V_1[:, c], .. at
-// a stride of vs = kmax * ld elements.  Inside a cycle every column has its own small arrays (GmSmall, the KrylovSmall of
-// bsm_krylov.h once per column) and its own partials: part[(c * m + i) * G + wg] for basis vector i, nrm[c * G + wg].
+// a stride of vs = kmax * ld elements.  Inside a cycle every column has its own small arrays (GmSmall) and its own partials: part[(c * m + i) * G + wg] for basis vector i, nrm[c * G + wg].
 #pragma once
 #include <cstdint>
 

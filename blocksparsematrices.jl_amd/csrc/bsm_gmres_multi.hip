@@ -1,14 +1,14 @@
-// bsm_gmres_multi.hip -- the kernels of bsm_gmres_multi_solve (include/bsm_rocm.h): right-preconditioned restarted GMRES on K
-// right-hand sides in lockstep.  Kept out of the product kernel units like bsm_cg.hip: the build id (Makefile BUILD_ID)
-// names the kernels and schedule of the PRODUCTS.
+// bsm_gmres_multi.hip -- the kernels of bsm_gmres_multi_solve and bsm_gmres_solve (include/bsm_rocm.h): right-preconditioned
+// restarted GMRES on K right-hand sides in lockstep (bsm_gmres_solve: K = 1).  Kept out of the product kernel units like
+// bsm_cg.hip: the build id (Makefile BUILD_ID) names the kernels and schedule of the PRODUCTS.
 // (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
 //
 // The conventions are those of bsm_cg.hip / bsm_bicgstab.hip, whose helpers this unit shares through bsm_cg_device.h; what it
-// shares with the single-column kernels of bsm_krylov.hip is bsm_krylov_device.h (the dot and the update of a tile, the sum of
-// the partials, the body of the hess kernel, the back substitution) and the plain C++ of bsm_krylov.h (rotations, division):
+// shares with the Gram-Schmidt pass of bsm_krylov.hip (bsm_krylov_orth) is bsm_krylov_device.h (the dot and the update of a
+// tile, the sum of the partials); the rotations and the division are the plain C++ of bsm_krylov.h:
 // 256-thread workgroups, the launch (krylov_grid, K), tiles of 256 threads x kU 16-byte groups, one partial per workgroup,
 // basis vector and column, unguarded 16-byte accesses on workspace vectors that carry zero padding (bsm_cg.h).  The
-// arithmetic of an iteration is that of bsm_krylov.hip with the right-hand side on blockIdx.y:
+// arithmetic of a pass is that of bsm_krylov.hip with the right-hand side on blockIdx.y:
 //   start_kernel    r = B - q (B element by element under a guard: any ldb, any alignment) -> V_0, the shares of ||r||^2
 //                   and on the first start of ||b||^2.
 //   begin_kernel    beta from the shares, summed by every workgroup for itself; V_0 *= 1 / beta; workgroup 0 of the column
@@ -18,8 +18,8 @@
 //                   partial per workgroup, basis vector and column.
 //   update_kernel   every workgroup sums the G partials of every basis vector in the same fixed order, keeps h in LDS,
 //                   W -= V h, the shares of ||w||^2; workgroup 0 adds h to hsum.
-//   hess_kernel     one wave per column: krylov_hess_column (bsm_krylov.h) on (hsum, ||w||), then the decision the host of
-//                   bsm_gmres_solve takes -- estimate <= tol: 0, not finite: 2 --, the counts, 1 / ||w|| and the record.
+//   hess_kernel     one wave per column: krylov_hess_column (bsm_krylov.h) on (hsum, ||w||), then the decision --
+//                   estimate <= tol: 0, not finite: 2 --, the counts, 1 / ||w|| and the record.
 //                   Beside begin_kernel the only writer of a column's state.
 //   scale_kernel    V_{j+1} = W * (1 / ||w||).
 //   trsolve_kernel  one wave per column, k = k_c from the state;  combine_kernel  U = V[:, 0 : k_c] y (zeros on a column
@@ -325,11 +325,25 @@ __global__ void __launch_bounds__(64) hess_kernel(int G, int m, int j, int par, 
     R *hsum = hsum_ + (long long)c * m * NC, *Hm = Hm_ + (long long)c * m * (m + 1) * NC, *cs = cs_ + (long long)c * m;
     R *sn = sn_ + (long long)c * m * NC, *g = g_ + (long long)c * (m + 1) * NC;
     const R hn = sqrt(wave_total(nrm + (long long)c * G, G, 1, lane));
-    BSM_HESS_GATHER(R, NC, j, lane, hsum, cs, sn, g, col, rot, gg)
+    // the column hsum[0 .. j] (zeroed behind it), the stored rotations and g[j] into LDS
+    for (int i = lane; i < (j + 1) * NC; i += 64) {
+        col[i] = hsum[i];
+        hsum[i] = R(0);
+    }
+    for (int i = lane; i < j; i += 64) rot[i] = cs[i];
+    for (int i = lane; i < j * NC; i += 64) rot[BSM_GMRES_MAX_RESTART + i] = sn[i];
+    if (lane < NC) gg[lane] = g[j * NC + lane];
+    __syncthreads();
     if (lane == 0) {
-        BSM_HESS_ROTATE(R, NC, j, hn, cs, sn, g, col, rot, gg, est)
+        const R est = krylov_hess_column<R, NC>(j, col, hn, rot, rot + BSM_GMRES_MAX_RESTART, gg - (long long)j * NC);
+        cs[j] = rot[j];
+        for (int q = 0; q < NC; ++q) {
+            sn[j * NC + q] = rot[BSM_GMRES_MAX_RESTART + j * NC + q];
+            g[j * NC + q] = gg[q];
+            g[(j + 1) * NC + q] = gg[NC + q];
+        }
         inv[c] = hn == R(0) ? R(0) : R(1) / hn;
-        // the decision of bsm_gmres_solve's host: the answer of this column uses exactly the iterations up to this one
+        // the decision: the answer of this column uses exactly the iterations up to this one
         const int status = !isfinite(est) || !isfinite(hn) ? 2 : ((double)est <= st->tol[c] ? 0 : kCgRun);
         const int done = in.done[c] + 1;
         out.rn[c] = (double)est;
@@ -341,7 +355,10 @@ __global__ void __launch_bounds__(64) hess_kernel(int G, int m, int j, int par, 
         st->rec.status[c] = status;
         st->rec.done[c] = done;
     }
-    BSM_HESS_SCATTER(R, NC, m, j, lane, Hm, col)
+    // column j of the rotated Hessenberg matrix (leading dimension m + 1)
+    __syncthreads();
+    R *const dst = Hm + (long long)j * (m + 1) * NC;
+    for (int i = lane; i < (j + 1) * NC; i += 64) dst[i] = col[i];
 }
 
 template <typename R, int NC>
@@ -360,6 +377,36 @@ __global__ void __launch_bounds__(kThreads) scale_kernel(long long ld, long long
         for (int k = 0; k < GC; ++k) v.r[k] *= sc;
         store16(Vn + off + g * GC, v);
     }
+}
+
+// y[0 .. k) = R^-1 g[0 .. k) by one wave on the rotated Hessenberg matrix Hm (leading dimension m + 1): lane 0 divides, the
+// column update of every step is spread over the lanes.  ys (BSM_GMRES_MAX_RESTART * NC) and q (2) are LDS.
+template <typename R, int NC>
+__device__ __forceinline__ void trsolve_wave(int m, int k, const R *__restrict__ Hm, const R *__restrict__ g, R *__restrict__ y, R *ys, R *q,
+                                             int lane) {
+    const long long ldh = m + 1;
+    for (int i = lane; i < k * NC; i += 64) ys[i] = g[i];
+    __syncthreads();
+    for (int i = k - 1; i >= 0; --i) {
+        if (lane == 0) {
+            R d[2] = {R(0), R(0)};
+            k_div<R, NC>(ys + i * NC, Hm + ((long long)i + i * ldh) * NC, d);
+            for (int c = 0; c < NC; ++c) q[c] = ys[i * NC + c] = d[c];
+        }
+        __syncthreads();
+        const R qr = q[0], qi = q[NC - 1];
+        for (int r = lane; r < i; r += 64) {
+            const R *a = Hm + ((long long)r + i * ldh) * NC;
+            if (NC == 1) {
+                ys[r] -= a[0] * qr;
+            } else {
+                ys[r * NC] -= a[0] * qr - a[NC - 1] * qi;
+                ys[r * NC + NC - 1] -= a[0] * qi + a[NC - 1] * qr;
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = lane; i < k * NC; i += 64) y[i] = ys[i];
 }
 
 template <typename R, int NC>

@@ -1,7 +1,8 @@
-// bsm_krylov.h -- what bsm_krylov.hip (the kernels), bsm_krylov.cpp (bsm_krylov_orth, bsm_gmres_*; include/bsm_rocm.h) and
-// tools/krylov_host_check.cpp share: the launch interface, and the small dense arithmetic of restarted GMRES -- Givens
-// rotations of one Hessenberg column, back substitution -- in plain C++, compiled for the host (bsm_debug_krylov_lsq_host, the
-// tests' and the sanitizer run's form) and for the one-wave kernels alike.
+// bsm_krylov.h -- what bsm_krylov.hip (the kernels of bsm_krylov_orth), bsm_krylov.cpp (bsm_krylov_orth; include/bsm_rocm.h),
+// the kernels of the GMRES solvers (bsm_gmres_multi.hip) and tools/krylov_host_check.cpp share: the launch interface of the
+// Gram-Schmidt pass, and the small dense arithmetic of restarted GMRES -- Givens rotations of one Hessenberg column, back
+// substitution -- in plain C++, compiled for the host (bsm_debug_krylov_lsq_host, the tests' and the sanitizer run's form) and
+// for the one-wave kernels of bsm_gmres_multi.hip alike.
 // (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
 //
 // Everything works on REAL components: an element is NC = 1 (real) or NC = 2 (re, im) values of R = float / double.
@@ -168,49 +169,12 @@ inline int krylov_grid(long long n, int es) {
 // part[c * G + wg] = the workgroup's share of V[:, c]^H w, c < k (G = krylov_grid)
 hipError_t launch_krylov_dot(int dtype, long long n, int k, const void *V, long long ldv, const void *w, void *part,
                              hipStream_t stream);
-// combine == false:  out = (in - V[:, 0:k] h) * scale,  h[c] = the sum of part[c * G + 0 .. G) in a fixed order (every
-//   workgroup forms the same h); hsum[0:k] += h (workgroup 0; may be null); scale: one real on the device (null: 1);
-//   nrmpart[wg] = the workgroup's share of ||out||^2 (may be null).  k == 0: out = in * scale and its norm.
-// combine == true:   out = V[:, 0:k] coef   (coef: k elements on the device)
-hipError_t launch_krylov_sweep(int dtype, bool combine, long long n, int k, const void *V, long long ldv, const void *in, void *out,
-                               const void *part, const void *coef, void *hsum, const void *scale, void *nrmpart, hipStream_t stream);
-// The jobs of the one sweep, by name (n elements of dtype; every pointer a device pointer):
-//   w = (w - V[:, 0:k] h),  h from the partials of launch_krylov_dot;  hsum[0:k] += h;  nrmpart = the shares of ||w||^2
-inline hipError_t krylov_orth_update(int dtype, long long n, int k, const void *V, long long ldv, void *w, const void *part,
-                                     void *hsum, void *nrmpart, hipStream_t st) {
-    return launch_krylov_sweep(dtype, false, n, k, V, ldv, w, w, part, nullptr, hsum, nullptr, nrmpart, st);
-}
-//   out = V[:, 0:k] y
-inline hipError_t krylov_combine(int dtype, long long n, int k, const void *V, long long ldv, const void *y, void *out, hipStream_t st) {
-    return launch_krylov_sweep(dtype, true, n, k, V, ldv, nullptr, out, nullptr, y, nullptr, nullptr, nullptr, st);
-}
-//   out = in * scale[0]  (scale: one real on the device)
-inline hipError_t krylov_scale_store(int dtype, long long n, const void *in, void *out, const void *scale, hipStream_t st) {
-    return launch_krylov_sweep(dtype, false, n, 0, nullptr, 1, in, out, nullptr, nullptr, nullptr, scale, nullptr, st);
-}
-//   out = in (out may be in);  nrmpart (may be null) = the shares of ||in||^2
-inline hipError_t krylov_copy_norm(int dtype, long long n, const void *in, void *out, void *nrmpart, hipStream_t st) {
-    return launch_krylov_sweep(dtype, false, n, 0, nullptr, 1, in, out, nullptr, nullptr, nullptr, nullptr, nrmpart, st);
-}
+// w -= V[:, 0:k] h,  h[c] = the sum of part[c * G + 0 .. G) in a fixed order (every workgroup forms the same h);
+// hsum[0:k] += h (workgroup 0; may be null);  nrmpart[wg] = the workgroup's share of ||w||^2 (may be null).  k == 0: the norm alone.
+hipError_t launch_krylov_update(int dtype, long long n, int k, const void *V, long long ldv, void *w, const void *part, void *hsum,
+                                void *nrmpart, hipStream_t stream);
 // nrm[0] = sqrt(sum of nrmpart[0 .. G)), one real, summed in a fixed order by one wave
 hipError_t launch_krylov_norm(int dtype, int G, const void *nrmpart, void *nrm, hipStream_t stream);
-// The small state of one cycle, device memory, restart m: see bsm_krylov.cpp (KrylovSmall).
-struct KrylovSmall {
-    void *Hm;       // m columns of (m + 1) elements: the rotated Hessenberg matrix (R)
-    void *cs, *sn;  // m reals, m elements
-    void *g;        // m + 1 elements
-    void *y;        // m elements
-    void *hsum;     // m elements: the column the two passes accumulate; zero between iterations
-    void *inv;      // one real: 1 / norm of the last start / hess (0 for a zero norm)
-    double *res;    // m + 1 doubles: res[j] = estimate after iteration j; res[m] = norm of the last start
-    void *nrmpart;  // kKrylovMaxGrid reals
-};
-// start of a cycle: beta = sqrt(sum nrmpart); g = beta e_1, hsum = 0, inv = 1 / beta (0 if beta == 0), res[m] = beta
-hipError_t launch_krylov_start(int dtype, int G, int m, const KrylovSmall &s, hipStream_t stream);
-// iteration j: the column (hsum[0 .. j], sqrt(sum nrmpart)) goes through krylov_hess_column; hsum is zeroed behind it
-hipError_t launch_krylov_hess(int dtype, int G, int m, int j, const KrylovSmall &s, hipStream_t stream);
-// y[0 .. k) = R^-1 g[0 .. k)
-hipError_t launch_krylov_trsolve(int dtype, int m, int k, const KrylovSmall &s, hipStream_t stream);
 #endif
 
 }  // namespace bsm

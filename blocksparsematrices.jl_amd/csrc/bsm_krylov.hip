@@ -1,6 +1,7 @@
-// bsm_krylov.hip -- the kernels of bsm_krylov_orth and bsm_gmres_solve (include/bsm_rocm.h): the orthogonalisation of
-// restarted GMRES and the small dense steps around it.  Kept out of the product kernel units like bsm_extract.hip and
-// bsm_invert.hip: the build id (Makefile BUILD_ID) names the kernels and schedule of the PRODUCTS.
+// bsm_krylov.hip -- the kernels of bsm_krylov_orth (include/bsm_rocm.h): one classical Gram-Schmidt pass on vectors of any
+// element alignment, for a caller's Krylov method.  (The GMRES solvers run the same pass on their padded workspace:
+// bsm_gmres_multi.hip.)  Kept out of the product kernel units like bsm_extract.hip and bsm_invert.hip: the build id (Makefile
+// BUILD_ID) names the kernels and schedule of the PRODUCTS.
 // (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
 //
 // One classical Gram-Schmidt pass  h = V^H w,  w -= V h,  ||w||  is two launches with a kernel boundary between them --
@@ -15,15 +16,12 @@
 //                 column, strided, then xor-shuffles: all workgroups get the same h, bit for bit), keeps h in LDS, and
 //                 walks its rows again: a tile of w in registers, the columns streamed past it, w -= V h, stored once,
 //                 |w|^2 summed on the way -> nrmpart[g].  Workgroup 0 also adds h to hsum.
-//                 The same kernel with combine = true is  u = V y  (coefficients read from y, accumulator starting at
-//                 0, no norm), and with k = 0 and a device scalar it is  V[:, j + 1] = w * inv_norm  (scale_store).
-// Loads and stores are 16 bytes per lane where the pointers allow it -- w, out and every column of V congruent modulo
+// Loads and stores are 16 bytes per lane where the pointers allow it -- w and every column of V congruent modulo
 // 16, i.e. (ldv * sizeof(T)) % 16 == 0 --: the vector groups start at the first 16-byte boundary of w, the elements in
 // front of it and behind the last whole group go element by element through the same code (a group that is not wholly
 // inside [0, n) is read and written under a per-element guard).  Otherwise every group is one element (VE = 1).
-// Every sum has a fixed order: the results are bit-identical from run to run.
-// The consumers of the per-workgroup norm shares -- norm_kernel (bsm_krylov_orth), start_kernel, hess_kernel (one wave
-// each) -- add them in a fixed order too.  hess_kernel and trsolve_kernel run the arithmetic of bsm_krylov.h.
+// Every sum has a fixed order: the results are bit-identical from run to run.  norm_kernel (one wave) adds the
+// per-workgroup norm shares in a fixed order too.
 #include "bsm_krylov.h"
 
 #include "../../include/bsm_rocm.h"
@@ -153,6 +151,9 @@ __global__ void __launch_bounds__(kThreads) dot_kernel(long long n, int k, const
     }
 }
 
+// (COMBINE, coef and scale serve no caller any more -- out = V coef and out = in * scale were steps of a solver that is gone.
+// They stay because the kernel without them compiles to other register counts; every launch has COMBINE = false, coef =
+// scale = null, in = out = w.)
 template <typename R, int NC, int VE, bool A16, bool COMBINE>
 __global__ void __launch_bounds__(kThreads)
     sweep_kernel(long long n, int k, const R *__restrict__ V, long long ldv, const R *in, R *out, const R *__restrict__ part,
@@ -246,55 +247,15 @@ template <typename R> __global__ void __launch_bounds__(64) norm_kernel(int G, c
     if (threadIdx.x == 0) nrm[0] = sqrt(a);
 }
 
-template <typename R, int NC>
-__global__ void __launch_bounds__(64) start_kernel(int G, int m, const R *__restrict__ nrmpart, R *__restrict__ g, R *__restrict__ hsum,
-                                                   R *__restrict__ inv, double *__restrict__ res) {
-    const int lane = threadIdx.x;
-    const R beta = sqrt(wave_total(nrmpart, G, lane));
-    for (int i = lane; i < (m + 1) * NC; i += 64) g[i] = i == 0 ? beta : R(0);
-    for (int i = lane; i < m * NC; i += 64) hsum[i] = R(0);
-    if (lane == 0) {
-        inv[0] = beta == R(0) ? R(0) : R(1) / beta;
-        res[m] = (double)beta;
-    }
-}
-
-template <typename R, int NC>
-__global__ void __launch_bounds__(64) hess_kernel(int G, int m, int j, const R *__restrict__ nrmpart, R *__restrict__ hsum,
-                                                  R *__restrict__ Hm, R *__restrict__ cs, R *__restrict__ sn, R *__restrict__ g,
-                                                  R *__restrict__ inv, double *__restrict__ res) {
-    __shared__ R col[(BSM_GMRES_MAX_RESTART + 1) * NC];
-    __shared__ R rot[BSM_GMRES_MAX_RESTART * 3];  // cs, sn of the stored rotations
-    __shared__ R gg[2 * NC];
-    const int lane = threadIdx.x;
-    const R hn = sqrt(wave_total(nrmpart, G, lane));
-    BSM_HESS_GATHER(R, NC, j, lane, hsum, cs, sn, g, col, rot, gg)
-    if (lane == 0) {
-        BSM_HESS_ROTATE(R, NC, j, hn, cs, sn, g, col, rot, gg, est)
-        res[j] = (double)est;
-        inv[0] = hn == R(0) ? R(0) : R(1) / hn;
-    }
-    BSM_HESS_SCATTER(R, NC, m, j, lane, Hm, col)
-}
-
-template <typename R, int NC>
-__global__ void __launch_bounds__(64) trsolve_kernel(int m, int k, const R *__restrict__ Hm, const R *__restrict__ g, R *__restrict__ y) {
-    __shared__ R ys[BSM_GMRES_MAX_RESTART * NC];
-    __shared__ R q[2];
-    trsolve_wave<R, NC>(m, k, Hm, g, y, ys, q, (int)threadIdx.x);
-}
-
-// whether 16-byte groups serve all of the pointers (null ones do not count), and where the first one starts
+// whether 16-byte groups serve w and the k columns of V, and where the first one starts
 struct Split {
     bool a16;
     long long lo, ng;
 };
-Split split_of(long long n, int es, long long ldv, int k, const void *V, const void *a, const void *b) {
+Split split_of(long long n, int es, long long ldv, int k, const void *V, const void *w) {
     const int ve = 16 / es;
-    const void *first = a ? a : b;
-    const uintptr_t f = (uintptr_t)first;
+    const uintptr_t f = (uintptr_t)w;
     bool ok = f % (uintptr_t)es == 0;
-    if (a && b) ok = ok && ((uintptr_t)a - (uintptr_t)b) % 16 == 0;
     if (k > 0) ok = ok && ((uintptr_t)V - f) % 16 == 0 && (k == 1 || (ldv * es) % 16 == 0);
     Split s;
     s.a16 = ok;
@@ -316,7 +277,7 @@ hipError_t launch_krylov_dot(int dtype, long long n, int k, const void *V, long 
     if (!is_vec_type(dtype) || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
     if (k == 0) return hipSuccess;
     const int es = elem_bytes(dtype);
-    const Split s = split_of(n, es, ldv, k, V, w, nullptr);
+    const Split s = split_of(n, es, ldv, k, V, w);
     const dim3 grid((unsigned)krylov_grid(n, es)), block(kThreads);
     with_types(dtype, [&](auto r, auto, auto nc) {
         using R = decltype(r);
@@ -332,25 +293,21 @@ hipError_t launch_krylov_dot(int dtype, long long n, int k, const void *V, long 
     return hipGetLastError();
 }
 
-hipError_t launch_krylov_sweep(int dtype, bool combine, long long n, int k, const void *V, long long ldv, const void *in, void *out,
-                               const void *part, const void *coef, void *hsum, const void *scale, void *nrmpart, hipStream_t stream) {
+hipError_t launch_krylov_update(int dtype, long long n, int k, const void *V, long long ldv, void *w, const void *part, void *hsum,
+                                void *nrmpart, hipStream_t stream) {
     if (!is_vec_type(dtype) || k < 0 || k > BSM_GMRES_MAX_RESTART || n < 0) return hipErrorInvalidValue;
     const int es = elem_bytes(dtype);
-    const Split s = split_of(n, es, ldv, k, V, combine ? nullptr : in, out);
+    const Split s = split_of(n, es, ldv, k, V, w);
     const dim3 grid((unsigned)krylov_grid(n, es)), block(kThreads);
     with_types(dtype, [&](auto r, auto, auto nc) {
         using R = decltype(r);
         constexpr int NC = decltype(nc)::value, VE = 16 / (int)(sizeof(R) * NC);
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)in, (R *)out, (const R *)part,
-                               (const R *)coef, (R *)hsum, (const R *)scale, (R *)nrmpart, s.lo, s.ng);
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w, (R *)w, (const R *)part, (const R *)nullptr,
+                               (R *)hsum, (const R *)nullptr, (R *)nrmpart, s.lo, s.ng);
         };
-        if (s.a16 && combine)
-            launch(sweep_kernel<R, NC, VE, true, true>);
-        else if (s.a16)
+        if (s.a16)
             launch(sweep_kernel<R, NC, VE, true, false>);
-        else if (combine)
-            launch(sweep_kernel<R, NC, 1, false, true>);
         else
             launch(sweep_kernel<R, NC, 1, false, false>);
     });
@@ -362,37 +319,6 @@ hipError_t launch_krylov_norm(int dtype, int G, const void *nrmpart, void *nrm, 
         hipLaunchKernelGGL(norm_kernel<float>, dim3(1), dim3(64), 0, stream, G, (const float *)nrmpart, (float *)nrm);
     else
         hipLaunchKernelGGL(norm_kernel<double>, dim3(1), dim3(64), 0, stream, G, (const double *)nrmpart, (double *)nrm);
-    return hipGetLastError();
-}
-
-hipError_t launch_krylov_start(int dtype, int G, int m, const KrylovSmall &s, hipStream_t stream) {
-    if (!is_vec_type(dtype)) return hipErrorInvalidValue;
-    with_types(dtype, [&](auto r, auto, auto nc) {
-        using R = decltype(r);
-        hipLaunchKernelGGL((start_kernel<R, decltype(nc)::value>), dim3(1), dim3(64), 0, stream, G, m, (const R *)s.nrmpart, (R *)s.g,
-                           (R *)s.hsum, (R *)s.inv, s.res);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_krylov_hess(int dtype, int G, int m, int j, const KrylovSmall &s, hipStream_t stream) {
-    if (!is_vec_type(dtype) || j < 0 || j >= m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
-    with_types(dtype, [&](auto r, auto, auto nc) {
-        using R = decltype(r);
-        hipLaunchKernelGGL((hess_kernel<R, decltype(nc)::value>), dim3(1), dim3(64), 0, stream, G, m, j, (const R *)s.nrmpart,
-                           (R *)s.hsum, (R *)s.Hm, (R *)s.cs, (R *)s.sn, (R *)s.g, (R *)s.inv, s.res);
-    });
-    return hipGetLastError();
-}
-
-hipError_t launch_krylov_trsolve(int dtype, int m, int k, const KrylovSmall &s, hipStream_t stream) {
-    if (!is_vec_type(dtype) || k < 0 || k > m || m > BSM_GMRES_MAX_RESTART) return hipErrorInvalidValue;
-    if (k == 0) return hipSuccess;
-    with_types(dtype, [&](auto r, auto, auto nc) {
-        using R = decltype(r);
-        hipLaunchKernelGGL((trsolve_kernel<R, decltype(nc)::value>), dim3(1), dim3(64), 0, stream, m, k, (const R *)s.Hm, (const R *)s.g,
-                           (R *)s.y);
-    });
     return hipGetLastError();
 }
 

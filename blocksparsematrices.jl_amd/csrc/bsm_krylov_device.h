@@ -1,9 +1,8 @@
-// bsm_krylov_device.h -- the device-side pieces of restarted GMRES that bsm_krylov.hip (one column: bsm_krylov_orth,
-// bsm_gmres_solve) and bsm_gmres_multi.hip (several columns in lockstep) share: the update of a Gram-Schmidt tile on the
-// elements of one 16-byte group, the fixed-order sum of a pass's partials, and the body of the one-wave back substitution
-// around the plain C++ of bsm_krylov.h.  The units differ in how they reach their vectors (guarded groups of any alignment
-// there, unguarded groups of padded workspace columns here) and in who decides.  The dot of a tile and the body of the hess
-// kernel are shared as statement macros at the end of this file.  For the kernel units only.
+// bsm_krylov_device.h -- the device-side pieces of a classical Gram-Schmidt pass that bsm_krylov.hip (bsm_krylov_orth: one
+// column of any alignment) and bsm_gmres_multi.hip (the GMRES solvers: padded workspace columns in lockstep) share: the
+// update of a tile on the elements of one 16-byte group, the fixed-order sum of a pass's partials, and the dot of a tile
+// as a statement macro at the end of this file.  The units differ in how they reach their vectors (guarded groups of any
+// alignment there, unguarded groups of padded workspace columns here).  For the kernel units only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,38 +52,8 @@ __device__ __forceinline__ bool gs_sum_partials(const R *__restrict__ part, int 
     return c < k && sl == 0;
 }
 
-// y[0 .. k) = R^-1 g[0 .. k) by one wave on the rotated Hessenberg matrix Hm (leading dimension m + 1): lane 0 divides, the
-// column update of every step is spread over the lanes.  ys (BSM_GMRES_MAX_RESTART * NC) and q (2) are LDS.
-template <typename R, int NC>
-__device__ __forceinline__ void trsolve_wave(int m, int k, const R *__restrict__ Hm, const R *__restrict__ g, R *__restrict__ y, R *ys, R *q,
-                                             int lane) {
-    const long long ldh = m + 1;
-    for (int i = lane; i < k * NC; i += 64) ys[i] = g[i];
-    __syncthreads();
-    for (int i = k - 1; i >= 0; --i) {
-        if (lane == 0) {
-            R d[2] = {R(0), R(0)};
-            k_div<R, NC>(ys + i * NC, Hm + ((long long)i + i * ldh) * NC, d);
-            for (int c = 0; c < NC; ++c) q[c] = ys[i * NC + c] = d[c];
-        }
-        __syncthreads();
-        const R qr = q[0], qi = q[NC - 1];
-        for (int r = lane; r < i; r += 64) {
-            const R *a = Hm + ((long long)r + i * ldh) * NC;
-            if (NC == 1) {
-                ys[r] -= a[0] * qr;
-            } else {
-                ys[r * NC] -= a[0] * qr - a[NC - 1] * qi;
-                ys[r * NC + NC - 1] -= a[0] * qi + a[NC - 1] * qr;
-            }
-        }
-        __syncthreads();
-    }
-    for (int i = lane; i < k * NC; i += 64) y[i] = ys[i];
-}
-
-// ---- statements both units expand in place.  Macros, not functions: as functions the dot tile and the hess body compiled to
-// other register counts in bsm_krylov.hip (docs/experiments_r25.md); an expansion is the very statements that unit had.
+// ---- a statement both units expand in place.  A macro, not a function: as a function the dot tile compiled to another
+// register count in bsm_krylov.hip (docs/experiments_r25.md); an expansion is the very statements that unit had.
 // s[0 .. NC) += conj(v) w over the VE elements of one group (v, w: arrays of reals; s: NC sums)
 #define BSM_GS_DOT(R, NC, VE, v, w, s)                                      \
     _Pragma("unroll") for (int e = 0; e < VE; ++e) {                        \
@@ -99,31 +68,5 @@ __device__ __forceinline__ void trsolve_wave(int m, int k, const R *__restrict__
             (s)[NC - 1] = fma(-vi, wr, (s)[NC - 1]);                        \
         }                                                                   \
     }
-// Iteration j of a cycle by one wave, in three pieces around what a unit does with the estimate (lane 0, between ROTATE and
-// SCATTER).  GATHER: the column hsum[0 .. j] (zeroed behind it), the stored rotations and g[j] into LDS -- col
-// ((BSM_GMRES_MAX_RESTART + 1) * NC), rot (BSM_GMRES_MAX_RESTART * 3), gg (2 * NC) --, then a barrier.
-#define BSM_HESS_GATHER(R, NC, j, lane, hsum, cs, sn, g, col, rot, gg)                        \
-    for (int i = lane; i < (j + 1) * NC; i += 64) {                                          \
-        col[i] = hsum[i];                                                                    \
-        hsum[i] = R(0);                                                                      \
-    }                                                                                        \
-    for (int i = lane; i < j; i += 64) rot[i] = cs[i];                                       \
-    for (int i = lane; i < j * NC; i += 64) rot[BSM_GMRES_MAX_RESTART + i] = sn[i];          \
-    if (lane < NC) gg[lane] = g[j * NC + lane];                                              \
-    __syncthreads();
-// ROTATE (lane 0): declares est = krylov_hess_column(..) and writes cs[j], sn[j], g[j], g[j + 1]
-#define BSM_HESS_ROTATE(R, NC, j, hn, cs, sn, g, col, rot, gg, est)                                                      \
-    const R est = krylov_hess_column<R, NC>(j, col, hn, rot, rot + BSM_GMRES_MAX_RESTART, gg - (long long)j * NC);      \
-    cs[j] = rot[j];                                                                                                     \
-    for (int q = 0; q < NC; ++q) {                                                                                      \
-        sn[j * NC + q] = rot[BSM_GMRES_MAX_RESTART + j * NC + q];                                                       \
-        g[j * NC + q] = gg[q];                                                                                          \
-        g[(j + 1) * NC + q] = gg[NC + q];                                                                               \
-    }
-// SCATTER: behind a barrier, column j of the rotated Hessenberg matrix Hm (leading dimension m + 1) from col
-#define BSM_HESS_SCATTER(R, NC, m, j, lane, Hm, col)                      \
-    __syncthreads();                                                     \
-    R *const dst = Hm + (long long)j * (m + 1) * NC;                      \
-    for (int i = lane; i < (j + 1) * NC; i += 64) dst[i] = col[i];
 
 }  // namespace bsm

@@ -1,5 +1,5 @@
 // bsm_lockstep.h -- the host side that the lockstep solver objects (bsm_cg.cpp: bsm_cg_*, bsm_bicgstab.cpp: bsm_bicgstab_*,
-// bsm_gmres_multi.cpp: bsm_gmres_multi_*; include/bsm_rocm.h) share: what a solver object holds whatever its method, the (handle, vector) pairings and the
+// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*; include/bsm_rocm.h) share: what a solver object holds whatever its method, the (handle, vector) pairings and the
 // multi-column product on the workspace, the refusals of create and solve, the one device allocation with its ring of
 // pinned record slots, the staging of host matrices, and the look-ahead loop that reads one record per iteration (lockstep_run; the multi-column GMRES, whose iterations come
 // in cycles, drives its own).  A
@@ -48,7 +48,7 @@ struct LockstepSolver {
     }
 };
 
-// how `H` is applied to vectors of type vt: 0 bsm_mul_multi, 1 bsm_mul_multi_cvec, -1 not at all (as bsm_gmres_create)
+// how `H` is applied to vectors of type vt: 0 bsm_mul_multi, 1 bsm_mul_multi_cvec, -1 not at all
 inline int pairing(const bsm_matrix_s *H, int vt) {
     const int dt = H->an.dtype;
     if (dt < 0 || dt > 5) return -1;
@@ -93,7 +93,7 @@ inline int lockstep_check_create(const void *A, int opA, const void *M, int opM,
     if (nrhs_max < 1 || nrhs_max > BSM_CG_MAX_RHS) return fail(BSM_ERR_INVALID, "nrhs_max outside 1 .. BSM_CG_MAX_RHS");
     return BSM_OK;
 }
-// The other refusals of create that do not depend on the method (`what`: "bsm_cg", "bsm_bicgstab", "bsm_gmres_multi"), and on success the fields
+// The other refusals of create that do not depend on the method (`what`: "bsm_cg", "bsm_bicgstab", "bsm_gmres_multi", "bsm_gmres"), and on success the fields
 // of S that follow from the arguments.  out has been checked and cleared by the caller.
 inline int lockstep_init(LockstepSolver *S, const char *what, bsm_matrix_s *A, int opA, bsm_matrix_s *M, int opM, int vdtype,
                          int32_t nrhs_max) {

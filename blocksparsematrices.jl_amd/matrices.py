@@ -1351,10 +1351,12 @@ class GmresInfo:
 
 
 class Gmres:
-    """Right-preconditioned restarted GMRES(restart) for A x = b, every step of it on the device (bsm_gmres_*).
+    """Right-preconditioned restarted GMRES(restart) for A x = b, every step of it on the device (bsm_gmres_*: the
+    solver of GmresMulti with one column behind its own info).
     A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g. block_jacobi(A,
     sets)), or None.  dtype: the type of b and x -- default A's vector type; a real A (and M) of the same precision
-    takes complex vectors.  The workspace (restart + 4 vectors) is allocated here, once; A and M are kept alive."""
+    takes complex vectors.  The workspace (restart + 3 vectors, restart + 4 with M) is allocated here, once; A and M are
+    kept alive."""
 
     def __init__(self, A, M=None, restart=30, dtype=None):
         base, op = _unwrap(A)

@@ -558,26 +558,29 @@ int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, int64_t ldv,
 
 /* bsm_gmres_*: right-preconditioned restarted GMRES(restart) for op(A) x = b with M ~ inv(op(A)) applied as opM(M).
  *   r = b - op(A) x,  beta = ||r||,  v_0 = r / beta;  iteration j: z = M v_j (skipped without M), w = op(A) z, two
- *   bsm_krylov_orth passes against v_0 .. v_j, one one-wave kernel that applies the j stored Givens rotations to the new
- *   Hessenberg column, forms rotation j and the residual estimate |g[j + 1]|, then v_{j+1} = w / ||w||.  At the end of a
- *   cycle, or at convergence after k iterations: back substitution R y = g[0:k] (one wave), u = V[:, 0:k] y, x += M u,
- *   and the next cycle starts from the TRUE residual b - op(A) x.  Right preconditioning: the estimate is the residual
- *   norm of the unpreconditioned system.
- * create: allocates everything a solve needs, once, on A's device: V as n x (restart + 2) (the basis, the residual in
- *   the spare column), two work vectors, the small arrays (Hessenberg factor, rotations, g, y, partial sums), a pinned
- *   host slot and an event per iteration of a cycle.  vdtype (BSM_F32 .. BSM_C128) is the type of b and x.  Each of A, M
- *   must have that vector type -- a mixed-storage handle counts with its double vectors -- or be a real, unmixed handle
- *   of the same precision under a complex vdtype, which is then driven through bsm_mul_cvec.  The handles must outlive
- *   the solver.  Refusals: null A or out, bad op / vdtype, a type pair not named above, op(A) not square, M of another
+ *   classical Gram-Schmidt passes against v_0 .. v_j (the pass of bsm_krylov_orth), one one-wave kernel that applies the j
+ *   stored Givens rotations to the new Hessenberg column, forms rotation j and the residual estimate |g[j + 1]|, then
+ *   v_{j+1} = w / ||w||.  At the end of a cycle, or at convergence after k iterations: back substitution R y = g[0:k] (one
+ *   wave), u = V[:, 0:k] y, x += M u, and the next cycle starts from the TRUE residual b - op(A) x.  Right preconditioning:
+ *   the estimate is the residual norm of the unpreconditioned system.
+ *   What runs is bsm_gmres_multi_* (below) with ONE column: the same solver object created with nrhs_max = 1, the same
+ *   kernels (csrc/bsm_gmres_multi.hip), every decision taken on the device, the host reading one record per start and
+ *   iteration from a ring of pinned slots, one step behind its enqueues.  These entry points only translate the structs:
+ *   b and x are a matrix of one column, info is filled from bsm_cg_info and the one bsm_cg_column.
+ * create: bsm_gmres_multi_create with nrhs_max = 1 -- one device allocation on A's device: restart + 3 vectors (the basis
+ *   v_0 .. v_restart, w, the solver's own x), restart + 4 with M (z), the small arrays of a cycle and the partial sums.
+ *   vdtype (BSM_F32 .. BSM_C128) is the type of b and x.  Each of A, M must have that vector type -- a mixed-storage
+ *   handle counts with its double vectors -- or be a real, unmixed handle of the same precision under a complex vdtype,
+ *   which is then driven through bsm_mul_cvec.  The handles must outlive the solver.  Refusals: null A or out, bad op / vdtype, a type pair not named above, op(A) not square, M of another
  *   order or on another device, restart < 1 or > BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID; a multi-device handle:
  *   BSM_ERR_UNSUPPORTED; an analysis-only handle: BSM_ERR_DEVICE.
- * solve: b, x of n elements.  Converged when the estimate is <= max(rtol * ||b||_2, atol).  maxiter bounds the
- *   iterations (products with A inside cycles).  use_x0 == 0: x is overwritten (NaN in the incoming x does not
- *   survive); else x is the initial guess.  b = 0 gives x = 0, 0 iterations, status 0.
- *   Look-ahead: after each iteration its estimate is copied to its pinned slot and an event is recorded; the host
- *   enqueues iteration j + 1 before it waits for the event of iteration j, so the device never idles on the check.  The
- *   answer uses exactly the k iterations up to the first one whose estimate met the tolerance; what was enqueued beyond
- *   it lands in workspace only: iterations, history and x do not depend on timing.
+ * solve: b, x of n elements, any element alignment: they are touched only by the start (b is read, x too with use_x0 != 0)
+ *   and by the final copy-out of the n entries of x.  Converged when the estimate is <= max(rtol * ||b||_2, atol).  maxiter
+ *   bounds the iterations (products with A inside cycles); values above INT32_MAX count as INT32_MAX (the counters on the
+ *   device are 32-bit).  use_x0 == 0: x is overwritten (NaN in the incoming x does not survive); else x is the initial
+ *   guess.  b = 0 gives x = 0, 0 iterations, status 0.
+ *   The answer uses exactly the k iterations up to the first one whose estimate met the tolerance; what the host enqueued
+ *   beyond it finds the column frozen and writes nothing: iterations, history and x do not depend on timing.
  *   history (may be NULL): history[i] = the absolute estimate after iteration i + 1, at most history_capacity entries.
  *   Two exits report status 0: an iteration whose ESTIMATE met the tolerance (the last history entry is then <= the
  *   tolerance and info.residual equals it), and the start of a cycle whose TRUE residual b - op(A) x already met it (the
@@ -589,9 +592,11 @@ int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, int64_t ldv,
  *   BSM_ERR_INVALID: null S / b / x / p / info with n > 0, x overlapping b, negative rtol / atol / maxiter /
  *   history_capacity, NaN tolerances, bad memspace, struct_size mismatch.
  * info.status: 0 converged; 1 maxiter reached; 2 a residual norm or estimate was not finite (NaN / Inf in b, x0 or the
- *   operator): x holds the last finished cycle.  The call returns BSM_OK for all three.
+ *   operator): x holds the last finished cycle.  The call returns BSM_OK for all three.  cycles = ceil(iterations / restart).
  *   a_products = iterations + one per cycle for the true residual (none for the first cycle with use_x0 == 0, where
- *   r = b); m_products (0 without M) = iterations + one per cycle that ran an iteration (x += M u).
+ *   r = b); m_products (0 without M) = iterations + one per cycle that ran an iteration (x += M u).  With use_x0 != 0 the
+ *   product op(A) x0 is enqueued before anything is known about b: a non-finite b then reports status 2 with
+ *   a_products = 1, not 0.
  *   workspace / workspace_bytes: the device address and size of the allocation made by create (fixed for its life). */
 typedef struct bsm_gmres_s *bsm_gmres_t;
 typedef struct {
@@ -793,9 +798,9 @@ int bsm_bicgstab_solve(struct bsm_bicgstab_s *S, int32_t nrhs, const void *B, in
 int bsm_bicgstab_destroy(struct bsm_bicgstab_s *S);
 
 /* bsm_gmres_multi_*: right-preconditioned restarted GMRES(restart) for op(A) X = B on nrhs = 1 .. BSM_CG_MAX_RHS right-hand
- * sides in lockstep, wholly on the device: the method for operators that need not be symmetric when the residual has to go
- * down monotonically and no breakdown is acceptable, on ONE multi-column product per iteration (bsm_mul_multi: the matrix
- * is streamed once per batch of columns).  Parameters, info and columns are those of bsm_cg_*.  Per column it is the method
+ * sides in lockstep, wholly on the device (bsm_gmres_* above is this solver with one column): the method for operators
+ * that need not be symmetric when the residual has to go down monotonically and no breakdown is acceptable, on ONE
+ * multi-column product per iteration (bsm_mul_multi: the matrix is streamed once per batch of columns).  Parameters, info and columns are those of bsm_cg_*.  Per column it is the method
  * bsm_gmres_solve documents -- two classical Gram-Schmidt passes, Givens rotations, the estimate |g[j + 1]|, x += opM(M) V y
  * at the end of a cycle, the next cycle from the TRUE residual --, so column c of a lockstep solve is, as a method, the
  * stand-alone solve of b_c.  All columns start together and restart together, every `restart` iterations: a column's cycle

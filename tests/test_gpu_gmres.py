@@ -282,6 +282,42 @@ def test_host_vectors_and_a_side_stream(torch_cuda, edge, dtype):
         e["S"].solve(torch.zeros(NOP, dtype=torch.complex128 if dtype == np.float64 else torch.float64, device="cuda"))
 
 
+@pytest.mark.parametrize("use_x0", [False, True], ids=["from-zero", "x0"])
+@pytest.mark.parametrize("dtype", EDGE, ids=EDGE_IDS)
+def test_vectors_one_element_off_alignment(torch_cuda, edge, dtype, use_x0):
+    """b and x as views that start ONE element into NaN-filled device buffers (no 16-byte alignment; torch allocations are
+    aligned far beyond that) with 5 guard elements behind them: the solve is the aligned solve -- status, iterations, x --
+    and not a byte of the guards changes.  b and x reach the workspace element by element (the start, the copy of x0) and
+    x leaves it the same way (the copy-out)."""
+    torch, e = torch_cuda, edge[np.dtype(dtype).name]
+    bd = dev(torch, e["b"])
+    assert bd.data_ptr() % 16 == 0
+    x0 = dev(torch, (e["x"] * dtype(1.001)).astype(dtype)) if use_x0 else None
+    if use_x0:
+        xr, ref = e["S"].solve(bd, x0=x0, rtol=e["rtol"], maxiter=100)
+        xr = xr.cpu().numpy()
+    else:
+        xr, ref = e["x"], e["info"]
+    es = bd.element_size()
+    bbuf = torch.full((NOP + 6,), float("nan"), dtype=bd.dtype, device="cuda")
+    xbuf = torch.full((NOP + 6,), float("nan"), dtype=bd.dtype, device="cuda")
+    bv, xv = bbuf[1:NOP + 1], xbuf[1:NOP + 1]
+    assert bv.data_ptr() % 16 == es % 16 and xv.data_ptr() % 16 == es % 16
+    bv.copy_(bd)
+    before = [t.cpu().numpy().tobytes() for t in (bbuf[:1], bbuf[NOP + 1:], xbuf[:1], xbuf[NOP + 1:])]
+    got, info = e["S"].solve(bv, x=xv, x0=x0, rtol=e["rtol"], maxiter=100)
+    assert got is xv
+    after = [t.cpu().numpy().tobytes() for t in (bbuf[:1], bbuf[NOP + 1:], xbuf[:1], xbuf[NOP + 1:])]
+    assert after == before, "a guard element around b or x was written"
+    assert len(before[1]) == 5 * es and bv.cpu().numpy().tobytes() == e["b"].tobytes()
+    assert (info.status, info.iterations) == (ref.status, ref.iterations) and info.status == 0
+    got = xv.cpu().numpy()
+    if e["same"]:
+        assert got.tobytes() == xr.tobytes()
+    else:
+        assert np.max(np.abs(got - xr)) <= TOL[np.dtype(dtype)] * np.max(np.abs(xr))
+
+
 # ---- operator and vector-type combinations ------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("op", ["T", "C"])
@@ -367,7 +403,7 @@ def test_one_solver_three_right_hand_sides(torch_cuda, edge):
         seen.add((info.workspace, info.workspace_bytes))
     assert len(seen) == 1 and e["info"].workspace != 0
     assert (e["info"].workspace, e["info"].workspace_bytes) in seen
-    # V (restart + 2 columns) and two work vectors at least
+    # with M: the basis v_0 .. v_restart, w, x and z
     assert e["info"].workspace_bytes >= (RESTART + 4) * NOP * 8
 
 
