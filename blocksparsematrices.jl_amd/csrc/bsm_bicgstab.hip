@@ -4,7 +4,7 @@
 // (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
 //
 // Every kernel is a pure stream over n x K elements with a reduction, in the conventions of bsm_cg.hip (whose helpers it
-// shares through bsm_cg_device.h): 256-thread workgroups, the launch (krylov_grid, K), tiles of 256 threads x kU 16-byte
+// shares through bsm_lockstep_device.h): 256-thread workgroups, the launch (krylov_grid, K), tiles of 256 threads x kU 16-byte
 // groups, one partial per workgroup and column.  The inner product is always conjugated: <u, v> = sum conj(u_i) v_i.
 //   start_kernel   r = rhat = B - q (B element by element under a guard: any ldb, any alignment; q = A x0 or none), the
 //                  shares of ||b||^2 and ||r||^2 (= rho at the start).
@@ -24,55 +24,17 @@
 #include "bsm_bicgstab.h"
 
 #include "../../include/bsm_rocm.h"
-#include "bsm_cg_device.h"
+#include "bsm_lockstep_device.h"
 
 namespace bsm {
 namespace {
-
-// y += a x on the elements of one 16-byte group
-template <typename R, int NC> __device__ __forceinline__ void axpy16(R ar, R ai, const Vec16<R> &x, Vec16<R> &y) {
-    constexpr int VE = 16 / (int)sizeof(R) / NC;
-#pragma unroll
-    for (int e = 0; e < VE; ++e) {
-        if (NC == 1) {
-            y.r[e] = fma(ar, x.r[e], y.r[e]);
-        } else {
-            const int i0 = e * NC, i1 = e * NC + NC - 1;
-            const R xr = x.r[i0], xi = x.r[i1];
-            y.r[i0] = fma(-ai, xi, fma(ar, xr, y.r[i0]));
-            y.r[i1] = fma(ai, xr, fma(ar, xi, y.r[i1]));
-        }
-    }
-}
-// s[0] += ||v||^2 over one 16-byte group
-template <typename R> __device__ __forceinline__ void norm16(const Vec16<R> &v, R &s) {
-#pragma unroll
-    for (int k = 0; k < 16 / (int)sizeof(R); ++k) s = fma(v.r[k], v.r[k], s);
-}
-// s[0 .. NC) += conj(u) v over one 16-byte group
-template <typename R, int NC> __device__ __forceinline__ void dot16(const Vec16<R> &u, const Vec16<R> &v, R *s) {
-    constexpr int VE = 16 / (int)sizeof(R) / NC;
-#pragma unroll
-    for (int e = 0; e < VE; ++e) {
-        if (NC == 1) {
-            s[0] = fma(u.r[e], v.r[e], s[0]);
-        } else {
-            const R ur = u.r[e * NC], ui = u.r[e * NC + NC - 1], vr = v.r[e * NC], vi = v.r[e * NC + NC - 1];
-            s[0] = fma(ur, vr, s[0]);
-            s[0] = fma(ui, vi, s[0]);
-            s[NC - 1] = fma(ur, vi, s[NC - 1]);
-            s[NC - 1] = fma(-ui, vr, s[NC - 1]);
-        }
-    }
-}
 
 // First half of an iteration on a column running in slot `in`: rho from the slot, sigma from its partials.  False: the
 // breakdown rho == 0 or sigma == 0 (no division is executed); else al = rho / sigma.
 template <typename R, int NC>
 __device__ __forceinline__ bool bicg_alpha(const R *__restrict__ psig, const CgSlot &in, int c, int G, int lane, R (&rho)[2], R (&al)[2]) {
     R sig[2] = {R(0), R(0)};
-#pragma unroll
-    for (int k = 0; k < NC; ++k) sig[k] = wave_total(psig + (long long)c * G * NC + k, G, NC, lane);
+    column_total<R, NC>(psig, c, G, lane, sig);
     rho[0] = (R)in.rz[c][0];
     rho[1] = (R)in.rz[c][1];
     al[0] = al[1] = R(0);
@@ -91,8 +53,7 @@ __device__ __forceinline__ int bicg_omega(const R *__restrict__ pss, const R *__
     if (!isfinite(sn)) return 2;
     if ((double)sn <= tol) return 0;
     R ts[2] = {R(0), R(0)};
-#pragma unroll
-    for (int k = 0; k < NC; ++k) ts[k] = wave_total(pts + (long long)c * G * NC + k, G, NC, lane);
+    column_total<R, NC>(pts, c, G, lane, ts);
     const R tt = wave_total(ptt + (long long)c * G, G, 1, lane);
     if (tt == R(0) || is_zero<R, NC>(ts)) return 3;
     om[0] = ts[0] / tt;
@@ -108,7 +69,7 @@ template <typename R, int NC>
 __global__ void __launch_bounds__(kThreads)
     start_kernel(long long n, long long ld, long long ng, long long ldb, const R *__restrict__ B, const R *__restrict__ q, R *__restrict__ r,
                  R *__restrict__ rhat, R *__restrict__ pbb, R *__restrict__ pnn) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     __shared__ R red[4][2];
     const int t = threadIdx.x, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     const R *Bc = B + (long long)c * ldb * NC;
@@ -121,19 +82,9 @@ __global__ void __launch_bounds__(kThreads)
         for (int u = 0; u < kU; ++u) {
             const long long g = tile + (long long)u * kThreads + t;
             if (g >= g1) continue;
-            Vec16<R> v;
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                const long long row = g * VE + e;
-#pragma unroll
-                for (int k = 0; k < NC; ++k) v.r[e * NC + k] = row < n ? Bc[row * NC + k] : R(0);
-            }
+            Vec16<R> v = load16_guarded<R, NC>(Bc, g, n);
             norm16(v, s[0]);
-            if (q) {
-                const Vec16<R> w = load16(q + off + g * GC);
-#pragma unroll
-                for (int k = 0; k < GC; ++k) v.r[k] -= w.r[k];
-            }
+            if (q) sub16(v, load16(q + off + g * GC));
             norm16(v, s[1]);
             store16(r + off + g * GC, v);
             store16(rhat + off + g * GC, v);
@@ -166,8 +117,7 @@ __global__ void __launch_bounds__(kThreads) dot_kernel(long long ld, long long n
                 a[i] = load16(u + off + g * GC);
                 b[i] = load16(v + off + g * GC);
             } else {
-#pragma unroll
-                for (int k = 0; k < GC; ++k) a[i].r[k] = b[i].r[k] = R(0);
+                a[i] = b[i] = zero16<R>();
             }
         }
 #pragma unroll
@@ -294,14 +244,7 @@ __global__ void __launch_bounds__(kThreads)
         const int so = in.status[c];
         const bool broke = so == kCgRun && !bicg_alpha<R, NC>(psig, in, c, G, lane, rho, al);
         if (so != kCgRun || broke) {  // frozen before this iteration, or at its top: the state moves to the other slot
-            if (writer) {
-                out.rz[c][0] = in.rz[c][0];
-                out.rz[c][1] = in.rz[c][1];
-                out.rn[c] = in.rn[c];
-                out.status[c] = broke ? 3 : so;
-                out.done[c] = in.done[c];
-                st->rec.status[c] = broke ? 3 : so;
-            }
+            if (writer) carry_frozen(in, out, st->rec, c, broke ? 3 : so);
             return;
         }
         half = bicg_omega<R, NC>(pss, pts, ptt, st->tol[c], c, G, lane, sn, om);
@@ -315,14 +258,12 @@ __global__ void __launch_bounds__(kThreads)
         rn = sqrt(nn);
         if (first) {
             rhn[0] = nn;  // <rhat, r> with rhat = r
-            bn = sqrt(wave_total(pbb + (long long)c * G, G, 1, lane));
-            tol = fmax(rtol * (double)bn, atol);
+            tol = first_tol(pbb + (long long)c * G, G, lane, rtol, atol, bn);
         } else {
-#pragma unroll
-            for (int k = 0; k < NC; ++k) rhn[k] = wave_total(prho + (long long)c * G * NC + k, G, NC, lane);
+            column_total<R, NC>(prho, c, G, lane, rhn);
             tol = st->tol[c];
         }
-        status = !isfinite(rn) ? 2 : ((double)rn <= tol ? 0 : kCgRun);
+        status = decide(rn, tol);
     }
     if (writer) {
         // (a column that ended at the half step never reads rho again)

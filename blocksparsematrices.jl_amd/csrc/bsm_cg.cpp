@@ -3,7 +3,7 @@
 // vector work through the kernels of bsm_cg.hip.  Every decision of the method is taken on the device; the host only
 // enqueues, and reads one record per iteration from a pinned slot, one iteration late (the look-ahead), to know when to
 // stop enqueuing.  What does not depend on the method -- the refusals, the allocation, the staging of host matrices, that
-// loop -- is bsm_lockstep.h, shared with bsm_bicgstab.cpp.
+// loop, create but for the layout of the workspace -- is bsm_lockstep.h, shared with bsm_bicgstab.cpp and bsm_gmres_multi.cpp.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
@@ -25,65 +25,28 @@ struct bsm_cg_s : LockstepSolver {
 
 extern "C" int bsm_cg_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, int32_t method,
                              struct bsm_cg_s **out) {
-    if (!out) return fail(BSM_ERR_INVALID, "out is null");
-    *out = nullptr;
     const bool method_ok = method == BSM_CG_METHOD_CG || method == BSM_CG_METHOD_COCG;
-    int rc = lockstep_check_create(A, opA, M, opM, vdtype, nrhs_max, method_ok ? nullptr : "method must be BSM_CG_METHOD_CG or BSM_CG_METHOD_COCG");
-    if (rc != BSM_OK) return rc;
-    bsm_cg_s *S = new (std::nothrow) bsm_cg_s;
-    if (!S) return fail(BSM_ERR_ALLOC, "out of host memory");
-    if ((rc = lockstep_init(S, "bsm_cg", A, opA, M, opM, vdtype, nrhs_max)) != BSM_OK) {
-        delete S;
-        return rc;
-    }
-    S->conj = method == BSM_CG_METHOD_CG;
-    const int64_t es = elem_bytes(vdtype), rs = real_bytes(vdtype), K = nrhs_max;
-    Carve cv;
-    const int64_t vec = S->ld * es * K;
-    const int64_t oX = cv.take(vec), oR = cv.take(vec), oP = cv.take(vec), oQ = cv.take(vec), oZ = M ? cv.take(vec) : 0;
-    const int64_t opq = cv.take(K * S->G * es), orz = cv.take(K * S->G * es), onn = cv.take(K * S->G * rs), obb = cv.take(K * S->G * rs);
-    const int64_t ost = cv.take((int64_t)sizeof(CgState));
-    if ((rc = lockstep_alloc(S, cv.off, "CG")) != BSM_OK) {
-        delete S;
-        return rc;
-    }
-    char *b = (char *)S->ws;
-    S->X = b + oX, S->R = b + oR, S->P = b + oP, S->Q = b + oQ, S->Z = M ? b + oZ : nullptr;
-    S->ppq = b + opq, S->prz = b + orz, S->pnn = b + onn, S->pbb = b + obb;
-    S->state = (CgState *)(b + ost);
-    *out = S;
-    return BSM_OK;
+    return lockstep_create("bsm_cg", "CG", A, opA, M, opM, vdtype, nrhs_max,
+                           method_ok ? nullptr : "method must be BSM_CG_METHOD_CG or BSM_CG_METHOD_COCG", out, [&](bsm_cg_s &S, Carve &cv) {
+                               S.conj = method == BSM_CG_METHOD_CG;
+                               const int64_t es = elem_bytes(vdtype), rs = real_bytes(vdtype), K = nrhs_max, vec = S.ld * es * K;
+                               S.X = cv.take(vec), S.R = cv.take(vec), S.P = cv.take(vec), S.Q = cv.take(vec), S.Z = M ? cv.take(vec) : nullptr;
+                               S.ppq = cv.take(K * S.G * es), S.prz = cv.take(K * S.G * es), S.pnn = cv.take(K * S.G * rs), S.pbb = cv.take(K * S.G * rs);
+                               S.state = (CgState *)cv.take((int64_t)sizeof(CgState));
+                           });
 }
 
-extern "C" int bsm_cg_destroy(struct bsm_cg_s *S) {
-    if (!S) return BSM_OK;
-    lockstep_destroy(S);
-    delete S;
-    return BSM_OK;
-}
+extern "C" int bsm_cg_destroy(struct bsm_cg_s *S) { return lockstep_destroy(S); }
 
 namespace {
 
 // the solve on device matrices B, X (arguments checked)
 int solve_device(bsm_cg_s *S, int nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_cg_params &p, bsm_cg_info &info,
                  bsm_cg_column *cols, double *history, hipStream_t st) {
-    const int vt = S->vt, es = elem_bytes(vt);
+    const int vt = S->vt;
     const CgDims d{vt, S->n, S->ld, S->G, nrhs, S->conj};
-    const size_t vec_bytes = (size_t)S->ld * es * nrhs;
     char *const Zv = S->M ? S->Z : S->R;          // z = r without M
     void *const prz_fused = S->M ? nullptr : S->prz;  // without M, cg_start / cg_update leave the shares of <r, r> themselves
-    hipError_t e = hipSuccess;
-    int rc = BSM_OK;
-#define HIP_TRY(call)                                   \
-    do {                                                \
-        e = (call);                                     \
-        if (e != hipSuccess) return hip_fail(e, #call); \
-    } while (0)
-#define RC_TRY(call)                 \
-    do {                             \
-        rc = (call);                 \
-        if (rc != BSM_OK) return rc; \
-    } while (0)
     // z = M r and the shares of <r, z> (with M only)
     auto precondition = [&](int par) -> int {
         if (!S->M) return BSM_OK;
@@ -93,16 +56,10 @@ int solve_device(bsm_cg_s *S, int nrhs, const void *B, int64_t ldb, void *X, int
         return q == hipSuccess ? BSM_OK : hip_fail(q, "launch_cg_dot");
     };
     // ---- the start: x, r, the norms, p = z, the first decision
-    if (p.use_x0) {
-        HIP_TRY(launch_cg_copy(d, true, X, ldx, S->X, st));
-        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, S->X, S->Q, st));
-    } else {
-        HIP_TRY(hipMemsetAsync(S->X, 0, vec_bytes, st));
-    }
+    RC_TRY(lockstep_start_x(S, d, p.use_x0, X, ldx, S->X, S->Q, st));
     HIP_TRY(launch_cg_start(d, B, ldb, p.use_x0 ? S->Q : nullptr, S->R, S->pbb, S->pnn, prz_fused, S->state, st));
     RC_TRY(precondition(-1));
     HIP_TRY(launch_cg_dir(d, true, 0, 0, p.rtol, p.atol, S->pbb, S->pnn, S->prz, Zv, S->P, S->state, st));
-    HIP_TRY(lockstep_post(S, 0, st));
     // ---- the iterations, their records read one behind the enqueue
     RC_TRY(lockstep_run(S, d, X, ldx, S->X, p, info, cols, history, st, [&](int64_t j) -> int {
         const int par = (int)(j & 1);
@@ -115,8 +72,6 @@ int solve_device(bsm_cg_s *S, int nrhs, const void *B, int64_t ldb, void *X, int
     }));
     info.a_products = info.iterations + (p.use_x0 ? 1 : 0);
     info.m_products = S->M ? info.iterations + 1 : 0;
-#undef HIP_TRY
-#undef RC_TRY
     return BSM_OK;
 }
 

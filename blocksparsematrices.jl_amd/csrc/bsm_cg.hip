@@ -5,8 +5,10 @@
 //
 // Every kernel is a pure stream over n x K elements with a reduction, in the conventions of bsm_krylov.hip: 256-thread
 // workgroups, the krylov_grid(n, es) row ranges walked in tiles of 256 threads x kU 16-byte groups, xor-shuffles for the
-// wave sum, one LDS slot per wave, one partial per workgroup (the helpers: bsm_cg_device.h, shared with bsm_bicgstab.hip).  The launch is (krylov_grid, K): a workgroup owns one row
-// range of ONE column, so K columns fill the compute units where one column of n = 100 000 gives 98 workgroups.
+// wave sum, one LDS slot per wave, one partial per workgroup (the helpers, from the 16-byte access to the decision of a
+// column: bsm_lockstep_device.h, shared with bsm_bicgstab.hip and bsm_gmres_multi.hip).  The launch is (krylov_grid, K): a
+// workgroup owns one row range of ONE column, so K columns fill the compute units where one column of n = 100 000 gives 98
+// workgroups.
 //   start_kernel   r = B - q (B element by element under a guard: any ldb, any alignment; q = A x0 or none), the shares of
 //                  ||b||^2, ||r||^2 and, without M, of <r, r> in the method's form.
 //   copy_kernel    the strided, guarded copy between the caller's X and the workspace X (both directions).
@@ -23,7 +25,7 @@
 #include "bsm_cg.h"
 
 #include "../../include/bsm_rocm.h"
-#include "bsm_cg_device.h"
+#include "bsm_lockstep_device.h"
 
 namespace bsm {
 namespace {
@@ -32,7 +34,7 @@ template <typename R, int NC, bool RR>
 __global__ void __launch_bounds__(kThreads)
     start_kernel(long long n, long long ld, long long ng, long long ldb, R sgn, const R *__restrict__ B, const R *__restrict__ q,
                  R *__restrict__ r, R *__restrict__ pbb, R *__restrict__ pnn, R *__restrict__ prz, CgState *__restrict__ st) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     __shared__ R red[4][4];
     const int t = threadIdx.x, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     const R *Bc = B + (long long)c * ldb * NC;
@@ -46,36 +48,11 @@ __global__ void __launch_bounds__(kThreads)
         for (int u = 0; u < kU; ++u) {
             const long long g = tile + (long long)u * kThreads + t;
             if (g >= g1) continue;
-            Vec16<R> v;
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                const long long row = g * VE + e;
-#pragma unroll
-                for (int k = 0; k < NC; ++k) v.r[e * NC + k] = row < n ? Bc[row * NC + k] : R(0);
-            }
-#pragma unroll
-            for (int k = 0; k < GC; ++k) s[0] = fma(v.r[k], v.r[k], s[0]);
-            if (qc) {
-                const Vec16<R> w = load16(qc + g * GC);
-#pragma unroll
-                for (int k = 0; k < GC; ++k) v.r[k] -= w.r[k];
-            }
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                const R a = v.r[e * NC], b = v.r[e * NC + NC - 1];
-                if (NC == 1) {
-                    s[1] = fma(a, a, s[1]);
-                } else {
-                    s[1] = fma(a, a, s[1]);
-                    s[1] = fma(b, b, s[1]);
-                    if (RR) {
-                        s[2] = fma(a, a, s[2]);
-                        s[2] = fma(sgn * b, b, s[2]);
-                        s[3] = fma(a, b, s[3]);
-                        s[3] = fma(-sgn * b, a, s[3]);
-                    }
-                }
-            }
+            Vec16<R> v = load16_guarded<R, NC>(Bc, g, n);
+            norm16(v, s[0]);
+            if (qc) sub16(v, load16(qc + g * GC));
+            norm16(v, s[1]);
+            if (NC == 2 && RR) form16(v, sgn, s + 2);
             store16(rc + g * GC, v);
         }
     }
@@ -102,27 +79,25 @@ __global__ void __launch_bounds__(kThreads) copy_kernel(long long n, long long l
     long long g0, g1;
     wg_range(ng, G, wg, g0, g1);
     for (long long g = g0 + t; g < g1; g += kThreads) {
-        Vec16<R> v;
-        if (!TO_WS) v = load16(wc + g * GC);
+        if (TO_WS) {
+            store16(wc + g * GC, load16_guarded<R, NC>(Xc, g, n));
+            continue;
+        }
+        const Vec16<R> v = load16(wc + g * GC);
 #pragma unroll
         for (int e = 0; e < VE; ++e) {
             const long long row = g * VE + e;
 #pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                if (TO_WS)
-                    v.r[e * NC + k] = row < n ? Xc[row * NC + k] : R(0);
-                else if (row < n)
-                    Xc[row * NC + k] = v.r[e * NC + k];
-            }
+            for (int k = 0; k < NC; ++k)
+                if (row < n) Xc[row * NC + k] = v.r[e * NC + k];
         }
-        if (TO_WS) store16(wc + g * GC, v);
     }
 }
 
 template <typename R, int NC>
 __global__ void __launch_bounds__(kThreads) dot_kernel(long long ld, long long ng, R sgn, int par, const R *__restrict__ u,
                                                        const R *__restrict__ v, R *__restrict__ part, const CgState *__restrict__ st) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     __shared__ R red[4][NC];
     const int t = threadIdx.x, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     if (par >= 0 && st->slot[par].status[c] != kCgRun) return;
@@ -141,24 +116,11 @@ __global__ void __launch_bounds__(kThreads) dot_kernel(long long ld, long long n
                 a[i] = load16(uc + g * GC);
                 b[i] = load16(vc + g * GC);
             } else {
-#pragma unroll
-                for (int k = 0; k < GC; ++k) a[i].r[k] = b[i].r[k] = R(0);
+                a[i] = b[i] = zero16<R>();
             }
         }
 #pragma unroll
-        for (int i = 0; i < kU * 2; ++i)
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                if (NC == 1) {
-                    s[0] = fma(a[i].r[e], b[i].r[e], s[0]);
-                } else {
-                    const R ur = a[i].r[e * NC], ui = a[i].r[e * NC + NC - 1], vr = b[i].r[e * NC], vi = b[i].r[e * NC + NC - 1];
-                    s[0] = fma(ur, vr, s[0]);
-                    s[0] = fma(sgn * ui, vi, s[0]);
-                    s[NC - 1] = fma(ur, vi, s[NC - 1]);
-                    s[NC - 1] = fma(-sgn * ui, vr, s[NC - 1]);
-                }
-            }
+        for (int i = 0; i < kU * 2; ++i) dot16<R, NC>(a[i], b[i], sgn, s);
     }
     block_sum<R, NC>(s, red);
     if (t == 0) {
@@ -171,11 +133,14 @@ template <typename R, int NC, bool RR>
 __global__ void __launch_bounds__(kThreads)
     update_kernel(long long ld, long long ng, R sgn, int par, const R *__restrict__ ppq, const R *__restrict__ p, const R *__restrict__ q,
                   R *__restrict__ x, R *__restrict__ r, R *__restrict__ pnn, R *__restrict__ prz, CgState *__restrict__ st) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     __shared__ R red[4][3];
     const int t = threadIdx.x, lane = t & 63, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     if (st->slot[par].status[c] != kCgRun) return;
     R pq[2] = {R(0), R(0)}, rz[2], al[2] = {R(0), R(0)};
+    // (not column_total: behind it the compiler contracts the a c + b e of k_div the other way round in the complex float
+    // instantiations -- which product is rounded before the fma -- and alpha of COCG changes in its last bit,
+    // docs/experiments_r27.md)
 #pragma unroll
     for (int k = 0; k < NC; ++k) pq[k] = wave_total(ppq + (long long)c * G * NC + k, G, NC, lane);
     rz[0] = (R)st->slot[par].rz[c][0];
@@ -206,32 +171,10 @@ __global__ void __launch_bounds__(kThreads)
         for (int u = 0; u < kU; ++u) {
             const long long g = tile + (long long)u * kThreads + t;
             if (g >= g1) continue;
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                if (NC == 1) {
-                    xv[u].r[e] = fma(ar, pv[u].r[e], xv[u].r[e]);
-                    const R a = fma(-ar, qv[u].r[e], rv[u].r[e]);
-                    rv[u].r[e] = a;
-                    s[0] = fma(a, a, s[0]);
-                } else {
-                    const int i0 = e * NC, i1 = e * NC + NC - 1;
-                    const R pr = pv[u].r[i0], pi = pv[u].r[i1], qr = qv[u].r[i0], qi = qv[u].r[i1];
-                    xv[u].r[i0] = fma(-ai, pi, fma(ar, pr, xv[u].r[i0]));
-                    xv[u].r[i1] = fma(ai, pr, fma(ar, pi, xv[u].r[i1]));
-                    const R a = fma(ai, qi, fma(-ar, qr, rv[u].r[i0]));
-                    const R b = fma(-ai, qr, fma(-ar, qi, rv[u].r[i1]));
-                    rv[u].r[i0] = a;
-                    rv[u].r[i1] = b;
-                    s[0] = fma(a, a, s[0]);
-                    s[0] = fma(b, b, s[0]);
-                    if (RR) {
-                        s[1] = fma(a, a, s[1]);
-                        s[1] = fma(sgn * b, b, s[1]);
-                        s[2] = fma(a, b, s[2]);
-                        s[2] = fma(-sgn * b, a, s[2]);
-                    }
-                }
-            }
+            axpy16<R, NC>(ar, ai, pv[u], xv[u]);
+            axpy16<R, NC>(-ar, -ai, qv[u], rv[u]);
+            norm16(rv[u], s[0]);
+            if (NC == 2 && RR) form16(rv[u], sgn, s + 1);
             store16(x + off + g * GC, xv[u]);
             store16(r + off + g * GC, rv[u]);
         }
@@ -250,7 +193,7 @@ template <typename R, int NC>
 __global__ void __launch_bounds__(kThreads)
     dir_kernel(long long ld, long long ng, int first, int par, long long it, double rtol, double atol, const R *__restrict__ pbb,
                const R *__restrict__ pnn, const R *__restrict__ prz, const R *__restrict__ z, R *__restrict__ p, CgState *__restrict__ st) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     const int t = threadIdx.x, lane = t & 63, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     const bool writer = wg == 0 && t == 0;
     const CgSlot &in = st->slot[par];
@@ -259,30 +202,15 @@ __global__ void __launch_bounds__(kThreads)
         const int so = in.status[c];
         const bool broke = so == kCgRun && st->brk[c] != 0;
         if (so != kCgRun || broke) {  // frozen before this iteration, or by its cg_update: the state moves to the other slot
-            if (writer) {
-                out.rz[c][0] = in.rz[c][0];
-                out.rz[c][1] = in.rz[c][1];
-                out.rn[c] = in.rn[c];
-                out.status[c] = broke ? 3 : so;
-                out.done[c] = in.done[c];
-                st->rec.status[c] = broke ? 3 : so;
-            }
+            if (writer) carry_frozen(in, out, st->rec, c, broke ? 3 : so);
             return;
         }
     }
     const R rn = sqrt(wave_total(pnn + (long long)c * G, G, 1, lane));
-    R rzn[2] = {R(0), R(0)};
-#pragma unroll
-    for (int k = 0; k < NC; ++k) rzn[k] = wave_total(prz + (long long)c * G * NC + k, G, NC, lane);
-    double tol;
-    R bn = R(0);
-    if (first) {
-        bn = sqrt(wave_total(pbb + (long long)c * G, G, 1, lane));
-        tol = fmax(rtol * (double)bn, atol);
-    } else {
-        tol = st->tol[c];
-    }
-    const int status = !isfinite(rn) ? 2 : ((double)rn <= tol ? 0 : kCgRun);
+    R rzn[2] = {R(0), R(0)}, bn = R(0);
+    column_total<R, NC>(prz, c, G, lane, rzn);
+    const double tol = first ? first_tol(pbb + (long long)c * G, G, lane, rtol, atol, bn) : st->tol[c];
+    const int status = decide(rn, tol);
     if (writer) {
         out.rz[c][0] = (double)rzn[0];
         out.rz[c][1] = (double)rzn[1];
@@ -321,19 +249,7 @@ __global__ void __launch_bounds__(kThreads)
         for (int u = 0; u < kU; ++u) {
             const long long g = tile + (long long)u * kThreads + t;
             if (g >= g1) continue;
-            if (!first) {
-#pragma unroll
-                for (int e = 0; e < VE; ++e) {
-                    if (NC == 1) {
-                        zv[u].r[e] = fma(br, pv[u].r[e], zv[u].r[e]);
-                    } else {
-                        const int i0 = e * NC, i1 = e * NC + NC - 1;
-                        const R pr = pv[u].r[i0], pi = pv[u].r[i1];
-                        zv[u].r[i0] = fma(-bi, pi, fma(br, pr, zv[u].r[i0]));
-                        zv[u].r[i1] = fma(bi, pr, fma(br, pi, zv[u].r[i1]));
-                    }
-                }
-            }
+            if (!first) axpy16<R, NC>(br, bi, pv[u], zv[u]);
             store16(p + off + g * GC, zv[u]);
         }
     }

@@ -3,9 +3,9 @@
 // bsm_cg.hip: the build id (Makefile BUILD_ID) names the kernels and schedule of the PRODUCTS.
 // (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
 //
-// The conventions are those of bsm_cg.hip / bsm_bicgstab.hip, whose helpers this unit shares through bsm_cg_device.h; what it
-// shares with the Gram-Schmidt pass of bsm_krylov.hip (bsm_krylov_orth) is bsm_krylov_device.h (the dot and the update of a
-// tile, the sum of the partials); the rotations and the division are the plain C++ of bsm_krylov.h:
+// The conventions are those of bsm_cg.hip / bsm_bicgstab.hip, whose helpers this unit shares through bsm_lockstep_device.h;
+// what it shares with the Gram-Schmidt pass of bsm_krylov.hip (bsm_krylov_orth) is bsm_krylov_device.h (the dot and the update
+// of a group, the sum of the partials); the rotations and the division are the plain C++ of bsm_krylov.h:
 // 256-thread workgroups, the launch (krylov_grid, K), tiles of 256 threads x kU 16-byte groups, one partial per workgroup,
 // basis vector and column, unguarded 16-byte accesses on workspace vectors that carry zero padding (bsm_cg.h).  The
 // arithmetic of a pass is that of bsm_krylov.hip with the right-hand side on blockIdx.y:
@@ -31,27 +31,19 @@
 #include "bsm_gmres_multi.h"
 
 #include "../../include/bsm_rocm.h"
-#include "bsm_cg_device.h"
-#include "bsm_krylov_device.h"
+#include "bsm_lockstep_device.h"
 
 namespace bsm {
 namespace {
 
 constexpr int kCB = 4;  // basis vectors in flight
 
-template <typename R> __device__ __forceinline__ Vec16<R> zero16() {
-    Vec16<R> v;
-#pragma unroll
-    for (int k = 0; k < 16 / (int)sizeof(R); ++k) v.r[k] = R(0);
-    return v;
-}
-
 template <typename R, int NC>
 __global__ void __launch_bounds__(kThreads)
     start_kernel(long long n, long long ld, long long ng, long long ldb, int first, int par, const R *__restrict__ B,
                  const R *__restrict__ q, R *__restrict__ v0, R *__restrict__ pbb, long long pbs, R *__restrict__ pnn,
                  const GmState *__restrict__ st) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     __shared__ R red[4][2];
     const int t = threadIdx.x, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     if (!first && st->slot[par].status[c] != kCgRun) return;
@@ -65,22 +57,10 @@ __global__ void __launch_bounds__(kThreads)
         for (int u = 0; u < kU; ++u) {
             const long long g = tile + (long long)u * kThreads + t;
             if (g >= g1) continue;
-            Vec16<R> v;
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                const long long row = g * VE + e;
-#pragma unroll
-                for (int k = 0; k < NC; ++k) v.r[e * NC + k] = row < n ? Bc[row * NC + k] : R(0);
-            }
-#pragma unroll
-            for (int k = 0; k < GC; ++k) s[0] = fma(v.r[k], v.r[k], s[0]);
-            if (q) {
-                const Vec16<R> w = load16(q + off + g * GC);
-#pragma unroll
-                for (int k = 0; k < GC; ++k) v.r[k] -= w.r[k];
-            }
-#pragma unroll
-            for (int k = 0; k < GC; ++k) s[1] = fma(v.r[k], v.r[k], s[1]);
+            Vec16<R> v = load16_guarded<R, NC>(Bc, g, n);
+            norm16(v, s[0]);
+            if (q) sub16(v, load16(q + off + g * GC));
+            norm16(v, s[1]);
             store16(v0 + off + g * GC, v);
         }
     }
@@ -114,15 +94,9 @@ __global__ void __launch_bounds__(kThreads)
         return;
     }
     const R beta = sqrt(wave_total(pnn + (long long)c * G, G, 1, lane));
-    double tol;
     R bn = R(0);
-    if (first) {
-        bn = sqrt(wave_total(pbb + (long long)c * pbs, G, 1, lane));
-        tol = fmax(rtol * (double)bn, atol);
-    } else {
-        tol = st->tol[c];
-    }
-    const int status = !isfinite(beta) ? 2 : ((double)beta <= tol ? 0 : kCgRun);
+    const double tol = first ? first_tol(pbb + (long long)c * pbs, G, lane, rtol, atol, bn) : st->tol[c];
+    const int status = decide(beta, tol);
     if (wg == 0) {
         R *gc = gv + (long long)c * (m + 1) * NC, *hc = hsum + (long long)c * m * NC;
         for (int i = t; i < (m + 1) * NC; i += kThreads) gc[i] = i == 0 ? beta : R(0);
@@ -151,8 +125,7 @@ __global__ void __launch_bounds__(kThreads)
     wg_range(ng, G, wg, g0, g1);
     for (long long g = g0 + t; g < g1; g += kThreads) {
         Vec16<R> v = load16(v0 + off + g * GC);
-#pragma unroll
-        for (int k = 0; k < GC; ++k) v.r[k] *= inv;
+        scale16(v, inv);
         store16(v0 + off + g * GC, v);
     }
 }
@@ -161,7 +134,7 @@ template <typename R, int NC>
 __global__ void __launch_bounds__(kThreads)
     dot_kernel(long long ld, long long ng, long long vs, int k, int m, int par, const R *__restrict__ V, const R *__restrict__ W,
                R *__restrict__ part, const GmState *__restrict__ st) {
-    constexpr int GC = 16 / (int)sizeof(R), VE = GC / NC;
+    constexpr int GC = 16 / (int)sizeof(R);
     __shared__ R acc[BSM_GMRES_MAX_RESTART * 4 * NC];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, G = gridDim.x, wg = blockIdx.x, c = blockIdx.y;
     if (st->slot[par].status[c] != kCgRun) return;
@@ -194,8 +167,7 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
                 for (int q = 0; q < NC; ++q) s[cc][q] = R(0);
 #pragma unroll
-                for (int u = 0; u < kU; ++u)
-                    BSM_GS_DOT(R, NC, VE, vv[cc][u].r, wv[u].r, s[cc])
+                for (int u = 0; u < kU; ++u) dot16<R, NC>(vv[cc][u], wv[u], s[cc]);
             }
 #pragma unroll
             for (int cc = 0; cc < kCB; ++cc)
@@ -286,10 +258,7 @@ __global__ void __launch_bounds__(kThreads)
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
             if (!ok[u]) continue;
-            if (UPDATE) {
-#pragma unroll
-                for (int q = 0; q < GC; ++q) nn[0] = fma(wv[u].r[q], wv[u].r[q], nn[0]);
-            }
+            if (UPDATE) norm16(wv[u], nn[0]);
             store16(W + go[u], wv[u]);
         }
     }
@@ -344,7 +313,7 @@ __global__ void __launch_bounds__(64) hess_kernel(int G, int m, int j, int par, 
         }
         inv[c] = hn == R(0) ? R(0) : R(1) / hn;
         // the decision: the answer of this column uses exactly the iterations up to this one
-        const int status = !isfinite(est) || !isfinite(hn) ? 2 : ((double)est <= st->tol[c] ? 0 : kCgRun);
+        const int status = !isfinite(hn) ? 2 : decide(est, st->tol[c]);
         const int done = in.done[c] + 1;
         out.rn[c] = (double)est;
         out.status[c] = status;
@@ -373,8 +342,7 @@ __global__ void __launch_bounds__(kThreads) scale_kernel(long long ld, long long
     wg_range(ng, G, wg, g0, g1);
     for (long long g = g0 + t; g < g1; g += kThreads) {
         Vec16<R> v = load16(W + off + g * GC);
-#pragma unroll
-        for (int k = 0; k < GC; ++k) v.r[k] *= sc;
+        scale16(v, sc);
         store16(Vn + off + g * GC, v);
     }
 }
@@ -434,9 +402,7 @@ __global__ void __launch_bounds__(kThreads) axpy_kernel(long long ld, long long 
     wg_range(ng, G, wg, g0, g1);
     for (long long g = g0 + t; g < g1; g += kThreads) {
         Vec16<R> x = load16(X + off + g * GC);
-        const Vec16<R> z = load16(Z + off + g * GC);
-#pragma unroll
-        for (int k = 0; k < GC; ++k) x.r[k] += z.r[k];
+        add16(x, load16(Z + off + g * GC));
         store16(X + off + g * GC, x);
     }
 }

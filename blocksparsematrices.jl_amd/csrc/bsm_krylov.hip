@@ -21,22 +21,17 @@
 // front of it and behind the last whole group go element by element through the same code (a group that is not wholly
 // inside [0, n) is read and written under a per-element guard).  Otherwise every group is one element (VE = 1).
 // Every sum has a fixed order: the results are bit-identical from run to run.  norm_kernel (one wave) adds the
-// per-workgroup norm shares in a fixed order too.
+// per-workgroup norm shares in a fixed order too.  The 16-byte access, the wave / workgroup sums and the row ranges are
+// those of the lockstep units (bsm_lockstep_device.h), the arithmetic of a group is bsm_krylov_device.h.
 #include "bsm_krylov.h"
 
 #include "../../include/bsm_rocm.h"
-#include "bsm_krylov_device.h"
+#include "bsm_lockstep_device.h"
 
 namespace bsm {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kU = 2;   // 16-byte groups per thread and tile
 constexpr int kCB = 4;  // columns in flight
-
-template <typename R> struct alignas(16) Vec16 {
-    R r[16 / sizeof(R)];
-};
 
 // one group of VE elements (GC = VE * NC components) starting at element e0 of p; A16: groups are 16-byte aligned
 template <typename R, int NC, int VE, bool A16>
@@ -44,7 +39,7 @@ __device__ __forceinline__ void load_group(const R *__restrict__ p, long long e0
     constexpr int GC = VE * NC;
     if (A16) {
         if (valid && e0 >= 0 && e0 + VE <= n) {
-            const Vec16<R> t = *reinterpret_cast<const Vec16<R> *>(p + e0 * NC);
+            const Vec16<R> t = load16(p + e0 * NC);
 #pragma unroll
             for (int q = 0; q < GC; ++q) v[q] = t.r[q];
             return;
@@ -65,7 +60,7 @@ __device__ __forceinline__ void store_group(R *__restrict__ p, long long e0, lon
             Vec16<R> t;
 #pragma unroll
             for (int q = 0; q < GC; ++q) t.r[q] = v[q];
-            *reinterpret_cast<Vec16<R> *>(p + e0 * NC) = t;
+            store16(p + e0 * NC, t);
             return;
         }
     }
@@ -78,20 +73,8 @@ __device__ __forceinline__ void store_group(R *__restrict__ p, long long e0, lon
     }
 }
 
-template <typename R> __device__ __forceinline__ R wave_sum(R v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// the rows of workgroup wg: groups [g0, g1) of the ng groups that cover elements lo .. n - 1 (lo <= 0: the first group
-// may start in front of the vector)
-__device__ __forceinline__ void wg_range(long long ng, int G, int wg, long long &g0, long long &g1) {
-    const long long per = (ng + G - 1) / G;
-    g0 = per * wg;
-    g1 = g0 + per < ng ? g0 + per : ng;
-}
-
+// (wg_range of the shared header on the ng groups that cover elements lo .. n - 1; lo <= 0: the first group may start in
+// front of the vector)
 template <typename R, int NC, int VE, bool A16>
 __global__ void __launch_bounds__(kThreads) dot_kernel(long long n, int k, const R *__restrict__ V, long long ldv,
                                                        const R *__restrict__ w, R *__restrict__ part, long long lo, long long ng) {
@@ -126,8 +109,7 @@ __global__ void __launch_bounds__(kThreads) dot_kernel(long long n, int k, const
 #pragma unroll
                 for (int c = 0; c < NC; ++c) s[cc][c] = R(0);
 #pragma unroll
-                for (int u = 0; u < kU; ++u)
-                    BSM_GS_DOT(R, NC, VE, vv[cc][u], wv[u], s[cc])
+                for (int u = 0; u < kU; ++u) gs_dot<R, NC, VE>(vv[cc][u], wv[u], s[cc]);
             }
 #pragma unroll
             for (int cc = 0; cc < kCB; ++cc)
@@ -151,21 +133,15 @@ __global__ void __launch_bounds__(kThreads) dot_kernel(long long n, int k, const
     }
 }
 
-// (COMBINE, coef and scale serve no caller any more -- out = V coef and out = in * scale were steps of a solver that is gone.
-// They stay because the kernel without them compiles to other register counts; every launch has COMBINE = false, coef =
-// scale = null, in = out = w.)
-template <typename R, int NC, int VE, bool A16, bool COMBINE>
+template <typename R, int NC, int VE, bool A16>
 __global__ void __launch_bounds__(kThreads)
-    sweep_kernel(long long n, int k, const R *__restrict__ V, long long ldv, const R *in, R *out, const R *__restrict__ part,
-                 const R *__restrict__ coef, R *__restrict__ hsum, const R *__restrict__ scale, R *__restrict__ nrmpart,
-                 long long lo, long long ng) {
+    sweep_kernel(long long n, int k, const R *__restrict__ V, long long ldv, R *__restrict__ w, const R *__restrict__ part,
+                 R *__restrict__ hsum, R *__restrict__ nrmpart, long long lo, long long ng) {
     constexpr int GC = VE * NC;
     __shared__ R hs[BSM_GMRES_MAX_RESTART * NC];
-    __shared__ R red[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, G = gridDim.x, wg = blockIdx.x;
-    if (COMBINE) {
-        for (int i = t; i < k * NC; i += kThreads) hs[i] = coef[i];
-    } else if (k > 0) {
+    __shared__ R red[4][1];
+    const int t = threadIdx.x, G = gridDim.x, wg = blockIdx.x;
+    if (k > 0) {
         int c;
         R a[NC];
         if (gs_sum_partials<R, NC>(part, k, G, t, kThreads, c, a)) {
@@ -177,8 +153,7 @@ __global__ void __launch_bounds__(kThreads)
         }
     }
     __syncthreads();
-    const R sc = scale ? scale[0] : R(1);
-    R nn = R(0);
+    R nn[1] = {R(0)};
     long long g0, g1;
     wg_range(ng, G, wg, g0, g1);
     for (long long tile = g0; tile < g1; tile += (long long)kThreads * kU) {
@@ -190,12 +165,7 @@ __global__ void __launch_bounds__(kThreads)
             const long long g = tile + (long long)u * kThreads + t;
             ok[u] = g < g1;
             e0[u] = lo + g * VE;
-            if (COMBINE) {
-#pragma unroll
-                for (int q = 0; q < GC; ++q) wv[u][q] = R(0);
-            } else {
-                load_group<R, NC, VE, A16>(in, e0[u], n, ok[u], wv[u]);
-            }
+            load_group<R, NC, VE, A16>(w, e0[u], n, ok[u], wv[u]);
         }
         for (int c0 = 0; c0 < k; c0 += kCB) {
             R vv[kCB][kU][GC];
@@ -215,35 +185,20 @@ __global__ void __launch_bounds__(kThreads)
         }
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-            if (scale) {
+            // (a group in front of the vector or behind it holds zeros where it is outside: they add nothing)
 #pragma unroll
-                for (int q = 0; q < GC; ++q) wv[u][q] *= sc;
-            }
-            if (!COMBINE) {
-                // (a group in front of the vector or behind it holds zeros where it is outside: they add nothing)
-#pragma unroll
-                for (int q = 0; q < GC; ++q) nn = fma(wv[u][q], wv[u][q], nn);
-            }
-            store_group<R, NC, VE, A16>(out, e0[u], n, ok[u], wv[u]);
+            for (int q = 0; q < GC; ++q) nn[0] = fma(wv[u][q], wv[u][q], nn[0]);
+            store_group<R, NC, VE, A16>(w, e0[u], n, ok[u], wv[u]);
         }
     }
-    if (!COMBINE && nrmpart) {
-        nn = wave_sum(nn);
-        if (lane == 0) red[wave] = nn;
-        __syncthreads();
-        if (t == 0) nrmpart[wg] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (nrmpart) {
+        block_sum<R, 1>(nn, red);
+        if (t == 0) nrmpart[wg] = nn[0];
     }
-}
-
-// sum of p[0 .. G) by one wave in a fixed order
-template <typename R> __device__ __forceinline__ R wave_total(const R *__restrict__ p, int G, int lane) {
-    R a = R(0);
-    for (int g = lane; g < G; g += 64) a += p[g];
-    return wave_sum(a);
 }
 
 template <typename R> __global__ void __launch_bounds__(64) norm_kernel(int G, const R *__restrict__ nrmpart, R *__restrict__ nrm) {
-    const R a = wave_total(nrmpart, G, (int)threadIdx.x);
+    const R a = wave_total(nrmpart, G, 1, (int)threadIdx.x);
     if (threadIdx.x == 0) nrm[0] = sqrt(a);
 }
 
@@ -303,13 +258,12 @@ hipError_t launch_krylov_update(int dtype, long long n, int k, const void *V, lo
         using R = decltype(r);
         constexpr int NC = decltype(nc)::value, VE = 16 / (int)(sizeof(R) * NC);
         auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, grid, block, 0, stream, n, k, (const R *)V, ldv, (const R *)w, (R *)w, (const R *)part, (const R *)nullptr,
-                               (R *)hsum, (const R *)nullptr, (R *)nrmpart, s.lo, s.ng);
+            hipLaunchKernelGGL(kernel, grid, block, 0, stream, n, k, (const R *)V, ldv, (R *)w, (const R *)part, (R *)hsum, (R *)nrmpart, s.lo, s.ng);
         };
         if (s.a16)
-            launch(sweep_kernel<R, NC, VE, true, false>);
+            launch(sweep_kernel<R, NC, VE, true>);
         else
-            launch(sweep_kernel<R, NC, 1, false, false>);
+            launch(sweep_kernel<R, NC, 1, false>);
     });
     return hipGetLastError();
 }

@@ -1,8 +1,7 @@
-// bsm_krylov_device.h -- the device-side pieces of a classical Gram-Schmidt pass that bsm_krylov.hip (bsm_krylov_orth: one
-// column of any alignment) and bsm_gmres_multi.hip (the GMRES solvers: padded workspace columns in lockstep) share: the
-// update of a tile on the elements of one 16-byte group, the fixed-order sum of a pass's partials, and the dot of a tile
-// as a statement macro at the end of this file.  The units differ in how they reach their vectors (guarded groups of any
-// alignment there, unguarded groups of padded workspace columns here).  For the kernel units only.
+// bsm_krylov_device.h -- the device-side arithmetic of a classical Gram-Schmidt pass on the elements of one group, as
+// plain functions over arrays of reals, and the fixed-order sum of a pass's partials.  bsm_krylov.hip (bsm_krylov_orth: one
+// column of any alignment, guarded groups) uses them as they are; the lockstep units reach them through the Vec16 forms of
+// bsm_lockstep_device.h (unguarded groups of padded workspace columns).  For the kernel units only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,18 +9,35 @@
 
 namespace bsm {
 
+// y += a x on one element: each component takes its ar term first, then its ai term.  (The one place the order of a complex
+// multiply-add is written down: axpy16 has the scalar as a, the Gram-Schmidt update the vector.)
+template <typename R, int NC> __device__ __forceinline__ void gs_madd(R ar, R ai, R xr, R xi, R &yr, R &yi) {
+    if (NC == 1) {
+        yr = fma(ar, xr, yr);
+    } else {
+        yr = fma(-ai, xi, fma(ar, xr, yr));
+        yi = fma(ai, xr, fma(ar, xi, yi));
+    }
+}
+
 // w += v h over the VE elements of one group, h = (hr, hi)
 template <typename R, int NC, int VE> __device__ __forceinline__ void gs_axpy(const R *v, R hr, R hi, R *w) {
 #pragma unroll
+    for (int e = 0; e < VE; ++e) gs_madd<R, NC>(v[e * NC], v[e * NC + NC - 1], hr, hi, w[e * NC], w[e * NC + NC - 1]);
+}
+
+// s[0 .. NC) += conj(v) w over the VE elements of one group
+template <typename R, int NC, int VE> __device__ __forceinline__ void gs_dot(const R *v, const R *w, R *s) {
+#pragma unroll
     for (int e = 0; e < VE; ++e) {
         if (NC == 1) {
-            w[e] = fma(v[e], hr, w[e]);
+            s[0] = fma(v[e], w[e], s[0]);
         } else {
-            const R vr = v[e * NC], vi = v[e * NC + NC - 1];
-            w[e * NC] = fma(vr, hr, w[e * NC]);
-            w[e * NC] = fma(-vi, hi, w[e * NC]);
-            w[e * NC + NC - 1] = fma(vr, hi, w[e * NC + NC - 1]);
-            w[e * NC + NC - 1] = fma(vi, hr, w[e * NC + NC - 1]);
+            const R vr = v[e * NC], vi = v[e * NC + NC - 1], wr = w[e * NC], wi = w[e * NC + NC - 1];
+            s[0] = fma(vr, wr, s[0]);
+            s[0] = fma(vi, wi, s[0]);
+            s[NC - 1] = fma(vr, wi, s[NC - 1]);
+            s[NC - 1] = fma(-vi, wr, s[NC - 1]);
         }
     }
 }
@@ -51,22 +67,5 @@ __device__ __forceinline__ bool gs_sum_partials(const R *__restrict__ part, int 
     }
     return c < k && sl == 0;
 }
-
-// ---- a statement both units expand in place.  A macro, not a function: as a function the dot tile compiled to another
-// register count in bsm_krylov.hip (docs/experiments_r25.md); an expansion is the very statements that unit had.
-// s[0 .. NC) += conj(v) w over the VE elements of one group (v, w: arrays of reals; s: NC sums)
-#define BSM_GS_DOT(R, NC, VE, v, w, s)                                      \
-    _Pragma("unroll") for (int e = 0; e < VE; ++e) {                        \
-        if (NC == 1) {                                                      \
-            (s)[0] = fma((v)[e], (w)[e], (s)[0]);                           \
-        } else { /* conj(v) * w */                                          \
-            const R vr = (v)[e * NC], vi = (v)[e * NC + NC - 1];            \
-            const R wr = (w)[e * NC], wi = (w)[e * NC + NC - 1];            \
-            (s)[0] = fma(vr, wr, (s)[0]);                                   \
-            (s)[0] = fma(vi, wi, (s)[0]);                                   \
-            (s)[NC - 1] = fma(vr, wi, (s)[NC - 1]);                         \
-            (s)[NC - 1] = fma(-vi, wr, (s)[NC - 1]);                        \
-        }                                                                   \
-    }
 
 }  // namespace bsm

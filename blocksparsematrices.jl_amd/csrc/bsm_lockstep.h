@@ -1,19 +1,33 @@
 // bsm_lockstep.h -- the host side that the lockstep solver objects (bsm_cg.cpp: bsm_cg_*, bsm_bicgstab.cpp: bsm_bicgstab_*,
-// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*; include/bsm_rocm.h) share: what a solver object holds whatever its method, the (handle, vector) pairings and the
-// multi-column product on the workspace, the refusals of create and solve, the one device allocation with its ring of
-// pinned record slots, the staging of host matrices, and the look-ahead loop that reads one record per iteration (lockstep_run; the multi-column GMRES, whose iterations come
-// in cycles, drives its own).  A
-// method adds its vectors and partial sums to the allocation (Carve) and supplies its start and its iteration.
+// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*; include/bsm_rocm.h) share: what a solver object
+// holds whatever its method, the (handle, vector) pairings and the multi-column product on the workspace, create from the
+// refusals to the one device allocation (lockstep_create: a method writes its layout once, as a function on a Carve), the
+// start of x, the ring of pinned record slots (RecordRing), what the host takes from a record and reports from the last
+// one, the look-ahead loop that reads one record per iteration (lockstep_run; the GMRES solvers, whose iterations come in
+// cycles, drive the same ring in their own loop), the refusals of solve and the staging of host matrices.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <new>
 #include <string>
 
 #include "bsm_cg.h"
 #include "bsm_internal.h"
+
+// return from the enclosing function with the failure of a HIP call / of a call that returns a BSM status
+#define HIP_TRY(call)                                     \
+    do {                                                  \
+        const hipError_t e_ = (call);                     \
+        if (e_ != hipSuccess) return hip_fail(e_, #call); \
+    } while (0)
+#define RC_TRY(call)                  \
+    do {                              \
+        const int rc_ = (call);       \
+        if (rc_ != BSM_OK) return rc_; \
+    } while (0)
 
 namespace bsm {
 
@@ -72,13 +86,15 @@ inline bool overlap(const void *a, size_t abytes, const void *b, size_t bbytes) 
     return p < q + bbytes && q < p + abytes;
 }
 
-// offsets into the one allocation, 64-byte aligned
+// The one allocation cut into 64-byte aligned pieces.  A method's layout is a function that takes its pieces in order; it
+// runs without a base for the size (every piece null) and on the allocation for the pointers.
 struct Carve {
+    char *base = nullptr;
     int64_t off = 0;
-    int64_t take(int64_t bytes) {
+    char *take(int64_t bytes) {
         const int64_t o = off;
         off += (bytes + 63) / 64 * 64;
-        return o;
+        return base ? base + o : nullptr;
     }
 };
 
@@ -130,55 +146,88 @@ inline int lockstep_alloc(LockstepSolver *S, int64_t bytes, const char *what) {
                                     : hip_fail(e, (std::string(what) + " workspace").c_str());
 }
 
-inline int lockstep_destroy(LockstepSolver *S) {
-    DeviceGuard guard;
-    (void)guard.enter(S->device);
-    S->release();
+// The whole of a create: out, the checks (method_error as in lockstep_check_create), the object, the refusals of
+// lockstep_init, the allocation sized by layout(S, carve) (`ws_name`: "CG", .. for its failure) and the pointers from the
+// same layout.  layout also sets the method's own fields of S.
+template <typename Solver, typename Layout>
+int lockstep_create(const char *what, const char *ws_name, bsm_matrix_s *A, int opA, bsm_matrix_s *M, int opM, int vdtype, int32_t nrhs_max,
+                    const char *method_error, Solver **out, Layout &&layout) {
+    if (!out) return fail(BSM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    RC_TRY(lockstep_check_create(A, opA, M, opM, vdtype, nrhs_max, method_error));
+    Solver *S = new (std::nothrow) Solver;
+    if (!S) return fail(BSM_ERR_ALLOC, "out of host memory");
+    int rc = lockstep_init(S, what, A, opA, M, opM, vdtype, nrhs_max);
+    if (rc == BSM_OK) {
+        Carve size;
+        layout(*S, size);
+        rc = lockstep_alloc(S, size.off, ws_name);
+    }
+    if (rc != BSM_OK) {
+        delete S;
+        return rc;
+    }
+    Carve cv{(char *)S->ws};
+    layout(*S, cv);
+    *out = S;
     return BSM_OK;
 }
 
-// record k (0: the start, j + 1: iteration j) -> its pinned slot, behind its event
-inline hipError_t lockstep_post(LockstepSolver *S, int64_t k, hipStream_t st) {
-    hipError_t q = hipMemcpyAsync(S->slots + k % kLockstepRing, &S->state->rec, sizeof(CgRecord), hipMemcpyDeviceToHost, st);
-    if (q == hipSuccess) q = hipEventRecord(S->ev[k % kLockstepRing], st);
-    return q;
-}
-// The loop of a device solve after its start has been enqueued and record 0 posted: iterate(j) enqueues iteration j (it
-// leaves its record in state->rec), the host reads record j one iteration behind the enqueue, fills history and stops
-// when no column runs or maxiter is reached; then the copy-out of X (launch_cg_copy: n rows of nrhs columns and nothing
-// else), and info / cols from the last record.  info.a_products / m_products are the caller's.
-template <typename Iterate>
-int lockstep_run(LockstepSolver *S, const CgDims &d, void *X, int64_t ldx, void *wsX, const bsm_cg_params &p, bsm_cg_info &info,
-                 bsm_cg_column *cols, double *history, hipStream_t st, Iterate &&iterate) {
-    const int nrhs = d.nrhs;
-    const int64_t maxiter = std::min<int64_t>(p.maxiter, INT32_MAX);
-    hipError_t e = hipSuccess;
-    int64_t enq = 0, rd = 0;
-    const CgRecord *last = nullptr;
-    for (;;) {
-        if (enq < maxiter) {
-            const int rc = iterate(enq);
-            if (rc != BSM_OK) return rc;
-            enq++;
-            if ((e = lockstep_post(S, enq, st)) != hipSuccess) return hip_fail(e, "record of an iteration");
-        }
-        if ((e = hipEventSynchronize(S->ev[rd % kLockstepRing])) != hipSuccess) return hip_fail(e, "hipEventSynchronize");
-        last = S->slots + rd % kLockstepRing;
-        int running = 0;
-        for (int c = 0; c < nrhs; c++) {
-            running += last->status[c] == kCgRun;
-            if (history && rd >= 1 && rd - 1 < p.history_capacity) history[(rd - 1) * nrhs + c] = last->rn[c];
-        }
-        if (running == 0 || rd == maxiter) break;
-        rd++;
+template <typename Solver> int lockstep_destroy(Solver *S) {
+    if (!S) return BSM_OK;
+    {
+        DeviceGuard guard;
+        (void)guard.enter(S->device);
+        S->release();
     }
-    // (an iteration enqueued beyond record rd found every column frozen: it wrote nothing)
-    CgRecord fin = *last;
-    if ((e = launch_cg_copy(d, false, X, ldx, wsX, st)) != hipSuccess) return hip_fail(e, "launch_cg_copy");
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    delete S;
+    return BSM_OK;
+}
+
+// The start of x every method shares: with use_x0 the caller's X into the workspace X and q = op(A) X; else X = 0 (q is
+// left alone: the method's start kernel gets no q)
+inline int lockstep_start_x(LockstepSolver *S, const CgDims &d, bool use_x0, void *X, int64_t ldx, void *wsX, void *q, hipStream_t st) {
+    if (!use_x0) {
+        HIP_TRY(hipMemsetAsync(wsX, 0, (size_t)S->ld * elem_bytes(S->vt) * d.nrhs, st));
+        return BSM_OK;
+    }
+    HIP_TRY(launch_cg_copy(d, true, X, ldx, wsX, st));
+    return apply(S->A, S->opA, S->a_cvec, d.nrhs, S->ld, S->vt, wsX, q, st);
+}
+
+// The records of one solve: post() copies the record at the device address `rec` to the next pinned slot behind what has
+// been enqueued, next() waits for the oldest unread one.  At most kLockstepRing - 1 may be unread.
+struct RecordRing {
+    LockstepSolver *S;
+    const CgRecord *rec;
+    hipStream_t st;
+    int64_t posted = 0, read = 0;
+    hipError_t post() {
+        hipError_t q = hipMemcpyAsync(S->slots + posted % kLockstepRing, rec, sizeof(CgRecord), hipMemcpyDeviceToHost, st);
+        if (q == hipSuccess) q = hipEventRecord(S->ev[posted % kLockstepRing], st);
+        posted++;
+        return q;
+    }
+    hipError_t next(const CgRecord *&r) {
+        r = S->slots + read % kLockstepRing;
+        return hipEventSynchronize(S->ev[read++ % kLockstepRing]);
+    }
+};
+// what the host takes from a record as it arrives: the residual norms as row `row` of history (row < 0: none) -> the
+// columns that still run
+inline int lockstep_take(const CgRecord &r, int nrhs, int64_t row, const bsm_cg_params &p, double *history) {
+    int running = 0;
     for (int c = 0; c < nrhs; c++) {
-        const int status = fin.status[c] == kCgRun ? 1 : fin.status[c];
-        const int64_t its = fin.done[c];
+        running += r.status[c] == kCgRun;
+        if (history && row >= 0 && row < p.history_capacity) history[row * nrhs + c] = r.rn[c];
+    }
+    return running;
+}
+// status, iterations and columns_converged of info and cols (may be null) from the last record of a solve
+inline void lockstep_report(const CgRecord &r, int nrhs, bsm_cg_info &info, bsm_cg_column *cols) {
+    for (int c = 0; c < nrhs; c++) {
+        const int status = r.status[c] == kCgRun ? 1 : r.status[c];
+        const int64_t its = r.done[c];
         info.status = std::max(info.status, status);
         info.iterations = std::max(info.iterations, its);
         info.columns_converged += status == 0;
@@ -186,11 +235,42 @@ int lockstep_run(LockstepSolver *S, const CgDims &d, void *X, int64_t ldx, void 
             cols[c].status = status;
             cols[c].reserved = 0;
             cols[c].iterations = its;
-            cols[c].residual = fin.rn[c];
-            cols[c].bnorm = fin.bnorm[c];
+            cols[c].residual = r.rn[c];
+            cols[c].bnorm = r.bnorm[c];
         }
     }
+}
+// the end of a device solve: the copy-out of X (launch_cg_copy: n rows of nrhs columns and nothing else), then the report
+inline int lockstep_finish(const CgDims &d, void *X, int64_t ldx, void *wsX, const CgRecord &last, bsm_cg_info &info, bsm_cg_column *cols,
+                           hipStream_t st) {
+    HIP_TRY(launch_cg_copy(d, false, X, ldx, wsX, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    lockstep_report(last, d.nrhs, info, cols);
     return BSM_OK;
+}
+
+// The loop of a device solve after its start has been enqueued: record 0 (the start) is posted, iterate(j) enqueues
+// iteration j (it leaves its record in state->rec), the host reads record j one iteration behind the enqueue, fills history
+// and stops when no column runs or maxiter is reached; then lockstep_finish.  info.a_products / m_products are the caller's.
+template <typename Iterate>
+int lockstep_run(LockstepSolver *S, const CgDims &d, void *X, int64_t ldx, void *wsX, const bsm_cg_params &p, bsm_cg_info &info,
+                 bsm_cg_column *cols, double *history, hipStream_t st, Iterate &&iterate) {
+    const int64_t maxiter = std::min<int64_t>(p.maxiter, INT32_MAX);
+    RecordRing ring{S, &S->state->rec, st};
+    HIP_TRY(ring.post());
+    const CgRecord *last = nullptr;
+    for (int64_t enq = 0;;) {
+        if (enq < maxiter) {
+            RC_TRY(iterate(enq));
+            enq++;
+            HIP_TRY(ring.post());
+        }
+        HIP_TRY(ring.next(last));
+        const int64_t rd = ring.read - 1;
+        if (lockstep_take(*last, d.nrhs, rd - 1, p, history) == 0 || rd == maxiter) break;
+    }
+    // (an iteration enqueued beyond the record read last found every column frozen: it wrote nothing)
+    return lockstep_finish(d, X, ldx, wsX, *last, info, cols, st);
 }
 
 // The whole of a solve entry point but the method: the refusals, info cleared and its workspace fields set, n == 0, the

@@ -1350,6 +1350,30 @@ class GmresInfo:
                 f"residual={self.residual:.3e}, bnorm={self.bnorm:.3e})")
 
 
+def _solver_operators(A, M, dtype):
+    """the checks every solver object begins with -> (A's matrix, its op, M's matrix or None, its op, the vector type)"""
+    base, op = _unwrap(A)
+    if not isinstance(base, AbstractBlockMatrix):
+        raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
+    mbase, mop = (None, L.BSM_OP_N) if M is None else _unwrap(M)
+    if M is not None and not isinstance(mbase, AbstractBlockMatrix):
+        raise TypeError("M must be a block matrix or its transpose/adjoint wrapper")
+    dtype = np.dtype(base.dtype if dtype is None else dtype)
+    if dtype not in _DT:
+        raise TypeError(f"dtype={dtype} is not a supported vector type")
+    return base, op, mbase, mop, dtype
+
+
+def _copy_guess(X, X0):
+    """the initial guess X0 (torch tensor or numpy array, checked) into X, where the solver reads and overwrites it"""
+    if X0 is X:
+        return
+    if torch is not None and isinstance(X, torch.Tensor):
+        X.copy_(X0 if isinstance(X0, torch.Tensor) else torch.from_numpy(X0))
+    else:
+        X[...] = X0.cpu().numpy() if torch is not None and isinstance(X0, torch.Tensor) else X0
+
+
 class Gmres:
     """Right-preconditioned restarted GMRES(restart) for A x = b, every step of it on the device (bsm_gmres_*: the
     solver of GmresMulti with one column behind its own info).
@@ -1359,15 +1383,7 @@ class Gmres:
     kept alive."""
 
     def __init__(self, A, M=None, restart=30, dtype=None):
-        base, op = _unwrap(A)
-        if not isinstance(base, AbstractBlockMatrix):
-            raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
-        mbase, mop = (None, L.BSM_OP_N) if M is None else _unwrap(M)
-        if M is not None and not isinstance(mbase, AbstractBlockMatrix):
-            raise TypeError("M must be a block matrix or its transpose/adjoint wrapper")
-        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
-        if self.dtype not in _DT:
-            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        base, op, mbase, mop, self.dtype = _solver_operators(A, M, dtype)
         self.A, self.M, self.restart = A, M, int(restart)
         self.n = size(A)[0]
         self._base, self._mbase = base, mbase
@@ -1399,11 +1415,7 @@ class Gmres:
         if x0 is not None:
             if _elt(x0) != self.dtype or tuple(x0.shape) != (self.n,):
                 raise TypeError(f"x0 must be a vector of {self.n} entries of {self.dtype}")
-            if x0 is not x:
-                if torch is not None and isinstance(x, torch.Tensor):
-                    x.copy_(x0 if isinstance(x0, torch.Tensor) else torch.from_numpy(x0))
-                else:
-                    x[...] = x0.cpu().numpy() if torch is not None and isinstance(x0, torch.Tensor) else x0
+            _copy_guess(x, x0)
         maxiter = max(self.n, 1) if maxiter is None else int(maxiter)
         hist = np.zeros(max(maxiter, 1), dtype=np.float64)
         p = L.BsmGmresParams(C.sizeof(L.BsmGmresParams), 0 if x0 is None else 1, float(rtol), float(atol), maxiter, maxiter)
@@ -1463,15 +1475,7 @@ class _LockstepSolver:
     def _setup(self, A, M, nrhs, dtype, extra=None):
         """the checks and the create call; extra(): called once A, M and dtype have passed, gives the arguments of create
         between nrhs_max and out"""
-        base, op = _unwrap(A)
-        if not isinstance(base, AbstractBlockMatrix):
-            raise TypeError("A must be a block matrix or its transpose/adjoint wrapper")
-        mbase, mop = (None, L.BSM_OP_N) if M is None else _unwrap(M)
-        if M is not None and not isinstance(mbase, AbstractBlockMatrix):
-            raise TypeError("M must be a block matrix or its transpose/adjoint wrapper")
-        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
-        if self.dtype not in _DT:
-            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        base, op, mbase, mop, self.dtype = _solver_operators(A, M, dtype)
         extra = () if extra is None else extra()
         self.A, self.M, self.nrhs = A, M, int(nrhs)
         self.n = size(A)[0]
@@ -1527,11 +1531,7 @@ class _LockstepSolver:
         if X0 is not None:
             if _elt(X0) != self.dtype or tuple(X0.shape) != tuple(X.shape):
                 raise TypeError(f"X0 must have the shape {tuple(X.shape)} and the type {self.dtype}")
-            if X0 is not X:
-                if torch is not None and isinstance(X, torch.Tensor):
-                    X.copy_(X0 if isinstance(X0, torch.Tensor) else torch.from_numpy(X0))
-                else:
-                    X[...] = X0.cpu().numpy() if torch is not None and isinstance(X0, torch.Tensor) else X0
+            _copy_guess(X, X0)
         maxiter = max(self.n, 1) if maxiter is None else int(maxiter)
         cap = min(maxiter, self.history_capacity) if history else 0
         hist = np.empty((max(cap, 1), k), dtype=np.float64)

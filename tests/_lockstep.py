@@ -55,7 +55,7 @@ def krylov_grid(n, es):
 
 
 def last_range_rows(n, es):
-    """rows of the LAST workgroup's range, mirror of wg_range (csrc/bsm_cg_device.h) on the 16-byte groups of a column"""
+    """rows of the LAST workgroup's range, mirror of wg_range (csrc/bsm_lockstep_device.h) on the 16-byte groups of a column"""
     ve = 16 // es
     ng = (max(n, 1) * es + 15) // 16
     G = krylov_grid(n, es)

@@ -36,7 +36,7 @@ def test_the_mirror_is_the_grid_rule_of_the_source():
     assert f"constexpr int kKrylovMaxGrid = {MAX_GRID};" in src
     assert "inline int krylov_grid(long long n, int es) { const long long per = 512LL * (16 / es); const long long g = (n + per - 1) / per;" in src
     assert RANGE_BYTES == 512 * 16
-    dev = re.sub(r"\s+", " ", open(os.path.join(CSRC, "bsm_cg_device.h")).read())
+    dev = re.sub(r"\s+", " ", open(os.path.join(CSRC, "bsm_lockstep_device.h")).read())
     assert "const long long per = (ng + G - 1) / G; g0 = per * wg;" in dev and "for (int g = lane; g < G; g += 64)" in dev
     for dt in DTYPES:
         es = np.dtype(dt).itemsize
