@@ -346,7 +346,7 @@ __device__ __forceinline__ ColMap col_map(const WaveD &wd, const PieceD &pc) {
     return {pc.xbase, pc.col_off, pc.kind, wd.seg1_w, wd.seg1_x - wd.seg1_w, wd.seg2_w, pc.seg2_x - wd.seg2_w};
 }
 // -> x / y index of piece column w, `raw` its list entry where the piece has a list; `off` tells whether the column is KIND_OFF
-// (il_panel.  run_panel, run_panel_multi and export_coo_kernel keep this decode in their own text: hipcc schedules them
+// (il_panel.  run_panel, PanelSetup of bsm_multi.hip and export_coo_kernel keep this decode in their own text: hipcc schedules them
 // differently around the shared form -- docs/experiments_r12.md)
 __device__ __forceinline__ int col_decode(const ColMap &cm, int w, int raw, bool &off) {
     if (cm.xbase < 0) {

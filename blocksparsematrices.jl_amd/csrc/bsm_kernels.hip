@@ -8,8 +8,8 @@
 //                   stream_policy, with_pair)
 //   bsm_families.h  what the families export to this file: Product, launch_one / _multi / _interleaved, launch_scale
 //   bsm_one.hip     one column: run_panel, panel_kernel, scale_kernel, gather_kernel, launch_typed
-//   bsm_multi.hip   4 / 8 / 16 columns per pass: run_panel_multi, panel_kernel_multi (register, tile-pipe and MFMA
-//                   paths), launch_typed_multi
+//   bsm_multi.hip   4 / 8 / 16 columns per pass: MultiShape, PanelSetup, panel_multi (one overload per path: register,
+//                   tile pipeline, matrix pipe), panel_kernel_multi, launch_typed_multi
 //   bsm_il.hip      the interleaved multi-RHS pass: ILT, il_panel, panel_kernel_il, il_pack_kernel, il_finish_kernel,
 //                   launch_il
 //   bsm_util.hip    fan-out vector helpers, COO export, pack / pack-convert, synth, the stream floor

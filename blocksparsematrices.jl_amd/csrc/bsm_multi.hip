@@ -1,5 +1,9 @@
-// bsm_multi.hip -- the multi-RHS family: panel_kernel_multi (run_panel_multi) with its register, tile-pipe and
-// matrix-pipe (MFMA) paths, K = 4 / 8 / 16 columns per pass over the matrix.
+// bsm_multi.hip -- the multi-RHS family, K = 4 / 8 / 16 columns per pass over the matrix: panel_kernel_multi and the three
+// paths an instance <T, L, TRN, K> can take, one device function each (overloads of panel_multi on PathTag):
+//   MultiShape    which path an instance takes, its LDS arrays, its resident-workgroup bound
+//   PanelSetup    what every path sets up for a wave's piece (flags, kact, piece fields, the column decode)
+//   panel_multi   Register: tile in registers;  TilePipe: tiles prefetched into LDS (kTilePipe);  MatrixPipe: the three
+//                 loops on v_mfma_*_16x16x4 (kMfmaAny) with their forward epilogue
 #include "bsm_device.h"
 #include "bsm_families.h"
 
@@ -121,45 +125,487 @@ template <typename T, int K> constexpr int x_chunk_cols_multi() {
     return kMfmaAny<T, K> ? 64 : x_chunk_cols_multi_vec<T, K>();
 }
 
-template <typename T, int L, int P, bool FWD, bool TRN, int K>
-__device__ __forceinline__ void run_panel_multi(const WaveD &wd, const uint4 *__restrict__ values,
-                                                const int *__restrict__ rows,
-                                                const int *__restrict__ cols, const T *__restrict__ x,
-                                                long long ldx, T *__restrict__ y, long long ldy, T alpha,
-                                                int flags, int lane, T *xs, Vec16<T> *tile, int *ixm, T (&out)[K],
-                                                bool &fwd_done) {
-    constexpr int E = TT<T>::E;
-    constexpr int G = 64 / P;
-    constexpr int NC = G * L * E;
-    constexpr bool PIPE = kTilePipe<T, L, TRN, K>;  // matrix tiles prefetched into LDS (below)
-    constexpr int XCH = PIPE ? x_chunk_cols_pipe<T, L>() : x_chunk_cols_multi<T, K>();
-    static_assert(kMfmaAny<T, K> || XCH % NC == 0, "x chunk must hold whole iterations");
-    const bool opT = (flags & FLAG_OPT) != 0;
-    const bool cjf = (flags & FLAG_CONJ) != 0;
-    const int kact = ((flags >> FLAG_KACT_SHIFT) & 15) ? ((flags >> FLAG_KACT_SHIFT) & 15) : K;
-    auto kc = [&](int k) { return k < kact ? k : kact - 1; };  // the column of X a (possibly padded) slot reads
-    const int m = wd.m;
-    const int i = lane & (P - 1);
-    const int g = lane / P;
-    const bool row_ok = i < m;
+// ----------------------------------------------------------------------------------------
+// The shape of an instance <T, L, TRN, K>: the ONE path it takes and what follows from that -- its LDS arrays and the
+// resident workgroups its register allocation must leave room for.  The kernel and the path functions read it here.
+// ----------------------------------------------------------------------------------------
+enum class MultiPath { Register, TilePipe, MatrixPipe };
+template <MultiPath PATH> using PathTag = std::integral_constant<MultiPath, PATH>;  // selects the overload of panel_multi
+template <typename T, int L, bool TRN, int K> struct MultiShape {
+    static constexpr MultiPath path = kTilePipe<T, L, TRN, K> ? MultiPath::TilePipe
+                                      : kMfmaAny<T, K>        ? MultiPath::MatrixPipe
+                                                              : MultiPath::Register;
+    static constexpr bool PIPE = path == MultiPath::TilePipe, MFA = path == MultiPath::MatrixPipe;
+    static constexpr int XCH = PIPE ? x_chunk_cols_pipe<T, L>() : x_chunk_cols_multi<T, K>();  // columns per staged chunk
+    static constexpr int XS = XCH * K;  // elements of the x slice (forward half); >= 64*K: also holds the combine slab
+    // 16-byte units: max over P of (64 / P) * L strips of P + 1 units; the pipelined kernels hold two tiles
+    // (matrix-pipe kernels: one 16 x 16 tile of elements, column stride 17)
+    static constexpr int TILE = PIPE ? 2 * L * 64 : (MFA ? (16 * 17 * (int)sizeof(T) + 15) / 16 : L * 72);
+    // y indices of the staged chunk (transposed half; the tile pipeline keeps them in registers)
+    static constexpr int IXM = (TRN && !PIPE && BSM_MULTI_IX) ? XCH : 1;
+    // resident workgroups per CU the register allocation must leave room for: 3 for the pipelined fp32 kernels (their
+    // LDS admits 3; fused: 189 VGPRs = 2 per CU without the bound, 168 + 16 spilled dwords with it: C3 in fp32 x 8
+    // 176 -> 159 us), 4 for the fp32 matrix-pipe ones (4 KB of slice per wave), BSM_MFMA_C128_WGS for the fp64
+    // matrix-pipe ones, 2 otherwise (the fp64 ones fit 3 by themselves)
+    static constexpr bool F32 = std::is_same<T, float>::value || std::is_same<T, c64>::value;
+    static constexpr int WGS = (MFA && F32) ? 4 : (((PIPE && F32) || (MFA && BSM_MFMA_C128_WGS == 3)) ? 3 : 2);
+};
 
+// number of the K slots of a (possibly padded) batch that carry columns
+template <int K> __device__ __forceinline__ int kact_of(int flags) {
+    const int k = (flags >> FLAG_KACT_SHIFT) & 15;
+    return k ? k : K;
+}
+
+// ----------------------------------------------------------------------------------------
+// What every path sets up for a wave's piece before its loop, built once per panel.
+// ----------------------------------------------------------------------------------------
+template <typename T, int K> struct PanelSetup {
+    bool opT, cjf;
+    int kact, m;
+    bool live;  // the wave has a piece
+    int xbase, col_off, nstrips, ncols;
+    // per-column kinds (a symmetric row group holds its diagonal block and its off-diagonal
+    // blocks in one panel): forward uses a column unless (op T/C and it is not KIND_OFF),
+    // transposed uses it iff (op T/C or KIND_OFF)
+    int kinds;
+    bool fwd_en, trn_en;
+    const Vec16<T> *vb;
+    const int *cols;
+    int s1w, s1x, s2w, s2x;
+    // the column of X a (possibly padded) slot reads
+    __device__ __forceinline__ int kc(int k) const { return k < kact ? k : kact - 1; }
+    // -> x / y index of piece column w; `off` tells whether the column is KIND_OFF  (the family's own text of
+    // col_decode, bsm_device.h: hipcc schedules these kernels differently around the shared form)
+    __device__ __forceinline__ int col_lookup(int w, bool &off) const {
+        if (xbase < 0) {
+            const int raw = cols[col_off + w];
+            off = raw >= 0 && (kinds & 3) == KIND_OFF;
+            return raw & 0x7fffffff;
+        }
+        const int sh = w < s1w ? 0 : (w < s2w ? 2 : 4);
+        off = ((kinds >> sh) & 3) == KIND_OFF;
+        return w + (w < s1w ? xbase : (w < s2w ? s1x : s2x));
+    }
+};
+template <typename T, int K>
+__device__ __forceinline__ PanelSetup<T, K> panel_setup(const WaveD &wd, int flags) {
+    PanelSetup<T, K> ps;
+    ps.opT = (flags & FLAG_OPT) != 0;
+    ps.cjf = (flags & FLAG_CONJ) != 0;
+    ps.kact = kact_of<K>(flags);
+    ps.m = wd.m;
+    ps.live = wd.npieces > 0;
+    ps.fwd_en = ps.trn_en = false;
+    return ps;
+}
+template <bool FWD, bool TRN, typename T, int K>
+__device__ __forceinline__ void load_piece(PanelSetup<T, K> &ps, const WaveD &wd, const uint4 *__restrict__ values,
+                                           const int *__restrict__ cols) {
+    const PieceD pc = wd.first;
+    ps.xbase = pc.xbase;
+    ps.col_off = pc.col_off;
+    ps.nstrips = pc.nstrips;
+    ps.ncols = pc.ncols;
+    ps.kinds = pc.kind;
+    const bool has_off = (pc.kind & kKindHasOff) != 0;
+    ps.fwd_en = FWD && (!ps.opT || has_off);
+    ps.trn_en = TRN && (ps.opT || has_off);
+    ps.vb = reinterpret_cast<const Vec16<T> *>(values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
+    ps.cols = cols;
+    ps.s1w = wd.seg1_w, ps.s1x = wd.seg1_x - wd.seg1_w;
+    ps.s2w = wd.seg2_w, ps.s2x = pc.seg2_x - wd.seg2_w;
+}
+
+// ----------------------------------------------------------------------------------------
+// What the register path and the tile pipeline share: K accumulators per lane with the lane on the row (forward half),
+// and the column-role layout of the transposed half.
+// Transposed half, V[w][k] = sum_i B[i][w] * X[row(i)][k].  With the lane on the row (the layout the
+// matrix arrives in) every one of the K right-hand sides would need its own cross-lane reduction per
+// iteration (K halving butterflies: the multi-RHS fused products were bound by exactly that: C3 x 8 at
+// 2.6 products, the BEM fixture at 6.4).  Instead the loaded tile (L * G strips of P rows, 16 bytes per
+// lane and load) goes through LDS once and comes back in a COLUMN-role layout: lane (sp = lane % NS,
+// rg = lane / NS) holds strip sp (E columns) for the L rows rg * L .. rg * L + L - 1 -- the same 16
+// bytes per lane and load, transposed.  The x entries of those L rows stay in registers for the whole
+// piece, the transposed product becomes L * E * K in-lane FMAs like the forward one, and only E * K
+// partial sums per lane are reduced over the RG = 64 / NS lanes of a strip.
+// ----------------------------------------------------------------------------------------
+template <typename T, int L, int K>
+__device__ __forceinline__ void load_x_rows(const PanelSetup<T, K> &ps, const WaveD &wd, const int *__restrict__ rows,
+                                            const T *__restrict__ x, long long ldx, int rg, T (&xrr)[L][K]) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        const int r = rg * L + j;
+        const bool ok = r < ps.m;
+        int ri = 0;
+        if (ok) ri = row_index(wd, rows, r);
+#pragma unroll
+        for (int k = 0; k < K; ++k) xrr[j][k] = ok ? x[ri + ps.kc(k) * ldx] : zero_of(T{});
+    }
+}
+// a lane's 16 bytes (E columns of one row) times the K staged x entries of each of the columns (forward half) ...
+template <typename T, int K> __device__ __forceinline__ void fma_row_role(T (&acc)[K], const Vec16<T> &b, const T *xp, bool cjf) {
+#pragma unroll
+    for (int e = 0; e < TT<T>::E; ++e) {
+        const T bv = cj(b.v[e], cjf);
+#pragma unroll
+        for (int k = 0; k < K; ++k) acc[k] = madd(acc[k], bv, xp[e * K + k]);
+    }
+}
+// ... and times the K x entries of its row, into the lane's E * K column sums (transposed half)
+template <typename T, int K, int EK> __device__ __forceinline__ void fma_col_role(T (&tv)[EK], const Vec16<T> &u, const T (&xr)[K], bool cjf) {
+#pragma unroll
+    for (int e = 0; e < TT<T>::E; ++e) {
+        const T bv = cj(u.v[e], cjf);
+#pragma unroll
+        for (int k = 0; k < K; ++k) tv[e * K + k] = madd(tv[e * K + k], bv, xr[k]);
+    }
+}
+// the forward sums of the 64 / P row groups of a wave, folded onto every lane of a row: what the kernel combines and writes
+template <int P, bool FWD, typename T, int K> __device__ __forceinline__ void fold_row_groups(const T (&acc)[K], T (&out)[K]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        T a = acc[k];
+        if (FWD) {
+#pragma unroll
+            for (int d = P; d < 64; d <<= 1) a = add(a, shx(a, d));
+        }
+        out[k] = a;
+    }
+}
+
+// ----------------------------------------------------------------------------------------
+// The register path: an iteration's tile is loaded into registers, used by row, and turned through LDS for the
+// transposed half.
+// ----------------------------------------------------------------------------------------
+template <typename T, int L, int P, bool FWD, bool TRN, int K>
+__device__ __forceinline__ bool panel_multi(PathTag<MultiPath::Register>, const WaveD &wd, const uint4 *__restrict__ values,
+                                            const int *__restrict__ rows, const int *__restrict__ cols,
+                                            const T *__restrict__ x, long long ldx, T *__restrict__ y, long long ldy,
+                                            T alpha, int flags, int lane, T *xs, Vec16<T> *tile, int *ixm, T (&out)[K]) {
+    PanelSetup<T, K> ps = panel_setup<T, K>(wd, flags);  // (the piece fields follow behind the x rows: load_piece)
+    constexpr int E = TT<T>::E, G = 64 / P, NC = G * L * E, XCH = MultiShape<T, L, TRN, K>::XCH;
+    constexpr int NS = G * L, RG = 64 / NS;
+    constexpr int PM = P + 1;  // strip stride in the LDS tile (16-byte units): conflict-free for both layouts
+    static_assert(XCH % NC == 0, "x chunk must hold whole iterations");
+    static_assert(NS <= 64, "an iteration's strips must fit the wave");
+    const int m = ps.m;
+    const int i = lane & (P - 1), g = lane / P;
+    const int sp = lane % NS, rg = lane / NS;
+    const bool row_ok = i < m;
     T acc[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] = zero_of(T{});
-    // Transposed half, V[w][k] = sum_i B[i][w] * X[row(i)][k].  With the lane on the row (the layout the
-    // matrix arrives in) every one of the K right-hand sides would need its own cross-lane reduction per
-    // iteration (K halving butterflies: the multi-RHS fused products were bound by exactly that: C3 x 8 at
-    // 2.6 products, the BEM fixture at 6.4).  Instead the loaded tile (L * G strips of P rows, 16 bytes per
-    // lane and load) goes through LDS once and comes back in a COLUMN-role layout: lane (sp = lane % NS,
-    // rg = lane / NS) holds strip sp (E columns) for the L rows rg * L .. rg * L + L - 1 -- the same 16
-    // bytes per lane and load, transposed.  The x entries of those L rows stay in registers for the whole
-    // piece, the transposed product becomes L * E * K in-lane FMAs like the forward one, and only E * K
-    // partial sums per lane are reduced over the RG = 64 / NS lanes of a strip.
-    constexpr int NS = G * L;
-    constexpr int RG = 64 / NS;
-    constexpr int PM = P + 1;  // strip stride in the LDS tile (16-byte units): conflict-free for both layouts
+    T xrr[TRN ? L : 1][K];
+    if constexpr (TRN) load_x_rows<T, L, K>(ps, wd, rows, x, ldx, rg, xrr);
+
+    if (ps.live) {
+        load_piece<FWD, TRN>(ps, wd, values, cols);
+        const int nstrips = ps.nstrips, ncols = ps.ncols;
+        // the x slice (forward half) and the y indices (transposed half) of the chunk of columns at c0
+        // (the lane that stages a column writes its K entries 64 / 128 bytes apart from its neighbours': 16- / 32-way bank
+        // conflicts per store -- an XOR swizzle of the slot (k ^ column index within the bank row) was measured: +-0, the
+        // staging is bound by the K x 64 scattered line requests of the gather, not by the LDS)
+        auto stage_columns = [&](int c0) {
+            if (!(ps.fwd_en || (BSM_MULTI_IX && ps.trn_en))) return;
+#pragma unroll
+            for (int q = 0; q < XCH / 64; ++q) {
+                const int c = q * 64 + lane;
+                const int w = c0 + c;
+                if (BSM_DBG(DBG_NO_XGATHER)) {  // (timing probe: no column list, no x loads)
+                    if (BSM_MULTI_IX && TRN) ixm[c] = w < ncols ? w : -1;
+                    if (ps.fwd_en) {
+#pragma unroll
+                        for (int k = 0; k < K; ++k) xs[c * K + k] = zero_of(T{});
+                    }
+                } else if (w < ncols + NC) {
+                    bool ok = w < ncols, off = false;
+                    const int xi = ok ? ps.col_lookup(w, off) : 0;
+                    // the chunk's y indices stay in LDS for the emission of its iterations (-1: the column takes no
+                    // part): read from the column list there, every iteration waited for a dependent load in front
+                    // of its atomics
+                    if (BSM_MULTI_IX && TRN) ixm[c] = (ok && (ps.opT || off)) ? xi : -1;
+                    ok = ok && (!ps.opT || off);
+                    if (ps.fwd_en) {
+#pragma unroll
+                        for (int k = 0; k < K; ++k) xs[c * K + k] = ok ? x[xi + ps.kc(k) * ldx] : zero_of(T{});
+                    }
+                }
+            }
+        };
+        for (int c0 = 0; c0 < ncols; c0 += XCH) {
+            stage_columns(c0);
+            const int s_end = min(nstrips, (c0 + XCH) / E);
+            for (int s0 = c0 / E; s0 < s_end; s0 += G * L) {
+                // (issuing the next iteration's matrix loads before this iteration's arithmetic -- two register
+                // buffers -- was measured here too: C3 x 8 379 -> 462 us, C4 slice x 8 406 -> 570 us)
+                Vec16<T> b[L];
+#pragma unroll
+                for (int l = 0; l < L; ++l) {
+                    const int s = s0 + l * G + g;
+                    if (row_ok && s < nstrips) {
+                        b[l] = load_stream16(&ps.vb[(uint32_t)(s * m + i)]);  // multi-RHS: always with the hint
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < E; ++e) b[l].v[e] = zero_of(T{});
+                    }
+                }
+                if (ps.fwd_en) {
+                    const int cb = (s0 - c0 / E) * E;
+#pragma unroll
+                    for (int l = 0; l < L; ++l) fma_row_role<T, K>(acc, b[l], &xs[(cb + (l * G + g) * E) * K], ps.cjf);
+                }
+                if (!ps.trn_en) continue;
+                // registers (row role) -> LDS -> registers (column role); one wave, LDS runs in order
+#pragma unroll
+                for (int l = 0; l < L; ++l) tile[(l * G + g) * PM + i] = b[l];
+                T tv[E * K];
+#pragma unroll
+                for (int q = 0; q < E * K; ++q) tv[q] = zero_of(T{});
+#pragma unroll
+                for (int j = 0; j < L; ++j) fma_col_role<T, K>(tv, tile[sp * PM + rg * L + j], xrr[j], ps.cjf);
+                int pos = 0, dup = 0;
+                ReduceAbove<T, E * K, NS>::run(tv, lane, pos, dup);
+                constexpr int CF = (E * K / RG) > 1 ? (E * K / RG) : 1;
+                const int s = s0 + sp;  // the lane's strip of the piece
+                if ((lane & dup) != 0 || s >= nstrips) continue;
+#pragma unroll
+                for (int jj = 0; jj < CF; ++jj) {
+                    const int q = pos + jj;
+                    const int e = q / K, k = q % K;
+                    const int w = s * E + e;
+                    if (w < ncols) {
+                        bool off = false;
+                        int yi;
+                        if (BSM_MULTI_IX) {
+                            yi = ixm[w - c0];
+                            off = yi >= 0;
+                        } else {
+                            yi = ps.col_lookup(w, off);
+                            off = ps.opT || off;
+                        }
+                        if (off && k < ps.kact) {
+                            T *yp = &y[yi + k * ldy];
+                            const T val = mul(alpha, tv[jj]);
+                            if (flags & FLAG_RMW)
+                                *yp = add(*yp, val);
+                            else if (!BSM_DBG(DBG_NO_GLOBAL_ATOMICS))
+                                atomic_acc(yp, val);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    fold_row_groups<P, FWD>(acc, out);
+    return false;
+}
+
+// ----------------------------------------------------------------------------------------
+// The tile pipeline (kTilePipe).
+// Fused / transposed multi-RHS products at 2-3 waves per SIMD were bound by the bytes in flight (one
+// 4 KB tile per wave, and only while the wave was not computing: C3 x 8 ran at 2.5 TB/s with the VALU
+// 39 % and the LDS 43 % busy), and a second register tile costs a resident wave.  The tile goes
+// through LDS anyway (transposition above), so it is loaded THERE directly, one iteration ahead, with
+// no register landing: two LDS tiles per wave, global_load_lds into the one while the other is read
+// by row (forward half) and by column (transposed half).  In-order completion of vector memory
+// operations does the bookkeeping: the wait for tile n is `all but tile n+1's loads`, which also
+// covers every older atomic -- so iteration n's y contributions are issued AFTER that wait in
+// iteration n+1 (held in CF registers meanwhile), and nothing else in the loop may load from global
+// memory: a slice's gathered column indices are fetched with its x values and kept (in registers).
+// ----------------------------------------------------------------------------------------
+template <typename T, int L, int P, bool FWD, bool TRN, int K>
+__device__ __forceinline__ bool panel_multi(PathTag<MultiPath::TilePipe>, const WaveD &wd, const uint4 *__restrict__ values,
+                                            const int *__restrict__ rows, const int *__restrict__ cols,
+                                            const T *__restrict__ x, long long ldx, T *__restrict__ y, long long ldy,
+                                            T alpha, int flags, int lane, T *xs, Vec16<T> *tile, int *, T (&out)[K]) {
+    PanelSetup<T, K> ps = panel_setup<T, K>(wd, flags);  // (the piece fields follow behind the x rows: load_piece)
+    constexpr int E = TT<T>::E, G = 64 / P, NC = G * L * E, XCH = MultiShape<T, L, TRN, K>::XCH;
+    constexpr int NS = G * L, RG = 64 / NS, NSI = G * L;
+    constexpr int CF = (E * K / RG) > 1 ? (E * K / RG) : 1;
+    constexpr int NE = CF > K ? CF / K : 1;  // columns (of E) a lane's CF sums belong to
+    static_assert(XCH % NC == 0, "x chunk must hold whole iterations");
     static_assert(NS <= 64, "an iteration's strips must fit the wave");
+    const int m = ps.m, kact = ps.kact;
+    const int i = lane & (P - 1), g = lane / P;
     const int sp = lane % NS, rg = lane / NS;
+    T acc[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = zero_of(T{});
+    T xrr[TRN ? L : 1][K];
+    if constexpr (TRN) load_x_rows<T, L, K>(ps, wd, rows, x, ldx, rg, xrr);
+    if (ps.live) {
+        load_piece<FWD, TRN>(ps, wd, values, cols);
+        const int nstrips = ps.nstrips, ncols = ps.ncols;
+        const int nit = (nstrips + NSI - 1) / NSI;
+        const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)tile);
+        const int hg = tile_swz<P, L>(g);
+        const int cbase = sp * P + ((rg * L) ^ tile_swz<P, L>(sp));
+        auto issue = [&](int it, int buf) {
+            const int s0 = it * NSI;
+#pragma unroll
+            for (int l = 0; l < L; ++l) {
+                if (s0 + l * G < nstrips) {  // wave-uniform: the load is issued, and counted
+                    const int s = s0 + l * G + g;
+                    const int rho = i ^ tile_swz<P, L>(l * G) ^ hg;
+                    if (BSM_DBG(DBG_NO_MATRIX)) {
+                    } else if (rho < m && s < nstrips)
+                        glds16_nt(&ps.vb[(uint32_t)(s * m + rho)], lds0 + (unsigned)((buf * L + l) * 1024));
+                    else
+                        tile[(buf * L + l) * 64 + lane] = Vec16<T>{};
+                } else {
+                    tile[(buf * L + l) * 64 + lane] = Vec16<T>{};
+                }
+            }
+        };
+        auto loads_of = [&](int it) {
+            const int left = nstrips - it * NSI;
+            const int nl = (left + G - 1) / G;
+            return nl < L ? nl : L;
+        };
+        int dq_yi[NE];
+        T dq_val[CF];
+#pragma unroll
+        for (int q = 0; q < NE; ++q) dq_yi[q] = -1;
+        int pos = 0, dup = 0;
+        auto emit = [&]() {
+#pragma unroll
+            for (int jj = 0; jj < CF; ++jj) {
+                const int yi = dq_yi[jj / K];
+                const int k = (pos + jj) % K;
+                // (atomics in coloured launches too: a read-modify-write's load would be waited for with
+                // vmcnt(0) by the compiler, i.e. drain the prefetch every iteration)
+                if (yi >= 0 && k < kact) atomic_acc(&y[yi + k * ldy], mul(alpha, dq_val[jj]));
+            }
+        };
+        // a slice of columns: x values (forward half) and the gathered indices.  The indices stay in
+        // REGISTERS, lane c of cir[q] holding column q * 64 + c of the slice, and are fetched across lanes
+        // (ds_bpermute) when a lane emits: an LDS array of them was the 256 bytes per wave that kept a fourth
+        // workgroup of the 4-column fp64 kernel off the CU.
+        int cir[XCH / 64];
+#pragma unroll
+        for (int q = 0; q < XCH / 64; ++q) cir[q] = 0;
+        auto stage_slice = [&](int c0) {
+#pragma unroll
+            for (int q = 0; q < XCH / 64; ++q) {
+                const int c = q * 64 + lane;
+                const int w = c0 + c;
+                if (ps.xbase < 0) {
+                    // (waited for HERE: a loaded register whose first use lies in the loop body makes hipcc
+                    // wait vmcnt(0) there in every iteration, which drains the prefetched tile)
+                    cir[q] = ps.cols[ps.col_off + min(w, ncols - 1)];
+                    settle(cir[q]);
+                }
+                if (w < ncols + NC) {
+                    bool ok = w < ncols, off = false;
+                    if (ps.fwd_en) {
+                        const int xi = ok ? ps.col_lookup(w, off) : 0;
+                        ok = ok && (!ps.opT || off);
+#pragma unroll
+                        for (int k = 0; k < K; ++k) xs[c * K + k] = ok ? x[xi + ps.kc(k) * ldx] : zero_of(T{});
+                    }
+                }
+            }
+        };
+        // A wave's start is a chain of dependent round trips (descriptor -> row list -> x rows, column list
+        // -> x slice -> first tile), and a panel of the BEM fixture is 3-4 iterations long: the first tile's
+        // loads go out first (they need the descriptor only), the first slice is staged while the x rows
+        // above are still in flight, and only then everything is waited for -- three round trips, not six.
+        if (nit > 0) issue(0, 0);
+        if (nit > 0) stage_slice(0);
+        // the x rows: no load hipcc knows of may be pending inside the loop, or its wait for it (a
+        // vmcnt(0) at the first use, executed every iteration) would drain the prefetched tile
+        if (TRN) {
+#pragma unroll
+            for (int j = 0; j < L; ++j)
+#pragma unroll
+                for (int k = 0; k < K; ++k) settle(xrr[j][k]);
+        }
+        for (int it = 0; it < nit; ++it) {
+            const int buf = it & 1;
+            const int s0 = it * NSI;
+            const int c0 = (s0 * E) / XCH * XCH;
+            if (s0 * E == c0 && it > 0) stage_slice(c0);
+            int younger = 0;
+            if (it + 1 < nit) {
+                issue(it + 1, buf ^ 1);
+                younger = BSM_DBG(DBG_NO_MATRIX) ? 0 : loads_of(it + 1);
+            }
+            vm_wait(younger);
+            if (!BSM_DBG(DBG_NO_GLOBAL_ATOMICS)) emit();  // iteration it-1's sums
+            if (ps.fwd_en && !BSM_DBG(DBG_NO_FWD_HALF)) {
+                const int cb = s0 * E - c0;
+#pragma unroll
+                for (int l = 0; l < L; ++l)
+                    fma_row_role<T, K>(acc, tile[(buf * L + l) * 64 + (lane ^ tile_swz<P, L>(l * G) ^ hg)],
+                                       &xs[(cb + (l * G + g) * E) * K], ps.cjf);
+            }
+            if (!ps.trn_en || BSM_DBG(DBG_NO_TRN_HALF)) continue;
+            T tv[E * K];
+#pragma unroll
+            for (int q = 0; q < E * K; ++q) tv[q] = zero_of(T{});
+#pragma unroll
+            for (int j = 0; j < L; ++j) fma_col_role<T, K>(tv, tile[buf * L * 64 + (cbase ^ j)], xrr[j], ps.cjf);
+            pos = 0, dup = 0;
+            ReduceAbove<T, E * K, NS>::run(tv, lane, pos, dup);
+            const int s = s0 + sp;
+            const bool mine = (lane & dup) == 0 && s < nstrips;
+#pragma unroll
+            for (int q = 0; q < NE; ++q) {
+                const int w = s * E + pos / K + q;
+                int raw = 0;
+                if (ps.xbase < 0) {  // (every lane takes part in the exchange)
+                    const int c = (w - c0) & (XCH - 1);
+#pragma unroll
+                    for (int h = 0; h < XCH / 64; ++h) {
+                        const int v = __shfl(cir[h], c & 63, 64);
+                        if ((c >> 6) == h) raw = v;
+                    }
+                }
+                int yi = -1;
+                if (mine && w < ncols) {
+                    bool off;
+                    if (ps.xbase < 0) {
+                        off = raw >= 0 && (ps.kinds & 3) == KIND_OFF;
+                        yi = raw & 0x7fffffff;
+                    } else {
+                        yi = ps.col_lookup(w, off);
+                    }
+                    if (!(ps.opT || off)) yi = -1;
+                }
+                dq_yi[q] = yi;
+            }
+#pragma unroll
+            for (int jj = 0; jj < CF; ++jj) dq_val[jj] = tv[jj];
+        }
+        emit();
+    }
+    fold_row_groups<P, FWD>(acc, out);
+    return false;
+}
+
+// ----------------------------------------------------------------------------------------
+// The matrix pipe (kMfmaAny; layouts in the comment at kMfmaPath above): row blocks of 16, the x rows of the panel as
+// operands, one accumulator per row block.  The three element classes -- ComplexF64 (MF), ComplexF32 (MF32), real x 16
+// (MFR) -- keep a prologue and a loop each, as they were written: the one loop over an element-type trait that was
+// tried costs <c64, 4, false, true, 8> 235 instructions and <c128, 4, true, true, 8> a spilled dword
+// (docs/experiments_r28.md).  They share the staging, and the epilogue that hands the forward sums on.
+// -> true: the wave has added its forward sums to y itself (accumulate mode); else they are in `out`, lane = row
+// ----------------------------------------------------------------------------------------
+template <typename T, int L, int P, bool FWD, bool TRN, int K>
+__device__ __forceinline__ bool panel_multi(PathTag<MultiPath::MatrixPipe>, const WaveD &wd, const uint4 *__restrict__ values,
+                                            const int *__restrict__ rows, const int *__restrict__ cols,
+                                            const T *__restrict__ x, long long ldx, T *__restrict__ y, long long ldy,
+                                            T alpha, int flags, int lane, T *xs, Vec16<T> *tile, int *ixm, T (&out)[K]) {
+    PanelSetup<T, K> ps = panel_setup<T, K>(wd, flags);  // (the piece fields follow behind the x rows: load_piece)
+    constexpr int E = TT<T>::E;
+    constexpr int G = 64 / P;
+    constexpr int NC = G * L * E;
+    constexpr int XCH = MultiShape<T, L, TRN, K>::XCH;
+    const bool opT = ps.opT, cjf = ps.cjf;
+    const int kact = ps.kact;
+    auto kc = [&](int k) { return ps.kc(k); };
+    const int m = ps.m;
     // matrix-pipe path (above): row blocks of 16, the x rows of the panel as B operands, one accumulator per row block
     constexpr bool MF = kMfmaPath<T, K>;
     constexpr int MR = (P + 15) / 16;
@@ -235,223 +681,13 @@ __device__ __forceinline__ void run_panel_multi(const WaveD &wd, const uint4 *__
             }
         }
     }
-    T xrr[(TRN && !MFA) ? L : 1][K];
-    if (TRN && !MFA) {
-#pragma unroll
-        for (int j = 0; j < L; ++j) {
-            const int r = rg * L + j;
-            const bool ok = r < m;
-            int ri = 0;
-            if (ok) ri = row_index(wd, rows, r);
-#pragma unroll
-            for (int k = 0; k < K; ++k) xrr[j][k] = ok ? x[ri + kc(k) * ldx] : zero_of(T{});
-        }
-    }
-
-    const PieceD pc = wd.first;
-    if (wd.npieces > 0) {
-        const int xbase = pc.xbase;
-        const int col_off = pc.col_off;
-        const int nstrips = pc.nstrips;
-        const int ncols = pc.ncols;
-        // per-column kinds (a symmetric row group holds its diagonal block and its off-diagonal
-        // blocks in one panel): forward uses a column unless (op T/C and it is not KIND_OFF),
-        // transposed uses it iff (op T/C or KIND_OFF)
-        const int kinds = pc.kind;
-        const bool has_off = (kinds & kKindHasOff) != 0;
-        const bool fwd_en = FWD && (!opT || has_off);
-        const bool trn_en = TRN && (opT || has_off);
-        const Vec16<T> *__restrict__ vb = reinterpret_cast<const Vec16<T> *>(
-            values + (((uint64_t)pc.val_hi << 32) | pc.val_lo));
-        const int s1w = wd.seg1_w, s1x = wd.seg1_x - wd.seg1_w;
-        const int s2w = wd.seg2_w, s2x = pc.seg2_x - wd.seg2_w;
-        // -> x / y index of piece column w; `off` tells whether the column is KIND_OFF
-        auto col_lookup = [&](int w, bool &off) -> int {
-            if (xbase < 0) {
-                const int raw = cols[col_off + w];
-                off = raw >= 0 && (kinds & 3) == KIND_OFF;
-                return raw & 0x7fffffff;
-            }
-            const int sh = w < s1w ? 0 : (w < s2w ? 2 : 4);
-            off = ((kinds >> sh) & 3) == KIND_OFF;
-            return w + (w < s1w ? xbase : (w < s2w ? s1x : s2x));
-        };
-
-        if constexpr (PIPE) {
-            // Fused / transposed multi-RHS products at 2-3 waves per SIMD were bound by the bytes in flight (one
-            // 4 KB tile per wave, and only while the wave was not computing: C3 x 8 ran at 2.5 TB/s with the VALU
-            // 39 % and the LDS 43 % busy), and a second register tile costs a resident wave.  The tile goes
-            // through LDS anyway (transposition above), so it is loaded THERE directly, one iteration ahead, with
-            // no register landing: two LDS tiles per wave, global_load_lds into the one while the other is read
-            // by row (forward half) and by column (transposed half).  In-order completion of vector memory
-            // operations does the bookkeeping: the wait for tile n is `all but tile n+1's loads`, which also
-            // covers every older atomic -- so iteration n's y contributions are issued AFTER that wait in
-            // iteration n+1 (held in CF registers meanwhile), and nothing else in the loop may load from global
-            // memory: a slice's gathered column indices are fetched with its x values and kept (in registers).
-            {
-                constexpr int NSI = G * L;
-                constexpr int CF = (E * K / RG) > 1 ? (E * K / RG) : 1;
-                constexpr int NE = CF > K ? CF / K : 1;  // columns (of E) a lane's CF sums belong to
-                const int nit = (nstrips + NSI - 1) / NSI;
-                const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(size_t)tile);
-                const int hg = tile_swz<P, L>(g);
-                const int cbase = sp * P + ((rg * L) ^ tile_swz<P, L>(sp));
-                auto issue = [&](int it, int buf) {
-                    const int s0 = it * NSI;
-#pragma unroll
-                    for (int l = 0; l < L; ++l) {
-                        if (s0 + l * G < nstrips) {  // wave-uniform: the load is issued, and counted
-                            const int s = s0 + l * G + g;
-                            const int rho = i ^ tile_swz<P, L>(l * G) ^ hg;
-                            if (BSM_DBG(DBG_NO_MATRIX)) {
-                            } else if (rho < m && s < nstrips)
-                                glds16_nt(&vb[(uint32_t)(s * m + rho)], lds0 + (unsigned)((buf * L + l) * 1024));
-                            else
-                                tile[(buf * L + l) * 64 + lane] = Vec16<T>{};
-                        } else {
-                            tile[(buf * L + l) * 64 + lane] = Vec16<T>{};
-                        }
-                    }
-                };
-                auto loads_of = [&](int it) {
-                    const int left = nstrips - it * NSI;
-                    const int nl = (left + G - 1) / G;
-                    return nl < L ? nl : L;
-                };
-                int dq_yi[NE];
-                T dq_val[CF];
-#pragma unroll
-                for (int q = 0; q < NE; ++q) dq_yi[q] = -1;
-                int pos = 0, dup = 0;
-                auto emit = [&]() {
-#pragma unroll
-                    for (int jj = 0; jj < CF; ++jj) {
-                        const int yi = dq_yi[jj / K];
-                        const int k = (pos + jj) % K;
-                        // (atomics in coloured launches too: a read-modify-write's load would be waited for with
-                        // vmcnt(0) by the compiler, i.e. drain the prefetch every iteration)
-                        if (yi >= 0 && k < kact) atomic_acc(&y[yi + k * ldy], mul(alpha, dq_val[jj]));
-                    }
-                };
-                // a slice of columns: x values (forward half) and the gathered indices.  The indices stay in
-                // REGISTERS, lane c of cir[q] holding column q * 64 + c of the slice, and are fetched across lanes
-                // (ds_bpermute) when a lane emits: an LDS array of them was the 256 bytes per wave that kept a fourth
-                // workgroup of the 4-column fp64 kernel off the CU.
-                int cir[XCH / 64];
-#pragma unroll
-                for (int q = 0; q < XCH / 64; ++q) cir[q] = 0;
-                auto stage_slice = [&](int c0) {
-#pragma unroll
-                    for (int q = 0; q < XCH / 64; ++q) {
-                        const int c = q * 64 + lane;
-                        const int w = c0 + c;
-                        if (xbase < 0) {
-                            // (waited for HERE: a loaded register whose first use lies in the loop body makes hipcc
-                            // wait vmcnt(0) there in every iteration, which drains the prefetched tile)
-                            cir[q] = cols[col_off + min(w, ncols - 1)];
-                            settle(cir[q]);
-                        }
-                        if (w < ncols + NC) {
-                            bool ok = w < ncols, off = false;
-                            if (fwd_en) {
-                                const int xi = ok ? col_lookup(w, off) : 0;
-                                ok = ok && (!opT || off);
-#pragma unroll
-                                for (int k = 0; k < K; ++k) xs[c * K + k] = ok ? x[xi + kc(k) * ldx] : zero_of(T{});
-                            }
-                        }
-                    }
-                };
-                // A wave's start is a chain of dependent round trips (descriptor -> row list -> x rows, column list
-                // -> x slice -> first tile), and a panel of the BEM fixture is 3-4 iterations long: the first tile's
-                // loads go out first (they need the descriptor only), the first slice is staged while the x rows
-                // above are still in flight, and only then everything is waited for -- three round trips, not six.
-                if (nit > 0) issue(0, 0);
-                if (nit > 0) stage_slice(0);
-                // the x rows: no load hipcc knows of may be pending inside the loop, or its wait for it (a
-                // vmcnt(0) at the first use, executed every iteration) would drain the prefetched tile
-                if (TRN) {
-#pragma unroll
-                    for (int j = 0; j < L; ++j)
-#pragma unroll
-                        for (int k = 0; k < K; ++k) settle(xrr[j][k]);
-                }
-                for (int it = 0; it < nit; ++it) {
-                    const int buf = it & 1;
-                    const int s0 = it * NSI;
-                    const int c0 = (s0 * E) / XCH * XCH;
-                    if (s0 * E == c0 && it > 0) stage_slice(c0);
-                    int younger = 0;
-                    if (it + 1 < nit) {
-                        issue(it + 1, buf ^ 1);
-                        younger = BSM_DBG(DBG_NO_MATRIX) ? 0 : loads_of(it + 1);
-                    }
-                    vm_wait(younger);
-                    if (!BSM_DBG(DBG_NO_GLOBAL_ATOMICS)) emit();  // iteration it-1's sums
-                    if (fwd_en && !BSM_DBG(DBG_NO_FWD_HALF)) {
-                        const int cb = s0 * E - c0;
-#pragma unroll
-                        for (int l = 0; l < L; ++l) {
-                            const Vec16<T> bl = tile[(buf * L + l) * 64 + (lane ^ tile_swz<P, L>(l * G) ^ hg)];
-                            const T *xp = &xs[(cb + (l * G + g) * E) * K];
-#pragma unroll
-                            for (int e = 0; e < E; ++e) {
-                                const T bv = cj(bl.v[e], cjf);
-#pragma unroll
-                                for (int k = 0; k < K; ++k) acc[k] = madd(acc[k], bv, xp[e * K + k]);
-                            }
-                        }
-                    }
-                    if (!trn_en || BSM_DBG(DBG_NO_TRN_HALF)) continue;
-                    T tv[E * K];
-#pragma unroll
-                    for (int q = 0; q < E * K; ++q) tv[q] = zero_of(T{});
-#pragma unroll
-                    for (int j = 0; j < L; ++j) {
-                        const Vec16<T> u = tile[buf * L * 64 + (cbase ^ j)];
-#pragma unroll
-                        for (int e = 0; e < E; ++e) {
-                            const T bv = cj(u.v[e], cjf);
-#pragma unroll
-                            for (int k = 0; k < K; ++k) tv[e * K + k] = madd(tv[e * K + k], bv, xrr[j][k]);
-                        }
-                    }
-                    pos = 0, dup = 0;
-                    ReduceAbove<T, E * K, NS>::run(tv, lane, pos, dup);
-                    const int s = s0 + sp;
-                    const bool mine = (lane & dup) == 0 && s < nstrips;
-#pragma unroll
-                    for (int q = 0; q < NE; ++q) {
-                        const int w = s * E + pos / K + q;
-                        int raw = 0;
-                        if (xbase < 0) {  // (every lane takes part in the exchange)
-                            const int c = (w - c0) & (XCH - 1);
-#pragma unroll
-                            for (int h = 0; h < XCH / 64; ++h) {
-                                const int v = __shfl(cir[h], c & 63, 64);
-                                if ((c >> 6) == h) raw = v;
-                            }
-                        }
-                        int yi = -1;
-                        if (mine && w < ncols) {
-                            bool off;
-                            if (xbase < 0) {
-                                off = raw >= 0 && (kinds & 3) == KIND_OFF;
-                                yi = raw & 0x7fffffff;
-                            } else {
-                                yi = col_lookup(w, off);
-                            }
-                            if (!(opT || off)) yi = -1;
-                        }
-                        dq_yi[q] = yi;
-                    }
-#pragma unroll
-                    for (int jj = 0; jj < CF; ++jj) dq_val[jj] = tv[jj];
-                }
-                emit();
-            }
-        }
-        // the x slice (forward half) and the y indices (transposed half) of the chunk of columns at c0
+    if (ps.live) {
+        load_piece<FWD, TRN>(ps, wd, values, cols);
+        const int nstrips = ps.nstrips;
+        const int ncols = ps.ncols;
+        const bool fwd_en = ps.fwd_en, trn_en = ps.trn_en;
+        const Vec16<T> *vb = ps.vb;
+        auto col_lookup = [&](int w, bool &off) -> int { return ps.col_lookup(w, off); };
         // (matrix-pipe path in accumulate mode: alpha goes into the slice, the forward sums leave from the accumulators)
         const bool fold = MFA && !(flags & (FLAG_DIRECT | FLAG_RMW));
         // (the lane that stages a column writes its K entries 64 / 128 bytes apart from its neighbours': 16- / 32-way bank
@@ -759,87 +995,6 @@ __device__ __forceinline__ void run_panel_multi(const WaveD &wd, const uint4 *__
             }
             if (pending) emit();
         }
-        for (int c0 = 0; !PIPE && !MFA && c0 < ncols; c0 += XCH) {
-            stage_columns(c0);
-            const int s_end = min(nstrips, (c0 + XCH) / E);
-            for (int s0 = c0 / E; s0 < s_end; s0 += G * L) {
-                // (issuing the next iteration's matrix loads before this iteration's arithmetic -- two register
-                // buffers -- was measured here too: C3 x 8 379 -> 462 us, C4 slice x 8 406 -> 570 us)
-                Vec16<T> b[L];
-#pragma unroll
-                for (int l = 0; l < L; ++l) {
-                    const int s = s0 + l * G + g;
-                    if (row_ok && s < nstrips) {
-                        b[l] = load_stream16(&vb[(uint32_t)(s * m + i)]);  // multi-RHS: always with the hint
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < E; ++e) b[l].v[e] = zero_of(T{});
-                    }
-                }
-                if (fwd_en) {
-                    const int cb = (s0 - c0 / E) * E;
-#pragma unroll
-                    for (int l = 0; l < L; ++l) {
-                        const T *xp = &xs[(cb + (l * G + g) * E) * K];
-#pragma unroll
-                        for (int e = 0; e < E; ++e) {
-                            const T bv = cj(b[l].v[e], cjf);
-#pragma unroll
-                            for (int k = 0; k < K; ++k) acc[k] = madd(acc[k], bv, xp[e * K + k]);
-                        }
-                    }
-                }
-                if (trn_en) {
-                    // registers (row role) -> LDS -> registers (column role); one wave, LDS runs in order
-#pragma unroll
-                    for (int l = 0; l < L; ++l) tile[(l * G + g) * PM + i] = b[l];
-                    T tv[E * K];
-#pragma unroll
-                    for (int q = 0; q < E * K; ++q) tv[q] = zero_of(T{});
-#pragma unroll
-                    for (int j = 0; j < L; ++j) {
-                        const Vec16<T> u = tile[sp * PM + rg * L + j];
-#pragma unroll
-                        for (int e = 0; e < E; ++e) {
-                            const T bv = cj(u.v[e], cjf);
-#pragma unroll
-                            for (int k = 0; k < K; ++k) tv[e * K + k] = madd(tv[e * K + k], bv, xrr[j][k]);
-                        }
-                    }
-                    int pos = 0, dup = 0;
-                    ReduceAbove<T, E * K, NS>::run(tv, lane, pos, dup);
-                    constexpr int CF = (E * K / RG) > 1 ? (E * K / RG) : 1;
-                    const int s = s0 + sp;  // the lane's strip of the piece
-                    if ((lane & dup) == 0 && s < nstrips) {
-#pragma unroll
-                        for (int jj = 0; jj < CF; ++jj) {
-                            const int q = pos + jj;
-                            const int e = q / K, k = q % K;
-                            const int w = s * E + e;
-                            if (w < ncols) {
-                                bool off = false;
-                                int yi;
-                                if (BSM_MULTI_IX) {
-                                    yi = ixm[w - c0];
-                                    off = yi >= 0;
-                                } else {
-                                    yi = col_lookup(w, off);
-                                    off = opT || off;
-                                }
-                                if (off && k < kact) {
-                                    T *yp = &y[yi + k * ldy];
-                                    const T val = mul(alpha, tv[jj]);
-                                    if (flags & FLAG_RMW)
-                                        *yp = add(*yp, val);
-                                    else if (!BSM_DBG(DBG_NO_GLOBAL_ATOMICS))
-                                        atomic_acc(yp, val);
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
     }
     if constexpr (MFA) {
         // The forward sums sit in the accumulators TRANSPOSED as well (A = the x slice, B = the tile): lane = (row ln of
@@ -871,8 +1026,7 @@ __device__ __forceinline__ void run_panel_multi(const WaveD &wd, const uint4 *__
                     }
                 }
             }
-            fwd_done = true;
-            return;
+            return true;
         }
         if (FWD) {
             // exclusive launches (plain stores, beta fused, groups combined in LDS by the caller): lane = row, K complex
@@ -904,37 +1058,21 @@ __device__ __forceinline__ void run_panel_multi(const WaveD &wd, const uint4 *__
                 out[k] = a;
             }
         }
-        return;
+        return false;
     }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        T a = acc[k];
-        if (FWD) {
-#pragma unroll
-            for (int d = P; d < 64; d <<= 1) a = add(a, shx(a, d));
-        }
-        out[k] = a;
-    }
+    return false;
 }
 
-// resident workgroups per CU the register allocation must leave room for: 3 for the pipelined fp32 kernels (their
-// LDS admits 3; fused: 189 VGPRs = 2 per CU without the bound, 168 + 16 spilled dwords with it: C3 in fp32 x 8
-// 176 -> 159 us), 2 otherwise (the fp64 ones fit 3 by themselves)
 template <typename T, int L, bool FWD, bool TRN, int K>
-__global__ void __launch_bounds__(64 * kWavesPerWg, ((kMfmaPath32<T, K> || (kMfmaReal<T, K> && sizeof(T) == 4)) ? 4 : ((kTilePipe<T, L, TRN, K> && sizeof(T) == 4) || (kMfmaAny<T, K> && BSM_MFMA_C128_WGS == 3) ? 3 : 2)))
+__global__ void __launch_bounds__(64 * kWavesPerWg, (MultiShape<T, L, TRN, K>::WGS))
     panel_kernel_multi(const WaveWork *__restrict__ waves, const uint4 *__restrict__ values,
                        const int *__restrict__ rows, const int *__restrict__ cols,
                        const T *__restrict__ x, long long ldx, T *__restrict__ y, long long ldy, T alpha,
                        T beta, int flags, unsigned wg_base) {
-    constexpr bool PIPE = kTilePipe<T, L, TRN, K>;
-    constexpr int XCH = PIPE ? x_chunk_cols_pipe<T, L>() : x_chunk_cols_multi<T, K>();
-    constexpr int XS = XCH * K;  // >= 64*K: also holds the combine slab
-    // 16-byte units: max over P of (64 / P) * L strips of P + 1 units; the pipelined kernels hold two tiles
-    // (matrix-pipe kernels: one 16 x 16 tile of elements, column stride 17)
-    constexpr int TILE = PIPE ? 2 * L * 64 : (kMfmaAny<T, K> ? (16 * 17 * (int)sizeof(T) + 15) / 16 : L * 72);
-    __shared__ __attribute__((aligned(16))) T xs[kWavesPerWg][FWD ? XS : 1];
-    __shared__ Vec16<T> tl[kWavesPerWg][TRN ? TILE : 1];
-    __shared__ int ixm[kWavesPerWg][(TRN && !PIPE && BSM_MULTI_IX) ? XCH : 1];  // y indices of the staged chunk (register path)
+    using SH = MultiShape<T, L, TRN, K>;
+    __shared__ __attribute__((aligned(16))) T xs[kWavesPerWg][FWD ? SH::XS : 1];
+    __shared__ Vec16<T> tl[kWavesPerWg][TRN ? SH::TILE : 1];
+    __shared__ int ixm[kWavesPerWg][SH::IXM];
 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -947,18 +1085,19 @@ __global__ void __launch_bounds__(64 * kWavesPerWg, ((kMfmaPath32<T, K> || (kMfm
     for (int k = 0; k < K; ++k) u[k] = zero_of(T{});
     bool fwd_done = false;  // the wave has added its forward sums to y itself (matrix-pipe path, accumulate mode)
     if (work == WORK_PANEL) {
+        constexpr PathTag<SH::path> path{};
         if (m <= 8)
-            run_panel_multi<T, L, 8, FWD, TRN, K>(wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u, fwd_done);
+            fwd_done = panel_multi<T, L, 8, FWD, TRN, K>(path, wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u);
         else if (m <= 16)
-            run_panel_multi<T, L, 16, FWD, TRN, K>(wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u, fwd_done);
+            fwd_done = panel_multi<T, L, 16, FWD, TRN, K>(path, wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u);
         else if (m <= 32)
-            run_panel_multi<T, L, 32, FWD, TRN, K>(wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u, fwd_done);
+            fwd_done = panel_multi<T, L, 32, FWD, TRN, K>(path, wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u);
         else
-            run_panel_multi<T, L, 64, FWD, TRN, K>(wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u, fwd_done);
+            fwd_done = panel_multi<T, L, 64, FWD, TRN, K>(path, wd, values, rows, cols, x, ldx, y, ldy, alpha, flags, lane, xs[wave], tl[wave], ixm[wave], u);
     }
     const bool direct = (flags & FLAG_DIRECT) != 0;
     const bool sz = (flags & FLAG_STRONG_ZERO) != 0;
-    const int kact = ((flags >> FLAG_KACT_SHIFT) & 15) ? ((flags >> FLAG_KACT_SHIFT) & 15) : K;
+    const int kact = kact_of<K>(flags);
     if (FWD) {
         if (wd.wg_sync) {
             // a wave's staged x slice is dead once it has left its loop: reuse it as this wave's

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Developer probe: K right-hand sides through bsm_mul_multi against K single products (and one), on the
-standard operator set.  usage: multirhs.py [name ...]"""
+standard operator set; every figure is the median of three timing windows, with their spread (max - min) / median.
+usage: multirhs.py [name ...]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,7 +23,7 @@ def timed(fn, reps):
         b.record()
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b) * 1e3 / reps)
-    return sorted(ts)[1]
+    return sorted(ts)[1], (max(ts) - min(ts)) / sorted(ts)[1]  # median window, spread of the windows
 
 
 def bem(K, dtype, part):
@@ -66,15 +67,15 @@ for name in names:
     y = torch.zeros_like(x)
     plan = bsm.MulPlan(y, A, x)
     reps = 100 if st["alg_bytes"] < 200e6 else 15
-    t1 = timed(plan, reps)
-    line = f"{name:9s} 1 rhs {t1:8.1f} us ({st['alg_bytes']/t1/1e3:5.0f} GB/s)"
+    t1, sp = timed(plan, reps)
+    line = f"{name:9s} 1 rhs {t1:8.1f} us +-{100 * sp:4.1f} % ({st['alg_bytes']/t1/1e3:5.0f} GB/s)"
     for K in (4, 8, 16):
         X = torch.empty((K, n), dtype=x.dtype, device="cuda").t()  # column-major n x K
         for k in range(K):
             X[:, k] = x * (k + 1)
         Y = torch.zeros((K, n), dtype=x.dtype, device="cuda").t()
-        tk = timed(lambda: bsm.mul(Y, A, X), reps)
-        line += f"   {K} rhs {tk:8.1f} us = {tk/t1:4.2f} x one product"
+        tk, sp = timed(lambda: bsm.mul(Y, A, X), reps)
+        line += f"   {K} rhs {tk:8.1f} us +-{100 * sp:4.1f} % = {tk/t1:4.2f} x one product"
         del X, Y
     print(line, flush=True)
     del plan, A, prob
