@@ -388,7 +388,7 @@ extern "C" int bsm_ctx_create(const int32_t *device_ids, int32_t ndevices, bsm_c
         }
         // direct xGMI access between every pair of distinct devices (the halo copies then run device
         // to device; without it the runtime stages them through host memory, still correct)
-        // (what the fused fan-out kernels of bsm_dist.cpp rely on is that the access was ENABLED, not that it is
+        // (what the fused fan-out kernels of bsm_fanout.cpp rely on is that the access was ENABLED, not that it is
         // possible: only hipSuccess / "already enabled" count, anything else leaves the context on the copy path)
         ctx->peer_ok = true;
         for (int a : ctx->devices)

@@ -1,6 +1,7 @@
-// bsm_internal.h -- what bsm_capi.cpp (the C ABI; single-device handles), bsm_dist.cpp (handles spread over the
-// devices of a bsm_ctx_t), bsm_operator.cpp (the packed operator on one device that both are made of) and the units that
-// hold a feature's own entry points (bsm_entries.cpp, bsm_invert.cpp, bsm_krylov.cpp) share.  Not part of the C ABI.
+// bsm_internal.h -- what bsm_capi.cpp (the C ABI; single-device handles), bsm_dist.cpp / bsm_fanout.cpp (handles spread
+// over the devices of a bsm_ctx_t: building them / issuing their products; their own types are in bsm_dist.h),
+// bsm_operator.cpp (the packed operator on one device that both are made of) and the units that hold a feature's own
+// entry points (bsm_entries.cpp, bsm_invert.cpp, bsm_krylov.cpp) share.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -24,7 +25,7 @@ struct bsm_ctx_s {
 };
 
 namespace bsm {
-struct DistState;  // bsm_dist.cpp
+struct DistState;  // bsm_dist.h
 
 // bsm_update_blocks on one device: the device copy of the refill plans of its images (uploaded at the first update,
 // kept until the handle is destroyed) and the per-call table of source blocks (RefillSrc by input block id) with the
@@ -113,7 +114,7 @@ struct ClaimState {
 
 // The operator of a single-device handle is the handle's base.  Multi-device handles: `an` holds the bookkeeping /
 // statistics of the WHOLE operator, there is no image (device == BSM_DEVICE_NONE) and every part is an operator of
-// its own (bsm_dist.cpp: Part).
+// its own (bsm_dist.h: Part).
 struct bsm_matrix_s : bsm::LocalOperator {
     bool on_device = false;
     // one product in flight per handle on the gather workspace of the images (one-column products) and on the work
@@ -172,16 +173,18 @@ bool capturing(hipStream_t st);
 // regrow frees the old arrays, so no product may still use them.  false: no memory (the arrays are left empty)
 bool il_reserve(ILWork &il, long long need);
 
+// ---- bsm_fanout.cpp: the products of a multi-device handle ---------------------------------------
+int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long long ldx, void *Y, long long ldy,
+                   const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream);
+int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *const *y_parts, const void *alpha,
+                   const void *beta, int beta_strong_zero, void *const *streams);
+
 // ---- bsm_dist.cpp -------------------------------------------------------------------------------
 // Row partition of `in` (already in its final order) over the context's devices; fills A->dist.
 // A->an must already hold the whole operator's bookkeeping (meta-only analysis).
 // ids[b]: input block id of in[b] (bsm_update_blocks)
 int dist_create(bsm_matrix_s *A, bsm_ctx_s *ctx, int mtype, int dtype, int64_t nrows, int64_t ncols,
                 const std::vector<BlockIn> &in, const std::vector<int64_t> &ids, const bsm_options &o);
-int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long long ldx, void *Y, long long ldy,
-                   const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream);
-int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *const *y_parts, const void *alpha,
-                   const void *beta, int beta_strong_zero, void *const *streams);
 void dist_destroy(bsm_matrix_s *A);
 int dist_part_info(bsm_matrix_s *A, int32_t part, bsm_part_info_t *out);
 // bsm_update_blocks of a multi-device handle (arguments checked by the caller; ids 0-based)

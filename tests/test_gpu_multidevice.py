@@ -320,7 +320,7 @@ def test_flag_and_event_ordering_of_the_fan_out(torch_cuda, bsm, oracle, monkeyp
 def test_a_fan_out_that_fails_half_way_leaves_a_usable_handle(torch_cuda, bsm, oracle, monkeypatch, mode):
     """A fan-out that fails between its two phases (injected: bsm_debug_dist_fail_after) may have consumed a sequence
     number whose write packets were never issued.  The library releases every counter from the host, drains the devices
-    and forgets the ordering form (csrc/bsm_dist.cpp: fan_out, the frame of both drivers): the failing call reports an
+    and forgets the ordering form (csrc/bsm_fanout.cpp: fan_out, the frame of both drivers): the failing call reports an
     error, and the products after it neither hang on `flag >= seq` nor accumulate into a half-written work vector.
     Fused path ordered by flags ("1") and by events ("0"); copy path forced with device vectors ("copies") and taken by
     host vectors ("host")."""
@@ -364,7 +364,7 @@ def test_a_fan_out_that_fails_half_way_leaves_a_usable_handle(torch_cuda, bsm, o
 @pytest.mark.parametrize("own_streams", ["0", "1"])
 def test_work_vectors_stay_zero_across_directions_batches_and_paths(torch_cuda, bsm, oracle, monkeypatch, own_streams):
     """The finish kernels write zeros behind what they read, so a product accumulates into its part's work vector
-    without a `w = 0` launch in front (csrc/bsm_dist.cpp: DistState::w_clean).  The invariant has to survive
+    without a `w = 0` launch in front (csrc/bsm_dist.h: Part::w_clean).  The invariant has to survive
     everything that touches those vectors: the two directions of a VBCRS operator (different segments travel), a
     multi-RHS batch that re-allocates them, a copy-path product (host vectors) that leaves partial sums in them,
     NaN in the incoming y, numeric beta -- chained without synchronisation, each against the oracle."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer probe: cost of the in-library multi-device fan-out (bsm_ctx_t, csrc/bsm_dist.cpp) on ONE GPU
+"""Developer probe: cost of the in-library multi-device fan-out (bsm_ctx_t, csrc/bsm_fanout.cpp) on ONE GPU
 listed several times (virtual devices): the same operator as one ordinary handle and spread over 2 / 4
 parts, device-resident and host vectors.  On one GPU the parts share the device, so the kernel time is
 the same; what shows is the fan-out itself (events, peer copies, halo adds, delivery)."""
