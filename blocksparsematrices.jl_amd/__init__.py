@@ -2,10 +2,14 @@
 djukic14/BlockSparseMatrices.jl (BlockSparseMatrix / SymmetricBlockMatrix / VBCRS x vector).
 
 The directory name contains a dot, so import it through the root-level shim:  `import bsm_amd`.
+
+matrices.py: the operator types and products; entries.py: A[I, J], diag and the COO / CSR export; solvers.py: the
+block-Jacobi preconditioner and the Krylov solvers; _marshal.py: the argument marshalling they share; _lib.py: the C ABI.
 """
 from . import _lib  # noqa: F401
+from . import entries, matrices, solvers, synthetic  # noqa: F401
+from .entries import *  # noqa: F401,F403
 from .matrices import *  # noqa: F401,F403
-from .matrices import __all__ as _m_all
-from . import synthetic  # noqa: F401
+from .solvers import *  # noqa: F401,F403
 
-__all__ = list(_m_all) + ["synthetic"]
+__all__ = matrices.__all__ + entries.__all__ + solvers.__all__ + ["synthetic"]

@@ -1,0 +1,417 @@
+"""The block-Jacobi preconditioner (invert_blocks, BlockJacobi, block_jacobi) and the Krylov solvers that run every step
+on the device: the Gram-Schmidt pass krylov_orth, Gmres, and the lockstep solvers Cg, BiCgStab, GmresMulti with their
+one-shot forms.  The solver objects share _Solver: the create and destroy calls and the prelude of solve()."""
+import contextlib
+import ctypes as C
+
+import numpy as np
+
+from . import _lib as L
+from ._marshal import _BlockList, _DT, _TORCH_DT, _blocks_kind, _describe, _elt, _i64, _is_dev, _is_tensor, _like, _p64, _stream_ptr, torch
+from .entries import _out_device, submatrices
+from .matrices import BlockSparseMatrix, SymmetricBlockMatrix, _no_mixed_update, _operator, _unwrap, size, update_blocks
+
+__all__ = ["invert_blocks", "BlockJacobi", "block_jacobi", "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg",
+           "CgInfo", "cg", "cocg", "BiCgStab", "bicgstab", "GmresMulti"]
+
+
+# ---- block-Jacobi: the self-interaction blocks inverted where they are (bsm_invert_blocks) -----------------------------
+def invert_blocks(blocks):
+    """Inverts square column-major blocks IN PLACE (bsm_invert_blocks: Gauss-Jordan with partial row pivoting, one
+    workgroup per block on the device, the same elimination serially for host blocks) -> info, one int64 per block:
+    0, or the 1-based step whose pivot was zero or not finite (that block is then unspecified).  blocks: numpy arrays
+    (Fortran order) or torch CUDA tensors (column-major, e.g. what submatrices(..., device=True) returns) of ONE
+    element type and device, orders 0 .. 1024.  Device blocks go on torch's current stream; the call is synchronous."""
+    blocks = list(blocks)
+    if _is_dev(blocks):
+        kind = _blocks_kind(blocks)
+    else:  # host blocks are inverted where they are: none may need a conversion
+        dt = None
+        for b in blocks:
+            if not (isinstance(b, np.ndarray) and b.ndim == 2 and b.dtype in _DT and b.flags.f_contiguous and b.flags.writeable):
+                raise TypeError("host blocks must be writeable 2-D Fortran-order numpy arrays of a supported element type")
+            if dt is not None and b.dtype != dt:
+                raise TypeError("the blocks must share one element type")
+            dt = b.dtype
+        kind = (dt, False)
+    bl = _BlockList(blocks, kind)
+    bad = np.nonzero(bl.m != bl.n)[0]
+    if len(bad):
+        raise ValueError(f"a block of shape {tuple(blocks[bad[0]].shape)} is not square")
+    info = np.zeros(max(len(bl), 1), dtype=np.int64)
+    if len(bl) == 0:
+        return info[:0]
+    for k in np.nonzero(bl.m == 0)[0]:
+        bl.ptrs[k] = None
+    st = _stream_ptr(None, blocks[0].device) if bl.dev else None
+    L.check(L.lib().bsm_invert_blocks(_DT[bl.dtype], *bl.square_args(), _p64(info), bl.memspace, st))
+    return info
+
+
+def _inverted_blocks(A, sets, stream=None):
+    """[inv(A[I_s, I_s]) for s]: extracted where the image lives and inverted there (device tensors on the handle's first
+    device, numpy arrays for an analysis-only handle)"""
+    base, _ = _unwrap(A)
+    on_dev = base.device is not None or base.devices is not None
+    ctx = contextlib.nullcontext()
+    if on_dev and stream is not None:
+        st = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
+        ctx = torch.cuda.stream(st)  # submatrices and invert_blocks both take torch's current stream
+    with ctx:
+        blocks = submatrices(A, sets, device=on_dev)
+        info = invert_blocks(blocks)
+    bad = np.nonzero(info)[0]
+    if len(bad):
+        raise np.linalg.LinAlgError(f"block_jacobi: A[I, I] of set {int(bad[0]) + 1} is singular to working precision (the pivot of "
+                                    f"elimination step {int(info[bad[0]])} is zero or not finite)")
+    return blocks
+
+
+class BlockJacobi(BlockSparseMatrix):
+    """M = sum_s E_s inv(A[I_s, I_s]) E_s^T -- the block-Jacobi (near-field) preconditioner of A as an ordinary
+    BlockSparseMatrix handle: mul, M @ X, MulPlan, the wrappers, complex vectors under a real M and M[I, J] work as on
+    any other.  Built by block_jacobi(A, sets).  Fields beside BlockSparseMatrix's: `sets` (1-based index arrays) and
+    `source` (the A it was built from)."""
+
+    def __init__(self, A, sets=None, *, storage=None, accumulate="auto", transpose_image=False):
+        base, _ = _operator(A)
+        if sets is None:
+            if not isinstance(base, SymmetricBlockMatrix):
+                raise ValueError("sets=None means the diagonalindices of a SymmetricBlockMatrix; pass index sets for other types")
+            sets = base.diagonalindices
+        m, n = size(A)
+        if m != n:
+            raise ValueError(f"block_jacobi needs a square operator, size(A) = {(m, n)}")
+        self.sets = [_i64(np.asarray(s).reshape(-1)) for s in sets]
+        self.source = A
+        blocks = _inverted_blocks(A, self.sets)
+        dev = L.BSM_DEVICE_NONE if base.device is None and base.devices is None else _out_device(base).index
+        super().__init__(blocks, self.sets, self.sets, (m, n), device=dev, storage=storage, accumulate=accumulate,
+                         transpose_image=transpose_image)
+
+    def refresh(self, A=None, stream=None):
+        """Re-extracts the blocks of A (default: `source`, e.g. after update_blocks(A, ...)), inverts them and pushes them
+        into this handle with update_blocks: no analysis, no reallocation of the image, the tensors of `blocks` stay.  A
+        singular block raises LinAlgError and leaves M as it was; a `storage=` M raises what update_blocks raises."""
+        _no_mixed_update(self)
+        A = self.source if A is None else A
+        if size(A) != self.size:
+            raise ValueError(f"size(A) = {size(A)} but the preconditioner is {self.size}")
+        update_blocks(self, _inverted_blocks(A, self.sets, stream), stream=stream)
+        self.source = A
+
+
+def block_jacobi(A, sets=None, *, storage=None, accumulate="auto", transpose_image=False):
+    """The block-Jacobi preconditioner of A over `sets` (1-based index lists, pairwise disjoint and free of repeats;
+    None: the diagonalindices of a SymmetricBlockMatrix) -> BlockJacobi.  submatrices(A, sets, device=True), invert_blocks
+    and the BlockSparseMatrix constructor from device tensors: no matrix byte crosses PCIe.  An analysis-only A takes
+    the same route on the host and gives an analysis-only M; a multi-device A gives a single-device M on its first
+    device; transpose(A) / adjoint(A) are taken as such; a mixed-storage A gives its stored values widened, inverted in
+    the vector type (storage= here is that of M).  Rows in no set are zero rows of M -- pass singleton sets for
+    point-Jacobi rows.  A singular block raises numpy.linalg.LinAlgError naming the set and the elimination step."""
+    return BlockJacobi(A, sets, storage=storage, accumulate=accumulate, transpose_image=transpose_image)
+
+
+# ---- restarted GMRES on the device (bsm_gmres_*) and its building block (bsm_krylov_orth) ------------------------------
+def krylov_orth_work(dtype, n, k):
+    """Bytes of the `work` array one krylov_orth pass over n entries and k columns of `dtype` needs."""
+    return int(L.lib().bsm_krylov_orth_work(_DT[np.dtype(dtype)], int(n), int(k)))
+
+
+def krylov_orth(V, w, k, hsum, nrm, work=None, stream=None):
+    """One classical Gram-Schmidt pass on the device (bsm_krylov_orth): h = V[:, :k]^H w, w -= V[:, :k] h, hsum[:k] += h,
+    nrm[0] = ||w||.  V: column-major torch CUDA tensor (n x >= k, e.g. torch.empty(cols, ld).t()[:n]), w: n entries of the
+    same type, hsum: >= k entries of it, nrm: one real of its precision, work: a uint8 tensor of krylov_orth_work bytes
+    (None: allocated here).  Enqueued on `stream` (default: torch's current stream); nothing is synchronised."""
+    if torch is None or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (V, w, hsum, nrm)):
+        raise TypeError("krylov_orth takes torch CUDA tensors")
+    dt = _TORCH_DT.get(w.dtype)
+    if dt is None or V.dtype != w.dtype or hsum.dtype != w.dtype:
+        raise TypeError("V, w and hsum must share one supported element type")
+    if _TORCH_DT.get(nrm.dtype) != np.dtype(np.zeros(1, dt).real.dtype):
+        raise TypeError(f"nrm must be one real of the precision of {dt}")
+    if any(t.device != w.device for t in (V, hsum, nrm)):
+        raise ValueError("V, w, hsum and nrm must live on one device")
+    n, k = w.numel(), int(k)
+    if w.dim() != 1 or not w.is_contiguous() or V.dim() != 2 or V.shape[0] != n:
+        raise ValueError(f"DimensionMismatch: w must be a contiguous vector and V have its {n} rows")
+    if not 0 <= k <= min(V.shape[1], L.BSM_GMRES_MAX_RESTART) or hsum.numel() < k or nrm.numel() < 1:
+        raise ValueError(f"k = {k} outside 0 .. min(columns of V, {L.BSM_GMRES_MAX_RESTART}), or hsum shorter than k")
+    if n > 1 and V.stride(0) != 1:
+        raise TypeError("V must be column-major (e.g. torch.empty(cols, ld).t()[:n])")
+    ldv = V.stride(1) if V.shape[1] > 1 else max(n, 1)
+    need = krylov_orth_work(dt, n, k)
+    if work is None:
+        work = torch.empty(need + 16, dtype=torch.uint8, device=w.device)
+    if work.device != w.device or work.numel() * work.element_size() < need:
+        raise ValueError(f"work must hold {need} bytes on the device of w")
+    L.check(L.lib().bsm_krylov_orth(_DT[dt], n, k, V.data_ptr(), ldv, w.data_ptr(), hsum.data_ptr(), nrm.data_ptr(),
+                                    work.data_ptr(), _stream_ptr(stream, w.device)))
+    return w
+
+
+class GmresInfo:
+    """What a solve reports (bsm_gmres_info): status (0 converged, 1 maxiter reached, 2 a non-finite residual),
+    iterations, cycles, residual (absolute estimate), bnorm, a_products, m_products, workspace_bytes, workspace (device
+    address) and history: the absolute estimate after every iteration, a numpy array."""
+
+    def __init__(self, info, history):
+        for name, _ in L.BsmGmresInfo._fields_:
+            setattr(self, name, getattr(info, name))
+        self.history = history
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"GmresInfo(status={self.status}, iterations={self.iterations}, cycles={self.cycles}, "
+                f"residual={self.residual:.3e}, bnorm={self.bnorm:.3e})")
+
+
+def _copy_guess(X, X0):
+    """the initial guess X0 (torch tensor or numpy array, checked) into X, where the solver reads and overwrites it"""
+    if X0 is X:
+        return
+    if _is_tensor(X):
+        X.copy_(X0 if isinstance(X0, torch.Tensor) else torch.from_numpy(X0))
+    else:
+        X[...] = X0.cpu().numpy() if _is_tensor(X0) else X0
+
+
+class _Solver:
+    """What the solver objects share: the checks and the create call (_create), the destroy call, and the prelude of solve().
+    A subclass names its entry points in _abi (_abi + "_create" / "_solve" / "_destroy") and calls _create()."""
+
+    _abi = None
+    _names = ("B", "X")  # what solve() calls its operands
+    _matrices = True  # solve() takes matrices of 1 .. self.nrhs columns beside vectors
+    _x0_refusal = "X0 must have the shape {shape} and the type {dtype}"
+
+    def _create(self, A, M, dtype, args):
+        """the checks and the create call; args(): called once A, M and dtype have passed, gives the arguments of create
+        between the vector type and out"""
+        base, op = _operator(A)
+        mbase, mop = (None, L.BSM_OP_N) if M is None else _operator(M, "M")
+        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
+        if self.dtype not in _DT:
+            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        args = args()
+        self.A, self.M = A, M
+        self.n = size(A)[0]
+        self._base, self._mbase = base, mbase
+        ptr = C.c_void_p()
+        L.check(getattr(L.lib(), self._abi + "_create")(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype],
+                                                        *args, C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                getattr(L.lib(), self._abi + "_destroy")(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def _prelude(self, B, X, X0, stream):
+        """What solve() begins with: B checked, X made like B (None) and checked against it, the guess X0 checked and copied
+        into X, the stream settled -> (X, the descriptors of B and of X (_describe), the stream pointer or None)."""
+        nb, nx = self._names
+        vector = not self._matrices or getattr(B, "ndim", 1) == 1
+        b = _describe(B, self.dtype, self.n, nb, self._base, not vector)
+        if X is None:
+            X = _like(B, self.n, None if vector else b[2])
+        x = _describe(X, self.dtype, self.n, nx, self._base, not vector)
+        if x[2] != b[2]:
+            raise ValueError(f"DimensionMismatch: {nb} and {nx} have different numbers of columns")
+        if b[3] != x[3]:
+            raise ValueError(f"{nb} and {nx} must live in the same memory space")
+        if self._matrices and not 1 <= b[2] <= self.nrhs:
+            raise ValueError(f"{nb} has {b[2]} columns; this solver takes 1 .. {self.nrhs}")
+        if X0 is not None:
+            if _elt(X0) != self.dtype or tuple(X0.shape) != tuple(X.shape):
+                raise TypeError(self._x0_refusal.format(n=self.n, shape=tuple(X.shape), dtype=self.dtype))
+            _copy_guess(X, X0)
+        st = None
+        if b[3] == L.BSM_MEM_DEVICE:
+            st = _stream_ptr(stream, B.device)
+            if stream is not None and X0 is not None and X0 is not X:
+                torch.cuda.current_stream(B.device).synchronize()  # the copy of X0 went on torch's current stream
+        return X, b, x, st
+
+
+class Gmres(_Solver):
+    """Right-preconditioned restarted GMRES(restart) for A x = b, every step of it on the device (bsm_gmres_*: the
+    solver of GmresMulti with one column behind its own info).
+    A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g. block_jacobi(A,
+    sets)), or None.  dtype: the type of b and x -- default A's vector type; a real A (and M) of the same precision
+    takes complex vectors.  The workspace (restart + 3 vectors, restart + 4 with M) is allocated here, once; A and M are
+    kept alive."""
+
+    _abi = "bsm_gmres"
+    _names = ("b", "x")
+    _matrices = False
+    _x0_refusal = "x0 must be a vector of {n} entries of {dtype}"
+
+    def __init__(self, A, M=None, restart=30, dtype=None):
+        self._create(A, M, dtype, lambda: (int(restart),))
+        self.restart = int(restart)
+
+    def solve(self, b, x=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None, stream=None):
+        """-> (x, GmresInfo).  b: torch CUDA tensor (enqueued on `stream`, default torch's current stream) or numpy
+        array (staged); x: where the solution goes (default: a new vector like b); x0: the initial guess (copied into x;
+        None: zero).  Converged when the estimate is <= max(rtol * ||b||, atol); maxiter (default: the order of A)
+        bounds the iterations.  Synchronous."""
+        x, (bp, _, _, bms, _, _), (xp, *_), st = self._prelude(b, x, x0, stream)
+        maxiter = max(self.n, 1) if maxiter is None else int(maxiter)
+        hist = np.zeros(max(maxiter, 1), dtype=np.float64)
+        p = L.BsmGmresParams(C.sizeof(L.BsmGmresParams), 0 if x0 is None else 1, float(rtol), float(atol), maxiter, maxiter)
+        info = L.BsmGmresInfo()
+        L.check(L.lib().bsm_gmres_solve(self._ptr, bp, xp, C.byref(p), C.byref(info), hist.ctypes.data_as(C.POINTER(C.c_double)),
+                                        bms, st))
+        return x, GmresInfo(info, hist[:min(info.iterations, maxiter)].copy())
+
+
+def gmres(A, b, M=None, restart=30, **kw):
+    """One-shot form: Gmres(A, M, restart, dtype of b).solve(b, **kw) -> (x, GmresInfo); a matrix B of k columns goes to
+    GmresMulti(A, M, k, restart, dtype of B).solve(B, **kw) -> (X, CgInfo), its columns advancing in lockstep."""
+    if getattr(b, "ndim", 1) == 2:
+        return GmresMulti(A, M, nrhs=b.shape[1], restart=restart, dtype=_elt(b)).solve(b, **kw)
+    return Gmres(A, M, restart=restart, dtype=_elt(b)).solve(b, **kw)
+
+
+# ---- CG / COCG on several right-hand sides in lockstep, on the device (bsm_cg_*) -------------------------------------------
+_CG_METHODS = {"cg": L.BSM_CG_METHOD_CG, "cocg": L.BSM_CG_METHOD_COCG}
+
+
+class CgInfo:
+    """What a solve reports (bsm_cg_info and the bsm_cg_column entries): status (the largest column status), iterations
+    (the largest column count), columns_converged, a_products, m_products, workspace_bytes, workspace (device address);
+    per column, as numpy arrays of k entries: column_status (0 converged, 1 maxiter reached, 2 a non-finite residual,
+    3 breakdown), column_iterations, residual (absolute, by the recurrence), bnorm; history: (iterations, k), the
+    residual norm of every column after every lockstep iteration (a finished column repeats its last value)."""
+
+    def __init__(self, info, cols, history):
+        for name, _ in L.BsmCgInfo._fields_:
+            setattr(self, name, getattr(info, name))
+        self.column_status = np.array([c.status for c in cols], dtype=np.int64)
+        self.column_iterations = np.array([c.iterations for c in cols], dtype=np.int64)
+        self.residual = np.array([c.residual for c in cols], dtype=np.float64)
+        self.bnorm = np.array([c.bnorm for c in cols], dtype=np.float64)
+        self.history = history
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"CgInfo(status={self.status}, iterations={self.iterations}, columns_converged={self.columns_converged} of "
+                f"{len(self.column_status)}, column_iterations={self.column_iterations.tolist()})")
+
+
+class _LockstepSolver(_Solver):
+    """The solve() of the lockstep solver objects (Cg, BiCgStab, GmresMulti), whose create calls take nrhs_max first."""
+
+    history_capacity = 4096  # rows of CgInfo.history a solve keeps at the most (an attribute: set it on the solver to change it)
+
+    def _setup(self, A, M, nrhs, dtype, extra=lambda: ()):
+        """extra(): called once A, M and dtype have passed, gives the arguments of create between nrhs_max and out"""
+        self._create(A, M, dtype, lambda: (int(nrhs), *extra()))
+        self.nrhs = int(nrhs)
+
+    def solve(self, B, X=None, X0=None, rtol=1e-8, atol=0.0, maxiter=None, stream=None, history=True):
+        """-> (X, CgInfo).  B: a vector (n,) or a column-major matrix (n, k), k <= nrhs -- torch CUDA tensor (enqueued on
+        `stream`, default torch's current stream) or numpy array (staged), taken as mul takes them; X: where the solution
+        goes (default: new, like B); X0: the initial guess (copied into X; None: zero).  Column c is converged when its
+        residual norm is <= max(rtol * ||b_c||, atol); maxiter (default: the order of A) bounds the lockstep iterations.
+        A vector in gives a vector out.  info.history holds the first min(iterations, history_capacity = 4096) rows;
+        history=False keeps none.  Synchronous."""
+        X, (bp, ldb, k, bms, _, _), (xp, ldx, *_), st = self._prelude(B, X, X0, stream)
+        maxiter = max(self.n, 1) if maxiter is None else int(maxiter)
+        cap = min(maxiter, self.history_capacity) if history else 0
+        hist = np.empty((max(cap, 1), k), dtype=np.float64)
+        p = L.BsmCgParams(C.sizeof(L.BsmCgParams), 0 if X0 is None else 1, float(rtol), float(atol), maxiter, cap)
+        info = L.BsmCgInfo()
+        cols = (L.BsmCgColumn * k)()
+        L.check(getattr(L.lib(), self._abi + "_solve")(self._ptr, k, bp, ldb, xp, ldx, C.byref(p), C.byref(info), cols,
+                                                       hist.ctypes.data_as(C.POINTER(C.c_double)), bms, st))
+        return X, CgInfo(info, cols, hist[:min(info.iterations, cap)].copy())
+
+
+class Cg(_LockstepSolver):
+    """Preconditioned conjugate gradients for A X = B with up to `nrhs` right-hand sides advancing in lockstep on ONE
+    multi-column product per iteration, every step on the device (bsm_cg_*).  method="cg": real symmetric / Hermitian
+    positive definite A (and M); method="cocg": complex symmetric ones (the unconjugated form).  The CALLER asserts the
+    symmetry.  A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g.
+    block_jacobi(A, sets)), or None.  dtype: the type of B and X -- default A's vector type; a real A (and M) of the same
+    precision takes complex vectors.  The workspace (4 n x nrhs matrices, 5 with M) is allocated here, once; A and M are
+    kept alive."""
+
+    _abi = "bsm_cg"
+
+    def __init__(self, A, M=None, nrhs=1, dtype=None, method="cg"):
+        def code():
+            if method not in _CG_METHODS:
+                raise ValueError(f"method={method!r}: 'cg' or 'cocg'")
+            return (_CG_METHODS[method],)
+        self._setup(A, M, nrhs, dtype, code)
+        self.method = method
+
+
+def _cg_oneshot(A, B, M, method, kw):
+    k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
+    return Cg(A, M, nrhs=k, dtype=_elt(B), method=method).solve(B, **kw)
+
+
+def cg(A, B, M=None, **kw):
+    """One-shot form: Cg(A, M, columns of B, dtype of B, "cg").solve(B, **kw) -> (X, info)."""
+    return _cg_oneshot(A, B, M, "cg", kw)
+
+
+def cocg(A, B, M=None, **kw):
+    """One-shot form of the unconjugated method for complex symmetric A: Cg(..., method="cocg").solve(B, **kw)."""
+    return _cg_oneshot(A, B, M, "cocg", kw)
+
+
+# ---- BiCGSTAB on several right-hand sides in lockstep, on the device (bsm_bicgstab_*) ---------------------------------------
+class BiCgStab(_LockstepSolver):
+    """Right-preconditioned BiCGSTAB for A X = B with A NOT necessarily symmetric and up to `nrhs` right-hand sides
+    advancing in lockstep on TWO multi-column products per iteration, every step on the device (bsm_bicgstab_*).  A: a
+    block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind and order (e.g. block_jacobi(A, sets)),
+    or None.  dtype: the type of B and X -- default A's vector type; a real A (and M) of the same precision takes complex
+    vectors.  The workspace (6 n x nrhs matrices, 7 with M) is allocated here, once; A and M are kept alive.  solve() is
+    the one Cg has: the same arguments, (X, CgInfo) back; a column that converges after the first half of an iteration reports
+    that half step's residual norm.  info.a_products = 2 * iterations (+ 1 with X0), m_products = 2 * iterations with M."""
+
+    _abi = "bsm_bicgstab"
+
+    def __init__(self, A, M=None, nrhs=1, dtype=None):
+        self._setup(A, M, nrhs, dtype)
+
+
+def bicgstab(A, B, M=None, **kw):
+    """One-shot form: BiCgStab(A, M, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
+    k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
+    return BiCgStab(A, M, nrhs=k, dtype=_elt(B)).solve(B, **kw)
+
+
+# ---- restarted GMRES on several right-hand sides in lockstep, on the device (bsm_gmres_multi_*) ----------------------------
+class GmresMulti(_LockstepSolver):
+    """Right-preconditioned restarted GMRES(restart) for A X = B with up to `nrhs` right-hand sides advancing in lockstep on
+    ONE multi-column product per iteration, every step on the device (bsm_gmres_multi_*): per column the method of Gmres,
+    all columns restarting together.  A: a block matrix or transpose(A) / adjoint(A); M: a preconditioner of the same kind
+    and order (e.g. block_jacobi(A, sets)), or None.  dtype: the type of B and X -- default A's vector type; a real A (and
+    M) of the same precision takes complex vectors.  The workspace (restart + 3 n x nrhs matrices, restart + 4 with M) is
+    allocated here, once; A and M are kept alive.  solve() is the one Cg has: the same arguments, (X, CgInfo) back;
+    info.history holds the residual ESTIMATES, info.cycles = ceil(iterations / restart); statuses 0, 1, 2 (never 3)."""
+
+    _abi = "bsm_gmres_multi"
+
+    def __init__(self, A, M=None, nrhs=1, restart=30, dtype=None):
+        self.restart = int(restart)
+        self._setup(A, M, nrhs, dtype, lambda: (self.restart,))
+
+    def solve(self, B, **kw):
+        X, info = super().solve(B, **kw)
+        info.cycles = -(-int(info.iterations) // self.restart)
+        return X, info

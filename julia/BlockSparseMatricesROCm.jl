@@ -4,7 +4,7 @@
 # this file has never run.  It is the binding a maintainer of BlockSparseMatrices.jl would add (e.g.
 # as a package extension): a matrix opts into the MI355X path through the EXISTING `scheduler=`
 # keyword, so no reference signature changes.  The Python mirror
-# (blocksparsematrices.jl_amd/matrices.py) exercises exactly the same C entry points with the same
+# (blocksparsematrices.jl_amd/matrices.py, entries.py, solvers.py) exercises exactly the same C entry points with the same
 # argument conventions and is what the parity tests run.
 module BlockSparseMatricesROCm
 

@@ -292,3 +292,39 @@ def test_config4_FULL_size_properties_on_one_gpu(torch_cuda, bsm):
     y2 = torch.full_like(x, float("nan"))
     bsm.mul(y2, B, x)
     assert float((y2 - ax).abs().max()) < 1e-5 * scale
+
+
+def test_device_forms_of_the_argument_checks_keep_type_and_message(torch_cuda, bsm):
+    """the refusals of test_marshalling_cpu.py that need device memory to be reached, on one 8 x 8 operator of two 4 x 4 blocks"""
+    torch = torch_cuda
+    idx = [[1, 2, 3, 4], [5, 6, 7, 8]]
+    blocks = [dev_copy(torch, np.arange(16.0).reshape(4, 4) + 4 * np.eye(4)) for _ in range(2)]
+    A = bsm.BlockSparseMatrix(blocks, idx, idx, (8, 8))
+    xd, yd = torch.zeros(8, dtype=torch.float64, device="cuda"), torch.zeros(8, dtype=torch.float64, device="cuda")
+    Xd = torch.zeros((2, 8), dtype=torch.float64, device="cuda").t()
+    V = torch.zeros((3, 8), dtype=torch.float64, device="cuda").t()
+    h, nrm = torch.zeros(3, dtype=torch.float64, device="cuda"), torch.zeros(1, dtype=torch.float64, device="cuda")
+    need = bsm.krylov_orth_work(np.float64, 8, 3)
+    assert need > 0
+    cases = [
+        ("a row-major CUDA block", lambda: bsm.BlockSparseMatrix([blocks[0], blocks[1].contiguous()], idx, idx, (8, 8)), TypeError,
+         "device-resident blocks must be column-major (e.g. torch.empty(n, m).t())"),
+        ("blocks of two types", lambda: bsm.SymmetricBlockMatrix(blocks, idx, [blocks[0].float()], idx[:1], idx[1:], (8, 8)), TypeError,
+         "device-resident blocks must share one supported element type"),
+        ("a host block among device blocks", lambda: bsm.VariableBlockCompressedRowStorage([blocks[0], np.eye(4)], [1, 5], [1, 5], (8, 8)),
+         TypeError, "device-resident blocks must all be 2-D torch CUDA tensors"),
+        ("invert_blocks on a row-major CUDA block", lambda: bsm.invert_blocks([blocks[0].contiguous()]), TypeError,
+         "device-resident blocks must be column-major (e.g. torch.empty(n, m).t())"),
+        ("MulPlan on host vectors", lambda: bsm.MulPlan(np.zeros(8), A, np.zeros(8)), ValueError, "MulPlan needs device-resident x and y"),
+        ("x on the device, y on the host", lambda: bsm.mul(np.zeros(8), A, xd), ValueError, "x and y must live in the same memory space"),
+        ("X on the host, Y on the device", lambda: bsm.mul(Xd, A, np.zeros((8, 2), order="F")), ValueError,
+         "X and Y must live in the same memory space"),
+        ("a work tensor one byte short", lambda: bsm.krylov_orth(V, xd, 3, h, nrm, work=torch.empty(need - 1, dtype=torch.uint8, device="cuda")),
+         ValueError, f"work must hold {need} bytes on the device of w"),
+    ]
+    for what, call, exc, message in cases:
+        with pytest.raises(exc) as ei:
+            call()
+        assert type(ei.value) is exc and str(ei.value) == message, what
+    bsm.mul(yd, A, xd)  # the operands every case refused one of are fine together
+    torch.cuda.synchronize()
