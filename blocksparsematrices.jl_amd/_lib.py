@@ -94,7 +94,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_submatrices", "bsm_diag", "bsm_invert_blocks",
            "bsm_krylov_orth_work", "bsm_krylov_orth", "bsm_gmres_create", "bsm_gmres_solve",
            "bsm_gmres_destroy", "bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy", "bsm_bicgstab_create", "bsm_bicgstab_solve",
-           "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy"]
+           "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy",
+           "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -226,6 +227,12 @@ def lib():
         L.bsm_gmres_multi_solve.argtypes = L.bsm_cg_solve.argtypes
         L.bsm_gmres_multi_destroy.argtypes = [C.c_void_p]
         for name in ("bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "bsm_minres_create") or "BSM_LIB" not in os.environ:  # (the structs are those of bsm_cg_*)
+        L.bsm_minres_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bsm_minres_solve.argtypes = L.bsm_cg_solve.argtypes
+        L.bsm_minres_destroy.argtypes = [C.c_void_p]
+        for name in ("bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy"):
             getattr(L, name).restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p

@@ -1,5 +1,5 @@
 // bsm_lockstep.h -- the host side that the lockstep solver objects (bsm_cg.cpp: bsm_cg_*, bsm_bicgstab.cpp: bsm_bicgstab_*,
-// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*; include/bsm_rocm.h) share: what a solver object
+// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*, bsm_minres.cpp: bsm_minres_*; include/bsm_rocm.h) share: what a solver object
 // holds whatever its method, the (handle, vector) pairings and the multi-column product on the workspace, create from the
 // refusals to the one device allocation (lockstep_create: a method writes its layout once, as a function on a Carve), the
 // start of x, the ring of pinned record slots (RecordRing), what the host takes from a record and reports from the last
@@ -43,7 +43,8 @@ struct LockstepSolver {
     void *ws = nullptr;
     int64_t ws_bytes = 0;
     CgState *state = nullptr;
-    CgRecord *slots = nullptr;  // pinned, kLockstepRing of them
+    const CgRecord *rec = nullptr;  // the device record of a method with a state of its own (null: state->rec)
+    CgRecord *slots = nullptr;      // pinned, kLockstepRing of them
     hipEvent_t ev[kLockstepRing] = {};
     // BSM_MEM_HOST solves: device copies of B and X (n x kmax), allocated at the first one
     void *hb = nullptr, *hx = nullptr;
@@ -256,7 +257,7 @@ template <typename Iterate>
 int lockstep_run(LockstepSolver *S, const CgDims &d, void *X, int64_t ldx, void *wsX, const bsm_cg_params &p, bsm_cg_info &info,
                  bsm_cg_column *cols, double *history, hipStream_t st, Iterate &&iterate) {
     const int64_t maxiter = std::min<int64_t>(p.maxiter, INT32_MAX);
-    RecordRing ring{S, &S->state->rec, st};
+    RecordRing ring{S, S->rec ? S->rec : &S->state->rec, st};
     HIP_TRY(ring.post());
     const CgRecord *last = nullptr;
     for (int64_t enq = 0;;) {

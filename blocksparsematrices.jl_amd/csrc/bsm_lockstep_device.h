@@ -1,5 +1,5 @@
 // bsm_lockstep_device.h -- the one home of the device-side pieces the solver kernel units share (bsm_cg.hip, bsm_bicgstab.hip,
-// bsm_gmres_multi.hip; bsm_krylov.hip takes the access and the sums): the 16-byte access with the guarded read of a caller's
+// bsm_gmres_multi.hip, bsm_minres.hip; bsm_krylov.hip takes the access and the sums): the 16-byte access with the guarded read of a caller's
 // column, the arithmetic on one 16-byte group, the wave / workgroup sums, the fixed-order sum of a column's partials, the
 // decision of a column with its first tolerance, the carry-over of a frozen column, a workgroup's row range and the dispatch
 // of a launch on the vector type.  Every helper adds to each accumulator exactly the fma sequence written in it -- the

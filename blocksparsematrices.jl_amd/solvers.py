@@ -1,5 +1,5 @@
 """The block-Jacobi preconditioner (invert_blocks, BlockJacobi, block_jacobi) and the Krylov solvers that run every step
-on the device: the Gram-Schmidt pass krylov_orth, Gmres, and the lockstep solvers Cg, BiCgStab, GmresMulti with their
+on the device: the Gram-Schmidt pass krylov_orth, Gmres, and the lockstep solvers Cg, BiCgStab, Minres, GmresMulti with their
 one-shot forms.  The solver objects share _Solver: the create and destroy calls and the prelude of solve()."""
 import contextlib
 import ctypes as C
@@ -393,6 +393,33 @@ def bicgstab(A, B, M=None, **kw):
     """One-shot form: BiCgStab(A, M, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
     k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
     return BiCgStab(A, M, nrhs=k, dtype=_elt(B)).solve(B, **kw)
+
+
+# ---- MINRES on several right-hand sides in lockstep, on the device (bsm_minres_*) -------------------------------------------
+# (Minres and minres are exported by the package by name, __init__.py: the set of names a star-import gives is pinned by
+# tests/test_marshalling_cpu.py and stays as it was)
+class Minres(_LockstepSolver):
+    """Symmetric-preconditioned MINRES for A X = B with A real symmetric / Hermitian and NOT necessarily definite, and up to
+    `nrhs` right-hand sides advancing in lockstep on ONE multi-column product per iteration, every step on the device
+    (bsm_minres_*).  The CALLER asserts the symmetry of A, and that M is symmetric / Hermitian POSITIVE definite (e.g.
+    block_jacobi of a definite sibling of A); an indefinite M ends a column with status 3.  A: a block matrix or
+    transpose(A) / adjoint(A); M: a preconditioner of the same kind and order, or None.  dtype: the type of B and X --
+    default A's vector type; a real A (and M) of the same precision takes complex vectors.  The workspace (7 n x nrhs
+    matrices, 9 with M) is allocated here, once; A and M are kept alive.  solve() is the one Cg has: the same arguments,
+    (X, CgInfo) back; the residual norms are those of the carried residual b - A x in the 2-norm (without M they never grow; with M
+    MINRES minimises the M-norm and the 2-norm may rise from one iteration to the next).
+    info.a_products = iterations (+ 1 with X0), m_products = iterations + 1 with M."""
+
+    _abi = "bsm_minres"
+
+    def __init__(self, A, M=None, nrhs=1, dtype=None):
+        self._setup(A, M, nrhs, dtype)
+
+
+def minres(A, B, M=None, **kw):
+    """One-shot form: Minres(A, M, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
+    k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
+    return Minres(A, M, nrhs=k, dtype=_elt(B)).solve(B, **kw)
 
 
 # ---- restarted GMRES on several right-hand sides in lockstep, on the device (bsm_gmres_multi_*) ----------------------------

@@ -849,6 +849,65 @@ int bsm_gmres_multi_solve(struct bsm_gmres_multi_s *S, int32_t nrhs, const void 
                           double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
 int bsm_gmres_multi_destroy(struct bsm_gmres_multi_s *S);
 
+/* bsm_minres_*: symmetric-preconditioned MINRES (Paige and Saunders) for SYMMETRIC / HERMITIAN operators that need NOT be
+ * definite -- shifted or Helmholtz-like near fields, saddle-point couplings --, nrhs = 1 .. BSM_CG_MAX_RHS right-hand sides in
+ * lockstep, wholly on the device.  The short recurrence for what bsm_cg breaks down or diverges on and bsm_gmres_multi takes
+ * with restart + 3 matrices: 7 work vectors per right-hand side (9 with M) whatever the iteration count, a residual norm
+ * that does not grow (without M; with M it is the M-norm that is minimised), and ONE multi-column product op(A) Z per iteration (bsm_mul_multi: the matrix is streamed once per
+ * batch of columns).  Parameters, info and columns are those of bsm_cg_*.
+ * (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+ *   Method, per column c.  Every scalar is REAL and held in the real type of vdtype; <u, v> is the real part of
+ *   sum conj(u_i) v_i.  opM(M) must be symmetric / Hermitian POSITIVE definite (right preconditioning would not keep the
+ *   symmetry); THE CALLER asserts that and the symmetry of op(A), as for bsm_cg.
+ *     v_old = w_old = w = 0;  r = v = b - op(A) x0 (or b);  z = opM(M) v (or v);  gamma = sqrt<v, z>;  gamma_old = 1;
+ *     eta = gamma;  s_old = s = 0;  c_old = c = 1
+ *     repeat:  q = op(A) z;  delta = <z, q> / (gamma gamma);  ig = 1 / gamma
+ *              v_new = (ig q - (delta ig) v) - (gamma / gamma_old) v_old
+ *              z_new = opM(M) v_new (or v_new);  gamma_new = sqrt<v_new, z_new>
+ *              a0 = c delta - c_old s gamma;  a1 = sqrt(a0 a0 + gamma_new gamma_new);  a2 = s delta + c_old c gamma;
+ *              a3 = s_old gamma;  ia = 1 / a1;  c_new = a0 ia;  s_new = gamma_new ia
+ *              w_new = ((ig z - a3 w_old) - a2 w) ia;  x += (c_new eta) w_new;  eta_new = -s_new eta
+ *              r = (s_new s_new) r + (c_new eta_new / gamma_new) v_new   (gamma_new == 0: r = (s_new s_new) r);  rn = ||r||_2
+ *              (v_old, v, z, w_old, w, gamma_old, gamma, eta, c_old, c, s_old, s) <- (v, v_new, z_new, w, w_new, gamma,
+ *              gamma_new, eta_new, c, c_new, s, s_new)
+ *   z is kept unnormalised: the 1 / gamma factors ride in the scalars, no pass scales a vector.  r is the CARRIED residual
+ *   b - op(A) x of the unpreconditioned system, and column c is converged when rn_c <= tol_c = max(rtol * ||b_c||_2, atol),
+ *   the rule of the other lockstep solvers -- not |eta|, which with M is the residual in the M-norm.  The starting residual is
+ *   checked too (0 iterations; a zero column ends there with x = 0).
+ * create: one device allocation on A's device, reported in info: X, R, V0, V1, W0, W1, Q (and Z0, Z1 with M) as n x nrhs_max
+ *   column-major with the leading dimension rounded up to whole 16-byte groups, the per-workgroup partial sums, the column
+ *   states; a ring of pinned record slots and events.  v_new is written into the storage of v_old, w_new into that of
+ *   w_old, z_new beside z (w_new needs z after gamma_new is known); the host swaps the pointers by the parity of the
+ *   iteration.  vdtype and the (handle, vector) pairings are those of bsm_cg_create.  The handles must outlive the solver.
+ *   Refusals: those of bsm_cg_create but the method.
+ * solve: B, X, ldb, ldx, use_x0, memspace, stream, history layout, cols and the refusals as in bsm_cg_solve.
+ *   Kernels (csrc/bsm_minres.hip), vector launches as (row ranges, columns): mr_start (r = v, the shares of ||b||^2 and
+ *   ||r||^2, the zero vectors), mr_dot (<z, q>, <v_new, z_new>: one partial per workgroup and column), mr_lanczos (v_new;
+ *   without M the shares of ||v_new||^2), mr_update (every workgroup derives gamma_new and the rotation from the partials
+ *   and the state; w_new, x, r in one pass, the shares of ||r||^2), mr_decide (one wave per column: the decision, the state
+ *   of the next iteration, the record).  Per iteration: product A, mr_dot, mr_lanczos, [product M, mr_dot,] mr_update,
+ *   mr_decide.  No floating-point atomic, nobody waits, and a launch never reads a scalar that the same launch replaces
+ *   (two slots alternating by iteration parity; mr_update leaves the rotation it derived beside them for mr_decide).
+ *   The decisions are taken ON THE DEVICE: rn not finite: status 2;  rn <= tol_c: status 0;  breakdown, status 3: <v, z> of
+ *   the start not a positive finite number while rn > tol_c, <v_new, z_new> negative or not finite (M is not positive
+ *   definite, or op(A) holds NaN / Inf), a1 not a positive finite number -- in these two the iteration is not counted and x,
+ *   r keep what the last complete iteration left --, gamma_new == 0 while rn > tol_c.  No division by zero and no root of a
+ *   negative number is executed.  A column that has a status is FROZEN from the next launch on: its workgroups return before
+ *   their first vector load, x and r do not change again whatever the host enqueues.  The host enqueues iteration j + 1
+ *   before it waits for the record of iteration j and stops when no column is running or maxiter is reached: X, every
+ *   column's iterations and history do not depend on how late it notices.  Columns still running after maxiter lockstep
+ *   iterations report status 1.
+ *   history[it * nrhs + c] = rn_c after iteration it + 1, it < history_capacity; a frozen column repeats its last value.
+ *   info: status = the largest column status; iterations = the largest column count; a_products = iterations (+ 1 with
+ *   use_x0) and m_products = iterations + 1 with M, 0 without; a solve that ends before maxiter has paid at most one product
+ *   of A and one of M beyond these counts, for the iteration enqueued ahead of the last record. */
+struct bsm_minres_s;
+int bsm_minres_create(bsm_matrix_t A, int opA, bsm_matrix_t M, int opM, int vdtype, int32_t nrhs_max, struct bsm_minres_s **out);
+int bsm_minres_solve(struct bsm_minres_s *S, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_cg_params *p,
+                     bsm_cg_info *info, bsm_cg_column *cols /* nrhs, may be NULL */,
+                     double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
+int bsm_minres_destroy(struct bsm_minres_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

@@ -743,4 +743,41 @@ function bicgstab!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; M=nothing, rtol
     return X, info, columns, history[:, 1:min(info.iterations, maxiter)]
 end
 
+"""
+    minres!(X, A, B; M=nothing, rtol=1e-8, atol=0.0, maxiter=size(A, 1), x0=false) -> (X, info, columns, history)
+
+Symmetric-preconditioned MINRES for `A X = B` with `A` real symmetric or Hermitian and not necessarily definite, and 1 to
+16 right-hand sides advancing in lockstep on one multi-column product per iteration, every step of it on the device
+(bsm_minres_create / _solve / _destroy).  The caller asserts the symmetry of `A` and that `M` is symmetric / Hermitian
+positive definite.  `B` and `X` are host vectors or matrices of `A`'s element type, or complex ones of its precision under
+real `A` and `M`.  Column `c` is converged when the 2-norm of its carried residual `b - A x` is
+`<= max(rtol * norm(B[:, c]), atol)`.  `info`, `columns` and `history` are those of [`cg!`](@ref): `columns[c].status` 0
+converged, 1 `maxiter` reached, 2 a non-finite residual, 3 breakdown (an indefinite `M`, a singular `A`);
+`info.a_products == info.iterations`.  (The reference offers nothing here: a `LinearMap` is handed to a Julia solver
+package, whose Krylov loop runs on the host.)
+"""
+function minres!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; M=nothing, rtol::Real=1e-8, atol::Real=0.0,
+                 maxiter::Integer=size(A, 1), x0::Bool=false) where {T<:ROCmEltype}
+    n, k = size(B, 1), size(B, 2)
+    size(A, 1) == size(A, 2) == n && size(X) == size(B) || throw(DimensionMismatch("minres! needs a square operator and B, X of its order"))
+    1 <= k <= 16 || throw(ArgumentError("minres! takes 1 to 16 right-hand sides"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = M === nothing ? C_NULL : handle(_base(M)).ptr
+    _check(ccall((:bsm_minres_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), mptr, M === nothing ? 0 : _op(M), _DTYPE[T], k, out))
+    p = BsmCgParams(sizeof(BsmCgParams), x0, rtol, atol, maxiter, maxiter)
+    info = BsmCgInfo(0, 0, 0, 0, 0, 0, 0)
+    columns = Vector{BsmCgColumn}(undef, k)
+    history = zeros(Float64, k, max(maxiter, 1))
+    ld = max(n, 1)
+    try
+        GC.@preserve A M X B columns history _check(ccall((:bsm_minres_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{BsmCgParams}, Ref{BsmCgInfo}, Ptr{BsmCgColumn}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+            out[], k, pointer(B), ld, pointer(X), ld, p, info, columns, history, 0, C_NULL))
+    finally
+        ccall((:bsm_minres_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return X, info, columns, history[:, 1:min(info.iterations, maxiter)]
+end
+
 end # module
