@@ -121,6 +121,11 @@ inline int lockstep_init(LockstepSolver *S, const char *what, bsm_matrix_s *A, i
         return fail(BSM_ERR_INVALID, "a handle's vector type must be vdtype, or real and unmixed of the same precision under a complex vdtype");
     if (A->dist || (M && M->dist)) return fail(BSM_ERR_UNSUPPORTED, std::string("multi-device handles are not supported by ") + what);
     if (!A->on_device || (M && !M->on_device)) return fail(BSM_ERR_DEVICE, "handle has no device image (created with BSM_DEVICE_NONE)");
+    // a handle that owns a row range only (one rank's share of a row partition) scales the owned rows of y alone: the other
+    // rows of a product on the workspace would keep what the previous iteration left there
+    for (const bsm_matrix_s *H : {A, M})
+        if (H && (H->img.own_lo > 0 || H->img.own_hi < H->img.nrows))
+            return fail(BSM_ERR_UNSUPPORTED, std::string("handles that own a row range only (bsm_options.own_lo / own_hi) are not supported by ") + what);
     if (M && M->img.device != A->img.device) return fail(BSM_ERR_INVALID, "A and M live on different devices");
     S->A = A, S->M = M, S->opA = opA, S->opM = opM, S->vt = vdtype, S->kmax = nrhs_max, S->device = A->img.device;
     S->a_cvec = pa == 1, S->m_cvec = pm == 1;

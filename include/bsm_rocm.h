@@ -572,7 +572,8 @@ int bsm_krylov_orth(int dtype, int64_t n, int64_t k, const void *V, int64_t ldv,
  *   vdtype (BSM_F32 .. BSM_C128) is the type of b and x.  Each of A, M must have that vector type -- a mixed-storage
  *   handle counts with its double vectors -- or be a real, unmixed handle of the same precision under a complex vdtype,
  *   which is then driven through bsm_mul_cvec.  The handles must outlive the solver.  Refusals: null A or out, bad op / vdtype, a type pair not named above, op(A) not square, M of another
- *   order or on another device, restart < 1 or > BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID; a multi-device handle:
+ *   order or on another device, restart < 1 or > BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID; a multi-device handle, or one
+ *   that owns a row range only (bsm_options.own_lo / own_hi: its products define the owned rows of y alone):
  *   BSM_ERR_UNSUPPORTED; an analysis-only handle: BSM_ERR_DEVICE.
  * solve: b, x of n elements, any element alignment: they are touched only by the start (b is read, x too with use_x0 != 0)
  *   and by the final copy-out of the n entries of x.  Converged when the estimate is <= max(rtol * ||b||_2, atol).  maxiter
@@ -650,7 +651,8 @@ int bsm_gmres_destroy(struct bsm_gmres_s *S);
  *   vectors) goes through bsm_mul_multi, a real unmixed handle of the same precision under a complex vdtype through
  *   bsm_mul_multi_cvec (one column is bsm_mul / bsm_mul_cvec: the same entry).  The handles must outlive the solver.
  *   Refusals: null A or out, bad op / vdtype / method, another pairing, op(A) not square, M of another order or on another
- *   device, nrhs_max outside 1 .. BSM_CG_MAX_RHS: BSM_ERR_INVALID; a multi-device handle: BSM_ERR_UNSUPPORTED; an
+ *   device, nrhs_max outside 1 .. BSM_CG_MAX_RHS: BSM_ERR_INVALID; a multi-device handle, or one that owns a row range
+ *   only (bsm_options.own_lo / own_hi: its products define the owned rows of y alone): BSM_ERR_UNSUPPORTED; an
  *   analysis-only handle: BSM_ERR_DEVICE.
  * solve: B (n x nrhs, leading dimension ldb) and X (ldx), column-major, ldb / ldx >= max(n, 1), any element alignment.
  *   They are touched only by the start (B is read, X too with use_x0 != 0) and by the final copy-out, which writes the n
@@ -747,8 +749,9 @@ int bsm_cg_destroy(struct bsm_cg_s *S);
  *   bsm_cg_create: a handle of that vector type (a mixed-storage handle counts with its double vectors) goes through
  *   bsm_mul_multi, a real unmixed handle of the same precision under a complex vdtype through bsm_mul_multi_cvec.  The
  *   handles must outlive the solver.  Refusals: null A or out, bad op / vdtype, another pairing, op(A) not square, M of
- *   another order or on another device, nrhs_max outside 1 .. BSM_CG_MAX_RHS: BSM_ERR_INVALID; a multi-device handle:
- *   BSM_ERR_UNSUPPORTED; an analysis-only handle: BSM_ERR_DEVICE.
+ *   another order or on another device, nrhs_max outside 1 .. BSM_CG_MAX_RHS: BSM_ERR_INVALID; a multi-device handle, or
+ *   one that owns a row range only (bsm_options.own_lo / own_hi): BSM_ERR_UNSUPPORTED; an analysis-only handle:
+ *   BSM_ERR_DEVICE.
  * solve: B (n x nrhs, leading dimension ldb) and X (ldx), column-major, ldb / ldx >= max(n, 1), any element alignment.
  *   They are touched only by the start (B is read, X too with use_x0 != 0) and by the final copy-out, which writes the n
  *   rows of the nrhs columns of X and nothing else.  use_x0 == 0: the solve starts from zero (NaN in the incoming X does
@@ -811,7 +814,8 @@ int bsm_bicgstab_destroy(struct bsm_bicgstab_s *S);
  *   groups (basis vector i of ALL columns is one such matrix, so op(A) V_j is a plain multi-column product), per column the
  *   small arrays of a cycle and the per-workgroup partial sums of a pass, the column states; a ring of pinned record slots
  *   and events.  vdtype and the (handle, vector) pairings are those of bsm_cg_create.  The handles must outlive the solver.
- *   Refusals: those of bsm_cg_create, and restart outside 1 .. BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID.
+ *   Refusals: those of bsm_cg_create (a handle that owns a row range only among them), and restart outside 1 ..
+ *   BSM_GMRES_MAX_RESTART: BSM_ERR_INVALID.
  * solve: B, X, ldb, ldx, use_x0, memspace, stream, history layout, cols and the refusals as in bsm_cg_solve.
  *   Kernels (csrc/bsm_gmres_multi.hip), vector launches as (row ranges, columns): gm_start (r = B - op(A) X -> V_0, the shares
  *   of ||r||^2 and ||b||^2), gm_begin (V_0 /= beta; g = beta e_1; the decision of a start), per iteration [product M,] product
@@ -879,7 +883,7 @@ int bsm_gmres_multi_destroy(struct bsm_gmres_multi_s *S);
  *   states; a ring of pinned record slots and events.  v_new is written into the storage of v_old, w_new into that of
  *   w_old, z_new beside z (w_new needs z after gamma_new is known); the host swaps the pointers by the parity of the
  *   iteration.  vdtype and the (handle, vector) pairings are those of bsm_cg_create.  The handles must outlive the solver.
- *   Refusals: those of bsm_cg_create but the method.
+ *   Refusals: those of bsm_cg_create but the method (a handle that owns a row range only among them).
  * solve: B, X, ldb, ldx, use_x0, memspace, stream, history layout, cols and the refusals as in bsm_cg_solve.
  *   Kernels (csrc/bsm_minres.hip), vector launches as (row ranges, columns): mr_start (r = v, the shares of ||b||^2 and
  *   ||r||^2, the zero vectors), mr_dot (<z, q>, <v_new, z_new>: one partial per workgroup and column), mr_lanczos (v_new;

@@ -238,6 +238,29 @@ def third_iterate_spread(orders=8):
     return a, worst
 
 
+# ---- what the GPU suite accepts (test_gpu_bicgstab.py; the solver table of _lockstep.py) ------------------------------------
+def check_columns(info, runs, D, x, B, tols, what):
+    """every column: status 0, the twin's count (+-1: the multi-column product rounds differently from one column, the
+    twin's count is stable under permuted sums -- test_bicgstab_cpu.py), true residual <= 2 tol evaluated in complex128"""
+    x = np.asarray(x).reshape(len(D), -1)
+    for c, run in enumerate(runs):
+        true = true_residual(D, x[:, c], B[:, c])
+        print(f"BICGSTAT {what} column {c}: {info.column_iterations[c]} iterations, twin {run.iterations}, true residual / tol "
+              f"{true / tols[c] if tols[c] else 0:.3f}")
+        assert run.status == 0, (what, c, "the twin did not converge")
+        assert info.column_status[c] == 0, (what, c, info.column_status[c])
+        assert abs(int(info.column_iterations[c]) - run.iterations) <= 1, (what, c, info.column_iterations[c], run.iterations)
+        assert true <= 2 * tols[c], (what, c, true, tols[c])
+    assert info.iterations == max(info.column_iterations) and info.status == 0 and info.columns_converged == len(runs)
+
+
+def check_products(info, has_m, use_x0=False):
+    """the documented counts: two A products per lockstep iteration (one more for the residual of an initial guess), two M
+    products per iteration"""
+    assert info.a_products == 2 * info.iterations + (1 if use_x0 else 0)
+    assert info.m_products == (2 * info.iterations if has_m else 0)
+
+
 # ---- raw ctypes drivers --------------------------------------------------------------------------------------------------
 def raw_bicgstab_create(A, opA, M, opM, code, nrhs_max):
     """bsm_bicgstab_create as C sees it -> (return code, solver pointer); a created solver is destroyed by the caller"""

@@ -210,6 +210,29 @@ def column_tol(b, rtol, atol=0.0):
     return max(rtol * float(np.linalg.norm(np.asarray(b).astype(np.complex128))), atol)
 
 
+# ---- what the GPU suite accepts (test_gpu_cg.py; the solver table of _lockstep.py) ------------------------------------------
+def check_columns(info, runs, D, x, B, tols, what):
+    """every column: status 0, the twin's count (+-1: the multi-column product rounds differently from one column, the
+    twin's count is stable under permuted sums -- test_cg_cpu.py), true residual <= 2 tol evaluated in complex128"""
+    x = np.asarray(x).reshape(len(D), -1)
+    for c, run in enumerate(runs):
+        true = true_residual(D, x[:, c], B[:, c])
+        print(f"CGSTAT {what} column {c}: {info.column_iterations[c]} iterations, twin {run.iterations}, true residual / tol "
+              f"{true / tols[c] if tols[c] else 0:.3f}")
+        assert run.status == 0, (what, c, "the twin did not converge")
+        assert info.column_status[c] == 0, (what, c, info.column_status[c])
+        assert abs(int(info.column_iterations[c]) - run.iterations) <= 1, (what, c, info.column_iterations[c], run.iterations)
+        assert true <= 2 * tols[c], (what, c, true, tols[c])
+    assert info.iterations == max(info.column_iterations) and info.status == 0 and info.columns_converged == len(runs)
+
+
+def check_products(info, has_m, use_x0=False):
+    """the documented counts: one A product per lockstep iteration (one more for the residual of an initial guess), one
+    M product per iteration and one for the first z"""
+    assert info.a_products == info.iterations + (1 if use_x0 else 0)
+    assert info.m_products == (info.iterations + 1 if has_m else 0)
+
+
 # ---- raw ctypes drivers --------------------------------------------------------------------------------------------------
 def raw_cg_create(A, opA, M, opM, code, nrhs_max, method=CG):
     """bsm_cg_create as C sees it -> (return code, solver pointer); a created solver is destroyed by the caller"""

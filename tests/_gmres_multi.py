@@ -23,8 +23,9 @@ import ctypes as C
 
 import numpy as np
 
-from _cg import MAX_RHS, BlockDiagonal
-from _krylov import MAX_RESTART, real_of
+from _cg import MAX_RHS, NB, BlockDiagonal, column_tol
+from _jacobi import DTYPES, KINDS, NOP, uniform
+from _krylov import MAX_RESTART, expected_products, real_of, true_residual
 from _lockstep import MARGIN, deviation, krylov_grid, reference_of
 
 GRID_RESTART = 3  # of the grid tests: maxiter = GRID_ITS takes one restart, with its op(A) X product and the second start
@@ -216,6 +217,37 @@ def check_history(h, status, residual, tol, restart, dtype):
         assert np.all(c[1:] <= c[:-1] * (1 + slack)), ("history rises inside a cycle", c0, float(np.max(c[1:] / c[:-1]) - 1))
 
 
+# ---- the order-400 columns and what the GPU suite accepts (test_gpu_gmres_multi.py; the solver table of _lockstep.py) ----
+def columns400(kind, dtype):
+    """five uniform right-hand sides of order 400 for krylov_problem(kind, dtype)"""
+    rng = np.random.default_rng(9000 + 4 * KINDS.index(kind) + DTYPES.index(dtype))
+    return np.asfortranarray(uniform(rng, (NOP, NB), dtype))
+
+
+def products(info, restart, use_x0, has_m):
+    """(a_products, m_products) by the documented formula (_krylov.expected_products on the largest count), plus the one
+    true-residual product of a restart BEHIND the last iteration where a column was still running there and froze on that
+    restart's true residual (its `residual` is then not its last estimate)"""
+    its = int(info.iterations)
+    a, m = expected_products(its, cycles_of(its, restart), use_x0, has_m)
+    late = its > 0 and its % restart == 0 and any(
+        info.column_status[c] == 0 and info.column_iterations[c] == its and info.residual[c] != info.history[its - 1, c]
+        for c in range(len(info.column_status)))
+    return a + (1 if late else 0), m
+
+
+def slack_of(twin_iterations):
+    """what test_gpu_gmres.py's check_against_twin allows above the twin's count"""
+    return max(2, twin_iterations // 10)
+
+
+def check_columns(info, runs, D, xh, B, rtol, what):
+    for c, run in enumerate(runs):
+        assert info.column_status[c] == 0 and run.status == 0, (what, c)
+        assert int(info.column_iterations[c]) <= run.iterations + slack_of(run.iterations), (what, c)
+        assert true_residual(D, xh[:, c], B[:, c]) <= 2 * column_tol(B[:, c], rtol), (what, c)
+
+
 # ---- raw ctypes drivers --------------------------------------------------------------------------------------------------
 def raw_gm_create(A, opA, M, opM, code, nrhs_max, restart):
     """bsm_gmres_multi_create as C sees it -> (return code, solver pointer); a created solver is destroyed by the caller"""
@@ -246,6 +278,6 @@ def raw_gm_solve(ptr, nrhs, B, ldb, X, ldx, rtol=1e-8, atol=0.0, maxiter=100, us
     return rc, info, cols, hist
 
 
-__all__ = ["GRID_ITS", "GRID_RESTART", "MARGIN", "MAX_RESTART", "MAX_RHS", "ORDERS", "GmTwin", "check_history", "cycles_of",
-           "gmres_multi_twin", "grid_spread", "raw_gm_create", "raw_gm_destroy", "raw_gm_solve", "reference", "spread",
-           "workspace_bytes"]
+__all__ = ["GRID_ITS", "GRID_RESTART", "MARGIN", "MAX_RESTART", "MAX_RHS", "ORDERS", "GmTwin", "check_columns", "check_history",
+           "columns400", "cycles_of", "gmres_multi_twin", "grid_spread", "products", "raw_gm_create", "raw_gm_destroy", "raw_gm_solve",
+           "reference", "slack_of", "spread", "workspace_bytes"]

@@ -134,6 +134,36 @@ def expected_products(iterations, cycles, use_x0, has_m):
     return a, (iterations + cycles) if has_m else 0
 
 
+# ---- what the GPU suite accepts (test_gpu_gmres.py; the solver table of _lockstep.py) -------------------------------------
+def check_history(info, tol, restart, dtype):
+    """len(history) == iterations; a solve that converged on an ESTIMATE ends on an entry <= tol with every earlier one
+    above it (one that converged on the true residual at a restart -- info.residual is then not the last entry -- has
+    every entry above tol and that residual <= tol); inside each cycle the history does not rise.
+    |g[j + 1]| = |s| |g[j]|.  Real types: s = +-hn / hypot(t, hn) and hypot(t, hn) >= hn, so |s| <= 1 in floating point
+    too: no slack.  Complex types: s = (a / |a|) hn / r carries the rounded phase -- |a| and the final modulus are hypots
+    (1 ulp = eps each), the divisions and the rounding of s eps / 2 each, the complex product conj(s) g sqrt(2) eps: under
+    5 eps(T) relative in all; 8 eps(T) is allowed."""
+    h = info.history
+    assert len(h) == info.iterations
+    if info.status == 0 and info.iterations:
+        if info.residual == h[-1]:
+            assert h[-1] <= tol and np.all(h[:-1] > tol)
+        else:
+            assert info.residual <= tol and np.all(h > tol)
+    slack = 8 * float(np.finfo(dtype).eps) if np.dtype(dtype).kind == "c" else 0.0
+    for c0 in range(0, len(h), restart):
+        c = h[c0:c0 + restart]
+        assert np.all(c[1:] <= c[:-1] * (1 + slack)), ("history rises inside a cycle", c0, float(np.max(c[1:] / c[:-1]) - 1))
+    assert info.cycles == -(-info.iterations // restart)
+
+
+def check_against_twin(info, twin, what):
+    assert twin.status == 0, (what, "the twin did not converge")
+    slack = max(2, twin.iterations // 10)
+    print(f"KRYSTAT gmres {what}: {info.iterations} iterations, twin {twin.iterations}")
+    assert info.iterations <= twin.iterations + slack, (what, info.iterations, twin.iterations)
+
+
 # ---- raw ctypes drivers --------------------------------------------------------------------------------------------------
 def raw_orth_work(code, n, k):
     from bsm_amd import _lib as L

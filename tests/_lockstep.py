@@ -20,10 +20,10 @@ Units.  An iterate's deviation is max|x - x_ref| in eps max|x_ref|, a history's 
 import numpy as np
 
 from _bicgstab import bicgstab_twin
-from _cg import MAX_RHS, BlockDiagonal, cg_twin, is_complex, spd_problem
+from _cg import MAX_RHS, BlockDiagonal, cg_twin, column_tol, is_complex, spd_problem
 from _gpu import dev_mat, outside_bytes
 from _jacobi import uniform
-from _krylov import real_of, rtol_of, wide_of
+from _krylov import real_of, rtol_of, true_residual, wide_of
 
 METHODS = ["cg", "cocg", "bicgstab"]
 RANGE_BYTES = 8192  # of one column, per workgroup: 512 sixteen-byte groups (krylov_grid)
@@ -272,3 +272,190 @@ def solve_in_guarded_buffers(torch, bsm, S, B, kmax, X0=None, **kw):
     assert outside_bytes(xbuf, n, n + 1, k, off=1) == before[1], "X was written outside its n x nrhs window"
     assert bbuf.cpu().numpy().tobytes() == before[2], "B was written"
     return X.cpu().numpy(), info
+
+
+# ---- the solver table (test_solver_handles_cpu.py, test_gpu_solver_handles.py) -------------------------------------------
+# One row per device solver: what a test that runs EVERY solver on some kind of handle needs of it -- the order-400 problem
+# of its own suite, its numpy twin, its Python class, the kinds it admits, the acceptance helper of its GPU suite (moved
+# into its _*.py module unchanged) and the rtol of that suite's test against the twin.  The rows hide the solvers' calling
+# conventions behind case() / runs() / make() / solve() / accept(); nothing here is looser or tighter than the suites.
+# D2 = D1 + W diag(SHIFT * J) W of the update legs.  Stale values of A show at any shift (true residuals 1e9 tolerances off);
+# a stale M shows in the COUNT only, and a uniform shift mostly rescales the block inverse, which CG does not see: at 8, 16
+# and 32 the twins of cg, cocg and bicgstab with the old block inverse stay within +-1 of the fresh ones; at 64 they leave
+# it by one, at 128 by 3 .. 5 (MINRES by 17 .. 20, GMRES(20) stagnates).  test_solver_handles_cpu.py asserts the margins.
+SHIFT = 128.0
+WIDE_TYPES = [np.float64, np.complex128]
+SINGLE_TYPES = [np.float32, np.complex64]
+
+
+class Case:
+    """p: the problem of A; pm: the problem M is built from (p itself; MINRES: the definite sibling); sets; D, P: their
+    dense forms; B: the right-hand sides (n x NB, GMRES: n x 1); w: the problem's power-of-two row scaling (ones where
+    it has none); sign: +-1 per row, the pattern J of the MINRES problem (ones elsewhere)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def row_scaling(seed, n, dtype):
+    """w of _cg.cg_problem / _bicgstab.bicgstab_problem / _minres.minres_problem, which keep it to themselves: their draws
+    replayed (the sets, G, then one exponent per set) -> (w, sets)"""
+    from _submat import cut
+    rng = np.random.default_rng(seed)
+    sets = cut(rng, n)
+    uniform(rng, (n, n), dtype)
+    w = np.ones(n)
+    for s in sets:
+        w[s - 1] = 2.0 ** int(rng.integers(-3, 4))
+    return w, sets
+
+
+class Solver:
+    def __init__(self, name, problem, twin, cls, kinds, accept, rtol, maxiter=100, complex_kinds=None, real=True, nrhs=5,
+                 restart=None, method=None, passes=None, m_passes=False):
+        self.name, self.problem, self.twin, self.cls, self.kinds, self.check, self.rtol = name, problem, twin, cls, kinds, accept, rtol
+        self.maxiter, self.complex_kinds, self.real, self.nrhs = maxiter, kinds if complex_kinds is None else complex_kinds, real, nrhs
+        self.restart, self.method = restart, method
+        # passes(info, first): info.a_products of a solve cut at the count of the free-running `first`, as the equality of
+        # the solver's own pass-count test states it (None: its suite has no such test); m_passes: that test counts M too
+        self.passes, self.m_passes = passes, m_passes
+
+    def kinds_of(self, dtype):
+        return self.complex_kinds if is_complex(dtype) else (self.kinds if self.real else [])
+
+    def cases(self, types=WIDE_TYPES, kinds=None):
+        return [(self.name, k, dt) for dt in types for k in self.kinds_of(dt) if kinds is None or k in kinds]
+
+    def case(self, kind, dtype):
+        from _krylov import krylov_problem
+        from _submat import Truth
+        n = 400
+        if self.name in ("gmres", "gmres_multi"):
+            from _gmres_multi import columns400
+            p, sets, b = krylov_problem(kind, dtype)
+            D = Truth(p).D
+            B = columns400(kind, dtype) if self.name == "gmres_multi" else np.asfortranarray(b.reshape(-1, 1))
+            return Case(p=p, pm=p, sets=sets, D=D, P=D, B=B, w=np.ones(n), sign=np.ones(n))
+        if self.name == "minres":
+            p, pp, sets, D, P, B = self.problem(kind, dtype)
+            w, wsets = row_scaling(4000, n, dtype)
+            sign = np.ones(n)
+            for k, s in enumerate(sets):
+                sign[s - 1] = 1.0 if k % 2 == 0 else -1.0
+        else:
+            p, sets, D, B = self.problem(kind, dtype, is_complex(dtype)) if self.name == "cg" else self.problem(kind, dtype)
+            w, wsets = row_scaling(6000 if self.name == "bicgstab" else 4000, n, dtype)
+            pp, P, sign = p, D, np.ones(n)
+        assert all(np.array_equal(a, b) for a, b in zip(sets, wsets))
+        return Case(p=p, pm=pp, sets=sets, D=D, P=P, B=B, w=w, sign=sign)
+
+    def runs(self, D, B, Minv, dtype, rtol=None):
+        """the twin on every column of B"""
+        rtol = self.rtol(dtype) if rtol is None else rtol
+        cols = [np.ascontiguousarray(B[:, c]) for c in range(B.shape[1])]
+        if self.name in ("cg", "cocg"):
+            return [self.twin(D, b, Minv, self.name == "cg", rtol, 0.0, self.maxiter, dtype) for b in cols]
+        if self.name in ("gmres", "gmres_multi"):
+            return [self.twin(D, b, Minv, self.restart, rtol, self.maxiter, dtype) for b in cols]
+        return [self.twin(D, b, Minv, rtol, 0.0, self.maxiter, dtype) for b in cols]
+
+    def make(self, bsm, A, M, nrhs=None, dtype=None):
+        kw = dict(dtype=dtype)
+        if self.restart is not None:
+            kw["restart"] = self.restart
+        if self.method is not None:
+            kw["method"] = self.method
+        if self.name != "gmres":
+            kw["nrhs"] = self.nrhs if nrhs is None else nrhs
+        return getattr(bsm, self.cls)(A, M, **kw)
+
+    def solve(self, S, Bd, **kw):
+        """-> (X, info) of S.solve on a column-major device matrix Bd (GMRES: on its one column) at this row's rtol / maxiter"""
+        kw.setdefault("rtol", self.rtol(np.dtype(S.dtype)))
+        kw.setdefault("maxiter", self.maxiter)
+        return S.solve(Bd[:, 0] if self.name == "gmres" else Bd, **kw)
+
+    def slack(self, twin_iterations):
+        """(below, above): how far a count may lie from the twin's under this row's acceptance"""
+        if self.name in ("gmres", "gmres_multi"):
+            return twin_iterations, max(2, twin_iterations // 10)
+        return 1, 1
+
+    def accept(self, info, runs, D, X, B, what, rtol=None):
+        """the acceptance of this solver's own suite on the columns B.shape[1] of a solve; prints the worst figures first"""
+        rtol = self.rtol(np.dtype(B.dtype)) if rtol is None else rtol
+        X = np.asarray(X).reshape(D.shape[0], -1)
+        k = B.shape[1]
+        tols = [column_tol(B[:, c], rtol) for c in range(k)]
+        its = [int(info.iterations)] if self.name == "gmres" else [int(v) for v in info.column_iterations]
+        worst = max(true_residual(D, X[:, c], B[:, c]) / tols[c] for c in range(k))
+        print(f"HANDSTAT {self.name} {what}: worst true residual / tol {worst:.3f}, iterations {its}, twin {[r.iterations for r in runs]}")
+        if self.name == "gmres":
+            assert info.status == 0 and info.converged
+            assert true_residual(D, X[:, 0], B[:, 0]) <= 2 * tols[0], (what, worst)
+            self.check(info, runs[0], what)
+        elif self.name == "gmres_multi":
+            self.check(info, runs, D, X, B, rtol, what)
+        else:
+            self.check(info, runs, D, X, B, tols, what)
+        return worst
+
+
+_solvers = {}
+
+
+def solvers():
+    """name -> Solver.  Built at the first call: _gmres_multi.py imports this module"""
+    if not _solvers:
+        import _bicgstab
+        import _cg
+        import _gmres_multi
+        import _krylov
+        import _minres
+        three, two = ["vbcrs", "blocksparse", "symmetric"], ["vbcrs", "blocksparse"]
+        rows = [
+            Solver("cg", _cg.cg_problem, _cg.cg_twin, "Cg", three, _cg.check_columns, rtol_of, complex_kinds=two, method="cg",
+                   passes=lambda info, first: info.iterations),
+            Solver("cocg", _cg.cg_problem, _cg.cg_twin, "Cg", three, _cg.check_columns, rtol_of, real=False, method="cocg",
+                   passes=lambda info, first: info.iterations),
+            Solver("bicgstab", _bicgstab.bicgstab_problem, _bicgstab.bicgstab_twin, "BiCgStab", two, _bicgstab.check_columns, rtol_of,
+                   passes=lambda info, first: 2 * info.iterations),
+            Solver("minres", _minres.minres_problem, _minres.minres_twin, "Minres", three, _minres.check_columns, rtol_of, maxiter=200,
+                   complex_kinds=two, passes=lambda info, first: info.iterations, m_passes=True),
+            Solver("gmres_multi", _krylov.krylov_problem, _gmres_multi.gmres_multi_twin, "GmresMulti", three, _gmres_multi.check_columns,
+                   rtol_of, restart=_krylov.RESTART, passes=lambda info, first: first.a_products),
+            Solver("gmres", _krylov.krylov_problem, _krylov.gmres_twin, "Gmres", three, _krylov.check_against_twin, rtol_of, nrhs=1,
+                   restart=_krylov.RESTART),
+        ]
+        _solvers.update({r.name: r for r in rows})
+    return _solvers
+
+
+def solver_cases(types=WIDE_TYPES, kinds=None, names=None):
+    """[(solver name, kind, dtype)] of the table, solver by solver"""
+    return [c for r in solvers().values() if names is None or r.name in names for c in r.cases(types, kinds)]
+
+
+def case_id(c):
+    return "-".join([c[0], c[1], np.dtype(c[2]).name] + [str(v) for v in c[3:]])
+
+
+def shifted(case, shift=SHIFT):
+    """the update legs' second set of values -> Case(ids, new: the 1-based ids and new values of the blocks of p that change;
+    mids, mnew: those of pm; p2, pm2: the problems with them in place; D2, P2: their dense forms).  D2 = D + W diag(shift *
+    sign) W, P2 = P + W diag(shift) W; only the blocks that hold a diagonal entry change (_values.diagonal_shift)"""
+    from _submat import Truth
+    from _values import diagonal_shift, src_list, with_values
+
+    def one(p, d):
+        ids, new = diagonal_shift(p, d)
+        vals = list(src_list(p))
+        for i, b in zip(ids, new):
+            vals[i - 1] = b
+        p2 = with_values(p, vals)
+        return ids, new, p2, Truth(p2).D
+    ids, new, p2, D2 = one(case.p, shift * case.sign * case.w * case.w)
+    if case.pm is case.p:
+        return Case(ids=ids, new=new, mids=ids, mnew=new, p2=p2, pm2=p2, D2=D2, P2=D2)
+    mids, mnew, pm2, P2 = one(case.pm, shift * case.w * case.w)
+    return Case(ids=ids, new=new, mids=mids, mnew=mnew, p2=p2, pm2=pm2, D2=D2, P2=P2)

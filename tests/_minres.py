@@ -21,7 +21,7 @@ import numpy as np
 
 from _cg import MAX_RHS, NB, NCG, BlockDiagonal, CgTwin, is_complex
 from _jacobi import set_blocks, uniform
-from _krylov import real_of
+from _krylov import real_of, true_residual
 from _submat import cut
 
 
@@ -222,6 +222,27 @@ def indef_case(n, dtype):
         p, Dop, ps, Dsib = indef_problem(rng, n, dtype)
         _cases[key] = (p, Dop, ps, Dsib, np.asfortranarray(uniform(rng, (n, MAX_RHS), dtype)))
     return _cases[key]
+
+
+# ---- what the GPU suite accepts (test_gpu_minres.py; the solver table of _lockstep.py) --------------------------------------
+def check_columns(info, runs, D, x, B, tols, what):
+    """every column: status 0, the twin's count (+-1: the multi-column product rounds differently from one column, the
+    twin's count is stable under permuted sums -- test_minres_cpu.py), true residual <= 2 tol evaluated in complex128"""
+    x = np.asarray(x).reshape(D.shape[0], -1)
+    for c, run in enumerate(runs):
+        true = true_residual(D, x[:, c], B[:, c])
+        print(f"MRSTAT {what} column {c}: {info.column_iterations[c]} iterations, twin {run.iterations}, true residual / tol "
+              f"{true / tols[c] if tols[c] else 0:.3f}")
+        assert run.status == 0, (what, c, "the twin did not converge")
+        assert info.column_status[c] == 0, (what, c, info.column_status[c])
+        assert abs(int(info.column_iterations[c]) - run.iterations) <= 1, (what, c, info.column_iterations[c], run.iterations)
+        assert true <= 2 * tols[c], (what, c, true, tols[c])
+    assert info.iterations == max(info.column_iterations) and info.status == 0 and info.columns_converged == len(runs)
+
+
+def check_products(info, has_m, use_x0=False):
+    assert info.a_products == info.iterations + (1 if use_x0 else 0)
+    assert info.m_products == (info.iterations + 1 if has_m else 0)
 
 
 # ---- raw ctypes drivers --------------------------------------------------------------------------------------------------

@@ -42,6 +42,41 @@ def new_values(p, rng):
     return out
 
 
+def block_indices(p):
+    """[(rows, cols)] of every block of p in constructor order (src_list's), 1-based"""
+    if p["kind"] == "vbcrs":
+        return [(np.arange(r0, r0 + b.shape[0]), np.arange(c0, c0 + b.shape[1]))
+                for b, r0, c0 in zip(p["blocks"], p["rowstart"], p["colstart"])]
+    pairs = [(np.asarray(r), np.asarray(c)) for r, c in zip(p["rowindices"], p["colindices"])]
+    if p["kind"] == "symmetric":
+        return [(np.asarray(d), np.asarray(d)) for d in p["diagonalindices"]] + pairs
+    return pairs
+
+
+def diagonal_shift(p, d):
+    """the blocks of p + diag(d) that differ from p's -> (1-based ids in constructor order, their new values): entry (i, i)
+    takes d[i] in the FIRST block that holds it (blocks may overlap: their values sum), every other block keeps its values
+    and is not listed.  A square host problem whose every diagonal entry with d != 0 lies in some block, and for the
+    symmetric kind in a diagonal block (a mirrored off-diagonal one would count it twice)"""
+    src, idx = src_list(p), block_indices(p)
+    nd = len(p["diagonals"]) if p["kind"] == "symmetric" else len(src)
+    done = np.zeros(p["size"][0], dtype=bool)
+    ids, out = [], []
+    for k, (b, (r, c)) in enumerate(zip(src, idx)):
+        a, q = np.nonzero(r[:, None] == c[None, :])
+        take = ~done[r[a] - 1]
+        if not take.any():
+            continue
+        assert k < nd, "a diagonal entry lies in an off-diagonal block only"
+        new = np.array(b, order="F", copy=True)
+        new[a[take], q[take]] += np.asarray(d)[r[a[take]] - 1].astype(b.dtype)
+        done[r[a[take]] - 1] = True
+        ids.append(k + 1)
+        out.append(new)
+    assert np.all(done | (np.asarray(d) == 0)), "a shifted diagonal entry lies in no block"
+    return ids, out
+
+
 def update_rc(A, ids, blocks, lds, memspace=MEM_HOST, stream=None, nupd=None):
     """bsm_update_blocks straight through the C ABI (1-based ids or None; numpy or CUDA-tensor blocks; nupd: the count
     passed in place of len(blocks)) -> its return code"""

@@ -6,8 +6,9 @@ import numpy as np
 import pytest
 
 from _bicgstab import (BI_KINDS, EDGE, EDGE_IDS, ERR_INVALID, ERR_UNSUPPORTED, MAX_RHS, NB, NBI, SIGMA_ZERO, TS_ZERO, bicgstab_problem,
-                       bicgstab_twin, breakdown_problem, column_tol, edge_case, edge_problem, exact_minv, is_complex, raw_bicgstab_create,
-                       raw_bicgstab_destroy, raw_bicgstab_solve, rtol_of, staggered, third_iterate_spread, true_residual)
+                       bicgstab_twin, breakdown_problem, check_columns, check_products, column_tol, edge_case, edge_problem, exact_minv,
+                       is_complex, raw_bicgstab_create, raw_bicgstab_destroy, raw_bicgstab_solve, rtol_of, staggered, third_iterate_spread,
+                       true_residual)
 from _ctors import ctor_build
 from _gpu import dev_copy, dev_mat, outside_bytes, torch_cuda, torch_dtype  # noqa: F401
 from _jacobi import CODE, DTYPES, uniform
@@ -34,28 +35,6 @@ def twins():
             out[key] = (D, B, Minv, [bicgstab_twin(D, B[:, c], Minv, rtol_of(dtype), 0.0, 100, dtype) for c in range(NB)])
         return out[key]
     return get
-
-
-def check_columns(info, runs, D, x, B, tols, what):
-    """every column: status 0, the twin's count (+-1: the multi-column product rounds differently from one column, the
-    twin's count is stable under permuted sums -- test_bicgstab_cpu.py), true residual <= 2 tol evaluated in complex128"""
-    x = np.asarray(x).reshape(len(D), -1)
-    for c, run in enumerate(runs):
-        true = true_residual(D, x[:, c], B[:, c])
-        print(f"BICGSTAT {what} column {c}: {info.column_iterations[c]} iterations, twin {run.iterations}, true residual / tol "
-              f"{true / tols[c] if tols[c] else 0:.3f}")
-        assert run.status == 0, (what, c, "the twin did not converge")
-        assert info.column_status[c] == 0, (what, c, info.column_status[c])
-        assert abs(int(info.column_iterations[c]) - run.iterations) <= 1, (what, c, info.column_iterations[c], run.iterations)
-        assert true <= 2 * tols[c], (what, c, true, tols[c])
-    assert info.iterations == max(info.column_iterations) and info.status == 0 and info.columns_converged == len(runs)
-
-
-def check_products(info, has_m, use_x0=False):
-    """the documented counts: two A products per lockstep iteration (one more for the residual of an initial guess), two M
-    products per iteration"""
-    assert info.a_products == 2 * info.iterations + (1 if use_x0 else 0)
-    assert info.m_products == (2 * info.iterations if has_m else 0)
 
 
 # ---- 1. against the twin -------------------------------------------------------------------------------------------------

@@ -5,8 +5,8 @@ statuses and the refusals.  The twin itself is tested in test_cg_cpu.py."""
 import numpy as np
 import pytest
 
-from _cg import (CG, COCG, ERR_INVALID, ERR_UNSUPPORTED, MAX_RHS, NB, NCG, cg_problem, cg_twin, column_tol, exact_minv, is_complex,
-                 raw_cg_create, raw_cg_destroy, raw_cg_solve, rtol_of, spd_problem, true_residual)
+from _cg import (CG, COCG, ERR_INVALID, ERR_UNSUPPORTED, MAX_RHS, NB, NCG, cg_problem, cg_twin, check_columns, check_products, column_tol,
+                 exact_minv, is_complex, raw_cg_create, raw_cg_destroy, raw_cg_solve, rtol_of, spd_problem, true_residual)
 from _ctors import ctor_build
 from _gpu import dev_copy, dev_mat, outside_bytes, torch_cuda, torch_dtype  # noqa: F401
 from _jacobi import CODE, DTYPES, KINDS, uniform
@@ -43,28 +43,6 @@ def twins():
             out[key] = (D, B, Minv, runs)
         return out[key]
     return get
-
-
-def check_columns(info, runs, D, x, B, tols, what):
-    """every column: status 0, the twin's count (+-1: the multi-column product rounds differently from one column, the
-    twin's count is stable under permuted sums -- test_cg_cpu.py), true residual <= 2 tol evaluated in complex128"""
-    x = np.asarray(x).reshape(len(D), -1)
-    for c, run in enumerate(runs):
-        true = true_residual(D, x[:, c], B[:, c])
-        print(f"CGSTAT {what} column {c}: {info.column_iterations[c]} iterations, twin {run.iterations}, true residual / tol "
-              f"{true / tols[c] if tols[c] else 0:.3f}")
-        assert run.status == 0, (what, c, "the twin did not converge")
-        assert info.column_status[c] == 0, (what, c, info.column_status[c])
-        assert abs(int(info.column_iterations[c]) - run.iterations) <= 1, (what, c, info.column_iterations[c], run.iterations)
-        assert true <= 2 * tols[c], (what, c, true, tols[c])
-    assert info.iterations == max(info.column_iterations) and info.status == 0 and info.columns_converged == len(runs)
-
-
-def check_products(info, has_m, use_x0=False):
-    """the documented counts: one A product per lockstep iteration (one more for the residual of an initial guess), one
-    M product per iteration and one for the first z"""
-    assert info.a_products == info.iterations + (1 if use_x0 else 0)
-    assert info.m_products == (info.iterations + 1 if has_m else 0)
 
 
 # ---- 1. against the twin -------------------------------------------------------------------------------------------------

@@ -7,8 +7,8 @@ import pytest
 from _ctors import ctor_build
 from _gpu import TOL, torch_cuda  # noqa: F401
 from _jacobi import CODE, DTYPES, KINDS, NOP, dense_of, set_blocks
-from _krylov import (ERR_INVALID, ERR_UNSUPPORTED, RESTART, Truth, exact_minv, expected_products, gmres_twin, krylov_problem,
-                     raw_gmres_create, raw_gmres_destroy, raw_gmres_solve, rtol_of, true_residual)
+from _krylov import (ERR_INVALID, ERR_UNSUPPORTED, RESTART, Truth, check_against_twin, check_history, exact_minv, expected_products,
+                     gmres_twin, krylov_problem, raw_gmres_create, raw_gmres_destroy, raw_gmres_solve, rtol_of, true_residual)
 
 pytestmark = pytest.mark.gpu
 IDS = [np.dtype(d).name for d in DTYPES]
@@ -21,35 +21,6 @@ def dev(torch, v):
 def reproducible(*ops):
     """the products of these handles are bitwise reproducible: exclusive forward images (no atomics)"""
     return all(o.stats()["exclusive"] == 1 for o in ops)
-
-
-def check_history(info, tol, restart, dtype):
-    """len(history) == iterations; a solve that converged on an ESTIMATE ends on an entry <= tol with every earlier one
-    above it (one that converged on the true residual at a restart -- info.residual is then not the last entry -- has
-    every entry above tol and that residual <= tol); inside each cycle the history does not rise.
-    |g[j + 1]| = |s| |g[j]|.  Real types: s = +-hn / hypot(t, hn) and hypot(t, hn) >= hn, so |s| <= 1 in floating point
-    too: no slack.  Complex types: s = (a / |a|) hn / r carries the rounded phase -- |a| and the final modulus are hypots
-    (1 ulp = eps each), the divisions and the rounding of s eps / 2 each, the complex product conj(s) g sqrt(2) eps: under
-    5 eps(T) relative in all; 8 eps(T) is allowed."""
-    h = info.history
-    assert len(h) == info.iterations
-    if info.status == 0 and info.iterations:
-        if info.residual == h[-1]:
-            assert h[-1] <= tol and np.all(h[:-1] > tol)
-        else:
-            assert info.residual <= tol and np.all(h > tol)
-    slack = 8 * float(np.finfo(dtype).eps) if np.dtype(dtype).kind == "c" else 0.0
-    for c0 in range(0, len(h), restart):
-        c = h[c0:c0 + restart]
-        assert np.all(c[1:] <= c[:-1] * (1 + slack)), ("history rises inside a cycle", c0, float(np.max(c[1:] / c[:-1]) - 1))
-    assert info.cycles == -(-info.iterations // restart)
-
-
-def check_against_twin(info, twin, what):
-    assert twin.status == 0, (what, "the twin did not converge")
-    slack = max(2, twin.iterations // 10)
-    print(f"KRYSTAT gmres {what}: {info.iterations} iterations, twin {twin.iterations}")
-    assert info.iterations <= twin.iterations + slack, (what, info.iterations, twin.iterations)
 
 
 @pytest.mark.parametrize("kind", KINDS)

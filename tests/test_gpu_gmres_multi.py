@@ -21,8 +21,8 @@ import pytest
 from _bicgstab import bicgstab_problem
 from _cg import MAX_RHS, cg_problem, column_tol
 from _ctors import ctor_build
-from _gmres_multi import (GRID_ITS, GRID_RESTART, MARGIN, check_history, cycles_of, gmres_multi_twin, grid_spread, raw_gm_create,
-                          raw_gm_destroy, raw_gm_solve, reference, workspace_bytes)
+from _gmres_multi import (GRID_ITS, GRID_RESTART, MARGIN, check_columns, check_history, columns400, cycles_of, gmres_multi_twin,
+                          grid_spread, products, raw_gm_create, raw_gm_destroy, raw_gm_solve, reference, slack_of, workspace_bytes)
 from _gpu import TOL, dev_copy, torch_cuda  # noqa: F401
 from _jacobi import CODE, DTYPES, KINDS, NOP, uniform
 from _krylov import (ERR_DEVICE, ERR_INVALID, ERR_UNSUPPORTED, MAX_RESTART, exact_minv, expected_products, krylov_problem, rtol_of,
@@ -48,29 +48,6 @@ def reproducible(*ops):
 
 
 # ---- 1. the order-400 operators with block-Jacobi ---------------------------------------------------------------------------
-def columns400(kind, dtype):
-    """five uniform right-hand sides of order 400 for krylov_problem(kind, dtype)"""
-    rng = np.random.default_rng(9000 + 4 * KINDS.index(kind) + DTYPES.index(dtype))
-    return np.asfortranarray(uniform(rng, (NOP, NB), dtype))
-
-
-def products(info, restart, use_x0, has_m):
-    """(a_products, m_products) by the documented formula (_krylov.expected_products on the largest count), plus the one
-    true-residual product of a restart BEHIND the last iteration where a column was still running there and froze on that
-    restart's true residual (its `residual` is then not its last estimate)"""
-    its = int(info.iterations)
-    a, m = expected_products(its, cycles_of(its, restart), use_x0, has_m)
-    late = its > 0 and its % restart == 0 and any(
-        info.column_status[c] == 0 and info.column_iterations[c] == its and info.residual[c] != info.history[its - 1, c]
-        for c in range(len(info.column_status)))
-    return a + (1 if late else 0), m
-
-
-def slack_of(twin_iterations):
-    """what test_gpu_gmres.py's check_against_twin allows above the twin's count"""
-    return max(2, twin_iterations // 10)
-
-
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("dtype", DTYPES, ids=[name(d) for d in DTYPES])
 def test_solves_with_block_jacobi(torch_cuda, bsm, kind, dtype):
@@ -365,13 +342,6 @@ def small(torch_cuda, bsm):
     Minv = exact_minv(D, sets)
     runs = [gmres_multi_twin(D, B[:, c], Minv, 20, 1e-10, 100, dtype) for c in range(NB)]
     return dict(p=p, sets=sets, b=b, D=D, B=B, A=A, M=M, Minv=Minv, runs=runs)
-
-
-def check_columns(info, runs, D, xh, B, rtol, what):
-    for c, run in enumerate(runs):
-        assert info.column_status[c] == 0 and run.status == 0, (what, c)
-        assert int(info.column_iterations[c]) <= run.iterations + slack_of(run.iterations), (what, c)
-        assert true_residual(D, xh[:, c], B[:, c]) <= 2 * column_tol(B[:, c], rtol), (what, c)
 
 
 def test_vectors_numpy_operands_and_the_one_shot_forms(torch_cuda, bsm, small):

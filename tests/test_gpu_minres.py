@@ -16,7 +16,8 @@ from _jacobi import CODE, uniform
 from _krylov import exact_minv, rtol_of, true_residual
 from _lockstep import (COLUMNS, ITS, MARGIN, RANGE_BYTES, TABLE, block_solve, deviation, half_sets, krylov_grid, path_rtol, reference_of,
                        solve_in_guarded_buffers, staggered6)
-from _minres import BROKEN_COUNTS, indef_case, minres_problem, minres_twin, raw_minres_create, raw_minres_destroy, raw_minres_solve
+from _minres import (BROKEN_COUNTS, check_columns, check_products, indef_case, minres_problem, minres_twin, raw_minres_create,
+                     raw_minres_destroy, raw_minres_solve)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,26 +47,6 @@ def build_400(bsm, kind, dtype, **kw):
     """-> (A, M): the indefinite operator and block_jacobi of its definite sibling"""
     p, pp, sets, _, _, _ = minres_problem(kind, dtype)
     return bsm.synthetic.build(p, **kw), bsm.block_jacobi(bsm.synthetic.build(pp, **kw), sets)
-
-
-def check_columns(info, runs, D, x, B, tols, what):
-    """every column: status 0, the twin's count (+-1: the multi-column product rounds differently from one column, the
-    twin's count is stable under permuted sums -- test_minres_cpu.py), true residual <= 2 tol evaluated in complex128"""
-    x = np.asarray(x).reshape(D.shape[0], -1)
-    for c, run in enumerate(runs):
-        true = true_residual(D, x[:, c], B[:, c])
-        print(f"MRSTAT {what} column {c}: {info.column_iterations[c]} iterations, twin {run.iterations}, true residual / tol "
-              f"{true / tols[c] if tols[c] else 0:.3f}")
-        assert run.status == 0, (what, c, "the twin did not converge")
-        assert info.column_status[c] == 0, (what, c, info.column_status[c])
-        assert abs(int(info.column_iterations[c]) - run.iterations) <= 1, (what, c, info.column_iterations[c], run.iterations)
-        assert true <= 2 * tols[c], (what, c, true, tols[c])
-    assert info.iterations == max(info.column_iterations) and info.status == 0 and info.columns_converged == len(runs)
-
-
-def check_products(info, has_m, use_x0=False):
-    assert info.a_products == info.iterations + (1 if use_x0 else 0)
-    assert info.m_products == (info.iterations + 1 if has_m else 0)
 
 
 # ---- 1. against the twin, order 400 ---------------------------------------------------------------------------------------
