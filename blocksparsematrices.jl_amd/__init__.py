@@ -11,6 +11,6 @@ from . import entries, matrices, solvers, synthetic  # noqa: F401
 from .entries import *  # noqa: F401,F403
 from .matrices import *  # noqa: F401,F403
 from .solvers import *  # noqa: F401,F403
-from .solvers import Minres, minres  # noqa: F401
+from .solvers import Lsqr, LsqrInfo, Minres, lsqr, minres  # noqa: F401
 
 __all__ = matrices.__all__ + entries.__all__ + solvers.__all__ + ["synthetic"]

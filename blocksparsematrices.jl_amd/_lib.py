@@ -63,6 +63,11 @@ class BsmCgParams(C.Structure):
                 ("maxiter", C.c_int64), ("history_capacity", C.c_int64)]
 
 
+class BsmLsqrParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("use_x0", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double), ("ntol", C.c_double),
+                ("damp", C.c_double), ("maxiter", C.c_int64), ("history_capacity", C.c_int64)]
+
+
 class BsmCgInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("columns_converged", C.c_int32), ("iterations", C.c_int64),
                 ("a_products", C.c_int64), ("m_products", C.c_int64), ("workspace_bytes", C.c_int64),
@@ -95,7 +100,7 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_krylov_orth_work", "bsm_krylov_orth", "bsm_gmres_create", "bsm_gmres_solve",
            "bsm_gmres_destroy", "bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy", "bsm_bicgstab_create", "bsm_bicgstab_solve",
            "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy",
-           "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy"]
+           "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy", "bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -233,6 +238,14 @@ def lib():
         L.bsm_minres_solve.argtypes = L.bsm_cg_solve.argtypes
         L.bsm_minres_destroy.argtypes = [C.c_void_p]
         for name in ("bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "bsm_lsqr_create") or "BSM_LIB" not in os.environ:  # (info and columns are those of bsm_cg_*)
+        L.bsm_lsqr_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bsm_lsqr_solve.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(BsmLsqrParams),
+                                     C.POINTER(BsmCgInfo), C.POINTER(BsmCgColumn), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_int, C.c_void_p]
+        L.bsm_lsqr_destroy.argtypes = [C.c_void_p]
+        for name in ("bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy"):
             getattr(L, name).restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p

@@ -49,11 +49,11 @@ int solve_device(bsm_bicgstab_s *S, int nrhs, const void *B, int64_t ldb, void *
     auto product = [&](const char *w, char *out, const char *&hat) -> int {
         hat = w;
         if (S->M) {
-            const int r = apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, vt, w, S->Z, st);
+            const int r = apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, S->ld, vt, w, S->Z, st);
             if (r != BSM_OK) return r;
             hat = S->Z;
         }
-        return apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, hat, out, st);
+        return apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, S->ld, vt, hat, out, st);
     };
     // ---- the start: x, r = rhat, the norms, p = r, the first decision
     RC_TRY(lockstep_start_x(S, d, p.use_x0, X, ldx, S->X, S->V, st));

@@ -50,7 +50,7 @@ int solve_device(bsm_cg_s *S, int nrhs, const void *B, int64_t ldb, void *X, int
     // z = M r and the shares of <r, z> (with M only)
     auto precondition = [&](int par) -> int {
         if (!S->M) return BSM_OK;
-        const int r = apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, vt, S->R, S->Z, st);
+        const int r = apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, S->ld, vt, S->R, S->Z, st);
         if (r != BSM_OK) return r;
         const hipError_t q = launch_cg_dot(d, par, S->R, S->Z, S->prz, S->state, st);
         return q == hipSuccess ? BSM_OK : hip_fail(q, "launch_cg_dot");
@@ -63,7 +63,7 @@ int solve_device(bsm_cg_s *S, int nrhs, const void *B, int64_t ldb, void *X, int
     // ---- the iterations, their records read one behind the enqueue
     RC_TRY(lockstep_run(S, d, X, ldx, S->X, p, info, cols, history, st, [&](int64_t j) -> int {
         const int par = (int)(j & 1);
-        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, S->P, S->Q, st));
+        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, S->ld, vt, S->P, S->Q, st));
         HIP_TRY(launch_cg_dot(d, par, S->P, S->Q, S->ppq, S->state, st));
         HIP_TRY(launch_cg_update(d, par, S->ppq, S->P, S->Q, S->X, S->R, S->pnn, prz_fused, S->state, st));
         RC_TRY(precondition(par));

@@ -101,10 +101,10 @@ int solve_device(bsm_gmres_multi_s *S, int nrhs, const void *B, int64_t ldb, voi
         for (; j < jmax; j++) {
             const char *vj = S->basis(j);
             if (S->M) {
-                RC_TRY(apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, vt, vj, S->Z, st));
-                RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, S->Z, S->W, st));
+                RC_TRY(apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, S->ld, vt, vj, S->Z, st));
+                RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, S->ld, vt, S->Z, S->W, st));
             } else {
-                RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, vj, S->W, st));
+                RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, S->ld, vt, vj, S->W, st));
             }
             for (int pass = 0; pass < 2; pass++) {
                 HIP_TRY(launch_gm_dot(g, par, j + 1, S->V, S->W, sm, gs, st));
@@ -126,12 +126,12 @@ int solve_device(bsm_gmres_multi_s *S, int nrhs, const void *B, int64_t ldb, voi
         if (j > 0 && !(stopped && last_was_begin)) {
             HIP_TRY(launch_gm_trsolve(g, par, sm, gs, st));
             HIP_TRY(launch_gm_combine(g, par, S->V, S->W, sm, gs, st));
-            if (S->M) RC_TRY(apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, vt, S->W, S->Z, st));
+            if (S->M) RC_TRY(apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, S->ld, vt, S->W, S->Z, st));
             HIP_TRY(launch_gm_axpy(g, par, S->M ? S->Z : S->W, S->X, gs, st));
         }
         if (running == 0 || it >= maxiter) break;
         // the restart, enqueued without waiting: the true residual b - op(A) x into V_0, its norm, the decision
-        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, S->X, S->W, st));
+        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, S->ld, vt, S->X, S->W, st));
         HIP_TRY(launch_gm_start(g, false, par, B, ldb, S->W, S->basis(0), sm, gs, st));
         HIP_TRY(launch_gm_begin(g, false, par, p.rtol, p.atol, S->basis(0), sm, gs, st));
         par ^= 1;

@@ -1,5 +1,6 @@
 // bsm_lockstep.h -- the host side that the lockstep solver objects (bsm_cg.cpp: bsm_cg_*, bsm_bicgstab.cpp: bsm_bicgstab_*,
-// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*, bsm_minres.cpp: bsm_minres_*; include/bsm_rocm.h) share: what a solver object
+// bsm_gmres_multi.cpp: bsm_gmres_multi_* and its one-column front bsm_gmres_*, bsm_minres.cpp: bsm_minres_*, bsm_lsqr.cpp:
+// bsm_lsqr_*; include/bsm_rocm.h) share: what a solver object
 // holds whatever its method, the (handle, vector) pairings and the multi-column product on the workspace, create from the
 // refusals to the one device allocation (lockstep_create: a method writes its layout once, as a function on a Carve), the
 // start of x, the ring of pinned record slots (RecordRing), what the host takes from a record and reports from the last
@@ -37,8 +38,11 @@ struct LockstepSolver {
     bsm_matrix_s *A = nullptr, *M = nullptr;
     int opA = 0, opM = 0, vt = 0, kmax = 0, device = 0;
     bool a_cvec = false, m_cvec = false;
-    int64_t n = 0, ld = 0;
+    int64_t n = 0, ld = 0;  // rows of X = cols(op(A)), their leading dimension in the workspace
     int G = 1;
+    // the same of the vectors of B's length, rows(op(A)): n, ld and G again for the solvers of square systems
+    int64_t rows_b = 0, ld_b = 0;
+    int G_b = 1;
     // ONE device allocation (info.workspace): the method's vectors as ld x kmax, its partials, the state
     void *ws = nullptr;
     int64_t ws_bytes = 0;
@@ -46,7 +50,7 @@ struct LockstepSolver {
     const CgRecord *rec = nullptr;  // the device record of a method with a state of its own (null: state->rec)
     CgRecord *slots = nullptr;      // pinned, kLockstepRing of them
     hipEvent_t ev[kLockstepRing] = {};
-    // BSM_MEM_HOST solves: device copies of B and X (n x kmax), allocated at the first one
+    // BSM_MEM_HOST solves: device copies of B (rows_b x kmax) and X (n x kmax), allocated at the first one
     void *hb = nullptr, *hx = nullptr;
 
     void release() {
@@ -72,13 +76,13 @@ inline int pairing(const bsm_matrix_s *H, int vt) {
     return -1;
 }
 
-// Y = op(H) X on nrhs columns of the workspace (leading dimension ld), Y overwritten
-inline int apply(bsm_matrix_s *H, int op, bool cvec, int nrhs, int64_t ld, int vt, const void *X, void *Y, hipStream_t st) {
+// Y = op(H) X on nrhs columns of the workspace (leading dimensions ldx of X, ldy of Y), Y overwritten
+inline int apply(bsm_matrix_s *H, int op, bool cvec, int nrhs, int64_t ldx, int64_t ldy, int vt, const void *X, void *Y, hipStream_t st) {
     const double one_d[2] = {1, 0}, zero_d[2] = {0, 0};
     const float one_f[2] = {1, 0}, zero_f[2] = {0, 0};
     const bool f = real_bytes(vt) == 4;
     auto fn = cvec ? bsm_mul_multi_cvec : bsm_mul_multi;
-    return fn(H, op, nrhs, X, ld, Y, ld, f ? (const void *)one_f : (const void *)one_d, f ? (const void *)zero_f : (const void *)zero_d, 1,
+    return fn(H, op, nrhs, X, ldx, Y, ldy, f ? (const void *)one_f : (const void *)one_d, f ? (const void *)zero_f : (const void *)zero_d, 1,
               BSM_MEM_DEVICE, (void *)st);
 }
 
@@ -111,10 +115,11 @@ inline int lockstep_check_create(const void *A, int opA, const void *M, int opM,
     return BSM_OK;
 }
 // The other refusals of create that do not depend on the method (`what`: "bsm_cg", "bsm_bicgstab", "bsm_gmres_multi", "bsm_gmres"), and on success the fields
-// of S that follow from the arguments.  out has been checked and cleared by the caller.
+// of S that follow from the arguments.  square: the method needs op(A) square (else B has rows(op(A)) rows and X
+// cols(op(A))).  out has been checked and cleared by the caller.
 inline int lockstep_init(LockstepSolver *S, const char *what, bsm_matrix_s *A, int opA, bsm_matrix_s *M, int opM, int vdtype,
-                         int32_t nrhs_max) {
-    if (A->an.nrows != A->an.ncols) return fail(BSM_ERR_INVALID, "op(A) is not square");
+                         int32_t nrhs_max, bool square = true) {
+    if (square && A->an.nrows != A->an.ncols) return fail(BSM_ERR_INVALID, "op(A) is not square");
     if (M && (M->an.nrows != A->an.nrows || M->an.ncols != A->an.ncols)) return fail(BSM_ERR_INVALID, "M has another order than A");
     const int pa = pairing(A, vdtype), pm = M ? pairing(M, vdtype) : 0;
     if (pa < 0 || pm < 0)
@@ -129,10 +134,13 @@ inline int lockstep_init(LockstepSolver *S, const char *what, bsm_matrix_s *A, i
     if (M && M->img.device != A->img.device) return fail(BSM_ERR_INVALID, "A and M live on different devices");
     S->A = A, S->M = M, S->opA = opA, S->opM = opM, S->vt = vdtype, S->kmax = nrhs_max, S->device = A->img.device;
     S->a_cvec = pa == 1, S->m_cvec = pm == 1;
-    S->n = A->an.nrows;
+    S->n = opA == BSM_OP_N ? A->an.ncols : A->an.nrows;
+    S->rows_b = opA == BSM_OP_N ? A->an.nrows : A->an.ncols;
     const int64_t es = elem_bytes(vdtype);
     S->ld = (std::max<int64_t>(S->n, 1) * es + 15) / 16 * 16 / es;
     S->G = krylov_grid(S->n, (int)es);
+    S->ld_b = (std::max<int64_t>(S->rows_b, 1) * es + 15) / 16 * 16 / es;
+    S->G_b = krylov_grid(S->rows_b, (int)es);
     return BSM_OK;
 }
 
@@ -154,16 +162,19 @@ inline int lockstep_alloc(LockstepSolver *S, int64_t bytes, const char *what) {
 
 // The whole of a create: out, the checks (method_error as in lockstep_check_create), the object, the refusals of
 // lockstep_init, the allocation sized by layout(S, carve) (`ws_name`: "CG", .. for its failure) and the pointers from the
-// same layout.  layout also sets the method's own fields of S.
+// same layout.  layout also sets the method's own fields of S.  square: as in lockstep_init.  refuse (may be null): a
+// refusal of the method's own that needs the checked arguments -- called behind the argument checks, a status other than
+// BSM_OK is returned as it is.
 template <typename Solver, typename Layout>
 int lockstep_create(const char *what, const char *ws_name, bsm_matrix_s *A, int opA, bsm_matrix_s *M, int opM, int vdtype, int32_t nrhs_max,
-                    const char *method_error, Solver **out, Layout &&layout) {
+                    const char *method_error, Solver **out, Layout &&layout, bool square = true, int (*refuse)(bsm_matrix_s *, int) = nullptr) {
     if (!out) return fail(BSM_ERR_INVALID, "out is null");
     *out = nullptr;
     RC_TRY(lockstep_check_create(A, opA, M, opM, vdtype, nrhs_max, method_error));
+    if (refuse) RC_TRY(refuse(A, opA));
     Solver *S = new (std::nothrow) Solver;
     if (!S) return fail(BSM_ERR_ALLOC, "out of host memory");
-    int rc = lockstep_init(S, what, A, opA, M, opM, vdtype, nrhs_max);
+    int rc = lockstep_init(S, what, A, opA, M, opM, vdtype, nrhs_max, square);
     if (rc == BSM_OK) {
         Carve size;
         layout(*S, size);
@@ -190,15 +201,15 @@ template <typename Solver> int lockstep_destroy(Solver *S) {
     return BSM_OK;
 }
 
-// The start of x every method shares: with use_x0 the caller's X into the workspace X and q = op(A) X; else X = 0 (q is
-// left alone: the method's start kernel gets no q)
+// The start of x every method shares: with use_x0 the caller's X into the workspace X and q = op(A) X (of B's length);
+// else X = 0 (q is left alone: the method's start kernel gets no q).  d: the dimensions of X.
 inline int lockstep_start_x(LockstepSolver *S, const CgDims &d, bool use_x0, void *X, int64_t ldx, void *wsX, void *q, hipStream_t st) {
     if (!use_x0) {
         HIP_TRY(hipMemsetAsync(wsX, 0, (size_t)S->ld * elem_bytes(S->vt) * d.nrhs, st));
         return BSM_OK;
     }
     HIP_TRY(launch_cg_copy(d, true, X, ldx, wsX, st));
-    return apply(S->A, S->opA, S->a_cvec, d.nrhs, S->ld, S->vt, wsX, q, st);
+    return apply(S->A, S->opA, S->a_cvec, d.nrhs, S->ld, S->ld_b, S->vt, wsX, q, st);
 }
 
 // The records of one solve: post() copies the record at the device address `rec` to the next pinned slot behind what has
@@ -291,17 +302,19 @@ int lockstep_solve(LockstepSolver *S, const char *what, int32_t nrhs, const void
     if (!(p->rtol >= 0) || !(p->atol >= 0) || p->maxiter < 0 || p->history_capacity < 0)
         return fail(BSM_ERR_INVALID, "rtol, atol, maxiter and history_capacity must be >= 0");
     if (nrhs < 1 || nrhs > S->kmax) return fail(BSM_ERR_INVALID, "nrhs outside 1 .. nrhs_max");
-    const int64_t n = S->n, lmin = std::max<int64_t>(n, 1);
-    if (ldb < lmin || ldx < lmin) return fail(BSM_ERR_INVALID, "ldb / ldx < max(n, 1)");
+    // B has the rows of op(A), X its columns: one number for the solvers of square systems
+    const int64_t n = S->n, mb = S->rows_b;
+    const bool empty = n == 0 || mb == 0;
+    if (ldb < std::max<int64_t>(mb, 1) || ldx < std::max<int64_t>(n, 1)) return fail(BSM_ERR_INVALID, "ldb / ldx < max(n, 1)");
     const size_t es = (size_t)elem_bytes(S->vt);
-    const size_t bbytes = ((size_t)(nrhs - 1) * (size_t)ldb + (size_t)n) * es, xbytes = ((size_t)(nrhs - 1) * (size_t)ldx + (size_t)n) * es;
-    if (n > 0 && (!B || !X)) return fail(BSM_ERR_INVALID, "null matrix");
-    if (n > 0 && overlap(B, bbytes, X, xbytes)) return fail(BSM_ERR_INVALID, "X must not overlap B");
+    const size_t bbytes = ((size_t)(nrhs - 1) * (size_t)ldb + (size_t)mb) * es, xbytes = ((size_t)(nrhs - 1) * (size_t)ldx + (size_t)n) * es;
+    if (!empty && (!B || !X)) return fail(BSM_ERR_INVALID, "null matrix");
+    if (!empty && overlap(B, bbytes, X, xbytes)) return fail(BSM_ERR_INVALID, "X must not overlap B");
     if (capturing(st)) return fail(BSM_ERR_INVALID, std::string(what) + " must not be graph-captured");
     std::memset(info, 0, sizeof(*info));
     info->workspace_bytes = S->ws_bytes;
     info->workspace = (uint64_t)(uintptr_t)S->ws;
-    if (n == 0) {  // nothing to solve: status 0, no iteration, B and X (which may be null) untouched
+    if (empty) {  // nothing to solve: status 0, no iteration, B and X (which may be null) untouched
         info->columns_converged = nrhs;
         if (cols) std::memset(cols, 0, sizeof(*cols) * (size_t)nrhs);
         return BSM_OK;
@@ -311,9 +324,9 @@ int lockstep_solve(LockstepSolver *S, const char *what, int32_t nrhs, const void
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
     if (memspace == BSM_MEM_DEVICE) return solve_device(B, ldb, X, ldx);
     // host matrices: staged column by column through dense buffers the solver keeps
-    const size_t col = (size_t)n * es;
+    const size_t col = (size_t)n * es, bcol = (size_t)mb * es;
     if (!S->hb || !S->hx) {
-        if (!S->hb) e = hipMalloc(&S->hb, col * (size_t)S->kmax + 16);
+        if (!S->hb) e = hipMalloc(&S->hb, bcol * (size_t)S->kmax + 16);
         if (e == hipSuccess && !S->hx) e = hipMalloc(&S->hx, col * (size_t)S->kmax + 16);
         if (e != hipSuccess) {  // (a buffer that was obtained is kept; the next host solve asks for the other again)
             if (e != hipErrorOutOfMemory) return hip_fail(e, "staging buffers");
@@ -322,12 +335,12 @@ int lockstep_solve(LockstepSolver *S, const char *what, int32_t nrhs, const void
         }
     }
     for (int c = 0; c < nrhs && e == hipSuccess; c++) {
-        e = hipMemcpyAsync((char *)S->hb + c * col, (const char *)B + (size_t)c * (size_t)ldb * es, col, hipMemcpyHostToDevice, st);
+        e = hipMemcpyAsync((char *)S->hb + c * bcol, (const char *)B + (size_t)c * (size_t)ldb * es, bcol, hipMemcpyHostToDevice, st);
         if (e == hipSuccess && p->use_x0)
             e = hipMemcpyAsync((char *)S->hx + c * col, (const char *)X + (size_t)c * (size_t)ldx * es, col, hipMemcpyHostToDevice, st);
     }
     if (e != hipSuccess) return hip_fail(e, "host-staged solve");
-    const int rc = solve_device(S->hb, n, S->hx, n);
+    const int rc = solve_device(S->hb, mb, S->hx, n);
     if (rc != BSM_OK) return rc;
     for (int c = 0; c < nrhs && e == hipSuccess; c++)
         e = hipMemcpyAsync((char *)X + (size_t)c * (size_t)ldx * es, (char *)S->hx + c * col, col, hipMemcpyDeviceToHost, st);

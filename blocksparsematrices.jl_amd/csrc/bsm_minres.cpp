@@ -49,7 +49,7 @@ int solve_device(bsm_minres_s *S, int nrhs, const void *B, int64_t ldb, void *X,
     // z_new = M v_new and the shares of <v_new, z_new> (with M only; without, z IS v and mr_lanczos leaves the shares)
     auto precondition = [&](int par, int slot) -> int {
         if (!S->M) return BSM_OK;
-        RC_TRY(apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, vt, S->V[slot], S->Z[slot], st));
+        RC_TRY(apply(S->M, S->opM, S->m_cvec, nrhs, S->ld, S->ld, vt, S->V[slot], S->Z[slot], st));
         HIP_TRY(launch_mr_dot(d, par, S->V[slot], S->Z[slot], S->pvz, S->mr, st));
         return BSM_OK;
     };
@@ -62,7 +62,7 @@ int solve_device(bsm_minres_s *S, int nrhs, const void *B, int64_t ldb, void *X,
     RC_TRY(lockstep_run(S, d, X, ldx, S->X, p, info, cols, history, st, [&](int64_t j) -> int {
         const int par = (int)(j & 1), cur = par, old = par ^ 1;
         char *const z = S->M ? S->Z[cur] : S->V[cur];
-        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, vt, z, S->Q, st));
+        RC_TRY(apply(S->A, S->opA, S->a_cvec, nrhs, S->ld, S->ld, vt, z, S->Q, st));
         HIP_TRY(launch_mr_dot(d, par, z, S->Q, S->pzq, S->mr, st));
         HIP_TRY(launch_mr_lanczos(d, par, S->pzq, S->Q, S->V[cur], S->V[old], S->M ? nullptr : S->pvz, S->mr, st));
         RC_TRY(precondition(par, old));

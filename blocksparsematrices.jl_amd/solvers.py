@@ -1,6 +1,6 @@
 """The block-Jacobi preconditioner (invert_blocks, BlockJacobi, block_jacobi) and the Krylov solvers that run every step
-on the device: the Gram-Schmidt pass krylov_orth, Gmres, and the lockstep solvers Cg, BiCgStab, Minres, GmresMulti with their
-one-shot forms.  The solver objects share _Solver: the create and destroy calls and the prelude of solve()."""
+on the device: the Gram-Schmidt pass krylov_orth, Gmres, and the lockstep solvers Cg, BiCgStab, Minres, GmresMulti, Lsqr with
+their one-shot forms.  The solver objects share _Solver: the create and destroy calls and the prelude of solve()."""
 import contextlib
 import ctypes as C
 
@@ -187,6 +187,7 @@ class _Solver:
     _names = ("B", "X")  # what solve() calls its operands
     _matrices = True  # solve() takes matrices of 1 .. self.nrhs columns beside vectors
     _x0_refusal = "X0 must have the shape {shape} and the type {dtype}"
+    _takes_m = True  # the create call has the (M, opM) pair behind (A, opA)
 
     def _create(self, A, M, dtype, args):
         """the checks and the create call; args(): called once A, M and dtype have passed, gives the arguments of create
@@ -198,11 +199,11 @@ class _Solver:
             raise TypeError(f"dtype={self.dtype} is not a supported vector type")
         args = args()
         self.A, self.M = A, M
-        self.n = size(A)[0]
+        self.nb, self.n = size(A)  # rows of B, rows of X: one number for the solvers of square systems
         self._base, self._mbase = base, mbase
         ptr = C.c_void_p()
-        L.check(getattr(L.lib(), self._abi + "_create")(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype],
-                                                        *args, C.byref(ptr)))
+        pair = (None if mbase is None else mbase._h.ptr, mop) if self._takes_m else ()
+        L.check(getattr(L.lib(), self._abi + "_create")(base._h.ptr, op, *pair, _DT[self.dtype], *args, C.byref(ptr)))
         self._ptr = ptr
 
     def __del__(self):
@@ -218,7 +219,7 @@ class _Solver:
         into X, the stream settled -> (X, the descriptors of B and of X (_describe), the stream pointer or None)."""
         nb, nx = self._names
         vector = not self._matrices or getattr(B, "ndim", 1) == 1
-        b = _describe(B, self.dtype, self.n, nb, self._base, not vector)
+        b = _describe(B, self.dtype, self.nb, nb, self._base, not vector)
         if X is None:
             X = _like(B, self.n, None if vector else b[2])
         x = _describe(X, self.dtype, self.n, nx, self._base, not vector)
@@ -420,6 +421,65 @@ def minres(A, B, M=None, **kw):
     """One-shot form: Minres(A, M, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
     k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
     return Minres(A, M, nrhs=k, dtype=_elt(B)).solve(B, **kw)
+
+
+# ---- LSQR on several right-hand sides in lockstep, on the device (bsm_lsqr_*) -----------------------------------------------
+# (Lsqr, LsqrInfo and lsqr are exported by the package by name, like Minres)
+class LsqrInfo(CgInfo):
+    """CgInfo plus, per column as numpy arrays of k entries: normal_residual (the estimate of ||op(A)^H r - damp^2 (x - x0)||
+    when the column stopped) and anorm (the running Frobenius-norm estimate of the bidiagonal factor, scipy's anorm).
+    residual and history hold the estimate rnorm of ||b - op(A) x|| (with damp: of the damped residual)."""
+
+    def __init__(self, info, cols, history, normal_residual, anorm):
+        super().__init__(info, cols, history)
+        self.normal_residual, self.anorm = normal_residual, anorm
+
+    def __repr__(self):
+        return "Lsqr" + super().__repr__()[2:]
+
+
+class Lsqr(_LockstepSolver):
+    """LSQR for min ||B - A X||^2 + damp^2 ||X - X0||^2 with A of ANY shape and rank -- over-determined, under-determined
+    (the minimum-norm solution) or singular --, up to `nrhs` right-hand sides advancing in lockstep on TWO multi-column
+    products per iteration, one with A and one with its adjoint, every step on the device (bsm_lsqr_*).  A: a block matrix
+    or transpose(A) / adjoint(A) (transpose of a COMPLEX matrix is refused: its adjoint is conj(A), which no product
+    offers); there is no preconditioner argument.  dtype: the type of B and X -- default A's vector type; a real A of the
+    same precision takes complex vectors.  B has size(A)[0] rows, X size(A)[1].  The workspace (4 matrices of X's shape, 2
+    of B's) is allocated here, once; A is kept alive.  info.a_products = 2 * iterations + 1 (+ 1 with X0)."""
+
+    _abi = "bsm_lsqr"
+    _takes_m = False
+
+    def __init__(self, A, nrhs=1, dtype=None):
+        self._setup(A, None, nrhs, dtype)
+
+    def solve(self, B, X=None, X0=None, rtol=1e-8, atol=0.0, ntol=1e-8, damp=0.0, maxiter=None, stream=None, history=True):
+        """-> (X, LsqrInfo).  B: a vector (m,) or a column-major matrix (m, k), k <= nrhs, m = size(A)[0] -- torch CUDA tensor
+        or numpy array, as in Cg.solve; X: where the solution goes (n = size(A)[1] rows; default: new, like B); X0: the
+        initial guess (copied into X; None: zero), which is also what damp pulls towards.  Column c stops with status 0
+        when the estimate of ||b_c - A x_c|| is <= max(rtol * ||b_c||, atol) (a consistent system), when the estimate of
+        the normal-equation residual is <= ntol * anorm * that residual estimate (a least-squares solution), or when the
+        Krylov space ends; maxiter (default: min(m, n)) bounds the lockstep iterations.  A vector in gives a vector out.
+        Synchronous."""
+        X, (bp, ldb, k, bms, _, _), (xp, ldx, *_), st = self._prelude(B, X, X0, stream)
+        maxiter = max(min(self.nb, self.n), 1) if maxiter is None else int(maxiter)
+        cap = min(maxiter, self.history_capacity) if history else 0
+        hist = np.empty((max(cap, 1), k), dtype=np.float64)
+        p = L.BsmLsqrParams(C.sizeof(L.BsmLsqrParams), 0 if X0 is None else 1, float(rtol), float(atol), float(ntol), float(damp),
+                            maxiter, cap)
+        info = L.BsmCgInfo()
+        cols = (L.BsmCgColumn * k)()
+        arn, an = np.zeros(k), np.zeros(k)
+        dp = C.POINTER(C.c_double)
+        L.check(L.lib().bsm_lsqr_solve(self._ptr, k, bp, ldb, xp, ldx, C.byref(p), C.byref(info), cols, hist.ctypes.data_as(dp),
+                                       arn.ctypes.data_as(dp), an.ctypes.data_as(dp), bms, st))
+        return X, LsqrInfo(info, cols, hist[:min(info.iterations, cap)].copy(), arn, an)
+
+
+def lsqr(A, B, **kw):
+    """One-shot form: Lsqr(A, columns of B, dtype of B).solve(B, **kw) -> (X, info)."""
+    k = 1 if getattr(B, "ndim", 1) == 1 else B.shape[1]
+    return Lsqr(A, nrhs=k, dtype=_elt(B)).solve(B, **kw)
 
 
 # ---- restarted GMRES on several right-hand sides in lockstep, on the device (bsm_gmres_multi_*) ----------------------------

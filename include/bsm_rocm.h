@@ -912,6 +912,87 @@ int bsm_minres_solve(struct bsm_minres_s *S, int32_t nrhs, const void *B, int64_
                      double *history /* history_capacity x nrhs, may be NULL */, int memspace, void *stream);
 int bsm_minres_destroy(struct bsm_minres_s *S);
 
+/* bsm_lsqr_*: LSQR (Paige and Saunders) for RECTANGULAR, rank-deficient and damped least-squares problems --
+ * over-determined fits and collocation systems, under-determined systems (the minimum-norm solution), singular square
+ * operators --, nrhs = 1 .. BSM_CG_MAX_RHS right-hand sides in lockstep, wholly on the device.  The one solver here that
+ * takes an op(A) that is not square, and the one that issues the ADJOINT product: per iteration one multi-column product
+ * with op(A) and one with op(A)^H (bsm_mul_multi: the matrix is streamed once per batch of columns), 6 work vectors per
+ * right-hand side whatever the iteration count (4 of X's length, 2 of B's).  Info and columns are those of bsm_cg_*.
+ * (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+ *   Method, per column c: it minimises ||b - op(A) x||^2 + damp^2 ||x - x0||^2.  Every scalar is REAL and held in the real
+ *   type of vdtype; the norms are 2-norms, the real parts of sum conj(u_i) u_i.  The Lanczos vectors u~ (m = rows(op(A))
+ *   entries) and v~ (n = cols(op(A)) entries) are kept UNNORMALISED, u~ = beta u and v~ = alpha v: the 1 / alpha, 1 / beta
+ *   factors ride in the scalars, no pass scales a vector.
+ *     start:  u~ = b - op(A) x0 (or b);  beta = ||u~||;  bnorm = ||b||;  tol_c = max(rtol bnorm, atol)
+ *             v~ = op(A)^H u~ / beta;  alpha = ||v~||;  w = v~ / alpha;  phibar = beta;  rhobar = alpha;  res2 = 0;  anorm = 0
+ *             rnorm = beta;  arnorm = alpha beta;  the decision below is taken here too (0 iterations)
+ *     repeat: u~ = op(A) v~ / alpha - (alpha / beta) u~;  beta' = ||u~||
+ *             anorm = sqrt(anorm^2 + alpha^2 + beta'^2 + damp^2)
+ *             v~ = op(A)^H u~ / beta' - (beta' / alpha) v~;  alpha' = ||v~||      (beta' == 0: v~ = 0, alpha' = 0, no division)
+ *             rhobar1 = sqrt(rhobar^2 + damp^2);  cs1 = rhobar / rhobar1;  sn1 = damp / rhobar1;  psi = sn1 phibar;
+ *             phibar = cs1 phibar
+ *             rho = sqrt(rhobar1^2 + beta'^2);  c = rhobar1 / rho;  s = beta' / rho;  theta = s alpha';  rhobar = -c alpha';
+ *             phi = c phibar;  phibar = s phibar;  tau = s phi
+ *             x += (phi / rho) w;  w = v~ / alpha' - (theta / rho) w          (alpha' == 0: w is not needed again)
+ *             res2 += psi^2;  rnorm = sqrt(phibar^2 + res2);  arnorm = alpha' |tau|
+ *     decide: rnorm or arnorm not finite: status 2;  rnorm <= tol_c: 0;  arnorm <= ntol anorm rnorm: 0;  alpha' == 0 or
+ *             beta' == 0: 0 (the Krylov space ended: the iterate IS the solution);  else the column runs on
+ *   rnorm is the estimate of ||[b; damp x0] - [op(A); damp I] x||, without damp that is ||b - op(A) x||; arnorm estimates
+ *   the norm of the normal-equation residual op(A)^H r - damp^2 (x - x0); anorm is the running Frobenius-norm estimate of
+ *   the bidiagonal factor (scipy's anorm).  The FIRST rule ends a column of a consistent system, the SECOND one a column whose
+ *   residual cannot vanish.  With use_x0 the damping term pulls towards X0, not towards zero.  Status 3 is never reported:
+ *   every breakdown of LSQR is convergence.  No division by zero and no root of a negative number is executed.
+ * create: one device allocation on A's device, reported in info: X, V, W, P (n rows) and U, Q (m rows) as column-major
+ *   matrices of nrhs_max columns with the leading dimension rounded up to whole 16-byte groups, the per-workgroup partial
+ *   sums of both lengths, the column states; a ring of pinned record slots and events.  vdtype and the (handle, vector)
+ *   pairings are those of bsm_cg_create.  op(A)^H is BSM_OP_C of the handle for opA = BSM_OP_N, BSM_OP_N for BSM_OP_C, and
+ *   for BSM_OP_T BSM_OP_N on a real handle; on a COMPLEX handle opA = BSM_OP_T would need conj(A), which no product offers:
+ *   BSM_ERR_UNSUPPORTED.  The other refusals are those of bsm_cg_create without M, method and the square requirement.  The
+ *   handle must outlive the solver.  There is no preconditioner argument.
+ * solve: B (m x nrhs, ldb >= max(m, 1)) and X (n x nrhs, ldx >= max(n, 1)), column-major, any element alignment, touched as
+ *   in bsm_cg_solve.  use_x0, memspace, stream, history layout (rnorm per row), cols and the refusals as in bsm_cg_solve
+ *   with bsm_lsqr_params in the place of bsm_cg_params; ntol or damp negative or NaN: BSM_ERR_INVALID.  arnorm, anorm (may
+ *   be NULL): nrhs doubles each, the two estimates of every column when it stopped, copied out once after the solve's final
+ *   synchronisation.  m == 0 or n == 0: status 0, B and X untouched.
+ *   Kernels (csrc/bsm_lsqr.hip).  The vectors have two lengths, so a solve runs on TWO grids: (krylov_grid(m), columns) for
+ *   U and Q, (krylov_grid(n), columns) for X, V, W, P; a kernel of the n-grid that needs ||u~||^2 adds the partials the
+ *   m-grid left.  ls_start (m: u~, the shares of ||b||^2 and ||u~||^2), ls_begin (n: v~ = P / beta, the shares of ||v~||^2),
+ *   ls_u (m), ls_v (n; at iteration 0 it also leaves w = v~ / alpha), ls_update (n: every workgroup derives alpha', beta',
+ *   the rotations and the decision from the partials and the state -- lsqr_step of csrc/bsm_lsqr.h, one function for host
+ *   and device --; x and w in one pass), ls_decide (one wave per column: the state of the next iteration, the record).  Per
+ *   iteration: product op(A), ls_u, product op(A)^H, ls_v, ls_update, ls_decide.  No floating-point atomic, nobody waits,
+ *   and a launch never reads a scalar that the same launch replaces (two slots alternating by iteration parity; ls_update
+ *   leaves the step it derived beside them for ls_decide).  A column that has a status is FROZEN from the next launch on.
+ *   Run-to-run reproducibility: the SOLVER's kernels add in one fixed order, so two runs of a solve agree to the bit where
+ *   BOTH products do.  One of the two products of an iteration is always a transposed one: on a handle without a second
+ *   ordering (bsm_options.transpose_image = 0, the default) it accumulates with floating-point atomics, the last bits of X
+ *   and of the estimates may then differ from run to run, and a count may move by one.  With transpose_image = 1 both
+ *   products are forward passes (exclusive stores on a conflict-free operator) and X, counts and history are bit-identical.
+ *   The solvers above never issue a transposed product unless asked to (opA), so this is particular to bsm_lsqr.
+ *   The host enqueues iteration j + 1 before it waits for the record of iteration j and stops when no column is running or
+ *   maxiter is reached: X, every column's iterations and history do not depend on how late it notices.
+ *   info: a_products = 2 * iterations + 1 (+ 1 with use_x0), m_products = 0; a solve that ends before maxiter has paid at
+ *   most two products beyond that, for the iteration enqueued ahead of the last record. */
+typedef struct {
+    int32_t struct_size; /* = sizeof(bsm_lsqr_params) */
+    int32_t use_x0;
+    double rtol, atol; /* rnorm <= max(rtol ||b||, atol) */
+    double ntol;       /* arnorm <= ntol anorm rnorm */
+    double damp;
+    int64_t maxiter;
+    int64_t history_capacity; /* rows of `history` */
+} bsm_lsqr_params;
+BSM_LAYOUT_ASSERT(sizeof(bsm_lsqr_params) == 56 && offsetof(bsm_lsqr_params, rtol) == 8 && offsetof(bsm_lsqr_params, ntol) == 24 &&
+                      offsetof(bsm_lsqr_params, maxiter) == 40,
+                  "bsm_lsqr_params layout");
+struct bsm_lsqr_s;
+int bsm_lsqr_create(bsm_matrix_t A, int opA, int vdtype, int32_t nrhs_max, struct bsm_lsqr_s **out);
+int bsm_lsqr_solve(struct bsm_lsqr_s *S, int32_t nrhs, const void *B, int64_t ldb, void *X, int64_t ldx, const bsm_lsqr_params *p,
+                   bsm_cg_info *info, bsm_cg_column *cols /* nrhs, may be NULL */,
+                   double *history /* history_capacity x nrhs, may be NULL */, double *arnorm /* nrhs, may be NULL */,
+                   double *anorm /* nrhs, may be NULL */, int memspace, void *stream);
+int bsm_lsqr_destroy(struct bsm_lsqr_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

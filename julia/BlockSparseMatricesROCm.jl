@@ -634,6 +634,10 @@ mutable struct BsmCgInfo            # mirrors bsm_cg_info (48 bytes)
     status::Int32; columns_converged::Int32; iterations::Int64
     a_products::Int64; m_products::Int64; workspace_bytes::Int64; workspace::UInt64
 end
+mutable struct BsmLsqrParams        # mirrors bsm_lsqr_params (56 bytes)
+    struct_size::Int32; use_x0::Int32; rtol::Float64; atol::Float64; ntol::Float64; damp::Float64
+    maxiter::Int64; history_capacity::Int64
+end
 struct BsmCgColumn                  # mirrors bsm_cg_column (32 bytes)
     status::Int32; reserved::Int32; iterations::Int64; residual::Float64; bnorm::Float64
 end
@@ -778,6 +782,44 @@ function minres!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; M=nothing, rtol::
         ccall((:bsm_minres_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
     end
     return X, info, columns, history[:, 1:min(info.iterations, maxiter)]
+end
+
+"""
+    lsqr!(X, A, B; rtol=1e-8, atol=0.0, ntol=1e-8, damp=0.0, maxiter=min(size(A)...), x0=false)
+        -> (X, info, columns, history, normal_residual, anorm)
+
+LSQR for `min ||B - A X||^2 + damp^2 ||X - X0||^2` with `A` of any shape and rank -- over-determined, under-determined (the
+minimum-norm solution) or singular --, and 1 to 16 right-hand sides advancing in lockstep on two multi-column products per
+iteration, one with `A` and one with `A'`, every step of it on the device (bsm_lsqr_create / _solve / _destroy).  `B` has
+`size(A, 1)` rows, `X` `size(A, 2)`; both are host vectors or matrices of `A`'s element type, or complex ones of its
+precision under a real `A`.  `transpose(A)` of a complex `A` is refused (its adjoint is `conj(A)`).  Column `c` stops with
+status 0 when the estimate of `norm(b - A x)` is `<= max(rtol * norm(B[:, c]), atol)`, when the estimate of the
+normal-equation residual is `<= ntol * anorm * ` that estimate, or when the Krylov space ends; 1 `maxiter` reached, 2 a
+non-finite estimate.  `info`, `columns` and `history` are those of [`cg!`](@ref); `normal_residual` and `anorm` hold the two
+estimates per column; `info.a_products == 2 * info.iterations + 1` (`+ 1` with `x0`).  There is no preconditioner argument.
+(The reference offers nothing here: a `LinearMap` is handed to a Julia solver package, whose Krylov loop runs on the host.)
+"""
+function lsqr!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; rtol::Real=1e-8, atol::Real=0.0, ntol::Real=1e-8, damp::Real=0.0,
+               maxiter::Integer=min(size(A, 1), size(A, 2)), x0::Bool=false) where {T<:ROCmEltype}
+    m, n, k = size(A, 1), size(A, 2), size(B, 2)
+    size(B, 1) == m && size(X, 1) == n && size(X, 2) == k || throw(DimensionMismatch("lsqr! needs B with size(A, 1) rows and X with size(A, 2) rows and the columns of B"))
+    1 <= k <= 16 || throw(ArgumentError("lsqr! takes 1 to 16 right-hand sides"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:bsm_lsqr_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Cint, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), _DTYPE[T], k, out))
+    p = BsmLsqrParams(sizeof(BsmLsqrParams), x0, rtol, atol, ntol, damp, maxiter, maxiter)
+    info = BsmCgInfo(0, 0, 0, 0, 0, 0, 0)
+    columns = Vector{BsmCgColumn}(undef, k)
+    history = zeros(Float64, k, max(maxiter, 1))
+    normal_residual, anorm = zeros(Float64, k), zeros(Float64, k)
+    try
+        GC.@preserve A X B columns history normal_residual anorm _check(ccall((:bsm_lsqr_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{BsmLsqrParams}, Ref{BsmCgInfo}, Ptr{BsmCgColumn}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Cint, Ptr{Cvoid}),
+            out[], k, pointer(B), max(m, 1), pointer(X), max(n, 1), p, info, columns, history, normal_residual, anorm, 0, C_NULL))
+    finally
+        ccall((:bsm_lsqr_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return X, info, columns, history[:, 1:min(info.iterations, maxiter)], normal_residual, anorm
 end
 
 end # module
