@@ -1,6 +1,7 @@
 """Device helpers shared by the GPU suites: the `torch_cuda` and `env` fixtures (imported by name into a test module),
 the tolerance table, column-major device copies (`dev_copy`, `dev_vec`, `dev_mat` with NaN padding, `outside_bytes`),
-`scatter` for partitioned vectors, and the two product drivers `gpu_mul` (one column) and `gpu_mul_multi` (several).
+`scatter` for partitioned vectors, the two product drivers `gpu_mul` (one column) and `gpu_mul_multi` (several), and the
+byte and pass-count checks of the handle suites (`same_products`, `passes_of_one_product`, `same_bytes`).
 `torch` is an argument wherever a helper needs it, so that this module imports without it.  Test code only."""
 import numpy as np
 import pytest
@@ -102,3 +103,38 @@ def gpu_mul_multi(torch, bsm, A, op, X, Y0, alpha=1, beta=0, strong=True, pad=0)
     torch.cuda.synchronize()
     assert (outside_bytes(xb, xl, xl + pad, k), outside_bytes(yb, yl, yl + pad, k)) == before, "padding of X / Y was written"
     return yv.cpu().numpy()
+
+
+# ---- what the solver-on-every-handle suites (test_gpu_solver_handles.py, test_gpu_lsqr_handles.py) share ------------------
+def result_like(torch, bsm, H, x):
+    """an uninitialised device vector / column-major matrix for op(H) x: the rows of op(H) (those of x where it is square), the
+    columns and the type of x"""
+    rows = bsm.size(H)[0]
+    return torch.empty((x.shape[1], rows), dtype=x.dtype, device="cuda").t() if x.dim() == 2 else torch.empty(rows, dtype=x.dtype, device="cuda")
+
+
+def same_products(torch, bsm, Bd, *ops):
+    """two products of every handle give the same bytes (as test_freezing_holds asserts before it compares solves)"""
+    x = Bd[:, 0] if Bd.shape[1] == 1 else Bd
+    for H in ops:
+        y1, y2 = (result_like(torch, bsm, H, x) for _ in range(2))
+        bsm.mul(y1, H, x)
+        bsm.mul(y2, H, x)
+        torch.cuda.synchronize()
+        assert y1.cpu().numpy().tobytes() == y2.cpu().numpy().tobytes(), "the products of this handle are not reproducible"
+
+
+def passes_of_one_product(torch, bsm, H, Hop, Bd):
+    """what one plain product of op(H) (Hop: H or its wrapper) of Bd's width adds to H.value_passes()"""
+    x = Bd[:, 0] if Bd.shape[1] == 1 else Bd
+    y = result_like(torch, bsm, Hop, x)
+    before = H.value_passes()
+    bsm.mul(y, Hop, x)
+    torch.cuda.synchronize()
+    return H.value_passes() - before
+
+
+def same_bytes(a, b, what):
+    (xa, ia), (xb, ib) = a, b
+    assert xa.cpu().numpy().tobytes() == xb.cpu().numpy().tobytes(), (what, "X differs")
+    assert np.asarray(ia.history).tobytes() == np.asarray(ib.history).tobytes(), (what, "the history differs")

@@ -1,5 +1,6 @@
-"""What the LSQR suites (test_lsqr_cpu.py, test_gpu_lsqr.py) share: the numpy twin of bsm_lsqr_solve, the rectangular test
-problems, the acceptance of a solve, and raw ctypes drivers of bsm_lsqr_create / _solve / _destroy and of the test hook
+"""What the LSQR suites (test_lsqr_cpu.py, test_gpu_lsqr.py, test_lsqr_handles_cpu.py, test_gpu_lsqr_handles.py) share: the
+numpy twin of bsm_lsqr_solve, the rectangular test problems, the operands and legs of the handle suites (described where they
+are defined), the acceptance of a solve, and raw ctypes drivers of bsm_lsqr_create / _solve / _destroy and of the test hook
 bsm_debug_lsqr_step.  Test code only.
 
 The twin.  lsqr_twin is LSQR as include/bsm_rocm.h states the recurrences -- unnormalised Lanczos vectors, every scalar real,
@@ -44,16 +45,25 @@ class Dense:
         self.A = np.asarray(A)
         self.shape = self.A.shape
         self.dtype = self.A.dtype
+        self._kept = {}  # the conjugate transpose and the permuted copies: the same arrays at every product of a run
 
     def astype(self, dtype):
         return Dense(self.A.astype(dtype))
 
+    def _keep(self, key, make):
+        if key not in self._kept:
+            self._kept[key] = make()
+        return self._kept[key]
+
+    def _permuted(self, which, M, perm):
+        return self._keep((which, id(perm)), lambda: (perm, np.ascontiguousarray(M[:, perm])))[1]  # (perm is kept: its id stays its own)
+
     def times(self, v, perm=None):
-        return self.A @ v if perm is None else np.ascontiguousarray(self.A[:, perm]) @ v[perm]
+        return self.A @ v if perm is None else self._permuted("N", self.A, perm) @ v[perm]
 
     def adj(self, u, perm=None):
-        H = self.A.conj().T
-        return H @ u if perm is None else np.ascontiguousarray(H[:, perm]) @ u[perm]
+        H = self._keep("H", lambda: self.A.conj().T)
+        return H @ u if perm is None else self._permuted("H", H, perm) @ u[perm]
 
     @property
     def H(self):
@@ -331,6 +341,174 @@ def singular_symmetric():
     D = (Q * np.concatenate([np.zeros(10), np.linspace(1, 3, 30)])) @ Q.T
     D = (D + D.T) / 2
     return D, np.asfortranarray(D @ rng.uniform(-1, 1, (40, 3)))
+
+
+# ---- the handle suites (test_lsqr_handles_cpu.py, test_gpu_lsqr_handles.py) -------------------------------------------------
+# An OPERAND is a dense operator A (m x n) with five inconsistent right-hand sides Bi (m rows) and five right-hand sides Bu (n
+# rows) of the under-determined system A^H X = Bu.  A LEG of it is a system the twin and the device solve: "inconsistent" is
+# (A, Bi), ended by rule 2; "adjoint" is (A^H, Bu) -- Lsqr(adjoint(H)) --, ended by rule 1.  The operands:
+#   base         lsqr_problem's A, Bi, Bu (the pairs test_lsqr_cpu.py pins: its legs "inconsistent" and "under");
+#   cvec         the real base operand of the complex type's precision under complex columns Bi + i Bi[:, ::-1], Bu + i Bu[:, ::-1]
+#                (the columns of test_real_operator_under_complex_vectors);
+#   rounded      base with A rounded to single precision and widened again: what a storage=float32 / complex64 handle holds;
+#   bordered     the blocks of the blocksparse base problem at size (608, 408): rows 601 .. 608 and columns 401 .. 408 lie in no
+#                block.  B (608 x 5), then Bu (408 x 5) uniform from default_rng(4700), the uncovered rows of Bu zeroed (A^H X =
+#                Bu is consistent then).  The uncovered entries of X are zero in every iterate: X is a combination of the v, and
+#                v = A^H u has exact zeros there;
+#   symmetric    D = Q diag(+-linspace(1, 3, 400)) Q^T of order 400, signs alternating, symmetrised to the bit, and five uniform
+#                columns B; rng = default_rng(4100): Q, the sets cut(rng, 400), B in this order.  Real types only.  D is regular,
+#                both legs are (D, B) ended by rule 1;
+#   vbcrs2       base with block 1 of the VBCRS grid (rows 1 .. 100 x columns 1 .. 100) negated, as
+#                test_one_solver_across_update_blocks does;
+#   blocksparse2 base with every block of the largest row set negated (block 1 of that cut is 1 x 1): ten ids, a partial update.
+LEGS = ("inconsistent", "adjoint")
+BORDER = 8
+_operands, _handle_runs, _extra = {}, {}, {}
+
+
+class Operand:
+    def __init__(self, A, Bi, Bu):
+        self.A, self.Bi, self.Bu = A, Bi, Bu
+
+
+def single_of(dtype):
+    return np.dtype(np.complex64 if is_complex(dtype) else np.float32)
+
+
+def complex_columns(B, cdtype):
+    return np.asfortranarray((B + 1j * B[:, ::-1]).astype(cdtype))
+
+
+def largest_row_set(dtype=np.float64):
+    """-> (position of the largest row set of the blocksparse cut, its 0-based rows, the 1-based ids of its blocks)"""
+    p = lsqr_problem("blocksparse", dtype)[0]
+    sizes = [len(r) for r in p["rowindices"]]
+    big = max(sizes)
+    ids = [k + 1 for k, s in enumerate(sizes) if s == big]
+    rows = p["rowindices"][ids[0] - 1]
+    assert all(np.array_equal(p["rowindices"][k - 1], rows) for k in ids)
+    return ids[0] - 1, rows - 1, ids
+
+
+def bordered_problem(dtype):
+    """-> (blocksparse problem of size (608, 408), A, B, Bu) (the operand `bordered`); computed once, not to be written to"""
+    key = ("bordered", np.dtype(dtype).name)
+    if key not in _extra:
+        p0, A0 = lsqr_problem("blocksparse", dtype)[:2]
+        m, n = M600 + BORDER, N400 + BORDER
+        A = np.zeros((m, n), dtype)
+        A[:M600, :N400] = A0
+        rng = np.random.default_rng(4700)
+        B = np.asfortranarray(uniform(rng, (m, NB), dtype))
+        Bu = np.asfortranarray(uniform(rng, (n, NB), dtype))
+        Bu[N400:] = 0
+        _extra[key] = (dict(p0, size=(m, n)), A, B, Bu)
+    return _extra[key]
+
+
+def symmetric_problem(dtype):
+    """-> (symmetric problem of order 400: a diagonal block per set, every lower off-diagonal block; D; B) (the operand
+    `symmetric`); computed once, not to be written to"""
+    key = ("symmetric", np.dtype(dtype).name)
+    if key not in _extra:
+        assert not is_complex(dtype)
+        rng = np.random.default_rng(4100)
+        Q, _ = np.linalg.qr(rng.uniform(-1, 1, (N400, N400)))
+        D = (Q * (np.linspace(1, 3, N400) * np.where(np.arange(N400) % 2 == 0, 1.0, -1.0))) @ Q.T
+        D = ((D + D.T) / 2).astype(dtype)
+        sets = cut(rng, N400)
+        B = np.asfortranarray(uniform(rng, (N400, NB), dtype))
+        offs, ri, ci = [], [], []
+        for a in range(len(sets)):
+            for b in range(a):
+                offs.append(np.asfortranarray(D[np.ix_(sets[a] - 1, sets[b] - 1)]))
+                ri.append(sets[a])
+                ci.append(sets[b])
+        p = dict(kind="symmetric", diagonals=[np.asfortranarray(D[np.ix_(s - 1, s - 1)]) for s in sets], diagonalindices=sets,
+                 offdiagonals=offs, rowindices=ri, colindices=ci, size=(N400, N400))
+        _extra[key] = (p, D, B)
+    return _extra[key]
+
+
+def operand(name, dtype):
+    """-> Operand (the table above); computed once per (name, dtype) and not to be written to"""
+    key = (name, np.dtype(dtype).name)
+    if key in _operands:
+        return _operands[key]
+    if name == "cvec":
+        assert is_complex(dtype)
+        _, A, _, _, Bi, Bu = lsqr_problem("vbcrs", real_of(dtype))
+        o = Operand(A.astype(dtype), complex_columns(Bi, dtype), complex_columns(Bu, dtype))
+    elif name == "bordered":
+        o = Operand(*bordered_problem(dtype)[1:])
+    elif name == "symmetric":
+        _, D, B = symmetric_problem(dtype)
+        o = Operand(D, B, B)
+    else:
+        _, A, _, _, Bi, Bu = lsqr_problem("vbcrs", dtype)
+        if name == "rounded":
+            assert np.dtype(dtype) != single_of(dtype)
+            A = A.astype(single_of(dtype)).astype(dtype)
+        elif name == "vbcrs2":
+            A = A.copy()
+            A[:100, :100] = -A[:100, :100]
+        elif name == "blocksparse2":
+            A = A.copy()
+            rows = largest_row_set(dtype)[1]
+            A[rows] = -A[rows]
+        else:
+            assert name == "base", name
+        o = Operand(A, Bi, Bu)
+    _operands[key] = o
+    return o
+
+
+def leg_system(name, dtype, leg):
+    """-> (dense operator of the system, B, the rule its columns end by)"""
+    o = operand(name, dtype)
+    assert leg in LEGS
+    if name == "symmetric":
+        return o.A, o.Bi, 1
+    return (o.A, o.Bi, 2) if leg == "inconsistent" else (np.ascontiguousarray(o.A.conj().T), o.Bu, 1)
+
+
+def leg_runs(name, dtype, leg):
+    """the twin on the five columns of a leg at rtol = ntol = lsqr_rtol(dtype), maxiter 400; computed once"""
+    key = (name, np.dtype(dtype).name, "adjoint" if name == "symmetric" else leg)
+    if key not in _handle_runs:
+        A, B, _ = leg_system(name, dtype, leg)
+        r = lsqr_rtol(dtype)
+        _handle_runs[key] = [lsqr_twin(A, B[:, c], r, 0.0, r, 0.0, 400, dtype) for c in range(NB)]
+    return _handle_runs[key]
+
+
+def new_values(kind, dtype):
+    """the update legs' second set of values -> (1-based ids, the new blocks, the problem with them in place, the operand's name)"""
+    p = lsqr_problem(kind, dtype)[0]
+    ids = [1] if kind == "vbcrs" else largest_row_set(dtype)[2]
+    blocks = list(p["blocks"])
+    for k in ids:
+        blocks[k - 1] = np.asfortranarray(-p["blocks"][k - 1])
+    return ids, [blocks[k - 1] for k in ids], dict(p, blocks=blocks), kind + "2"
+
+
+class Half:
+    """an operator whose forward product uses one set of values and whose adjoint product another: what LSQR sees of a
+    transpose_image handle whose refill reached one image only"""
+
+    def __init__(self, forward, backward):
+        self.forward, self.backward = _as_op(forward), _as_op(backward)
+        assert self.forward.shape == self.backward.shape
+        self.shape, self.dtype = self.forward.shape, self.forward.dtype
+
+    def astype(self, dtype):
+        return Half(self.forward.astype(dtype), self.backward.astype(dtype))
+
+    def times(self, v, perm=None):
+        return self.forward.times(v, perm)
+
+    def adj(self, u, perm=None):
+        return self.backward.adj(u, perm)
 
 
 # ---- what the GPU suite accepts ---------------------------------------------------------------------------------------------

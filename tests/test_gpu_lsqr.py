@@ -17,6 +17,7 @@ from _jacobi import CODE, uniform
 from _lockstep import COLUMNS, MARGIN, RANGE_BYTES, deviation, krylov_grid, reference_of, staggered6
 from _lsqr import (LSQR_ITS, M600, N400, NB, check_columns, check_products, history_unit, lsqr_problem, lsqr_rtol, lsqr_spread, lsqr_twin, raw_lsqr_create,
                    raw_lsqr_destroy, raw_lsqr_solve, singular_symmetric, tall_case, true_criteria)
+from _values import copied
 
 pytestmark = pytest.mark.gpu
 
@@ -360,7 +361,7 @@ def test_numpy_arrays_a_callers_stream_and_the_one_shot(torch_cuda, bsm):
 def test_one_solver_across_update_blocks(torch_cuda, bsm):
     torch, dtype = torch_cuda, np.float64
     p, A, _, _, Bi, _ = lsqr_problem("vbcrs", dtype)
-    H = bsm.synthetic.build(p)
+    H = bsm.synthetic.build(copied(p))  # (update_blocks writes into the blocks a handle was built from; the problem is shared)
     S = bsm.Lsqr(H, nrhs=NB)
     Bd = dev_copy(torch, Bi)
     X, info = S.solve(Bd, rtol=1e-8, ntol=1e-8, maxiter=400)

@@ -31,7 +31,7 @@ import numpy as np
 import pytest
 
 from _common import Cc, N, T, wrap
-from _gpu import dev_copy, torch_cuda  # noqa: F401
+from _gpu import dev_copy, passes_of_one_product, same_bytes, same_products, torch_cuda  # noqa: F401
 from _jacobi import CODE, uniform
 from _krylov import ERR_UNSUPPORTED, exact_minv
 from _lockstep import SINGLE_TYPES, WIDE_TYPES, case_id, shifted, solver_cases, solvers
@@ -79,34 +79,6 @@ def handles(bsm, c, akw=None, mkw=None, op=N, torch=None, p=None, pm=None):
     A = bsm.synthetic.build(p, **(akw or {}))
     Am = A if same else bsm.synthetic.build(pm, **(akw or {}))
     return A, Am, bsm.block_jacobi(wrap(bsm, Am, op), c.sets, **(mkw or {}))
-
-
-def same_products(torch, bsm, Bd, *ops):
-    """two products of every handle give the same bytes (as test_freezing_holds asserts before it compares solves)"""
-    x = Bd[:, 0] if Bd.shape[1] == 1 else Bd
-    y1, y2 = (torch.empty(tuple(reversed(x.shape)), dtype=x.dtype, device="cuda").t() if x.dim() == 2 else torch.empty_like(x)
-              for _ in range(2))
-    for H in ops:
-        bsm.mul(y1, H, x)
-        bsm.mul(y2, H, x)
-        torch.cuda.synchronize()
-        assert y1.cpu().numpy().tobytes() == y2.cpu().numpy().tobytes(), "the products of this handle are not reproducible"
-
-
-def passes_of_one_product(torch, bsm, H, Hop, Bd):
-    """what one plain product of op(H) (Hop: H or its wrapper) of Bd's width adds to H.value_passes()"""
-    x = Bd[:, 0] if Bd.shape[1] == 1 else Bd
-    y = torch.empty(tuple(reversed(x.shape)), dtype=x.dtype, device="cuda").t() if x.dim() == 2 else torch.empty_like(x)
-    before = H.value_passes()
-    bsm.mul(y, Hop, x)
-    torch.cuda.synchronize()
-    return H.value_passes() - before
-
-
-def same_bytes(a, b, what):
-    (xa, ia), (xb, ib) = a, b
-    assert xa.cpu().numpy().tobytes() == xb.cpu().numpy().tobytes(), (what, "X differs")
-    assert np.asarray(ia.history).tobytes() == np.asarray(ib.history).tobytes(), (what, "the history differs")
 
 
 def check_pass_count(torch, bsm, R, S, A, M, Aop, Bd, first, per, what):
