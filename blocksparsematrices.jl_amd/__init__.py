@@ -12,5 +12,7 @@ from .entries import *  # noqa: F401,F403
 from .matrices import *  # noqa: F401,F403
 from .solvers import *  # noqa: F401,F403
 from .solvers import Lsqr, LsqrInfo, Minres, lsqr, minres  # noqa: F401
+from .solvers import (PolynomialPreconditioner, chebyshev, chebyshev_coefficients, lanczos_bounds, neumann,  # noqa: F401
+                      polynomial)
 
 __all__ = matrices.__all__ + entries.__all__ + solvers.__all__ + ["synthetic"]

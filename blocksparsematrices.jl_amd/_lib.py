@@ -23,6 +23,7 @@ BSM_INVERT_LDS_BYTES, BSM_INVERT_MAX_N = 131072, 1024
 BSM_GMRES_MAX_RESTART = 128  # bsm_gmres_create's restart, bsm_krylov_orth's k (include/bsm_rocm.h)
 BSM_CG_MAX_RHS = 16  # bsm_cg_create's nrhs_max (include/bsm_rocm.h)
 BSM_CG_METHOD_CG, BSM_CG_METHOD_COCG = 0, 1
+BSM_POLY_MAX_STEPS = 64  # bsm_poly_create's steps (include/bsm_rocm.h)
 (BSM_BK_VBCRS_PERM, BSM_BK_VBCRS_ROWPTR, BSM_BK_VBCRS_COLINDICES, BSM_BK_VBCRS_ROWINDICES,
  BSM_BK_COLORS, BSM_BK_TRANSPOSECOLORS, BSM_BK_DIAGONALCOLORS) = range(7)
 
@@ -100,7 +101,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_krylov_orth_work", "bsm_krylov_orth", "bsm_gmres_create", "bsm_gmres_solve",
            "bsm_gmres_destroy", "bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy", "bsm_bicgstab_create", "bsm_bicgstab_solve",
            "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy",
-           "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy", "bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy"]
+           "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy", "bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy",
+           "bsm_poly_create", "bsm_poly_info"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -247,6 +249,12 @@ def lib():
         L.bsm_lsqr_destroy.argtypes = [C.c_void_p]
         for name in ("bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy"):
             getattr(L, name).restype = C.c_int
+    if hasattr(L, "bsm_poly_create") or "BSM_LIB" not in os.environ:  # (developer A/B builds may predate them)
+        _F64P = C.POINTER(C.c_double)
+        L.bsm_poly_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, _F64P, _F64P,
+                                      C.POINTER(C.c_void_p)]
+        L.bsm_poly_info.argtypes = [C.c_void_p, _I32P, _F64P, _F64P, _I64P]
+        L.bsm_poly_create.restype = L.bsm_poly_info.restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p
     L.bsm_version.restype = C.c_char_p

@@ -1,6 +1,6 @@
 // bsm_capi.cpp -- the extern "C" surface of libbsmrocm.so (include/bsm_rocm.h), but for the features whose unit holds
 // its own entry points: reading entries (bsm_entries.cpp), the block inverse (bsm_invert.cpp), the Gram-Schmidt pass
-// (bsm_krylov.cpp), GMRES (bsm_gmres_multi.cpp).
+// (bsm_krylov.cpp), the solvers (bsm_cg.cpp, ...), composed handles (bsm_poly.cpp).
 // Plain pointers and sizes only; checks and converts arguments, has the operator built, refilled and
 // released (bsm_operator.cpp: LocalOperator; bsm_dist.cpp for handles over several devices) and
 // forwards bsm_mul to the HIP launchers.  Never throws across the ABI.
@@ -532,6 +532,7 @@ extern "C" int bsm_vec_add_segments(int dtype, void *y, int32_t nseg, const int6
 
 extern "C" int bsm_part_info(bsm_matrix_t A, int32_t part, bsm_part_info_t *out) {
     if (!A || !out) return fail(BSM_ERR_INVALID, "null argument");
+    if (int rc = poly_refusal(A, "bsm_part_info")) return rc;
     if (!A->dist) return fail(BSM_ERR_INVALID, "not a multi-device handle");
     return dist_part_info(A, part, out);
 }
@@ -660,6 +661,7 @@ static int mul_k(bsm_matrix_s *A, int op, long long K, const void *X, long long 
 static int mul_entry(bsm_matrix_s *A, int op, bool cplx, bool multi, int64_t nrhs, const void *X, int64_t ldx, void *Y,
                      int64_t ldy, const void *alpha, const void *beta, int beta_strong_zero, int memspace, void *stream) {
     if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    if (A->poly) return poly_mul(A, op, cplx, multi, nrhs, X, ldx, Y, ldy, alpha, beta, beta_strong_zero, memspace, (hipStream_t)stream);
     const int dt = A->an.dtype;
     if (cplx && (dt == BSM_C64 || dt == BSM_C128))
         return fail(BSM_ERR_INVALID, "complex handle: bsm_mul / bsm_mul_multi take its complex vectors");
@@ -709,6 +711,7 @@ extern "C" int bsm_mul_multi_cvec(bsm_matrix_t A, int op, int64_t nrhs, const vo
 extern "C" int bsm_value_passes(bsm_matrix_t A, int64_t *count) {
     if (!A) return fail(BSM_ERR_INVALID, "null handle");
     if (!count) return fail(BSM_ERR_INVALID, "null count");
+    if (int rc = poly_refusal(A, "bsm_value_passes")) return rc;
     if (A->dist) return fail(BSM_ERR_UNSUPPORTED, "bsm_value_passes: single-device handles only");
     *count = __atomic_load_n(&A->img.value_passes, __ATOMIC_RELAXED) + __atomic_load_n(&A->img_t.value_passes, __ATOMIC_RELAXED);
     return BSM_OK;
@@ -719,6 +722,7 @@ extern "C" int bsm_mul_parts(bsm_matrix_t A, int op, const void *const *x_parts,
     if (!A) return fail(BSM_ERR_INVALID, "null handle");
     if (op < 0 || op > 2) return fail(BSM_ERR_INVALID, "bad op");
     if (!x_parts || !y_parts) return fail(BSM_ERR_INVALID, "null vector parts");
+    if (int rc = poly_refusal(A, "bsm_mul_parts")) return rc;
     if (!A->dist) return fail(BSM_ERR_INVALID, "bsm_mul_parts needs a multi-device handle (bsm_options.ctx)");
     return dist_mul_parts(A, op, x_parts, y_parts, alpha, beta, beta_strong_zero, streams);
 }
@@ -727,6 +731,7 @@ extern "C" int bsm_update_blocks(bsm_matrix_t A, int64_t nupd, const int64_t *id
                                  const int64_t *ld, int memspace, void *stream) {
     BSM_GUARDED(
         if (!A) return fail(BSM_ERR_INVALID, "null handle");
+        if (int rc = poly_refusal(A, "bsm_update_blocks")) return rc;
         if (is_mixed(A->an.dtype))
             return fail(BSM_ERR_UNSUPPORTED, "bsm_update_blocks: not available on a mixed-precision handle (BSM_F64_F32 / "
                                              "BSM_C128_C64); create a new handle from the new blocks");
@@ -770,6 +775,7 @@ static int copy_out(const std::vector<int64_t> &v, int64_t *out, int64_t *len) {
 
 extern "C" int bsm_get_bookkeeping(bsm_matrix_t A, int which, int64_t *out, int64_t *len) {
     if (!A) return fail(BSM_ERR_INVALID, "null handle");
+    if (int rc = poly_refusal(A, "bsm_get_bookkeeping")) return rc;
     const Analysis &an = A->an;
     switch (which) {
         case BSM_BK_VBCRS_PERM:
@@ -804,6 +810,7 @@ extern "C" int bsm_get_bookkeeping(bsm_matrix_t A, int which, int64_t *out, int6
 
 extern "C" int bsm_get_image(bsm_matrix_t A, int which, void *out, int64_t *nbytes) {
     if (!A || !nbytes) return fail(BSM_ERR_INVALID, "null argument");
+    if (int rc = poly_refusal(A, "bsm_get_image")) return rc;
     if (A->on_device || A->dist) return fail(BSM_ERR_UNSUPPORTED, "image dump needs an analysis-only handle");
     if (which >= 16 && !A->has_t) return fail(BSM_ERR_INVALID, "handle has no transposed image");
     const Analysis &an = (which >= 16) ? A->an_t : A->an;
@@ -834,7 +841,7 @@ extern "C" int bsm_get_image(bsm_matrix_t A, int which, void *out, int64_t *nbyt
 // to a fresh allocation -- which = 0 values, 1 rows, 2 cols, 3 wave records -- to find out which one a handle's
 // "placement level" depends on.
 extern "C" int bsm_debug_move_image_array(bsm_matrix_t A, int which) {
-    if (!A || !A->on_device || A->dist) return fail(BSM_ERR_INVALID, "needs a single-device handle");
+    if (!A || !A->on_device || A->dist || A->poly) return fail(BSM_ERR_INVALID, "needs a single-device handle");
     DeviceGuard guard;
     hipError_t e = guard.enter(A->img.device);
     if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
@@ -905,6 +912,7 @@ extern "C" int bsm_destroy(bsm_matrix_t A) {
         (void)guard.enter(A->device);
         if (A->stage_x) (void)hipFree(A->stage_x);
         if (A->stage_y) (void)hipFree(A->stage_y);
+        poly_release(A);  // a composed handle's workspace
     }
     A->release();
     delete A;

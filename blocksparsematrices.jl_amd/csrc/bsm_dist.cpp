@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "bsm_dist.h"
+#include "bsm_poly.h"
 
 namespace bsm {
 
@@ -95,7 +96,7 @@ void Workers::loop(int p, int dev) {
 
 }  // namespace bsm
 
-// (defined here: DistState must be complete where the handle's unique_ptr is destroyed)
+// (defined here: DistState and PolyState must be complete where the handle's unique_ptrs are destroyed)
 bsm_matrix_s::bsm_matrix_s() = default;
 bsm_matrix_s::~bsm_matrix_s() = default;
 

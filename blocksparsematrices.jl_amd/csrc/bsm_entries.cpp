@@ -64,6 +64,7 @@ extern "C" int bsm_rowcolvals(bsm_matrix_t A, int64_t *rows, int64_t *cols, void
                               int memspace, void *stream) {
     BSM_GUARDED(
         if (!A || !count) return fail(BSM_ERR_INVALID, "null argument");
+        if (int rc = poly_refusal(A, "bsm_rowcolvals")) return rc;
         if (!rows || !cols || !vals) {
             *count = A->an.nnz;
             return BSM_OK;
@@ -287,6 +288,7 @@ extern "C" int bsm_submatrices(bsm_matrix_t A, int op, int64_t nsets, const int6
                                void *stream) {
     BSM_GUARDED(
         if (!A) return fail(BSM_ERR_INVALID, "null handle");
+        if (int rc = poly_refusal(A, "bsm_submatrices")) return rc;
         if (op != BSM_OP_N && op != BSM_OP_T && op != BSM_OP_C) return fail(BSM_ERR_INVALID, "bad op");
         if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
         if (memspace == BSM_MEM_DEVICE && !A->on_device)
@@ -335,6 +337,7 @@ extern "C" int bsm_submatrices(bsm_matrix_t A, int op, int64_t nsets, const int6
 extern "C" int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream) {
     BSM_GUARDED(
         if (!A) return fail(BSM_ERR_INVALID, "null handle");
+        if (int rc = poly_refusal(A, "bsm_diag")) return rc;
         if (memspace != BSM_MEM_HOST && memspace != BSM_MEM_DEVICE) return fail(BSM_ERR_INVALID, "bad memspace");
         if (memspace == BSM_MEM_DEVICE && !A->on_device)
             return fail(BSM_ERR_INVALID, "a BSM_MEM_DEVICE result needs a device image (handle created with BSM_DEVICE_NONE)");

@@ -26,6 +26,7 @@ struct bsm_ctx_s {
 
 namespace bsm {
 struct DistState;  // bsm_dist.h
+struct PolyState;  // bsm_poly.h
 
 // bsm_update_blocks on one device: the device copy of the refill plans of its images (uploaded at the first update,
 // kept until the handle is destroyed) and the per-call table of source blocks (RefillSrc by input block id) with the
@@ -128,6 +129,8 @@ struct bsm_matrix_s : bsm::LocalOperator {
     size_t stage_x_bytes = 0, stage_y_bytes = 0;
     // handle spread over the devices of a context (bsm_options.ctx)
     std::unique_ptr<bsm::DistState> dist;
+    // composed handle (bsm_poly_create): a polynomial in other handles; it has no image, its product is poly_mul
+    std::unique_ptr<bsm::PolyState> poly;
     // bsm_update_blocks: stored shape of every input block (constructor order); one update at a time
     std::vector<int64_t> blk_m, blk_n;
     std::mutex upd_mu;
@@ -178,6 +181,15 @@ int dist_mul_multi(bsm_matrix_s *A, int op, long long nrhs, const void *X, long 
                    const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream);
 int dist_mul_parts(bsm_matrix_s *A, int op, const void *const *x_parts, void *const *y_parts, const void *alpha,
                    const void *beta, int beta_strong_zero, void *const *streams);
+
+// ---- bsm_poly.cpp: composed handles (bsm_poly_create) ------------------------------------------
+// the product behind the four product entry points (arguments as mul_entry of bsm_capi.cpp takes them)
+int poly_mul(bsm_matrix_s *M, int op, bool cplx, bool multi, int64_t nrhs, const void *X, int64_t ldx, void *Y, int64_t ldy,
+             const void *alpha, const void *beta, int beta_strong_zero, int memspace, hipStream_t stream);
+// BSM_OK, or the BSM_ERR_UNSUPPORTED of entry point `what`, which reads or writes entries, for a composed handle
+int poly_refusal(const bsm_matrix_s *A, const char *what);
+// frees the workspace of a composed handle (no-op on any other); its device must be current
+void poly_release(bsm_matrix_s *M);
 
 // ---- bsm_dist.cpp -------------------------------------------------------------------------------
 // Row partition of `in` (already in its final order) over the context's devices; fills A->dist.

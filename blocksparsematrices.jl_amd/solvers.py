@@ -9,7 +9,8 @@ import numpy as np
 from . import _lib as L
 from ._marshal import _BlockList, _DT, _TORCH_DT, _blocks_kind, _describe, _elt, _i64, _is_dev, _is_tensor, _like, _p64, _stream_ptr, torch
 from .entries import _out_device, submatrices
-from .matrices import BlockSparseMatrix, SymmetricBlockMatrix, _no_mixed_update, _operator, _unwrap, size, update_blocks
+from .matrices import (AbstractBlockMatrix, BlockSparseMatrix, SymmetricBlockMatrix, _no_mixed_update, _operator, _unwrap, mul, size,
+                       update_blocks)
 
 __all__ = ["invert_blocks", "BlockJacobi", "block_jacobi", "Gmres", "GmresInfo", "gmres", "krylov_orth", "krylov_orth_work", "Cg",
            "CgInfo", "cg", "cocg", "BiCgStab", "bicgstab", "GmresMulti"]
@@ -502,3 +503,174 @@ class GmresMulti(_LockstepSolver):
         X, info = super().solve(B, **kw)
         info.cycles = -(-int(info.iterations) // self.restart)
         return X, info
+
+
+# ---- polynomial preconditioners as handles (bsm_poly_*) ---------------------------------------------------------------------
+# (PolynomialPreconditioner, polynomial, chebyshev, neumann, chebyshev_coefficients and lanczos_bounds are exported by the
+# package by name, like Minres)
+def chebyshev_coefficients(lmin, lmax, steps):
+    """-> (a, b), float64 arrays of `steps` entries: the coefficients of bsm_poly_create's recurrence for the Chebyshev
+    polynomial of a spectrum inside [lmin, lmax] (Saad, Iterative Methods for Sparse Linear Systems, Alg. 12.1):
+    theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta, rho_0 = 1 / sigma, b_0 = 1 / theta,
+    rho_{k+1} = 1 / (2 sigma - rho_k), a_{k+1} = rho_{k+1} rho_k, b_{k+1} = 2 rho_{k+1} / delta; a_0 = 0 (ignored).  The residual
+    polynomial 1 - lambda p(lambda) is T_s((theta - lambda) / delta) / T_s(sigma).  Pure numpy; ValueError unless
+    0 < lmin < lmax and steps >= 1."""
+    lmin, lmax, steps = float(lmin), float(lmax), int(steps)
+    if not (0 < lmin < lmax and np.isfinite(lmax)) or steps < 1:
+        raise ValueError(f"chebyshev_coefficients needs 0 < lmin < lmax and steps >= 1, got ({lmin}, {lmax}, {steps})")
+    theta, delta = (lmax + lmin) / 2, (lmax - lmin) / 2
+    sigma = theta / delta
+    a, b = np.zeros(steps), np.zeros(steps)
+    rho = 1 / sigma
+    b[0] = 1 / theta
+    for k in range(1, steps):
+        nxt = 1 / (2 * sigma - rho)
+        a[k], b[k] = nxt * rho, 2 * nxt / delta
+        rho = nxt
+    return a, b
+
+
+class PolynomialPreconditioner(AbstractBlockMatrix):
+    """z = p(A) x as a handle of its own (bsm_poly_create): `steps` steps of the recurrence r_0 = x, d_0 = b_0 D r_0,
+    r_{k+1} = r_k - A d_k, d_{k+1} = a_{k+1} d_k + b_{k+1} D r_{k+1}, p(A) x = d_0 + .. + d_{steps-1}, with real coefficients
+    a, b over an operator A and an optional inner preconditioner D (None: the identity) -- steps - 1 multi-column products
+    with A and steps with D per product, the vector work between them in fused kernels.  Every solver takes it as M; mul,
+    M @ X, transpose(M) and adjoint(M) apply it to torch CUDA tensors of `dtype` (M @ X also to numpy arrays, staged through
+    torch).  It holds HANDLES: update_blocks(A, ...) and D.refresh() are seen by the next product.  One product at a time.
+    It has no entries: M[I, J], diag, rowcolvals, update_blocks and value_passes raise BsmError.  Built by polynomial(),
+    chebyshev() and neumann().  Fields beside AbstractBlockMatrix's: source (A), inner (D), steps, a, b, nrhs."""
+
+    def __init__(self, A, a, b, D=None, nrhs=16, dtype=None):
+        base, op = _operator(A)
+        dbase, dop = (None, L.BSM_OP_N) if D is None else _operator(D, "D")
+        a, b = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (a, b))
+        if len(a) != len(b) or not 1 <= len(b) <= L.BSM_POLY_MAX_STEPS:
+            raise ValueError(f"a and b must have the same length, 1 .. {L.BSM_POLY_MAX_STEPS} steps; got {len(a)} and {len(b)}")
+        if not (np.all(np.isfinite(b)) and np.all(np.isfinite(a[1:]))):
+            raise ValueError("the coefficients must be finite")
+        dt = np.dtype(base.dtype if dtype is None else dtype)
+        if dt not in _DT:
+            raise TypeError(f"dtype={dt} is not a supported vector type")
+        m, n = size(A)
+        if m != n:
+            raise ValueError(f"a polynomial preconditioner needs a square operator, size(A) = {(m, n)}")
+        dp = C.POINTER(C.c_double)
+        h = C.c_void_p()
+        L.check(L.lib().bsm_poly_create(base._h.ptr, op, None if dbase is None else dbase._h.ptr, dop, _DT[dt], int(nrhs), len(b),
+                                        a.ctypes.data_as(dp), b.ctypes.data_as(dp), C.byref(h)))
+        self._finish(h, dt, (n, n), base.scheduler, base.device)
+        self.source, self.inner, self.steps, self.a, self.b, self.nrhs = A, D, len(b), a, b, int(nrhs)
+
+    def _src(self):
+        """update_blocks / refresh: what the library answers for a composed handle"""
+        L.check(L.lib().bsm_update_blocks(self._h.ptr, 0, None, None, None, L.BSM_MEM_HOST, None))
+        raise L.BsmError("a polynomial preconditioner has no blocks")
+
+    def info(self):
+        """-> (steps, a, b, workspace bytes) as the library holds them (bsm_poly_info)"""
+        steps, ws = C.c_int32(0), C.c_int64(0)
+        a, b = np.zeros(L.BSM_POLY_MAX_STEPS), np.zeros(L.BSM_POLY_MAX_STEPS)
+        dp = C.POINTER(C.c_double)
+        L.check(L.lib().bsm_poly_info(self._h.ptr, C.byref(steps), a.ctypes.data_as(dp), b.ctypes.data_as(dp), C.byref(ws)))
+        return steps.value, a[:steps.value], b[:steps.value], ws.value
+
+    def __matmul__(self, x):
+        """M @ X.  The library's product takes device vectors only: numpy operands are staged through torch (synchronous)"""
+        if _is_tensor(x):
+            return super().__matmul__(x)
+        x = np.asarray(x, dtype=self.dtype)
+        dev = torch.device("cuda", self.device)
+        xd = torch.from_numpy(np.ascontiguousarray(x.T)).to(dev).t() if x.ndim == 2 else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        y = super().__matmul__(xd).cpu().numpy()
+        return np.asfortranarray(y) if y.ndim == 2 else y
+
+    __mul__ = __matmul__
+
+
+def polynomial(A, a, b, D=None, nrhs=16, dtype=None):
+    """The polynomial preconditioner of A with the coefficient arrays a, b of bsm_poly_create's recurrence (a[0] is ignored)
+    over the inner preconditioner D (a block matrix of A's order, e.g. block_jacobi(A, sets), or None) -> PolynomialPreconditioner.
+    A, D: block matrices or transpose / adjoint wrappers, single-device, with a device image; nrhs: the columns one pass of
+    the recurrence takes (1 .. 16; wider operands run in batches); dtype: the type of the vectors -- default A's vector type;
+    a real A (and D) of the same precision serves a complex dtype.  The workspace (4 n x nrhs matrices, 5 with D) is
+    allocated here, once; A and D are kept alive."""
+    return PolynomialPreconditioner(A, a, b, D, nrhs, dtype)
+
+
+def chebyshev(A, lmin, lmax, steps, D=None, nrhs=16, dtype=None):
+    """The Chebyshev polynomial preconditioner of `steps` steps for a spectrum of D A inside [lmin, lmax]
+    (chebyshev_coefficients) -> PolynomialPreconditioner.  For symmetric / Hermitian positive definite A and D, with bounds
+    from lanczos_bounds: lo, hi = lanczos_bounds(A, D); M = chebyshev(A, 0.95 * lo, 1.05 * hi, steps, D).  steps = 1 is
+    D / theta."""
+    return PolynomialPreconditioner(A, *chebyshev_coefficients(lmin, lmax, steps), D, nrhs, dtype)
+
+
+def neumann(A, omega, steps, D=None, nrhs=16, dtype=None):
+    """The Neumann (Richardson) polynomial preconditioner omega sum_{k < steps} (I - omega D A)^k D -> PolynomialPreconditioner:
+    a_k = 0, b_k = omega.  It approaches inv(A) as steps grows iff rho(I - omega D A) < 1; A need not be symmetric."""
+    steps, omega = int(steps), float(omega)
+    if steps < 1 or not np.isfinite(omega):
+        raise ValueError(f"neumann needs steps >= 1 and a finite omega, got ({omega}, {steps})")
+    return PolynomialPreconditioner(A, np.zeros(steps), np.full(steps, omega), D, nrhs, dtype)
+
+
+def _lanczos_ritz(apply_a, apply_d, v0, steps, xp):
+    """The core of lanczos_bounds on any array module xp with vdot (numpy, torch): `steps` preconditioned-CG recurrences on
+    A x = v0 with the preconditioner D -> (smallest, largest) eigenvalue of their tridiagonal matrix, the extreme Ritz values
+    of D A.  apply_a(v), apply_d(v): A v and D v as new arrays.  It stops early when the Krylov space ends."""
+    def dot(u, v):
+        return float(xp.vdot(u, v).real)
+    r = v0
+    z = apply_d(r)
+    p = z
+    rz = dot(r, z)
+    if not rz > 0:
+        raise ValueError("lanczos_bounds: <v0, D v0> must be positive (D positive definite, v0 not zero)")
+    rz0 = rz
+    diag, off = [], []
+    alpha_prev = beta_prev = None
+    for j in range(int(steps)):
+        q = apply_a(p)
+        pq = dot(p, q)
+        if not pq > 0:
+            break
+        alpha = rz / pq
+        diag.append(1 / alpha + (beta_prev / alpha_prev if j else 0.0))
+        r = r - alpha * q
+        z = apply_d(r)
+        rzn = dot(r, z)
+        if j + 1 == int(steps) or not rzn > 1e-28 * rz0:
+            break
+        beta = rzn / rz
+        off.append(beta ** 0.5 / alpha)
+        p = z + beta * p
+        rz, alpha_prev, beta_prev = rzn, alpha, beta
+    if not diag:
+        raise ValueError("lanczos_bounds: <p, A p> must be positive (A positive definite)")
+    k = len(diag)
+    T = np.diag(diag) + np.diag(off[:k - 1], 1) + np.diag(off[:k - 1], -1)
+    ev = np.linalg.eigvalsh(T)
+    return float(ev[0]), float(ev[-1])
+
+
+def lanczos_bounds(A, D=None, steps=20, v0=None, seed=0):
+    """-> (lo, hi): the extreme Ritz values of D A for a symmetric / Hermitian positive definite A and D (None: the
+    identity), from the tridiagonal matrix of `steps` preconditioned-CG recurrences started at v0 (default: uniform in
+    (-1, 1) from numpy's default_rng(seed)).  Set-up code: bsm.mul on torch CUDA vectors plus torch reductions, synchronous.
+    Ritz values lie INSIDE the spectrum, lo >= lambda_min and hi <= lambda_max, so widen them before use:
+    chebyshev(A, 0.95 * lo, 1.05 * hi, steps, D) is the idiom."""
+    base, _ = _operator(A)
+    if D is not None:
+        _operator(D, "D")
+    n = size(A)[0]
+    dt = np.dtype(base.dtype)
+    if base.device is None:
+        raise ValueError("lanczos_bounds needs a single-device operator with a device image")
+    dev = torch.device("cuda", base.device)
+    if v0 is None:
+        v0 = np.random.default_rng(seed).uniform(-1, 1, n).astype(dt)
+    v = v0 if _is_tensor(v0) else torch.from_numpy(np.ascontiguousarray(np.asarray(v0, dtype=dt))).to(dev)
+
+    def times(H):
+        return lambda x: mul(torch.empty_like(x), H, x)
+    return _lanczos_ritz(times(A), (lambda x: x) if D is None else times(D), v, steps, torch)

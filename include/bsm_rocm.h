@@ -993,6 +993,55 @@ int bsm_lsqr_solve(struct bsm_lsqr_s *S, int32_t nrhs, const void *B, int64_t ld
                    double *anorm /* nrhs, may be NULL */, int memspace, void *stream);
 int bsm_lsqr_destroy(struct bsm_lsqr_s *S);
 
+/* bsm_poly_*: a POLYNOMIAL PRECONDITIONER as a handle.  bsm_poly_create returns a bsm_matrix_t whose product is z = p(A) x,
+ * a fixed polynomial in an operator handle A and an optional inner preconditioner handle D (e.g. the block-Jacobi handle
+ * of A; NULL: the identity).  Because it is a bsm_matrix_t, bsm_mul and bsm_mul_multi apply it and every bsm_*_create above
+ * takes it as (M, opM): a solver trades outer iterations -- where its dot products, Gram-Schmidt passes and decisions are
+ * paid -- for multi-column products, the matrix streamed once for up to BSM_CG_MAX_RHS columns.
+ * (No counterpart in the reference: its operators are LinearMaps handed to a Julia solver package.)
+ *   The recurrence, with REAL coefficients a[0 .. steps), b[0 .. steps) (a[0] is ignored), on the operand x:
+ *     r_0 = x;  d_0 = b_0 D r_0
+ *     k = 0 .. steps - 2:   r_{k+1} = r_k - A d_k;   d_{k+1} = a_{k+1} d_k + b_{k+1} D r_{k+1}
+ *     p(A) x = d_0 + d_1 + .. + d_{steps-1};   y = alpha p(A) x + beta y   (beta_strong_zero as in bsm_mul)
+ *   steps - 1 products with A and steps with D per product of the composed handle.  The host computes the coefficients; two
+ *   families matter.  Chebyshev for a spectrum of D A inside [lmin, lmax], 0 < lmin < lmax (Saad, Iterative Methods for
+ *   Sparse Linear Systems, Alg. 12.1):  theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta,
+ *   rho_0 = 1 / sigma, b_0 = 1 / theta;  rho_{k+1} = 1 / (2 sigma - rho_k), a_{k+1} = rho_{k+1} rho_k, b_{k+1} = 2 rho_{k+1} /
+ *   delta.  Neumann / Richardson: a_k = 0, b_k = omega, which converges as steps grows iff rho(I - omega D A) < 1.
+ *   op: BSM_OP_T / BSM_OP_C on the composed handle run the same recurrence with op composed onto opA and opD -- right because
+ *   the coefficients are real.  A composition that needs conj(A) or conj(D) of a COMPLEX handle (BSM_OP_T onto BSM_OP_C or
+ *   the reverse) is BSM_ERR_UNSUPPORTED, as in bsm_lsqr_create.
+ * create: vdtype is the type of the vectors the composed handle takes; the (handle, vector) pairings of A and D are those
+ *   of bsm_cg_create (a real handle serves a complex vdtype of its precision, a mixed-storage one its vector type).  ONE
+ *   device allocation on A's device (bsm_poly_info, bsm_stats.device_bytes): R, d, acc, Q (and T = D R with D) as
+ *   column-major matrices of nrhs_max columns, the leading dimension rounded up to whole 16-byte groups, the padding zero.
+ *   Refused, before anything is allocated and in this order: null A / out, a bad op, a vdtype that is no vector type;
+ *   steps outside 1 .. BSM_POLY_MAX_STEPS, null a / b, a coefficient that is not finite; nrhs_max outside 1 ..
+ *   BSM_CG_MAX_RHS; op(A) not square, D of another order; a pairing bsm_cg_create refuses (all BSM_ERR_INVALID); a
+ *   multi-device handle (BSM_ERR_UNSUPPORTED), an analysis-only handle (BSM_ERR_DEVICE), a handle that owns a row range only
+ *   (BSM_ERR_UNSUPPORTED), A and D on different devices (BSM_ERR_INVALID); a composed handle as A or D (BSM_ERR_UNSUPPORTED).
+ *   A and D must outlive the composed handle, which bsm_destroy frees.  It holds HANDLES, not values: the next product sees
+ *   a bsm_update_blocks of A or D.
+ * product: bsm_mul / bsm_mul_multi with vectors of vdtype in device memory; any ldx, ldy >= max(n, 1), any element
+ *   alignment; X is read and n rows of nrhs columns of Y are written element by element, nothing else is touched.  nrhs >
+ *   nrhs_max runs in batches of nrhs_max columns.  After create a product allocates nothing and synchronises nothing: it
+ *   only enqueues on the caller's stream.  Refused: the _cvec entries (BSM_ERR_UNSUPPORTED: to precondition complex vectors
+ *   over real handles, create with a complex vdtype), BSM_MEM_HOST (BSM_ERR_UNSUPPORTED), a stream that is being captured
+ *   (BSM_ERR_UNSUPPORTED).  ONE product may be in flight per composed handle -- it has one workspace; products on other
+ *   streams or threads are the caller's to order, as for bsm_update_blocks.  Run to run the result is bit-identical
+ *   wherever the products of A and D are (the kernels between them, csrc/bsm_poly.hip, have no reduction).
+ * every other entry point that takes a bsm_matrix_t -- bsm_rowcolvals, bsm_submatrices, bsm_diag, bsm_update_blocks,
+ *   bsm_value_passes, bsm_get_bookkeeping, bsm_get_image, bsm_part_info, bsm_mul_parts -- answers BSM_ERR_UNSUPPORTED for a
+ *   composed handle; bsm_stats reports nnz = 0 and the workspace as device_bytes.
+ * bsm_poly_info: steps, the coefficients as held (a, b: capacity BSM_POLY_MAX_STEPS, may be NULL) and the bytes of the
+ *   workspace; BSM_ERR_INVALID for a handle that is not a composed one. */
+#define BSM_POLY_MAX_STEPS 64
+int bsm_poly_create(bsm_matrix_t A, int opA, bsm_matrix_t D /* may be NULL */, int opD, int vdtype,
+                    int32_t nrhs_max /* 1 .. BSM_CG_MAX_RHS */, int32_t steps, const double *a, const double *b,
+                    bsm_matrix_t *out);
+int bsm_poly_info(bsm_matrix_t M, int32_t *steps, double *a, double *b /* capacity BSM_POLY_MAX_STEPS, may be NULL */,
+                  int64_t *workspace_bytes);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

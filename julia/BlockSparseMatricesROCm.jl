@@ -822,4 +822,86 @@ function lsqr!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; rtol::Real=1e-8, at
     return X, info, columns, history[:, 1:min(info.iterations, maxiter)], normal_residual, anorm
 end
 
+# ---- polynomial preconditioners as handles (bsm_poly_*) -----------------------------------------------------------------
+"""
+    PolynomialPreconditioner
+
+`z = p(A) x` as a handle of its own (bsm_poly_create): `steps` steps of the recurrence `r_0 = x`, `d_0 = b_0 D r_0`,
+`r_{k+1} = r_k - A d_k`, `d_{k+1} = a_{k+1} d_k + b_{k+1} D r_{k+1}`, `p(A) x = d_0 + ... + d_{steps-1}` with real
+coefficients over an operator `A` and an optional inner preconditioner `D` (`nothing`: the identity).  Pass it as `M` to
+`cg!`, `minres!`, `bicgstab!` and `gmres!`; it keeps `A` and `D` alive.  Its own product takes device vectors only, so
+`mul!` with host arrays is not offered for it.  Built by `chebyshev_preconditioner` and `neumann_preconditioner`.
+(The reference offers nothing here: a `LinearMap` is handed to a Julia solver package.)
+"""
+struct PolynomialPreconditioner
+    handle::Handle
+    source::Any
+    inner::Any
+    a::Vector{Float64}
+    b::Vector{Float64}
+end
+handle(P::PolynomialPreconditioner) = P.handle
+_base(P::PolynomialPreconditioner) = P
+_op(::PolynomialPreconditioner) = 0
+Base.size(P::PolynomialPreconditioner) = size(P.source)
+
+function _polynomial(A::ROCmAnyOp, D, a::Vector{Float64}, b::Vector{Float64}, nrhs::Integer, ::Type{T}) where {T<:ROCmEltype}
+    length(a) == length(b) && 1 <= length(b) <= 64 || throw(ArgumentError("a and b must have the same length, 1 to 64 steps"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    dptr = D === nothing ? C_NULL : handle(_base(D)).ptr
+    GC.@preserve A D a b _check(ccall((:bsm_poly_create, libbsm), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), dptr, D === nothing ? 0 : _op(D), _DTYPE[T], nrhs, length(b), a, b, out))
+    return PolynomialPreconditioner(Handle(out[]), A, D, a, b)
+end
+
+"""
+    polynomial_info(P) -> (steps, a, b, workspace_bytes)
+
+What the library holds of a `PolynomialPreconditioner` (bsm_poly_info).
+"""
+function polynomial_info(P::PolynomialPreconditioner)
+    steps, ws = Ref{Int32}(0), Ref{Int64}(0)
+    a, b = zeros(Float64, 64), zeros(Float64, 64)
+    _check(ccall((:bsm_poly_info, libbsm), Cint, (Ptr{Cvoid}, Ref{Int32}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+        P.handle.ptr, steps, a, b, ws))
+    return Int(steps[]), a[1:steps[]], b[1:steps[]], ws[]
+end
+
+"""
+    chebyshev_preconditioner(A, lmin, lmax, steps; D=nothing, nrhs=16, eltype=eltype(A))
+
+The Chebyshev polynomial preconditioner of `steps` steps for a spectrum of `D A` inside `[lmin, lmax]`, `0 < lmin < lmax`
+(Saad, Iterative Methods for Sparse Linear Systems, Alg. 12.1): `theta = (lmax + lmin) / 2`, `delta = (lmax - lmin) / 2`,
+`sigma = theta / delta`, `rho_0 = 1 / sigma`, `b_0 = 1 / theta`, `rho_{k+1} = 1 / (2 sigma - rho_k)`,
+`a_{k+1} = rho_{k+1} rho_k`, `b_{k+1} = 2 rho_{k+1} / delta`.  For symmetric / Hermitian positive definite `A` and `D`
+(e.g. `block_jacobi(A, sets)`); `steps = 1` is `D / theta`.  Ritz values lie inside the spectrum: widen bounds taken from
+a Lanczos run before use.
+"""
+function chebyshev_preconditioner(A::ROCmAnyOp, lmin::Real, lmax::Real, steps::Integer; D=nothing, nrhs::Integer=16, eltype::Type=Base.eltype(A))
+    0 < lmin < lmax && isfinite(lmax) && steps >= 1 || throw(ArgumentError("chebyshev_preconditioner needs 0 < lmin < lmax and steps >= 1"))
+    theta, delta = (Float64(lmax) + Float64(lmin)) / 2, (Float64(lmax) - Float64(lmin)) / 2
+    sigma = theta / delta
+    a, b = zeros(Float64, steps), zeros(Float64, steps)
+    rho = 1 / sigma
+    b[1] = 1 / theta
+    for k in 2:steps
+        nxt = 1 / (2 * sigma - rho)
+        a[k], b[k] = nxt * rho, 2 * nxt / delta
+        rho = nxt
+    end
+    return _polynomial(A, D, a, b, nrhs, eltype)
+end
+
+"""
+    neumann_preconditioner(A, omega, steps; D=nothing, nrhs=16, eltype=eltype(A))
+
+The Neumann (Richardson) polynomial preconditioner `omega sum_{k < steps} (I - omega D A)^k D`: `a_k = 0`, `b_k = omega`.
+It approaches `inv(A)` as `steps` grows iff `rho(I - omega D A) < 1`; `A` need not be symmetric.
+"""
+function neumann_preconditioner(A::ROCmAnyOp, omega::Real, steps::Integer; D=nothing, nrhs::Integer=16, eltype::Type=Base.eltype(A))
+    steps >= 1 && isfinite(omega) || throw(ArgumentError("neumann_preconditioner needs steps >= 1 and a finite omega"))
+    return _polynomial(A, D, zeros(Float64, steps), fill(Float64(omega), steps), nrhs, eltype)
+end
+
 end # module
