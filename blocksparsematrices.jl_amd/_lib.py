@@ -24,6 +24,7 @@ BSM_GMRES_MAX_RESTART = 128  # bsm_gmres_create's restart, bsm_krylov_orth's k (
 BSM_CG_MAX_RHS = 16  # bsm_cg_create's nrhs_max (include/bsm_rocm.h)
 BSM_CG_METHOD_CG, BSM_CG_METHOD_COCG = 0, 1
 BSM_POLY_MAX_STEPS = 64  # bsm_poly_create's steps (include/bsm_rocm.h)
+BSM_EIGSH_LA, BSM_EIGSH_SA, BSM_EIGSH_BE, BSM_EIGSH_LM = 0, 1, 2, 3  # bsm_eigsh_params.which (include/bsm_rocm.h)
 (BSM_BK_VBCRS_PERM, BSM_BK_VBCRS_ROWPTR, BSM_BK_VBCRS_COLINDICES, BSM_BK_VBCRS_ROWINDICES,
  BSM_BK_COLORS, BSM_BK_TRANSPOSECOLORS, BSM_BK_DIAGONALCOLORS) = range(7)
 
@@ -80,6 +81,20 @@ class BsmCgColumn(C.Structure):
                 ("bnorm", C.c_double)]
 
 
+class BsmEigshParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("maxcycles", C.c_int32), ("vectors", C.c_int32)]
+
+
+class BsmEigshInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("nconv", C.c_int32), ("cycles", C.c_int32), ("reserved", C.c_int32),
+                ("a_products", C.c_int64), ("anorm", C.c_double), ("workspace_bytes", C.c_int64), ("workspace", C.c_uint64)]
+
+
+class BsmEigshPair(C.Structure):
+    _fields_ = [("value", C.c_double), ("estimate", C.c_double), ("residual", C.c_double)]
+
+
 class BsmError(RuntimeError):
     pass
 
@@ -102,7 +117,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_gmres_destroy", "bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy", "bsm_bicgstab_create", "bsm_bicgstab_solve",
            "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy",
            "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy", "bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy",
-           "bsm_poly_create", "bsm_poly_info"]
+           "bsm_poly_create", "bsm_poly_info", "bsm_krylov_combine_tile", "bsm_krylov_combine", "bsm_eigsh_create",
+           "bsm_eigsh_solve", "bsm_eigsh_destroy"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -255,6 +271,17 @@ def lib():
                                       C.POINTER(C.c_void_p)]
         L.bsm_poly_info.argtypes = [C.c_void_p, _I32P, _F64P, _F64P, _I64P]
         L.bsm_poly_create.restype = L.bsm_poly_info.restype = C.c_int
+    if hasattr(L, "bsm_eigsh_create") or "BSM_LIB" not in os.environ:  # (developer A/B builds may predate them)
+        L.bsm_krylov_combine_tile.argtypes = [C.c_int, C.c_int64]
+        L.bsm_krylov_combine_tile.restype = C.c_int64
+        L.bsm_krylov_combine.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.bsm_eigsh_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bsm_eigsh_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(BsmEigshParams), C.POINTER(BsmEigshInfo),
+                                      C.POINTER(BsmEigshPair), C.c_int, C.c_void_p]
+        L.bsm_eigsh_destroy.argtypes = [C.c_void_p]
+        for name in ("bsm_krylov_combine", "bsm_eigsh_create", "bsm_eigsh_solve", "bsm_eigsh_destroy"):
+            getattr(L, name).restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p
     L.bsm_version.restype = C.c_char_p

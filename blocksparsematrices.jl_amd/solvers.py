@@ -674,3 +674,143 @@ def lanczos_bounds(A, D=None, steps=20, v0=None, seed=0):
     def times(H):
         return lambda x: mul(torch.empty_like(x), H, x)
     return _lanczos_ritz(times(A), (lambda x: x) if D is None else times(D), v, steps, torch)
+
+
+# ---- extreme eigenpairs of symmetric / Hermitian operators on the device (bsm_eigsh_*) and its building block ---------------
+# (Eigsh, EigshInfo, eigsh and krylov_combine are exported by the package by name, like Minres)
+_EIGSH_WHICH = {"LA": L.BSM_EIGSH_LA, "SA": L.BSM_EIGSH_SA, "BE": L.BSM_EIGSH_BE, "LM": L.BSM_EIGSH_LM}
+
+
+def krylov_combine_tile(dtype, m):
+    """Rows (elements of `dtype`) of the tile one workgroup of krylov_combine stages for m columns (bsm_krylov_combine_tile)."""
+    return int(L.lib().bsm_krylov_combine_tile(_DT[np.dtype(dtype)], int(m)))
+
+
+def krylov_combine(V, S, out=None, carry=None, stream=None):
+    """out[:, c] = sum_j V[:, j] S[j, c] on the device (bsm_krylov_combine), the sum over j ascending with one fma per term;
+    with carry (a column index of V, 0 .. m) out[:, k] = V[:, carry] too.  V: column-major torch CUDA tensor (n x >= max(m,
+    carry + 1)); S: column-major m x k tensor of the REAL type of V's precision (m <= 128, k <= m); out: column-major, n x
+    (k, or k + 1 with a carry), of V's type -- None: IN PLACE, the leading columns of V are overwritten and V[:, :k (+ 1)] is
+    returned.  out must not overlap V otherwise, and S must not overlap out.  Enqueued on `stream` (default: torch's current stream); nothing is
+    synchronised."""
+    if torch is None or not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (V, S) + (() if out is None else (out,))):
+        raise TypeError("krylov_combine takes torch CUDA tensors")
+    dt = _TORCH_DT.get(V.dtype)
+    if dt is None or V.dim() != 2 or S.dim() != 2:
+        raise TypeError("V must be a matrix of a supported element type and S a matrix")
+    if _TORCH_DT.get(S.dtype) != np.dtype(np.zeros(1, dt).real.dtype):
+        raise TypeError(f"S must have the real type of the precision of {dt}")
+    n, (m, k) = V.shape[0], S.shape
+    c = -1 if carry is None else int(carry)
+    cols = k + (1 if c >= 0 else 0)
+    if not (1 <= m <= L.BSM_GMRES_MAX_RESTART and k <= m and -1 <= c <= m and V.shape[1] >= max(m, c + 1)):
+        raise ValueError(f"S is {m} x {k}, carry = {carry}: m must be 1 .. {L.BSM_GMRES_MAX_RESTART}, k <= m, carry in 0 .. m, and V hold "
+                         "the columns they name")
+    if out is None:
+        out = V[:, :cols]
+    if out.dtype != V.dtype or out.dim() != 2 or tuple(out.shape) != (n, cols) or out.device != V.device or S.device != V.device:
+        raise ValueError(f"out must be a {n} x {cols} matrix of V's type on V's device, S live there too")
+    for t, name in ((V, "V"), (S, "S"), (out, "out")):
+        if t.shape[0] > 1 and t.stride(0) != 1:
+            raise TypeError(f"{name} must be column-major (e.g. torch.empty(cols, ld).t()[:n])")
+
+    def ld(t):
+        return t.stride(1) if t.shape[1] > 1 else max(t.shape[0], 1)
+    L.check(L.lib().bsm_krylov_combine(_DT[dt], n, m, k, V.data_ptr(), ld(V), S.data_ptr(), ld(S), out.data_ptr(),
+                                       ld(V) if out.data_ptr() == V.data_ptr() and out.shape[1] <= 1 else ld(out), c,
+                                       _stream_ptr(stream, V.device)))
+    return out
+
+
+class EigshInfo:
+    """What a solve reports (bsm_eigsh_info and the bsm_eigsh_pair entries): status (0 converged, 1 maxcycles reached, 2 a
+    non-finite norm or Ritz value, 3 the Krylov space ended before nev pairs existed), nconv, cycles, a_products (Lanczos
+    steps + residual columns), anorm (the largest |Ritz value| seen: a lower bound of ||A||_2), workspace_bytes, workspace;
+    per pair, as numpy arrays of nconv entries: value, estimate (|beta_m S[m - 1, i]|), residual (the true
+    ||A x - theta x||; the estimate with vectors=False)."""
+
+    def __init__(self, info, pairs):
+        for name, _ in L.BsmEigshInfo._fields_:
+            if name != "reserved":
+                setattr(self, name, getattr(info, name))
+        k = self.nconv
+        self.value = np.array([pairs[i].value for i in range(k)], dtype=np.float64)
+        self.estimate = np.array([pairs[i].estimate for i in range(k)], dtype=np.float64)
+        self.residual = np.array([pairs[i].residual for i in range(k)], dtype=np.float64)
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"EigshInfo(status={self.status}, nconv={self.nconv}, cycles={self.cycles}, a_products={self.a_products}, "
+                f"anorm={self.anorm:.3e})")
+
+
+class Eigsh:
+    """`nev` extreme eigenpairs of a real symmetric / complex Hermitian A by thick-restart Lanczos (the Hermitian
+    Krylov-Schur method), the basis, the products, the orthogonalisation and the restart on the device (bsm_eigsh_*).  The
+    CALLER asserts the symmetry.  A: a block matrix or transpose(A) / adjoint(A), single-device with a device image.  which:
+    "LA" (largest algebraic), "SA" (smallest), "BE" (both ends: ceil(nev / 2) from the top, the rest from the bottom), "LM"
+    (largest magnitude).  ncv: columns of the basis, nev + 2 .. min(n, 128); default min(n, 128, max(2 nev + 1, 20)).  dtype: A's
+    own vector type (a mixed-storage A solves in double).  The workspace (ncv + 1 + min(nev, 16) vectors) is allocated here,
+    once; A is kept alive and update_blocks(A, ...) is seen by the next solve.  Not in it: interior eigenvalues,
+    shift-invert, the generalised problem, preconditioning, multiplicities, singular values, block methods."""
+
+    def __init__(self, A, nev=6, ncv=None, which="LA", dtype=None):
+        base, op = _operator(A)
+        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
+        if self.dtype not in _DT:
+            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        if which not in _EIGSH_WHICH:
+            raise ValueError(f"which={which!r}: 'LA', 'SA', 'BE' or 'LM'")
+        m, n = size(A)
+        self.nev = int(nev)
+        self.ncv = min(n, L.BSM_GMRES_MAX_RESTART, max(2 * self.nev + 1, 20)) if ncv is None else int(ncv)
+        self.which, self.A, self.n, self._base = which, A, n, base
+        ptr = C.c_void_p()
+        L.check(L.lib().bsm_eigsh_create(base._h.ptr, op, _DT[self.dtype], self.nev, self.ncv, C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                L.lib().bsm_eigsh_destroy(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def solve(self, v0=None, rtol=1e-10, atol=0.0, maxcycles=300, vectors=True, stream=None, seed=0, *, X=None):
+        """-> (w, X, EigshInfo).  v0: the start vector, n entries -- torch CUDA tensor (the solve is enqueued on `stream`,
+        default torch's current stream) or numpy array (staged); None: uniform in (-1, 1) from numpy's default_rng(seed), on
+        A's device.  X: where the Ritz vectors go (n x nev, column-major, like v0; None: new); with vectors=False it is not
+        touched and (w, None, info) comes back.  w: the info.nconv eigenvalues in the order of `which` (numpy); X[:, :nconv]
+        their vectors, orthonormal.  Converged when every wanted pair's estimate is <= max(rtol * anorm, atol).  Synchronous."""
+        if v0 is None:
+            v0 = np.random.default_rng(seed).uniform(-1, 1, self.n)
+            if self.dtype.kind == "c":
+                v0 = v0 + 0j
+            v0 = torch.from_numpy(v0.astype(self.dtype)).to(torch.device("cuda", self._base.device))
+        vp, _, _, ms, _, _ = _describe(v0, self.dtype, self.n, "v0", self._base)
+        xp, ldx = None, max(self.n, 1)
+        if vectors:
+            if X is None:
+                X = _like(v0, self.n, self.nev)
+            xp, ldx, k, xms, _, _ = _describe(X, self.dtype, self.n, "X", self._base, True)
+            if k != self.nev:
+                raise ValueError(f"DimensionMismatch: X has {k} columns, expected nev = {self.nev}")
+            if xms != ms:
+                raise ValueError("v0 and X must live in the same memory space")
+        st = _stream_ptr(stream, v0.device) if ms == L.BSM_MEM_DEVICE else None
+        p = L.BsmEigshParams(C.sizeof(L.BsmEigshParams), _EIGSH_WHICH[self.which], float(rtol), float(atol), int(maxcycles),
+                             1 if vectors else 0)
+        info = L.BsmEigshInfo()
+        pairs = (L.BsmEigshPair * self.nev)()
+        L.check(L.lib().bsm_eigsh_solve(self._ptr, vp, xp, ldx, C.byref(p), C.byref(info), pairs, ms, st))
+        out = EigshInfo(info, pairs)
+        return out.value.copy(), (X if vectors else None), out
+
+
+def eigsh(A, nev=6, ncv=None, which="LA", dtype=None, **kw):
+    """One-shot form: Eigsh(A, nev, ncv, which, dtype).solve(**kw) -> (w, X, EigshInfo)."""
+    return Eigsh(A, nev=nev, ncv=ncv, which=which, dtype=dtype).solve(**kw)

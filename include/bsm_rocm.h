@@ -1042,6 +1042,109 @@ int bsm_poly_create(bsm_matrix_t A, int opA, bsm_matrix_t D /* may be NULL */, i
 int bsm_poly_info(bsm_matrix_t M, int32_t *steps, double *a, double *b /* capacity BSM_POLY_MAX_STEPS, may be NULL */,
                   int64_t *workspace_bytes);
 
+/* bsm_krylov_combine: the compression of a tall basis by a small REAL matrix, beside bsm_krylov_orth the second building
+ * block of a caller's Krylov method -- the thick restart of a Lanczos run, and the way Ritz vectors leave it:
+ *     Out[:, c] = sum_{j < m} V[:, j] S[j, c]   for c < k;      carry >= 0:  Out[:, k] = V[:, carry]
+ * V: n x >= max(m, carry + 1), Out: n x (k, or k + 1 with a carry), column-major device matrices of dtype (BSM_F32 ..
+ * BSM_C128), ldv, ldo >= max(n, 1), ANY element alignment.  S: m x k, column-major with lds >= m, in device memory, of the REAL
+ * type of dtype (float for BSM_F32 / BSM_C64, double for BSM_F64 / BSM_C128): the projected matrix of a Hermitian operator is
+ * real symmetric, so its eigenvectors are real, and a complex column of n entries is walked as 2 n reals.
+ * The sum runs over j ascending with one fused multiply-add per term, in the precision of dtype: the result is fixed to the
+ * bit, run to run and whatever the launch geometry.  Out == V with ldo == ldv works IN PLACE (a row of the output depends on
+ * the same row of V only): a workgroup stages a tile of rows x m in LDS, V is read once, nothing is allocated, and m + 1
+ * columns serve a whole restarted solve.  bsm_krylov_combine_tile(dtype, m): the rows (elements) of that tile -- as many
+ * whole waves of real rows as fit into 128 KiB of LDS beside each other, at most 1024 reals:
+ * min(1024, floor(131072 / (m * sizeof(real)) / 64) * 64) reals, half as many complex elements.
+ * The call only enqueues on `stream`; it synchronises nothing and may be graph-captured.
+ * Refused (BSM_ERR_INVALID): a dtype that is no vector type; n < 0; m outside 1 .. BSM_GMRES_MAX_RESTART; k outside 0 .. m;
+ * carry outside -1 .. m; ldv or ldo < max(n, 1); lds < m; a null pointer that is needed (S with k > 0; V, Out with n > 0);
+ * Out overlapping V in any way other than Out == V with ldo == ldv; S overlapping Out (in place: V).  k == 0 with a carry
+ * moves one column; n == 0 is legal. */
+int64_t bsm_krylov_combine_tile(int dtype, int64_t m);
+int bsm_krylov_combine(int dtype, int64_t n, int64_t m, int64_t k, const void *V, int64_t ldv, const void *S, int64_t lds, void *Out,
+                       int64_t ldo, int64_t carry, void *stream);
+
+/* bsm_eigsh_*: `nev` EXTREME EIGENPAIRS of op(A) for an A the caller asserts to be real symmetric / complex Hermitian (nothing
+ * checks that, as for bsm_cg), by thick-restart Lanczos -- the Hermitian Krylov-Schur method (Stewart; Wu and Simon), what
+ * KrylovKit's eigsolve runs on a Hermitian LinearMap --, the basis, the products, the orthogonalisation and the restart on
+ * the device.  (No counterpart in the reference: its operators are LinearMaps handed to a Julia eigensolver package.)
+ *   Recurrence.  V holds ncv + 1 columns.  v_0 = v0 / ||v0||.  Step j of a cycle (j = start .. ncv - 1; start = 0 in the first
+ *   cycle, `keep` after a restart):
+ *       w = op(A) v_j                      one bsm_mul, written straight into column j + 1
+ *       h = V[:, 0:j+1]^H w;  w -= V[:, 0:j+1] h      TWICE (classical Gram-Schmidt with one reorthogonalisation, the fused pass
+ *                                          of bsm_krylov_orth); the coefficients of both passes add up in column j of H
+ *       alpha_j = Re H[j, j];  beta_j = ||w||;  v_{j+1} = w / beta_j    (beta_j zero or not finite: v_{j+1} = 0, nothing divided)
+ *   No host read happens inside a cycle; it ends with ONE device-to-host copy (diag(H), beta, ||v0||) and one synchronisation.
+ *   The host keeps the real symmetric projected matrix T (ncv x ncv, double): after a restart its leading keep x keep part is
+ *   diag(theta kept) with the arrow row T[keep, i] = beta_m S[m - 1, i] (taken analytically, m = ncv), the new columns take
+ *   alpha_j on and beta_j beside the diagonal.  T = S diag(theta) S^T by a cyclic Jacobi method with a fixed sweep order
+ *   (csrc/bsm_eig.h), theta ascending.  The rotations leave S orthonormal to about ncv eps only; the columns that go to the
+ *   device (the kept ones of a restart, the wanted ones at the end) are made orthonormal to working precision on the host
+ *   first, by two modified Gram-Schmidt passes in the order of the selection.
+ *   Selection (`which`) of `count` Ritz values, and the order they are reported in:  BSM_EIGSH_LA the largest, largest first;
+ *   BSM_EIGSH_SA the smallest, smallest first;  BSM_EIGSH_BE ceil(count / 2) from the top, largest first, then the rest from the
+ *   bottom, smallest first;  BSM_EIGSH_LM the largest |theta|, largest first (of two equal magnitudes the positive one first).
+ *   Estimate and tolerance.  The residual estimate of Ritz pair i is |beta_m S[m - 1, i]|.  anorm = the largest |theta| seen in
+ *   the solve, a lower bound of ||op(A)||_2.  Converged: every wanted pair has estimate <= max(rtol anorm, atol).
+ *   Restart.  keep = min(ncv - 1, nev + (ncv - nev) / 2); the keep pairs are selected by the same rule as the wanted ones; S is
+ *   uploaded, V[:, 0:keep] = V[:, 0:ncv] S[:, kept] by bsm_krylov_combine IN PLACE with the residual vector v_m carried to column
+ *   keep; the next cycle starts at step keep.  The basis is never duplicated.
+ *   End.  X[:, i] = V S[:, wanted_i] through the same kernel into the caller's matrix, every column scaled to norm one (a kept
+ *   column's norm drifts by a rounding error per restart), then the TRUE residuals
+ *   ||op(A) x_i - theta_i x_i||: Q = op(A) X by bsm_mul_multi in batches of at most 16 columns, one partial per workgroup and
+ *   column, one wave per column adds them in a fixed order.  No floating-point atomic in the unit's own kernels, nobody waits.
+ * create: vdtype must be the handle's own vector type (a mixed-storage handle solves in double; a real handle under a complex
+ *   vdtype has no use here: BSM_ERR_INVALID).  1 <= nev, nev + 2 <= ncv <= min(n, BSM_GMRES_MAX_RESTART).  ONE device allocation,
+ *   reported in info: V (ncv + 1 columns), a block Q of min(nev, 16) columns, H (ncv x ncv), beta, S, theta and the partials;
+ *   leading dimensions rounded up to whole 16-byte groups.  Refused, before anything is allocated: null A / out, a bad op, a
+ *   vdtype that is no vector type (BSM_ERR_INVALID); a composed handle (BSM_ERR_UNSUPPORTED); op(A) not square, a vdtype other
+ *   than the handle's own (BSM_ERR_INVALID); a multi-device handle (BSM_ERR_UNSUPPORTED), an analysis-only handle
+ *   (BSM_ERR_DEVICE), a handle that owns a row range only (BSM_ERR_UNSUPPORTED); nev / ncv outside their ranges
+ *   (BSM_ERR_INVALID).  The handle must outlive the solver.
+ * solve: v0 (n entries) and X (n x nev, ldx >= max(n, 1), column-major), any element alignment; BSM_MEM_HOST operands are
+ *   staged through device buffers the solver keeps.  pairs: nev entries.  Synchronous.
+ *   info.status:  0 converged;  1 maxcycles reached (X and pairs hold all nev Ritz pairs as they stand, nconv = nev);  2 a norm,
+ *   a coefficient or a Ritz value is not finite (nconv = 0, X is not written);  3 the Krylov space ended before nev pairs
+ *   existed: beta_j was exactly zero with j + 1 < nev (nconv = j + 1, the pairs of that invariant subspace, exact; a zero v0
+ *   gives nconv = 0).  A space that ends with j + 1 >= nev is convergence: its Ritz pairs are exact.
+ *   pairs[i], i < nconv, in the order of `which`: value, estimate, residual (the true one; with vectors = 0 neither X nor
+ *   the residual pass is produced and residual = estimate).  Entries i >= nconv are NaN; columns i >= nconv of X are untouched.
+ *   X is orthonormal to working precision.  a_products = Lanczos steps + residual columns.
+ *   Refused (BSM_ERR_INVALID): null S, p, info, pairs, v0; a struct_size mismatch; a bad memspace or which; rtol or atol negative
+ *   or NaN; maxcycles < 1; with vectors: null X, ldx < max(n, 1), X overlapping v0; a stream that is being captured.
+ *   Run to run, value, X, cycles and the residuals are bit-identical wherever the product of the handle is (the forward
+ *   product of a conflict-free or gather / coloured operator; see bsm_lsqr above for the transposed product).
+ * Not in it: interior eigenvalues / shift-invert, the generalised problem or a preconditioner, multiplicities (a single-vector
+ *   Krylov space sees one vector of an eigenspace), singular values, block Lanczos / LOBPCG, locking beyond what the thick
+ *   restart keeps. */
+typedef enum { BSM_EIGSH_LA = 0, BSM_EIGSH_SA = 1, BSM_EIGSH_BE = 2, BSM_EIGSH_LM = 3 } bsm_eigsh_which;
+typedef struct {
+    int32_t struct_size; /* = sizeof(bsm_eigsh_params) */
+    int32_t which;       /* bsm_eigsh_which */
+    double rtol, atol;   /* estimate <= max(rtol anorm, atol) */
+    int32_t maxcycles;
+    int32_t vectors;     /* 0: values and estimates only */
+} bsm_eigsh_params;
+typedef struct {
+    int32_t status, nconv, cycles, reserved;
+    int64_t a_products;
+    double anorm;
+    int64_t workspace_bytes;
+    uint64_t workspace; /* device address of the allocation */
+} bsm_eigsh_info;
+typedef struct {
+    double value, estimate, residual;
+} bsm_eigsh_pair;
+BSM_LAYOUT_ASSERT(sizeof(bsm_eigsh_params) == 32 && offsetof(bsm_eigsh_params, rtol) == 8 && offsetof(bsm_eigsh_params, maxcycles) == 24,
+                  "bsm_eigsh_params layout");
+BSM_LAYOUT_ASSERT(sizeof(bsm_eigsh_info) == 48 && offsetof(bsm_eigsh_info, a_products) == 16 && sizeof(bsm_eigsh_pair) == 24,
+                  "bsm_eigsh_info layout");
+struct bsm_eigsh_s;
+int bsm_eigsh_create(bsm_matrix_t A, int opA, int vdtype, int32_t nev, int32_t ncv, struct bsm_eigsh_s **out);
+int bsm_eigsh_solve(struct bsm_eigsh_s *S, const void *v0, void *X /* may be NULL with vectors = 0 */, int64_t ldx,
+                    const bsm_eigsh_params *p, bsm_eigsh_info *info, bsm_eigsh_pair *pairs /* nev */, int memspace, void *stream);
+int bsm_eigsh_destroy(struct bsm_eigsh_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

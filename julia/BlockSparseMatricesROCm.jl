@@ -822,6 +822,76 @@ function lsqr!(X::VecOrMat{T}, A::ROCmAnyOp, B::VecOrMat{T}; rtol::Real=1e-8, at
     return X, info, columns, history[:, 1:min(info.iterations, maxiter)], normal_residual, anorm
 end
 
+# ---- extreme eigenpairs of symmetric / Hermitian operators (bsm_eigsh_*) and the basis compression (bsm_krylov_combine) ----
+mutable struct BsmEigshParams       # mirrors bsm_eigsh_params (32 bytes)
+    struct_size::Int32; which::Int32; rtol::Float64; atol::Float64; maxcycles::Int32; vectors::Int32
+end
+mutable struct BsmEigshInfo         # mirrors bsm_eigsh_info (48 bytes)
+    status::Int32; nconv::Int32; cycles::Int32; reserved::Int32
+    a_products::Int64; anorm::Float64; workspace_bytes::Int64; workspace::UInt64
+end
+struct BsmEigshPair                 # mirrors bsm_eigsh_pair (24 bytes)
+    value::Float64; estimate::Float64; residual::Float64
+end
+const _EIGSH_WHICH = Dict(:LA => 0, :SA => 1, :BE => 2, :LM => 3)
+
+"""
+    eigsh!(X, A, v0; which=:LA, ncv=min(size(A, 1), 128, max(2 nev + 1, 20)), rtol=1e-10, atol=0.0, maxcycles=300, vectors=true)
+        -> (w, X, info, pairs)
+
+`nev = size(X, 2)` extreme eigenpairs of a real symmetric / Hermitian `A` by thick-restart Lanczos (the Hermitian
+Krylov-Schur method that KrylovKit's `eigsolve` runs), the basis, the products, the orthogonalisation and the restart on the
+device (bsm_eigsh_create / _solve / _destroy).  The caller asserts the symmetry.  `which`: `:LA` largest algebraic, `:SA`
+smallest, `:BE` both ends (`cld(nev, 2)` from the top, the rest from the bottom), `:LM` largest magnitude.  `v0` (the start
+vector) and `X` are host arrays of `A`'s element type; `nev + 2 <= ncv <= min(size(A, 1), 128)`.  Converged when every wanted
+pair's estimate `|beta_m S[m, i]|` is `<= max(rtol * anorm, atol)`, `anorm` being the largest `|theta|` seen.  `info.status`:
+0 converged, 1 `maxcycles` reached, 2 a non-finite norm or Ritz value, 3 the Krylov space ended before `nev` pairs existed.
+`w` holds the `info.nconv` eigenvalues in the order of `which`, `X[:, 1:nconv]` their orthonormal vectors, `pairs[i]` value,
+estimate and true residual.  Not in it: interior eigenvalues, shift-invert, the generalised problem, preconditioning,
+multiplicities, singular values, block methods.
+"""
+function eigsh!(X::Matrix{T}, A::ROCmAnyOp, v0::Vector{T}; which::Symbol=:LA,
+                ncv::Integer=min(size(A, 1), 128, max(2 * size(X, 2) + 1, 20)), rtol::Real=1e-10, atol::Real=0.0,
+                maxcycles::Integer=300, vectors::Bool=true) where {T<:ROCmEltype}
+    n, nev = size(X, 1), size(X, 2)
+    size(A, 1) == size(A, 2) == n == length(v0) || throw(DimensionMismatch("eigsh! needs a square operator and v0, X of its order"))
+    haskey(_EIGSH_WHICH, which) || throw(ArgumentError("which must be :LA, :SA, :BE or :LM"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:bsm_eigsh_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), _DTYPE[T], nev, ncv, out))
+    p = BsmEigshParams(sizeof(BsmEigshParams), _EIGSH_WHICH[which], rtol, atol, maxcycles, vectors)
+    info = BsmEigshInfo(0, 0, 0, 0, 0, 0.0, 0, 0)
+    pairs = Vector{BsmEigshPair}(undef, nev)
+    try
+        GC.@preserve A X v0 pairs _check(ccall((:bsm_eigsh_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ref{BsmEigshParams}, Ref{BsmEigshInfo}, Ptr{BsmEigshPair}, Cint, Ptr{Cvoid}),
+            out[], pointer(v0), pointer(X), max(n, 1), p, info, pairs, 0, C_NULL))
+    finally
+        ccall((:bsm_eigsh_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return [pairs[i].value for i in 1:info.nconv], X, info, pairs[1:info.nconv]
+end
+
+"""
+    krylov_combine!(Out, V, S, T, n, m, k; ldv=max(n, 1), lds=m, ldo=max(n, 1), carry=-1, stream=C_NULL)
+
+`Out[:, c] = sum_j V[:, j] S[j, c]` for `c <= k` on the device (bsm_krylov_combine), the sum over `j` ascending with one fma
+per term; with `carry >= 0` (a 0-based column of `V`, at most `m`) that column is also copied behind them.  `Out`, `V`, `S`
+are DEVICE pointers (e.g. of AMDGPU.jl arrays): `V` `n x m` of element type `T`, `S` `m x k` of `real(T)`, column-major.
+`Out == V` with `ldo == ldv` works in place.  Enqueues on `stream`; synchronises nothing.  `krylov_combine_tile(T, m)` is the
+number of rows one workgroup stages.
+"""
+function krylov_combine!(Out::Ptr{Cvoid}, V::Ptr{Cvoid}, S::Ptr{Cvoid}, ::Type{T}, n::Integer, m::Integer, k::Integer;
+                         ldv::Integer=max(n, 1), lds::Integer=m, ldo::Integer=max(n, 1), carry::Integer=-1,
+                         stream::Ptr{Cvoid}=C_NULL) where {T<:ROCmEltype}
+    _check(ccall((:bsm_krylov_combine, libbsm), Cint,
+        (Cint, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}),
+        _DTYPE[T], n, m, k, V, ldv, S, lds, Out, ldo, carry, stream))
+    return Out
+end
+krylov_combine_tile(::Type{T}, m::Integer) where {T<:ROCmEltype} =
+    ccall((:bsm_krylov_combine_tile, libbsm), Int64, (Cint, Int64), _DTYPE[T], m)
+
 # ---- polynomial preconditioners as handles (bsm_poly_*) -----------------------------------------------------------------
 """
     PolynomialPreconditioner
