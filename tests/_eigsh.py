@@ -1,6 +1,7 @@
-"""What the eigsh suites (test_eigsh_cpu.py, test_gpu_eigsh.py) share: the numpy twin of bsm_eigsh_solve, the test problems,
-the acceptance checks and raw ctypes drivers of bsm_krylov_combine, bsm_eigsh_create / _solve / _destroy and the test hooks
-bsm_debug_eig_jacobi / _select / _keep.  Test code only.
+"""What the eigsh suites (test_eigsh_cpu.py, test_gpu_eigsh.py, test_eigsh_grid_cpu.py, test_gpu_eigsh_grid.py) share: the numpy
+twin of bsm_eigsh_solve, the test problems, the acceptance checks (check_pairs, and accept for a device solve) and raw ctypes
+drivers of bsm_krylov_combine, bsm_eigsh_create / _solve / _destroy and the test hooks bsm_debug_eig_jacobi / _select / _keep.
+Test code only.
 
 The twin.  eigsh_twin is thick-restart Lanczos as include/bsm_rocm.h states it: the same step order (product, two classical
 Gram-Schmidt passes whose coefficients add up, norm, guarded scale), the projected matrix T kept in double with the analytic
@@ -12,11 +13,18 @@ The problem.  Order 400.  Eigenvalues lam: -3.3, -2.2, -1.5, -0.9, -0.4, then 39
 6.  rng = default_rng(3600): sets = _submat.cut(rng, 400), the bulk, G Gaussian 400 x 400 (complex types: real part, then
 imaginary part), Q = the Q of qr(G), D = Q diag(lam) Q^H symmetrised, v0 = uniform(-1, 1) from default_rng(1).  D is cut the way
 _cg.cg_problem cuts its D: a 4 x 4 grid of 100 x 100 blocks (vbcrs), one block per pair of sets (blocksparse), or D[I_s, I_s]
-as diagonals and D[I_a, I_b], a > b, as off-diagonals (symmetric: real types only)."""
+as diagonals and D[I_a, I_b], a > b, as off-diagonals (symmetric: real types only).
+
+The grid problems (grid_eig_problem).  Orders that put 2 and 3 workgroups on a vector (grid_sizes).  Block diagonal, Hermitian
+blocks of order 8 and one of order n mod 8, so that the twin and the acceptance need no dense array: the designed eigenvalues
+-- LOW, a bulk uniform in [1, 2], and `high` -- are dealt to the rows by a random permutation, block b is Q_b diag(lam_b)
+Q_b^H with Q_b the Q of qr(Gaussian), symmetrised and rounded to the type; v0 uniform(-1, 1); the reference spectrum is
+eigvalsh of the blocks as stored, widened, block by block."""
 import ctypes as C
 
 import numpy as np
 
+from _cg import BlockDiagonal
 from _jacobi import CODE, set_blocks
 from _krylov import ERR_DEVICE, ERR_INVALID, ERR_UNSUPPORTED, real_of, wide_of  # noqa: F401
 from _submat import cut
@@ -27,6 +35,8 @@ LA, SA, BE, LM = 0, 1, 2, 3
 WHICH = {"LA": LA, "SA": SA, "BE": BE, "LM": LM}
 LOW = np.array([-3.3, -2.2, -1.5, -0.9, -0.4])
 HIGH = np.array([3.0, 3.6, 4.3, 5.1, 6.0])
+# for the cases with more than 5 wanted pairs: the [1, 2] bulk gives LA with nev > 5 nothing separated to converge to
+HIGH40 = 3.0 + 0.4 * np.arange(40)
 DTYPES = [np.float32, np.float64, np.complex64, np.complex128]
 # (nev, ncv) the GPU module runs; (4, 400) is the twin's alone: the library takes ncv <= BSM_GMRES_MAX_RESTART = 128
 CASES = [(4, 20), (5, 12), (1, 3), (4, 128)]
@@ -160,18 +170,149 @@ def tridiagonal_block(dtype):
     return p, D, e1
 
 
+# ---- the grid problems: several workgroups on a vector ------------------------------------------------------------------------
+class HermitianBlocks(BlockDiagonal):
+    """_cg.BlockDiagonal with what the twin and the acceptance ask of a dense array besides: len, dtype, products with
+    matrices (column by column the product with a vector), and the spectrum block by block"""
+
+    @property
+    def dtype(self):
+        return self.main.dtype
+
+    def __len__(self):
+        return self.main.shape[0] * self.main.shape[1] + self.tail.shape[0]
+
+    def astype(self, dtype):
+        return HermitianBlocks(self.main.astype(dtype), self.tail.astype(dtype))
+
+    def times(self, v, order=None):
+        if np.ndim(v) == 1:
+            return BlockDiagonal.times(self, v, order)
+        assert order is None
+        nb, bs, _ = self.main.shape
+        out = np.empty_like(v)
+        out[:nb * bs] = np.einsum("bij,bjk->bik", self.main, v[:nb * bs].reshape(nb, bs, -1)).reshape(nb * bs, -1)
+        out[nb * bs:] = self.tail @ v[nb * bs:]
+        return out
+
+    def shifted(self, shift):
+        """diag(blocks) + shift I, rounded to the blocks' type"""
+        eye, eyet = np.eye(self.main.shape[1]), np.eye(self.tail.shape[0])
+        return HermitianBlocks((self.main + shift * eye).astype(self.dtype), (self.tail + shift * eyet).astype(self.dtype))
+
+    def eigenvalues(self):
+        """eigvalsh of the blocks AS STORED (widened), ascending"""
+        wide = wide_of(self.dtype)
+        tail = [np.linalg.eigvalsh(self.tail.astype(wide))] if self.tail.size else []
+        return np.sort(np.concatenate([np.linalg.eigvalsh(self.main.astype(wide)).ravel()] + tail))
+
+
+def grid_sizes(dtype):
+    """(n with krylov_grid = 2, n with krylov_grid = 3): one row more than a row range of 8192 bytes, and three more than two
+    of them -- odd, so that the padded leading dimension of the workspace differs from n in every type but complex128"""
+    r0 = 8192 // np.dtype(dtype).itemsize
+    return r0 + 1, 2 * r0 + 3
+
+
+_grid_problems = {}
+
+
+def grid_eig_problem(dtype, n, high, seed):
+    """-> (vbcrs problem, HermitianBlocks, ref: its spectrum as stored, ascending, v0) (module docstring); computed once, not to
+    be written to"""
+    dtype, high = np.dtype(dtype), np.asarray(high, dtype=float)
+    key = (dtype.name, n, high.tobytes(), seed)
+    if key not in _grid_problems:
+        rng = np.random.default_rng(seed)
+        bs, nb, t = 8, n // 8, n % 8
+        lam = np.concatenate([LOW, rng.uniform(1, 2, n - len(LOW) - len(high)), high])[rng.permutation(n)]
+
+        def blocks(lams, k):
+            G = rng.standard_normal((len(lams), k, k))
+            if is_complex(dtype):
+                G = G + 1j * rng.standard_normal((len(lams), k, k))
+            out = np.empty(G.shape, dtype)
+            for b in range(len(lams)):
+                Q, _ = np.linalg.qr(G[b])
+                B = (Q * lams[b]) @ Q.conj().T
+                out[b] = ((B + B.conj().T) / 2).astype(dtype)
+            return out
+        main = blocks(lam[:nb * bs].reshape(nb, bs), bs)
+        tail = blocks(lam[nb * bs:].reshape(1, t), t)[0] if t else np.zeros((0, 0), dtype)
+        v0 = rng.uniform(-1, 1, n).astype(dtype)
+        blks = [np.asfortranarray(main[b]) for b in range(nb)] + ([np.asfortranarray(tail)] if t else [])
+        starts = np.arange(len(blks), dtype=np.int64) * bs + 1
+        p = dict(kind="vbcrs", blocks=blks, rowstart=starts, colstart=starts.copy(), size=(n, n))
+        Dop = HermitianBlocks(main, tail)
+        _grid_problems[key] = (p, Dop, Dop.eigenvalues(), v0, lam)
+    return _grid_problems[key][:4]
+
+
+# name -> (the outliers above the bulk, the seed's base: the generator is default_rng(base + n))
+SPECTRA = {"high": (HIGH, 3700), "high20": (HIGH40[:20], 3900), "high40": (HIGH40, 4100)}
+# (nev, ncv, which) at both grid sizes of every type, on "high"; (1, 3) restarts 24 .. 59 times, (4, 20) would not restart
+GRID_CASES = [(5, 12, "LA"), (5, 12, "BE"), (3, 8, "LM"), (1, 3, "SA")]
+# (nev, ncv, which, spectrum) at the G = 2 size: true-residual batches of 16 + 1 and 16 + 16 + 1
+BATCH_CASES = [(17, 24, "LA", "high20"), (33, 48, "LA", "high40"), (33, 40, "LA", "high40")]
+# The single types once more at a LOOSE tolerance.  At eig_rtol = 2e-5 their residuals are of the size of the acceptance's
+# |true - residual| <= 1e-5 anorm, which a residual that lost a workgroup's share therefore passes; at 1e-2 the last pair's
+# residual is some 5e-3 anorm and the share of the last row range some 5e-4 anorm of it (pinned in test_eigsh_grid_cpu.py)
+LOOSE_RTOL, LOOSE_CASE, LOOSE_TYPES = 1e-2, (3, 8, "LM"), [np.float32, np.complex64]
+# what test_gpu_eigsh_grid.py runs besides: (dtype, n index, nev, ncv, which, spectrum)
+EXTRA_CASES = [(np.float64, 1, 5, 12, "LM", "high"), (np.complex128, 1, 5, 12, "LA", "high")]
+
+
+def grid_problem(dtype, n, spec="high"):
+    high, base = SPECTRA[spec]
+    return grid_eig_problem(dtype, n, high, base + n)
+
+
+def all_grid_cases():
+    """[(dtype, n, nev, ncv, which, spectrum)]: every solve of test_gpu_eigsh_grid.py on a grid problem"""
+    out = []
+    for dt in DTYPES:
+        sizes = grid_sizes(dt)
+        out += [(dt, n, nev, ncv, which, "high") for n in sizes for nev, ncv, which in GRID_CASES]
+        out += [(dt, sizes[0]) + c for c in BATCH_CASES]
+    out += [(dt, grid_sizes(dt)[i]) + tuple(c) for dt, i, *c in EXTRA_CASES]
+    seen, uniq = set(), []
+    for c in out:
+        k = grid_id(c)
+        if k not in seen:
+            seen.add(k)
+            uniq.append(c)
+    return uniq
+
+
+def grid_id(c):
+    dt, n, nev, ncv, which, spec = c
+    return f"{np.dtype(dt).name}-n{n}-{nev}of{ncv}-{which}-{spec}"
+
+
+_grid_twins = {}
+
+
+def grid_twin(dtype, n, nev, ncv, which, spec="high", rtol=None):
+    """the twin on grid_problem(dtype, n, spec) at rtol (None: eig_rtol(dtype)) from the problem's v0; computed once"""
+    key = (grid_id((dtype, n, nev, ncv, which, spec)), rtol)
+    if key not in _grid_twins:
+        _, Dop, _, v0 = grid_problem(dtype, n, spec)
+        _grid_twins[key] = eigsh_twin(Dop, v0, nev, ncv, which, eig_rtol(dtype) if rtol is None else rtol, dtype=dtype)
+    return _grid_twins[key]
+
+
 # ---- the twin -----------------------------------------------------------------------------------------------------------------
 class EigTwin:
     pass
 
 
 def eigsh_twin(D, v0, nev, ncv, which, rtol, atol=0.0, maxcycles=300, dtype=None):
-    """numpy twin of bsm_eigsh_solve (module docstring) -> EigTwin: status, nconv, cycles, steps, anorm, value, estimate,
+    """numpy twin of bsm_eigsh_solve (module docstring) on a dense array or a HermitianBlocks operator -> EigTwin: status, nconv, cycles, steps, anorm, value, estimate,
     residual (||D x - theta x|| in `dtype` arithmetic, norm in double), X (n x nconv), orth = max |X^H X - I|"""
     dtype = np.dtype(D.dtype if dtype is None else dtype)
     real = real_of(dtype)
     which = WHICH.get(which, which)
-    D = np.asarray(D).astype(dtype)
+    D = D.astype(dtype) if isinstance(D, BlockDiagonal) else np.asarray(D).astype(dtype)
     n = len(D)
     assert 1 <= nev and nev + 2 <= ncv <= n
     V = np.zeros((n, ncv + 1), dtype)
@@ -308,6 +449,44 @@ def check_pairs(value, estimate, residual, anorm, ref, which, tol, dtype, what):
         assert err <= bound, (what, i, err, bound)
         assert residual[i] <= tol + g, (what, i, residual[i], tol, g)
     return gap
+
+
+def steps_of(nev, ncv, cycles):
+    return ncv + (cycles - 1) * (ncv - keep_of(nev, ncv))
+
+
+def accept(torch, w, X, info, D, n, twin, nev, ncv, which, dtype, what, ref=None, rtol=None):
+    """the acceptance of a converged device solve (docstring of test_gpu_eigsh.py).  D: the operator of order n, a dense array
+    or HermitianBlocks (then with ref, its spectrum); X: a torch tensor"""
+    from _gpu import TOL
+    dtype = np.dtype(dtype)
+    eps = float(np.finfo(dtype).eps)
+    ref = stored_eigenvalues(D) if ref is None else ref
+    assert len(D) == n == len(ref)
+    assert twin.status == 0, (what, "the twin did not converge")
+    assert info.status == 0 and info.nconv == nev == len(w), (what, info)
+    tol = (eig_rtol(dtype) if rtol is None else rtol) * info.anorm
+    assert np.all(info.estimate <= tol), (what, info.estimate, tol)
+    gap = check_pairs(w, info.estimate, info.residual, info.anorm, ref, which, tol, dtype, what)
+    # the derived bound of test_eigsh_cpu.py on |residual - estimate|: forming X = V S ((ncv + 1) eps |V| |S| ||A||) and the product
+    # (n eps ||A||).  With estimate <= tol it is what makes the residual of the returned X small.
+    gap_bound = n + ncv + 2
+    assert gap <= gap_bound, (what, gap, gap_bound)
+    Xh = X.cpu().numpy().astype(wide_of(dtype))
+    true = np.linalg.norm(D.astype(wide_of(dtype)) @ Xh - Xh * w, axis=0)
+    print(f"EIGSTAT {what}: gap / (eps anorm) {gap:.2f} of {gap_bound}, max |true - residual| / anorm {np.max(np.abs(true - info.residual)) / info.anorm:.3e} "
+          f"of {TOL[dtype]:.0e}, max |true - estimate| / (eps anorm) {np.max(np.abs(true - info.estimate)) / (eps * info.anorm):.2f} of {gap_bound}, "
+          f"max estimate / tol {np.max(info.estimate) / tol:.3e}")
+    assert np.all(np.abs(true - info.residual) <= TOL[dtype] * info.anorm), (what, true, info.residual)
+    assert np.all(np.abs(true - info.estimate) <= gap_bound * eps * info.anorm), (what, true, info.estimate)
+    assert np.all(true <= tol + gap_bound * eps * info.anorm), (what, true, tol)
+    orth = float(np.max(np.abs(Xh.conj().T @ Xh - np.eye(nev))))
+    print(f"EIGSTAT {what}: cycles {info.cycles} (twin {twin.cycles}), orth / eps {orth / eps:.2f} (twin {twin.orth / eps:.2f}, margin used "
+          f"{orth / twin.orth if twin.orth else float('inf'):.2f} of 8), anorm {info.anorm:.6f}, a_products {info.a_products}")
+    assert orth <= 8 * twin.orth, (what, orth / eps, twin.orth / eps)
+    assert info.cycles <= twin.cycles + 1, (what, info.cycles, twin.cycles)
+    assert info.a_products == steps_of(nev, ncv, info.cycles) + nev, (what, info.a_products)
+    assert info.anorm <= float(np.max(np.abs(ref))) * (1 + n * eps)  # a lower bound of ||A||_2, up to the error of both sides
 
 
 # ---- raw ctypes drivers --------------------------------------------------------------------------------------------------

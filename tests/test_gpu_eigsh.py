@@ -9,7 +9,7 @@ feature: the entry points do not exist there.
 Gram-Schmidt kernels and the LDS tile are sized by it -- so the device runs (4, 128) as its widest case and REFUSES (4, 400),
 which test_refusals_of_create asserts.
 
-Acceptance of a converged solve (accept): the two inequalities of the issue; the gap |residual - estimate| under the derived
+Acceptance of a converged solve (accept, tests/_eigsh.py): the two inequalities of the issue; the gap |residual - estimate| under the derived
 bound (n + ncv + 2) eps anorm that test_eigsh_cpu.py pins -- with estimate <= tol this is what bounds the residual of the
 returned X --, for the reported residual and for the one recomputed in numpy from X and w; max |X^H X - I| <= 8 x the twin's
 value on the same case; the twin's cycle count (+ 1); the product count."""
@@ -18,10 +18,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from _eigsh import (CASES, DTYPES, ERR_DEVICE, ERR_INVALID, ERR_UNSUPPORTED, LA, NEIG, WHICH, check_pairs, eig_dense, eig_problem, eig_rtol,
-                    eigsh_twin, keep_of, raw_combine, raw_eigsh_create, raw_eigsh_destroy, raw_eigsh_solve, stored_eigenvalues,
-                    tridiagonal_block, twin_of)
-from _gpu import TOL, dev_mat, outside_bytes, torch_cuda, torch_dtype  # noqa: F401
+from _eigsh import (CASES, DTYPES, ERR_DEVICE, ERR_INVALID, ERR_UNSUPPORTED, NEIG, WHICH, accept, eig_dense, eig_problem, eig_rtol, eigsh_twin,
+                    raw_combine, raw_eigsh_create, raw_eigsh_destroy, raw_eigsh_solve, steps_of, tridiagonal_block, twin_of)
+from _gpu import dev_mat, outside_bytes, torch_cuda, torch_dtype  # noqa: F401
 from _jacobi import CODE
 from _krylov import real_of, wide_of
 from _values import copied, diagonal_shift, on_device
@@ -139,38 +138,6 @@ def handle(bsm, kind, dtype, **kw):
     return _handles[key]
 
 
-def steps_of(nev, ncv, cycles):
-    return ncv + (cycles - 1) * (ncv - keep_of(nev, ncv))
-
-
-def accept(torch, w, X, info, D, twin, nev, ncv, which, dtype, what, ref=None, rtol=None):
-    """the acceptance of a converged solve (module docstring)"""
-    dtype = np.dtype(dtype)
-    eps = float(np.finfo(dtype).eps)
-    ref = stored_eigenvalues(D) if ref is None else ref
-    assert twin.status == 0, (what, "the twin did not converge")
-    assert info.status == 0 and info.nconv == nev == len(w), (what, info)
-    tol = (eig_rtol(dtype) if rtol is None else rtol) * info.anorm
-    assert np.all(info.estimate <= tol), (what, info.estimate, tol)
-    gap = check_pairs(w, info.estimate, info.residual, info.anorm, ref, which, tol, dtype, what)
-    # the derived bound of test_eigsh_cpu.py on |residual - estimate|: forming X = V S ((ncv + 1) eps |V| |S| ||A||) and the product
-    # (n eps ||A||).  With estimate <= tol it is what makes the residual of the returned X small.
-    gap_bound = len(D) + ncv + 2
-    assert gap <= gap_bound, (what, gap, gap_bound)
-    Xh = X.cpu().numpy().astype(wide_of(dtype))
-    true = np.linalg.norm(D.astype(wide_of(dtype)) @ Xh - Xh * w, axis=0)
-    assert np.all(np.abs(true - info.residual) <= TOL[dtype] * info.anorm), (what, true, info.residual)
-    assert np.all(np.abs(true - info.estimate) <= gap_bound * eps * info.anorm), (what, true, info.estimate)
-    assert np.all(true <= tol + gap_bound * eps * info.anorm), (what, true, tol)
-    orth = float(np.max(np.abs(Xh.conj().T @ Xh - np.eye(nev))))
-    print(f"EIGSTAT {what}: cycles {info.cycles} (twin {twin.cycles}), orth / eps {orth / eps:.2f} (twin {twin.orth / eps:.2f}, margin used "
-          f"{orth / twin.orth if twin.orth else float('inf'):.2f} of 8), anorm {info.anorm:.6f}, a_products {info.a_products}")
-    assert orth <= 8 * twin.orth, (what, orth / eps, twin.orth / eps)
-    assert info.cycles <= twin.cycles + 1, (what, info.cycles, twin.cycles)
-    assert info.a_products == steps_of(nev, ncv, info.cycles) + nev, (what, info.a_products)
-    assert info.anorm <= float(np.max(np.abs(ref))) * (1 + NEIG * eps)  # a lower bound of ||A||_2, up to the error of both sides
-
-
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}of{c[1]}")
 @pytest.mark.parametrize("which", list(WHICH))
 @pytest.mark.parametrize("dtype", DTYPES, ids=name)
@@ -179,7 +146,7 @@ def test_solve_against_twin_and_dense_reference(torch_cuda, bsm, dtype, which, c
     D, _, _, v0 = eig_dense(dtype)
     A = handle(bsm, "vbcrs", dtype)
     w, X, info = bsm.Eigsh(A, nev=nev, ncv=ncv, which=which).solve(dev(torch_cuda, v0), rtol=eig_rtol(dtype))
-    accept(torch_cuda, w, X, info, D, twin_of(dtype, nev, ncv, which), nev, ncv, which, dtype, f"vbcrs {name(dtype)} {which} {case}")
+    accept(torch_cuda, w, X, info, D, NEIG, twin_of(dtype, nev, ncv, which), nev, ncv, which, dtype, f"vbcrs {name(dtype)} {which} {case}")
 
 
 @pytest.mark.parametrize("which", list(WHICH))
@@ -189,7 +156,7 @@ def test_solve_on_the_other_kinds(torch_cuda, bsm, kind, dtype, which):
     D, _, _, v0 = eig_dense(dtype)
     A = handle(bsm, kind, dtype)
     w, X, info = bsm.eigsh(A, 4, ncv=20, which=which, v0=dev(torch_cuda, v0), rtol=eig_rtol(dtype))
-    accept(torch_cuda, w, X, info, D, twin_of(dtype, 4, 20, which), 4, 20, which, dtype, f"{kind} {name(dtype)} {which}")
+    accept(torch_cuda, w, X, info, D, NEIG, twin_of(dtype, 4, 20, which), 4, 20, which, dtype, f"{kind} {name(dtype)} {which}")
 
 
 def test_host_operands_and_default_start_vector(torch_cuda, bsm):
@@ -198,7 +165,7 @@ def test_host_operands_and_default_start_vector(torch_cuda, bsm):
     S = bsm.Eigsh(A, nev=4, ncv=20, which="SA")
     w, X, info = S.solve(v0)  # numpy in, numpy out: staged
     assert isinstance(X, np.ndarray) and X.flags.f_contiguous
-    accept(torch_cuda, w, torch_cuda.from_numpy(X), info, D, twin_of(np.float64, 4, 20, "SA"), 4, 20, "SA", np.float64, "host operands")
+    accept(torch_cuda, w, torch_cuda.from_numpy(X), info, D, NEIG, twin_of(np.float64, 4, 20, "SA"), 4, 20, "SA", np.float64, "host operands")
     wd, Xd, infod = S.solve(dev(torch_cuda, v0))
     assert wd.tobytes() == w.tobytes() and Xd.cpu().numpy().tobytes() == X.tobytes()
     w2, X2, info2 = S.solve(seed=3)  # the default start vector, on the device
@@ -291,7 +258,7 @@ def test_one_case_per_kind_of_handle(torch_cuda, bsm, what, kind, dtype, kw, mod
     S = bsm.Eigsh(op, nev=4, ncv=20, which="BE")
     assert S.dtype == np.dtype(dtype)
     w, X, info = S.solve(dev(torch, v0), rtol=rtol)
-    accept(torch, w, X, info, D, twin, 4, 20, "BE", dtype, what, ref=ref)
+    accept(torch, w, X, info, D, NEIG, twin, 4, 20, "BE", dtype, what, ref=ref)
 
 
 @pytest.mark.parametrize("kind,dtype", [("symmetric", np.float64), ("vbcrs", np.complex128)], ids=lambda v: v if isinstance(v, str) else name(v))
@@ -302,13 +269,13 @@ def test_one_solver_across_update_blocks(torch_cuda, bsm, kind, dtype):
     S = bsm.Eigsh(A, nev=4, ncv=20, which="SA")
     vd = dev(torch, v0)
     w, X, info = S.solve(vd)
-    accept(torch, w, X, info, D, twin_of(dtype, 4, 20, "SA"), 4, 20, "SA", dtype, f"before the update {kind}")
+    accept(torch, w, X, info, D, NEIG, twin_of(dtype, 4, 20, "SA"), 4, 20, "SA", dtype, f"before the update {kind}")
     shift = 2.5
     ids, new = diagonal_shift(p, np.full(NEIG, shift))
     bsm.update_blocks(A, new, ids=ids)
     D2 = (D + shift * np.eye(NEIG)).astype(dtype)
     w2, X2, info2 = S.solve(vd)
-    accept(torch, w2, X2, info2, D2, eigsh_twin(D2, v0, 4, 20, "SA", eig_rtol(dtype)), 4, 20, "SA", dtype, f"after the update {kind}",
+    accept(torch, w2, X2, info2, D2, NEIG, eigsh_twin(D2, v0, 4, 20, "SA", eig_rtol(dtype)), 4, 20, "SA", dtype, f"after the update {kind}",
            ref=np.linalg.eigvalsh(D2.astype(wide_of(dtype))))
     assert np.max(np.abs(w2 - w - shift)) <= info.residual.max() + info2.residual.max() + 2 * NEIG * np.finfo(dtype).eps * info2.anorm
 
