@@ -15,5 +15,7 @@ from .solvers import Lsqr, LsqrInfo, Minres, lsqr, minres  # noqa: F401
 from .solvers import (PolynomialPreconditioner, chebyshev, chebyshev_coefficients, lanczos_bounds, neumann,  # noqa: F401
                       polynomial)
 from .solvers import Eigsh, EigshInfo, eigsh, krylov_combine, krylov_combine_tile  # noqa: F401
+from .solvers import (Lobpcg, LobpcgInfo, lobpcg, block_gram, block_gram_grid, block_gram_work, block_combine,  # noqa: F401
+                      block_combine_tile)
 
 __all__ = matrices.__all__ + entries.__all__ + solvers.__all__ + ["synthetic"]

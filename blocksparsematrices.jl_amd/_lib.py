@@ -95,6 +95,16 @@ class BsmEigshPair(C.Structure):
     _fields_ = [("value", C.c_double), ("estimate", C.c_double), ("residual", C.c_double)]
 
 
+class BsmLobpcgParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("maxiter", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BsmLobpcgInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("nconv", C.c_int32), ("iterations", C.c_int32), ("drops", C.c_int32),
+                ("a_products", C.c_int64), ("m_products", C.c_int64), ("anorm", C.c_double), ("workspace_bytes", C.c_int64)]
+
+
 class BsmError(RuntimeError):
     pass
 
@@ -118,7 +128,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy",
            "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy", "bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy",
            "bsm_poly_create", "bsm_poly_info", "bsm_krylov_combine_tile", "bsm_krylov_combine", "bsm_eigsh_create",
-           "bsm_eigsh_solve", "bsm_eigsh_destroy"]
+           "bsm_eigsh_solve", "bsm_eigsh_destroy", "bsm_block_gram_grid", "bsm_block_gram_work", "bsm_block_gram",
+           "bsm_block_combine_tile", "bsm_block_combine", "bsm_lobpcg_create", "bsm_lobpcg_solve", "bsm_lobpcg_destroy"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -281,6 +292,22 @@ def lib():
                                       C.POINTER(BsmEigshPair), C.c_int, C.c_void_p]
         L.bsm_eigsh_destroy.argtypes = [C.c_void_p]
         for name in ("bsm_krylov_combine", "bsm_eigsh_create", "bsm_eigsh_solve", "bsm_eigsh_destroy"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "bsm_lobpcg_create") or "BSM_LIB" not in os.environ:  # (developer A/B builds may predate them)
+        L.bsm_block_gram_grid.argtypes = [C.c_int, C.c_int64]
+        L.bsm_block_gram_work.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64]
+        L.bsm_block_combine_tile.argtypes = [C.c_int, C.c_int64]
+        L.bsm_block_gram_grid.restype = L.bsm_block_gram_work.restype = L.bsm_block_combine_tile.restype = C.c_int64
+        L.bsm_block_gram.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                     C.c_int64, C.c_void_p, C.c_void_p]
+        L.bsm_block_combine.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_int64, C.c_void_p]
+        L.bsm_lobpcg_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bsm_lobpcg_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(BsmLobpcgParams),
+                                       C.POINTER(BsmLobpcgInfo), C.POINTER(BsmEigshPair), C.POINTER(C.c_double), C.c_int64, C.c_int,
+                                       C.c_void_p]
+        L.bsm_lobpcg_destroy.argtypes = [C.c_void_p]
+        for name in ("bsm_block_gram", "bsm_block_combine", "bsm_lobpcg_create", "bsm_lobpcg_solve", "bsm_lobpcg_destroy"):
             getattr(L, name).restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._marshal import _BlockList, _DT, _TORCH_DT, _blocks_kind, _describe, _elt, _i64, _is_dev, _is_tensor, _like, _p64, _stream_ptr, torch
+from ._marshal import _BlockList, _DT, _TORCH_DT, _TORCH_OF, _blocks_kind, _describe, _elt, _i64, _is_dev, _is_tensor, _like, _p64, _stream_ptr, torch
 from .entries import _out_device, submatrices
 from .matrices import (AbstractBlockMatrix, BlockSparseMatrix, SymmetricBlockMatrix, _no_mixed_update, _operator, _unwrap, mul, size,
                        update_blocks)
@@ -814,3 +814,184 @@ class Eigsh:
 def eigsh(A, nev=6, ncv=None, which="LA", dtype=None, **kw):
     """One-shot form: Eigsh(A, nev, ncv, which, dtype).solve(**kw) -> (w, X, EigshInfo)."""
     return Eigsh(A, nev=nev, ncv=ncv, which=which, dtype=dtype).solve(**kw)
+
+
+# ---- LOBPCG on the device (bsm_lobpcg_*) and the two tall-skinny products of a block method ---------------------------------
+# (Lobpcg, LobpcgInfo, lobpcg, block_gram and block_combine are exported by the package by name, like Eigsh)
+def _wide(dt):
+    return np.dtype(np.complex128 if np.dtype(dt).kind == "c" else np.float64)
+
+
+def _ld(t):
+    return t.stride(1) if t.shape[1] > 1 else max(t.shape[0], 1)
+
+
+def _column_major(ts, fn):
+    if torch is None or not all(isinstance(t, torch.Tensor) and t.is_cuda and t.dim() == 2 for t, _ in ts):
+        raise TypeError(f"{fn} takes torch CUDA matrices")
+    for t, name in ts:
+        if t.shape[0] > 1 and t.stride(0) != 1:
+            raise TypeError(f"{name} must be column-major (e.g. torch.empty(cols, ld).t()[:n])")
+        if t.device != ts[0][0].device:
+            raise ValueError(f"{name} must live on the device of {ts[0][1]}")
+
+
+def block_gram_grid(dtype, n):
+    """Workgroups (row ranges) of the first launch of block_gram on n rows of `dtype` (bsm_block_gram_grid)."""
+    return int(L.lib().bsm_block_gram_grid(_DT[np.dtype(dtype)], int(n)))
+
+
+def block_gram_work(dtype, n, p, q):
+    """Bytes of the work buffer of block_gram (bsm_block_gram_work)."""
+    return int(L.lib().bsm_block_gram_work(_DT[np.dtype(dtype)], int(n), int(p), int(q)))
+
+
+def block_gram(U, W, out=None, stream=None, *, work=None):
+    """out = U^H W on the device (bsm_block_gram).  U: n x p (p <= 48), W: n x q (q <= 96), column-major torch CUDA matrices of
+    one element type, any alignment; W may alias or contain U.  out: p x q column-major of the WIDE type (float64 / complex128;
+    None: new).  work: a 16-byte aligned CUDA tensor of at least block_gram_work(...) bytes (None: new).  Partial sums per row
+    range on the matrix pipe in U's precision, added in a fixed order in double: run to run the same bits.  Enqueued on
+    `stream` (default: torch's current stream); nothing is synchronised."""
+    _column_major([(U, "U"), (W, "W")] + ([] if out is None else [(out, "out")]), "block_gram")
+    dt = _TORCH_DT.get(U.dtype)
+    if dt is None or W.dtype != U.dtype or U.shape[0] != W.shape[0]:
+        raise TypeError("U and W must have one supported element type and the same number of rows")
+    n, p, q = U.shape[0], U.shape[1], W.shape[1]
+    if not (1 <= p <= 48 and 1 <= q <= 96):
+        raise ValueError(f"U has {p} columns and W {q}: 1 .. 48 and 1 .. 96")
+    if out is None:
+        out = torch.empty((q, p), dtype=_TORCH_OF[_wide(dt)], device=U.device).t()
+    if _TORCH_DT.get(out.dtype) != _wide(dt) or tuple(out.shape) != (p, q):
+        raise ValueError(f"out must be a {p} x {q} matrix of {_wide(dt)}")
+    need = block_gram_work(dt, n, p, q)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=U.device)
+    if work.device != U.device or work.numel() * work.element_size() < need:
+        raise ValueError(f"work must hold {need} bytes on U's device")
+    L.check(L.lib().bsm_block_gram(_DT[dt], n, p, U.data_ptr(), _ld(U), q, W.data_ptr(), _ld(W), out.data_ptr(), _ld(out),
+                                   work.data_ptr(), _stream_ptr(stream, U.device)))
+    return out
+
+
+def block_combine_tile(dtype, p):
+    """Rows (elements of `dtype`) of the tile one workgroup of block_combine stages for p columns (bsm_block_combine_tile)."""
+    return int(L.lib().bsm_block_combine_tile(_DT[np.dtype(dtype)], int(p)))
+
+
+def block_combine(V, C, out=None, stream=None):
+    """out[:, c] = sum_j V[:, j] C[j, c] on the device (bsm_block_combine), C of V's own type -- complex for complex V --, the sum
+    over j ascending with fused multiply-adds: fixed to the bit.  V: n x >= p, C: p x q (p <= 48, q <= p), column-major torch
+    CUDA matrices; out: n x q of V's type -- None: IN PLACE, the leading q columns of V are overwritten and returned.  Enqueued
+    on `stream` (default: torch's current stream); nothing is synchronised."""
+    _column_major([(V, "V"), (C, "C")] + ([] if out is None else [(out, "out")]), "block_combine")
+    dt = _TORCH_DT.get(V.dtype)
+    if dt is None or C.dtype != V.dtype:
+        raise TypeError("V and C must have one supported element type")
+    n, (p, q) = V.shape[0], C.shape
+    if not (1 <= p <= 48 and q <= p and V.shape[1] >= p):
+        raise ValueError(f"C is {p} x {q}: p must be 1 .. 48, q <= p, and V hold p columns")
+    if out is None:
+        out = V[:, :q]
+    if out.dtype != V.dtype or tuple(out.shape) != (n, q):
+        raise ValueError(f"out must be a {n} x {q} matrix of V's type")
+    L.check(L.lib().bsm_block_combine(_DT[dt], n, p, q, V.data_ptr(), _ld(V), C.data_ptr(), _ld(C), out.data_ptr(),
+                                      _ld(V) if out.data_ptr() == V.data_ptr() and out.shape[1] <= 1 else _ld(out),
+                                      _stream_ptr(stream, V.device)))
+    return out
+
+
+class LobpcgInfo:
+    """What a solve reports (bsm_lobpcg_info and the bsm_eigsh_pair entries): status (0 converged, 1 maxiter reached, 2 a
+    non-finite norm, Gram entry or Ritz value, 3 fewer than `block` directions kept), nconv, iterations, drops (directions the
+    Rayleigh-Ritz steps dropped), a_products (= iterations + 2 multi-column products), m_products (= iterations), anorm (the
+    largest |Ritz value| seen: a lower bound of ||A||_2), workspace_bytes; per pair, as numpy arrays of nev entries: value,
+    estimate (the CARRIED residual norm), residual (the true ||A x - theta x||); history: (iterations + 1) x nev carried norms
+    (None without history)."""
+
+    def __init__(self, info, pairs, nev, history):
+        for name, _ in L.BsmLobpcgInfo._fields_:
+            setattr(self, name, getattr(info, name))
+        self.value = np.array([pairs[i].value for i in range(nev)], dtype=np.float64)
+        self.estimate = np.array([pairs[i].estimate for i in range(nev)], dtype=np.float64)
+        self.residual = np.array([pairs[i].residual for i in range(nev)], dtype=np.float64)
+        self.history = history
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"LobpcgInfo(status={self.status}, nconv={self.nconv}, iterations={self.iterations}, drops={self.drops}, "
+                f"a_products={self.a_products}, m_products={self.m_products}, anorm={self.anorm:.3e})")
+
+
+class Lobpcg:
+    """The `nev` smallest (which="SA") or largest ("LA") eigenpairs of a real symmetric / complex Hermitian A by LOBPCG on a
+    block of `block` vectors (bsm_lobpcg_*), with an optional preconditioner M -- Hermitian positive definite, ~ inv(A) on the
+    wanted end: block_jacobi(A), chebyshev(A, ...), neumann(A, ...) or any block matrix.  The CALLER asserts both.  A block
+    method finds every copy of a multiple eigenvalue, and A is streamed once per iteration for the whole block.  block: nev ..
+    16, 3 block <= n; None: min(16, nev + 2).  dtype: A's own vector type (a mixed-storage A solves in double).  The workspace
+    (6 block vectors, 7 with M) is allocated here, once; A and M are kept alive and update_blocks(A, ...) is seen by the next
+    solve.  Per iteration the host synchronises once and runs a Rayleigh-Ritz step of order up to 3 block."""
+
+    def __init__(self, A, nev=4, block=None, M=None, which="SA", dtype=None):
+        base, op = _operator(A)
+        mbase, mop = (None, L.BSM_OP_N) if M is None else _operator(M, "M")
+        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
+        if self.dtype not in _DT:
+            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        if which not in ("SA", "LA"):
+            raise ValueError(f"which={which!r}: 'SA' or 'LA'")
+        m, n = size(A)
+        self.nev = int(nev)
+        self.block = min(L.BSM_CG_MAX_RHS, self.nev + 2) if block is None else int(block)
+        self.which, self.A, self.M, self.n, self._base, self._mbase = which, A, M, n, base, mbase
+        ptr = C.c_void_p()
+        L.check(L.lib().bsm_lobpcg_create(base._h.ptr, op, None if mbase is None else mbase._h.ptr, mop, _DT[self.dtype], self.nev,
+                                          self.block, C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                L.lib().bsm_lobpcg_destroy(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def solve(self, X0=None, rtol=1e-10, atol=0.0, maxiter=200, stream=None, seed=0, history=True, *, X=None):
+        """-> (w, X, LobpcgInfo).  X0: the start block, n x block, column-major -- torch CUDA tensor (the solve is enqueued on
+        `stream`, default torch's current stream) or numpy array (staged); None: uniform in (-1, 1) from numpy's
+        default_rng(seed), on A's device.  X: where the vectors go (n x nev, column-major, like X0; None: new).  w: the nev
+        eigenvalues in the order of `which` (numpy; NaN with status 2 or 3, X is then not written).  Converged when the carried
+        residual norms of the first nev columns are <= max(rtol * anorm, atol).  Synchronous."""
+        if X0 is None:
+            X0 = np.random.default_rng(seed).uniform(-1, 1, (self.n, self.block))
+            if self.dtype.kind == "c":
+                X0 = X0 + 0j
+            X0 = torch.from_numpy(np.ascontiguousarray(X0.astype(self.dtype).T)).to(torch.device("cuda", self._base.device)).t()
+        x0p, ldx0, k0, ms, _, _ = _describe(X0, self.dtype, self.n, "X0", self._base, True)
+        if k0 != self.block:
+            raise ValueError(f"DimensionMismatch: X0 has {k0} columns, expected block = {self.block}")
+        if X is None:
+            X = _like(X0, self.n, self.nev)
+        xp, ldx, k, xms, _, _ = _describe(X, self.dtype, self.n, "X", self._base, True)
+        if k != self.nev:
+            raise ValueError(f"DimensionMismatch: X has {k} columns, expected nev = {self.nev}")
+        if xms != ms:
+            raise ValueError("X0 and X must live in the same memory space")
+        st = _stream_ptr(stream, X0.device) if ms == L.BSM_MEM_DEVICE else None
+        p = L.BsmLobpcgParams(C.sizeof(L.BsmLobpcgParams), _EIGSH_WHICH[self.which], float(rtol), float(atol), int(maxiter), 0)
+        info = L.BsmLobpcgInfo()
+        pairs = (L.BsmEigshPair * self.nev)()
+        cap = int(maxiter) + 1 if history else 0
+        hist = np.full((max(cap, 1), self.nev), np.nan)
+        L.check(L.lib().bsm_lobpcg_solve(self._ptr, x0p, ldx0, xp, ldx, C.byref(p), C.byref(info), pairs,
+                                         hist.ctypes.data_as(C.POINTER(C.c_double)) if history else None, cap, ms, st))
+        out = LobpcgInfo(info, pairs, self.nev, hist[:info.iterations + 1].copy() if history and info.status <= 1 else None)
+        return out.value.copy(), X, out
+
+
+def lobpcg(A, nev=4, block=None, M=None, which="SA", dtype=None, **kw):
+    """One-shot form: Lobpcg(A, nev, block, M, which, dtype).solve(**kw) -> (w, X, LobpcgInfo)."""
+    return Lobpcg(A, nev=nev, block=block, M=M, which=which, dtype=dtype).solve(**kw)

@@ -1145,6 +1145,122 @@ int bsm_eigsh_solve(struct bsm_eigsh_s *S, const void *v0, void *X /* may be NUL
                     const bsm_eigsh_params *p, bsm_eigsh_info *info, bsm_eigsh_pair *pairs /* nev */, int memspace, void *stream);
 int bsm_eigsh_destroy(struct bsm_eigsh_s *S);
 
+/* bsm_block_gram, bsm_block_combine: the two tall-skinny products of a caller's BLOCK method, beside bsm_krylov_orth (one w per
+ * call) and bsm_krylov_combine (a REAL S).  Both only enqueue on `stream`, synchronise nothing and may be graph-captured.
+ *
+ * bsm_block_gram:  G = U^H W.  U: n x p, 1 <= p <= 48; W: n x q, 1 <= q <= 96; column-major device matrices of dtype (BSM_F32 ..
+ * BSM_C128), ldu, ldw >= max(n, 1), ANY element alignment; U is conjugated for complex types; W may alias or contain U.
+ * G: p x q, column-major with ldg >= p, in device memory, of the WIDE type (double for real types, complex double for complex
+ * ones).  work: bsm_block_gram_work(dtype, n, p, q) bytes of device memory, 16-byte aligned.  Two launches.  Launch 1:
+ * bsm_block_gram_grid(dtype, n) workgroups (one per 8192 bytes of a column, at most 256, at least 1), each owns one row range,
+ * stages chunks of its rows through LDS with coalesced loads and feeds v_mfma_{f64,f32}_16x16x4 with the rows as the K
+ * dimension, 16 columns of U by 16 of W per tile -- complex types as four real products of split real and imaginary parts --
+ * and leaves ONE partial p x q matrix in the precision of dtype (a chunk of rows is one chain of MFMAs in that precision; the
+ * chunks' sums are added in double in registers and rounded once).  Launch 2 adds the partials in a fixed order in double.  No
+ * floating-point atomic, nobody waits: the result is fixed to the bit run to run.  U and W are each read once from memory
+ * (columns of U that W contains are read twice).
+ * Refused (BSM_ERR_INVALID): a dtype that is no vector type; n < 0; p or q out of range; ldu or ldw < max(n, 1); ldg < p; a null
+ * G or work (U, W with n > 0); a work that is not 16-byte aligned; G or work overlapping U, W or each other.  n == 0 is legal:
+ * G = 0.
+ *
+ * bsm_block_combine:  Out[:, c] = sum_{j < p} V[:, j] C[j, c] for c < q, with C of dtype ITSELF -- complex for complex types --,
+ * p x q column-major in device memory, ldc >= p.  1 <= p <= 48, 0 <= q <= p.  V: n x p, Out: n x q, ldv, ldo >= max(n, 1), any
+ * element alignment.  Out == V with ldo == ldv works IN PLACE on columns 0 .. q - 1 (a tile of rows goes through LDS, all reads
+ * of a tile in front of the barrier).  The sum runs over j ascending with fused multiply-adds -- a complex term as
+ * re = fma(vr, cr, re), re = fma(-vi, ci, re), im = fma(vr, ci, im), im = fma(vi, cr, im), 2 p fmas per part --: the result is
+ * fixed to the bit and independent of the launch geometry.  Real types run the kernel of bsm_krylov_combine.
+ * bsm_block_combine_tile(dtype, p): the rows (elements) of the tile: bsm_krylov_combine_tile for real types,
+ * min(512, floor(131072 / (p * sizeof(element)) / 64) * 64) for complex ones.
+ * Refused (BSM_ERR_INVALID): those of bsm_krylov_combine without the carry: a dtype that is no vector type; n < 0; p outside
+ * 1 .. 48; q outside 0 .. p; ldv or ldo < max(n, 1); ldc < p; a null pointer that is needed (C with q > 0; V, Out with n > 0); Out
+ * overlapping V other than Out == V with ldo == ldv; C overlapping Out. */
+int64_t bsm_block_gram_grid(int dtype, int64_t n);
+int64_t bsm_block_gram_work(int dtype, int64_t n, int64_t p, int64_t q);
+int bsm_block_gram(int dtype, int64_t n, int64_t p, const void *U, int64_t ldu, int64_t q, const void *W, int64_t ldw, void *G,
+                   int64_t ldg, void *work, void *stream);
+int64_t bsm_block_combine_tile(int dtype, int64_t p);
+int bsm_block_combine(int dtype, int64_t n, int64_t p, int64_t q, const void *V, int64_t ldv, const void *C, int64_t ldc, void *Out,
+                      int64_t ldo, void *stream);
+
+/* bsm_lobpcg_*: the `nev` smallest (BSM_EIGSH_SA) or largest (BSM_EIGSH_LA) EIGENPAIRS of op(A), A asserted real symmetric /
+ * complex Hermitian by the caller, by LOBPCG (Knyazev) on a block of `block` vectors with an optional preconditioner M, which
+ * the caller asserts to be Hermitian positive definite, ~ inv(A) on the wanted end.  A block method sees every copy of a
+ * multiple eigenvalue, streams A once per iteration for the whole block (bsm_mul_multi), and takes the preconditioners the
+ * linear solvers take.  (No counterpart in the reference.)
+ *   Write k = block, p = 3 k, eps that of vdtype, tau = 64 p eps.  The workspace holds Z = [S | AS], S = [X | P | W],
+ *   AS = [AX | AP | AW], 6 k columns (and T, k columns, with M).
+ *   Start.  Z = 0; X = X0; AX = op(A) X (one bsm_mul_multi); the Gram matrix below, one copy, one synchronisation; the
+ *   Rayleigh-Ritz step on X alone; the combination below.
+ *   Iteration i (X_i the block it starts with):
+ *     1. R[:, c] = AX[:, c] - theta_c X[:, c] into W (with M: into T) on a (row ranges, k) grid; one partial of ||R_c||^2 per
+ *        workgroup and column, added by one wave per column in a fixed order: the CARRIED residual norms of X_i.
+ *     2. with M:  W = op(M) T (bsm_mul_multi).      3. AW = op(A) W (bsm_mul_multi), straight into the workspace.
+ *     4. ONE bsm_block_gram with U = S (p columns) and W = Z:  [G_B | G_A] = [S^H S | S^H AS].
+ *     5. ONE device-to-host copy (G, the k norms) and one synchronisation.
+ *     6. anorm = the largest |Ritz value| of any projected problem so far.  Column c is LIVE while ||R_c|| > max(rtol anorm,
+ *        atol).  The block has CONVERGED when the first nev columns (in the order of `which`) are not live.
+ *     7. Rayleigh-Ritz on the host, in double / complex double (csrc/bsm_lobpcg.h), deterministic.  Basis columns in use: X,
+ *        the W columns of live columns, the P columns of the columns whose W the previous iteration used (none in the first):
+ *        soft locking on the host only, the device always works on 3 k columns.  G_A, G_B are symmetrised and scaled by
+ *        d_i = 1 / sqrt(G_B[i, i]); the scaled G_B = Q Lambda Q^H by a cyclic Hermitian Jacobi method with a fixed sweep order;
+ *        directions with lambda <= tau lambda_max are dropped (counted in info.drops); L = Q_kept Lambda^{-1/2};
+ *        L^H G_A L = Z Mu Z^H by the same method; the k extreme Ritz values of `which` are theta, C = diag(d) L Z_sel (p x k,
+ *        zero rows for columns not in use), C_P = C with its X rows zeroed.
+ *     8. CC = [C | C_P] and theta are uploaded.     9. [X | P] = S CC and [AX | AP] = AS CC by two in-place bsm_block_combine.
+ *   Every iteration runs all nine steps.  The one that found the block converged (or was number maxiter) is followed by step 1
+ *   alone and a copy of the k norms: the carried norms of the X it left.  If they confirm the convergence the solve ends with
+ *   status 0 -- status 0 therefore means that the carried residuals of the RETURNED pairs are within the tolerance --,
+ *   otherwise (and below maxiter) it goes on with step 2.  Hence ONE synchronisation per iteration, one more per confirmation,
+ *   a_products = iterations + 2 multi-column products (start, one per iteration, the true-residual pass), m_products =
+ *   iterations, and a history of iterations + 1 rows.
+ *   End.  X[:, :nev], every column scaled to norm one, goes to the caller's matrix; then the TRUE residuals
+ *   ||op(A) x_i - theta_i x_i|| as in bsm_eigsh_solve.  AX is never recomputed: the true residual reports what the drift left.
+ * create: vdtype must be A's own vector type, as for bsm_eigsh_create; 1 <= nev <= block <= BSM_CG_MAX_RHS = 16, 3 block <= n.
+ *   M (may be NULL) with opM: paired with vdtype as for bsm_cg_create (its own vector type, or real and unmixed of the same
+ *   precision under a complex vdtype); a composed handle (bsm_poly_create) is accepted as M, not as A.  ONE device allocation,
+ *   leading dimensions rounded up to whole 16-byte groups: Z, T, the partials of the Gram, G (p x 2 p wide) with the norms, CC,
+ *   theta, the partials of the residual pass.  Refused: those of bsm_eigsh_create for A, those of bsm_cg_create for M (another
+ *   order, a bad pairing, multi-device, analysis-only, own-range, another device), nev or block out of range (BSM_ERR_INVALID).
+ *   Both handles must outlive the solver.
+ * solve: X0 (n x block, ldx0 >= max(n, 1)) and X (n x nev, ldx >= max(n, 1)), column-major, any element alignment;
+ *   BSM_MEM_HOST operands are staged through device buffers the solver keeps.  pairs: nev entries of bsm_eigsh_pair in the order
+ *   of `which`: value, estimate = the carried residual norm, residual = the true one.  history (may be NULL with capacity 0):
+ *   row r < history_capacity takes the nev carried norms of X_r, history[r * nev + c].  Synchronous.
+ *   info.status:  0 converged;  1 maxiter reached (X and pairs hold the pairs as they stand; nconv counts those within the
+ *   tolerance);  2 a norm, a Gram entry or a Ritz value is not finite, or Jacobi hit its sweep cap (X is not written, pairs are
+ *   NaN);  3 fewer than `block` directions kept: a rank-deficient or zero X0 at the start, or a G_B[i, i] that is not positive
+ *   (X is not written, pairs are NaN).
+ *   Refused (BSM_ERR_INVALID): null S, p, info, pairs, X0, X; a struct_size mismatch; a bad memspace; a `which` other than
+ *   BSM_EIGSH_SA / _LA; rtol or atol negative or NaN; maxiter < 1; ldx or ldx0 < max(n, 1); X overlapping X0; a negative
+ *   history_capacity, or a positive one without an array; a stream that is being captured.
+ *   Run to run, the values, X, the counts and the history are bit-identical wherever the products of the handles are.
+ * Not in it: the generalised problem, hard locking, a periodic recompute of AX, interior eigenvalues, block > 16, multi-device or
+ *   own-range handles, graph capture of a solve, the small eigenproblem on the device. */
+typedef struct {
+    int32_t struct_size; /* = sizeof(bsm_lobpcg_params) */
+    int32_t which;       /* BSM_EIGSH_SA or BSM_EIGSH_LA */
+    double rtol, atol;   /* carried residual <= max(rtol anorm, atol) */
+    int32_t maxiter;
+    int32_t reserved;
+} bsm_lobpcg_params;
+typedef struct {
+    int32_t status, nconv, iterations, drops;
+    int64_t a_products, m_products;
+    double anorm;
+    int64_t workspace_bytes;
+} bsm_lobpcg_info;
+BSM_LAYOUT_ASSERT(sizeof(bsm_lobpcg_params) == 32 && offsetof(bsm_lobpcg_params, rtol) == 8 && offsetof(bsm_lobpcg_params, maxiter) == 24,
+                  "bsm_lobpcg_params layout");
+BSM_LAYOUT_ASSERT(sizeof(bsm_lobpcg_info) == 48 && offsetof(bsm_lobpcg_info, a_products) == 16 && offsetof(bsm_lobpcg_info, anorm) == 32,
+                  "bsm_lobpcg_info layout");
+struct bsm_lobpcg_s;
+int bsm_lobpcg_create(bsm_matrix_t A, int opA, bsm_matrix_t M /* may be NULL */, int opM, int vdtype, int32_t nev, int32_t block,
+                      struct bsm_lobpcg_s **out);
+int bsm_lobpcg_solve(struct bsm_lobpcg_s *S, const void *X0, int64_t ldx0, void *X, int64_t ldx, const bsm_lobpcg_params *p,
+                     bsm_lobpcg_info *info, bsm_eigsh_pair *pairs /* nev */, double *history, int64_t history_capacity, int memspace,
+                     void *stream);
+int bsm_lobpcg_destroy(struct bsm_lobpcg_s *S);
+
 /* Statistics of a handle. */
 typedef struct {
     int64_t nnz;            /* SparseArrays.nnz as the reference defines it (off-diagonal

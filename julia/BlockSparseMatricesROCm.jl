@@ -892,6 +892,89 @@ end
 krylov_combine_tile(::Type{T}, m::Integer) where {T<:ROCmEltype} =
     ccall((:bsm_krylov_combine_tile, libbsm), Int64, (Cint, Int64), _DTYPE[T], m)
 
+# ---- LOBPCG (bsm_lobpcg_*) and the two tall-skinny products of a block method (bsm_block_gram, bsm_block_combine) --------
+mutable struct BsmLobpcgParams      # mirrors bsm_lobpcg_params (32 bytes)
+    struct_size::Int32; which::Int32; rtol::Float64; atol::Float64; maxiter::Int32; reserved::Int32
+end
+mutable struct BsmLobpcgInfo        # mirrors bsm_lobpcg_info (48 bytes)
+    status::Int32; nconv::Int32; iterations::Int32; drops::Int32
+    a_products::Int64; m_products::Int64; anorm::Float64; workspace_bytes::Int64
+end
+
+"""
+    lobpcg!(X, A, X0; M=nothing, which=:SA, rtol=1e-10, atol=0.0, maxiter=200) -> (w, X, info, pairs, history)
+
+The `nev = size(X, 2)` smallest (`:SA`) or largest (`:LA`) eigenpairs of a real symmetric / Hermitian `A` by LOBPCG on the
+block `X0` (`size(A, 1) x block`, `nev <= block <= 16`, `3 block <= size(A, 1)`), with an optional preconditioner `M` --
+Hermitian positive definite, `~ inv(A)` on the wanted end: a block-Jacobi or a polynomial handle --, on the device
+(bsm_lobpcg_create / _solve / _destroy).  The caller asserts both.  A block method finds every copy of a multiple eigenvalue;
+`A` is streamed once per iteration for the whole block.  `X0` and `X` are host matrices of `A`'s element type.  Converged when
+the carried residual norms of the first `nev` columns are `<= max(rtol * anorm, atol)`.  `info.status`: 0 converged, 1
+`maxiter` reached, 2 a non-finite norm, Gram entry or Ritz value, 3 fewer than `block` directions kept (a rank-deficient
+`X0`).  `w` holds the eigenvalues in the order of `which`, `pairs[i]` value, carried and true residual, `history` the carried
+norms as `nev x (iterations + 1)`.  Per iteration the host synchronises once and runs a Rayleigh-Ritz step of order up to
+`3 block`.
+"""
+function lobpcg!(X::Matrix{T}, A::ROCmAnyOp, X0::Matrix{T}; M=nothing, which::Symbol=:SA, rtol::Real=1e-10, atol::Real=0.0,
+                 maxiter::Integer=200) where {T<:ROCmEltype}
+    n, nev, block = size(X, 1), size(X, 2), size(X0, 2)
+    size(A, 1) == size(A, 2) == n == size(X0, 1) || throw(DimensionMismatch("lobpcg! needs a square operator and X0, X of its order"))
+    which in (:SA, :LA) || throw(ArgumentError("which must be :SA or :LA"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    mptr = M === nothing ? C_NULL : handle(_base(M)).ptr
+    _check(ccall((:bsm_lobpcg_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), mptr, M === nothing ? 0 : _op(M), _DTYPE[T], nev, block, out))
+    p = BsmLobpcgParams(sizeof(BsmLobpcgParams), _EIGSH_WHICH[which], rtol, atol, maxiter, 0)
+    info = BsmLobpcgInfo(0, 0, 0, 0, 0, 0, 0.0, 0)
+    pairs = Vector{BsmEigshPair}(undef, nev)
+    history = fill(NaN, nev, maxiter + 1)
+    try
+        GC.@preserve A M X X0 pairs history _check(ccall((:bsm_lobpcg_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{BsmLobpcgParams}, Ref{BsmLobpcgInfo}, Ptr{BsmEigshPair}, Ptr{Float64}, Int64, Cint, Ptr{Cvoid}),
+            out[], pointer(X0), max(n, 1), pointer(X), max(n, 1), p, info, pairs, history, maxiter + 1, 0, C_NULL))
+    finally
+        ccall((:bsm_lobpcg_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return [pairs[i].value for i in 1:nev], X, info, pairs, history[:, 1:(info.status <= 1 ? info.iterations + 1 : 0)]
+end
+
+"""
+    block_gram!(G, U, W, work, T, n, p, q; ldu=max(n, 1), ldw=max(n, 1), ldg=p, stream=C_NULL)
+
+`G = U' W` on the device (bsm_block_gram): `U` `n x p` (`p <= 48`), `W` `n x q` (`q <= 96`) of element type `T`, `G` `p x q` of
+the WIDE type (`Float64` / `ComplexF64`), `work` `block_gram_work(T, n, p, q)` bytes, 16-byte aligned; all DEVICE pointers,
+column-major.  `W` may alias or contain `U`.  Partial sums per row range on the matrix pipe in the precision of `T`, added in a
+fixed order in double.  Enqueues on `stream`; synchronises nothing.  `block_gram_grid(T, n)` is the number of row ranges.
+"""
+function block_gram!(G::Ptr{Cvoid}, U::Ptr{Cvoid}, W::Ptr{Cvoid}, work::Ptr{Cvoid}, ::Type{T}, n::Integer, p::Integer, q::Integer;
+                     ldu::Integer=max(n, 1), ldw::Integer=max(n, 1), ldg::Integer=p, stream::Ptr{Cvoid}=C_NULL) where {T<:ROCmEltype}
+    _check(ccall((:bsm_block_gram, libbsm), Cint,
+        (Cint, Int64, Int64, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+        _DTYPE[T], n, p, U, ldu, q, W, ldw, G, ldg, work, stream))
+    return G
+end
+block_gram_grid(::Type{T}, n::Integer) where {T<:ROCmEltype} = ccall((:bsm_block_gram_grid, libbsm), Int64, (Cint, Int64), _DTYPE[T], n)
+block_gram_work(::Type{T}, n::Integer, p::Integer, q::Integer) where {T<:ROCmEltype} =
+    ccall((:bsm_block_gram_work, libbsm), Int64, (Cint, Int64, Int64, Int64), _DTYPE[T], n, p, q)
+
+"""
+    block_combine!(Out, V, C, T, n, p, q; ldv=max(n, 1), ldc=p, ldo=max(n, 1), stream=C_NULL)
+
+`Out[:, c] = sum_j V[:, j] C[j, c]` for `c <= q` on the device (bsm_block_combine) with `C` of element type `T` itself --
+complex for complex `T` --, the sum over `j` ascending with fused multiply-adds.  `Out`, `V`, `C` are DEVICE pointers: `V`
+`n x p` (`p <= 48`), `C` `p x q` (`q <= p`), column-major.  `Out == V` with `ldo == ldv` works in place.  Enqueues on `stream`;
+synchronises nothing.  `block_combine_tile(T, p)` is the number of rows one workgroup stages.
+"""
+function block_combine!(Out::Ptr{Cvoid}, V::Ptr{Cvoid}, C::Ptr{Cvoid}, ::Type{T}, n::Integer, p::Integer, q::Integer;
+                        ldv::Integer=max(n, 1), ldc::Integer=p, ldo::Integer=max(n, 1), stream::Ptr{Cvoid}=C_NULL) where {T<:ROCmEltype}
+    _check(ccall((:bsm_block_combine, libbsm), Cint,
+        (Cint, Int64, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+        _DTYPE[T], n, p, q, V, ldv, C, ldc, Out, ldo, stream))
+    return Out
+end
+block_combine_tile(::Type{T}, p::Integer) where {T<:ROCmEltype} =
+    ccall((:bsm_block_combine_tile, libbsm), Int64, (Cint, Int64), _DTYPE[T], p)
+
 # ---- polynomial preconditioners as handles (bsm_poly_*) -----------------------------------------------------------------
 """
     PolynomialPreconditioner
