@@ -12,6 +12,7 @@ from .entries import *  # noqa: F401,F403
 from .matrices import *  # noqa: F401,F403
 from .solvers import *  # noqa: F401,F403
 from .solvers import Lsqr, LsqrInfo, Minres, lsqr, minres  # noqa: F401
+from .solvers import eigh_blocks, spectral_blocks  # noqa: F401
 from .solvers import (PolynomialPreconditioner, chebyshev, chebyshev_coefficients, lanczos_bounds, neumann,  # noqa: F401
                       polynomial)
 from .solvers import Eigsh, EigshInfo, eigsh, krylov_combine, krylov_combine_tile  # noqa: F401

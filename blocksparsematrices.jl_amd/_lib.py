@@ -20,6 +20,9 @@ BSM_DEVICE_CURRENT, BSM_DEVICE_NONE = -1, -2
 BSM_COLOR_WORKSTREAM_DSATUR, BSM_COLOR_DSATUR = 0, 1
 # bsm_invert_blocks: largest n * n * sizeof(T) eliminated in LDS, largest order it takes (include/bsm_rocm.h)
 BSM_INVERT_LDS_BYTES, BSM_INVERT_MAX_N = 131072, 1024
+# bsm_eigh_blocks: largest 2 * n * n * sizeof(T) kept in LDS, largest order, the sweep cap; bsm_spectral_blocks' func
+BSM_EIGH_LDS_BYTES, BSM_EIGH_MAX_N, BSM_EIGH_MAX_SWEEPS = 131072, 512, 60
+BSM_SPEC_VALUES, BSM_SPEC_INV, BSM_SPEC_ABSINV, BSM_SPEC_PINV = 0, 1, 2, 3
 BSM_GMRES_MAX_RESTART = 128  # bsm_gmres_create's restart, bsm_krylov_orth's k (include/bsm_rocm.h)
 BSM_CG_MAX_RHS = 16  # bsm_cg_create's nrhs_max (include/bsm_rocm.h)
 BSM_CG_METHOD_CG, BSM_CG_METHOD_COCG = 0, 1
@@ -122,7 +125,7 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_mul_cvec", "bsm_mul_multi_cvec", "bsm_get_bookkeeping", "bsm_get_image", "bsm_stats",
            "bsm_color", "bsm_destroy", "bsm_last_error", "bsm_version",
            "bsm_vec_add_segments", "bsm_stream_create_reserved", "bsm_stream_destroy", "bsm_update_blocks", "bsm_value_passes",
-           "bsm_submatrices", "bsm_diag", "bsm_invert_blocks",
+           "bsm_submatrices", "bsm_diag", "bsm_invert_blocks", "bsm_eigh_blocks", "bsm_spectral_blocks",
            "bsm_krylov_orth_work", "bsm_krylov_orth", "bsm_gmres_create", "bsm_gmres_solve",
            "bsm_gmres_destroy", "bsm_cg_create", "bsm_cg_solve", "bsm_cg_destroy", "bsm_bicgstab_create", "bsm_bicgstab_solve",
            "bsm_bicgstab_destroy", "bsm_gmres_multi_create", "bsm_gmres_multi_solve", "bsm_gmres_multi_destroy",
@@ -231,6 +234,11 @@ def lib():
     if hasattr(L, "bsm_invert_blocks") or "BSM_LIB" not in os.environ:
         L.bsm_invert_blocks.argtypes = [C.c_int, C.c_int64, _PP, _I64P, _I64P, _I64P, C.c_int, C.c_void_p]
         L.bsm_invert_blocks.restype = C.c_int
+    if hasattr(L, "bsm_eigh_blocks") or "BSM_LIB" not in os.environ:  # (developer A/B builds may predate them)
+        L.bsm_eigh_blocks.argtypes = [C.c_int, C.c_int64, _PP, _I64P, _I64P, _PP, C.c_int32, _I64P, _I32P, C.c_int, C.c_void_p]
+        # bsm_spectral_blocks takes a double BY VALUE: it keeps argtypes = None (the static mirror check of the suite classes
+        # integers and pointers only) and is called through spectral_blocks_call below, which converts every argument itself
+        L.bsm_eigh_blocks.restype = L.bsm_spectral_blocks.restype = C.c_int
     if hasattr(L, "bsm_gmres_create") or "BSM_LIB" not in os.environ:
         L.bsm_krylov_orth_work.argtypes = [C.c_int, C.c_int64, C.c_int64]
         L.bsm_krylov_orth_work.restype = C.c_int64
@@ -317,6 +325,13 @@ def lib():
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
+
+
+def spectral_blocks_call(dtype, nblocks, V, n, ldv, w, func, rcond, out, ldo, info, memspace, stream):
+    """bsm_spectral_blocks with every argument converted here (lib(): why it has no argtypes).  V, w, out: void* arrays; n,
+    ldv, ldo, info: int64 pointers (info may be None)"""
+    return lib().bsm_spectral_blocks(C.c_int(dtype), C.c_int64(nblocks), V, n, ldv, w, C.c_int32(func), C.c_double(rcond), out, ldo,
+                                     info, C.c_int(memspace), C.c_void_p(stream))
 
 
 def check(rc):

@@ -1,4 +1,4 @@
-"""The block-Jacobi preconditioner (invert_blocks, BlockJacobi, block_jacobi) and the Krylov solvers that run every step
+"""The block-Jacobi preconditioner (invert_blocks, eigh_blocks, spectral_blocks, BlockJacobi, block_jacobi) and the Krylov solvers that run every step
 on the device: the Gram-Schmidt pass krylov_orth, Gmres, and the lockstep solvers Cg, BiCgStab, Minres, GmresMulti, Lsqr with
 their one-shot forms.  The solver objects share _Solver: the create and destroy calls and the prelude of solve()."""
 import contextlib
@@ -17,16 +17,13 @@ __all__ = ["invert_blocks", "BlockJacobi", "block_jacobi", "Gmres", "GmresInfo",
 
 
 # ---- block-Jacobi: the self-interaction blocks inverted where they are (bsm_invert_blocks) -----------------------------
-def invert_blocks(blocks):
-    """Inverts square column-major blocks IN PLACE (bsm_invert_blocks: Gauss-Jordan with partial row pivoting, one
-    workgroup per block on the device, the same elimination serially for host blocks) -> info, one int64 per block:
-    0, or the 1-based step whose pivot was zero or not finite (that block is then unspecified).  blocks: numpy arrays
-    (Fortran order) or torch CUDA tensors (column-major, e.g. what submatrices(..., device=True) returns) of ONE
-    element type and device, orders 0 .. 1024.  Device blocks go on torch's current stream; the call is synchronous."""
+def _square_blocks(blocks):
+    """the operand rules of invert_blocks / eigh_blocks: square blocks of ONE element type and device, worked on where they
+    are -> _BlockList with the pointers of empty blocks NULL"""
     blocks = list(blocks)
     if _is_dev(blocks):
         kind = _blocks_kind(blocks)
-    else:  # host blocks are inverted where they are: none may need a conversion
+    else:  # host blocks are worked on where they are: none may need a conversion
         dt = None
         for b in blocks:
             if not (isinstance(b, np.ndarray) and b.ndim == 2 and b.dtype in _DT and b.flags.f_contiguous and b.flags.writeable):
@@ -39,25 +36,118 @@ def invert_blocks(blocks):
     bad = np.nonzero(bl.m != bl.n)[0]
     if len(bad):
         raise ValueError(f"a block of shape {tuple(blocks[bad[0]].shape)} is not square")
+    for k in np.nonzero(bl.m == 0)[0]:
+        bl.ptrs[k] = None
+    return bl
+
+
+def invert_blocks(blocks):
+    """Inverts square column-major blocks IN PLACE (bsm_invert_blocks: Gauss-Jordan with partial row pivoting, one
+    workgroup per block on the device, the same elimination serially for host blocks) -> info, one int64 per block:
+    0, or the 1-based step whose pivot was zero or not finite (that block is then unspecified).  blocks: numpy arrays
+    (Fortran order) or torch CUDA tensors (column-major, e.g. what submatrices(..., device=True) returns) of ONE
+    element type and device, orders 0 .. 1024.  Device blocks go on torch's current stream; the call is synchronous."""
+    bl = _square_blocks(blocks)
     info = np.zeros(max(len(bl), 1), dtype=np.int64)
     if len(bl) == 0:
         return info[:0]
-    for k in np.nonzero(bl.m == 0)[0]:
-        bl.ptrs[k] = None
-    st = _stream_ptr(None, blocks[0].device) if bl.dev else None
+    st = _stream_ptr(None, bl.blocks[0].device) if bl.dev else None
     L.check(L.lib().bsm_invert_blocks(_DT[bl.dtype], *bl.square_args(), _p64(info), bl.memspace, st))
     return info
 
 
-def _inverted_blocks(A, sets, stream=None):
-    """[inv(A[I_s, I_s]) for s]: extracted where the image lives and inverted there (device tensors on the handle's first
-    device, numpy arrays for an analysis-only handle)"""
+# ---- spectral forms of the blocks: eigh_blocks, spectral_blocks (bsm_eigh_blocks, bsm_spectral_blocks) ------------------
+_SPEC = {"values": L.BSM_SPEC_VALUES, "inv": L.BSM_SPEC_INV, "absinv": L.BSM_SPEC_ABSINV, "pinv": L.BSM_SPEC_PINV}
+
+
+def _real_of(dt):
+    return np.dtype(np.float32) if np.dtype(dt) in (np.dtype(np.float32), np.dtype(np.complex64)) else np.dtype(np.float64)
+
+
+def _value_ptrs(ws, bl):
+    """the addresses of the eigenvalue arrays of the blocks of bl (NULL for an empty block), each checked: n reals of the
+    blocks' precision, contiguous, where the blocks live"""
+    real = _real_of(bl.dtype)
+    out = (C.c_void_p * max(len(bl), 1))()
+    if len(ws) != len(bl):
+        raise ValueError(f"{len(ws)} eigenvalue arrays for {len(bl)} blocks")
+    for k, (w, n) in enumerate(zip(ws, bl.m)):
+        if bl.dev:
+            ok = _is_tensor(w) and w.is_cuda and w.device == bl.blocks[k].device and w.dim() == 1 and w.numel() == n and \
+                w.dtype == _TORCH_OF[real] and w.is_contiguous()
+        else:
+            ok = isinstance(w, np.ndarray) and w.ndim == 1 and w.shape[0] == n and w.dtype == real and w.flags.c_contiguous
+        if not ok:
+            raise TypeError(f"w[{k}] must be a contiguous 1-D {real} array of {int(n)} entries where the blocks live")
+        out[k] = None if n == 0 else (w.data_ptr() if bl.dev else w.ctypes.data)
+    return out
+
+
+def eigh_blocks(blocks, vectors=True, *, sweeps=False):
+    """Eigendecomposition of square HERMITIAN column-major blocks IN PLACE (bsm_eigh_blocks: two-sided round-robin Jacobi in
+    the blocks' own type, one workgroup per block on the device, the same rotations serially for host blocks) -> (w, info):
+    w[b] the eigenvalues of (B_b + B_b^H) / 2 ascending -- 1-D real arrays, views of one flat numpy array or of one flat
+    tensor on the blocks' device --, block b its orthonormal eigenvectors as columns (vectors=False: unspecified contents);
+    info[b] = 0, 1 (a non-finite entry: the block is untouched, w[b] is NaN) or 2 (the cap of 60 sweeps was hit).  The
+    operand rules are those of invert_blocks, orders 0 .. 512.  sweeps=True: -> (w, info, sweeps taken per block)."""
+    bl = _square_blocks(blocks)
+    real = _real_of(bl.dtype)
+    info = np.zeros(max(len(bl), 1), dtype=np.int64)
+    nsw = np.zeros(max(len(bl), 1), dtype=np.int32)
+    off = np.concatenate(([0], np.cumsum(bl.m))).astype(np.int64)
+    if bl.dev:
+        flat = torch.empty(int(off[-1]), dtype=_TORCH_OF[real], device=bl.blocks[0].device)
+    else:
+        flat = np.empty(int(off[-1]), dtype=real)
+    w = [flat[int(off[k]):int(off[k + 1])] for k in range(len(bl))]
+    if len(bl):
+        st = _stream_ptr(None, bl.blocks[0].device) if bl.dev else None
+        L.check(L.lib().bsm_eigh_blocks(_DT[bl.dtype], *bl.square_args(), _value_ptrs(w, bl), 1 if vectors else 0, _p64(info),
+                                        nsw.ctypes.data_as(C.POINTER(C.c_int32)), bl.memspace, st))
+    info, nsw = info[:len(bl)], nsw[:len(bl)]
+    return (w, info, nsw) if sweeps else (w, info)
+
+
+def spectral_blocks(V, w, func="inv", rcond=0.0, out=None):
+    """out[b] = V[b] diag(f(w[b])) V[b]^H (bsm_spectral_blocks) -> (out, info).  func: "values" (f = w), "inv" (1 / w), "absinv"
+    (1 / max(|w|, rcond * max|w|): positive definite) or "pinv" (1 / w where |w| > rcond * max|w|, else 0).  V: square
+    column-major blocks as eigh_blocks leaves them, w: its eigenvalue arrays; out: None (fresh blocks like V) or blocks of the
+    same kind that overlap neither V nor w.  Hermitian to the bit.  info[b] = 0, or the 1-based index of the first eigenvalue
+    at which f is undefined (out[b] is then not written)."""
+    if func not in _SPEC:
+        raise ValueError(f"func={func!r}: one of {sorted(_SPEC)}")
+    bl = _square_blocks(V)
+    if out is None:
+        if bl.dev:
+            out = [torch.empty((int(n), int(n)), dtype=b.dtype, device=b.device).t() for b, n in zip(bl.blocks, bl.m)]
+        else:
+            out = [np.empty((int(n), int(n)), dtype=bl.dtype, order="F") for n in bl.m]
+    ol = _square_blocks(out)
+    if (ol.dtype, ol.dev) != (bl.dtype, bl.dev) or len(ol) != len(bl) or np.any(ol.m != bl.m):
+        raise ValueError("out must hold blocks of the orders, element type and memory space of V")
+    info = np.zeros(max(len(bl), 1), dtype=np.int64)
+    if len(bl):
+        st = _stream_ptr(None, bl.blocks[0].device) if bl.dev else None
+        L.check(L.spectral_blocks_call(_DT[bl.dtype], len(bl), bl.ptrs, _p64(bl.m), _p64(bl.ld), _value_ptrs(list(w), bl), _SPEC[func],
+                                       float(rcond), ol.ptrs, _p64(ol.ld), _p64(info), bl.memspace, st))
+    return list(out), info[:len(bl)]
+
+
+def _block_stream(A, stream):
+    """-> (whether A's image lives on a device, the context in which submatrices and the block calls take `stream`)"""
     base, _ = _unwrap(A)
     on_dev = base.device is not None or base.devices is not None
     ctx = contextlib.nullcontext()
     if on_dev and stream is not None:
         st = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(stream)
-        ctx = torch.cuda.stream(st)  # submatrices and invert_blocks both take torch's current stream
+        ctx = torch.cuda.stream(st)  # submatrices and the block calls all take torch's current stream
+    return on_dev, ctx
+
+
+def _inverted_blocks(A, sets, stream=None):
+    """[inv(A[I_s, I_s]) for s]: extracted where the image lives and inverted there (device tensors on the handle's first
+    device, numpy arrays for an analysis-only handle)"""
+    on_dev, ctx = _block_stream(A, stream)
     with ctx:
         blocks = submatrices(A, sets, device=on_dev)
         info = invert_blocks(blocks)
@@ -68,14 +158,57 @@ def _inverted_blocks(A, sets, stream=None):
     return blocks
 
 
+def _spectral_jacobi_blocks(A, sets, kind, rcond, stream=None):
+    """([V_s f(w_s) V_s^H for s], [w_s for s]) of A[I_s, I_s] = V_s diag(w_s) V_s^H, f = 1 / |w| (kind "abs") or the pseudo-
+    inverse (kind "pinv"): extracted, decomposed and put together where the image lives"""
+    on_dev, ctx = _block_stream(A, stream)
+    with ctx:
+        blocks = submatrices(A, sets, device=on_dev)
+        w, info = eigh_blocks(blocks)
+        bad = np.nonzero(info)[0]
+        if len(bad):
+            why = "holds an entry that is not finite" if info[bad[0]] == 1 else "did not converge in the sweep cap of the Jacobi method"
+            raise np.linalg.LinAlgError(f"block_jacobi: A[I, I] of set {int(bad[0]) + 1} {why}")
+        if kind == "abs" and rcond == 0 and len(w):
+            # an eigenvalue the decomposition cannot tell from zero counts as zero: eigh_blocks leaves an exact zero within
+            # 4 n eps ||A_ss||_F <= 4 n^1.5 eps max|w| (the accuracy its suite holds it to), and 1 / |w| of such a value is noise
+            flat = (torch.cat(w).cpu().numpy() if _is_tensor(w[0]) else np.concatenate(w)).astype(np.float64)
+            at, eps = 0, float(np.finfo(_real_of(blocks[0].cpu().numpy().dtype if _is_tensor(blocks[0]) else blocks[0].dtype)).eps)
+            for s, ws in enumerate(w):
+                n = len(ws)
+                mag = np.abs(flat[at:at + n])
+                at += n
+                small = np.nonzero(mag <= 4 * n ** 1.5 * eps * np.max(mag, initial=0.0))[0] if np.all(np.isfinite(mag)) else []
+                if len(small):
+                    raise np.linalg.LinAlgError(f"block_jacobi: eigenvalue {int(small[0]) + 1} of A[I, I] of set {s + 1} is zero to working "
+                                                f"precision (kind='abs', rcond=0: pass rcond > 0 to clamp, or kind='pinv')")
+        out, info = spectral_blocks(blocks, w, "absinv" if kind == "abs" else "pinv", rcond)
+    bad = np.nonzero(info)[0]
+    if len(bad):
+        raise np.linalg.LinAlgError(f"block_jacobi: eigenvalue {int(info[bad[0]])} of A[I, I] of set {int(bad[0]) + 1} is zero or not finite "
+                                    f"(kind={kind!r}, rcond={rcond})")
+    return out, w
+
+
+_KINDS = ("inverse", "abs", "pinv")
+
+
 class BlockJacobi(BlockSparseMatrix):
     """M = sum_s E_s inv(A[I_s, I_s]) E_s^T -- the block-Jacobi (near-field) preconditioner of A as an ordinary
     BlockSparseMatrix handle: mul, M @ X, MulPlan, the wrappers, complex vectors under a real M and M[I, J] work as on
-    any other.  Built by block_jacobi(A, sets).  Fields beside BlockSparseMatrix's: `sets` (1-based index arrays) and
-    `source` (the A it was built from)."""
+    any other.  Built by block_jacobi(A, sets).  Fields beside BlockSparseMatrix's: `sets` (1-based index arrays),
+    `source` (the A it was built from), `kind` ("inverse", "abs" or "pinv": what stands in the place of inv), `rcond` (None
+    for "inverse") and `eigenvalues` (None for "inverse"; else the eigenvalues of every A[I_s, I_s] ascending, where the
+    blocks live: the inertia of the diagonal blocks)."""
 
-    def __init__(self, A, sets=None, *, storage=None, accumulate="auto", transpose_image=False):
+    def __init__(self, A, sets=None, *, kind="inverse", rcond=None, storage=None, accumulate="auto", transpose_image=False):
         base, _ = _operator(A)
+        if kind not in _KINDS:
+            raise ValueError(f"kind={kind!r}: one of {_KINDS}")
+        if kind == "inverse" and rcond is not None:
+            raise ValueError("rcond has no meaning with kind='inverse'")
+        if rcond is not None and not float(rcond) >= 0:
+            raise ValueError(f"rcond={rcond} is negative or NaN")
         if sets is None:
             if not isinstance(base, SymmetricBlockMatrix):
                 raise ValueError("sets=None means the diagonalindices of a SymmetricBlockMatrix; pass index sets for other types")
@@ -85,32 +218,56 @@ class BlockJacobi(BlockSparseMatrix):
             raise ValueError(f"block_jacobi needs a square operator, size(A) = {(m, n)}")
         self.sets = [_i64(np.asarray(s).reshape(-1)) for s in sets]
         self.source = A
-        blocks = _inverted_blocks(A, self.sets)
+        self.kind = kind
+        self.rcond = None if rcond is None else float(rcond)
+        blocks, self.eigenvalues = self._build(A)
         dev = L.BSM_DEVICE_NONE if base.device is None and base.devices is None else _out_device(base).index
         super().__init__(blocks, self.sets, self.sets, (m, n), device=dev, storage=storage, accumulate=accumulate,
                          transpose_image=transpose_image)
 
+    def _build(self, A, stream=None):
+        """-> (the blocks of M, the eigenvalues or None) from the present values of A, by `kind`"""
+        if self.kind == "inverse":
+            return _inverted_blocks(A, self.sets, stream), None
+        if self.rcond is None:  # (the blocks come in A's vector type: a mixed-storage A gives them widened)
+            self.rcond = 0.0 if self.kind == "abs" else float(np.sqrt(np.finfo(_real_of(_unwrap(A)[0].dtype)).eps))
+        return _spectral_jacobi_blocks(A, self.sets, self.kind, self.rcond, stream)
+
     def refresh(self, A=None, stream=None):
-        """Re-extracts the blocks of A (default: `source`, e.g. after update_blocks(A, ...)), inverts them and pushes them
-        into this handle with update_blocks: no analysis, no reallocation of the image, the tensors of `blocks` stay.  A
-        singular block raises LinAlgError and leaves M as it was; a `storage=` M raises what update_blocks raises."""
+        """Re-extracts the blocks of A (default: `source`, e.g. after update_blocks(A, ...)), rebuilds them by the same `kind`
+        and pushes them into this handle with update_blocks: no analysis, no reallocation of the image, the tensors of
+        `blocks` stay.  A block that raises LinAlgError leaves M (and `eigenvalues`) as it was; a `storage=` M raises what
+        update_blocks raises."""
         _no_mixed_update(self)
         A = self.source if A is None else A
         if size(A) != self.size:
             raise ValueError(f"size(A) = {size(A)} but the preconditioner is {self.size}")
-        update_blocks(self, _inverted_blocks(A, self.sets, stream), stream=stream)
-        self.source = A
+        blocks, w = self._build(A, stream)
+        update_blocks(self, blocks, stream=stream)
+        self.source, self.eigenvalues = A, w
 
 
-def block_jacobi(A, sets=None, *, storage=None, accumulate="auto", transpose_image=False):
+def block_jacobi(A, sets=None, *, kind="inverse", rcond=None, storage=None, accumulate="auto", transpose_image=False):
     """The block-Jacobi preconditioner of A over `sets` (1-based index lists, pairwise disjoint and free of repeats;
     None: the diagonalindices of a SymmetricBlockMatrix) -> BlockJacobi.  submatrices(A, sets, device=True), invert_blocks
     and the BlockSparseMatrix constructor from device tensors: no matrix byte crosses PCIe.  An analysis-only A takes
     the same route on the host and gives an analysis-only M; a multi-device A gives a single-device M on its first
     device; transpose(A) / adjoint(A) are taken as such; a mixed-storage A gives its stored values widened, inverted in
     the vector type (storage= here is that of M).  Rows in no set are zero rows of M -- pass singleton sets for
-    point-Jacobi rows.  A singular block raises numpy.linalg.LinAlgError naming the set and the elimination step."""
-    return BlockJacobi(A, sets, storage=storage, accumulate=accumulate, transpose_image=transpose_image)
+    point-Jacobi rows.  A singular block raises numpy.linalg.LinAlgError naming the set and the elimination step.
+
+    kind: what M holds for every set, with A[I_s, I_s] = V diag(w) V^H (the caller asserts that these blocks are Hermitian;
+    what is decomposed is (A_ss + A_ss^H) / 2 -- eigh_blocks, spectral_blocks in the place of invert_blocks):
+      "inverse"  the explicit inverse, as above (rcond must be None);
+      "abs"      V diag(1 / |w|) V^H: Hermitian POSITIVE DEFINITE for an indefinite A -- what Minres, Lobpcg and Cg ask of M --
+                 and the exact inverse wherever A_ss is definite.  rcond (default 0): |w| is clamped from below at rcond *
+                 max|w| of its block.  A zero or non-finite eigenvalue raises LinAlgError naming the set and the eigenvalue's
+                 index; with rcond > 0 finite data never raises;
+      "pinv"     the Hermitian pseudo-inverse: 1 / w where |w| > rcond * max|w|, else 0, for singular blocks (a floating sub-
+                 domain, a pure Neumann patch).  rcond defaults to sqrt(eps) of the type: a regularisation parameter, and a
+                 conservative one -- eigenvalues below it are treated as zero.  Never raises for finite data.
+    The eigenvalues stay in M.eigenvalues."""
+    return BlockJacobi(A, sets, kind=kind, rcond=rcond, storage=storage, accumulate=accumulate, transpose_image=transpose_image)
 
 
 # ---- restarted GMRES on the device (bsm_gmres_*) and its building block (bsm_krylov_orth) ------------------------------

@@ -530,6 +530,77 @@ int bsm_diag(bsm_matrix_t A, void *d, int memspace, void *stream);
 int bsm_invert_blocks(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld,
                       int64_t *info, int memspace, void *stream);
 
+/* Batched eigendecomposition of dense HERMITIAN blocks of different sizes, in place:
+ *   (B_b + B_b^H) / 2 = V_b diag(w_b) V_b^H,   B_b = blocks[b][i + j * ld[b]], i, j < n[b]       for b < nblocks
+ * -- what a spectral block-Jacobi preconditioner needs where the explicit inverse of bsm_invert_blocks does not serve: an
+ * indefinite A[I_s, I_s] (M_ss = V diag(1 / |w|) V^H is Hermitian positive definite, which MINRES, LOBPCG and CG ask of M) or
+ * a singular one (the pseudo-inverse); bsm_spectral_blocks puts such an M_ss together.  (No counterpart in the reference.)
+ *   Arguments: those of bsm_invert_blocks -- dtype BSM_F32 .. BSM_C128 (the mixed storage codes are BSM_ERR_INVALID); blocks,
+ *     n, ld, w, info and sweeps are HOST arrays; block b is column-major with ld[b] >= max(n[b], 1); n[b] == 0 is legal with a
+ *     NULL block; the blocks must not overlap.  w[b] points to n[b] entries of the REAL type of dtype (float for BSM_F32 /
+ *     BSM_C64, double for BSM_F64 / BSM_C128) in the memory space of the blocks.  n[b] > BSM_EIGH_MAX_N is BSM_ERR_UNSUPPORTED
+ *     (one workgroup decomposes one block).  info and sweeps may be NULL.
+ *   What is decomposed: H = (B + B^H) / 2 -- both triangles are read and symmetrised at load, the imaginary part of the
+ *     diagonal is dropped, so the rounding-level asymmetry of an extracted A[I_s, I_s] is harmless.
+ *   Result: w[b] holds the eigenvalues ascending, ties in the order of the diagonal positions they came from (a stable sort).
+ *     vectors != 0: block b holds the orthonormal eigenvectors as its columns, in that order.  vectors == 0: the contents of
+ *     the block are unspecified.
+ *   info[b] = 0 -- done;  1 -- block b holds an entry that is not finite: the block is untouched, w[b] is filled with NaN;
+ *     2 -- the sweep cap was hit: w, V hold the pairs as they stand, sorted.  The other blocks are unaffected and the call
+ *     returns BSM_OK in all three cases (LAPACK style).  sweeps[b]: the sweeps that rotated (BSM_EIGH_MAX_SWEEPS with info 2).
+ *   Algorithm (fixed, so that host and device run the same sequence of rotations): two-sided Jacobi in the block's own type
+ *     in a round-robin (tournament) order.  m = n rounded up to even; a sweep has m - 1 steps; step t = 0 .. m-2 holds the
+ *     m / 2 disjoint pairs (t, m-1) and ((t + k) mod (m-1), (t - k) mod (m-1)), k = 1 .. m/2 - 1, in each p = min, q = max; a
+ *     pair with q >= n (the padding index of an odd n) idles.  The rotation of a pair is that of the project's host-side
+ *     Jacobi solvers: with a_pq = g omega, g = |a_pq|, nothing is done if g == 0; the pair is skipped and a_pq = a_qp = 0 is
+ *     set when |a_pp| + g == |a_pp| and |a_qq| + g == |a_qq| in the working type; otherwise tau = (a_qq - a_pp) / (2 g),
+ *     t = sign(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c; columns: x = col_p, y = conj(omega) col_q,
+ *     col_p <- c x - s y, col_q <- s x + c y, for A and for V; rows: the same with omega; then a_pp <- a_pp - t g, a_qq <-
+ *     a_qq + t g, a_pq = a_qp = 0.  All pairs of a step derive their rotations first and rotate together: the column phase of
+ *     every pair, then the row phase of every pair -- J^H (A J) with J the product of the step's commuting rotations.  The
+ *     method ends with the first sweep that rotates nothing.  The order of w is a rank sort: rank_i = #{j : w_j < w_i or
+ *     (w_j == w_i and j < i)}.
+ *   memspace: where the blocks and the w[b] live.
+ *     BSM_MEM_DEVICE: pointers valid on the current device, or on the device of `stream` when one is given; the work is
+ *       enqueued on `stream`.  One 256-thread workgroup per block, the largest blocks first.  A block with 2 * n * n *
+ *       sizeof(T) <= BSM_EIGH_LDS_BYTES (n <= 128 / 90 / 90 / 64 for float / double / complex float / complex double) keeps A
+ *       and V in LDS for the whole solve; a larger one is rotated in place in device memory, its V in a scratch array the call
+ *       allocates and frees.  The call is SYNCHRONOUS like bsm_invert_blocks -- it uploads a table of (block, n, ld, w) and
+ *       reads info and sweeps back -- and is not to be graph-captured.  Results are bit-identical from run to run; host and
+ *       device results agree to rounding, not to the bit.
+ *     BSM_MEM_HOST: the same rotations, serially on the host in plain C++, in the block's own type; needs no device (works
+ *       wherever analysis-only handles do); `stream` is ignored.
+ *   Nothing outside the n x n windows and the n entries of w[b] is written.  Every argument is checked before the first byte
+ *   is written.  BSM_ERR_INVALID: what bsm_invert_blocks refuses, null w, a NULL w[b] with n[b] > 0. */
+#define BSM_EIGH_LDS_BYTES 131072 /* A and V of a resident block; the staging arrays take less than 8 KiB more */
+#define BSM_EIGH_MAX_N 512
+#define BSM_EIGH_MAX_SWEEPS 60
+int bsm_eigh_blocks(int dtype, int64_t nblocks, void *const *blocks, const int64_t *n, const int64_t *ld,
+                    void *const *w, int32_t vectors, int64_t *info, int32_t *sweeps, int memspace, void *stream);
+
+/* out_b = V_b diag(f(w_b)) V_b^H from the eigenpairs of bsm_eigh_blocks (any V and real w are taken: V need not be orthogonal):
+ *   out[i, j] = sum_k f_k V[i, k] conj(V[j, k]),   the sum over k ascending with fused multiply-adds (t = f_k V[i, k] rounded,
+ * then acc += t conj(V[j, k])), computed for i >= j and mirrored: out is Hermitian TO THE BIT with a real diagonal, and the
+ * same bytes from run to run.  With wmax = the largest |w_k| over the finite w_k of the block and bound = rcond * wmax (0 when
+ * rcond == 0), f_k is
+ *   BSM_SPEC_VALUES  w_k -- the caller has applied its function already;
+ *   BSM_SPEC_INV     1 / w_k;
+ *   BSM_SPEC_ABSINV  1 / max(|w_k|, bound) -- always positive: with rcond > 0 the result is Hermitian positive definite;
+ *   BSM_SPEC_PINV    1 / w_k where |w_k| > bound, else 0 -- the Hermitian pseudo-inverse.
+ * info[b] (may be NULL) = 0, or the 1-based index of the first eigenvalue at which f is undefined -- BSM_SPEC_INV: w_k zero or
+ * not finite; BSM_SPEC_ABSINV: w_k not finite, or max(|w_k|, bound) zero; BSM_SPEC_PINV: w_k not finite --: out[b] is then not
+ * written, the other blocks are unaffected and the call still returns BSM_OK.
+ *   V, n, ldv, w, out, ldo, info are HOST arrays; V[b] and out[b] are column-major with ldv[b], ldo[b] >= max(n[b], 1), w[b]
+ * holds n[b] reals, all in `memspace`.  out must overlap neither V nor w (the caller's contract, as in bsm_invert_blocks).
+ * Device: one workgroup per block, largest first, V staged in LDS when n * n * sizeof(T) <= BSM_EIGH_LDS_BYTES and read from
+ * device memory otherwise; orders, the synchronous contract and the plain C++ host route are those of bsm_eigh_blocks.
+ * Nothing outside the n x n windows of out is written.  BSM_ERR_INVALID: a negative or NaN rcond, an unknown func, null
+ * arrays, and what bsm_eigh_blocks refuses; n[b] > BSM_EIGH_MAX_N: BSM_ERR_UNSUPPORTED. */
+enum { BSM_SPEC_VALUES = 0, BSM_SPEC_INV = 1, BSM_SPEC_ABSINV = 2, BSM_SPEC_PINV = 3 };
+int bsm_spectral_blocks(int dtype, int64_t nblocks, const void *const *V, const int64_t *n, const int64_t *ldv,
+                        const void *const *w, int32_t func, double rcond, void *const *out, const int64_t *ldo,
+                        int64_t *info, int memspace, void *stream);
+
 /* ---- Krylov building block and solver: restarted GMRES wholly on the device ----------------------------------------
  * What consumes a preconditioner handle M (block_jacobi: bsm_submatrices + bsm_invert_blocks + a BlockSparseMatrix
  * handle): A x = b for the non-symmetric and complex operators the reference exists for, without a Krylov loop in the

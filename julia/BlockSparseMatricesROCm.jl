@@ -569,18 +569,79 @@ function invert_blocks!(blocks::AbstractVector{Matrix{T}}) where {T<:ROCmEltype}
 end
 
 """
-    block_jacobi(A, sets=A.diagonalindices; scheduler=ROCmScheduler())
+    eigh_blocks!(blocks; vectors=true) -> (w, info)
+
+Eigendecomposition of the square Hermitian matrices of `blocks` in place (bsm_eigh_blocks: two-sided round-robin Jacobi in
+the blocks' own type, orders 0 .. 512).  `w[b]` holds the eigenvalues of `(B + B') / 2` ascending, block `b` its orthonormal
+eigenvectors as columns (`vectors=false`: unspecified contents).  `info[b]`: 0 done, 1 a non-finite entry (the block is
+untouched, `w[b]` is NaN), 2 the cap of 60 sweeps was hit.  Host matrices run the rotations on the host.
+"""
+function eigh_blocks!(blocks::AbstractVector{Matrix{T}}; vectors::Bool=true) where {T<:ROCmEltype}
+    all(b -> size(b, 1) == size(b, 2), blocks) || throw(DimensionMismatch("eigh_blocks! takes square blocks"))
+    n = Int64[size(b, 1) for b in blocks]
+    w = [Vector{real(T)}(undef, k) for k in n]
+    info = zeros(Int64, length(blocks))
+    GC.@preserve blocks w _check(ccall((:bsm_eigh_blocks, libbsm), Cint,
+        (Cint, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Cvoid}}, Int32, Ptr{Int64}, Ptr{Int32}, Cint, Ptr{Cvoid}),
+        _DTYPE[T], length(blocks), Ptr{Cvoid}[pointer(b) for b in blocks], n, max.(n, 1), Ptr{Cvoid}[pointer(x) for x in w],
+        vectors ? 1 : 0, info, C_NULL, 0, C_NULL))
+    return w, info
+end
+
+const _SPEC_FUNC = Dict(:values => 0, :inv => 1, :absinv => 2, :pinv => 3)
+
+"""
+    spectral_blocks!(out, V, w; func=:inv, rcond=0.0) -> info
+
+`out[b] = V[b] * Diagonal(f.(w[b])) * V[b]'` (bsm_spectral_blocks), Hermitian to the bit.  `func`: `:values` (f = w), `:inv`
+(1 / w), `:absinv` (1 / max(|w|, rcond * max|w|): positive definite) or `:pinv` (1 / w where |w| > rcond * max|w|, else 0).
+`info[b]` is 0, or the index of the first eigenvalue at which `f` is undefined (`out[b]` is then not written).
+"""
+function spectral_blocks!(out::AbstractVector{Matrix{T}}, V::AbstractVector{Matrix{T}}, w::AbstractVector{<:Vector}; func::Symbol=:inv,
+                          rcond::Real=0.0) where {T<:ROCmEltype}
+    n = Int64[size(b, 1) for b in V]
+    all(k -> size(V[k]) == size(out[k]) == (n[k], n[k]) && length(w[k]) == n[k] && eltype(w[k]) == real(T), eachindex(V)) ||
+        throw(DimensionMismatch("spectral_blocks! takes square blocks, outputs of their shapes and real eigenvalue vectors"))
+    info = zeros(Int64, length(V))
+    GC.@preserve out V w _check(ccall((:bsm_spectral_blocks, libbsm), Cint,
+        (Cint, Int64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Ptr{Ptr{Cvoid}}, Int32, Float64, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Int64}, Cint,
+         Ptr{Cvoid}),
+        _DTYPE[T], length(V), Ptr{Cvoid}[pointer(b) for b in V], n, max.(n, 1), Ptr{Cvoid}[pointer(x) for x in w], _SPEC_FUNC[func],
+        Float64(rcond), Ptr{Cvoid}[pointer(b) for b in out], max.(n, 1), info, 0, C_NULL))
+    return info
+end
+
+"""
+    block_jacobi(A, sets=A.diagonalindices; kind=:inverse, rcond=nothing, scheduler=ROCmScheduler())
 
 The block-Jacobi preconditioner `M = sum_s E_s inv(A[I_s, I_s]) E_s'` of a square operator as a `BlockSparseMatrix` on
 the MI355X path: `submatrices(A, sets)`, `invert_blocks!`, and the reference's own constructor.  The sets must be
 pairwise disjoint and free of repeats; rows in no set are zero rows of `M` (pass singleton sets for point-Jacobi
 rows).  Throws `SingularException(s)` for the first set whose block is singular to working precision.
+
+`kind` (with `A[I_s, I_s] = V diag(w) V'`, the blocks taken as Hermitian): `:inverse` as above (`rcond` must be `nothing`);
+`:abs` gives `V diag(1 / |w|) V'`, Hermitian positive definite for an indefinite `A` (`rcond`, default 0, clamps `|w|` at
+`rcond * max|w|`; a zero eigenvalue throws `SingularException(s)`); `:pinv` the Hermitian pseudo-inverse (`rcond` defaults to
+`sqrt(eps)`).  Through `eigh_blocks!` and `spectral_blocks!`.
 """
-function block_jacobi(A::ROCmAnyOp, sets=_base(A).diagonalindices; scheduler::ROCmScheduler=ROCmScheduler())
+function block_jacobi(A::ROCmAnyOp, sets=_base(A).diagonalindices; kind::Symbol=:inverse, rcond=nothing,
+                      scheduler::ROCmScheduler=ROCmScheduler())
     size(A, 1) == size(A, 2) || throw(DimensionMismatch("block_jacobi needs a square operator"))
+    kind in (:inverse, :abs, :pinv) || throw(ArgumentError("kind must be :inverse, :abs or :pinv"))
     I = [collect(Int64, s) for s in sets]
     blocks = submatrices(A, I)
-    info = invert_blocks!(blocks)
+    if kind == :inverse
+        rcond === nothing || throw(ArgumentError("rcond has no meaning with kind = :inverse"))
+        info = invert_blocks!(blocks)
+    else
+        rc = rcond === nothing ? (kind == :abs ? 0.0 : sqrt(eps(real(eltype(_base(A)))))) : Float64(rcond)
+        w, einfo = eigh_blocks!(blocks)
+        s = findfirst(!iszero, einfo)
+        s === nothing || throw(ArgumentError("block_jacobi: A[I, I] of set $s is not finite or did not converge"))
+        out = [similar(b) for b in blocks]
+        info = spectral_blocks!(out, blocks, w; func=(kind == :abs ? :absinv : :pinv), rcond=rc)
+        blocks = out
+    end
     s = findfirst(!iszero, info)
     s === nothing || throw(LinearAlgebra.SingularException(s))
     return BlockSparseMatrix(blocks, I, I, size(A); scheduler=scheduler)
