@@ -18,5 +18,6 @@ from .solvers import (PolynomialPreconditioner, chebyshev, chebyshev_coefficient
 from .solvers import Eigsh, EigshInfo, eigsh, krylov_combine, krylov_combine_tile  # noqa: F401
 from .solvers import (Lobpcg, LobpcgInfo, lobpcg, block_gram, block_gram_grid, block_gram_work, block_combine,  # noqa: F401
                       block_combine_tile)
+from .solvers import Svds, SvdsInfo, svds  # noqa: F401
 
 __all__ = matrices.__all__ + entries.__all__ + solvers.__all__ + ["synthetic"]

@@ -28,6 +28,7 @@ BSM_CG_MAX_RHS = 16  # bsm_cg_create's nrhs_max (include/bsm_rocm.h)
 BSM_CG_METHOD_CG, BSM_CG_METHOD_COCG = 0, 1
 BSM_POLY_MAX_STEPS = 64  # bsm_poly_create's steps (include/bsm_rocm.h)
 BSM_EIGSH_LA, BSM_EIGSH_SA, BSM_EIGSH_BE, BSM_EIGSH_LM = 0, 1, 2, 3  # bsm_eigsh_params.which (include/bsm_rocm.h)
+BSM_SVDS_LM, BSM_SVDS_SM = 0, 1  # bsm_svds_params.which (include/bsm_rocm.h)
 (BSM_BK_VBCRS_PERM, BSM_BK_VBCRS_ROWPTR, BSM_BK_VBCRS_COLINDICES, BSM_BK_VBCRS_ROWINDICES,
  BSM_BK_COLORS, BSM_BK_TRANSPOSECOLORS, BSM_BK_DIAGONALCOLORS) = range(7)
 
@@ -98,6 +99,20 @@ class BsmEigshPair(C.Structure):
     _fields_ = [("value", C.c_double), ("estimate", C.c_double), ("residual", C.c_double)]
 
 
+class BsmSvdsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
+                ("maxcycles", C.c_int32), ("vectors", C.c_int32)]
+
+
+class BsmSvdsInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("nconv", C.c_int32), ("cycles", C.c_int32), ("reserved", C.c_int32),
+                ("a_products", C.c_int64), ("anorm", C.c_double), ("workspace_bytes", C.c_int64), ("workspace", C.c_uint64)]
+
+
+class BsmSvdsTriplet(C.Structure):
+    _fields_ = [("value", C.c_double), ("estimate", C.c_double), ("residual_av", C.c_double), ("residual_ahu", C.c_double)]
+
+
 class BsmLobpcgParams(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("which", C.c_int32), ("rtol", C.c_double), ("atol", C.c_double),
                 ("maxiter", C.c_int32), ("reserved", C.c_int32)]
@@ -132,7 +147,8 @@ EXPORTS = ["bsm_options_default", "bsm_vbcrs_create", "bsm_vbcrs_create_from_sym
            "bsm_minres_create", "bsm_minres_solve", "bsm_minres_destroy", "bsm_lsqr_create", "bsm_lsqr_solve", "bsm_lsqr_destroy",
            "bsm_poly_create", "bsm_poly_info", "bsm_krylov_combine_tile", "bsm_krylov_combine", "bsm_eigsh_create",
            "bsm_eigsh_solve", "bsm_eigsh_destroy", "bsm_block_gram_grid", "bsm_block_gram_work", "bsm_block_gram",
-           "bsm_block_combine_tile", "bsm_block_combine", "bsm_lobpcg_create", "bsm_lobpcg_solve", "bsm_lobpcg_destroy"]
+           "bsm_block_combine_tile", "bsm_block_combine", "bsm_lobpcg_create", "bsm_lobpcg_solve", "bsm_lobpcg_destroy",
+           "bsm_svds_create", "bsm_svds_solve", "bsm_svds_destroy"]
 
 
 # include/bsm_synth.h (bench / test utility: synthetic operators generated in HBM)
@@ -316,6 +332,13 @@ def lib():
                                        C.c_void_p]
         L.bsm_lobpcg_destroy.argtypes = [C.c_void_p]
         for name in ("bsm_block_gram", "bsm_block_combine", "bsm_lobpcg_create", "bsm_lobpcg_solve", "bsm_lobpcg_destroy"):
+            getattr(L, name).restype = C.c_int
+    if hasattr(L, "bsm_svds_create") or "BSM_LIB" not in os.environ:  # (developer A/B builds may predate them)
+        L.bsm_svds_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bsm_svds_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(BsmSvdsParams),
+                                     C.POINTER(BsmSvdsInfo), C.POINTER(BsmSvdsTriplet), C.c_int, C.c_void_p]
+        L.bsm_svds_destroy.argtypes = [C.c_void_p]
+        for name in ("bsm_svds_create", "bsm_svds_solve", "bsm_svds_destroy"):
             getattr(L, name).restype = C.c_int
     L.bsm_destroy.argtypes = [C.c_void_p]
     L.bsm_last_error.restype = C.c_char_p

@@ -973,6 +973,110 @@ def eigsh(A, nev=6, ncv=None, which="LA", dtype=None, **kw):
     return Eigsh(A, nev=nev, ncv=ncv, which=which, dtype=dtype).solve(**kw)
 
 
+# ---- largest / smallest singular triplets of rectangular operators on the device (bsm_svds_*) --------------------------------
+# (Svds, SvdsInfo and svds are exported by the package by name, like Eigsh)
+_SVDS_WHICH = {"LM": L.BSM_SVDS_LM, "SM": L.BSM_SVDS_SM}
+
+
+class SvdsInfo:
+    """What a solve reports (bsm_svds_info and the bsm_svds_triplet entries): status (0 converged, 1 maxcycles reached, 2 a
+    non-finite norm or value or the sweep cap of the small SVD, 3 the space ended before nsv triplets existed), nconv, cycles,
+    a_products (2 x steps + 2 x residual columns), anorm (the largest sigma seen: a lower bound of ||A||_2), workspace_bytes,
+    workspace; per triplet, as numpy arrays of nconv entries: value, estimate (|beta_m X[m - 1, i]|), residual_av (the true
+    ||A v - sigma u||) and residual_ahu (||A^H u - sigma v||); with vectors=False the estimate stands for the one that belongs
+    to the short side's product, zero for the other."""
+
+    def __init__(self, info, triplets):
+        for name, _ in L.BsmSvdsInfo._fields_:
+            if name != "reserved":
+                setattr(self, name, getattr(info, name))
+        k = self.nconv
+        for f in ("value", "estimate", "residual_av", "residual_ahu"):
+            setattr(self, f, np.array([getattr(triplets[i], f) for i in range(k)], dtype=np.float64))
+
+    @property
+    def converged(self):
+        return self.status == 0
+
+    def __repr__(self):
+        return (f"SvdsInfo(status={self.status}, nconv={self.nconv}, cycles={self.cycles}, a_products={self.a_products}, "
+                f"anorm={self.anorm:.3e})")
+
+
+class Svds:
+    """The `nsv` largest ("LM") or smallest ("SM") singular triplets of a rectangular or nonsymmetric A (m x n) by thick-restart
+    Golub-Kahan-Lanczos bidiagonalisation with full two-sided reorthogonalisation, the bases, both products, the
+    orthogonalisation, the restart and the true residuals on the device (bsm_svds_*).  A: a block matrix or transpose(A) /
+    adjoint(A) (transpose of a complex A is refused: it would need conj(A)), single-device with a device image.  ncv: columns of
+    the bases, nsv + 2 .. min(m, n, 128); default min(m, n, 128, max(2 nsv + 1, 20)).  dtype: A's own vector type (a mixed-storage
+    A solves in double).  The workspace (2 ncv + 1 + 2 min(nsv, 16) vectors) is allocated here, once; A is kept alive and
+    update_blocks(A, ...) is seen by the next solve.  One product per step is a transposed one: two solves give the same bytes
+    only on handles whose transposed product is reproducible (transpose_image=True on a conflict-free operator, gather,
+    coloured).  NOT in it: one-sided reorthogonalisation, harmonic / refined Ritz values or shift-invert for interior and tiny
+    values, a block method, multi-device and own-range handles, graph capture."""
+
+    def __init__(self, A, nsv=6, ncv=None, which="LM", dtype=None):
+        base, op = _operator(A)
+        self.dtype = np.dtype(base.dtype if dtype is None else dtype)
+        if self.dtype not in _DT:
+            raise TypeError(f"dtype={self.dtype} is not a supported vector type")
+        if which not in _SVDS_WHICH:
+            raise ValueError(f"which={which!r}: 'LM' or 'SM'")
+        m, n = size(A)
+        self.nsv = int(nsv)
+        self.ncv = min(m, n, L.BSM_GMRES_MAX_RESTART, max(2 * self.nsv + 1, 20)) if ncv is None else int(ncv)
+        self.which, self.A, self.m, self.n, self._base = which, A, m, n, base
+        ptr = C.c_void_p()
+        L.check(L.lib().bsm_svds_create(base._h.ptr, op, _DT[self.dtype], self.nsv, self.ncv, C.byref(ptr)))
+        self._ptr = ptr
+
+    def __del__(self):
+        try:
+            if self._ptr:
+                L.lib().bsm_svds_destroy(self._ptr)
+                self._ptr = None
+        except Exception:
+            pass
+
+    def solve(self, v0=None, rtol=1e-10, atol=0.0, maxcycles=300, vectors=True, stream=None, seed=0, *, U=None, V=None):
+        """-> (s, U, V, SvdsInfo).  v0: the start vector, min(m, n) entries -- torch CUDA tensor (the solve is enqueued on
+        `stream`, default torch's current stream) or numpy array (staged); None: uniform in (-1, 1) from numpy's
+        default_rng(seed), on A's device.  U (m x nsv), V (n x nsv): where the singular vectors go (column-major, like v0;
+        None: new); with vectors=False they are not touched and (s, None, None, info) comes back.  s: the info.nconv singular
+        values in the order of `which` (numpy); U[:, :nconv], V[:, :nconv] their vectors, orthonormal, A V = U diag(s).
+        Converged when every wanted triplet's estimate is <= max(rtol * anorm, atol).  Synchronous."""
+        short = min(self.m, self.n)
+        if v0 is None:
+            v0 = np.random.default_rng(seed).uniform(-1, 1, short)
+            if self.dtype.kind == "c":
+                v0 = v0 + 0j
+            v0 = torch.from_numpy(v0.astype(self.dtype)).to(torch.device("cuda", self._base.device))
+        vp, _, _, ms, _, _ = _describe(v0, self.dtype, short, "v0", self._base)
+        up, ldu, wp, ldv = None, max(self.m, 1), None, max(self.n, 1)
+        if vectors:
+            U = _like(v0, self.m, self.nsv) if U is None else U
+            V = _like(v0, self.n, self.nsv) if V is None else V
+            up, ldu, ku, ums, _, _ = _describe(U, self.dtype, self.m, "U", self._base, True)
+            wp, ldv, kv, vms, _, _ = _describe(V, self.dtype, self.n, "V", self._base, True)
+            if ku != self.nsv or kv != self.nsv:
+                raise ValueError(f"DimensionMismatch: U, V have {ku}, {kv} columns, expected nsv = {self.nsv}")
+            if ums != ms or vms != ms:
+                raise ValueError("v0, U and V must live in the same memory space")
+        st = _stream_ptr(stream, v0.device) if ms == L.BSM_MEM_DEVICE else None
+        p = L.BsmSvdsParams(C.sizeof(L.BsmSvdsParams), _SVDS_WHICH[self.which], float(rtol), float(atol), int(maxcycles),
+                            1 if vectors else 0)
+        info = L.BsmSvdsInfo()
+        trip = (L.BsmSvdsTriplet * self.nsv)()
+        L.check(L.lib().bsm_svds_solve(self._ptr, vp, up, ldu, wp, ldv, C.byref(p), C.byref(info), trip, ms, st))
+        out = SvdsInfo(info, trip)
+        return out.value.copy(), (U if vectors else None), (V if vectors else None), out
+
+
+def svds(A, nsv=6, ncv=None, which="LM", dtype=None, **kw):
+    """One-shot form: Svds(A, nsv, ncv, which, dtype).solve(**kw) -> (s, U, V, SvdsInfo)."""
+    return Svds(A, nsv=nsv, ncv=ncv, which=which, dtype=dtype).solve(**kw)
+
+
 # ---- LOBPCG on the device (bsm_lobpcg_*) and the two tall-skinny products of a block method ---------------------------------
 # (Lobpcg, LobpcgInfo, lobpcg, block_gram and block_combine are exported by the package by name, like Eigsh)
 def _wide(dt):

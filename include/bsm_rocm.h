@@ -1186,7 +1186,7 @@ int bsm_krylov_combine(int dtype, int64_t n, int64_t m, int64_t k, const void *V
  *   Run to run, value, X, cycles and the residuals are bit-identical wherever the product of the handle is (the forward
  *   product of a conflict-free or gather / coloured operator; see bsm_lsqr above for the transposed product).
  * Not in it: interior eigenvalues / shift-invert, the generalised problem or a preconditioner, multiplicities (a single-vector
- *   Krylov space sees one vector of an eigenspace), singular values, block Lanczos / LOBPCG, locking beyond what the thick
+ *   Krylov space sees one vector of an eigenspace), singular values (bsm_svds below), block Lanczos / LOBPCG, locking beyond what the thick
  *   restart keeps. */
 typedef enum { BSM_EIGSH_LA = 0, BSM_EIGSH_SA = 1, BSM_EIGSH_BE = 2, BSM_EIGSH_LM = 3 } bsm_eigsh_which;
 typedef struct {
@@ -1215,6 +1215,102 @@ int bsm_eigsh_create(bsm_matrix_t A, int opA, int vdtype, int32_t nev, int32_t n
 int bsm_eigsh_solve(struct bsm_eigsh_s *S, const void *v0, void *X /* may be NULL with vectors = 0 */, int64_t ldx,
                     const bsm_eigsh_params *p, bsm_eigsh_info *info, bsm_eigsh_pair *pairs /* nev */, int memspace, void *stream);
 int bsm_eigsh_destroy(struct bsm_eigsh_s *S);
+
+/* bsm_svds_*: the `nsv` LARGEST or SMALLEST SINGULAR TRIPLETS (sigma_i, u_i, v_i), op(A) v_i = sigma_i u_i, op(A)^H u_i = sigma_i v_i,
+ * of a rectangular or nonsymmetric op(A) (m x n), by thick-restart Golub-Kahan-Lanczos bidiagonalisation with full two-sided
+ * reorthogonalisation (Baglama and Reichel; what KrylovKit's svdsolve runs on a LinearMap), the bases, the products, the
+ * orthogonalisation, the restart and the true residuals on the device.  The two-sided sibling of bsm_eigsh, and the first
+ * eigen-type solver that uses the transposed half of the engine: ||A||_2, sigma_min, the 2-norm condition number, a leading
+ * or trailing singular subspace.  (No counterpart in the reference: its operators are LinearMaps handed to KrylovKit.)
+ *   Recurrence.  It always starts in the SHORT space: with l = max(m, n), s = min(m, n) it runs on B = op(A) if m >= n and on
+ *   B = op(A)^H otherwise, U and V exchanged on the way out.  (Started in the long space of a 400 x 600 operator it never converges
+ *   for the smallest values: it sees the 200-dimensional null space.)  P (s x (ncv + 1)) holds the right vectors of B, Q (l x
+ *   ncv) the left ones; p_0 = v0 / ||v0||, v0 of s entries.  Step j of a cycle (j = start .. ncv - 1; start = 0 in the first
+ *   cycle, `keep` after a restart):
+ *       q = B p_j                          one bsm_mul, written straight into Q[:, j]
+ *       h = Q[:, 0:j]^H q;  q -= Q[:, 0:j] h          TWICE (the fused pass of bsm_krylov_orth)
+ *       alpha_j = ||q||;  q_j = q / alpha_j          (alpha_j zero or not finite: q_j = 0, nothing divided)
+ *       r = B^H q_j                        one bsm_mul, written straight into P[:, j + 1]
+ *       h = P[:, 0:j+1]^H r;  r -= P[:, 0:j+1] h      TWICE
+ *       beta_j = ||r||;  p_{j+1} = r / beta_j        (the same guard)
+ *   No host read happens inside a cycle; it ends with ONE device-to-host copy (the alpha, the beta, ||v0||) and one
+ *   synchronisation.  The host keeps the real upper-triangular projected matrix Bp (ncv x ncv, double), B P = Q Bp: alpha_j on
+ *   the diagonal, beta_j beside it (row j, column j + 1); after a restart its leading keep x keep part is diag(sigma kept) and
+ *   column keep holds the arrow rho_i = beta_m X[m - 1, i] (taken analytically, m = ncv).  Bp Y = X diag(sigma) by a one-sided
+ *   (Hestenes) Jacobi method in double with a fixed sweep order (csrc/bsm_svds.h): a column pair is skipped when its inner
+ *   product is within sqrt(ncv) eps of the product of its norms, at most 60 sweeps, sigma descending, deterministic; a column of
+ *   Bp Y that is zero to ncv eps sigma_max gets its X column completed by Gram-Schmidt from the unit vectors in index order.  The
+ *   columns of X and Y that go to the device are made orthonormal to working precision on the host first, by two modified
+ *   Gram-Schmidt passes in the order of the selection.
+ *   Selection (`which`): BSM_SVDS_LM the largest, largest first; BSM_SVDS_SM the smallest, smallest first.
+ *   Estimate and tolerance.  The estimate of triplet i is |beta_m X[m - 1, i]| = ||B^H u_i - sigma_i v_i|| in exact arithmetic (B
+ *   v_i = sigma_i u_i holds by construction).  anorm = the largest sigma seen in the solve, a lower bound of ||op(A)||_2.
+ *   Converged: every wanted triplet has estimate <= max(rtol anorm, atol).
+ *   Restart.  keep = min(ncv - 1, nsv + (ncv - nsv) / 2), selected by the same rule as the wanted ones; P[:, 0:keep] = P[:, 0:ncv]
+ *   Y[:, kept] IN PLACE with p_m carried to column keep, Q[:, 0:keep] = Q X[:, kept] in place with no carry: two
+ *   bsm_krylov_combine launches.  The bases are never duplicated.
+ *   End.  V and U leave through the same kernel into the caller's matrices, every column scaled to norm one, then the TRUE
+ *   residuals r_av = ||op(A) v_i - sigma_i u_i|| and r_ahu = ||op(A)^H u_i - sigma_i v_i||: two bsm_mul_multi per batch of at most
+ *   16 columns, ONE launch pair per batch that leaves one partial per workgroup and column for both residuals, over the m-row
+ *   grid and the n-row grid, and adds them in a fixed order, one wave per column.  No floating-point atomic in the unit's own
+ *   kernels, nobody waits.
+ * create: vdtype must be the handle's own vector type (a mixed-storage handle solves in double).  1 <= nsv, nsv + 2 <= ncv <=
+ *   min(m, n, BSM_GMRES_MAX_RESTART).  ONE device allocation, reported in info: P (ncv + 1 columns of s rows), Q (ncv columns of l
+ *   rows), two residual blocks of min(nsv, 16) columns, one on each grid, and the small arrays; leading dimensions rounded up to
+ *   whole 16-byte groups.  Refused, before anything is allocated: what bsm_eigsh_create refuses except a non-square op(A); opA =
+ *   BSM_OP_T on a complex handle (BSM_ERR_UNSUPPORTED: op(A)^H would be conj(A), as in bsm_lsqr_create).  The handle must
+ *   outlive the solver; it holds the HANDLE, not values: the next solve sees a bsm_update_blocks.
+ * solve: v0 (min(m, n) entries), U (m x nsv, ldu >= max(m, 1)), V (n x nsv, ldv >= max(n, 1)), column-major, any element
+ *   alignment; BSM_MEM_HOST operands are staged through device buffers the solver keeps.  triplets: nsv entries.  Synchronous.
+ *   info.status:  0 converged;  1 maxcycles reached (all nsv triplets are returned as they stand, nconv = nsv);  2 a norm or a
+ *   singular value is not finite, or the Jacobi method hit its sweep cap (nconv = 0, U and V are not written);  3 the space
+ *   ended before nsv triplets existed: a beta_j -- or an alpha_j, which gives q_j = 0 and beta_j = 0 with it -- was exactly zero
+ *   with j + 1 < nsv (nconv = j + 1 triplets of that invariant pair of subspaces, exact; a zero v0 gives nconv = 0).  A space that
+ *   ends with j + 1 >= nsv is convergence.  A triplet whose alpha_j was exactly zero has sigma = 0 and the ZERO vector on the long
+ *   side (the recurrence offers no left null vector; both residuals are zero all the same).  Where that alpha_j is rounding
+ *   noise instead of zero -- a singular SQUARE operator whose space is exhausted, ncv = n -- u_i is a unit vector of noise: the
+ *   estimate is tiny, and residual_ahu, the TRUE one, is what shows it.
+ *   triplets[i], i < nconv, in the order of `which`: value, estimate, residual_av, residual_ahu (the true ones; with vectors = 0
+ *   neither U, V nor the residual pass is produced, and the estimate stands for the residual of the product with B^H, zero for
+ *   the other one).  Entries i >= nconv are NaN; columns i >= nconv of U and V are untouched.  U and V are orthonormal to
+ *   working precision.  a_products = 2 * steps + 2 * nconv, steps = ncv + (cycles - 1)(ncv - keep); with vectors = 0: 2 * steps.
+ *   Refused (BSM_ERR_INVALID): null S, p, info, triplets, v0; a struct_size mismatch; a bad memspace or which; rtol or atol
+ *   negative or NaN; maxcycles < 1; with vectors: null U or V, ldu < max(m, 1), ldv < max(n, 1), U or V overlapping v0 or each
+ *   other; a stream that is being captured.
+ *   Run to run.  One product per step is a transposed one: sigma, U, V, cycles and the residuals are bit-identical only where
+ *   BOTH products of the handle are -- a handle created with transpose_image = 1 on a conflict-free operator, or a gather /
+ *   coloured one (see bsm_lsqr above); elsewhere the last bits may differ and a cycle count may move by one.
+ * NOT in it: one-sided reorthogonalisation; harmonic / refined Ritz values or shift-invert for interior and tiny values (the
+ *   smallest values converge as the extreme Ritz values of the bidiagonalisation do); a block method; multi-device and own-range
+ *   handles; graph capture. */
+typedef enum { BSM_SVDS_LM = 0, BSM_SVDS_SM = 1 } bsm_svds_which;
+typedef struct {
+    int32_t struct_size; /* = sizeof(bsm_svds_params) */
+    int32_t which;       /* bsm_svds_which */
+    double rtol, atol;   /* estimate <= max(rtol anorm, atol) */
+    int32_t maxcycles;
+    int32_t vectors;     /* 0: values and estimates only */
+} bsm_svds_params;
+typedef struct {
+    int32_t status, nconv, cycles, reserved;
+    int64_t a_products;
+    double anorm;
+    int64_t workspace_bytes;
+    uint64_t workspace; /* device address of the allocation */
+} bsm_svds_info;
+typedef struct {
+    double value, estimate, residual_av, residual_ahu;
+} bsm_svds_triplet;
+BSM_LAYOUT_ASSERT(sizeof(bsm_svds_params) == 32 && offsetof(bsm_svds_params, rtol) == 8 && offsetof(bsm_svds_params, maxcycles) == 24,
+                  "bsm_svds_params layout");
+BSM_LAYOUT_ASSERT(sizeof(bsm_svds_info) == 48 && offsetof(bsm_svds_info, a_products) == 16 && sizeof(bsm_svds_triplet) == 32,
+                  "bsm_svds_info layout");
+struct bsm_svds_s;
+int bsm_svds_create(bsm_matrix_t A, int opA, int vdtype, int32_t nsv, int32_t ncv, struct bsm_svds_s **out);
+int bsm_svds_solve(struct bsm_svds_s *S, const void *v0 /* min(m, n) */, void *U /* may be NULL with vectors = 0 */, int64_t ldu,
+                   void *V /* may be NULL with vectors = 0 */, int64_t ldv, const bsm_svds_params *p, bsm_svds_info *info,
+                   bsm_svds_triplet *triplets /* nsv */, int memspace, void *stream);
+int bsm_svds_destroy(struct bsm_svds_s *S);
 
 /* bsm_block_gram, bsm_block_combine: the two tall-skinny products of a caller's BLOCK method, beside bsm_krylov_orth (one w per
  * call) and bsm_krylov_combine (a REAL S).  Both only enqueue on `stream`, synchronise nothing and may be graph-captured.

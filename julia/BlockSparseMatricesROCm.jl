@@ -933,6 +933,61 @@ function eigsh!(X::Matrix{T}, A::ROCmAnyOp, v0::Vector{T}; which::Symbol=:LA,
     return [pairs[i].value for i in 1:info.nconv], X, info, pairs[1:info.nconv]
 end
 
+# ---- largest / smallest singular triplets of rectangular operators (bsm_svds_*) ----
+mutable struct BsmSvdsParams        # mirrors bsm_svds_params (32 bytes)
+    struct_size::Int32; which::Int32; rtol::Float64; atol::Float64; maxcycles::Int32; vectors::Int32
+end
+mutable struct BsmSvdsInfo          # mirrors bsm_svds_info (48 bytes)
+    status::Int32; nconv::Int32; cycles::Int32; reserved::Int32
+    a_products::Int64; anorm::Float64; workspace_bytes::Int64; workspace::UInt64
+end
+struct BsmSvdsTriplet               # mirrors bsm_svds_triplet (32 bytes)
+    value::Float64; estimate::Float64; residual_av::Float64; residual_ahu::Float64
+end
+const _SVDS_WHICH = Dict(:LM => 0, :SM => 1)
+
+"""
+    svds!(U, V, A, v0; which=:LM, ncv=min(size(A)..., 128, max(2 nsv + 1, 20)), rtol=1e-10, atol=0.0, maxcycles=300, vectors=true)
+        -> (s, U, V, info, triplets)
+
+`nsv = size(U, 2)` largest (`:LM`) or smallest (`:SM`) singular triplets of a rectangular or nonsymmetric `A` (`m x n`) by
+thick-restart Golub-Kahan-Lanczos bidiagonalisation with full two-sided reorthogonalisation (what KrylovKit's `svdsolve`
+runs), the bases, both products, the orthogonalisation, the restart and the true residuals on the device (bsm_svds_create /
+_solve / _destroy).  `U` (`m x nsv`), `V` (`n x nsv`) and `v0` (`min(m, n)` entries: the recurrence starts in the short space)
+are host arrays of `A`'s element type; `nsv + 2 <= ncv <= min(m, n, 128)`.  `transpose(A)` of a complex `A` is refused (it
+would need `conj(A)`).  Converged when every wanted triplet's estimate `|beta_m X[m, i]|` is `<= max(rtol * anorm, atol)`,
+`anorm` being the largest `sigma` seen.  `info.status`: 0 converged, 1 `maxcycles` reached, 2 a non-finite norm or value or
+the sweep cap of the small SVD, 3 the space ended before `nsv` triplets existed.  `s` holds the `info.nconv` values in the
+order of `which`, `U[:, 1:nconv]`, `V[:, 1:nconv]` their orthonormal vectors, `triplets[i]` value, estimate and the true
+residuals `||A v - sigma u||`, `||A' u - sigma v||`.  One product per step is a transposed one: two runs give the same bits only
+on handles whose transposed product is reproducible (`transpose_image`).  NOT in it: one-sided reorthogonalisation, harmonic /
+refined Ritz values or shift-invert for interior and tiny values, a block method, multi-device and own-range handles, graph
+capture.
+"""
+function svds!(U::Matrix{T}, V::Matrix{T}, A::ROCmAnyOp, v0::Vector{T}; which::Symbol=:LM,
+               ncv::Integer=min(size(A, 1), size(A, 2), 128, max(2 * size(U, 2) + 1, 20)), rtol::Real=1e-10, atol::Real=0.0,
+               maxcycles::Integer=300, vectors::Bool=true) where {T<:ROCmEltype}
+    m, n, nsv = size(A, 1), size(A, 2), size(U, 2)
+    (size(U, 1) == m && size(V, 1) == n && size(V, 2) == nsv && length(v0) == min(m, n)) ||
+        throw(DimensionMismatch("svds! needs U (m x nsv), V (n x nsv) and v0 of min(m, n) entries"))
+    haskey(_SVDS_WHICH, which) || throw(ArgumentError("which must be :LM or :SM"))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:bsm_svds_create, libbsm), Cint, (Ptr{Cvoid}, Cint, Cint, Int32, Int32, Ref{Ptr{Cvoid}}),
+        handle(_base(A)).ptr, _op(A), _DTYPE[T], nsv, ncv, out))
+    p = BsmSvdsParams(sizeof(BsmSvdsParams), _SVDS_WHICH[which], rtol, atol, maxcycles, vectors)
+    info = BsmSvdsInfo(0, 0, 0, 0, 0, 0.0, 0, 0)
+    triplets = Vector{BsmSvdsTriplet}(undef, nsv)
+    try
+        GC.@preserve A U V v0 triplets _check(ccall((:bsm_svds_solve, libbsm), Cint,
+            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ref{BsmSvdsParams}, Ref{BsmSvdsInfo}, Ptr{BsmSvdsTriplet}, Cint,
+             Ptr{Cvoid}),
+            out[], pointer(v0), pointer(U), max(m, 1), pointer(V), max(n, 1), p, info, triplets, 0, C_NULL))
+    finally
+        ccall((:bsm_svds_destroy, libbsm), Cint, (Ptr{Cvoid},), out[])
+    end
+    return [triplets[i].value for i in 1:info.nconv], U, V, info, triplets[1:info.nconv]
+end
+
 """
     krylov_combine!(Out, V, S, T, n, m, k; ldv=max(n, 1), lds=m, ldo=max(n, 1), carry=-1, stream=C_NULL)
 
